@@ -19,6 +19,8 @@
     engine, one launch per step, a host sync after every step (rounds 1-2).
 Metric = aligned audio frames per second, whole job (all ranks); no data-path collective.  N>1 without a launcher
 starts one rank per GPU itself (a child process running torch.distributed.run, before anything touches the GPU).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed its caller as DIR/<name>.npy
+    (dump_outputs below); the inputs depend on the arguments only, so two builds can be compared output for output.
 
 Prints ONE JSON line (rank 0).
 """
@@ -393,6 +395,52 @@ def pipeline_entry():
     return out
 
 
+DUMP_BYTES = 64 * 10**6   # --dump-outputs: all files together stay below this
+DUMP_SEED = 20261015      # which lattices' per-frame outputs are written: a fixed sample
+
+
+def dump_outputs(out_dir, batches):
+    """--dump-outputs: the outputs of the timed path's last step, as a caller of DeviceBatch receives them.
+    Per lattice, all of this rank's lattices in input order: total (score of the best path) and status.  Per frame, for a
+    fixed seeded sample of the lattices that fits in DUMP_BYTES: path and best_labels (float64, exact) and best_scores
+    (float32), each the sampled lattices' arrays one after the other; lattice and frames name them and give their lengths."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    path = [p for b in batches for p in b.path]
+    best_labels = [x for b in batches for x in b.best_labels]
+    best_scores = [x for b in batches for x in b.best_scores]
+    n = len(path)
+    budget = DUMP_BYTES - 16 * n - 7 * 4096          # the per-lattice arrays and the .npy headers
+    pick = []
+    for i in np.random.default_rng(DUMP_SEED).permutation(n).tolist():
+        cost = 20 * int(path[i].shape[0])             # 8 + 8 + 4 bytes per frame
+        if cost > budget:
+            break
+        budget -= cost
+        pick.append(i)
+    pick.sort()
+
+    def frames(xs, dtype):
+        if not pick:
+            return np.zeros(0, np.float64 if dtype == torch.float64 else np.float32)
+        return torch.cat([xs[i].to(dtype) for i in pick]).cpu().numpy()
+
+    arrays = {
+        "total": np.concatenate([np.asarray(b.total, np.float32) for b in batches]),
+        "status": np.concatenate([np.asarray(b.status) for b in batches]).astype(np.float64),
+        "lattice": np.asarray(pick, np.float64),
+        "frames": np.asarray([int(path[i].shape[0]) for i in pick], np.float64),
+        "path": frames(path, torch.float64),
+        "best_labels": frames(best_labels, torch.float64),
+        "best_scores": frames(best_scores, torch.float32),
+    }
+    assert sum(a.nbytes for a in arrays.values()) + 4096 * len(arrays) <= DUMP_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def np_bits(x):
     import numpy as np
     return int(np.float32(x).view(np.int32))
@@ -420,7 +468,11 @@ def main():
     ap.add_argument("--cpu-baseline-seconds", type=float, default=8.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true", help="skip the single-lattice / book / corpus entries")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) to DIR/<name>.npy, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world_env = int(os.environ.get("WORLD_SIZE", "0"))
     if world_env:
@@ -578,6 +630,8 @@ def main():
         for i in range(0, B, max(1, B // 128)):
             ok = ok and np_chain(best_scores[i]) == np_bits(total[i])
         ok = bool(ok)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, batches)
 
     if rank == 0:
         value = frames_per_step * args.steps / elapsed
