@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define KA_VERSION 100 /* 0.1.0 */
+#define KA_VERSION 101 /* 0.1.1: best-path posteriors */
 
 /* status codes (per call and per lattice) */
 #define KA_OK 0
@@ -38,6 +38,9 @@ extern "C" {
 #define KA_ERR_INTERNAL (-8)  /* tiled form: a tile's hand-off timed out (an internal error, never an input condition) */
 #define KA_ERR_NAN (-6)       /* a log-prob is NaN: the reference's np.argmax treats NaN as the maximum (align.py:83); that
                                  is not reproduced - the lattice is rejected (fast path, V <= 64, band <= 1009 or tiled form) */
+
+#define KA_ERR_ZERO_MASS (-9) /* posteriors: no path of finite score reaches the best path's terminal (the lattice
+                                 log-likelihood is -inf; the reference can end its path on a state reached only through -inf) */
 
 /* where the caller's buffers live */
 #define KA_MEM_HOST 0
@@ -113,6 +116,34 @@ int ka_ctc_best_path_batch_enqueue_f32(ka_engine *e, int32_t n, const float *con
                                        int32_t *const *best_path, int32_t *const *best_labels,
                                        float *const *best_scores, void *stream);
 int ka_batch_finish(ka_engine *e, float *total_score, int32_t *status);
+
+/*
+ * Posterior of a best path and the lattice log-likelihood: the forward-backward pass over the same band, moves and veto
+ * as ctc_best_path, with sums where the best path takes maxima.
+ *   alpha_t(s) = logsumexp_j alpha_{t-1}(s-j) + lp[t, lab'[s]],  Z = alpha_{T-1}(s*), s* = best_path[T-1]
+ *   beta_{T-1} = {s*: 0},  beta_t(s) = logsumexp_j beta_{t+1}(s+j) + lp[t+1, lab'[s+j]]
+ *   posteriors[t] = exp(alpha_t(p_t) + beta_t(p_t) - Z), p_t = best_path[t]  (0 where p_t is outside band t)
+ * Arguments as ka_ctc_best_path[_batch]_f32, plus best_path [T] int32 (input: any path, usually that call's output) and
+ *   posteriors      [T] float32 output (where `mem` says)
+ *   log_likelihood  Z in nats, HOST double array [n] (may be NULL): float32 cannot hold it to a useful precision
+ *   status          per lattice, HOST [n] (may be NULL)
+ * Per lattice: KA_ERR_BAD_LABEL, KA_ERR_NAN, KA_ERR_NONFINITE (+inf among the log-probs; -inf is legal), KA_ERR_BAD_ARGS
+ * (a best_path value outside [0, 2S+1)) - posteriors NaN, log-likelihood NaN; KA_ERR_ZERO_MASS - posteriors NaN,
+ * log-likelihood -inf.  The call returns KA_OK or the status of the first lattice that failed.  It uses its own kernels
+ * (ka_engine_set_mode / set_backtrace do not apply) and synchronises `stream` before it returns.
+ */
+int ka_ctc_path_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld,
+                               const int32_t *labels, int64_t S, int32_t beam_size, int32_t max_move,
+                               const int32_t *best_path, float *posteriors, double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_path_posteriors_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                     const int64_t *ld, const int32_t *const *labels, const int64_t *S,
+                                     int32_t beam_size, int32_t max_move, const int32_t *const *best_path,
+                                     float *const *posteriors, double *log_likelihood, int32_t *status, int32_t mem,
+                                     void *stream);
+/* device-workspace bytes such a call carves (0 for unsupported arguments): reserving the larger of this and
+ * ka_engine_workspace_bytes keeps both calls free of allocations */
+size_t ka_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size,
+                                    int32_t max_move, int32_t mem);
 
 /* Kernel form of the fast path.
  *   KA_MODE_WAVE        one wavefront per lattice, checkpointed (throughput; fills the chip from ~4096

@@ -5,7 +5,8 @@ Public surface mirrors the reference (kokoro_align/align.py):
     best_path(input_file, voca_file, output_file)                  align.py:112
     align(best_path_file, mfcc_file, voca_file, align_file, remove_wordsep)   align.py:127
     pandas_read_align(files)                                       align.py:172
-plus batched / device-resident entry points (ctc_best_path_batch, ctc_best_path_device).
+plus batched / device-resident entry points (ctc_best_path_batch, ctc_best_path_device) and the
+forward-backward quality signal of a best path (ctc_path_posteriors[_batch|_device], segment_confidence).
 
 The DP and backtrace run in the HIP C-ABI library (include/kokoro_align_amd.h); there is no
 CPU fallback — importing works without a GPU, computing does not.
@@ -17,8 +18,12 @@ from .align import (  # noqa: F401
     ctc_best_path,
     ctc_best_path_batch,
     ctc_best_path_device,
+    ctc_path_posteriors,
+    ctc_path_posteriors_batch,
+    ctc_path_posteriors_device,
     log_softmax_device,
     pandas_read_align,
+    segment_confidence,
 )
 from ._lib import KAError, build_library, library_path, load_library  # noqa: F401
 

@@ -22,6 +22,7 @@ KA_ERR_NOMEM = -4
 KA_ERR_BAD_LABEL = -5
 KA_ERR_NAN = -6
 KA_ERR_NONFINITE = -7
+KA_ERR_ZERO_MASS = -9
 KA_MEM_HOST = 0
 KA_MEM_DEVICE = 1
 
@@ -36,6 +37,7 @@ EXPORTS = [
     "ka_engine_set_verify", "ka_stream_create", "ka_stream_destroy",
     "ka_debug_set_split", "ka_engine_workspace_bytes", "ka_debug_set_tile_lds",
     "ka_debug_auto_split", "ka_debug_set_rc_gather", "ka_lstm_layer0_f32", "ka_debug_set_tile_width", "ka_debug_tile_width_choice", "ka_debug_plan_tiles_width",
+    "ka_ctc_path_posteriors_f32", "ka_ctc_path_posteriors_batch_f32", "ka_posterior_workspace_bytes",
 ]
 
 
@@ -96,6 +98,12 @@ def load_library():
     L.ka_ctc_best_path_batch_enqueue_f32.argtypes = batch_common + [vp]
     L.ka_batch_finish.restype = ctypes.c_int
     L.ka_batch_finish.argtypes = [vp, vp, vp]
+    L.ka_ctc_path_posteriors_f32.restype = ctypes.c_int
+    L.ka_ctc_path_posteriors_f32.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, vp, vp, vp, i32, vp]
+    L.ka_ctc_path_posteriors_batch_f32.restype = ctypes.c_int
+    L.ka_ctc_path_posteriors_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pp, pp, vp, vp, i32, vp]
+    L.ka_posterior_workspace_bytes.restype = sz
+    L.ka_posterior_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
     L.ka_engine_set_mode.restype = ctypes.c_int
     L.ka_engine_set_mode.argtypes = [vp, i32]
     L.ka_engine_set_backtrace.restype = ctypes.c_int
@@ -176,6 +184,8 @@ def check(rc, what):
     if rc == KA_ERR_NAN:
         raise ValueError(f"{what}: log_probs contain NaN ({msg})")
     if rc == KA_ERR_NONFINITE:
+        raise ValueError(f"{what}: {msg}")
+    if rc == KA_ERR_ZERO_MASS:
         raise ValueError(f"{what}: {msg}")
     if rc == KA_ERR_BAD_ARGS:
         raise ValueError(f"{what}: {msg}")

@@ -237,6 +237,145 @@ def ctc_best_path_device(log_probs, labels, beam_size=1000, max_move=4, verbose=
     return batch.results()
 
 
+# ------------------------------------------------------------------------------------------
+# best-path posteriors and lattice log-likelihood (forward-backward over the same band)
+# ------------------------------------------------------------------------------------------
+_POSTERIOR_LATTICE_STATUSES = (_lib.KA_OK, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_NONFINITE, _lib.KA_ERR_BAD_ARGS,
+                               _lib.KA_ERR_ZERO_MASS)
+
+
+def ctc_path_posteriors(log_probs, labels, best_path, beam_size=1000, max_move=4):
+    """How sure the model is of a best path, frame by frame: (posteriors float32 [T], log_likelihood float).
+
+    posteriors[t] is the probability, over every path of the band of ``ctc_best_path`` that ends where ``best_path`` ends,
+    that frame t sits at ``best_path[t]``; log_likelihood is the log of the total probability of those paths (nats).
+    NumPy in -> NumPy out; ROCm torch tensors are handed to ``ctc_path_posteriors_device``.  Raises IndexError for a label
+    outside [0, V), ValueError for NaN / +inf log-probs, a path value outside [0, 2S+1) or a terminal no finite path reaches.
+    """
+    if _is_tensor(log_probs):
+        (post, ll), = ctc_path_posteriors_device([log_probs], [labels], [best_path], beam_size, max_move)
+        return post, ll
+    (post, ll), = ctc_path_posteriors_batch([log_probs], [labels], [best_path], beam_size, max_move)
+    return post, ll
+
+
+def ctc_path_posteriors_batch(log_probs_list, labels_list, best_path_list, beam_size=1000, max_move=4, device=None,
+                              return_status=False):
+    """Posteriors of many lattices in ONE launch; host NumPy buffers in and out.
+
+    Returns a list of (posteriors, log_likelihood); with ``return_status`` also the per-lattice status list, in which case
+    failures do not raise (their posteriors are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    """
+    n = len(log_probs_list)
+    if n != len(labels_list) or n != len(best_path_list):
+        raise ValueError("log_probs, labels and best paths must be lists of one length")
+    if n == 0:
+        return ([], []) if return_status else []
+    lps = [np.ascontiguousarray(x, dtype=np.float32) for x in log_probs_list]
+    labs = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32) for x in labels_list]
+    paths = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32) for x in best_path_list]
+    V = lps[0].shape[1] if lps[0].ndim == 2 else 0
+    for x, p in zip(lps, paths):
+        if x.ndim != 2 or x.shape[1] != V:
+            raise ValueError("all log_probs must be [T_i, V] with one V")
+        if x.shape[0] == 0:
+            raise IndexError("list index out of range")
+        if p.shape[0] != x.shape[0]:
+            raise ValueError("a best path must have one position per frame")
+    Ts = [x.shape[0] for x in lps]
+    posts = [np.empty(t, np.float32) for t in Ts]
+    status = np.zeros(n, np.int32)
+    ll = np.zeros(n, np.float64)
+    eng = _lib.default_engine(_current_device() if device is None else device)
+    p_lp, _k1 = _ptr_array([x.ctypes.data for x in lps])
+    p_lab, _k2 = _ptr_array([x.ctypes.data for x in labs])
+    p_path, _k3 = _ptr_array([x.ctypes.data for x in paths])
+    p_post, _k4 = _ptr_array([x.ctypes.data for x in posts])
+    p_T, _k5 = _i64_array(Ts)
+    p_S, _k6 = _i64_array([x.shape[0] for x in labs])
+    p_ld, _k7 = _i64_array([V] * n)
+    rc = eng.lib.ka_ctc_path_posteriors_batch_f32(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size), int(max_move),
+                                                  p_path, p_post, ll.ctypes.data, status.ctypes.data, _lib.KA_MEM_HOST, None)
+    results = [(p, float(z)) for p, z in zip(posts, ll)]
+    if return_status:
+        if rc not in _POSTERIOR_LATTICE_STATUSES:
+            _lib.check(rc, "ctc_path_posteriors_batch")
+        return results, status.tolist()
+    _lib.check(rc, "ctc_path_posteriors_batch")
+    return results
+
+
+def ctc_path_posteriors_device(log_probs, labels, best_paths, beam_size=1000, max_move=4, return_status=False):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V], labels [S_i], best paths [T_i] - e.g. the outputs of
+    ``ctc_best_path_device``), list of (posteriors tensor [T_i] on the device, log_likelihood float) out.  One launch on
+    torch's current stream."""
+    import torch
+    n = len(log_probs)
+    if n != len(labels) or n != len(best_paths) or n == 0:
+        raise ValueError("log_probs, labels and best paths must be non-empty lists of one length")
+    dev = log_probs[0].device
+    V = int(log_probs[0].shape[1])
+    lps, labs, paths = [], [], []
+    for lp, lab, bp in zip(log_probs, labels, best_paths):
+        if lp.dtype != torch.float32:
+            lp = lp.float()
+        if lp.dim() != 2 or lp.shape[1] != V:
+            raise ValueError("all log_probs must be [T_i, V] tensors with one V")
+        if lp.shape[0] == 0:
+            raise IndexError("list index out of range")
+        if lp.stride(1) != 1:
+            lp = lp.contiguous()
+        lab = lab if _is_tensor(lab) else torch.as_tensor(np.asarray(lab).reshape(-1).astype(np.int32))
+        lab = lab.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+        bp = bp if _is_tensor(bp) else torch.as_tensor(np.asarray(bp).reshape(-1).astype(np.int32))
+        bp = bp.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+        if bp.shape[0] != lp.shape[0]:
+            raise ValueError("a best path must have one position per frame")
+        lps.append(lp)
+        labs.append(lab)
+        paths.append(bp)
+    dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
+    posts = [torch.empty(int(x.shape[0]), dtype=torch.float32, device=dev) for x in lps]
+    status = np.zeros(n, np.int32)
+    ll = np.zeros(n, np.float64)
+    eng = _lib.default_engine(dev_index)
+    p_lp, _k1 = _ptr_array([x.data_ptr() for x in lps])
+    p_lab, _k2 = _ptr_array([x.data_ptr() for x in labs])
+    p_path, _k3 = _ptr_array([x.data_ptr() for x in paths])
+    p_post, _k4 = _ptr_array([x.data_ptr() for x in posts])
+    p_T, _k5 = _i64_array([x.shape[0] for x in lps])
+    p_S, _k6 = _i64_array([x.shape[0] for x in labs])
+    p_ld, _k7 = _i64_array([x.stride(0) for x in lps])
+    with torch.cuda.device(dev):
+        rc = eng.lib.ka_ctc_path_posteriors_batch_f32(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size), int(max_move),
+                                                      p_path, p_post, ll.ctypes.data, status.ctypes.data, _lib.KA_MEM_DEVICE,
+                                                      _stream_ptr(dev_index))
+    results = [(p, float(z)) for p, z in zip(posts, ll)]
+    if return_status:
+        if rc not in _POSTERIOR_LATTICE_STATUSES:
+            _lib.check(rc, "ctc_path_posteriors_device")
+        return results, status.tolist()
+    _lib.check(rc, "ctc_path_posteriors_device")
+    return results
+
+
+def segment_confidence(posteriors, seg_ends):
+    """Mean and minimum posterior of every segment that ``align()`` writes a line for: frames [a, b) with
+    a = seg_ends[i-1] (0 for the first), b = seg_ends[i], clipped to the posteriors' length.  Returns two float64 arrays
+    (NaN for a segment without frames)."""
+    post = np.asarray(posteriors, dtype=np.float64).reshape(-1)
+    ends = np.asarray(seg_ends).reshape(-1)
+    mean = np.full(len(ends), np.nan)
+    low = np.full(len(ends), np.nan)
+    for i in range(len(ends)):
+        a = int(ends[i - 1]) if i > 0 else 0
+        b = min(int(ends[i]), len(post))
+        if b > a:
+            mean[i] = post[a:b].mean()
+            low[i] = post[a:b].min()
+    return mean, low
+
+
 def log_softmax_device(logits, out=None):
     """Mean-subtracted log-softmax of align.py:116-117 on the device (HIP kernel), float32."""
     import torch

@@ -563,6 +563,107 @@ void redo_declined(ka_engine *e, const std::vector<ka_engine::Redo> &again, std:
     }
 }
 
+// ---- best-path posteriors (ka_posterior.hpp): their own kernels and workspace layout, whatever the engine's mode ----
+int posteriors_impl(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                    const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move, const int32_t *const *best_path,
+                    float *const *posteriors, double *log_likelihood, int32_t *status, int32_t mem, hipStream_t stream)
+{
+    if (!e) return fail(KA_ERR_BAD_ARGS, "engine is NULL");
+    if (e->pending) return fail(KA_ERR_BAD_ARGS, "a batch is already enqueued: call ka_batch_finish first");
+    if (n < 0 || (n > 0 && (!log_probs || !T || !ld || !labels || !S || !best_path || !posteriors)))
+        return fail(KA_ERR_BAD_ARGS, "posteriors: NULL array argument");
+    if (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE) return fail(KA_ERR_BAD_ARGS, "mem must be KA_MEM_HOST or KA_MEM_DEVICE");
+    if (n == 0) return KA_OK;
+    std::vector<ka::plan::PostCarve> cv(n);
+    size_t off_res = 0;
+    const size_t total = ka::plan::posterior_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, cv.data(), &off_res);
+    if (total == 0) return fail(KA_ERR_BAD_ARGS, "posteriors: unsupported T/S/V/beam_size/max_move");
+    for (int32_t i = 0; i < n; ++i) {
+        if (ld[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld < V");
+        if (!log_probs[i] || !best_path[i] || !posteriors[i] || (S[i] > 0 && !labels[i]))
+            return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": NULL buffer");
+    }
+    DeviceGuard guard;
+    KA_HIP(guard.enter(e->device));
+    int rc = ensure_ws(e, total);
+    if (rc != KA_OK) return rc;
+    const size_t desc_bytes = align_up((size_t)n * sizeof(ka::PostLattice));
+    rc = ensure_pin(e, desc_bytes + (size_t)n * sizeof(ka::PostResult));
+    if (rc != KA_OK) return rc;
+    // the workspace is shared with the best-path calls: wait for the refill behind their last tile launch, and what it left
+    // clean is clean no more
+    if (e->refill_done) KA_HIP(hipStreamWaitEvent(stream, e->refill_done, 0));
+    e->clean_lo = e->clean_hi = 0;
+    e->dbg_entry_n = e->dbg_map0_bytes = e->dbg_n_tasks = 0;
+    // descriptors: fast-form lattices first, then the generic ones
+    ka::PostLattice *h = reinterpret_cast<ka::PostLattice *>(e->pin);
+    ka::PostResult *h_res = reinterpret_cast<ka::PostResult *>(e->pin + desc_bytes);
+    int32_t n_fast = 0;
+    for (int32_t i = 0; i < n; ++i) n_fast += ka::plan::posterior_fast(S[i], V, beam_size, max_move) ? 1 : 0;
+    int32_t k_fast = 0, k_gen = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const bool fast = ka::plan::posterior_fast(S[i], V, beam_size, max_move);
+        ka::PostLattice &d = h[fast ? k_fast++ : n_fast + k_gen++];
+        std::memset(&d, 0, sizeof(d));
+        const ka::plan::PostCarve &c = cv[i];
+        if (mem == KA_MEM_HOST) {
+            d.lp = reinterpret_cast<const float *>(e->ws + c.lp);
+            d.labels = reinterpret_cast<const int32_t *>(e->ws + c.lab);
+            d.path = reinterpret_cast<const int32_t *>(e->ws + c.path);
+            d.post = reinterpret_cast<float *>(e->ws + c.post);
+            d.ld = V;
+        } else {
+            d.lp = log_probs[i];
+            d.labels = labels[i];
+            d.path = best_path[i];
+            d.post = posteriors[i];
+            d.ld = ld[i];
+        }
+        d.ck = reinterpret_cast<double *>(e->ws + c.ck);
+        d.col = reinterpret_cast<double *>(e->ws + c.col);
+        d.T = (int32_t)T[i];
+        d.S = (int32_t)S[i];
+        d.L = (int32_t)(2 * S[i] + 1);
+        d.V = V;
+        d.beam = beam_size;
+        d.max_move = max_move;
+        d.idx = i;
+    }
+    if (mem == KA_MEM_HOST)
+        for (int32_t i = 0; i < n; ++i) {
+            KA_HIP(hipMemcpy2DAsync(e->ws + cv[i].lp, (size_t)V * 4, log_probs[i], (size_t)ld[i] * 4, (size_t)V * 4, (size_t)T[i],
+                                    hipMemcpyHostToDevice, stream));
+            if (S[i] > 0) KA_HIP(hipMemcpyAsync(e->ws + cv[i].lab, labels[i], (size_t)S[i] * 4, hipMemcpyHostToDevice, stream));
+            KA_HIP(hipMemcpyAsync(e->ws + cv[i].path, best_path[i], (size_t)T[i] * 4, hipMemcpyHostToDevice, stream));
+        }
+    ka::PostLattice *d_lats = reinterpret_cast<ka::PostLattice *>(e->ws);
+    ka::PostResult *d_res = reinterpret_cast<ka::PostResult *>(e->ws + off_res);
+    KA_HIP(hipMemcpyAsync(d_lats, h, (size_t)n * sizeof(ka::PostLattice), hipMemcpyHostToDevice, stream));
+    ka::launch_posteriors(d_lats, n_fast, n - n_fast, max_move, d_res, stream);
+    KA_HIP(hipGetLastError());
+    KA_HIP(hipMemcpyAsync(h_res, d_res, (size_t)n * sizeof(ka::PostResult), hipMemcpyDeviceToHost, stream));
+    if (mem == KA_MEM_HOST)
+        for (int32_t i = 0; i < n; ++i)
+            KA_HIP(hipMemcpyAsync(posteriors[i], e->ws + cv[i].post, (size_t)T[i] * 4, hipMemcpyDeviceToHost, stream));
+    KA_HIP(hipStreamSynchronize(stream));
+    int first_bad = KA_OK;
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t st = h_res[i].status;
+        if (status) status[i] = st;
+        if (log_likelihood) log_likelihood[i] = h_res[i].log_likelihood;
+        if (st != KA_OK && first_bad == KA_OK) {
+            first_bad = st;
+            g_err = "lattice " + std::to_string(i) + (st == KA_ERR_BAD_LABEL   ? ": label outside [0, V)"
+                                                      : st == KA_ERR_NAN       ? ": a log-prob is NaN"
+                                                      : st == KA_ERR_NONFINITE ? ": a log-prob is +inf"
+                                                      : st == KA_ERR_BAD_ARGS  ? ": a best-path position outside [0, 2S+1)"
+                                                      : st == KA_ERR_ZERO_MASS ? ": no path of finite score reaches the best path's terminal"
+                                                                               : ": failed");
+        }
+    }
+    return first_bad;
+}
+
 }  // namespace
 
 extern "C" {
@@ -818,6 +919,29 @@ int ka_ctc_best_path_f32(ka_engine *e, const float *log_probs, int64_t T, int32_
                                         &best_labels, &best_scores, &total, &status, mem, stream);
     if (total_score) *total_score = total;
     return rc;
+}
+
+int ka_ctc_path_posteriors_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                     const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                     const int32_t *const *best_path, float *const *posteriors, double *log_likelihood, int32_t *status,
+                                     int32_t mem, void *stream)
+{
+    return posteriors_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, best_path, posteriors, log_likelihood, status, mem,
+                           (hipStream_t)stream);
+}
+
+int ka_ctc_path_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                               int32_t beam_size, int32_t max_move, const int32_t *best_path, float *posteriors, double *log_likelihood,
+                               int32_t mem, void *stream)
+{
+    return posteriors_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &best_path, &posteriors, log_likelihood, nullptr,
+                           mem, (hipStream_t)stream);
+}
+
+size_t ka_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::posterior_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
 int ka_debug_chunk_entries(ka_engine *e, int32_t *out, int32_t max_entries, uint8_t *map0_out, int64_t map0_max)

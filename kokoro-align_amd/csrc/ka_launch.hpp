@@ -67,4 +67,9 @@ void launch_stft_frames(const float *y, const int64_t *seg_start, const int64_t 
 void launch_power(const float *reim, int64_t ld_in, float *power, int64_t ld_out, int64_t n, int nf, hipStream_t s);
 void launch_power_to_db(float *x, int64_t ld, int cols, const int64_t *frame_off, unsigned grid_x, unsigned nseg, float top_db, float *segmax, hipStream_t s);
 
+// ---- ka_posterior.hip: forward-backward over the band, posteriors of the caller's best path (ka_posterior.hpp) ----
+// descriptors [0, n_fast): one wavefront per lattice (band <= kFastMaxBand, V <= 64, max_move <= 4), then [n_fast, n_fast +
+// n_generic): one 256-thread workgroup per lattice, columns in global memory
+void launch_posteriors(const PostLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+
 }  // namespace ka

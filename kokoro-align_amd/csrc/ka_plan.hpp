@@ -577,3 +577,48 @@ inline size_t workspace_upper_bound(int32_t n, const int64_t *T, const int64_t *
 
 }  // namespace plan
 }  // namespace ka
+
+namespace ka {
+namespace plan {
+
+// ---- ka_ctc_path_posteriors_batch_f32 (ka_posterior.hpp): workspace layout ----
+// descriptors, per-lattice results (status + double log-likelihood), then per lattice: the forward offsets (a double per 32
+// frames), the generic form's four columns (4 L doubles), and for host buffers the staged log-probs, labels, path and output.
+inline bool posterior_fast(int64_t S, int32_t V, int32_t beam, int32_t max_move)
+{
+    return V <= 64 && max_move <= 4 && std::min<int64_t>(beam, 2 * S + 1) <= kFastMaxBand;
+}
+struct PostCarve {
+    size_t ck, col, lp, lab, path, post;
+};
+inline size_t posterior_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
+                                  PostCarve *cv, size_t *off_res)
+{
+    size_t off = align_up((size_t)n * sizeof(PostLattice));
+    if (off_res) *off_res = off;
+    off += align_up((size_t)n * sizeof(PostResult));
+    for (int32_t i = 0; i < n; ++i) {
+        Shape sh;
+        if (!shape_of(T[i], S[i], V, beam, max_move, sh)) return 0;
+        PostCarve c{};
+        c.ck = off;
+        off += align_up((size_t)((sh.T - 1) / kPostCk + 1) * sizeof(double));
+        c.col = off;
+        if (!posterior_fast(sh.S, V, beam, max_move)) off += align_up((size_t)sh.L * 4 * sizeof(double));
+        if (host_buffers) {
+            c.lp = off;
+            off += align_up((size_t)sh.T * (size_t)V * 4);
+            c.lab = off;
+            off += align_up((size_t)sh.S * 4);
+            c.path = off;
+            off += align_up((size_t)sh.T * 4);
+            c.post = off;
+            off += align_up((size_t)sh.T * 4);
+        }
+        if (cv) cv[i] = c;
+    }
+    return off;
+}
+
+}  // namespace plan
+}  // namespace ka

@@ -1,0 +1,488 @@
+// ka_posterior.hpp — forward-backward over the band of align.py:64-65: the posterior of the caller's best path at every frame
+// and the lattice log-likelihood.  Included by ka_posterior.hip only.
+//
+// What is computed, with lab'[2i] = 0, lab'[2i+1] = labels[i], L = 2S+1 and the band and moves of
+// the best-path DP (the label-VALUE-0 veto of align.py:80-81 included):
+//   alpha_t(s) = logsumexp_j alpha_{t-1}(s-j) + lp[t, lab'[s]]     s in band t, alpha_{-1} = {0: 0}
+//   Z          = alpha_{T-1}(s*),  s* = path[T-1]
+//   beta_t(s)  = logsumexp_j beta_{t+1}(s+j) + lp[t+1, lab'[s+j]]   s+j in band t+1, beta_{T-1} = {s*: 0}
+//   post[t]    = exp(alpha_t(p_t) + beta_t(p_t) - Z)                 (0 where p_t is outside band t)
+// Numerics: cells are float64 base-2 logs held RELATIVE to a per-frame offset, the frame's largest cell; the offsets are
+// summed in double.  A linear-domain scaling would underflow the terminal of a poorly aligned chapter.  Float32 cells are not
+// enough: alpha and Z come from one pass, beta from the other, and rounding that does not cancel between them grows with the
+// frames behind t (1.3e-3 of a posterior at T = 8000 in a float32 build).
+//   forward:  u_t(s) = lse2_j u_{t-1}(s-j) - m_{t-1} + e_t(s),  m_t = max_s u_t(s),  C_t = C_{t-1} + m_t,
+//             alpha_t(s) = C_{t-1} + u_t(s)   (log2 units; m = 0 for a frame without mass)
+//   backward: G_t(s) = w_t(s) + e_t(s),  n_t = max_s G_t(s),  D_t = D_{t+1} + n_t,
+//             w_t(s) = lse2_j G_{t+1}(s+j) - n_{t+1},  beta_t(s) = D_{t+1} + w_t(s)
+// No alpha lattice is stored: the forward pass writes alpha_t(p_t) - C_{32k-1} (k = t / 32) into the caller's posterior
+// buffer as a float and C_{32k-1} into a double per 32 frames; the backward pass carries beta across the band and
+// overwrites the buffer with the posterior, combining the two halves and Z in double before the one exp.
+#pragma once
+#include "ka_types.hpp"
+
+namespace ka {
+
+constexpr double kLog2e64 = 1.44269504088896340736;
+constexpr double kLn2 = 0.693147180559945309417;
+
+__device__ __forceinline__ float post_ninf() { return -__builtin_inff(); }
+// (integer tests on the bits, hidden from the optimiser: the library is built with -fno-honor-nans, under which a test of a
+//  float's bits may be folded as a floating-point class test that assumes no NaN)
+__device__ __forceinline__ int post_bad_bits(float x)
+{
+    uint32_t b = __builtin_bit_cast(uint32_t, x);
+    asm volatile("" : "+v"(b));
+    return ((b & 0x7fffffffu) > 0x7f800000u ? 1 : 0) | (b == 0x7f800000u ? 2 : 0);   // 1: NaN, 2: +inf
+}
+__device__ __forceinline__ double post_wave_max(double x)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x = fmaxf(x, __shfl_xor(x, off));
+    return x;
+}
+// One wavefront: its LDS operations execute in program order, so a frame hand-off needs no s_barrier (whose fence would also
+// wait for the global loads prefetched for the next frame), only a compiler fence that keeps the accesses in order.
+__device__ __forceinline__ void post_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+__device__ __forceinline__ double post_dninf() { return -__builtin_inf(); }
+// log2(sum 2^x_j) from the running maximum; all -inf -> -inf (never 2^(-inf - -inf))
+__device__ __forceinline__ double post_lse2(const double *x, int n, double mx)
+{
+    double s = 0.0;
+    for (int j = 0; j < n; ++j) s += exp2(x[j] - mx);
+    return mx == post_dninf() ? post_dninf() : mx + log2(s);
+}
+// band of align.py:64-65 from q = floor(L t / T)
+__device__ __forceinline__ void post_band(int64_t q, int64_t L, int64_t B, int64_t &lo, int64_t &hi)
+{
+    lo = q - B / 2;
+    lo = lo < 0 ? 0 : lo;
+    hi = (L - lo < B) ? L : lo + B;
+}
+// error flags -> status: a bad label is reported before anything runs; then NaN, +inf, a path value outside [0, L)
+__device__ __forceinline__ int post_status_of(int flags)
+{
+    return (flags & 1) ? kStatusNaN : (flags & 2) ? kStatusNonFinite : (flags & 4) ? kStatusBadArgs : kStatusOk;
+}
+// the OR of every thread's error flags (__syncthreads_or is a predicate: it answers 0 or 1)
+__device__ __forceinline__ int post_block_flags(int flags)
+{
+    return (__syncthreads_or(flags & 1) ? 1 : 0) | (__syncthreads_or(flags & 2) ? 2 : 0) | (__syncthreads_or(flags & 4) ? 4 : 0);
+}
+// a lattice without a result: NaN posteriors; log-likelihood NaN, or -inf for kStatusZeroMass (stored as bits: the library
+// is built with -fno-honor-nans, under which a NaN constant is undefined)
+constexpr uint64_t kNaN64 = 0x7ff8000000000000ull, kNinf64 = 0xfff0000000000000ull;
+__device__ __forceinline__ void post_fail(const PostLattice &d, PostResult *res, int status)
+{
+    uint32_t *post = reinterpret_cast<uint32_t *>(d.post);
+    for (int t = threadIdx.x; t < d.T; t += blockDim.x) post[t] = 0x7fc00000u;
+    if (threadIdx.x == 0) {
+        res[d.idx].status = status;
+        *reinterpret_cast<uint64_t *>(&res[d.idx].log_likelihood) = status == kStatusZeroMass ? kNinf64 : kNaN64;
+    }
+}
+__device__ __forceinline__ bool post_labels_bad(const PostLattice &d)
+{
+    int bad = 0;
+    for (int i = threadIdx.x; i < d.S; i += blockDim.x) {
+        const int l = d.labels[i];
+        bad |= (l < 0 || l >= d.V) ? 1 : 0;
+    }
+    return __syncthreads_or(bad) != 0;
+}
+// posterior of one frame from its two halves (log2 units), clamped to a probability
+__device__ __forceinline__ float post_value(double cb, float dt, double D, double w, double Z)
+{
+    const double l2 = (cb + (double)dt) + (D + w) - Z;
+    const double p = exp2(l2);
+    return (float)(p < 1.0 ? p : 1.0);
+}
+
+// ---------------------------------------------------------------------------------------
+// fast form: one wavefront per lattice, band <= kFastMaxBand, V <= 64, M = max_move <= 4
+// ---------------------------------------------------------------------------------------
+// Cell k of lane l is position lo + l + 64 k (16 cells cover the widest band).  Everything a frame exchanges lives in LDS,
+// addressed by slot = position & 1023 (the band is narrower than the ring, so slots never alias within a frame): the
+// previous column (forward: u; backward: G and its vetoable copy), the frame's log-prob row (scaled to log2) and a ring of
+// labels that is refilled, one frame ahead, as the band slides.  Global loads (the next row, the next path value, the
+// labels entering the ring) are issued a frame before their use.
+template <int M>
+__global__ __launch_bounds__(64) void posterior_fast_kernel(const PostLattice *__restrict__ lats, PostResult *res)
+{
+    const PostLattice &d = lats[blockIdx.x];
+    __shared__ double colA[1024], colB[1024], vetA[1024], vetB[1024];
+    __shared__ double row[64];
+    __shared__ int32_t ring[1024];
+    const int lane = threadIdx.x;
+    const int64_t T = d.T, L = d.L, B = d.beam, V = d.V;
+    const int64_t dq = L / T, dr = L % T;
+    const double NINF = post_dninf();
+
+    if (post_labels_bad(d)) {
+        post_fail(d, res, kStatusBadLabel);
+        return;
+    }
+    auto lab_of = [&](int64_t p) -> int32_t { return (p & 1) ? d.labels[p >> 1] : 0; };
+
+    // ---- forward ----
+    for (int64_t p = lane; p < (L < 1024 ? L : 1024); p += 64) ring[p] = lab_of(p);
+    int64_t lfill = L < 1024 ? L : 1024;   // ring holds positions [lfill - 1024, lfill)
+    if (lane == 0) colA[0] = 0.0f;         // virtual state before frame 0
+    double *prev = colA, *cur = colB;
+    int64_t plo = 0, phi = 1, q = 0, r = 0;
+    double C = 0.0, Cb = 0.0;
+    double mprev = 0.0;
+    int flags = 0;
+    float rv = lane < V ? d.lp[lane] : 0.0f;
+    int32_t ptn = d.path[0];
+    post_wave_sync();
+    for (int64_t t = 0; t < T; ++t) {
+        int64_t lo, hi;
+        post_band(q, L, B, lo, hi);
+        // next frame's band: where the label ring has to reach
+        int64_t qn = q + dq, rn = r + dr;
+        if (rn >= T) { rn -= T; ++qn; }
+        int64_t lon, hin;
+        post_band(qn, L, B, lon, hin);
+        const int64_t want = (lon + 1024 < L) ? lon + 1024 : L;
+        const int64_t np = lfill + lane;
+        const bool fill = np < want;
+        const int32_t nlab = fill ? lab_of(np) : 0;
+        if (lane < V) {
+            flags |= post_bad_bits(rv);
+            row[lane] = (double)rv * kLog2e64;
+        }
+        if (t + 1 < T && lane < V) rv = d.lp[(size_t)(t + 1) * (size_t)d.ld + lane];
+        const int32_t pt = ptn;
+        if (t + 1 < T) ptn = d.path[t + 1];
+        flags |= (pt < 0 || pt >= L) ? 4 : 0;
+        if (t % kPostCk == 0) {
+            Cb = C;
+            if (lane == 0) d.ck[t / kPostCk] = C;
+        }
+        post_wave_sync();
+        double mymax = NINF;
+        for (int64_t p = lo + lane; p < hi; p += 64) {
+            {
+                const int32_t lab = ring[p & 1023];
+                const double e = row[lab];
+                double x[M];
+                double mx = NINF;
+#pragma unroll
+                for (int j = 0; j < M; ++j) {
+                    const int64_t u = p - j;
+                    const bool ok = u >= plo && u < phi && !(j >= 2 && (j & 1) == 0 && lab == 0);
+                    x[j] = ok ? prev[u & 1023] : NINF;
+                    mx = fmaxf(mx, x[j]);
+                }
+                const double val = post_lse2(x, M, mx) + (e - mprev);
+                cur[p & 1023] = val;
+                mymax = fmaxf(mymax, val);
+                if (p == pt) d.post[t] = (float)((C - Cb) + val);
+            }
+        }
+        if (lane == 0 && !(pt >= lo && pt < hi)) d.post[t] = post_ninf();
+        double m = post_wave_max(mymax);
+        m = (m == NINF) ? 0.0 : m;
+        C += m;
+        mprev = m;
+        { double *x = prev; prev = cur; cur = x; }
+        plo = lo;
+        phi = hi;
+        q = qn;
+        r = rn;
+        if (fill) ring[np & 1023] = nlab;
+        lfill = (lfill + 64 < want) ? lfill + 64 : (want > lfill ? want : lfill);
+        for (int64_t p = lfill + lane; lfill < want; p = lfill + lane) {   // the band jumped more than 64 positions (L > 64 T)
+            if (p < want) ring[p & 1023] = lab_of(p);
+            lfill = (lfill + 64 < want) ? lfill + 64 : want;
+        }
+        post_wave_sync();
+    }
+    flags = post_block_flags(flags);
+    if (flags) {
+        post_fail(d, res, post_status_of(flags));
+        return;
+    }
+    // ---- Z ----
+    const int64_t tl = T - 1;
+    const double cbl = d.ck[tl / kPostCk];
+    const float dl = d.post[tl];
+    const int32_t sstar = d.path[tl];
+    if (dl == post_ninf()) {
+        post_fail(d, res, kStatusZeroMass);
+        return;
+    }
+    const double Z = cbl + (double)dl;
+    post_wave_sync();
+    // ---- backward ----
+    // frame T-1: G = e at s* (beta = 0 there), -inf elsewhere
+    if (lane < V) row[lane] = (double)d.lp[(size_t)tl * (size_t)d.ld + lane] * kLog2e64;
+    post_wave_sync();
+    int64_t nlo = plo, nhi = phi;          // band of frame t+1
+    double *gn = colA, *gc = colB, *vn = vetA, *vc = vetB;
+    for (int64_t p = nlo + lane; p < nhi; p += 64) {
+        const int32_t lab = ring[p & 1023];
+        const double g = (p == sstar) ? row[lab] : NINF;
+        gn[p & 1023] = g;
+        vn[p & 1023] = lab == 0 ? NINF : g;
+    }
+    const double nT = row[ring[sstar & 1023]];
+    double nprev = nT;
+    double D = nT;
+    if (lane == 0) d.post[tl] = 1.0f;
+    // the ring holds [lbot, lbot + 1024) from here on; frame T-2 must find its band in it
+    int64_t lbot = lfill - 1024 > 0 ? lfill - 1024 : 0;
+    q -= dq; r -= dr;                       // q, r were one frame past the end
+    if (r < 0) { r += T; --q; }
+    q -= dq; r -= dr;
+    if (r < 0) { r += T; --q; }             // frame T-2
+    {
+        int64_t lo, hi;
+        post_band(q, L, B, lo, hi);
+        for (int64_t p = lo + lane; p < lbot && p < lo + 1024; p += 64) ring[p & 1023] = lab_of(p);
+        if (lo < lbot) lbot = lo;
+    }
+    if (T >= 2) {
+        rv = lane < V ? d.lp[(size_t)(T - 2) * (size_t)d.ld + lane] : 0.0f;
+        ptn = d.path[T - 2];
+    }
+    float dtn = T >= 2 ? d.post[T - 2] : 0.0f;
+    post_wave_sync();
+    for (int64_t t = T - 2; t >= 0; --t) {
+        int64_t lo, hi;
+        post_band(q, L, B, lo, hi);
+        int64_t qn = q - dq, rn = r - dr;
+        if (rn < 0) { rn += T; --qn; }
+        int64_t lon = 0, hin = 0;
+        if (t >= 1) post_band(qn, L, B, lon, hin);
+        const int64_t np = lbot - 1 - lane;
+        const bool fill = t >= 1 && np >= lon;
+        const int32_t nlab = fill ? lab_of(np) : 0;
+        if (lane < V) row[lane] = (double)rv * kLog2e64;
+        if (t >= 1 && lane < V) rv = d.lp[(size_t)(t - 1) * (size_t)d.ld + lane];
+        const int32_t pt = ptn;
+        const float dt = dtn;
+        if (t >= 1) {
+            ptn = d.path[t - 1];
+            dtn = d.post[t - 1];
+        }
+        const double cb = d.ck[t / kPostCk];
+        post_wave_sync();
+        double mymax = NINF;
+        for (int64_t p = lo + lane; p < hi; p += 64) {
+            {
+                const int32_t lab = ring[p & 1023];
+                const double e = row[lab];
+                double x[M];
+                double mx = NINF;
+#pragma unroll
+                for (int j = 0; j < M; ++j) {
+                    const int64_t u = p + j;
+                    const bool ok = u >= nlo && u < nhi;
+                    const double g = (j >= 2 && (j & 1) == 0) ? vn[u & 1023] : gn[u & 1023];
+                    x[j] = ok ? g : NINF;
+                    mx = fmaxf(mx, x[j]);
+                }
+                const double w = post_lse2(x, M, mx) - nprev;
+                const double g = w + e;
+                gc[p & 1023] = g;
+                vc[p & 1023] = lab == 0 ? NINF : g;
+                mymax = fmaxf(mymax, g);
+                if (p == pt) d.post[t] = post_value(cb, dt, D, w, Z);
+            }
+        }
+        if (lane == 0 && !(pt >= lo && pt < hi)) d.post[t] = 0.0f;
+        double n = post_wave_max(mymax);
+        n = (n == NINF) ? 0.0 : n;
+        D += n;
+        nprev = n;
+        { double *x = gn; gn = gc; gc = x; }
+        { double *x = vn; vn = vc; vc = x; }
+        nlo = lo;
+        nhi = hi;
+        q = qn;
+        r = rn;
+        if (fill) ring[np & 1023] = nlab;
+        if (t >= 1) {
+            lbot = (lbot - 64 > lon) ? lbot - 64 : (lon < lbot ? lon : lbot);
+            for (int64_t p = lbot - 1 - lane; lbot > lon; p = lbot - 1 - lane) {   // the band jumped more than 64 positions
+                if (p >= lon) ring[p & 1023] = lab_of(p);
+                lbot = (lbot - 64 > lon) ? lbot - 64 : lon;
+            }
+        }
+        post_wave_sync();
+    }
+    if (lane == 0) {
+        res[d.idx].status = kStatusOk;
+        res[d.idx].log_likelihood = Z * kLn2;
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// generic form: any band, any V, max_move <= 255.  One 256-thread workgroup per lattice, the columns in global memory
+// (absolute positions, L2-resident), labels and emissions read where they lie.  A correctness path, not tuned.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ double post_block_max(double x, double *red)   // red: 4 values of this frame's parity
+{
+    x = post_wave_max(x);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+__global__ __launch_bounds__(256) void posterior_generic_kernel(const PostLattice *__restrict__ lats, PostResult *res)
+{
+    const PostLattice &d = lats[blockIdx.x];
+    __shared__ double red[2][4];
+    const int tid = threadIdx.x;
+    const int64_t T = d.T, L = d.L, B = d.beam, V = d.V;
+    const int M = d.max_move;
+    const int64_t dq = L / T, dr = L % T;
+    const double NINF = post_dninf();
+    if (post_labels_bad(d)) {
+        post_fail(d, res, kStatusBadLabel);
+        return;
+    }
+    auto lab_of = [&](int64_t p) -> int32_t { return (p & 1) ? d.labels[p >> 1] : 0; };
+    double *A0 = d.col, *A1 = d.col + L, *V0 = d.col + 2 * L, *V1 = d.col + 3 * L;
+
+    // ---- forward ----
+    if (tid == 0) A0[0] = 0.0;
+    double *prev = A0, *cur = A1;
+    int64_t plo = 0, phi = 1, q = 0, r = 0;
+    double C = 0.0, Cb = 0.0;
+    double mprev = 0.0;
+    int flags = 0;
+    __syncthreads();
+    for (int64_t t = 0; t < T; ++t) {
+        int64_t lo, hi;
+        post_band(q, L, B, lo, hi);
+        const float *lrow = d.lp + (size_t)t * (size_t)d.ld;
+        for (int64_t v = tid; v < V; v += 256) flags |= post_bad_bits(lrow[v]);
+        const int32_t pt = d.path[t];
+        flags |= (pt < 0 || pt >= L) ? 4 : 0;
+        if (t % kPostCk == 0) {
+            Cb = C;
+            if (tid == 0) d.ck[t / kPostCk] = C;
+        }
+        double mymax = NINF;
+        for (int64_t p = lo + tid; p < hi; p += 256) {
+            const int32_t lab = lab_of(p);
+            const double e = (double)lrow[lab] * kLog2e64;
+            double mx = NINF;
+            for (int j = 0; j < M && j <= p; ++j) {
+                const int64_t u = p - j;
+                if (u >= plo && u < phi && !(j >= 2 && (j & 1) == 0 && lab == 0)) mx = fmaxf(mx, prev[u]);
+            }
+            double s = 0.0;
+            for (int j = 0; j < M && j <= p; ++j) {
+                const int64_t u = p - j;
+                if (u >= plo && u < phi && !(j >= 2 && (j & 1) == 0 && lab == 0)) s += exp2(prev[u] - mx);
+            }
+            const double l = mx == NINF ? NINF : mx + log2(s);
+            const double val = l + (e - mprev);
+            cur[p] = val;
+            mymax = fmaxf(mymax, val);
+            if (p == pt) d.post[t] = (float)((C - Cb) + val);
+        }
+        if (tid == 0 && !(pt >= lo && pt < hi)) d.post[t] = post_ninf();
+        double m = post_block_max(mymax, red[t & 1]);
+        m = (m == NINF) ? 0.0 : m;
+        C += m;
+        mprev = m;
+        { double *x = prev; prev = cur; cur = x; }
+        plo = lo;
+        phi = hi;
+        q += dq;
+        r += dr;
+        if (r >= T) { r -= T; ++q; }
+    }
+    flags = post_block_flags(flags);
+    if (flags) {
+        post_fail(d, res, post_status_of(flags));
+        return;
+    }
+    const int64_t tl = T - 1;
+    const double cbl = d.ck[tl / kPostCk];
+    const float dl = d.post[tl];
+    const int32_t sstar = d.path[tl];
+    if (dl == post_ninf()) {
+        post_fail(d, res, kStatusZeroMass);
+        return;
+    }
+    const double Z = cbl + (double)dl;
+    __syncthreads();
+
+    // ---- backward ----
+    int64_t nlo = plo, nhi = phi;
+    double *gn = A0, *gc = A1, *vn = V0, *vc = V1;
+    const double nT = (double)d.lp[(size_t)tl * (size_t)d.ld + lab_of(sstar)] * kLog2e64;
+    for (int64_t p = nlo + tid; p < nhi; p += 256) {
+        const double g = (p == sstar) ? nT : NINF;
+        gn[p] = g;
+        vn[p] = lab_of(p) == 0 ? NINF : g;
+    }
+    double nprev = nT;
+    double D = nT;
+    if (tid == 0) d.post[tl] = 1.0f;
+    // q, r: one frame past the end -> frame T-2
+    for (int i = 0; i < 2; ++i) {
+        q -= dq;
+        r -= dr;
+        if (r < 0) { r += T; --q; }
+    }
+    __syncthreads();
+    for (int64_t t = T - 2; t >= 0; --t) {
+        int64_t lo, hi;
+        post_band(q, L, B, lo, hi);
+        const float *lrow = d.lp + (size_t)t * (size_t)d.ld;
+        const int32_t pt = d.path[t];
+        const float dt = d.post[t];
+        const double cb = d.ck[t / kPostCk];
+        __syncthreads();   // (every thread has read post[t] before its owner overwrites it)
+        double mymax = NINF;
+        for (int64_t p = lo + tid; p < hi; p += 256) {
+            const int32_t lab = lab_of(p);
+            const double e = (double)lrow[lab] * kLog2e64;
+            double mx = NINF;
+            for (int j = 0; j < M; ++j) {
+                const int64_t u = p + j;
+                if (u >= nlo && u < nhi) mx = fmaxf(mx, (j >= 2 && (j & 1) == 0) ? vn[u] : gn[u]);
+            }
+            double s = 0.0;
+            for (int j = 0; j < M; ++j) {
+                const int64_t u = p + j;
+                if (u >= nlo && u < nhi) s += exp2(((j >= 2 && (j & 1) == 0) ? vn[u] : gn[u]) - mx);
+            }
+            const double w = (mx == NINF ? NINF : mx + log2(s)) - nprev;
+            const double g = w + e;
+            gc[p] = g;
+            vc[p] = lab == 0 ? NINF : g;
+            mymax = fmaxf(mymax, g);
+            if (p == pt) d.post[t] = post_value(cb, dt, D, w, Z);
+        }
+        if (tid == 0 && !(pt >= lo && pt < hi)) d.post[t] = 0.0f;
+        double n = post_block_max(mymax, red[t & 1]);
+        n = (n == NINF) ? 0.0 : n;
+        D += n;
+        nprev = n;
+        { double *x = gn; gn = gc; gc = x; }
+        { double *x = vn; vn = vc; vc = x; }
+        nlo = lo;
+        nhi = hi;
+        q -= dq;
+        r -= dr;
+        if (r < 0) { r += T; --q; }
+    }
+    if (tid == 0) {
+        res[d.idx].status = kStatusOk;
+        res[d.idx].log_likelihood = Z * kLn2;
+    }
+}
+
+}  // namespace ka

@@ -131,4 +131,28 @@ constexpr int kLstmH = 128;
 constexpr int kLstmTile = 16;          // sequences per workgroup
 constexpr int kLstmIn = 40;           // input features of layer 0 (MFCC coefficients)
 
+// ---- best-path posteriors and lattice log-likelihood (ka_posterior.hpp) ----
+constexpr int kStatusBadArgs = -2;     // a best-path position outside [0, L)
+constexpr int kStatusNonFinite = -7;   // a log-prob is +inf
+constexpr int kStatusZeroMass = -9;    // no path of finite score ends at the best path's terminal
+constexpr int kPostCk = 32;            // frames per forward offset checkpoint
+struct PostLattice {
+    const float *lp;         // [T, ld] log-probs (device)
+    const int32_t *labels;   // [S] caller labels (device)
+    const int32_t *path;     // [T] the best path the posteriors are asked for (device)
+    float *post;             // [T] output; between the two passes: log2 alpha at the path, relative to ck[t / kPostCk]
+    double *ck;              // [(T - 1) / kPostCk + 1] the forward pass's log2 offset at the first frame of every block (workspace)
+    double *col;             // generic form only: 4 x L doubles, two score columns and two vetoable copies (workspace)
+    int64_t ld;
+    int32_t T, S, L, V;
+    int32_t beam, max_move;
+    int32_t idx;             // index of this lattice in the caller's batch (its PostResult)
+    int32_t pad_;
+};
+struct PostResult {
+    int32_t status;
+    int32_t pad_;
+    double log_likelihood;   // nats
+};
+
 }  // namespace ka

@@ -1,0 +1,115 @@
+"""Wall time of ka_ctc_path_posteriors_batch_f32 (best-path posteriors + lattice log-likelihood, ka_posterior.hpp) on the
+shapes of DESIGN.md section 4.17: one cfg2 lattice, cfg2 batches of 1024 and 8192, the corpus stand-in (workloads.corpus()).
+
+    python tools/bench_posteriors.py [--cases single,b1024,b8192,corpus] [--reps 3] [--out profiles/posteriors.jsonl]
+
+Device-resident inputs (hash-generated); best paths from the library's own best-path call.  The 8192 batch points its
+lattices at the 1024 batch's log-probs, labels and paths eight times over (distinct outputs): 105 GB of log-probs would
+not be a better measurement.  One JSON line per case: ms per call (min, median over reps), frames/s."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import kokoro_align_amd as ka  # noqa: E402
+from kokoro_align_amd import _lib, workloads  # noqa: E402
+from kokoro_align_amd.align import DeviceBatch, _i64_array, _ptr_array, _stream_ptr  # noqa: E402
+
+
+def cfg2(n, seed0=9000, T=50000, V=64, S=5000):
+    lib = _lib.load_library()
+    lp = torch.empty((n, T, V), dtype=torch.float32, device="cuda")
+    lab = torch.empty((n, S), dtype=torch.int32, device="cuda")
+    _lib.check(lib.ka_hash_logprobs_batch_f32(lp.data_ptr(), n, T, V, V, T * V, seed0, None), "hash")
+    _lib.check(lib.ka_hash_labels_batch_i32(lab.data_ptr(), n, S, V, S, seed0, None), "hash")
+    torch.cuda.synchronize()
+    return list(lp.unbind(0)), list(lab.unbind(0))
+
+
+def best_paths(lps, labs):
+    b = DeviceBatch(lps, labs, 1000, 4)
+    b.run()
+    return b.path
+
+
+def time_posteriors(lps, labs, paths, reps):
+    n, V = len(lps), int(lps[0].shape[1])
+    eng = _lib.default_engine(torch.cuda.current_device())
+    posts = [torch.empty(int(x.shape[0]), dtype=torch.float32, device="cuda") for x in lps]
+    ll = np.zeros(n, np.float64)
+    st = np.zeros(n, np.int32)
+    k = [_ptr_array([x.data_ptr() for x in xs]) for xs in (lps, labs, paths, posts)]
+    T = _i64_array([x.shape[0] for x in lps])
+    S = _i64_array([x.shape[0] for x in labs])
+    ld = _i64_array([x.stride(0) for x in lps])
+    stream = _stream_ptr(torch.cuda.current_device())
+
+    def call():
+        rc = eng.lib.ka_ctc_path_posteriors_batch_f32(eng.handle, n, k[0][0], T[0], V, ld[0], k[1][0], S[0], 1000, 4, k[2][0], k[3][0],
+                                                      ll.ctypes.data, st.ctypes.data, _lib.KA_MEM_DEVICE, stream)
+        _lib.check(rc, "ka_ctc_path_posteriors_batch_f32")
+
+    need = eng.lib.ka_posterior_workspace_bytes(n, T[0], S[0], V, 1000, 4, _lib.KA_MEM_DEVICE)
+    eng.reserve(need)
+    call()                                   # warm-up
+    ms = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call()                               # (the call synchronises its stream)
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return ms, st, ll
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default="single,b1024,b8192,corpus")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    torch.cuda.set_device(0)
+    lines = []
+    cases = a.cases.split(",")
+    b1024 = None
+    for case in cases:
+        if case == "single":
+            lps, labs = cfg2(1)
+        elif case in ("b1024", "b8192"):
+            if b1024 is None:
+                lps, labs = cfg2(1024)
+                b1024 = (lps, labs, best_paths(lps, labs))
+            lps, labs, paths = b1024
+            if case == "b8192":
+                lps, labs, paths = lps * 8, labs * 8, paths * 8
+        elif case == "corpus":
+            lps, labs = [], []
+            for k, (name, shapes) in enumerate(workloads.corpus()):
+                x, y = workloads.device_book(shapes, seed0=workloads.corpus_seed0(k))
+                lps += x
+                labs += y
+        else:
+            raise SystemExit(f"unknown case {case}")
+        if case in ("single", "corpus"):
+            paths = best_paths(lps, labs)
+        ms, st, ll = time_posteriors(lps, labs, paths, a.reps)
+        frames = sum(int(x.shape[0]) for x in lps)
+        line = dict(case=case, lattices=len(lps), frames=frames, ms_min=round(min(ms), 3), ms_median=round(float(np.median(ms)), 3),
+                    frames_per_s=frames / (min(ms) / 1e3), status_ok=int((st == 0).sum()), reps=a.reps)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()
