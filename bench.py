@@ -2,6 +2,7 @@
 """bench.py — benchmark of the CTC forced-alignment hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload cfg2|book|corpus] [--lattices B] [--streams G] [--mode M] [--backtrace HOW]
+                    [--dump-outputs DIR] [--full]
 
 --workload cfg2 (default; BASELINE.json configs[1], the configuration the metric is quoted on): synthetic log-probs
     T=50000 x V=64, S=5000 phonemes (L=10001), beam_size=1000, max_move=4.  One "step" = one pass of the hot path (label
@@ -21,6 +22,10 @@ Metric = aligned audio frames per second, whole job (all ranks); no data-path co
 starts one rank per GPU itself (a child process running torch.distributed.run, before anything touches the GPU).
 --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed its caller as DIR/<name>.npy
     (dump_outputs below); the inputs depend on the arguments only, so two builds can be compared output for output.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the result line, nothing else.
+--full adds what goes beyond the headline figure: the CPU baseline (--no-cpu-baseline skips it; the parent of a multi-GPU run
+    times it), the parity spot check of the timed outputs, for cfg2 the serial one-launch pass with the dominant kernel's
+    roofline, and at N=1 the single-lattice, book, cfg1/cfg5, corpus and pipeline entries (--no-latency skips them).
 
 Prints ONE JSON line (rank 0).
 """
@@ -172,7 +177,7 @@ def relay_to_children(args):
     merges it into rank 0's line."""
     import subprocess
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_baseline_seconds)
     # torch.distributed.run picks the rendezvous port itself (--standalone), on the loopback address
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--standalone",
@@ -441,6 +446,32 @@ def dump_outputs(out_dir, batches):
         np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
+def parity_spot_check(batches, B, workload):
+    """--full: checks of the timed step's outputs (rank 0).  Every lattice's status; for cfg2 the golden path of lattice 0,
+    the end positions of the first 64 and, without any reference, on a spread of lattices: the float32 chain of the
+    per-frame scores along the returned path must be the forward pass's best cumulative score bit for bit (a path that is
+    not THE best path of its lattice misses it; this is what caught a store hazard that left every end position right)."""
+    import numpy as np
+    import torch
+    path = [p for b in batches for p in b.path]
+    best_scores = [x for b in batches for x in b.best_scores]
+    total = np.concatenate([np.asarray(b.total, np.float32) for b in batches])
+    ok = all(not (b.status != 0).any() for b in batches)
+    if workload == "cfg2":
+        from tests.golden_util import g3_case
+        g3 = g3_case()       # lattice 0 of rank 0 is the golden cfg2 lattice
+        ok = ok and bool(np.array_equal(path[0].cpu().numpy(), g3["path"]))
+        ends = torch.stack([p[-1] for p in path[: min(B, 64)]]).cpu().numpy()
+        ok = ok and bool((ends == 2 * S).all())
+        pick = sorted(set(np.linspace(0, B - 1, num=min(B, 256), dtype=np.int64).tolist()))
+        chain = np.add.accumulate(torch.stack([best_scores[i] for i in pick]).cpu().numpy(), axis=1, dtype=np.float32)[:, -1]
+        ok = ok and bool(np.array_equal(chain.view(np.int32), total[pick].view(np.int32)))
+    else:
+        for i in range(0, B, max(1, B // 128)):
+            ok = ok and np_chain(best_scores[i]) == np_bits(total[i])
+    return bool(ok)
+
+
 def np_bits(x):
     import numpy as np
     return int(np.float32(x).view(np.int32))
@@ -465,9 +496,11 @@ def main():
     ap.add_argument("--mode", default="auto", choices=["auto", "wave", "wave_exact", "tiled"],
                     help="kernel form (DESIGN.md section 4); auto = one wavefront per lattice, checkpointed, at this batch size")
     ap.add_argument("--backtrace", default="auto", choices=["auto", "serial", "parallel"])
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, parity spot check, roofline and the single-lattice / book / corpus / pipeline entries")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=8.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true", help="skip the single-lattice / book / corpus entries")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the single-lattice / book / corpus / pipeline entries")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's outputs (rank 0) to DIR/<name>.npy, at most 64 MB")
     args = ap.parse_args()
@@ -485,7 +518,7 @@ def main():
     # (the other ranks wait for it in the process group's first barrier); started by relay_to_children the parent has.
     rank_env = int(os.environ.get("RANK", "0"))
     cpu = None
-    if rank_env == 0 and not args.no_cpu_baseline:
+    if rank_env == 0 and args.full and not args.no_cpu_baseline:
         # (under a launcher with several ranks only the one-core figures: the others are waiting for rank 0 in the process
         #  group's rendezvous, and the 16-process pool belongs to the parent of relay_to_children, which has no ranks waiting)
         cpu = cpu_baseline(args.cpu_baseline_seconds, share=world_env <= 1)
@@ -608,28 +641,7 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
 
-    # parity spot check on the timed outputs
-    path = [p for b in batches for p in b.path]
-    best_scores = [x for b in batches for x in b.best_scores]
-    total = np.concatenate([np.asarray(b.total, np.float32) for b in batches])
-    status_ok = all(not (b.status != 0).any() for b in batches)
-    ok = status_ok
-    if rank == 0 and args.workload == "cfg2":
-        from tests.golden_util import g3_case
-        g3 = g3_case()       # lattice 0 of rank 0 is the golden cfg2 lattice
-        ok = ok and bool(np.array_equal(path[0].cpu().numpy(), g3["path"]))
-        ends = torch.stack([p[-1] for p in path[: min(B, 64)]]).cpu().numpy()
-        ok = ok and bool((ends == 2 * S).all())
-        # and, without any reference, on a spread of lattices: the float32 chain of the per-frame scores along the
-        # returned path must be the forward pass's best cumulative score bit for bit (a path that is not THE best
-        # path of its lattice misses it; this is what caught a store hazard that left every end position right)
-        pick = sorted(set(np.linspace(0, B - 1, num=min(B, 256), dtype=np.int64).tolist()))
-        chain = np.add.accumulate(torch.stack([best_scores[i] for i in pick]).cpu().numpy(), axis=1, dtype=np.float32)[:, -1]
-        ok = ok and bool(np.array_equal(chain.view(np.int32), total[pick].view(np.int32)))
-    elif rank == 0:
-        for i in range(0, B, max(1, B // 128)):
-            ok = ok and np_chain(best_scores[i]) == np_bits(total[i])
-        ok = bool(ok)
+    ok = parity_spot_check(batches, B, args.workload) if rank == 0 and args.full else None
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, batches)
 
@@ -648,9 +660,10 @@ def main():
                                "one launch per step, host sync after every step"},
             "kernels_ms": dict(launch_ms, per="launch, HIP events on the launch's own stream inside the timed region"
                                               + (f" ({G} launches in flight: a launch shares the GPU)" if G > 1 else ""), launches=n_launches),
-            "parity_spot_check": ok,
         }
-        if args.workload == "cfg2":
+        if args.full:
+            out["parity_spot_check"] = ok
+        if args.full and args.workload == "cfg2":
             fwd_b, job_b, wbar, survey_fwd_b, survey_job_b = algorithmic_bytes_per_frame()
             checkpointed = args.mode in ("auto", "wave", "tiled")
             if not checkpointed:     # every back-pointer stored: SURVEY.md 8d's bytes are this form's own
@@ -716,10 +729,10 @@ def main():
             out["job_bytes_per_frame"] = job_b
             if serial is not None:
                 out["one_launch_per_step"] = serial
-        if world == 1 and args.workload == "cfg2" and not args.no_latency:
+        if args.full and world == 1 and args.workload == "cfg2" and not args.no_latency:
             lps0, labs0 = lps[0].clone(), labs[0].clone()
             aligner.close()
-            del batches, path, best_scores
+            del batches
             lps = labs = None
             torch.cuda.empty_cache()
             out.update(latency_entries(lps0, labs0))
