@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define KA_VERSION 101 /* 0.1.1: best-path posteriors */
+#define KA_VERSION 102 /* 0.1.2: label occupancy posteriors */
 
 /* status codes (per call and per lattice) */
 #define KA_OK 0
@@ -144,6 +144,30 @@ int ka_ctc_path_posteriors_batch_f32(ka_engine *e, int32_t n, const float *const
  * ka_engine_workspace_bytes keeps both calls free of allocations */
 size_t ka_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size,
                                     int32_t max_move, int32_t mem);
+
+/*
+ * Label occupancy posteriors and the lattice log-likelihood of a terminal: the forward-backward pass
+ * of ka_ctc_path_posteriors over the same band, moves and veto, for a caller-given terminal s* (host array, one per lattice).
+ *   Z = alpha_{T-1}(s*)  (the value ka_ctc_path_posteriors returns for a path that ends at s*)
+ *   gamma_t(s) = exp(alpha_t(s) + beta_t(s) - Z),  beta_{T-1} = {s*: 0}
+ *   occupancy[t, v] = sum over s in band t with lab'[s] = v of gamma_t(s)   (= dZ / d log_probs[t, v]; rows sum to 1)
+ * Arguments as ka_ctc_path_posteriors[_batch]_f32, with terminal in place of best_path and
+ *   occupancy       [T_i rows of V] float32 output (where `mem` says), row pitch ld_out[i] >= V elements (other columns untouched)
+ * Rows are accumulated in 32.32 fixed point: bit-stable, within 2.5e-7 of their float sum, occupancy[T-1, lab'[s*]] = 1 exactly.
+ * Per lattice: KA_ERR_BAD_LABEL, KA_ERR_NAN, KA_ERR_NONFINITE, KA_ERR_BAD_ARGS (terminal outside [0, 2S+1)) - rows NaN,
+ * log-likelihood NaN; KA_ERR_ZERO_MASS - rows NaN, log-likelihood -inf.  The call returns KA_OK or the status of the first
+ * lattice that failed, uses its own kernels (mode and backtrace settings do not apply) and synchronises `stream`.
+ */
+int ka_ctc_label_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                int32_t beam_size, int32_t max_move, int64_t terminal, float *occupancy, int64_t ld_out,
+                                double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_label_posteriors_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                      const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                      int32_t max_move, const int64_t *terminal, float *const *occupancy, const int64_t *ld_out,
+                                      double *log_likelihood, int32_t *status, int32_t mem, void *stream);
+/* device-workspace bytes such a call carves (0 for unsupported arguments); bounded by the lattices resident at once, not by n */
+size_t ka_label_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size,
+                                          int32_t max_move, int32_t mem);
 
 /* Kernel form of the fast path.
  *   KA_MODE_WAVE        one wavefront per lattice, checkpointed (throughput; fills the chip from ~4096

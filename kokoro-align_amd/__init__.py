@@ -6,7 +6,9 @@ Public surface mirrors the reference (kokoro_align/align.py):
     align(best_path_file, mfcc_file, voca_file, align_file, remove_wordsep)   align.py:127
     pandas_read_align(files)                                       align.py:172
 plus batched / device-resident entry points (ctc_best_path_batch, ctc_best_path_device) and the
-forward-backward quality signal of a best path (ctc_path_posteriors[_batch|_device], segment_confidence).
+forward-backward quality signal of a best path (ctc_path_posteriors[_batch|_device], segment_confidence), the label
+occupancy of every frame (ctc_label_posteriors[_batch|_device], segment_agreement) and the differentiable lattice
+log-likelihood (lattice_log_likelihood).
 
 The DP and backtrace run in the HIP C-ABI library (include/kokoro_align_amd.h); there is no
 CPU fallback — importing works without a GPU, computing does not.
@@ -18,11 +20,16 @@ from .align import (  # noqa: F401
     ctc_best_path,
     ctc_best_path_batch,
     ctc_best_path_device,
+    ctc_label_posteriors,
+    ctc_label_posteriors_batch,
+    ctc_label_posteriors_device,
     ctc_path_posteriors,
     ctc_path_posteriors_batch,
     ctc_path_posteriors_device,
+    lattice_log_likelihood,
     log_softmax_device,
     pandas_read_align,
+    segment_agreement,
     segment_confidence,
 )
 from ._lib import KAError, build_library, library_path, load_library  # noqa: F401

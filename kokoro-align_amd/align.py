@@ -376,6 +376,231 @@ def segment_confidence(posteriors, seg_ends):
     return mean, low
 
 
+# ------------------------------------------------------------------------------------------
+# label occupancy posteriors and a differentiable lattice log-likelihood (same band, same forward-backward)
+# ------------------------------------------------------------------------------------------
+def _terminal_of(terminal):
+    """An int, or a best path whose last value is the terminal."""
+    if _is_tensor(terminal):
+        terminal = terminal.detach().reshape(-1)[-1].item() if terminal.dim() > 0 else terminal.item()
+    a = np.asarray(terminal)
+    return int(a.reshape(-1)[-1]) if a.ndim > 0 else int(a)
+
+
+def ctc_label_posteriors(log_probs, labels, terminal, beam_size=1000, max_move=4):
+    """Per-frame label posteriors of the band's paths that end at ``terminal``: (occ float32 [T, V], log_likelihood float).
+
+    occ[t, v] is the probability that frame t emits label value v (blank = 0), over every path of the band of
+    ``ctc_best_path`` that ends at state ``terminal`` (an int, or a best path whose last value is used); each row sums to 1 and
+    occ equals d log_likelihood / d log_probs.  log_likelihood is the value ``ctc_path_posteriors`` returns for a path that
+    ends there.  NumPy in -> NumPy out; ROCm torch tensors go to ``ctc_label_posteriors_device``.  Raises IndexError for a
+    label outside [0, V), ValueError for NaN / +inf log-probs, a terminal outside [0, 2S+1) or one no finite path reaches.
+    """
+    if _is_tensor(log_probs):
+        (occ, ll), = ctc_label_posteriors_device([log_probs], [labels], [terminal], beam_size, max_move)
+        return occ, ll
+    (occ, ll), = ctc_label_posteriors_batch([log_probs], [labels], [terminal], beam_size, max_move)
+    return occ, ll
+
+
+def ctc_label_posteriors_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False):
+    """Label posteriors of many lattices in ONE launch; host NumPy buffers in and out.
+
+    Returns a list of (occ [T_i, V], log_likelihood); with ``return_status`` also the per-lattice status list, in which case
+    failures do not raise (their rows are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    """
+    n = len(log_probs_list)
+    if n != len(labels_list) or n != len(terminals):
+        raise ValueError("log_probs, labels and terminals must be lists of one length")
+    if n == 0:
+        return ([], []) if return_status else []
+    lps = [np.ascontiguousarray(x, dtype=np.float32) for x in log_probs_list]
+    labs = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32) for x in labels_list]
+    V = lps[0].shape[1] if lps[0].ndim == 2 else 0
+    for x in lps:
+        if x.ndim != 2 or x.shape[1] != V:
+            raise ValueError("all log_probs must be [T_i, V] with one V")
+        if x.shape[0] == 0:
+            raise IndexError("list index out of range")
+    occs = [np.empty((x.shape[0], V), np.float32) for x in lps]
+    status = np.zeros(n, np.int32)
+    ll = np.zeros(n, np.float64)
+    eng = _lib.default_engine(_current_device() if device is None else device)
+    p_lp, _k1 = _ptr_array([x.ctypes.data for x in lps])
+    p_lab, _k2 = _ptr_array([x.ctypes.data for x in labs])
+    p_occ, _k3 = _ptr_array([x.ctypes.data for x in occs])
+    p_T, _k4 = _i64_array([x.shape[0] for x in lps])
+    p_S, _k5 = _i64_array([x.shape[0] for x in labs])
+    p_ld, _k6 = _i64_array([V] * n)
+    p_term, _k7 = _i64_array([_terminal_of(s) for s in terminals])
+    rc = eng.lib.ka_ctc_label_posteriors_batch_f32(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size), int(max_move), p_term,
+                                                   p_occ, p_ld, ll.ctypes.data, status.ctypes.data, _lib.KA_MEM_HOST, None)
+    results = [(o, float(z)) for o, z in zip(occs, ll)]
+    if return_status:
+        if rc not in _POSTERIOR_LATTICE_STATUSES:
+            _lib.check(rc, "ctc_label_posteriors_batch")
+        return results, status.tolist()
+    _lib.check(rc, "ctc_label_posteriors_batch")
+    return results
+
+
+def ctc_label_posteriors_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]) and terminals (ints
+    or best paths), list of (occ tensor [T_i, V] on the device, log_likelihood float) out.  ``out``: optional list of float32
+    [T_i, V] tensors with unit column stride to write into (views into wider tensors keep their other columns).  One launch
+    on torch's current stream."""
+    import torch
+    n = len(log_probs)
+    if n != len(labels) or n != len(terminals) or n == 0:
+        raise ValueError("log_probs, labels and terminals must be non-empty lists of one length")
+    dev = log_probs[0].device
+    V = int(log_probs[0].shape[1])
+    lps, labs = [], []
+    for lp, lab in zip(log_probs, labels):
+        if lp.dtype != torch.float32:
+            lp = lp.float()
+        if lp.dim() != 2 or lp.shape[1] != V:
+            raise ValueError("all log_probs must be [T_i, V] tensors with one V")
+        if lp.shape[0] == 0:
+            raise IndexError("list index out of range")
+        if lp.stride(1) != 1:
+            lp = lp.contiguous()
+        lab = lab if _is_tensor(lab) else torch.as_tensor(np.asarray(lab).reshape(-1).astype(np.int32))
+        lab = lab.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+        lps.append(lp)
+        labs.append(lab)
+    if out is None:
+        out = [torch.empty((int(x.shape[0]), V), dtype=torch.float32, device=dev) for x in lps]
+    else:
+        if len(out) != n:
+            raise ValueError("out must hold one tensor per lattice")
+        for o, x in zip(out, lps):
+            if o.dtype != torch.float32 or o.dim() != 2 or tuple(o.shape) != (int(x.shape[0]), V) or o.stride(1) != 1 or o.device != dev:
+                raise ValueError("out tensors must be float32 [T_i, V] on the input's device with unit column stride")
+    dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
+    status = np.zeros(n, np.int32)
+    ll = np.zeros(n, np.float64)
+    eng = _lib.default_engine(dev_index)
+    p_lp, _k1 = _ptr_array([x.data_ptr() for x in lps])
+    p_lab, _k2 = _ptr_array([x.data_ptr() for x in labs])
+    p_occ, _k3 = _ptr_array([x.data_ptr() for x in out])
+    p_T, _k4 = _i64_array([x.shape[0] for x in lps])
+    p_S, _k5 = _i64_array([x.shape[0] for x in labs])
+    p_ld, _k6 = _i64_array([x.stride(0) for x in lps])
+    p_ldo, _k7 = _i64_array([x.stride(0) for x in out])
+    p_term, _k8 = _i64_array([_terminal_of(s) for s in terminals])
+    with torch.cuda.device(dev):
+        rc = eng.lib.ka_ctc_label_posteriors_batch_f32(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size), int(max_move),
+                                                       p_term, p_occ, p_ldo, ll.ctypes.data, status.ctypes.data, _lib.KA_MEM_DEVICE,
+                                                       _stream_ptr(dev_index))
+    results = [(o, float(z)) for o, z in zip(out, ll)]
+    if return_status:
+        if rc not in _POSTERIOR_LATTICE_STATUSES:
+            _lib.check(rc, "ctc_label_posteriors_device")
+        return results, status.tolist()
+    _lib.check(rc, "ctc_label_posteriors_device")
+    return results
+
+
+def _lattice_ll_function():
+    import torch
+
+    class LatticeLogLikelihood(torch.autograd.Function):
+        """Z of every lattice (float64 [n]); backward: grad_out[i] * occ_i, the occupancy saved by forward."""
+
+        @staticmethod
+        def forward(ctx, labels, terminals, beam_size, max_move, zero_infinity, *lps):
+            n = len(lps)
+            if lps[0].is_cuda:
+                res, st = ctc_label_posteriors_device([x.detach() for x in lps], labels, terminals, beam_size, max_move,
+                                                      return_status=True)
+            else:
+                res, st = ctc_label_posteriors_batch([x.detach().float().numpy() for x in lps], labels, terminals, beam_size,
+                                                     max_move, return_status=True)
+                res = [(torch.from_numpy(o), z) for o, z in res]
+            for i, s in enumerate(st):
+                if s == _lib.KA_ERR_ZERO_MASS and zero_infinity:
+                    continue
+                if s != _lib.KA_OK:
+                    _raise_lattice_status(s, i)
+            occs, zs = [], []
+            for (o, z), s in zip(res, st):
+                if s == _lib.KA_ERR_ZERO_MASS:
+                    o = torch.zeros_like(o)
+                    z = 0.0
+                occs.append(o)
+                zs.append(z)
+            ctx.occs = occs
+            ctx.dtypes = [x.dtype for x in lps]
+            return torch.tensor(zs, dtype=torch.float64, device=lps[0].device).reshape(n)
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            grads = [(g * o.to(torch.float64)).to(dt) for g, o, dt in zip(grad_out.unbind(0), ctx.occs, ctx.dtypes)]
+            ctx.occs = None
+            return (None, None, None, None, None, *grads)
+
+    return LatticeLogLikelihood
+
+
+_LATTICE_LL = None
+
+
+def _raise_lattice_status(st, i):
+    what = f"lattice_log_likelihood: lattice {i}"
+    if st == _lib.KA_ERR_BAD_LABEL:
+        raise IndexError(f"{what}: label outside [0, V)")
+    if st == _lib.KA_ERR_NAN:
+        raise ValueError(f"{what}: log_probs contain NaN")
+    if st == _lib.KA_ERR_NONFINITE:
+        raise ValueError(f"{what}: a log-prob is +inf")
+    if st == _lib.KA_ERR_BAD_ARGS:
+        raise ValueError(f"{what}: terminal outside [0, 2S+1)")
+    if st == _lib.KA_ERR_ZERO_MASS:
+        raise ValueError(f"{what}: no path of finite score reaches the terminal")
+    raise _lib.KAError(f"{what}: status {st}")
+
+
+def lattice_log_likelihood(log_probs, labels, terminal, beam_size=1000, max_move=4, zero_infinity=False):
+    """Differentiable log-likelihood Z of the band's paths that end at ``terminal`` (this engine's topology: band, moves,
+    label-0 veto), float64 on the input's device.  One [T, V] tensor (labels, terminal for it) -> 0-d; a list of them (lists
+    of labels and terminals) -> [n].  The gradient with respect to the log-probs is the label occupancy (``ctc_label_posteriors``)
+    times the incoming gradient; the forward pass saves it, so backward launches nothing.  With ``zero_infinity``, a lattice
+    whose terminal no finite path reaches gives 0 and a zero gradient (as ``torch.nn.CTCLoss``); otherwise, and for every
+    other failure, this raises as ``ctc_label_posteriors`` does."""
+    global _LATTICE_LL
+    if _LATTICE_LL is None:
+        _LATTICE_LL = _lattice_ll_function()
+    single = _is_tensor(log_probs)
+    lps = [log_probs] if single else list(log_probs)
+    labs = [labels] if single else list(labels)
+    terms = [terminal] if single else list(terminal)
+    if len(lps) == 0 or len(labs) != len(lps) or len(terms) != len(lps):
+        raise ValueError("log_probs, labels and terminals must be non-empty lists of one length")
+    z = _LATTICE_LL.apply(labs, [_terminal_of(s) for s in terms], int(beam_size), int(max_move), bool(zero_infinity), *lps)
+    return z[0] if single else z
+
+
+def segment_agreement(occ, labels, best_path, seg_ends):
+    """Soft transcript agreement of every segment that ``align()`` writes a line for: the mean over its frames [a, b)
+    (a = seg_ends[i-1], 0 for the first, b = seg_ends[i], clipped to the frames) of occ[t, lab'[best_path[t]]], the
+    occupancy of the label the best path emits.  float64 array, NaN for a segment without frames."""
+    occ = np.asarray(occ.detach().cpu() if _is_tensor(occ) else occ, dtype=np.float64)
+    lab = np.zeros(2 * len(np.asarray(labels).reshape(-1)) + 1, np.int64)
+    lab[1::2] = np.asarray(labels).reshape(-1)
+    path = np.asarray(best_path).reshape(-1).astype(np.int64)
+    T = min(len(path), occ.shape[0])
+    agree = occ[np.arange(T), lab[path[:T]]]
+    ends = np.asarray(seg_ends).reshape(-1)
+    mean = np.full(len(ends), np.nan)
+    for i in range(len(ends)):
+        a = int(ends[i - 1]) if i > 0 else 0
+        b = min(int(ends[i]), T)
+        if b > a:
+            mean[i] = agree[a:b].mean()
+    return mean
+
+
 def log_softmax_device(logits, out=None):
     """Mean-subtracted log-softmax of align.py:116-117 on the device (HIP kernel), float32."""
     import torch

@@ -664,6 +664,112 @@ int posteriors_impl(ka_engine *e, int32_t n, const float *const *log_probs, cons
     return first_bad;
 }
 
+// ---- label occupancy posteriors (ka_occupancy.hpp): their own kernels and workspace layout, whatever the engine's mode ----
+int label_posteriors_impl(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                          const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move, const int64_t *terminal,
+                          float *const *occupancy, const int64_t *ld_out, double *log_likelihood, int32_t *status, int32_t mem,
+                          hipStream_t stream)
+{
+    if (!e) return fail(KA_ERR_BAD_ARGS, "engine is NULL");
+    if (e->pending) return fail(KA_ERR_BAD_ARGS, "a batch is already enqueued: call ka_batch_finish first");
+    if (n < 0 || (n > 0 && (!log_probs || !T || !ld || !labels || !S || !terminal || !occupancy || !ld_out)))
+        return fail(KA_ERR_BAD_ARGS, "label posteriors: NULL array argument");
+    if (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE) return fail(KA_ERR_BAD_ARGS, "mem must be KA_MEM_HOST or KA_MEM_DEVICE");
+    if (n == 0) return KA_OK;
+    std::vector<ka::plan::OccCarve> cv(n);
+    size_t off_res = 0;
+    const size_t total = ka::plan::label_posterior_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, cv.data(), &off_res);
+    if (total == 0) return fail(KA_ERR_BAD_ARGS, "label posteriors: unsupported T/S/V/beam_size/max_move");
+    for (int32_t i = 0; i < n; ++i) {
+        if (ld[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld < V");
+        if (ld_out[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld_out < V");
+        if (!log_probs[i] || !occupancy[i] || (S[i] > 0 && !labels[i]))
+            return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": NULL buffer");
+    }
+    DeviceGuard guard;
+    KA_HIP(guard.enter(e->device));
+    int rc = ensure_ws(e, total);
+    if (rc != KA_OK) return rc;
+    const size_t desc_bytes = align_up((size_t)n * sizeof(ka::OccLattice));
+    rc = ensure_pin(e, desc_bytes + (size_t)n * sizeof(ka::PostResult));
+    if (rc != KA_OK) return rc;
+    // the workspace is shared with the best-path calls (see posteriors_impl)
+    if (e->refill_done) KA_HIP(hipStreamWaitEvent(stream, e->refill_done, 0));
+    e->clean_lo = e->clean_hi = 0;
+    e->dbg_entry_n = e->dbg_map0_bytes = e->dbg_n_tasks = 0;
+    // descriptors: fast-form lattices first, then the generic ones, each in batch order (the order their slots assume)
+    ka::OccLattice *h = reinterpret_cast<ka::OccLattice *>(e->pin);
+    ka::PostResult *h_res = reinterpret_cast<ka::PostResult *>(e->pin + desc_bytes);
+    int32_t n_fast = 0;
+    for (int32_t i = 0; i < n; ++i) n_fast += cv[i].fast ? 1 : 0;
+    int32_t k_fast = 0, k_gen = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const ka::plan::OccCarve &c = cv[i];
+        ka::OccLattice &d = h[c.fast ? k_fast++ : n_fast + k_gen++];
+        std::memset(&d, 0, sizeof(d));
+        if (mem == KA_MEM_HOST) {
+            d.lp = reinterpret_cast<const float *>(e->ws + c.lp);
+            d.labels = reinterpret_cast<const int32_t *>(e->ws + c.lab);
+            d.occ = reinterpret_cast<float *>(e->ws + c.occ);
+            d.ld = V;
+            d.ld_out = V;
+        } else {
+            d.lp = log_probs[i];
+            d.labels = labels[i];
+            d.occ = occupancy[i];
+            d.ld = ld[i];
+            d.ld_out = ld_out[i];
+        }
+        d.ck = reinterpret_cast<double *>(e->ws + c.slot + c.parts.ck);
+        d.ckcol = reinterpret_cast<double *>(e->ws + c.slot + c.parts.ckcol);
+        d.slab = reinterpret_cast<double *>(e->ws + c.slot + c.parts.slab);
+        d.col = reinterpret_cast<double *>(e->ws + c.slot + c.parts.col);
+        d.gbin = reinterpret_cast<unsigned long long *>(e->ws + c.slot + c.parts.gbin);
+        d.T = (int32_t)T[i];
+        d.S = (int32_t)S[i];
+        d.L = (int32_t)(2 * S[i] + 1);
+        d.V = V;
+        d.beam = beam_size;
+        d.max_move = max_move;
+        d.terminal = (terminal[i] >= 0 && terminal[i] <= INT32_MAX) ? (int32_t)terminal[i] : -1;
+        d.cw = c.parts.cw;
+        d.idx = i;
+    }
+    if (mem == KA_MEM_HOST)
+        for (int32_t i = 0; i < n; ++i) {
+            KA_HIP(hipMemcpy2DAsync(e->ws + cv[i].lp, (size_t)V * 4, log_probs[i], (size_t)ld[i] * 4, (size_t)V * 4, (size_t)T[i],
+                                    hipMemcpyHostToDevice, stream));
+            if (S[i] > 0) KA_HIP(hipMemcpyAsync(e->ws + cv[i].lab, labels[i], (size_t)S[i] * 4, hipMemcpyHostToDevice, stream));
+        }
+    ka::OccLattice *d_lats = reinterpret_cast<ka::OccLattice *>(e->ws);
+    ka::PostResult *d_res = reinterpret_cast<ka::PostResult *>(e->ws + off_res);
+    KA_HIP(hipMemcpyAsync(d_lats, h, (size_t)n * sizeof(ka::OccLattice), hipMemcpyHostToDevice, stream));
+    ka::launch_label_posteriors(d_lats, n_fast, n - n_fast, max_move, d_res, stream);
+    KA_HIP(hipGetLastError());
+    KA_HIP(hipMemcpyAsync(h_res, d_res, (size_t)n * sizeof(ka::PostResult), hipMemcpyDeviceToHost, stream));
+    if (mem == KA_MEM_HOST)
+        for (int32_t i = 0; i < n; ++i)
+            KA_HIP(hipMemcpy2DAsync(occupancy[i], (size_t)ld_out[i] * 4, e->ws + cv[i].occ, (size_t)V * 4, (size_t)V * 4, (size_t)T[i],
+                                    hipMemcpyDeviceToHost, stream));
+    KA_HIP(hipStreamSynchronize(stream));
+    int first_bad = KA_OK;
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t st = h_res[i].status;
+        if (status) status[i] = st;
+        if (log_likelihood) log_likelihood[i] = h_res[i].log_likelihood;
+        if (st != KA_OK && first_bad == KA_OK) {
+            first_bad = st;
+            g_err = "lattice " + std::to_string(i) + (st == KA_ERR_BAD_LABEL   ? ": label outside [0, V)"
+                                                      : st == KA_ERR_NAN       ? ": a log-prob is NaN"
+                                                      : st == KA_ERR_NONFINITE ? ": a log-prob is +inf"
+                                                      : st == KA_ERR_BAD_ARGS  ? ": terminal outside [0, 2S+1)"
+                                                      : st == KA_ERR_ZERO_MASS ? ": no path of finite score reaches the terminal"
+                                                                               : ": failed");
+        }
+    }
+    return first_bad;
+}
+
 }  // namespace
 
 extern "C" {
@@ -942,6 +1048,30 @@ size_t ka_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *
 {
     if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
     return ka::plan::posterior_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+int ka_ctc_label_posteriors_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                      const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                      const int64_t *terminal, float *const *occupancy, const int64_t *ld_out, double *log_likelihood,
+                                      int32_t *status, int32_t mem, void *stream)
+{
+    return label_posteriors_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, terminal, occupancy, ld_out, log_likelihood,
+                                 status, mem, (hipStream_t)stream);
+}
+
+int ka_ctc_label_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                int32_t beam_size, int32_t max_move, int64_t terminal, float *occupancy, int64_t ld_out,
+                                double *log_likelihood, int32_t mem, void *stream)
+{
+    return label_posteriors_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &terminal, &occupancy, &ld_out,
+                                 log_likelihood, nullptr, mem, (hipStream_t)stream);
+}
+
+size_t ka_label_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                          int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::label_posterior_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
 int ka_debug_chunk_entries(ka_engine *e, int32_t *out, int32_t max_entries, uint8_t *map0_out, int64_t map0_max)

@@ -622,3 +622,87 @@ inline size_t posterior_workspace(int32_t n, const int64_t *T, const int64_t *S,
 
 }  // namespace plan
 }  // namespace ka
+
+namespace ka {
+namespace plan {
+
+// ---- ka_ctc_label_posteriors_batch_f32 (ka_occupancy.hpp): workspace layout ----
+// descriptors, per-lattice results, for host buffers the staged log-probs, labels and output of every lattice, then the
+// slots: min(n_fast, kOccFastSlots) fast-form slots and min(n_generic, kOccGenericSlots) generic-form ones, each as large as
+// the largest lattice of its form needs.  A slot holds the block offsets (2 doubles per 32 frames), the checkpointed columns
+// (cw doubles per 32 frames), the slab (32 cw doubles) and, in the generic form, 4 L working doubles and, for V above
+// kOccLdsBins, V 64-bit bins.  cw = 1024 in the fast form (slot = position & 1023), the band width in the generic one.
+struct OccParts {
+    size_t ck, ckcol, slab, col, gbin, bytes;
+    int32_t cw;
+};
+inline OccParts occ_parts(const Shape &sh, int32_t V, int32_t beam, int32_t max_move)
+{
+    OccParts o{};
+    const bool fast = posterior_fast(sh.S, V, beam, max_move);
+    o.cw = fast ? 1024 : (int32_t)sh.W;
+    const size_t nblk = (size_t)((sh.T - 1) / kPostCk + 1);
+    size_t off = 0;
+    o.ck = off;
+    off += align_up(nblk * 2 * sizeof(double));
+    o.ckcol = off;
+    off += align_up(nblk * (size_t)o.cw * sizeof(double));
+    o.slab = off;
+    off += align_up((size_t)kPostCk * (size_t)o.cw * sizeof(double));
+    o.col = off;
+    if (!fast) off += align_up((size_t)sh.L * 4 * sizeof(double));
+    o.gbin = off;
+    if (!fast && V > kOccLdsBins) off += align_up((size_t)V * 8);
+    o.bytes = off;
+    return o;
+}
+struct OccCarve {
+    size_t slot;            // base of this lattice's slot
+    size_t lp, lab, occ;    // host buffers only
+    OccParts parts;
+    bool fast;
+};
+inline size_t label_posterior_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move,
+                                        bool host_buffers, OccCarve *cv, size_t *off_res)
+{
+    size_t off = align_up((size_t)n * sizeof(OccLattice));
+    if (off_res) *off_res = off;
+    off += align_up((size_t)n * sizeof(PostResult));
+    int32_t n_fast = 0, n_gen = 0;
+    size_t fast_bytes = 0, gen_bytes = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        Shape sh;
+        if (!shape_of(T[i], S[i], V, beam, max_move, sh)) return 0;
+        const OccParts o = occ_parts(sh, V, beam, max_move);
+        const bool fast = posterior_fast(sh.S, V, beam, max_move);
+        size_t &slot_bytes = fast ? fast_bytes : gen_bytes;
+        slot_bytes = std::max(slot_bytes, o.bytes);
+        OccCarve c{};
+        c.parts = o;
+        c.fast = fast;
+        c.slot = (size_t)(fast ? n_fast++ : n_gen++);   // (the lattice's rank in its form until the slots are placed)
+        if (host_buffers) {
+            c.lp = off;
+            off += align_up((size_t)sh.T * (size_t)V * 4);
+            c.lab = off;
+            off += align_up((size_t)sh.S * 4);
+            c.occ = off;
+            off += align_up((size_t)sh.T * (size_t)V * 4);
+        }
+        if (cv) cv[i] = c;
+    }
+    const size_t fast_base = off;
+    const int32_t fast_slots = std::min(n_fast, kOccFastSlots), gen_slots = std::min(n_gen, kOccGenericSlots);
+    off += (size_t)fast_slots * fast_bytes;
+    const size_t gen_base = off;
+    off += (size_t)gen_slots * gen_bytes;
+    if (cv)
+        for (int32_t i = 0; i < n; ++i) {
+            OccCarve &c = cv[i];
+            c.slot = c.fast ? fast_base + (c.slot % (size_t)fast_slots) * fast_bytes : gen_base + (c.slot % (size_t)gen_slots) * gen_bytes;
+        }
+    return off;
+}
+
+}  // namespace plan
+}  // namespace ka

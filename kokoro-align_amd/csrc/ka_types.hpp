@@ -155,4 +155,26 @@ struct PostResult {
     double log_likelihood;   // nats
 };
 
+// ---- label occupancy posteriors (ka_occupancy.hpp) ----
+constexpr int kOccFastSlots = 1024;    // fast-form lattices resident at once (four wavefronts per CU): per-slot workspace
+constexpr int kOccGenericSlots = 512;  // generic-form workgroups of one launch, each walking its lattices in turn
+constexpr int kOccLdsBins = 2048;      // generic form: V up to this bins in LDS, above it in a workspace row
+struct OccLattice {
+    const float *lp;              // [T, ld] log-probs (device)
+    const int32_t *labels;        // [S] caller labels (device)
+    float *occ;                   // [T, ld_out] output, V columns written
+    double *ck;                   // [nblk][2] forward offset C and frame maximum m before the first frame of every block (slot)
+    double *ckcol;                // [nblk][cw] alpha column before the first frame of every block, relative to its offset (slot)
+    double *slab;                 // [kPostCk][cw] alpha of the block being walked back (slot)
+    double *col;                  // generic form only: 4 x L doubles, the working columns (slot)
+    unsigned long long *gbin;     // generic form, V > kOccLdsBins only: [V] fixed-point bins (slot)
+    int64_t ld, ld_out;
+    int32_t T, S, L, V;
+    int32_t beam, max_move;
+    int32_t terminal;             // s*, or -1 for a value outside int32
+    int32_t cw;                   // column stride of ckcol / slab: 1024 (fast form, slot = position & 1023) or the band width
+    int32_t idx;                  // index of this lattice in the caller's batch (its PostResult)
+    int32_t pad_;
+};
+
 }  // namespace ka

@@ -1,5 +1,7 @@
 """Wall time of ka_ctc_path_posteriors_batch_f32 (best-path posteriors + lattice log-likelihood, ka_posterior.hpp) on the
-shapes of DESIGN.md section 4.17: one cfg2 lattice, cfg2 batches of 1024 and 8192, the corpus stand-in (workloads.corpus()).
+shapes of DESIGN.md section 4.17: one cfg2 lattice, cfg2 batches of 1024 and 8192, the corpus stand-in (workloads.corpus());
+and of ka_ctc_label_posteriors_batch_f32 (label occupancy, ka_occupancy.hpp, section 4.18) on the same cfg2 shapes, the
+terminal taken from the best path (cases occ_single, occ_b1024, occ_b8192).
 
     python tools/bench_posteriors.py [--cases single,b1024,b8192,corpus] [--reps 3] [--out profiles/posteriors.jsonl]
 
@@ -68,6 +70,37 @@ def time_posteriors(lps, labs, paths, reps):
     return ms, st, ll
 
 
+def time_occupancy(lps, labs, paths, reps):
+    n, V = len(lps), int(lps[0].shape[1])
+    eng = _lib.default_engine(torch.cuda.current_device())
+    occs = [torch.empty((int(x.shape[0]), V), dtype=torch.float32, device="cuda") for x in lps]
+    ll = np.zeros(n, np.float64)
+    st = np.zeros(n, np.int32)
+    k = [_ptr_array([x.data_ptr() for x in xs]) for xs in (lps, labs, occs)]
+    T = _i64_array([x.shape[0] for x in lps])
+    S = _i64_array([x.shape[0] for x in labs])
+    ld = _i64_array([x.stride(0) for x in lps])
+    ldo = _i64_array([x.stride(0) for x in occs])
+    term = _i64_array(torch.stack([p[-1] for p in paths]).cpu().tolist())
+    stream = _stream_ptr(torch.cuda.current_device())
+
+    def call():
+        rc = eng.lib.ka_ctc_label_posteriors_batch_f32(eng.handle, n, k[0][0], T[0], V, ld[0], k[1][0], S[0], 1000, 4, term[0], k[2][0],
+                                                       ldo[0], ll.ctypes.data, st.ctypes.data, _lib.KA_MEM_DEVICE, stream)
+        _lib.check(rc, "ka_ctc_label_posteriors_batch_f32")
+
+    need = eng.lib.ka_label_posterior_workspace_bytes(n, T[0], S[0], V, 1000, 4, _lib.KA_MEM_DEVICE)
+    eng.reserve(need)
+    call()                                   # warm-up
+    ms = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call()                               # (the call synchronises its stream)
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return ms, st, ll
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="single,b1024,b8192,corpus")
@@ -79,16 +112,18 @@ def main():
     cases = a.cases.split(",")
     b1024 = None
     for case in cases:
-        if case == "single":
+        occ = case.startswith("occ_")
+        case_in = case[4:] if occ else case
+        if case_in == "single":
             lps, labs = cfg2(1)
-        elif case in ("b1024", "b8192"):
+        elif case_in in ("b1024", "b8192"):
             if b1024 is None:
                 lps, labs = cfg2(1024)
                 b1024 = (lps, labs, best_paths(lps, labs))
             lps, labs, paths = b1024
-            if case == "b8192":
+            if case_in == "b8192":
                 lps, labs, paths = lps * 8, labs * 8, paths * 8
-        elif case == "corpus":
+        elif case_in == "corpus":
             lps, labs = [], []
             for k, (name, shapes) in enumerate(workloads.corpus()):
                 x, y = workloads.device_book(shapes, seed0=workloads.corpus_seed0(k))
@@ -96,9 +131,9 @@ def main():
                 labs += y
         else:
             raise SystemExit(f"unknown case {case}")
-        if case in ("single", "corpus"):
+        if case_in in ("single", "corpus"):
             paths = best_paths(lps, labs)
-        ms, st, ll = time_posteriors(lps, labs, paths, a.reps)
+        ms, st, ll = (time_occupancy if occ else time_posteriors)(lps, labs, paths, a.reps)
         frames = sum(int(x.shape[0]) for x in lps)
         line = dict(case=case, lattices=len(lps), frames=frames, ms_min=round(min(ms), 3), ms_median=round(float(np.median(ms)), 3),
                     frames_per_s=frames / (min(ms) / 1e3), status_ok=int((st == 0).sum()), reps=a.reps)
