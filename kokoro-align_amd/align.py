@@ -259,64 +259,44 @@ def ctc_path_posteriors(log_probs, labels, best_path, beam_size=1000, max_move=4
     return post, ll
 
 
-def ctc_path_posteriors_batch(log_probs_list, labels_list, best_path_list, beam_size=1000, max_move=4, device=None,
-                              return_status=False):
-    """Posteriors of many lattices in ONE launch; host NumPy buffers in and out.
-
-    Returns a list of (posteriors, log_likelihood); with ``return_status`` also the per-lattice status list, in which case
-    failures do not raise (their posteriors are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
-    """
+def _host_lattices(log_probs_list, labels_list, others, what, paths=False):
+    """The input handling of the two ``*_batch`` calls: (log-probs, labels, best paths or None, V) as contiguous NumPy arrays,
+    or None for an empty batch.  ``others`` holds one best path (``paths``) or terminal per lattice."""
     n = len(log_probs_list)
-    if n != len(labels_list) or n != len(best_path_list):
-        raise ValueError("log_probs, labels and best paths must be lists of one length")
+    if n != len(labels_list) or n != len(others):
+        raise ValueError(f"log_probs, labels and {what} must be lists of one length")
     if n == 0:
-        return ([], []) if return_status else []
+        return None
     lps = [np.ascontiguousarray(x, dtype=np.float32) for x in log_probs_list]
     labs = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32) for x in labels_list]
-    paths = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32) for x in best_path_list]
+    bps = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32) for x in others] if paths else None
     V = lps[0].shape[1] if lps[0].ndim == 2 else 0
-    for x, p in zip(lps, paths):
+    for i, x in enumerate(lps):
         if x.ndim != 2 or x.shape[1] != V:
             raise ValueError("all log_probs must be [T_i, V] with one V")
         if x.shape[0] == 0:
             raise IndexError("list index out of range")
-        if p.shape[0] != x.shape[0]:
+        if paths and bps[i].shape[0] != x.shape[0]:
             raise ValueError("a best path must have one position per frame")
-    Ts = [x.shape[0] for x in lps]
-    posts = [np.empty(t, np.float32) for t in Ts]
-    status = np.zeros(n, np.int32)
-    ll = np.zeros(n, np.float64)
-    eng = _lib.default_engine(_current_device() if device is None else device)
-    p_lp, _k1 = _ptr_array([x.ctypes.data for x in lps])
-    p_lab, _k2 = _ptr_array([x.ctypes.data for x in labs])
-    p_path, _k3 = _ptr_array([x.ctypes.data for x in paths])
-    p_post, _k4 = _ptr_array([x.ctypes.data for x in posts])
-    p_T, _k5 = _i64_array(Ts)
-    p_S, _k6 = _i64_array([x.shape[0] for x in labs])
-    p_ld, _k7 = _i64_array([V] * n)
-    rc = eng.lib.ka_ctc_path_posteriors_batch_f32(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size), int(max_move),
-                                                  p_path, p_post, ll.ctypes.data, status.ctypes.data, _lib.KA_MEM_HOST, None)
-    results = [(p, float(z)) for p, z in zip(posts, ll)]
-    if return_status:
-        if rc not in _POSTERIOR_LATTICE_STATUSES:
-            _lib.check(rc, "ctc_path_posteriors_batch")
-        return results, status.tolist()
-    _lib.check(rc, "ctc_path_posteriors_batch")
-    return results
+    return lps, labs, bps, V
 
 
-def ctc_path_posteriors_device(log_probs, labels, best_paths, beam_size=1000, max_move=4, return_status=False):
-    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V], labels [S_i], best paths [T_i] - e.g. the outputs of
-    ``ctc_best_path_device``), list of (posteriors tensor [T_i] on the device, log_likelihood float) out.  One launch on
-    torch's current stream."""
+def _device_lattices(log_probs, labels, others, what, paths=False):
+    """The input handling of the two ``*_device`` calls: (log-probs, labels, best paths or None, V, device, device index) as
+    tensors on the first log-prob's device, log-probs float32 with unit column stride, labels and paths int32 contiguous."""
     import torch
     n = len(log_probs)
-    if n != len(labels) or n != len(best_paths) or n == 0:
-        raise ValueError("log_probs, labels and best paths must be non-empty lists of one length")
+    if n != len(labels) or n != len(others) or n == 0:
+        raise ValueError(f"log_probs, labels and {what} must be non-empty lists of one length")
     dev = log_probs[0].device
     V = int(log_probs[0].shape[1])
-    lps, labs, paths = [], [], []
-    for lp, lab, bp in zip(log_probs, labels, best_paths):
+
+    def int32_on_dev(x):
+        x = x if _is_tensor(x) else torch.as_tensor(np.asarray(x).reshape(-1).astype(np.int32))
+        return x.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+
+    lps, labs, bps = [], [], ([] if paths else None)
+    for i, (lp, lab) in enumerate(zip(log_probs, labels)):
         if lp.dtype != torch.float32:
             lp = lp.float()
         if lp.dim() != 2 or lp.shape[1] != V:
@@ -325,38 +305,74 @@ def ctc_path_posteriors_device(log_probs, labels, best_paths, beam_size=1000, ma
             raise IndexError("list index out of range")
         if lp.stride(1) != 1:
             lp = lp.contiguous()
-        lab = lab if _is_tensor(lab) else torch.as_tensor(np.asarray(lab).reshape(-1).astype(np.int32))
-        lab = lab.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
-        bp = bp if _is_tensor(bp) else torch.as_tensor(np.asarray(bp).reshape(-1).astype(np.int32))
-        bp = bp.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
-        if bp.shape[0] != lp.shape[0]:
-            raise ValueError("a best path must have one position per frame")
+        labs.append(int32_on_dev(lab))
+        if paths:
+            bp = int32_on_dev(others[i])
+            if bp.shape[0] != lp.shape[0]:
+                raise ValueError("a best path must have one position per frame")
+            bps.append(bp)
         lps.append(lp)
-        labs.append(lab)
-        paths.append(bp)
     dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
-    posts = [torch.empty(int(x.shape[0]), dtype=torch.float32, device=dev) for x in lps]
+    return lps, labs, bps, V, dev, dev_index
+
+
+def _run_lattices(eng, fn, name, lp_ptrs, Ts, V, lds, lab_ptrs, Ss, beam_size, max_move, own_args, outs, mem, stream, return_status):
+    """One ``ka_ctc_{path,label}_posteriors_batch_f32`` call: the arguments both take around ``own_args`` (the call's own
+    pointer arrays), then the results (outs[i], log_likelihood[i]) and the status handling of ``return_status``."""
+    n = len(lp_ptrs)
     status = np.zeros(n, np.int32)
     ll = np.zeros(n, np.float64)
-    eng = _lib.default_engine(dev_index)
-    p_lp, _k1 = _ptr_array([x.data_ptr() for x in lps])
-    p_lab, _k2 = _ptr_array([x.data_ptr() for x in labs])
-    p_path, _k3 = _ptr_array([x.data_ptr() for x in paths])
-    p_post, _k4 = _ptr_array([x.data_ptr() for x in posts])
-    p_T, _k5 = _i64_array([x.shape[0] for x in lps])
-    p_S, _k6 = _i64_array([x.shape[0] for x in labs])
-    p_ld, _k7 = _i64_array([x.stride(0) for x in lps])
-    with torch.cuda.device(dev):
-        rc = eng.lib.ka_ctc_path_posteriors_batch_f32(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size), int(max_move),
-                                                      p_path, p_post, ll.ctypes.data, status.ctypes.data, _lib.KA_MEM_DEVICE,
-                                                      _stream_ptr(dev_index))
-    results = [(p, float(z)) for p, z in zip(posts, ll)]
+    p_lp, _k1 = _ptr_array(lp_ptrs)
+    p_lab, _k2 = _ptr_array(lab_ptrs)
+    p_T, _k3 = _i64_array(Ts)
+    p_S, _k4 = _i64_array(Ss)
+    p_ld, _k5 = _i64_array(lds)
+    rc = getattr(eng.lib, fn)(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size), int(max_move), *own_args,
+                              ll.ctypes.data, status.ctypes.data, mem, stream)
+    results = [(o, float(z)) for o, z in zip(outs, ll)]
     if return_status:
         if rc not in _POSTERIOR_LATTICE_STATUSES:
-            _lib.check(rc, "ctc_path_posteriors_device")
+            _lib.check(rc, name)
         return results, status.tolist()
-    _lib.check(rc, "ctc_path_posteriors_device")
+    _lib.check(rc, name)
     return results
+
+
+def ctc_path_posteriors_batch(log_probs_list, labels_list, best_path_list, beam_size=1000, max_move=4, device=None,
+                              return_status=False):
+    """Posteriors of many lattices in ONE launch; host NumPy buffers in and out.
+
+    Returns a list of (posteriors, log_likelihood); with ``return_status`` also the per-lattice status list, in which case
+    failures do not raise (their posteriors are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    """
+    got = _host_lattices(log_probs_list, labels_list, best_path_list, "best paths", paths=True)
+    if got is None:
+        return ([], []) if return_status else []
+    lps, labs, paths, V = got
+    posts = [np.empty(x.shape[0], np.float32) for x in lps]
+    eng = _lib.default_engine(_current_device() if device is None else device)
+    p_path, _k1 = _ptr_array([x.ctypes.data for x in paths])
+    p_post, _k2 = _ptr_array([x.ctypes.data for x in posts])
+    return _run_lattices(eng, "ka_ctc_path_posteriors_batch_f32", "ctc_path_posteriors_batch", [x.ctypes.data for x in lps],
+                         [x.shape[0] for x in lps], V, [V] * len(lps), [x.ctypes.data for x in labs], [x.shape[0] for x in labs],
+                         beam_size, max_move, (p_path, p_post), posts, _lib.KA_MEM_HOST, None, return_status)
+
+
+def ctc_path_posteriors_device(log_probs, labels, best_paths, beam_size=1000, max_move=4, return_status=False):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V], labels [S_i], best paths [T_i] - e.g. the outputs of
+    ``ctc_best_path_device``), list of (posteriors tensor [T_i] on the device, log_likelihood float) out.  One launch on
+    torch's current stream."""
+    import torch
+    lps, labs, paths, V, dev, dev_index = _device_lattices(log_probs, labels, best_paths, "best paths", paths=True)
+    posts = [torch.empty(int(x.shape[0]), dtype=torch.float32, device=dev) for x in lps]
+    eng = _lib.default_engine(dev_index)
+    p_path, _k1 = _ptr_array([x.data_ptr() for x in paths])
+    p_post, _k2 = _ptr_array([x.data_ptr() for x in posts])
+    with torch.cuda.device(dev):
+        return _run_lattices(eng, "ka_ctc_path_posteriors_batch_f32", "ctc_path_posteriors_device", [x.data_ptr() for x in lps],
+                             [x.shape[0] for x in lps], V, [x.stride(0) for x in lps], [x.data_ptr() for x in labs],
+                             [x.shape[0] for x in labs], beam_size, max_move, (p_path, p_post), posts, _lib.KA_MEM_DEVICE,
+                             _stream_ptr(dev_index), return_status)
 
 
 def segment_confidence(posteriors, seg_ends):
@@ -409,39 +425,18 @@ def ctc_label_posteriors_batch(log_probs_list, labels_list, terminals, beam_size
     Returns a list of (occ [T_i, V], log_likelihood); with ``return_status`` also the per-lattice status list, in which case
     failures do not raise (their rows are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
     """
-    n = len(log_probs_list)
-    if n != len(labels_list) or n != len(terminals):
-        raise ValueError("log_probs, labels and terminals must be lists of one length")
-    if n == 0:
+    got = _host_lattices(log_probs_list, labels_list, terminals, "terminals")
+    if got is None:
         return ([], []) if return_status else []
-    lps = [np.ascontiguousarray(x, dtype=np.float32) for x in log_probs_list]
-    labs = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32) for x in labels_list]
-    V = lps[0].shape[1] if lps[0].ndim == 2 else 0
-    for x in lps:
-        if x.ndim != 2 or x.shape[1] != V:
-            raise ValueError("all log_probs must be [T_i, V] with one V")
-        if x.shape[0] == 0:
-            raise IndexError("list index out of range")
+    lps, labs, _, V = got
     occs = [np.empty((x.shape[0], V), np.float32) for x in lps]
-    status = np.zeros(n, np.int32)
-    ll = np.zeros(n, np.float64)
     eng = _lib.default_engine(_current_device() if device is None else device)
-    p_lp, _k1 = _ptr_array([x.ctypes.data for x in lps])
-    p_lab, _k2 = _ptr_array([x.ctypes.data for x in labs])
-    p_occ, _k3 = _ptr_array([x.ctypes.data for x in occs])
-    p_T, _k4 = _i64_array([x.shape[0] for x in lps])
-    p_S, _k5 = _i64_array([x.shape[0] for x in labs])
-    p_ld, _k6 = _i64_array([V] * n)
-    p_term, _k7 = _i64_array([_terminal_of(s) for s in terminals])
-    rc = eng.lib.ka_ctc_label_posteriors_batch_f32(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size), int(max_move), p_term,
-                                                   p_occ, p_ld, ll.ctypes.data, status.ctypes.data, _lib.KA_MEM_HOST, None)
-    results = [(o, float(z)) for o, z in zip(occs, ll)]
-    if return_status:
-        if rc not in _POSTERIOR_LATTICE_STATUSES:
-            _lib.check(rc, "ctc_label_posteriors_batch")
-        return results, status.tolist()
-    _lib.check(rc, "ctc_label_posteriors_batch")
-    return results
+    p_occ, _k1 = _ptr_array([x.ctypes.data for x in occs])
+    p_ldo, _k2 = _i64_array([V] * len(lps))
+    p_term, _k3 = _i64_array([_terminal_of(s) for s in terminals])
+    return _run_lattices(eng, "ka_ctc_label_posteriors_batch_f32", "ctc_label_posteriors_batch", [x.ctypes.data for x in lps],
+                         [x.shape[0] for x in lps], V, [V] * len(lps), [x.ctypes.data for x in labs], [x.shape[0] for x in labs],
+                         beam_size, max_move, (p_term, p_occ, p_ldo), occs, _lib.KA_MEM_HOST, None, return_status)
 
 
 def ctc_label_posteriors_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False):
@@ -450,25 +445,8 @@ def ctc_label_posteriors_device(log_probs, labels, terminals, beam_size=1000, ma
     [T_i, V] tensors with unit column stride to write into (views into wider tensors keep their other columns).  One launch
     on torch's current stream."""
     import torch
-    n = len(log_probs)
-    if n != len(labels) or n != len(terminals) or n == 0:
-        raise ValueError("log_probs, labels and terminals must be non-empty lists of one length")
-    dev = log_probs[0].device
-    V = int(log_probs[0].shape[1])
-    lps, labs = [], []
-    for lp, lab in zip(log_probs, labels):
-        if lp.dtype != torch.float32:
-            lp = lp.float()
-        if lp.dim() != 2 or lp.shape[1] != V:
-            raise ValueError("all log_probs must be [T_i, V] tensors with one V")
-        if lp.shape[0] == 0:
-            raise IndexError("list index out of range")
-        if lp.stride(1) != 1:
-            lp = lp.contiguous()
-        lab = lab if _is_tensor(lab) else torch.as_tensor(np.asarray(lab).reshape(-1).astype(np.int32))
-        lab = lab.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
-        lps.append(lp)
-        labs.append(lab)
+    lps, labs, _, V, dev, dev_index = _device_lattices(log_probs, labels, terminals, "terminals")
+    n = len(lps)
     if out is None:
         out = [torch.empty((int(x.shape[0]), V), dtype=torch.float32, device=dev) for x in lps]
     else:
@@ -477,29 +455,15 @@ def ctc_label_posteriors_device(log_probs, labels, terminals, beam_size=1000, ma
         for o, x in zip(out, lps):
             if o.dtype != torch.float32 or o.dim() != 2 or tuple(o.shape) != (int(x.shape[0]), V) or o.stride(1) != 1 or o.device != dev:
                 raise ValueError("out tensors must be float32 [T_i, V] on the input's device with unit column stride")
-    dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
-    status = np.zeros(n, np.int32)
-    ll = np.zeros(n, np.float64)
     eng = _lib.default_engine(dev_index)
-    p_lp, _k1 = _ptr_array([x.data_ptr() for x in lps])
-    p_lab, _k2 = _ptr_array([x.data_ptr() for x in labs])
-    p_occ, _k3 = _ptr_array([x.data_ptr() for x in out])
-    p_T, _k4 = _i64_array([x.shape[0] for x in lps])
-    p_S, _k5 = _i64_array([x.shape[0] for x in labs])
-    p_ld, _k6 = _i64_array([x.stride(0) for x in lps])
-    p_ldo, _k7 = _i64_array([x.stride(0) for x in out])
-    p_term, _k8 = _i64_array([_terminal_of(s) for s in terminals])
+    p_occ, _k1 = _ptr_array([x.data_ptr() for x in out])
+    p_ldo, _k2 = _i64_array([x.stride(0) for x in out])
+    p_term, _k3 = _i64_array([_terminal_of(s) for s in terminals])
     with torch.cuda.device(dev):
-        rc = eng.lib.ka_ctc_label_posteriors_batch_f32(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size), int(max_move),
-                                                       p_term, p_occ, p_ldo, ll.ctypes.data, status.ctypes.data, _lib.KA_MEM_DEVICE,
-                                                       _stream_ptr(dev_index))
-    results = [(o, float(z)) for o, z in zip(out, ll)]
-    if return_status:
-        if rc not in _POSTERIOR_LATTICE_STATUSES:
-            _lib.check(rc, "ctc_label_posteriors_device")
-        return results, status.tolist()
-    _lib.check(rc, "ctc_label_posteriors_device")
-    return results
+        return _run_lattices(eng, "ka_ctc_label_posteriors_batch_f32", "ctc_label_posteriors_device", [x.data_ptr() for x in lps],
+                             [x.shape[0] for x in lps], V, [x.stride(0) for x in lps], [x.data_ptr() for x in labs],
+                             [x.shape[0] for x in labs], beam_size, max_move, (p_term, p_occ, p_ldo), out, _lib.KA_MEM_DEVICE,
+                             _stream_ptr(dev_index), return_status)
 
 
 def _lattice_ll_function():

@@ -563,31 +563,131 @@ void redo_declined(ka_engine *e, const std::vector<ka_engine::Redo> &again, std:
     }
 }
 
-// ---- best-path posteriors (ka_posterior.hpp): their own kernels and workspace layout, whatever the engine's mode ----
-int posteriors_impl(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
-                    const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move, const int32_t *const *best_path,
-                    float *const *posteriors, double *log_likelihood, int32_t *status, int32_t mem, hipStream_t stream)
+// ---- best-path posteriors (ka_posterior.hpp) and label occupancy (ka_occupancy.hpp): their own kernels and workspace layout,
+// whatever the engine's mode.  One driver, fb_impl; a call (PostCall, OccCall) brings what differs: its own arrays and their
+// checks, its planner and launch, the descriptor fields beyond FbLattice, its own staging, and what two statuses mean.
+struct FbArgs {
+    int32_t n;
+    const float *const *log_probs;
+    const int64_t *T;
+    int32_t V;
+    const int64_t *ld;
+    const int32_t *const *labels;
+    const int64_t *S;
+    int32_t beam_size, max_move;
+    double *log_likelihood;
+    int32_t *status;
+    int32_t mem;
+    hipStream_t stream;
+};
+
+struct PostCall {
+    using Desc = ka::PostLattice;
+    using Carve = ka::plan::PostCarve;
+    static constexpr const char *kName = "posteriors";
+    static constexpr const char *kBadArgs = ": a best-path position outside [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score reaches the best path's terminal";
+    const int32_t *const *best_path;
+    float *const *posteriors;
+
+    bool arrays() const { return best_path && posteriors; }
+    const char *bad_lattice(const FbArgs &, int32_t) const { return nullptr; }
+    bool buffers(int32_t i) const { return best_path[i] && posteriors[i]; }
+    static constexpr auto plan = ka::plan::posterior_workspace;
+    static constexpr auto launch = ka::launch_posteriors;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (a.mem == KA_MEM_HOST) {
+            d.path = reinterpret_cast<const int32_t *>(ws + c.path);
+            d.post = reinterpret_cast<float *>(ws + c.post);
+        } else {
+            d.path = best_path[i];
+            d.post = posteriors[i];
+        }
+        d.ck = reinterpret_cast<double *>(ws + c.ck);
+        d.col = reinterpret_cast<double *>(ws + c.col);
+    }
+    int upload(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        KA_HIP(hipMemcpyAsync(ws + c.path, best_path[i], (size_t)a.T[i] * 4, hipMemcpyHostToDevice, a.stream));
+        return KA_OK;
+    }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        KA_HIP(hipMemcpyAsync(posteriors[i], ws + c.post, (size_t)a.T[i] * 4, hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
+struct OccCall {
+    using Desc = ka::OccLattice;
+    using Carve = ka::plan::OccCarve;
+    static constexpr const char *kName = "label posteriors";
+    static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score reaches the terminal";
+    const int64_t *terminal;
+    float *const *occupancy;
+    const int64_t *ld_out;
+
+    bool arrays() const { return terminal && occupancy && ld_out; }
+    const char *bad_lattice(const FbArgs &a, int32_t i) const { return ld_out[i] < a.V ? ": ld_out < V" : nullptr; }
+    bool buffers(int32_t i) const { return occupancy[i] != nullptr; }
+    static constexpr auto plan = ka::plan::label_posterior_workspace;
+    static constexpr auto launch = ka::launch_label_posteriors;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (a.mem == KA_MEM_HOST) {
+            d.occ = reinterpret_cast<float *>(ws + c.occ);
+            d.ld_out = a.V;
+        } else {
+            d.occ = occupancy[i];
+            d.ld_out = ld_out[i];
+        }
+        d.ck = reinterpret_cast<double *>(ws + c.slot + c.parts.ck);
+        d.ckcol = reinterpret_cast<double *>(ws + c.slot + c.parts.ckcol);
+        d.slab = reinterpret_cast<double *>(ws + c.slot + c.parts.slab);
+        d.col = reinterpret_cast<double *>(ws + c.slot + c.parts.col);
+        d.gbin = reinterpret_cast<unsigned long long *>(ws + c.slot + c.parts.gbin);
+        d.terminal = (terminal[i] >= 0 && terminal[i] <= INT32_MAX) ? (int32_t)terminal[i] : -1;
+        d.cw = c.parts.cw;
+    }
+    int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        KA_HIP(hipMemcpy2DAsync(occupancy[i], (size_t)ld_out[i] * 4, ws + c.occ, (size_t)a.V * 4, (size_t)a.V * 4, (size_t)a.T[i],
+                                hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
+template <class Call>
+int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
 {
+    using Desc = typename Call::Desc;
+    const int32_t n = a.n, V = a.V;
+    const hipStream_t stream = a.stream;
+    const bool host = a.mem == KA_MEM_HOST;
     if (!e) return fail(KA_ERR_BAD_ARGS, "engine is NULL");
     if (e->pending) return fail(KA_ERR_BAD_ARGS, "a batch is already enqueued: call ka_batch_finish first");
-    if (n < 0 || (n > 0 && (!log_probs || !T || !ld || !labels || !S || !best_path || !posteriors)))
-        return fail(KA_ERR_BAD_ARGS, "posteriors: NULL array argument");
-    if (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE) return fail(KA_ERR_BAD_ARGS, "mem must be KA_MEM_HOST or KA_MEM_DEVICE");
+    if (n < 0 || (n > 0 && (!a.log_probs || !a.T || !a.ld || !a.labels || !a.S || !call.arrays())))
+        return fail(KA_ERR_BAD_ARGS, std::string(Call::kName) + ": NULL array argument");
+    if (a.mem != KA_MEM_HOST && a.mem != KA_MEM_DEVICE) return fail(KA_ERR_BAD_ARGS, "mem must be KA_MEM_HOST or KA_MEM_DEVICE");
     if (n == 0) return KA_OK;
-    std::vector<ka::plan::PostCarve> cv(n);
+    std::vector<typename Call::Carve> cv(n);
     size_t off_res = 0;
-    const size_t total = ka::plan::posterior_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, cv.data(), &off_res);
-    if (total == 0) return fail(KA_ERR_BAD_ARGS, "posteriors: unsupported T/S/V/beam_size/max_move");
+    const size_t total = Call::plan(n, a.T, a.S, V, a.beam_size, a.max_move, host, cv.data(), &off_res);
+    if (total == 0) return fail(KA_ERR_BAD_ARGS, std::string(Call::kName) + ": unsupported T/S/V/beam_size/max_move");
     for (int32_t i = 0; i < n; ++i) {
-        if (ld[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld < V");
-        if (!log_probs[i] || !best_path[i] || !posteriors[i] || (S[i] > 0 && !labels[i]))
+        if (a.ld[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld < V");
+        if (const char *why = call.bad_lattice(a, i)) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + why);
+        if (!a.log_probs[i] || !call.buffers(i) || (a.S[i] > 0 && !a.labels[i]))
             return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": NULL buffer");
     }
     DeviceGuard guard;
     KA_HIP(guard.enter(e->device));
     int rc = ensure_ws(e, total);
     if (rc != KA_OK) return rc;
-    const size_t desc_bytes = align_up((size_t)n * sizeof(ka::PostLattice));
+    const size_t desc_bytes = align_up((size_t)n * sizeof(Desc));
     rc = ensure_pin(e, desc_bytes + (size_t)n * sizeof(ka::PostResult));
     if (rc != KA_OK) return rc;
     // the workspace is shared with the best-path calls: wait for the refill behind their last tile launch, and what it left
@@ -595,175 +695,63 @@ int posteriors_impl(ka_engine *e, int32_t n, const float *const *log_probs, cons
     if (e->refill_done) KA_HIP(hipStreamWaitEvent(stream, e->refill_done, 0));
     e->clean_lo = e->clean_hi = 0;
     e->dbg_entry_n = e->dbg_map0_bytes = e->dbg_n_tasks = 0;
-    // descriptors: fast-form lattices first, then the generic ones
-    ka::PostLattice *h = reinterpret_cast<ka::PostLattice *>(e->pin);
-    ka::PostResult *h_res = reinterpret_cast<ka::PostResult *>(e->pin + desc_bytes);
-    int32_t n_fast = 0;
-    for (int32_t i = 0; i < n; ++i) n_fast += ka::plan::posterior_fast(S[i], V, beam_size, max_move) ? 1 : 0;
-    int32_t k_fast = 0, k_gen = 0;
-    for (int32_t i = 0; i < n; ++i) {
-        const bool fast = ka::plan::posterior_fast(S[i], V, beam_size, max_move);
-        ka::PostLattice &d = h[fast ? k_fast++ : n_fast + k_gen++];
-        std::memset(&d, 0, sizeof(d));
-        const ka::plan::PostCarve &c = cv[i];
-        if (mem == KA_MEM_HOST) {
-            d.lp = reinterpret_cast<const float *>(e->ws + c.lp);
-            d.labels = reinterpret_cast<const int32_t *>(e->ws + c.lab);
-            d.path = reinterpret_cast<const int32_t *>(e->ws + c.path);
-            d.post = reinterpret_cast<float *>(e->ws + c.post);
-            d.ld = V;
-        } else {
-            d.lp = log_probs[i];
-            d.labels = labels[i];
-            d.path = best_path[i];
-            d.post = posteriors[i];
-            d.ld = ld[i];
-        }
-        d.ck = reinterpret_cast<double *>(e->ws + c.ck);
-        d.col = reinterpret_cast<double *>(e->ws + c.col);
-        d.T = (int32_t)T[i];
-        d.S = (int32_t)S[i];
-        d.L = (int32_t)(2 * S[i] + 1);
-        d.V = V;
-        d.beam = beam_size;
-        d.max_move = max_move;
-        d.idx = i;
-    }
-    if (mem == KA_MEM_HOST)
-        for (int32_t i = 0; i < n; ++i) {
-            KA_HIP(hipMemcpy2DAsync(e->ws + cv[i].lp, (size_t)V * 4, log_probs[i], (size_t)ld[i] * 4, (size_t)V * 4, (size_t)T[i],
-                                    hipMemcpyHostToDevice, stream));
-            if (S[i] > 0) KA_HIP(hipMemcpyAsync(e->ws + cv[i].lab, labels[i], (size_t)S[i] * 4, hipMemcpyHostToDevice, stream));
-            KA_HIP(hipMemcpyAsync(e->ws + cv[i].path, best_path[i], (size_t)T[i] * 4, hipMemcpyHostToDevice, stream));
-        }
-    ka::PostLattice *d_lats = reinterpret_cast<ka::PostLattice *>(e->ws);
-    ka::PostResult *d_res = reinterpret_cast<ka::PostResult *>(e->ws + off_res);
-    KA_HIP(hipMemcpyAsync(d_lats, h, (size_t)n * sizeof(ka::PostLattice), hipMemcpyHostToDevice, stream));
-    ka::launch_posteriors(d_lats, n_fast, n - n_fast, max_move, d_res, stream);
-    KA_HIP(hipGetLastError());
-    KA_HIP(hipMemcpyAsync(h_res, d_res, (size_t)n * sizeof(ka::PostResult), hipMemcpyDeviceToHost, stream));
-    if (mem == KA_MEM_HOST)
-        for (int32_t i = 0; i < n; ++i)
-            KA_HIP(hipMemcpyAsync(posteriors[i], e->ws + cv[i].post, (size_t)T[i] * 4, hipMemcpyDeviceToHost, stream));
-    KA_HIP(hipStreamSynchronize(stream));
-    int first_bad = KA_OK;
-    for (int32_t i = 0; i < n; ++i) {
-        const int32_t st = h_res[i].status;
-        if (status) status[i] = st;
-        if (log_likelihood) log_likelihood[i] = h_res[i].log_likelihood;
-        if (st != KA_OK && first_bad == KA_OK) {
-            first_bad = st;
-            g_err = "lattice " + std::to_string(i) + (st == KA_ERR_BAD_LABEL   ? ": label outside [0, V)"
-                                                      : st == KA_ERR_NAN       ? ": a log-prob is NaN"
-                                                      : st == KA_ERR_NONFINITE ? ": a log-prob is +inf"
-                                                      : st == KA_ERR_BAD_ARGS  ? ": a best-path position outside [0, 2S+1)"
-                                                      : st == KA_ERR_ZERO_MASS ? ": no path of finite score reaches the best path's terminal"
-                                                                               : ": failed");
-        }
-    }
-    return first_bad;
-}
-
-// ---- label occupancy posteriors (ka_occupancy.hpp): their own kernels and workspace layout, whatever the engine's mode ----
-int label_posteriors_impl(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
-                          const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move, const int64_t *terminal,
-                          float *const *occupancy, const int64_t *ld_out, double *log_likelihood, int32_t *status, int32_t mem,
-                          hipStream_t stream)
-{
-    if (!e) return fail(KA_ERR_BAD_ARGS, "engine is NULL");
-    if (e->pending) return fail(KA_ERR_BAD_ARGS, "a batch is already enqueued: call ka_batch_finish first");
-    if (n < 0 || (n > 0 && (!log_probs || !T || !ld || !labels || !S || !terminal || !occupancy || !ld_out)))
-        return fail(KA_ERR_BAD_ARGS, "label posteriors: NULL array argument");
-    if (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE) return fail(KA_ERR_BAD_ARGS, "mem must be KA_MEM_HOST or KA_MEM_DEVICE");
-    if (n == 0) return KA_OK;
-    std::vector<ka::plan::OccCarve> cv(n);
-    size_t off_res = 0;
-    const size_t total = ka::plan::label_posterior_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, cv.data(), &off_res);
-    if (total == 0) return fail(KA_ERR_BAD_ARGS, "label posteriors: unsupported T/S/V/beam_size/max_move");
-    for (int32_t i = 0; i < n; ++i) {
-        if (ld[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld < V");
-        if (ld_out[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld_out < V");
-        if (!log_probs[i] || !occupancy[i] || (S[i] > 0 && !labels[i]))
-            return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": NULL buffer");
-    }
-    DeviceGuard guard;
-    KA_HIP(guard.enter(e->device));
-    int rc = ensure_ws(e, total);
-    if (rc != KA_OK) return rc;
-    const size_t desc_bytes = align_up((size_t)n * sizeof(ka::OccLattice));
-    rc = ensure_pin(e, desc_bytes + (size_t)n * sizeof(ka::PostResult));
-    if (rc != KA_OK) return rc;
-    // the workspace is shared with the best-path calls (see posteriors_impl)
-    if (e->refill_done) KA_HIP(hipStreamWaitEvent(stream, e->refill_done, 0));
-    e->clean_lo = e->clean_hi = 0;
-    e->dbg_entry_n = e->dbg_map0_bytes = e->dbg_n_tasks = 0;
-    // descriptors: fast-form lattices first, then the generic ones, each in batch order (the order their slots assume)
-    ka::OccLattice *h = reinterpret_cast<ka::OccLattice *>(e->pin);
+    // descriptors: fast-form lattices first, then the generic ones, each in batch order (the order occupancy slots assume)
+    Desc *h = reinterpret_cast<Desc *>(e->pin);
     ka::PostResult *h_res = reinterpret_cast<ka::PostResult *>(e->pin + desc_bytes);
     int32_t n_fast = 0;
     for (int32_t i = 0; i < n; ++i) n_fast += cv[i].fast ? 1 : 0;
     int32_t k_fast = 0, k_gen = 0;
     for (int32_t i = 0; i < n; ++i) {
-        const ka::plan::OccCarve &c = cv[i];
-        ka::OccLattice &d = h[c.fast ? k_fast++ : n_fast + k_gen++];
+        const auto &c = cv[i];
+        Desc &d = h[c.fast ? k_fast++ : n_fast + k_gen++];
         std::memset(&d, 0, sizeof(d));
-        if (mem == KA_MEM_HOST) {
+        if (host) {
             d.lp = reinterpret_cast<const float *>(e->ws + c.lp);
             d.labels = reinterpret_cast<const int32_t *>(e->ws + c.lab);
-            d.occ = reinterpret_cast<float *>(e->ws + c.occ);
             d.ld = V;
-            d.ld_out = V;
         } else {
-            d.lp = log_probs[i];
-            d.labels = labels[i];
-            d.occ = occupancy[i];
-            d.ld = ld[i];
-            d.ld_out = ld_out[i];
+            d.lp = a.log_probs[i];
+            d.labels = a.labels[i];
+            d.ld = a.ld[i];
         }
-        d.ck = reinterpret_cast<double *>(e->ws + c.slot + c.parts.ck);
-        d.ckcol = reinterpret_cast<double *>(e->ws + c.slot + c.parts.ckcol);
-        d.slab = reinterpret_cast<double *>(e->ws + c.slot + c.parts.slab);
-        d.col = reinterpret_cast<double *>(e->ws + c.slot + c.parts.col);
-        d.gbin = reinterpret_cast<unsigned long long *>(e->ws + c.slot + c.parts.gbin);
-        d.T = (int32_t)T[i];
-        d.S = (int32_t)S[i];
-        d.L = (int32_t)(2 * S[i] + 1);
+        d.T = (int32_t)a.T[i];
+        d.S = (int32_t)a.S[i];
+        d.L = (int32_t)(2 * a.S[i] + 1);
         d.V = V;
-        d.beam = beam_size;
-        d.max_move = max_move;
-        d.terminal = (terminal[i] >= 0 && terminal[i] <= INT32_MAX) ? (int32_t)terminal[i] : -1;
-        d.cw = c.parts.cw;
+        d.beam = a.beam_size;
+        d.max_move = a.max_move;
         d.idx = i;
+        call.fill(d, c, a, i, e->ws);
     }
-    if (mem == KA_MEM_HOST)
+    if (host)
         for (int32_t i = 0; i < n; ++i) {
-            KA_HIP(hipMemcpy2DAsync(e->ws + cv[i].lp, (size_t)V * 4, log_probs[i], (size_t)ld[i] * 4, (size_t)V * 4, (size_t)T[i],
+            KA_HIP(hipMemcpy2DAsync(e->ws + cv[i].lp, (size_t)V * 4, a.log_probs[i], (size_t)a.ld[i] * 4, (size_t)V * 4, (size_t)a.T[i],
                                     hipMemcpyHostToDevice, stream));
-            if (S[i] > 0) KA_HIP(hipMemcpyAsync(e->ws + cv[i].lab, labels[i], (size_t)S[i] * 4, hipMemcpyHostToDevice, stream));
+            if (a.S[i] > 0) KA_HIP(hipMemcpyAsync(e->ws + cv[i].lab, a.labels[i], (size_t)a.S[i] * 4, hipMemcpyHostToDevice, stream));
+            if ((rc = call.upload(cv[i], a, i, e->ws)) != KA_OK) return rc;
         }
-    ka::OccLattice *d_lats = reinterpret_cast<ka::OccLattice *>(e->ws);
+    Desc *d_lats = reinterpret_cast<Desc *>(e->ws);
     ka::PostResult *d_res = reinterpret_cast<ka::PostResult *>(e->ws + off_res);
-    KA_HIP(hipMemcpyAsync(d_lats, h, (size_t)n * sizeof(ka::OccLattice), hipMemcpyHostToDevice, stream));
-    ka::launch_label_posteriors(d_lats, n_fast, n - n_fast, max_move, d_res, stream);
+    KA_HIP(hipMemcpyAsync(d_lats, h, (size_t)n * sizeof(Desc), hipMemcpyHostToDevice, stream));
+    Call::launch(d_lats, n_fast, n - n_fast, a.max_move, d_res, stream);
     KA_HIP(hipGetLastError());
     KA_HIP(hipMemcpyAsync(h_res, d_res, (size_t)n * sizeof(ka::PostResult), hipMemcpyDeviceToHost, stream));
-    if (mem == KA_MEM_HOST)
+    if (host)
         for (int32_t i = 0; i < n; ++i)
-            KA_HIP(hipMemcpy2DAsync(occupancy[i], (size_t)ld_out[i] * 4, e->ws + cv[i].occ, (size_t)V * 4, (size_t)V * 4, (size_t)T[i],
-                                    hipMemcpyDeviceToHost, stream));
+            if ((rc = call.download(cv[i], a, i, e->ws)) != KA_OK) return rc;
     KA_HIP(hipStreamSynchronize(stream));
     int first_bad = KA_OK;
     for (int32_t i = 0; i < n; ++i) {
         const int32_t st = h_res[i].status;
-        if (status) status[i] = st;
-        if (log_likelihood) log_likelihood[i] = h_res[i].log_likelihood;
+        if (a.status) a.status[i] = st;
+        if (a.log_likelihood) a.log_likelihood[i] = h_res[i].log_likelihood;
         if (st != KA_OK && first_bad == KA_OK) {
             first_bad = st;
             g_err = "lattice " + std::to_string(i) + (st == KA_ERR_BAD_LABEL   ? ": label outside [0, V)"
                                                       : st == KA_ERR_NAN       ? ": a log-prob is NaN"
                                                       : st == KA_ERR_NONFINITE ? ": a log-prob is +inf"
-                                                      : st == KA_ERR_BAD_ARGS  ? ": terminal outside [0, 2S+1)"
-                                                      : st == KA_ERR_ZERO_MASS ? ": no path of finite score reaches the terminal"
+                                                      : st == KA_ERR_BAD_ARGS  ? Call::kBadArgs
+                                                      : st == KA_ERR_ZERO_MASS ? Call::kZeroMass
                                                                                : ": failed");
         }
     }
@@ -1032,16 +1020,16 @@ int ka_ctc_path_posteriors_batch_f32(ka_engine *e, int32_t n, const float *const
                                      const int32_t *const *best_path, float *const *posteriors, double *log_likelihood, int32_t *status,
                                      int32_t mem, void *stream)
 {
-    return posteriors_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, best_path, posteriors, log_likelihood, status, mem,
-                           (hipStream_t)stream);
+    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+                   PostCall{best_path, posteriors});
 }
 
 int ka_ctc_path_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
                                int32_t beam_size, int32_t max_move, const int32_t *best_path, float *posteriors, double *log_likelihood,
                                int32_t mem, void *stream)
 {
-    return posteriors_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &best_path, &posteriors, log_likelihood, nullptr,
-                           mem, (hipStream_t)stream);
+    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+                   PostCall{&best_path, &posteriors});
 }
 
 size_t ka_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
@@ -1055,16 +1043,16 @@ int ka_ctc_label_posteriors_batch_f32(ka_engine *e, int32_t n, const float *cons
                                       const int64_t *terminal, float *const *occupancy, const int64_t *ld_out, double *log_likelihood,
                                       int32_t *status, int32_t mem, void *stream)
 {
-    return label_posteriors_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, terminal, occupancy, ld_out, log_likelihood,
-                                 status, mem, (hipStream_t)stream);
+    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+                   OccCall{terminal, occupancy, ld_out});
 }
 
 int ka_ctc_label_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
                                 int32_t beam_size, int32_t max_move, int64_t terminal, float *occupancy, int64_t ld_out,
                                 double *log_likelihood, int32_t mem, void *stream)
 {
-    return label_posteriors_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &terminal, &occupancy, &ld_out,
-                                 log_likelihood, nullptr, mem, (hipStream_t)stream);
+    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+                   OccCall{&terminal, &occupancy, &ld_out});
 }
 
 size_t ka_label_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,

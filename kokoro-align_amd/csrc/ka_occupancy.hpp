@@ -6,8 +6,8 @@
 // which is also dZ / d log_probs[t, v].  The posterior kernels keep alpha only at the path; this backward pass needs it at
 // every band cell, so the forward pass checkpoints the whole column before the first frame of every 32-frame block (with
 // the offset C and the frame maximum m it runs on), and the backward pass, last block first, recomputes the block's alpha
-// from its checkpoint into a per-slot slab with the forward pass's own frame function, then steps beta back through the
-// block.  The recompute runs the same instructions on the same operands: its alpha is the forward pass's bit for bit, so
+// from its checkpoint into a per-slot slab with the forward pass's own frame function (fb_fast_fwd / fb_gen_fwd of
+// ka_posterior_common.hpp), then steps beta back through the block (fb_fast_bwd / fb_gen_bwd).  The recompute runs the same instructions on the same operands: its alpha is the forward pass's bit for bit, so
 // gamma at (T-1, s*) is 2^0 exactly.
 // Binning: gamma is formed in double, rounded to float and raised by the hardware exp2 (an output in [0, 1] needs no more),
 // then added as an unsigned 32.32 fixed-point integer, so the row's bits do not depend on the order of the adds: blank cells
@@ -38,8 +38,7 @@ __device__ __forceinline__ unsigned long long occ_wave_sum(unsigned long long x)
     for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
     return x;
 }
-__device__ __forceinline__ int32_t occ_lab(const OccLattice &d, int64_t p) { return (p & 1) ? d.labels[p >> 1] : 0; }
-// a lattice without a result: NaN rows; log-likelihood NaN, or -inf for kStatusZeroMass
+// a lattice without a result: NaN rows, and the status and log-likelihood of fb_fail_result
 __device__ __forceinline__ void occ_fail(const OccLattice &d, PostResult *res, int status)
 {
     const int64_t n = (int64_t)d.T * d.V;
@@ -47,19 +46,7 @@ __device__ __forceinline__ void occ_fail(const OccLattice &d, PostResult *res, i
         const int64_t t = k / d.V, v = k - t * d.V;
         reinterpret_cast<uint32_t *>(d.occ)[t * d.ld_out + v] = 0x7fc00000u;
     }
-    if (threadIdx.x == 0) {
-        res[d.idx].status = status;
-        *reinterpret_cast<uint64_t *>(&res[d.idx].log_likelihood) = status == kStatusZeroMass ? kNinf64 : kNaN64;
-    }
-}
-__device__ __forceinline__ bool occ_labels_bad(const OccLattice &d)
-{
-    int bad = 0;
-    for (int i = threadIdx.x; i < d.S; i += blockDim.x) {
-        const int l = d.labels[i];
-        bad |= (l < 0 || l >= d.V) ? 1 : 0;
-    }
-    return __syncthreads_or(bad) != 0;
+    fb_fail_result(d, res, status);
 }
 // Z as ka_posterior.hpp forms it (the block offset plus the float-stored relative alpha), in nats: the value the
 // path-posterior call returns for a path that ends at s*
@@ -70,62 +57,37 @@ __device__ __forceinline__ double occ_reported_z(double cb, double ca, double us
 
 // ---------------------------------------------------------------------------------------
 // fast form: one wavefront per lattice, band <= kFastMaxBand, V <= 64, M = max_move <= 4; the cell layout of
-// posterior_fast_kernel (position p at slot p & 1023 of an LDS column; lane l owns lo + l + 64 k)
+// posterior_fast_kernel (position p at slot p & 1023 of an LDS column; lane l owns lo + l + 64 k).  The forward pass and
+// the recompute both run fb_fast_fwd with the same label source, so the two produce the same bits.
 // ---------------------------------------------------------------------------------------
-// One forward frame: u_t over [lo, hi) from u_{t-1} over [plo, phi).  Both the forward pass and the recompute call this, so
-// the two produce the same bits.  Returns the lane's maximum.
-template <int M>
-__device__ __forceinline__ double occ_fast_fwd(const OccLattice &d, int64_t lo, int64_t hi, int64_t plo, int64_t phi, const double *prev,
-                                              double *cur, const double *row, double mprev, double *alpha_out)
-{
-    const double NINF = post_dninf();
-    double mymax = NINF;
-    for (int64_t p = lo + threadIdx.x; p < hi; p += 64) {
-        const int32_t lab = occ_lab(d, p);
-        const double e = row[lab];
-        double x[M];
-        double mx = NINF;
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-            const int64_t u = p - j;
-            const bool ok = u >= plo && u < phi && !(j >= 2 && (j & 1) == 0 && lab == 0);
-            x[j] = ok ? prev[u & 1023] : NINF;
-            mx = fmaxf(mx, x[j]);
-        }
-        const double val = post_lse2(x, M, mx) + (e - mprev);
-        cur[p & 1023] = val;
-        if (alpha_out) alpha_out[p & 1023] = val;
-        mymax = fmaxf(mymax, val);
-    }
-    return mymax;
-}
-
 template <int M>
 __device__ __forceinline__ void occ_fast_one(const OccLattice &d, PostResult *res, double (*col)[1024], double *row, double *cav,
                                              unsigned long long *bins)
 {
     const int lane = threadIdx.x;
     const int64_t T = d.T, L = d.L, B = d.beam, V = d.V;
-    const int64_t dq = L / T, dr = L % T;
     const size_t ld = (size_t)d.ld;
     const double NINF = post_dninf();
-    if (occ_labels_bad(d)) {
+    if (fb_labels_bad(d)) {
         occ_fail(d, res, kStatusBadLabel);
         return;
     }
     bins[lane] = 0;
+    auto lab_of = [&](int64_t p) { return fb_lab(d, p); };
+    auto no_cell = [](int64_t, double) {};
 
     // ---- forward: Z, and a checkpoint before every block ----
     double *prev = col[0], *cur = col[1];
     if (lane == 0) prev[0] = 0.0;   // virtual state before frame 0
-    int64_t plo = 0, phi = 1, q = 0, r = 0;
+    int64_t plo = 0, phi = 1;
+    BandWalk bw(L, B, T);
     double C = 0.0, Cb = 0.0, Ca = 0.0, mprev = 0.0;
     int flags = 0;
     float rv = lane < V ? d.lp[lane] : 0.0f;
     post_wave_sync();
     for (int64_t t = 0; t < T; ++t) {
         int64_t lo, hi;
-        post_band(q, L, B, lo, hi);
+        bw.band(lo, hi);
         if (lane < V) {
             flags |= post_bad_bits(rv);
             row[lane] = (double)rv * kLog2e64;
@@ -141,7 +103,7 @@ __device__ __forceinline__ void occ_fast_one(const OccLattice &d, PostResult *re
             for (int s = lane; s < 1024; s += 64) d.ckcol[k * 1024 + s] = prev[s];
         }
         post_wave_sync();
-        double m = post_wave_max(occ_fast_fwd<M>(d, lo, hi, plo, phi, prev, cur, row, mprev, nullptr));
+        double m = post_wave_max(fb_fast_fwd<M>(lo, hi, plo, phi, prev, cur, row, mprev, lab_of, no_cell));
         m = (m == NINF) ? 0.0 : m;
         Ca = C;
         C += m;
@@ -149,9 +111,7 @@ __device__ __forceinline__ void occ_fast_one(const OccLattice &d, PostResult *re
         { double *x = prev; prev = cur; cur = x; }
         plo = lo;
         phi = hi;
-        q += dq;
-        r += dr;
-        if (r >= T) { r -= T; ++q; }
+        bw.next();
         post_wave_sync();
     }
     const int64_t sstar = d.terminal;
@@ -181,68 +141,50 @@ __device__ __forceinline__ void occ_fast_one(const OccLattice &d, PostResult *re
         for (int s = lane; s < 1024; s += 64) pv[s] = d.ckcol[k * 1024 + s];
         double C2 = d.ck[2 * k], mp = d.ck[2 * k + 1];
         int64_t rlo = 0, rhi = 1;
-        if (t0 > 0) post_band((L * (t0 - 1)) / T, L, B, rlo, rhi);
-        int64_t q2 = (L * t0) / T, r2 = (L * t0) % T;
+        bw.seek(t0);
+        if (t0 > 0) {
+            bw.prev();
+            bw.band(rlo, rhi);
+            bw.next();
+        }
         float rv2 = lane < V ? d.lp[(size_t)t0 * ld + lane] : 0.0f;
         post_wave_sync();
         for (int64_t t = t0; t < t1; ++t) {
             int64_t lo, hi;
-            post_band(q2, L, B, lo, hi);
+            bw.band(lo, hi);
             if (lane < V) row[lane] = (double)rv2 * kLog2e64;
             if (t + 1 < t1 && lane < V) rv2 = d.lp[(size_t)(t + 1) * ld + lane];
             if (lane == 0) cav[t - t0] = C2;
             post_wave_sync();
-            double m = post_wave_max(occ_fast_fwd<M>(d, lo, hi, rlo, rhi, pv, cu, row, mp, d.slab + (t - t0) * 1024));
+            double *al = d.slab + (t - t0) * 1024;
+            double m = post_wave_max(fb_fast_fwd<M>(lo, hi, rlo, rhi, pv, cu, row, mp, lab_of, [&](int64_t p, double val) { al[p & 1023] = val; }));
             m = (m == NINF) ? 0.0 : m;
             C2 += m;
             mp = m;
             { double *x = pv; pv = cu; cu = x; }
             rlo = lo;
             rhi = hi;
-            q2 += dq;
-            r2 += dr;
-            if (r2 >= T) { r2 -= T; ++q2; }
+            bw.next();
             post_wave_sync();
         }
-        // beta back through the block; gamma binned per frame
+        // beta back through the block (bw walks back from t1); gamma binned per frame
         float rv3 = lane < V ? d.lp[(size_t)(t1 - 1) * ld + lane] : 0.0f;
         for (int64_t t = t1 - 1; t >= t0; --t) {
+            bw.prev();
             int64_t lo, hi;
-            post_band((L * t) / T, L, B, lo, hi);
+            bw.band(lo, hi);
             if (lane < V) row[lane] = (double)rv3 * kLog2e64;
             if (t > t0 && lane < V) rv3 = d.lp[(size_t)(t - 1) * ld + lane];
             const double ca = cav[t - t0];
             const double *al = d.slab + (t - t0) * 1024;
-            const bool last = t == T - 1;
             post_wave_sync();
-            double mymax = NINF;
             unsigned long long blank = 0;
-            for (int64_t p = lo + lane; p < hi; p += 64) {
-                const int32_t lab = occ_lab(d, p);
-                double w;
-                if (last) {
-                    w = (p == sstar) ? 0.0 : NINF;
-                } else {
-                    double x[M];
-                    double mx = NINF;
-#pragma unroll
-                    for (int j = 0; j < M; ++j) {
-                        const int64_t u = p + j;
-                        const bool ok = u >= nlo && u < nhi;
-                        const double g = (j >= 2 && (j & 1) == 0) ? vn[u & 1023] : gn[u & 1023];
-                        x[j] = ok ? g : NINF;
-                        mx = fmaxf(mx, x[j]);
-                    }
-                    w = post_lse2(x, M, mx) - nprev;
-                }
-                const double g = w + row[lab];
-                gc[p & 1023] = g;
-                vc[p & 1023] = lab == 0 ? NINF : g;
-                mymax = fmaxf(mymax, g);
-                const unsigned long long f = occ_fix(((ca + al[p & 1023]) + (D + w)) - Z);
-                if ((p & 1) == 0) blank += f;
-                else if (f) atomicAdd(&bins[lab], f);
-            }
+            const double mymax = fb_fast_bwd<M>(lo, hi, nlo, nhi, gn, vn, gc, vc, row, nprev, t == T - 1, sstar, lab_of,
+                                                [&](int64_t p, int32_t lab, double w) {
+                                                    const unsigned long long f = occ_fix(((ca + al[p & 1023]) + (D + w)) - Z);
+                                                    if ((p & 1) == 0) blank += f;
+                                                    else if (f) atomicAdd(&bins[lab], f);
+                                                });
             blank = occ_wave_sum(blank);
             double n = post_wave_max(mymax);
             n = (n == NINF) ? 0.0 : n;
@@ -284,43 +226,14 @@ __global__ __launch_bounds__(64) void occupancy_fast_kernel(const OccLattice *__
 // generic form: any band, any V, max_move <= 255.  One 256-thread workgroup per lattice, working columns at absolute
 // positions in global memory, checkpoints and slab relative to the band's low end.  A correctness path, not tuned.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ double occ_gen_fwd(const OccLattice &d, const float *lrow, int64_t lo, int64_t hi, int64_t plo, int64_t phi,
-                                             const double *prev, double *cur, double mprev, double *alpha_out)
-{
-    const int M = d.max_move;
-    const double NINF = post_dninf();
-    double mymax = NINF;
-    for (int64_t p = lo + threadIdx.x; p < hi; p += 256) {
-        const int32_t lab = occ_lab(d, p);
-        const double e = (double)lrow[lab] * kLog2e64;
-        double mx = NINF;
-        for (int j = 0; j < M && j <= p; ++j) {
-            const int64_t u = p - j;
-            if (u >= plo && u < phi && !(j >= 2 && (j & 1) == 0 && lab == 0)) mx = fmaxf(mx, prev[u]);
-        }
-        double s = 0.0;
-        for (int j = 0; j < M && j <= p; ++j) {
-            const int64_t u = p - j;
-            if (u >= plo && u < phi && !(j >= 2 && (j & 1) == 0 && lab == 0)) s += exp2(prev[u] - mx);
-        }
-        const double l = mx == NINF ? NINF : mx + log2(s);
-        const double val = l + (e - mprev);
-        cur[p] = val;
-        if (alpha_out) alpha_out[p - lo] = val;
-        mymax = fmaxf(mymax, val);
-    }
-    return mymax;
-}
-
 __device__ __forceinline__ void occ_gen_one(const OccLattice &d, PostResult *res, double (*red)[4], double *cav, unsigned long long *lbins)
 {
     const int tid = threadIdx.x;
     const int64_t T = d.T, L = d.L, B = d.beam, V = d.V;
-    const int M = d.max_move;
-    const int64_t dq = L / T, dr = L % T, cw = d.cw;
+    const int64_t cw = d.cw;
     const size_t ld = (size_t)d.ld;
     const double NINF = post_dninf();
-    if (occ_labels_bad(d)) {
+    if (fb_labels_bad(d)) {
         occ_fail(d, res, kStatusBadLabel);
         return;
     }
@@ -328,17 +241,19 @@ __device__ __forceinline__ void occ_gen_one(const OccLattice &d, PostResult *res
     for (int64_t v = tid; v < V; v += 256) atomicExch(&bins[v], 0ull);
     double *A[4] = {d.col, d.col + L, d.col + 2 * L, d.col + 3 * L};
     int ph = 0;   // parity of the reduction slots
+    auto no_cell = [](int64_t, double) {};
 
     // ---- forward ----
     double *prev = A[0], *cur = A[1];
     if (tid == 0) prev[0] = 0.0;
-    int64_t plo = 0, phi = 1, q = 0, r = 0;
+    int64_t plo = 0, phi = 1;
+    BandWalk bw(L, B, T);
     double C = 0.0, Cb = 0.0, Ca = 0.0, mprev = 0.0;
     int flags = 0;
     __syncthreads();
     for (int64_t t = 0; t < T; ++t) {
         int64_t lo, hi;
-        post_band(q, L, B, lo, hi);
+        bw.band(lo, hi);
         const float *lrow = d.lp + (size_t)t * ld;
         for (int64_t v = tid; v < V; v += 256) flags |= post_bad_bits(lrow[v]);
         if (t % kPostCk == 0) {
@@ -350,7 +265,7 @@ __device__ __forceinline__ void occ_gen_one(const OccLattice &d, PostResult *res
             }
             for (int64_t p = plo + tid; p < phi; p += 256) d.ckcol[k * cw + (p - plo)] = prev[p];
         }
-        double m = post_block_max(occ_gen_fwd(d, lrow, lo, hi, plo, phi, prev, cur, mprev, nullptr), red[ph]);
+        double m = post_block_max(fb_gen_fwd(d, lrow, lo, hi, plo, phi, prev, cur, mprev, no_cell), red[ph]);
         ph ^= 1;
         m = (m == NINF) ? 0.0 : m;
         Ca = C;
@@ -359,9 +274,7 @@ __device__ __forceinline__ void occ_gen_one(const OccLattice &d, PostResult *res
         { double *x = prev; prev = cur; cur = x; }
         plo = lo;
         phi = hi;
-        q += dq;
-        r += dr;
-        if (r >= T) { r -= T; ++q; }
+        bw.next();
     }
     const int64_t sstar = d.terminal;
     flags |= (sstar < 0 || sstar >= L) ? 4 : 0;
@@ -387,16 +300,23 @@ __device__ __forceinline__ void occ_gen_one(const OccLattice &d, PostResult *res
         const int64_t t0 = k * kPostCk, t1 = (t0 + kPostCk < T) ? t0 + kPostCk : T;
         double *pv = gc, *cu = vc;
         int64_t rlo = 0, rhi = 1;
-        if (t0 > 0) post_band((L * (t0 - 1)) / T, L, B, rlo, rhi);
+        bw.seek(t0);
+        if (t0 > 0) {
+            bw.prev();
+            bw.band(rlo, rhi);
+            bw.next();
+        }
         for (int64_t p = rlo + tid; p < rhi; p += 256) pv[p] = d.ckcol[k * cw + (p - rlo)];
         double C2 = d.ck[2 * k], mp = d.ck[2 * k + 1];
-        int64_t q2 = (L * t0) / T, r2 = (L * t0) % T;
         __syncthreads();
         for (int64_t t = t0; t < t1; ++t) {
             int64_t lo, hi;
-            post_band(q2, L, B, lo, hi);
+            bw.band(lo, hi);
             if (tid == 0) cav[t - t0] = C2;
-            double m = post_block_max(occ_gen_fwd(d, d.lp + (size_t)t * ld, lo, hi, rlo, rhi, pv, cu, mp, d.slab + (t - t0) * cw), red[ph]);
+            double *al = d.slab + (t - t0) * cw;
+            double m = post_block_max(fb_gen_fwd(d, d.lp + (size_t)t * ld, lo, hi, rlo, rhi, pv, cu, mp,
+                                                 [&](int64_t p, double val) { al[p - lo] = val; }),
+                                      red[ph]);
             ph ^= 1;
             m = (m == NINF) ? 0.0 : m;
             C2 += m;
@@ -404,47 +324,22 @@ __device__ __forceinline__ void occ_gen_one(const OccLattice &d, PostResult *res
             { double *x = pv; pv = cu; cu = x; }
             rlo = lo;
             rhi = hi;
-            q2 += dq;
-            r2 += dr;
-            if (r2 >= T) { r2 -= T; ++q2; }
+            bw.next();
         }
         __syncthreads();
         for (int64_t t = t1 - 1; t >= t0; --t) {
+            bw.prev();
             int64_t lo, hi;
-            post_band((L * t) / T, L, B, lo, hi);
-            const float *lrow = d.lp + (size_t)t * ld;
+            bw.band(lo, hi);
             const double ca = cav[t - t0];
             const double *al = d.slab + (t - t0) * cw;
-            const bool last = t == T - 1;
-            double mymax = NINF;
             unsigned long long blank = 0;
-            for (int64_t p = lo + tid; p < hi; p += 256) {
-                const int32_t lab = occ_lab(d, p);
-                const double e = (double)lrow[lab] * kLog2e64;
-                double w;
-                if (last) {
-                    w = (p == sstar) ? 0.0 : NINF;
-                } else {
-                    double mx = NINF;
-                    for (int j = 0; j < M; ++j) {
-                        const int64_t u = p + j;
-                        if (u >= nlo && u < nhi) mx = fmaxf(mx, (j >= 2 && (j & 1) == 0) ? vn[u] : gn[u]);
-                    }
-                    double s = 0.0;
-                    for (int j = 0; j < M; ++j) {
-                        const int64_t u = p + j;
-                        if (u >= nlo && u < nhi) s += exp2(((j >= 2 && (j & 1) == 0) ? vn[u] : gn[u]) - mx);
-                    }
-                    w = (mx == NINF ? NINF : mx + log2(s)) - nprev;
-                }
-                const double g = w + e;
-                gc[p] = g;
-                vc[p] = lab == 0 ? NINF : g;
-                mymax = fmaxf(mymax, g);
-                const unsigned long long f = occ_fix(((ca + al[p - lo]) + (D + w)) - Z);
-                if ((p & 1) == 0) blank += f;
-                else if (f) atomicAdd(&bins[lab], f);
-            }
+            const double mymax = fb_gen_bwd(d, d.lp + (size_t)t * ld, lo, hi, nlo, nhi, gn, vn, gc, vc, nprev, t == T - 1, sstar,
+                                            [&](int64_t p, int32_t lab, double w) {
+                                                const unsigned long long f = occ_fix(((ca + al[p - lo]) + (D + w)) - Z);
+                                                if ((p & 1) == 0) blank += f;
+                                                else if (f) atomicAdd(&bins[lab], f);
+                                            });
             if (blank) atomicAdd(&bins[0], blank);
             double n = post_block_max(mymax, red[ph]);   // (its barrier also closes the frame's atomics)
             ph ^= 1;

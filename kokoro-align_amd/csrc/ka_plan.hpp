@@ -588,8 +588,20 @@ inline bool posterior_fast(int64_t S, int32_t V, int32_t beam, int32_t max_move)
 {
     return V <= 64 && max_move <= 4 && std::min<int64_t>(beam, 2 * S + 1) <= kFastMaxBand;
 }
-struct PostCarve {
-    size_t ck, col, lp, lab, path, post;
+// what both planners carve per lattice: its form, and for host buffers its staged log-probs [T, V] and labels [S]
+struct FbCarve {
+    size_t lp, lab;   // host buffers only
+    bool fast;
+};
+inline void carve_staged(size_t &off, const Shape &sh, int32_t V, FbCarve &c)
+{
+    c.lp = off;
+    off += align_up((size_t)sh.T * (size_t)V * 4);
+    c.lab = off;
+    off += align_up((size_t)sh.S * 4);
+}
+struct PostCarve : FbCarve {
+    size_t ck, col, path, post;
 };
 inline size_t posterior_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
                                   PostCarve *cv, size_t *off_res)
@@ -601,15 +613,13 @@ inline size_t posterior_workspace(int32_t n, const int64_t *T, const int64_t *S,
         Shape sh;
         if (!shape_of(T[i], S[i], V, beam, max_move, sh)) return 0;
         PostCarve c{};
+        c.fast = posterior_fast(sh.S, V, beam, max_move);
         c.ck = off;
         off += align_up((size_t)((sh.T - 1) / kPostCk + 1) * sizeof(double));
         c.col = off;
-        if (!posterior_fast(sh.S, V, beam, max_move)) off += align_up((size_t)sh.L * 4 * sizeof(double));
+        if (!c.fast) off += align_up((size_t)sh.L * 4 * sizeof(double));
         if (host_buffers) {
-            c.lp = off;
-            off += align_up((size_t)sh.T * (size_t)V * 4);
-            c.lab = off;
-            off += align_up((size_t)sh.S * 4);
+            carve_staged(off, sh, V, c);
             c.path = off;
             off += align_up((size_t)sh.T * 4);
             c.post = off;
@@ -656,11 +666,10 @@ inline OccParts occ_parts(const Shape &sh, int32_t V, int32_t beam, int32_t max_
     o.bytes = off;
     return o;
 }
-struct OccCarve {
-    size_t slot;            // base of this lattice's slot
-    size_t lp, lab, occ;    // host buffers only
+struct OccCarve : FbCarve {
+    size_t slot;   // base of this lattice's slot
+    size_t occ;    // host buffers only
     OccParts parts;
-    bool fast;
 };
 inline size_t label_posterior_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move,
                                         bool host_buffers, OccCarve *cv, size_t *off_res)
@@ -673,19 +682,14 @@ inline size_t label_posterior_workspace(int32_t n, const int64_t *T, const int64
     for (int32_t i = 0; i < n; ++i) {
         Shape sh;
         if (!shape_of(T[i], S[i], V, beam, max_move, sh)) return 0;
-        const OccParts o = occ_parts(sh, V, beam, max_move);
-        const bool fast = posterior_fast(sh.S, V, beam, max_move);
-        size_t &slot_bytes = fast ? fast_bytes : gen_bytes;
-        slot_bytes = std::max(slot_bytes, o.bytes);
         OccCarve c{};
-        c.parts = o;
-        c.fast = fast;
-        c.slot = (size_t)(fast ? n_fast++ : n_gen++);   // (the lattice's rank in its form until the slots are placed)
+        c.parts = occ_parts(sh, V, beam, max_move);
+        c.fast = posterior_fast(sh.S, V, beam, max_move);
+        size_t &slot_bytes = c.fast ? fast_bytes : gen_bytes;
+        slot_bytes = std::max(slot_bytes, c.parts.bytes);
+        c.slot = (size_t)(c.fast ? n_fast++ : n_gen++);   // (the lattice's rank in its form until the slots are placed)
         if (host_buffers) {
-            c.lp = off;
-            off += align_up((size_t)sh.T * (size_t)V * 4);
-            c.lab = off;
-            off += align_up((size_t)sh.S * 4);
+            carve_staged(off, sh, V, c);
             c.occ = off;
             off += align_up((size_t)sh.T * (size_t)V * 4);
         }

@@ -18,10 +18,20 @@
 // No alpha lattice is stored: the forward pass writes alpha_t(p_t) - C_{32k-1} (k = t / 32) into the caller's posterior
 // buffer as a float and C_{32k-1} into a double per 32 frames; the backward pass carries beta across the band and
 // overwrites the buffer with the posterior, combining the two halves and Z in double before the one exp.
+// The frame recurrences themselves are fb_fast_fwd / fb_fast_bwd and fb_gen_fwd / fb_gen_bwd of ka_posterior_common.hpp;
+// the kernels here bring the label ring, the prefetches and what happens at the path.
 #pragma once
 #include "ka_posterior_common.hpp"
 
 namespace ka {
+
+// a lattice without a result: NaN posteriors, and the status and log-likelihood of fb_fail_result
+__device__ __forceinline__ void post_fail(const PostLattice &d, PostResult *res, int status)
+{
+    uint32_t *post = reinterpret_cast<uint32_t *>(d.post);
+    for (int t = threadIdx.x; t < d.T; t += blockDim.x) post[t] = 0x7fc00000u;
+    fb_fail_result(d, res, status);
+}
 
 // ---------------------------------------------------------------------------------------
 // fast form: one wavefront per lattice, band <= kFastMaxBand, V <= 64, M = max_move <= 4
@@ -40,21 +50,22 @@ __global__ __launch_bounds__(64) void posterior_fast_kernel(const PostLattice *_
     __shared__ int32_t ring[1024];
     const int lane = threadIdx.x;
     const int64_t T = d.T, L = d.L, B = d.beam, V = d.V;
-    const int64_t dq = L / T, dr = L % T;
     const double NINF = post_dninf();
 
-    if (post_labels_bad(d)) {
+    if (fb_labels_bad(d)) {
         post_fail(d, res, kStatusBadLabel);
         return;
     }
-    auto lab_of = [&](int64_t p) -> int32_t { return (p & 1) ? d.labels[p >> 1] : 0; };
+    auto lab_of = [&](int64_t p) { return fb_lab(d, p); };
+    auto ring_lab = [&](int64_t p) { return ring[p & 1023]; };
 
     // ---- forward ----
     for (int64_t p = lane; p < (L < 1024 ? L : 1024); p += 64) ring[p] = lab_of(p);
     int64_t lfill = L < 1024 ? L : 1024;   // ring holds positions [lfill - 1024, lfill)
     if (lane == 0) colA[0] = 0.0f;         // virtual state before frame 0
     double *prev = colA, *cur = colB;
-    int64_t plo = 0, phi = 1, q = 0, r = 0;
+    int64_t plo = 0, phi = 1;
+    BandWalk bw(L, B, T);
     double C = 0.0, Cb = 0.0;
     double mprev = 0.0;
     int flags = 0;
@@ -63,12 +74,11 @@ __global__ __launch_bounds__(64) void posterior_fast_kernel(const PostLattice *_
     post_wave_sync();
     for (int64_t t = 0; t < T; ++t) {
         int64_t lo, hi;
-        post_band(q, L, B, lo, hi);
+        bw.band(lo, hi);
         // next frame's band: where the label ring has to reach
-        int64_t qn = q + dq, rn = r + dr;
-        if (rn >= T) { rn -= T; ++qn; }
+        bw.next();
         int64_t lon, hin;
-        post_band(qn, L, B, lon, hin);
+        bw.band(lon, hin);
         const int64_t want = (lon + 1024 < L) ? lon + 1024 : L;
         const int64_t np = lfill + lane;
         const bool fill = np < want;
@@ -86,26 +96,9 @@ __global__ __launch_bounds__(64) void posterior_fast_kernel(const PostLattice *_
             if (lane == 0) d.ck[t / kPostCk] = C;
         }
         post_wave_sync();
-        double mymax = NINF;
-        for (int64_t p = lo + lane; p < hi; p += 64) {
-            {
-                const int32_t lab = ring[p & 1023];
-                const double e = row[lab];
-                double x[M];
-                double mx = NINF;
-#pragma unroll
-                for (int j = 0; j < M; ++j) {
-                    const int64_t u = p - j;
-                    const bool ok = u >= plo && u < phi && !(j >= 2 && (j & 1) == 0 && lab == 0);
-                    x[j] = ok ? prev[u & 1023] : NINF;
-                    mx = fmaxf(mx, x[j]);
-                }
-                const double val = post_lse2(x, M, mx) + (e - mprev);
-                cur[p & 1023] = val;
-                mymax = fmaxf(mymax, val);
-                if (p == pt) d.post[t] = (float)((C - Cb) + val);
-            }
-        }
+        const double mymax = fb_fast_fwd<M>(lo, hi, plo, phi, prev, cur, row, mprev, ring_lab, [&](int64_t p, double val) {
+            if (p == pt) d.post[t] = (float)((C - Cb) + val);
+        });
         if (lane == 0 && !(pt >= lo && pt < hi)) d.post[t] = post_ninf();
         double m = post_wave_max(mymax);
         m = (m == NINF) ? 0.0 : m;
@@ -114,8 +107,6 @@ __global__ __launch_bounds__(64) void posterior_fast_kernel(const PostLattice *_
         { double *x = prev; prev = cur; cur = x; }
         plo = lo;
         phi = hi;
-        q = qn;
-        r = rn;
         if (fill) ring[np & 1023] = nlab;
         lfill = (lfill + 64 < want) ? lfill + 64 : (want > lfill ? want : lfill);
         for (int64_t p = lfill + lane; lfill < want; p = lfill + lane) {   // the band jumped more than 64 positions (L > 64 T)
@@ -158,13 +149,11 @@ __global__ __launch_bounds__(64) void posterior_fast_kernel(const PostLattice *_
     if (lane == 0) d.post[tl] = 1.0f;
     // the ring holds [lbot, lbot + 1024) from here on; frame T-2 must find its band in it
     int64_t lbot = lfill - 1024 > 0 ? lfill - 1024 : 0;
-    q -= dq; r -= dr;                       // q, r were one frame past the end
-    if (r < 0) { r += T; --q; }
-    q -= dq; r -= dr;
-    if (r < 0) { r += T; --q; }             // frame T-2
+    bw.prev();                              // bw was one frame past the end
+    bw.prev();                              // frame T-2
     {
         int64_t lo, hi;
-        post_band(q, L, B, lo, hi);
+        bw.band(lo, hi);
         for (int64_t p = lo + lane; p < lbot && p < lo + 1024; p += 64) ring[p & 1023] = lab_of(p);
         if (lo < lbot) lbot = lo;
     }
@@ -176,11 +165,10 @@ __global__ __launch_bounds__(64) void posterior_fast_kernel(const PostLattice *_
     post_wave_sync();
     for (int64_t t = T - 2; t >= 0; --t) {
         int64_t lo, hi;
-        post_band(q, L, B, lo, hi);
-        int64_t qn = q - dq, rn = r - dr;
-        if (rn < 0) { rn += T; --qn; }
+        bw.band(lo, hi);
+        bw.prev();
         int64_t lon = 0, hin = 0;
-        if (t >= 1) post_band(qn, L, B, lon, hin);
+        if (t >= 1) bw.band(lon, hin);
         const int64_t np = lbot - 1 - lane;
         const bool fill = t >= 1 && np >= lon;
         const int32_t nlab = fill ? lab_of(np) : 0;
@@ -194,29 +182,10 @@ __global__ __launch_bounds__(64) void posterior_fast_kernel(const PostLattice *_
         }
         const double cb = d.ck[t / kPostCk];
         post_wave_sync();
-        double mymax = NINF;
-        for (int64_t p = lo + lane; p < hi; p += 64) {
-            {
-                const int32_t lab = ring[p & 1023];
-                const double e = row[lab];
-                double x[M];
-                double mx = NINF;
-#pragma unroll
-                for (int j = 0; j < M; ++j) {
-                    const int64_t u = p + j;
-                    const bool ok = u >= nlo && u < nhi;
-                    const double g = (j >= 2 && (j & 1) == 0) ? vn[u & 1023] : gn[u & 1023];
-                    x[j] = ok ? g : NINF;
-                    mx = fmaxf(mx, x[j]);
-                }
-                const double w = post_lse2(x, M, mx) - nprev;
-                const double g = w + e;
-                gc[p & 1023] = g;
-                vc[p & 1023] = lab == 0 ? NINF : g;
-                mymax = fmaxf(mymax, g);
-                if (p == pt) d.post[t] = post_value(cb, dt, D, w, Z);
-            }
-        }
+        const double mymax = fb_fast_bwd<M>(lo, hi, nlo, nhi, gn, vn, gc, vc, row, nprev, false, 0, ring_lab,
+                                            [&](int64_t p, int32_t, double w) {
+                                                if (p == pt) d.post[t] = post_value(cb, dt, D, w, Z);
+                                            });
         if (lane == 0 && !(pt >= lo && pt < hi)) d.post[t] = 0.0f;
         double n = post_wave_max(mymax);
         n = (n == NINF) ? 0.0 : n;
@@ -226,8 +195,6 @@ __global__ __launch_bounds__(64) void posterior_fast_kernel(const PostLattice *_
         { double *x = vn; vn = vc; vc = x; }
         nlo = lo;
         nhi = hi;
-        q = qn;
-        r = rn;
         if (fill) ring[np & 1023] = nlab;
         if (t >= 1) {
             lbot = (lbot - 64 > lon) ? lbot - 64 : (lon < lbot ? lon : lbot);
@@ -254,27 +221,25 @@ __global__ __launch_bounds__(256) void posterior_generic_kernel(const PostLattic
     __shared__ double red[2][4];
     const int tid = threadIdx.x;
     const int64_t T = d.T, L = d.L, B = d.beam, V = d.V;
-    const int M = d.max_move;
-    const int64_t dq = L / T, dr = L % T;
     const double NINF = post_dninf();
-    if (post_labels_bad(d)) {
+    if (fb_labels_bad(d)) {
         post_fail(d, res, kStatusBadLabel);
         return;
     }
-    auto lab_of = [&](int64_t p) -> int32_t { return (p & 1) ? d.labels[p >> 1] : 0; };
     double *A0 = d.col, *A1 = d.col + L, *V0 = d.col + 2 * L, *V1 = d.col + 3 * L;
 
     // ---- forward ----
     if (tid == 0) A0[0] = 0.0;
     double *prev = A0, *cur = A1;
-    int64_t plo = 0, phi = 1, q = 0, r = 0;
+    int64_t plo = 0, phi = 1;
+    BandWalk bw(L, B, T);
     double C = 0.0, Cb = 0.0;
     double mprev = 0.0;
     int flags = 0;
     __syncthreads();
     for (int64_t t = 0; t < T; ++t) {
         int64_t lo, hi;
-        post_band(q, L, B, lo, hi);
+        bw.band(lo, hi);
         const float *lrow = d.lp + (size_t)t * (size_t)d.ld;
         for (int64_t v = tid; v < V; v += 256) flags |= post_bad_bits(lrow[v]);
         const int32_t pt = d.path[t];
@@ -283,26 +248,9 @@ __global__ __launch_bounds__(256) void posterior_generic_kernel(const PostLattic
             Cb = C;
             if (tid == 0) d.ck[t / kPostCk] = C;
         }
-        double mymax = NINF;
-        for (int64_t p = lo + tid; p < hi; p += 256) {
-            const int32_t lab = lab_of(p);
-            const double e = (double)lrow[lab] * kLog2e64;
-            double mx = NINF;
-            for (int j = 0; j < M && j <= p; ++j) {
-                const int64_t u = p - j;
-                if (u >= plo && u < phi && !(j >= 2 && (j & 1) == 0 && lab == 0)) mx = fmaxf(mx, prev[u]);
-            }
-            double s = 0.0;
-            for (int j = 0; j < M && j <= p; ++j) {
-                const int64_t u = p - j;
-                if (u >= plo && u < phi && !(j >= 2 && (j & 1) == 0 && lab == 0)) s += exp2(prev[u] - mx);
-            }
-            const double l = mx == NINF ? NINF : mx + log2(s);
-            const double val = l + (e - mprev);
-            cur[p] = val;
-            mymax = fmaxf(mymax, val);
+        const double mymax = fb_gen_fwd(d, lrow, lo, hi, plo, phi, prev, cur, mprev, [&](int64_t p, double val) {
             if (p == pt) d.post[t] = (float)((C - Cb) + val);
-        }
+        });
         if (tid == 0 && !(pt >= lo && pt < hi)) d.post[t] = post_ninf();
         double m = post_block_max(mymax, red[t & 1]);
         m = (m == NINF) ? 0.0 : m;
@@ -311,9 +259,7 @@ __global__ __launch_bounds__(256) void posterior_generic_kernel(const PostLattic
         { double *x = prev; prev = cur; cur = x; }
         plo = lo;
         phi = hi;
-        q += dq;
-        r += dr;
-        if (r >= T) { r -= T; ++q; }
+        bw.next();
     }
     flags = post_block_flags(flags);
     if (flags) {
@@ -334,51 +280,29 @@ __global__ __launch_bounds__(256) void posterior_generic_kernel(const PostLattic
     // ---- backward ----
     int64_t nlo = plo, nhi = phi;
     double *gn = A0, *gc = A1, *vn = V0, *vc = V1;
-    const double nT = (double)d.lp[(size_t)tl * (size_t)d.ld + lab_of(sstar)] * kLog2e64;
+    const double nT = (double)d.lp[(size_t)tl * (size_t)d.ld + fb_lab(d, sstar)] * kLog2e64;
     for (int64_t p = nlo + tid; p < nhi; p += 256) {
         const double g = (p == sstar) ? nT : NINF;
         gn[p] = g;
-        vn[p] = lab_of(p) == 0 ? NINF : g;
+        vn[p] = fb_lab(d, p) == 0 ? NINF : g;
     }
     double nprev = nT;
     double D = nT;
     if (tid == 0) d.post[tl] = 1.0f;
-    // q, r: one frame past the end -> frame T-2
-    for (int i = 0; i < 2; ++i) {
-        q -= dq;
-        r -= dr;
-        if (r < 0) { r += T; --q; }
-    }
+    bw.prev();   // bw was one frame past the end
+    bw.prev();   // frame T-2
     __syncthreads();
     for (int64_t t = T - 2; t >= 0; --t) {
         int64_t lo, hi;
-        post_band(q, L, B, lo, hi);
+        bw.band(lo, hi);
         const float *lrow = d.lp + (size_t)t * (size_t)d.ld;
         const int32_t pt = d.path[t];
         const float dt = d.post[t];
         const double cb = d.ck[t / kPostCk];
         __syncthreads();   // (every thread has read post[t] before its owner overwrites it)
-        double mymax = NINF;
-        for (int64_t p = lo + tid; p < hi; p += 256) {
-            const int32_t lab = lab_of(p);
-            const double e = (double)lrow[lab] * kLog2e64;
-            double mx = NINF;
-            for (int j = 0; j < M; ++j) {
-                const int64_t u = p + j;
-                if (u >= nlo && u < nhi) mx = fmaxf(mx, (j >= 2 && (j & 1) == 0) ? vn[u] : gn[u]);
-            }
-            double s = 0.0;
-            for (int j = 0; j < M; ++j) {
-                const int64_t u = p + j;
-                if (u >= nlo && u < nhi) s += exp2(((j >= 2 && (j & 1) == 0) ? vn[u] : gn[u]) - mx);
-            }
-            const double w = (mx == NINF ? NINF : mx + log2(s)) - nprev;
-            const double g = w + e;
-            gc[p] = g;
-            vc[p] = lab == 0 ? NINF : g;
-            mymax = fmaxf(mymax, g);
+        const double mymax = fb_gen_bwd(d, lrow, lo, hi, nlo, nhi, gn, vn, gc, vc, nprev, false, 0, [&](int64_t p, int32_t, double w) {
             if (p == pt) d.post[t] = post_value(cb, dt, D, w, Z);
-        }
+        });
         if (tid == 0 && !(pt >= lo && pt < hi)) d.post[t] = 0.0f;
         double n = post_block_max(mymax, red[t & 1]);
         n = (n == NINF) ? 0.0 : n;
@@ -388,9 +312,7 @@ __global__ __launch_bounds__(256) void posterior_generic_kernel(const PostLattic
         { double *x = vn; vn = vc; vc = x; }
         nlo = lo;
         nhi = hi;
-        q -= dq;
-        r -= dr;
-        if (r < 0) { r += T; --q; }
+        bw.prev();
     }
     if (tid == 0) {
         res[d.idx].status = kStatusOk;

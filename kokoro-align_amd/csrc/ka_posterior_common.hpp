@@ -1,5 +1,8 @@
-// ka_posterior_common.hpp — the forward-backward helpers shared by ka_posterior.hpp (best-path posteriors) and
-// ka_occupancy.hpp (label occupancy posteriors): base-2 log-sum-exp, the band, status flags, wave and block reductions.
+// ka_posterior_common.hpp — the forward-backward core shared by ka_posterior.hpp (best-path posteriors) and ka_occupancy.hpp
+// (label occupancy posteriors): base-2 log-sum-exp, the band and its walk, status flags, wave and block reductions, and the
+// frame recurrences themselves, one forward and one backward per form (fb_fast_fwd / fb_fast_bwd, fb_gen_fwd / fb_gen_bwd).
+// The callers differ only in where a cell's label comes from and what they do with a cell once it is computed; both are
+// template arguments, so each recurrence exists once and every caller runs the same expressions on the same operands.
 #pragma once
 #include "ka_types.hpp"
 
@@ -45,6 +48,29 @@ __device__ __forceinline__ void post_band(int64_t q, int64_t L, int64_t B, int64
     lo = lo < 0 ? 0 : lo;
     hi = (L - lo < B) ? L : lo + B;
 }
+// q = floor(L t / T) of frame t, stepped one frame at a time (Bresenham: q + r / T = L t / T with 0 <= r < T)
+struct BandWalk {
+    int64_t q, r, dq, dr, T, L, B;
+    __device__ __forceinline__ BandWalk(int64_t L_, int64_t B_, int64_t T_) : q(0), r(0), dq(L_ / T_), dr(L_ % T_), T(T_), L(L_), B(B_) {}
+    __device__ __forceinline__ void seek(int64_t t)
+    {
+        q = (L * t) / T;
+        r = (L * t) % T;
+    }
+    __device__ __forceinline__ void next()
+    {
+        q += dq;
+        r += dr;
+        if (r >= T) { r -= T; ++q; }
+    }
+    __device__ __forceinline__ void prev()
+    {
+        q -= dq;
+        r -= dr;
+        if (r < 0) { r += T; --q; }
+    }
+    __device__ __forceinline__ void band(int64_t &lo, int64_t &hi) const { post_band(q, L, B, lo, hi); }
+};
 // error flags -> status: a bad label is reported before anything runs; then NaN, +inf, a path value outside [0, L)
 __device__ __forceinline__ int post_status_of(int flags)
 {
@@ -55,19 +81,17 @@ __device__ __forceinline__ int post_block_flags(int flags)
 {
     return (__syncthreads_or(flags & 1) ? 1 : 0) | (__syncthreads_or(flags & 2) ? 2 : 0) | (__syncthreads_or(flags & 4) ? 4 : 0);
 }
-// a lattice without a result: NaN posteriors; log-likelihood NaN, or -inf for kStatusZeroMass (stored as bits: the library
-// is built with -fno-honor-nans, under which a NaN constant is undefined)
+// a lattice without a result: log-likelihood NaN, or -inf for kStatusZeroMass (stored as bits: the library is built with
+// -fno-honor-nans, under which a NaN constant is undefined); each caller also fills its output with NaN
 constexpr uint64_t kNaN64 = 0x7ff8000000000000ull, kNinf64 = 0xfff0000000000000ull;
-__device__ __forceinline__ void post_fail(const PostLattice &d, PostResult *res, int status)
+__device__ __forceinline__ void fb_fail_result(const FbLattice &d, PostResult *res, int status)
 {
-    uint32_t *post = reinterpret_cast<uint32_t *>(d.post);
-    for (int t = threadIdx.x; t < d.T; t += blockDim.x) post[t] = 0x7fc00000u;
     if (threadIdx.x == 0) {
         res[d.idx].status = status;
         *reinterpret_cast<uint64_t *>(&res[d.idx].log_likelihood) = status == kStatusZeroMass ? kNinf64 : kNaN64;
     }
 }
-__device__ __forceinline__ bool post_labels_bad(const PostLattice &d)
+__device__ __forceinline__ bool fb_labels_bad(const FbLattice &d)
 {
     int bad = 0;
     for (int i = threadIdx.x; i < d.S; i += blockDim.x) {
@@ -76,6 +100,8 @@ __device__ __forceinline__ bool post_labels_bad(const PostLattice &d)
     }
     return __syncthreads_or(bad) != 0;
 }
+// lab'[p]: blanks at even positions, the caller's labels at odd ones
+__device__ __forceinline__ int32_t fb_lab(const FbLattice &d, int64_t p) { return (p & 1) ? d.labels[p >> 1] : 0; }
 // posterior of one frame from its two halves (log2 units), clamped to a probability
 __device__ __forceinline__ float post_value(double cb, float dt, double D, double w, double Z)
 {
@@ -90,6 +116,142 @@ __device__ __forceinline__ double post_block_max(double x, double *red)   // red
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
     __syncthreads();
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// ---------------------------------------------------------------------------------------
+// the frame recurrences, with lab'[s] the label of position s:
+//   forward:  u_t(s) = lse2_j u_{t-1}(s-j) - m_{t-1} + e_t(s)          j in [0, max_move), s-j in band t-1, not vetoed
+//   backward: w_t(s) = lse2_j G_{t+1}(s+j) - n_{t+1},  G_t(s) = w_t(s) + e_t(s)
+// A move of an even j >= 2 skips a label; it may not land on a cell whose label VALUE is 0 (align.py:80-81).  The backward
+// pass reads such a move's source from the vetoable copy of G, -inf where the label value is 0.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ bool fb_skip(int j) { return j >= 2 && (j & 1) == 0; }
+__device__ __forceinline__ bool fb_vetoed(int j, int32_t lab) { return fb_skip(j) && lab == 0; }
+
+// fast form: one wavefront, position p at slot p & 1023 of an LDS column, row = the frame's log-probs in log2 units.
+// lab_at(p): the cell's label; cell(p, val): the caller's use of u_t(p).  Returns the lane's maximum.
+template <int M, class LabAt, class Cell>
+__device__ __forceinline__ double fb_fast_fwd(int64_t lo, int64_t hi, int64_t plo, int64_t phi, const double *prev, double *cur,
+                                              const double *row, double mprev, LabAt lab_at, Cell cell)
+{
+    const double NINF = post_dninf();
+    double mymax = NINF;
+    for (int64_t p = lo + threadIdx.x; p < hi; p += 64) {
+        const int32_t lab = lab_at(p);
+        const double e = row[lab];
+        double x[M];
+        double mx = NINF;
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            const int64_t u = p - j;
+            const bool ok = u >= plo && u < phi && !fb_vetoed(j, lab);
+            x[j] = ok ? prev[u & 1023] : NINF;
+            mx = fmaxf(mx, x[j]);
+        }
+        const double val = post_lse2(x, M, mx) + (e - mprev);
+        cur[p & 1023] = val;
+        cell(p, val);
+        mymax = fmaxf(mymax, val);
+    }
+    return mymax;
+}
+// G_t over [lo, hi) from G_{t+1} (gn, its vetoable copy vn) over [nlo, nhi) into gc / vc.  last: t = T-1 of a pass that
+// starts there, beta_{T-1} = {sstar: 0}.  cell(p, lab, w): the caller's use of w_t(p).  Returns the lane's maximum of G_t.
+template <int M, class LabAt, class Cell>
+__device__ __forceinline__ double fb_fast_bwd(int64_t lo, int64_t hi, int64_t nlo, int64_t nhi, const double *gn, const double *vn,
+                                              double *gc, double *vc, const double *row, double nprev, bool last, int64_t sstar,
+                                              LabAt lab_at, Cell cell)
+{
+    const double NINF = post_dninf();
+    double mymax = NINF;
+    for (int64_t p = lo + threadIdx.x; p < hi; p += 64) {
+        const int32_t lab = lab_at(p);
+        double w;
+        if (last) {
+            w = (p == sstar) ? 0.0 : NINF;
+        } else {
+            double x[M];
+            double mx = NINF;
+#pragma unroll
+            for (int j = 0; j < M; ++j) {
+                const int64_t u = p + j;
+                const bool ok = u >= nlo && u < nhi;
+                const double g = fb_skip(j) ? vn[u & 1023] : gn[u & 1023];
+                x[j] = ok ? g : NINF;
+                mx = fmaxf(mx, x[j]);
+            }
+            w = post_lse2(x, M, mx) - nprev;
+        }
+        const double g = w + row[lab];   // (read here, not before the branch: a global label load stays behind the lse)
+        gc[p & 1023] = g;
+        vc[p & 1023] = lab == 0 ? NINF : g;
+        mymax = fmaxf(mymax, g);
+        cell(p, lab, w);
+    }
+    return mymax;
+}
+
+// generic form: one 256-thread workgroup, columns at absolute positions, labels and the log-prob row lrow read where they lie,
+// M = d.max_move at run time.  The same contracts as the fast form's.
+template <class Cell>
+__device__ __forceinline__ double fb_gen_fwd(const FbLattice &d, const float *lrow, int64_t lo, int64_t hi, int64_t plo, int64_t phi,
+                                             const double *prev, double *cur, double mprev, Cell cell)
+{
+    const int M = d.max_move;
+    const double NINF = post_dninf();
+    double mymax = NINF;
+    for (int64_t p = lo + threadIdx.x; p < hi; p += 256) {
+        const int32_t lab = fb_lab(d, p);
+        const double e = (double)lrow[lab] * kLog2e64;
+        auto in = [&](int j) {
+            const int64_t u = p - j;
+            return u >= plo && u < phi && !fb_vetoed(j, lab);
+        };
+        double mx = NINF;
+        for (int j = 0; j < M && j <= p; ++j)
+            if (in(j)) mx = fmaxf(mx, prev[p - j]);
+        double s = 0.0;
+        for (int j = 0; j < M && j <= p; ++j)
+            if (in(j)) s += exp2(prev[p - j] - mx);
+        const double l = mx == NINF ? NINF : mx + log2(s);
+        const double val = l + (e - mprev);
+        cur[p] = val;
+        cell(p, val);
+        mymax = fmaxf(mymax, val);
+    }
+    return mymax;
+}
+template <class Cell>
+__device__ __forceinline__ double fb_gen_bwd(const FbLattice &d, const float *lrow, int64_t lo, int64_t hi, int64_t nlo, int64_t nhi,
+                                             const double *gn, const double *vn, double *gc, double *vc, double nprev, bool last,
+                                             int64_t sstar, Cell cell)
+{
+    const int M = d.max_move;
+    const double NINF = post_dninf();
+    double mymax = NINF;
+    for (int64_t p = lo + threadIdx.x; p < hi; p += 256) {
+        const int32_t lab = fb_lab(d, p);
+        const double e = (double)lrow[lab] * kLog2e64;
+        double w;
+        if (last) {
+            w = (p == sstar) ? 0.0 : NINF;
+        } else {
+            auto g = [&](int j) { return fb_skip(j) ? vn[p + j] : gn[p + j]; };
+            double mx = NINF;
+            for (int j = 0; j < M; ++j)
+                if (p + j >= nlo && p + j < nhi) mx = fmaxf(mx, g(j));
+            double s = 0.0;
+            for (int j = 0; j < M; ++j)
+                if (p + j >= nlo && p + j < nhi) s += exp2(g(j) - mx);
+            w = (mx == NINF ? NINF : mx + log2(s)) - nprev;
+        }
+        const double g = w + e;
+        gc[p] = g;
+        vc[p] = lab == 0 ? NINF : g;
+        mymax = fmaxf(mymax, g);
+        cell(p, lab, w);
+    }
+    return mymax;
 }
 
 }  // namespace ka

@@ -136,18 +136,20 @@ constexpr int kStatusBadArgs = -2;     // a best-path position outside [0, L)
 constexpr int kStatusNonFinite = -7;   // a log-prob is +inf
 constexpr int kStatusZeroMass = -9;    // no path of finite score ends at the best path's terminal
 constexpr int kPostCk = 32;            // frames per forward offset checkpoint
-struct PostLattice {
+// what both forward-backward calls describe of a lattice; the shared device code (ka_posterior_common.hpp) takes this part
+struct FbLattice {
     const float *lp;         // [T, ld] log-probs (device)
     const int32_t *labels;   // [S] caller labels (device)
-    const int32_t *path;     // [T] the best path the posteriors are asked for (device)
-    float *post;             // [T] output; between the two passes: log2 alpha at the path, relative to ck[t / kPostCk]
-    double *ck;              // [(T - 1) / kPostCk + 1] the forward pass's log2 offset at the first frame of every block (workspace)
-    double *col;             // generic form only: 4 x L doubles, two score columns and two vetoable copies (workspace)
     int64_t ld;
     int32_t T, S, L, V;
     int32_t beam, max_move;
     int32_t idx;             // index of this lattice in the caller's batch (its PostResult)
-    int32_t pad_;
+};
+struct PostLattice : FbLattice {
+    const int32_t *path;     // [T] the best path the posteriors are asked for (device)
+    float *post;             // [T] output; between the two passes: log2 alpha at the path, relative to ck[t / kPostCk]
+    double *ck;              // [(T - 1) / kPostCk + 1] the forward pass's log2 offset at the first frame of every block (workspace)
+    double *col;             // generic form only: 4 x L doubles, two score columns and two vetoable copies (workspace)
 };
 struct PostResult {
     int32_t status;
@@ -159,22 +161,18 @@ struct PostResult {
 constexpr int kOccFastSlots = 1024;    // fast-form lattices resident at once (four wavefronts per CU): per-slot workspace
 constexpr int kOccGenericSlots = 512;  // generic-form workgroups of one launch, each walking its lattices in turn
 constexpr int kOccLdsBins = 2048;      // generic form: V up to this bins in LDS, above it in a workspace row
-struct OccLattice {
-    const float *lp;              // [T, ld] log-probs (device)
-    const int32_t *labels;        // [S] caller labels (device)
+struct OccLattice : FbLattice {
     float *occ;                   // [T, ld_out] output, V columns written
     double *ck;                   // [nblk][2] forward offset C and frame maximum m before the first frame of every block (slot)
     double *ckcol;                // [nblk][cw] alpha column before the first frame of every block, relative to its offset (slot)
     double *slab;                 // [kPostCk][cw] alpha of the block being walked back (slot)
     double *col;                  // generic form only: 4 x L doubles, the working columns (slot)
     unsigned long long *gbin;     // generic form, V > kOccLdsBins only: [V] fixed-point bins (slot)
-    int64_t ld, ld_out;
-    int32_t T, S, L, V;
-    int32_t beam, max_move;
+    int64_t ld_out;
     int32_t terminal;             // s*, or -1 for a value outside int32
     int32_t cw;                   // column stride of ckcol / slab: 1024 (fast form, slot = position & 1023) or the band width
-    int32_t idx;                  // index of this lattice in the caller's batch (its PostResult)
-    int32_t pad_;
 };
+// the workspace planners (ka_plan.hpp) carve n descriptors: their sizes are part of the published workspace byte counts
+static_assert(sizeof(PostLattice) == 88 && sizeof(OccLattice) == 120, "descriptor sizes");
 
 }  // namespace ka
