@@ -222,8 +222,8 @@ int ka_debug_auto_split(const int64_t *T, int32_t n, int32_t tiles_alive, int32_
  * two; a request below what the kernel uses - 27-52 KB by tile width, V and row layout - is raised to that): an occupancy
  * experiment knob, results are identical. */
 int ka_debug_set_tile_lds(ka_engine *e, int32_t bytes);
-/* Positions per tile of the tiled form: 256 (four cells per lane, two wavefronts per tile: ka_tiled2.hpp), 128 (two cells per lane,
- * three wavefronts per tile, self-vouching halo packets: ka_tiled_stream.hpp - a shorter frame, twice the tiles), or 0 = the
+/* Positions per tile of the tiled form: 256 (four cells per lane, two wavefronts per tile: ka_tiled256.hpp), 128 (two cells per lane,
+ * three wavefronts per tile, self-vouching halo packets: ka_tiled128.hpp - a shorter frame, twice the tiles), or 0 = the
  * library's choice (128 while the tiles alive at once are no more than 3.2 per workgroup slot of the device).  Results are identical. */
 int ka_debug_set_tile_width(ka_engine *e, int32_t positions);
 /* Host-side probe of the library's choice (no GPU needed): the tile width - 128 or 256 - a launch of these n lattices, ALL run in

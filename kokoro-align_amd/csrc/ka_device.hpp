@@ -1,4 +1,4 @@
-// ka_kernels.hpp — gfx950 (CDNA4) device code of the CTC best-path hot path.
+// ka_device.hpp — the device helpers every kernel family of the CTC best-path hot path shares (gfx950, CDNA4).
 //
 // What is computed (dense-band form of kokoro_align/align.py:43-109):
 //   lab'[p] = p odd ? labels[p/2] : 0;  A_{-1} = {0}, sc_{-1}[0] = 0
@@ -17,11 +17,11 @@
 //     cells come from the previous lane with DPP wave_ror:1.
 //   * lane v of a "row" register holds lp[t, v] (V <= 64): one coalesced 256-B load per
 //     frame, prefetched 4 frames ahead; blank emission = readfirstlane; the 8 label emissions per
-//     lane are gathers lp[t, lab'[p]]: ds_bpermute on the row register in the exact / recompute /
-//     workgroup kernels, ds_read_b32 from an LDS copy of the row in the checkpointed forward kernel.
+//     lane are gathers lp[t, lab'[p]]: ds_bpermute on the row register in the exact / recompute
+//     kernels, ds_read_b32 from an LDS copy of the row in the checkpointed forward kernel.
 //   * the band [lo,hi) is applied with 16 wave-uniform 64-bit lane masks (one per cell
 //     index) held in SGPRs and updated only when lo/hi move.
-// Three kernel forms:
+// Kernel forms:
 //   * checkpointed: forward_ck_kernel keeps scores only and stores the score ring every 32
 //     frames; backtrace_rc_kernel recomputes the back-pointers of the 124-cell window below the
 //     path, chunk by chunk, walks it and writes all outputs.  Time on gfx950 is proportional
@@ -31,9 +31,9 @@
 //     lane masks, combines them on the scalar unit and shifts the 2-bit code into a per-lane
 //     word with v_addc_co_u32 (16 cells x 2 bit = one dword per lane per frame);
 //     backtrace_w16_kernel walks the stored codes, gather_outputs_kernel fills labels/scores.
-//   * workgroup (forward_wg4_kernel): four wavefronts per lattice, for latency.
+//   * tiled: forward_tp2_kernel / forward_ts_kernel cut a lattice into tiles of 256 / 128 positions that run as a
+//     pipeline, for latency (ka_tiled.hpp); backtrace_rc_kernel as for the checkpointed form.
 // No MFMA: ~7 flop per cell, nothing to contract.
-#pragma once
 #pragma once
 #include "ka_types.hpp"
 
@@ -519,7 +519,7 @@ __device__ __forceinline__ float wave_shr1(float first, float x)
 }
 
 // Which compute unit this wavefront runs on, as an index into a kCuSlots-entry table: XCC_ID (3 bits) | HW_ID's se_id, sh_id,
-// cu_id (bits 15:8).  Used for SPEED only (ka_tiled_stream.hpp spreads the tiles that are alive first over the CUs).
+// cu_id (bits 15:8).  Used for SPEED only (ka_tiled128.hpp spreads the tiles that are alive first over the CUs).
 __device__ __forceinline__ uint32_t cu_slot()
 {
     uint32_t hw, xcc;

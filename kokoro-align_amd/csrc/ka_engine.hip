@@ -244,7 +244,7 @@ hipError_t join_aux(ka_engine *e, hipStream_t stream, int k)
 }
 
 // The halo slots of the launch start as the NaN sentinel: always for the 128-position tiles' self-vouching packets
-// (ka_tiled_stream.hpp), and under ka_engine_set_verify(1) for the 256-position form (a tile that consumes a slot nobody wrote
+// (ka_tiled128.hpp), and under ka_engine_set_verify(1) for the 256-position form (a tile that consumes a slot nobody wrote
 // reports KA_ERR_INTERNAL).
 bool wants_halo_sentinel(const ka_engine *e, const LaunchPlan &p) { return p.halo_bytes && ((e->verify & 1) || p.narrow); }
 int fill_halo_sentinel(ka_engine *e, const LaunchPlan &p, hipStream_t stream)

@@ -44,13 +44,27 @@ struct TileLaunch {
     uint32_t *ticket;
     int verify;
     TpStats *stats;
-    uint32_t *cu_rank;  // [kCuSlots] workgroups per CU, zeroed per launch (128-position tiles: ka_tiled_stream.hpp)
+    uint32_t *cu_rank;  // [kCuSlots] workgroups per CU, zeroed per launch (128-position tiles: ka_tiled128.hpp)
     unsigned lds;       // LDS bytes a workgroup requests (at least what the kernel uses)
     int max_move;
     int pitch;          // 0: rows staged one by one; 256 (V = 64) or 156 (V = 39): contiguous rows, copied as they lie
 };
-void launch_forward_tiled256(const TileLaunch &a, hipStream_t s);               // two wavefronts per 256-position tile (ka_tiled2.hpp)
-void launch_forward_tiled128(const TileLaunch &a, hipStream_t s);               // three wavefronts per 128-position tile (ka_tiled_stream.hpp); `prog` unused
+void launch_forward_tiled256(const TileLaunch &a, hipStream_t s);               // two wavefronts per 256-position tile (ka_tiled256.hpp)
+void launch_forward_tiled128(const TileLaunch &a, hipStream_t s);               // three wavefronts per 128-position tile (ka_tiled128.hpp); `prog` unused
+// The kernel instance <max_move, PITCH, CONTIG> of a tile launch, for either width: Form<M, PITCH, CONTIG>::launch(a, s).
+// Contiguous rows (pitch 256 or 156) have one instance each, with max_move 4; rows staged one by one, one per max_move.
+template <template <int, int, bool> class Form>
+void launch_tile_instance(const TileLaunch &a, hipStream_t s)
+{
+    if (a.pitch == 256) return Form<4, 256, true>::launch(a, s);
+    if (a.pitch == 156) return Form<4, 156, true>::launch(a, s);
+    switch (a.max_move) {
+    case 1: Form<1, 256, false>::launch(a, s); break;
+    case 2: Form<2, 256, false>::launch(a, s); break;
+    case 3: Form<3, 256, false>::launch(a, s); break;
+    default: Form<4, 256, false>::launch(a, s); break;
+    }
+}
 
 // ---- ka_misc.hip: log-softmax, hash generators, the log-prob producer's LSTM, the audio front end ----
 void launch_log_softmax(const float *in, float *out, int64_t T, int V, int64_t ld_in, int64_t ld_out, hipStream_t s);

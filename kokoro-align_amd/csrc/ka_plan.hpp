@@ -46,7 +46,7 @@ inline size_t par_bt_bytes(const Shape &sh)
            align_up((size_t)(chunks_of_T(sh.T) + supers_of_T(sh.T)) * 4);
 }
 
-// Which frames each tile of P positions (256, or 128: ka_tiled_stream.hpp) is alive in, from the band of align.py:64-65:
+// Which frames each tile of P positions (256, or 128: ka_tiled128.hpp) is alive in, from the band of align.py:64-65:
 //   lo(t) = max(0, floor(L t / T) - B/2),  hi(t) = min(lo(t) + B, L)
 //   t_in(b)  = first t with hi(t) > P b        = 0 if P b < B, else ceil((P b - B + B/2 + 1) T / L)
 //   t_end(b) = first t with lo(t) >= P (b+1)   = ceil((P (b+1) + B/2) T / L), at most T
@@ -143,7 +143,7 @@ inline TileCount count_tiles(const Shape &sh, int32_t V, int32_t beam, int32_t m
     return {n > 0, n};
 }
 
-// Tile width of a launch's tiled lattices: 128 positions (two cells per lane and three wavefronts per tile, ka_tiled_stream.hpp:
+// Tile width of a launch's tiled lattices: 128 positions (two cells per lane and three wavefronts per tile, ka_tiled128.hpp:
 // a frame of half the instructions, twice the tiles and twice the hand-offs, 46-52 KB of LDS per tile) while the tiles alive
 // at once are no more than 3.2 per workgroup slot of the device, else 256.  Measured on prefixes of the corpus stand-in, all
 // tiled, V = 39: three workgroups per CU (tools/sweep_width.py, profiles/r03_sweep_width.jsonl): against 256 positions the
@@ -163,7 +163,7 @@ inline bool narrow_tiles_pay(const std::vector<TileCount> &counts, const std::ve
     }
     if (forced == kTnTile) return true;
     const int64_t slots = (int64_t)(n_simd / 4) * 3;   // 46-52 KB of LDS per workgroup: three per CU
-    // (round 4, ka_tiled_stream.hpp against 256 positions, profiles/r04_sweep_width.jsonl: 0.49 x for one chapter, 0.56 x for 64,
+    // (round 4, ka_tiled128.hpp against 256 positions, profiles/r04_sweep_width.jsonl: 0.49 x for one chapter, 0.56 x for 64,
     //  0.73 x for 160, 0.93 x for 250 (~2250 tiles alive), 1.04 x for 320 (~2900): 3.2 tiles per slot; round 3's kernels: 2.6)
     return permanent <= slots && 5 * alive_now <= 16 * (slots - permanent);
 }
@@ -443,7 +443,7 @@ inline void carve_workspace(LaunchPlan &p)
             ninf_slots = std::max<int64_t>(ninf_slots, sh[i].t_end[0]);
         }
     p.off_zero = off;
-    // ... [progress words | terminal records | ticket (16 bytes) | workgroups per CU (kCuSlots words: ka_tiled_stream.hpp)]
+    // ... [progress words | terminal records | ticket (16 bytes) | workgroups per CU (kCuSlots words: ka_tiled128.hpp)]
     p.zero_bytes = p.n_tiled ? align_up((1 + p.n_tasks) * 4 + (size_t)n * sizeof(TileAux) + 16, 16) + (size_t)kCuSlots * 4 : 0;
     p.off_prog = p.off_zero;
     p.off_aux = p.off_zero + align_up((1 + p.n_tasks) * 4, 16);
@@ -458,7 +458,7 @@ inline void carve_workspace(LaunchPlan &p)
     p.ninf_bytes = p.n_tiled ? align_up((size_t)(ninf_slots + 2 * kTpBlock) * 16) : 0;
     off += p.ninf_bytes;
     p.cv.assign(n, Carve());
-    // ... then the halo slots of every tiled lattice, in one piece (one fill with the sentinel per launch: ka_tiled_stream.hpp)
+    // ... then the halo slots of every tiled lattice, in one piece (one fill with the sentinel per launch: ka_tiled128.hpp)
     p.halo_bytes = 0;
     for (int32_t i = 0; i < n; ++i) {
         p.cv[i].halo = off;

@@ -1,4 +1,4 @@
-// ka_tiled_stream.hpp — the 128-position tile pipeline, round 4: packets that vouch for themselves, no drain between blocks.
+// ka_tiled128.hpp — the 128-position tile pipeline (ka_tiled.hpp), round 4: packets that vouch for themselves, no drain between blocks.
 //
 // A workgroup of three wavefronts per 128-position tile (two cells per lane): the COMPUTE wavefront runs the frames - 11
 // instructions each -, the LOOK-UP wavefront turns the staged log-prob rows into per-lane emission pairs with the band's kills
@@ -32,75 +32,17 @@
 // so at barrier k the pairs and packets of block k+1 are complete, and every buffer that is rewritten during epoch k+1 was last
 // read before barrier k (the compute wavefront drains its reads there: the one wait per block, ~an LDS latency minus frame 27).
 #pragma once
-#include "ka_tiled2.hpp"
+#include "ka_tiled.hpp"
 
 namespace ka {
 
-// ---- a tile of 128 positions: two cells per lane ----
+// A 128-position tile: two cells per lane
 template <int M, bool ZL>
-struct TnTile {
-    uint32_t T, L, B, dq, dr;
-    uint32_t q0, r0, dq32, dr32, ev;
-    uint32_t KL, KE;
-    float inv_T;
-    __device__ __forceinline__ uint32_t lo_of(uint32_t q) const
-    {
-        const int32_t d = (int32_t)q - (int32_t)(B >> 1);
-        return (uint32_t)(d > 0 ? d : 0);
-    }
-    __device__ __forceinline__ uint32_t hi_of(uint32_t lo) const { return (L - lo < B) ? L : lo + B; }
-    int32_t base, t_in, t_end;
-    const char *lp;
-    size_t ld;
-    uint32_t lane_off;
-    const char *halo_in;
-    char *halo_out;
-    gu32w_t prog_in, prog_out;
-    char *ck;
-    uint32_t ck_pitch;
-    uint32_t ck_off;        // per lane: ((base + 2 lane) & ck_mask) * 4
+struct TnTile : TileCore<kTnCells> {
     f32x2 S;                // {blank at base + 2 lane, label at base + 2 lane + 1}
     int la0;                // 4 * label of the lane's label cell
     float vz0;
-    float absum;
-    uint32_t lds_rows, lds_halo;
-    uint32_t lds_stage;
-    uint32_t lds_packets;
 };
-
-// tp_band_block for a tile of 128 positions
-template <int M, bool ZL>
-__device__ __forceinline__ void tn_band_block(TnTile<M, ZL> &c, uint32_t tb, int lane)
-{
-    const uint32_t l1 = lane > 0 ? (uint32_t)lane - 1u : 0u;
-    const uint32_t x = c.r0 + l1 * c.dr;
-    uint32_t qe = (uint32_t)((float)x * c.inv_T);
-    qe -= (qe * c.T > x) ? 1u : 0u;
-    qe += (x - qe * c.T >= c.T) ? 1u : 0u;
-    uint32_t qa = c.q0 + l1 * c.dq + qe;
-    const uint32_t q_before = tb == 0 ? c.q0 : (c.r0 >= c.dr ? c.q0 - c.dq : c.q0 - c.dq - 1u);
-    qa = lane == 0 ? q_before : qa;
-    const uint32_t qn = (uint32_t)__builtin_amdgcn_update_dpp((int)qa, (int)qa, 0x130, 0xF, 0xF, false);
-    const uint32_t tile_lo = (uint32_t)c.base, tile_hi = (uint32_t)c.base + kTnTile;
-    const uint32_t lo_a = c.lo_of(qa), lo_n = c.lo_of(qn);
-    const uint32_t hi_a = c.hi_of(lo_a), hi_n = c.hi_of(lo_n);
-    const uint32_t t = tb - 1u + (uint32_t)lane;
-    const uint32_t la = lo_a > tile_lo ? lo_a : tile_lo, lb = lo_n < tile_hi ? lo_n : tile_hi;
-    const bool leave = la < lb;
-    c.KL = leave ? (la - tile_lo) | ((lb - la) << 16) : 0u;
-    const uint32_t ea = hi_a > tile_lo ? hi_a : tile_lo, eb = hi_n < tile_hi ? hi_n : tile_hi;
-    const bool enter = ea < eb && t + 1u < c.T;
-    c.KE = enter ? (ea - tile_lo) | ((eb - ea) << 16) : 0u;
-    const uint64_t b_leave = __builtin_amdgcn_ballot_w64(leave), b_enter = __builtin_amdgcn_ballot_w64(enter);
-    c.ev = (uint32_t)b_leave | (uint32_t)(b_enter >> 1);
-}
-template <int M, bool ZL>
-__device__ __forceinline__ void tn_band_advance(TnTile<M, ZL> &c)
-{
-    c.q0 += c.dq32;
-    c.r0 += c.dr32;
-    if (c.r0 >= c.T) { c.r0 -= c.T; ++c.q0; }
-}
 
 // The compute wavefront's LDS traffic goes through asm statements the compiler cannot see into, with the waits written by hand:
 // hipcc waits with lgkmcnt(0) at every branch merge, i.e. a frame would wait for the reads it has just issued and take an LDS
@@ -132,8 +74,7 @@ __device__ __forceinline__ void tg_wait_all(TgIn (&in)[4])
 // LDS map of a workgroup (bytes from the dynamic block's start)
 template <int PITCH, bool CONTIG>
 struct TsLds {
-    static constexpr int kRowDmas = !CONTIG ? kTpBlock : (kTpBlock * PITCH + 1023) / 1024;
-    static constexpr int kSlot = CONTIG ? kRowDmas * 1024 : kTpSlotBytes;        // a block of rows
+    static constexpr int kSlot = TileRows<PITCH, CONTIG>::kSlot;                 // a block of rows
     static constexpr int kRows = 0;                                              // two row slots
     static constexpr int kPackets = kRows + 2 * kSlot;                           // two blocks of 32 packets of the tile below
     static constexpr int kStageBytes = 1536;                                     // a publish staging buffer: 32 packet rows + the other lanes' scratch, 8 bytes apart
@@ -212,7 +153,6 @@ template <int M, bool ZL, int PITCH, bool CONTIG>
 __device__ __forceinline__ void ts_run_tile(const Lattice &d, const TileTask &tk, int32_t *meta, char *halo, TileAux *aux, uint32_t lds0, int verify,
                                             TpStats *stats_out)
 {
-    typedef __attribute__((address_space(3))) uint32_t *lu32_t;
     typedef TsLds<PITCH, CONTIG> Lds;
     const int lane = threadIdx.x & 63;
     const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // 0 compute, 1 feeder, 2 look-up
@@ -220,48 +160,11 @@ __device__ __forceinline__ void ts_run_tile(const Lattice &d, const TileTask &tk
     if (role == 0) __builtin_amdgcn_s_setprio(3);
     const uint32_t lds_rows = lds0 + Lds::kRows, lds_packets = lds0 + Lds::kPackets, lds_stage0 = lds0 + Lds::kStage, stat_lds = lds0 + Lds::kStat,
                    lds_pairs = lds0 + Lds::kPairs;
-    constexpr int kRowSlot = Lds::kSlot, kStageBytes = Lds::kStageBytes, kRowDmas = Lds::kRowDmas;
-    if (threadIdx.x < 10) ((lu32_t)(uintptr_t)stat_lds)[threadIdx.x] = 0;
-    if ((verify & 4) && role == 0 && lane == 0) {   // where the compute wavefront runs (the feeder reports its own place below)
-        uint32_t hw;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        ((lu32_t)(uintptr_t)stat_lds)[10] = hw & 0xffffu;
-    }
-    if ((verify & 4) && role == 1) {   // start stamps: wall clock (100 MHz) and shader clock
-        stats_out->start_tick = (unsigned long long)wall_clock64();
-        stats_out->total_ticks = __builtin_amdgcn_s_memtime();
-    }
+    constexpr int kRowSlot = Lds::kSlot, kStageBytes = Lds::kStageBytes;
+    tile_stats_open(stat_lds, verify, role == 0, role == 1, lane, stats_out);
     const float NINF = ninf();
     TnTile<M, ZL> c;
-    c.T = (uint32_t)__builtin_amdgcn_readfirstlane(d.T);
-    c.L = (uint32_t)__builtin_amdgcn_readfirstlane(d.L);
-    c.B = (uint32_t)__builtin_amdgcn_readfirstlane(d.beam);
-    c.dq = c.L / c.T;
-    c.dr = c.L % c.T;
-    c.base = __builtin_amdgcn_readfirstlane(tk.tile) * kTnTile;
-    c.t_in = __builtin_amdgcn_readfirstlane(tk.t_in);
-    c.t_end = __builtin_amdgcn_readfirstlane(tk.t_end);
-    c.lp = reinterpret_cast<const char *>(d.lp);
-    c.ld = (size_t)d.ld * 4;
-    c.lane_off = (lane < d.V ? (uint32_t)lane : 0u) * 4u;
-    c.halo_in = halo + tk.halo_in;
-    c.halo_out = halo + tk.halo_out;
-    c.ck = reinterpret_cast<char *>(d.bp);
-    c.ck_pitch = (uint32_t)d.ck_pitch;
-    c.ck_off = (((uint32_t)c.base + (uint32_t)kTnCells * (uint32_t)lane) & (uint32_t)d.ck_mask) * 4u;
-    c.lds_rows = lds_rows;
-    c.lds_halo = lds_packets;
-    const auto uni = [](uint64_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v); };
-    {
-        const uint64_t x = (uint64_t)c.L * (uint64_t)((uint32_t)c.t_in / kTpBlock * kTpBlock);
-        c.q0 = uni(x / c.T);
-        c.r0 = uni(x % c.T);
-        c.dq32 = uni(((uint64_t)c.L * kTpBlock) / c.T);
-        c.dr32 = uni(((uint64_t)c.L * kTpBlock) % c.T);
-        c.inv_T = 1.0f / (float)c.T;
-        c.ev = 0;
-        c.KL = c.KE = 0;
-    }
+    tile_setup(c, d, tk, halo, lane, lds_rows, lds_packets, lds_stage0);
     {
         gci32_t labx = (gci32_t)d.labx + ((size_t)c.base >> 1) + (size_t)lane;   // the lane's ONE label cell: position base + 2 lane + 1
         c.la0 = labx[0];
@@ -270,14 +173,7 @@ __device__ __forceinline__ void ts_run_tile(const Lattice &d, const TileTask &tk
     // state before frame t_in: nothing of the tile is live, except the virtual start state (align.py:57-58)
     c.S = f32x2{NINF, NINF};
     if (c.base == 0 && c.t_in == 0 && lane == 0) c.S[0] = 0.0f;
-    c.absum = 0.0f;
-    c.lds_packets = lds_stage0;
-    c.lds_stage = 0;
 
-    typedef __attribute__((address_space(1))) const void *gptr_t;
-    typedef __attribute__((address_space(3))) void *lptr_t;
-    typedef __attribute__((address_space(3))) char *lchar_t;
-    const uint32_t last_row = c.T - 1;
     // This tile reads slots t_in .. t_end - 1 of the boundary below.  The tile below computes frames < below_end, so its slots
     // <= below_end are states it computed and every slot behind them is -inf BY CONSTRUCTION (it is under the band): it stores
     // ONE of those, slot below_end + 1, with its last block, and this tile reads that one for all of them.
@@ -289,52 +185,10 @@ __device__ __forceinline__ void ts_run_tile(const Lattice &d, const TileTask &tk
 
     if (role == 1) {
         // =============================================== the feeder ===============================================
-        static_assert(CONTIG || PITCH == kTpRowBytes, "row-by-row staging uses 256-byte rows");
-        auto issue_rows = [&](int32_t k) {    // k >= 0: the log-prob rows of block k (they do not depend on the tile below)
-            const uint32_t tb = (uint32_t)k * kTpBlock;
-            lchar_t dst = (lchar_t)(uintptr_t)(lds_rows + (uint32_t)(k & 1) * kRowSlot);
-            if constexpr (!CONTIG) {
-                const char *rp = c.lp + (size_t)(tb < last_row ? tb : last_row) * c.ld;
-                if (tb + kTpBlock <= c.T) {
-#pragma unroll
-                    for (int f = 0; f < kTpBlock; ++f) {
-                        __builtin_amdgcn_global_load_lds((gptr_t)(rp + c.lane_off), (lptr_t)(dst + f * kTpRowBytes), 4, 0, 0);
-                        rp += c.ld;
-                    }
-                } else {
-#pragma unroll
-                    for (int f = 0; f < kTpBlock; ++f) {
-                        __builtin_amdgcn_global_load_lds((gptr_t)(rp + c.lane_off), (lptr_t)(dst + f * kTpRowBytes), 4, 0, 0);
-                        rp += tb + f < last_row ? c.ld : 0;
-                    }
-                }
-            } else {
-                const uint32_t first = tb < last_row ? tb : last_row;
-                const uint32_t rows_there = c.T - first < (uint32_t)kTpBlock ? c.T - first : (uint32_t)kTpBlock;
-                const uint32_t last_chunk = (rows_there * PITCH - 16u) & ~15u;
-                const char *bp = c.lp + (size_t)first * PITCH;
-#pragma unroll
-                for (int j = 0; j < kRowDmas; ++j) {
-                    uint32_t off = (uint32_t)j * 1024u + (uint32_t)lane * 16u;
-                    off = off < last_chunk ? off : last_chunk;
-                    __builtin_amdgcn_global_load_lds((gptr_t)(bp + off), (lptr_t)(dst + j * 1024), 16, 0, 0);
-                }
-            }
-        };
-        auto issue_packets = [&](int32_t k) {    // the tile below's packets of block k: slot 32 k + f for frame f
-            const uint32_t tb = (uint32_t)k * kTpBlock;
-            if (lane < kTpBlock) {
-                uint32_t s = tb + (uint32_t)lane;
-                s = s < (uint32_t)c.t_in ? (uint32_t)c.t_in : (s > last_slot ? last_slot : s);
-                __builtin_amdgcn_global_load_lds((gptr_t)(c.halo_in + (size_t)(s - (uint32_t)c.t_in) * 16), (lptr_t)(lchar_t)(uintptr_t)(lds_packets + (uint32_t)(k & 1) * (kTpBlock * 16)),
-                                                 16, 0, 16);
-            }
-        };
+        auto issue_packets = [&](int32_t k) { stage_packets(c, k, lds_packets + (uint32_t)(k & 1) * (kTpBlock * 16), last_slot, lane); };
         auto packets_there = [&](int32_t k) {     // (landed) none of the three words a frame uses is the sentinel
             const f32x4 h = lds_f32x4(lds_packets + (uint32_t)(k & 1) * (kTpBlock * 16) + (uint32_t)(lane & (kTpBlock - 1)) * 16u);
-            const bool missing = __builtin_bit_cast(uint32_t, h[1]) == kTpSentinel || __builtin_bit_cast(uint32_t, h[2]) == kTpSentinel ||
-                                 __builtin_bit_cast(uint32_t, h[3]) == kTpSentinel;
-            return __builtin_amdgcn_ballot_w64(missing) == 0ull;
+            return __builtin_amdgcn_ballot_w64(tp_sentinel_in(h)) == 0ull;
         };
         // slot t_in of the upper boundary = the state before the tile's first frame: lane 63's cells, all -inf
         tp_halo_store<0>(c.halo_out, f32x4{NINF, NINF, NINF, NINF}, 1ull << 63);
@@ -364,13 +218,13 @@ __device__ __forceinline__ void ts_run_tile(const Lattice &d, const TileTask &tk
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 if (lane < kTpBlock && t >= c.t_in && t < c.t_end) {
                     const char *out_block = c.halo_out + ((int64_t)tbp - (int64_t)c.t_in) * 16;
-                    asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 offset:16 sc1\n\ts_nop 1" : : "v"((uint32_t)lane * 16u), "v"(pk), "s"(out_block) : "memory");
+                    tp_slot_store<16>(out_block, (uint32_t)lane * 16u, pk);
                 }
                 // with the last block, the one -inf slot that stands for everything behind t_end (the tile above reads slots up to
                 // its own t_end - 1 = fill_end: none behind t_end when the two end together)
                 if (tbp + kTpBlock >= (uint32_t)c.t_end && c.t_end <= fill_end && lane == 0) {
                     const f32x4 dead = {NINF, NINF, NINF, NINF};
-                    asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" : : "v"((uint32_t)((c.t_end + 1 - c.t_in) * 16)), "v"(dead), "s"(c.halo_out) : "memory");
+                    tp_slot_store<0>(c.halo_out, (uint32_t)((c.t_end + 1 - c.t_in) * 16), dead);
                 }
                 // the checkpoint row behind this block (the scores after frame tbp + 31), if the tile is alive in that frame
                 if ((int32_t)(tbp + kTpBlock) <= c.t_end && tbp + kTpBlock < c.T)
@@ -378,7 +232,7 @@ __device__ __forceinline__ void ts_run_tile(const Lattice &d, const TileTask &tk
                 if (lane == 0) asm volatile("ds_write_b32 %0, %1 offset:%2" : : "v"(stage), "v"(kTpSentinel), "n"((kTpBlock - 1) * 16 + 8) : "memory");
             }
             // ---- the rows of block k+2 (for the look-up wavefront in epoch k+1) ----
-            if (k + 2 >= 0 && k + 2 <= kb1) issue_rows(k + 2);
+            if (k + 2 >= 0 && k + 2 <= kb1) stage_rows<PITCH, CONTIG>(c, k + 2, lds_rows + (uint32_t)((k + 2) & 1) * kRowSlot, lane);
             // ---- the packets of block k+1: fetched until every one of them is there ----
             if (k + 1 >= kb0 && k + 1 <= kb1 && fed) {
                 issue_packets(k + 1);
@@ -415,20 +269,14 @@ __device__ __forceinline__ void ts_run_tile(const Lattice &d, const TileTask &tk
         __threadfence();
         tp2_barrier();      // (the three wavefronts leave through the same number of barriers)
         if ((verify & 4) && lane == 0) {
-            uint32_t hw, xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
             const __attribute__((address_space(3))) uint32_t *sw = (const __attribute__((address_space(3))) uint32_t *)(uintptr_t)stat_lds;
             TpStats st;
-            st.spins = sw[0] | ((unsigned long long)((xcc & 0xf) << 16 | (hw & 0xffff))) << 32;
             st.phase[0] = st.phase[1] = 0;
             st.phase[2] = (unsigned long long)sw[10] << 32;   // (high half: HW_ID of the compute wavefront)
             st.extra[0] = sw[8] | ((unsigned long long)sw[2] << 32);    // compute wavefront: cycles at the barrier | cycles inside the frame blocks
             st.extra[1] = sw[9];                                         // look-up wavefront: busy cycles
             st.wait_ticks = (uint32_t)t_wait | ((unsigned long long)sw[2] << 32);
-            st.start_tick = __builtin_amdgcn_s_memtime() - stats_out->total_ticks;
-            st.total_ticks = wall_clock64() - stats_out->start_tick;
-            *stats_out = st;
+            tile_stats_close(st, sw[0], stats_out);
         }
         return;
     }
@@ -440,17 +288,8 @@ __device__ __forceinline__ void ts_run_tile(const Lattice &d, const TileTask &tk
             if (k + 1 >= kb0 && k + 1 <= kb1) {
                 const uint32_t tbn = (uint32_t)(k + 1) * kTpBlock;
                 const uint32_t rows = lds_rows + (uint32_t)((k + 1) & 1) * kRowSlot;
-                {   // block k+1 landed before the last barrier: its finiteness sum (all reads first, then the adds)
-                    const uint32_t r = rows + (uint32_t)lane * 16u;
-                    constexpr int kReads = !CONTIG ? kTpSlotBytes / 1024 : kRowDmas;
-                    f32x4 v[kReads];
-#pragma unroll
-                    for (int j = 0; j < kReads; ++j) v[j] = lds_f32x4(r + j * 1024);
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-                    for (int j = 0; j < kReads; ++j) c.absum += (__builtin_fabsf(v[j][0]) + __builtin_fabsf(v[j][1])) + (__builtin_fabsf(v[j][2]) + __builtin_fabsf(v[j][3]));
-                }
-                tn_band_block(c, tbn, lane);
+                sum_rows<PITCH, CONTIG>(c, rows, lane);   // block k+1 landed before the last barrier: its finiteness sum
+                band_block(c, tbn, lane);
                 // the emissions of block k+1, per frame and lane {blank, label} ...
                 const uint32_t pb = lds_pairs + (uint32_t)((k + 1) & 1) * kTgPairBytes;
                 const uint32_t mine = pb + (uint32_t)lane * 8u, col = rows + (uint32_t)c.la0;
@@ -472,19 +311,12 @@ __device__ __forceinline__ void ts_run_tile(const Lattice &d, const TileTask &tk
                     if (n2) { *(__attribute__((address_space(3))) float *)(uintptr_t)(fb + r2 * 4u) = NINF; ++r2; --n2; }
                     if (n1) { *(__attribute__((address_space(3))) float *)(uintptr_t)(fb + r1 * 4u) = NINF; ++r1; --n1; }
                 }
-                tn_band_advance(c);
+                band_advance(c);
             }
             if (verify & 4) ((lu32_t)(uintptr_t)stat_lds)[9] += (uint32_t)(__builtin_amdgcn_s_memtime() - k0);
             tp2_barrier();
         }
-        // ---- finiteness (as forward_ck: the scores-only form is valid for finite log-probs of sane magnitude) ----
-        int32_t *m = meta_of(meta, d.idx);
-        const uint32_t abits = __builtin_bit_cast(uint32_t, c.absum) & 0x7fffffffu;
-        if (__builtin_amdgcn_ballot_w64(abits > 0x7f800000u)) {
-            if (lane == 0) atomicMin(&m[0], kStatusNaN);
-        } else if (__builtin_amdgcn_ballot_w64(abits >= __builtin_bit_cast(uint32_t, 1e30f))) {
-            if (lane == 0) atomicOr(&m[2], d.W <= kFastMaxBand ? kFlagExact : kFlagDeclined);
-        }
+        flag_finiteness(c.absum, d, meta_of(meta, d.idx), lane);
         __threadfence();
         tp2_barrier();      // (flagged before the compute wavefront closes the lattice)
         return;
@@ -563,12 +395,11 @@ __device__ __forceinline__ void ts_run_tile(const Lattice &d, const TileTask &tk
     barrier_timed();      // barrier kb1+1: the feeder publishes the last block
     tp2_barrier();        // the look-up wavefront has flagged what it had to flag
 
-    // ---- terminal state: the HIGHEST live position of frame T-1 (align.py:99-101), over the tiles alive then ----
-    int32_t *m = meta_of(meta, d.idx);
+    // ---- terminal state: the highest live position of frame T-1 over the tiles alive then (close_lattice) ----
     if ((uint32_t)c.t_end == c.T) {
         // (the only full band mask of a tile's life: cells above hi may hold leaked scores)
-        const uint32_t q_last = c.L - (c.L + c.T - 1u) / c.T;   // floor(L (T-1) / T) = L - ceil(L / T)
-        const uint32_t lo_last = c.lo_of(q_last), hi_last = c.hi_of(lo_last);
+        uint32_t lo_last, hi_last;
+        c.last_band(lo_last, hi_last);
         const float cell[2] = {c.S[0], c.S[1]};
         unsigned long long key = 0;
 #pragma unroll
@@ -576,31 +407,7 @@ __device__ __forceinline__ void ts_run_tile(const Lattice &d, const TileTask &tk
             const uint32_t pos = (uint32_t)c.base + (uint32_t)kTnCells * (uint32_t)lane + (uint32_t)kk;
             if (pos >= lo_last && pos < hi_last && cell[kk] != NINF) key = ((unsigned long long)(pos + 1u) << 32) | __builtin_bit_cast(uint32_t, cell[kk]);
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const unsigned long long o = __shfl_xor(key, off);
-            key = o > key ? o : key;
-        }
-        if (lane == 0) {
-            TileAux *a = aux + d.idx;
-            if (key) atomicMax(&a->best, key);
-            __threadfence();
-            const uint32_t n = atomicAdd(&a->arrived, 1u) + 1u;
-            if (n == (uint32_t)d.n_final) {
-                __threadfence();
-                const unsigned long long best = atomicMax(&a->best, 0ull);
-                const int fl = atomicOr(&m[2], 0);
-                if (fl & (kFlagExact | kFlagDeclined)) {
-                    m[1] = -1;   // declined: the exact kernels redo the lattice (or ka_batch_finish hands it to the generic ones)
-                } else if (best == 0) {
-                    m[1] = -1;
-                    atomicMin(&m[0], kStatusEmptyBeam);
-                } else {
-                    m[1] = (int32_t)(best >> 32) - 1;
-                    m[3] = (int32_t)(uint32_t)best;
-                }
-            }
-        }
+        close_lattice(key, d, aux, meta_of(meta, d.idx), lane);
     }
 }
 

@@ -1,10 +1,10 @@
-// ka_tiled2.hpp — the tile pipeline of ka_tiled.hpp with TWO wavefronts per tile: one computes, one feeds.
+// ka_tiled256.hpp — the 256-position tile pipeline (ka_tiled.hpp) with TWO wavefronts per tile: one computes, one feeds.
 //
 // Why: a lattice's tiles form a chain, so a lone lattice (and a book: its longest chapter) runs at the speed of ONE
 // wavefront's frame loop - and a wavefront that is alone on its SIMD issues one instruction every four cycles, whatever
-// the instruction.  In the one-wavefront tile (ka_tiled.hpp, tp_run_tile) a block of 32 frames costs ~4000 cycles of frames
-// and ~2700 cycles of everything around them: the wait for the staged block, its finiteness sum, the progress store, the
-// poll of the tile below, the LDS-DMA requests of the block three ahead, the publish of the block's halo packets
+// the instruction.  In the one-wavefront tile of round 2 a block of 32 frames cost ~4000 cycles of frames and ~2700 cycles
+// of everything around them: the wait for the staged block, its finiteness sum, the progress store, the poll of the tile
+// below, the LDS-DMA requests of the block three ahead, the publish of the block's halo packets
 // (profiles/r03_tile_stats_cfg2_one_wave.txt).  None of that depends on the scores.  Here wavefront 1 of the workgroup (the
 // FEEDER) does all of it and wavefront 0 (the COMPUTE wavefront) only runs frames; they meet at one s_barrier per block.
 //   iteration `it` (both wavefronts, after the barrier):
@@ -15,23 +15,236 @@
 //               for EVERYTHING it has in flight (s_waitcnt vmcnt(0)) and announces block it-1 in the progress word
 //   so the compute wavefront finds blocks it+1 and it+2 landed at barrier it+1, the requests have the whole iteration of the
 //   compute wavefront (~1.8 us) to land, and a block is announced one iteration after it was computed.
-// Everything of the hand-off protocol (sc1 packets, in-order vmcnt accounting, progress words, bounded stall detector) is
-// the feeder's alone, exactly as in the one-wavefront form; the compute wavefront's only vector-memory instruction is the
-// checkpoint store.  Same LDS request (40 KB: 4 workgroups per CU), twice the wavefronts.
+// Hand-off (cdna_hip_programming.md Guideline 16, sc1 payload + drained + sc1 flag; all loads of it sc1): halo packets are
+// write-through stores; a tile publishes "slots < n are complete" in its progress word once per 32-frame block, and the tile
+// above polls that word once per block, two blocks ahead of use.  Every slot is written once and read once: no ring, no
+// back-pressure.  All of it is the feeder's; the compute wavefront's only vector-memory instruction is the checkpoint store.
 #pragma once
 #include "ka_tiled.hpp"
 
 namespace ka {
 
+// lanes [a, b) of a 64-bit mask, any a, b (clamped to 0..64)
+__device__ __forceinline__ uint64_t tp_lane_range(int32_t a, int32_t b)
+{
+    a = a < 0 ? 0 : (a > 64 ? 64 : a);
+    b = b < 0 ? 0 : (b > 64 ? 64 : b);
+    if (b <= a) return 0ull;
+    const uint32_t n = (uint32_t)(b - a);
+    return (n >= 64u ? ~0ull : ((1ull << n) - 1ull)) << a;
+}
+struct TpMasks {
+    uint64_t m0, m1, m2, m3;   // m<k>: lanes whose cell k (position base + 4 lane + k) is inside the band
+};
+// band [lo, hi) relative to the tile's first position (may be negative / beyond the tile)
+__device__ __forceinline__ void tp_masks(TpMasks &mk, int32_t lo_rel, int32_t hi_rel)
+{
+    lo_rel = lo_rel < -8 ? -8 : (lo_rel > kTpTile + 8 ? kTpTile + 8 : lo_rel);
+    hi_rel = hi_rel < -8 ? -8 : (hi_rel > kTpTile + 8 ? kTpTile + 8 : hi_rel);
+    // lanes l with lo_rel <= 4 l + k < hi_rel  <=>  l in [ceil((lo_rel - k) / 4), ceil((hi_rel - k) / 4))
+    mk.m0 = tp_lane_range((lo_rel + 3) >> 2, (hi_rel + 3) >> 2);
+    mk.m1 = tp_lane_range((lo_rel + 2) >> 2, (hi_rel + 2) >> 2);
+    mk.m2 = tp_lane_range((lo_rel + 1) >> 2, (hi_rel + 1) >> 2);
+    mk.m3 = tp_lane_range((lo_rel + 0) >> 2, (hi_rel + 0) >> 2);
+}
+// -inf into the cell at tile-relative position rel (0..255): S = {cell 0, 2, 1, 3} of lane rel >> 2.  ONE v_cndmask behind
+// a two-level scalar branch INSIDE one asm statement (6 instructions executed; as C++ - four selects on masks picked by
+// s_cselect, or a switch whose arms are asm statements - hipcc made 24 to 35 of it, with copies at the merges).
+__device__ __forceinline__ void tp_kill(f32x4 &S, uint32_t rel, float NINF)
+{
+    const uint64_t m = 1ull << (rel >> 2);
+    float c0 = S[0], c2 = S[1], c1 = S[2], c3 = S[3];
+    asm volatile("s_bitcmp1_b32 %[rel], 1\n\t"
+                 "s_cbranch_scc1 .Lka_k23_%=\n\t"
+                 "s_bitcmp1_b32 %[rel], 0\n\t"
+                 "s_cbranch_scc1 .Lka_k1_%=\n\t"
+                 "v_cndmask_b32 %[c0], %[c0], %[ninf], %[m]\n\t"
+                 "s_branch .Lka_ke_%=\n"
+                 ".Lka_k1_%=:\n\t"
+                 "v_cndmask_b32 %[c1], %[c1], %[ninf], %[m]\n\t"
+                 "s_branch .Lka_ke_%=\n"
+                 ".Lka_k23_%=:\n\t"
+                 "s_bitcmp1_b32 %[rel], 0\n\t"
+                 "s_cbranch_scc1 .Lka_k3_%=\n\t"
+                 "v_cndmask_b32 %[c2], %[c2], %[ninf], %[m]\n\t"
+                 "s_branch .Lka_ke_%=\n"
+                 ".Lka_k3_%=:\n\t"
+                 "v_cndmask_b32 %[c3], %[c3], %[ninf], %[m]\n"
+                 ".Lka_ke_%=:"
+                 : [c0] "+v"(c0), [c1] "+v"(c1), [c2] "+v"(c2), [c3] "+v"(c3)
+                 : [rel] "s"(rel), [m] "s"(m), [ninf] "v"(NINF)
+                 : "scc");
+    S = f32x4{c0, c2, c1, c3};
+}
+// state of a lane: S = {cell 0, cell 2, cell 1, cell 3} = {blank, blank, label, label} - the two blanks and the two labels
+// are register pairs (v_pk_add_f32 of the emissions), and the four registers as they lie ARE the halo packet
+__device__ __forceinline__ void tp_mask_state(f32x4 &S, const TpMasks &mk, float NINF)
+{
+    S[0] = select_by_mask(NINF, S[0], mk.m0);
+    S[2] = select_by_mask(NINF, S[2], mk.m1);
+    S[1] = select_by_mask(NINF, S[1], mk.m2);
+    S[3] = select_by_mask(NINF, S[3], mk.m3);
+}
 
-// LDS map of a workgroup: kTpRing blocks of rows - as they lie in memory when the rows are contiguous (32 x PITCH bytes, rounded up
-// to whole 1-KB LDS-DMA instructions: 5 KB for V = 39), else 32 rows of 256 bytes -, the ring's packets, the poll words, two
-// publish staging buffers, the diagnostic words (ticket at +48), two buffers of band words.  27.1 KB for V = 39 with contiguous
-// rows: FIVE workgroups per CU when the engine asks for no more (launches whose tiles outnumber the slots), 39.1 KB otherwise.
+// sc1 (write-through, agent scope) accesses of the progress words.  The loads are untracked by hipcc like the row loads:
+// pair with a counted wait.
+__device__ __forceinline__ void tp_prog_store(gu32w_t word /* uniform */, uint32_t value)
+{
+    uint64_t saved;
+    asm volatile("s_nop 4\n\ts_mov_b64 %0, exec\n\ts_and_b64 exec, exec, 1\n\tglobal_store_dword %1, %2, %3 sc1\n\ts_mov_b64 exec, %0"
+                 : "=&s"(saved) : "v"(0u), "v"(value), "s"(word) : "memory", "scc");
+}
+__device__ __forceinline__ void tp_prog_load(uint32_t &dst, gu32w_t word /* uniform */)
+{
+    asm volatile("s_nop 4\n\tglobal_load_dword %0, %1, %2 sc1" : "+v"(dst) : "v"(0u), "s"(word) : "memory");
+}
+// progress of the tile below must reach `need` leading slots; polled relaxed with a sleep that grows while far away.
+// Bounded by a STALL detector: a tile whose producer has not advanced its progress word for ~4 s of wall clock gives up
+// (returns false; the lattice gets KA_ERR_INTERNAL) instead of hanging the GPU - this can only be a bug in the hand-off,
+// never an input.  The clock restarts whenever the polled word moves: a tile whose producer is healthy but far behind
+// (a long lattice with every tile resident, a queue that is time-sliced with another process) waits as long as it takes.
+// Hysteresis: a tile that does have to wait waits for `want` >= need (two blocks more): the poll it carries into a block
+// start is a block old, so a tile sitting exactly at the limit would pay a poll round trip (~1 us) at every block;
+// after one longer wait it stays ahead of its stale information for as long as it is not faster than its producer.
+// (diagnostic counters - number of waits, 100 MHz ticks spent in them - live in two LDS words at `stat_lds`)
+__device__ __forceinline__ bool tp_wait_progress(gu32w_t word, uint32_t need, uint32_t want, uint32_t have, uint32_t stat_lds)
+{
+    if (have >= need) return true;
+    const uint64_t t0 = wall_clock64();   // 100 MHz
+    uint64_t t_moved = t0;
+    __attribute__((address_space(3))) uint32_t *st = (__attribute__((address_space(3))) uint32_t *)(uintptr_t)stat_lds;
+    st[0] += 1;
+    for (;;) {
+        const uint32_t gap = want - have;
+        if (gap > 4096u) __builtin_amdgcn_s_sleep(127);
+        else if (gap > 256u) __builtin_amdgcn_s_sleep(32);
+        else __builtin_amdgcn_s_sleep(4);
+        uint32_t v = 0;
+        tp_prog_load(v, word);
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(v) : : "memory");
+        const uint32_t now_have = (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+        const uint64_t now = wall_clock64();
+        if (now_have != have) t_moved = now;
+        have = now_have;
+        if (have >= want) {
+            st[1] += (uint32_t)(now - t0);
+            return true;
+        }
+        if (now - t_moved > 400000000ull) return false;
+    }
+}
+
+// A 256-position tile: four cells per lane
+template <int M, bool ZL>
+struct TpTile : TileCore<kTpCells> {
+    gu32w_t prog_in, prog_out;
+    // per lane
+    f32x4 S;
+    int la0, la1;           // 4 * label of cells 1 and 3
+    float vz0, vz1;
+};
+
+// One frame, F = its index in the block.  The LDS reads run TWO frames ahead of their use (an LDS read takes longer than
+// half a frame of this loop): In.cur = inputs of this frame (emissions E, e0 and H, the three cells below each lane's
+// first cell), In.nxt = raw LDS data of frame t+1 (issued a frame ago, landed by now), and the reads for frame t+2 are
+// issued here from `r2_*` / `h2` (byte addresses of row / packet t+2 in LDS).  H of frame t+1 is taken at the end, from
+// this frame's final scores and the packet of slot t+1.
+struct TpIn {
+    f32x2 E;      // emissions of the two label cells
+    float e0;     // blank emission
+    f32x4 hp;     // packet of the tile below: {cell 0, 2, 1, 3} of the lane below lane 0
+};
+template <int M, bool ZL, bool GUARDED, int F>
+__device__ __forceinline__ void tp_frame(TpTile<M, ZL> &c, uint32_t t, float (&H)[3], TpIn &cur, TpIn &nxt, uint32_t r2_l0, uint32_t r2_l1, uint32_t r2_0,
+                                         uint32_t h2, float NINF)
+{
+    const bool live = !GUARDED || ((int32_t)t >= c.t_in && (int32_t)t < c.t_end);
+    if (live) {
+        const float b0 = c.S[0], b1 = c.S[1], l0 = c.S[2], l1 = c.S[3];
+        f32x2 ml, mb;
+        ml = label_pair_max<M, ZL>(l1, b1, l0, b0, H[0], H[1], c.vz1, c.vz0);   // {lower, upper}
+        mb[1] = cell_blank_max<M>(b1, l0, H[0]);
+        mb[0] = cell_blank_max<M>(b0, H[0], H[2]);
+        const f32x2 sl = ml + cur.E, sb = mb + f32x2{cur.e0, cur.e0};
+        c.S = f32x4{sb[0], sb[1], sl[0], sl[1]};
+        // The band is enforced by KILLING single cells, not by masking all of them: a cell above hi collects "leaked" scores
+        // from the live cells under it and must hold -inf at the moment it enters the band (rule i: the positions
+        // [hi(t), hi(t+1)) are killed after frame t); a cell that has dropped below lo was live in the last frame of the old
+        // band, is still computed in the first frame of the new one and must be dead after it (rule ii: the positions
+        // [lo(t-1), lo(t)) are killed after frame t) - from then on it only reads cells below itself, which are dead, and
+        // stays -inf by itself.  `ev` marks the frames in which either range meets this tile (band_block).
+        if (__builtin_expect((c.ev >> F) & 1u, 0)) {
+            asm volatile("" ::: "memory");
+            // what to kill was worked out for the whole block (band_block): first tile-relative position | count << 16
+            const uint32_t k2 = (uint32_t)__builtin_amdgcn_readlane((int)c.KL, F), k1 = (uint32_t)__builtin_amdgcn_readlane((int)c.KE, F + 1);
+            for (uint32_t r = k2 & 0xffffu, e = r + (k2 >> 16); r < e; ++r) tp_kill(c.S, r, NINF);   // rule ii: left the band before this frame
+            for (uint32_t r = k1 & 0xffffu, e = r + (k1 >> 16); r < e; ++r) tp_kill(c.S, r, NINF);   // rule i: enters it after this frame
+        }
+    }
+    // the three cells below every lane's first cell, for frame t+1 (lane 0: from the packet of the tile below)
+    // (the packet's first dword is not needed; it is kept alive up to here so that its register is not recycled - and
+    //  the LDS read waited for - earlier)
+    asm volatile("" : : "v"(nxt.hp));
+    H[0] = wave_shr1(nxt.hp[3], c.S[3]);   // position base + 4 lane - 1 (label)
+    H[1] = wave_shr1(nxt.hp[1], c.S[1]);   // - 2 (blank)
+    H[2] = wave_shr1(nxt.hp[2], c.S[2]);   // - 3 (label)
+    // publish the state after frame t = slot t+1 of the upper boundary (lane 63's four cells)
+    // (staged: every lane drops its four cells into this frame's 1-KB row of the LDS staging area - no EXEC change and
+    //  no vector-memory instruction per frame; lane 63's go out at the end of the block, tp_publish_block)
+    if (live) *(__attribute__((address_space(3))) f32x4 *)(uintptr_t)(c.lds_stage + F * 16) = c.S;
+    // LDS reads of frame t+2 (skipped frames read too: they prime the pipeline).  At the END of the frame, behind the branch
+    // merge above: hipcc waits with lgkmcnt(0) at every merge (the band visit, the guarded frames), and with the reads at the
+    // top of the frame that wait covered reads issued a dozen instructions earlier - every frame stalled for most of an LDS
+    // round trip.  Down here the wait of the next frame finds reads that are a whole frame old.
+    TpIn far;
+    far.E = f32x2{lds_f32(r2_l0), lds_f32(r2_l1)};
+    far.e0 = lds_f32(r2_0);
+    far.hp = lds_f32x4(h2);
+    cur = nxt;
+    nxt = far;
+}
+
+// the frames of a block.  LDS byte addresses of this block's slot (A[0]) and the next one's (A[1]): row 0 + the lane's
+// two label columns, row 0 itself (column 0 = blank), packet 0 - per block, so that a frame adds only an immediate offset
+struct TpAddr {
+    uint32_t l0, l1, r, h;
+};
+template <int M, bool ZL, int PITCH, bool GUARDED, int F>
+__device__ __forceinline__ void tp_block_frames(TpTile<M, ZL> &c, uint32_t tb, float (&H)[3], TpIn &cur, TpIn &nxt, const TpAddr (&A)[2], float NINF)
+{
+    // frame t+2 = F+2 of this block, or F+2-16 of the next one
+    constexpr int F2 = (F + 2) % kTpBlock, W = (F + 2) / kTpBlock;
+    tp_frame<M, ZL, GUARDED, F>(c, tb + F, H, cur, nxt, A[W].l0 + F2 * PITCH, A[W].l1 + F2 * PITCH, A[W].r + F2 * PITCH, A[W].h + F2 * 16, NINF);
+    if constexpr (F + 1 < kTpBlock) tp_block_frames<M, ZL, PITCH, GUARDED, F + 1>(c, tb, H, cur, nxt, A, NINF);
+}
+
+// end of a block: lane f < kTpBlock fetches what lane 63 staged in frame f and stores it as slot tb + f + 1 (one write-through
+// store instruction for the block's packets = 512 contiguous bytes); frames the tile did not compute store nothing
+template <int M, bool ZL>
+__device__ __forceinline__ void tp_publish_block(TpTile<M, ZL> &c, uint32_t tb, int lane)
+{
+    const int32_t t = (int32_t)tb + lane;
+    if (lane < kTpBlock && t >= c.t_in && t < c.t_end) {
+        const f32x4 pk = lds_f32x4(c.lds_packets + (uint32_t)lane * 16u);
+        // slot tb of the upper boundary (frame tb + f publishes slot tb + f + 1); worked out here, after the frames: two
+        // scalar registers that are not live across them
+        const char *out_block = c.halo_out + ((int64_t)tb - (int64_t)c.t_in) * 16;
+        tp_slot_store<16>(out_block, (uint32_t)lane * 16u, pk);
+    }
+}
+
+template <int M, bool ZL>
+__device__ __forceinline__ void tp_checkpoint(TpTile<M, ZL> &c, uint32_t t_next /* multiple of 32 */)
+{
+    const f32x4 v = {c.S[0], c.S[2], c.S[1], c.S[3]};   // cells 0..3 in position order
+    asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2\n\ts_nop 1" : : "v"(c.ck_off), "v"(v), "s"(c.ck + ((size_t)(t_next / kCkFrames) - 1) * (size_t)c.ck_pitch) : "memory");
+}
+// LDS map of a workgroup: kTpRing blocks of rows (TileRows), the ring's packets, the poll words, two publish staging buffers,
+// the diagnostic words (ticket at +48), two buffers of band words.  27.1 KB for V = 39 with contiguous rows: FIVE workgroups
+// per CU when the engine asks for no more (launches whose tiles outnumber the slots), 39.1 KB otherwise.
 template <int PITCH, bool CONTIG>
 struct Tp2Lds {
-    static constexpr int kRowDmas = !CONTIG ? kTpBlock : (kTpBlock * PITCH + 1023) / 1024;
-    static constexpr int kSlot = CONTIG ? kRowDmas * 1024 : kTpSlotBytes;
+    static constexpr int kSlot = TileRows<PITCH, CONTIG>::kSlot;
     static constexpr int kHalo = kTpRing * kSlot;
     static constexpr int kTicket = kHalo + kTpRing * kTpBlock * 16 + 16 + kTp2StageBytes + 48;
     static constexpr int kTotal = kHalo + kTpRing * kTpBlock * 16 + 16 + kTp2StageBytes + 64 + 2 * kTp2BandBytes;
@@ -39,26 +252,17 @@ struct Tp2Lds {
 static_assert(Tp2Lds<256, false>::kTotal <= (int)kTpLdsRequest && Tp2Lds<256, true>::kTotal <= (int)kTpLdsRequest, "four workgroups per CU");
 static_assert(5 * ((Tp2Lds<156, true>::kTotal + 511) / 512 * 512) <= 160 * 1024, "five workgroups per CU with V = 39");
 
-// the barrier of an iteration: each side first finishes what the other is going to look at (the compute wavefront its LDS
-// writes; the feeder has already waited for its LDS-DMA with a counted vmcnt) - NOT the vmcnt(0) of __syncthreads, which
-// would drain the feeder's requests
-__device__ __forceinline__ void tp2_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 template <int M, bool ZL, int PITCH, bool CONTIG>
 __device__ __forceinline__ void tp2_run_tile(const Lattice &d, const TileTask &tk, int32_t *meta, char *halo, gu32w_t prog, TileAux *aux,
                                              uint32_t lds_rows, uint32_t lds_halo, int verify, TpStats *stats_out)
 {
-    typedef __attribute__((address_space(3))) uint32_t *lu32_t;
     const int lane = threadIdx.x & 63;
     const bool feeder = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0;
     const uint32_t lds_poll = lds_halo + kTpRing * kTpBlock * 16;
     const uint32_t lds_stage0 = lds_poll + 16;                                  // two staging buffers of kTpStageBytes
     const uint32_t stat_lds = lds_stage0 + kTp2StageBytes;                      // diagnostic words, then two flag words
     const uint32_t lds_band = stat_lds + 64;                                    // two buffers of kTp2BandBytes: the band code's kill words and event mask of a block
-    if (threadIdx.x < 10) ((lu32_t)(uintptr_t)stat_lds)[threadIdx.x] = 0;
+    tile_stats_open(stat_lds, verify, !feeder, feeder, lane, stats_out);
     unsigned long long ph = 0;
     auto phase = [&](int w) {
         if (verify & 4) {
@@ -67,51 +271,14 @@ __device__ __forceinline__ void tp2_run_tile(const Lattice &d, const TileTask &t
             ph = now;
         }
     };
-    if ((verify & 4) && !feeder && lane == 0) {   // where the compute wavefront runs (the feeder reports its own place below)
-        uint32_t hw;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        ((lu32_t)(uintptr_t)stat_lds)[10] = hw & 0xffffu;
-    }
-    if ((verify & 4) && feeder) {   // start stamps: wall clock (100 MHz) and shader clock
-        stats_out->start_tick = (unsigned long long)wall_clock64();
-        stats_out->total_ticks = __builtin_amdgcn_s_memtime();
-    }
     // the compute wavefront is the chain: where it shares a SIMD with feeders and with other kernels' wavefronts it issues first
     if (!feeder) __builtin_amdgcn_s_setprio(3);
     const float NINF = ninf();
     TpTile<M, ZL> c;
-    c.T = (uint32_t)__builtin_amdgcn_readfirstlane(d.T);
-    c.L = (uint32_t)__builtin_amdgcn_readfirstlane(d.L);
-    c.B = (uint32_t)__builtin_amdgcn_readfirstlane(d.beam);
-    c.dq = c.L / c.T;
-    c.dr = c.L % c.T;
-    c.base = __builtin_amdgcn_readfirstlane(tk.tile) * kTpTile;
-    c.t_in = __builtin_amdgcn_readfirstlane(tk.t_in);
-    c.t_end = __builtin_amdgcn_readfirstlane(tk.t_end);
-    c.lp = reinterpret_cast<const char *>(d.lp);
-    c.ld = (size_t)d.ld * 4;
-    c.lane_off = (lane < d.V ? (uint32_t)lane : 0u) * 4u;
-    c.halo_in = halo + tk.halo_in;
-    c.halo_out = halo + tk.halo_out;
+    tile_setup(c, d, tk, halo, lane, lds_rows, lds_halo, lds_stage0);
     c.prog_in = prog + tk.prog_in;
     c.prog_out = prog + tk.prog_out;
-    c.ck = reinterpret_cast<char *>(d.bp);
-    c.ck_pitch = (uint32_t)d.ck_pitch;
-    c.ck_off = (((uint32_t)c.base + 4u * (uint32_t)lane) & (uint32_t)d.ck_mask) * 4u;
-    c.lds_rows = lds_rows;
-    c.lds_halo = lds_halo;
     static_assert(kTpBlock * 16 + 62 * 16 + (kTpBlock - 1) * 16 + 16 <= kTpStageBytes, "publish staging");
-    const auto uni = [](uint64_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v); };
-    {
-        const uint64_t x = (uint64_t)c.L * (uint64_t)((uint32_t)c.t_in / kTpBlock * kTpBlock);
-        c.q0 = uni(x / c.T);
-        c.r0 = uni(x % c.T);
-        c.dq32 = uni(((uint64_t)c.L * kTpBlock) / c.T);
-        c.dr32 = uni(((uint64_t)c.L * kTpBlock) % c.T);
-        c.inv_T = 1.0f / (float)c.T;
-        c.ev = 0;
-        c.KL = c.KE = 0;
-    }
     {
         gci32_t labx = (gci32_t)d.labx + ((size_t)c.base >> 1) + 2 * (size_t)lane;
         c.la0 = labx[0];
@@ -122,77 +289,28 @@ __device__ __forceinline__ void tp2_run_tile(const Lattice &d, const TileTask &t
     // state before frame t_in: nothing of the tile is live, except the virtual start state (align.py:57-58)
     c.S = f32x4{NINF, NINF, NINF, NINF};
     if (c.base == 0 && c.t_in == 0 && lane == 0) c.S[0] = 0.0f;
-    c.absum = 0.0f;
-    c.lds_packets = lds_stage0;
-    c.lds_stage = 0;
     // slot t_in of the upper boundary = the state before the tile's first frame: lane 63's cells, all -inf.  The FEEDER
     // stores it: every store the progress word vouches for is in its own in-order vmcnt history.
     if (feeder) tp_halo_store<0>(c.halo_out, f32x4{NINF, NINF, NINF, NINF}, 1ull << 63);
 
-    typedef __attribute__((address_space(1))) const void *gptr_t;
-    typedef __attribute__((address_space(3))) void *lptr_t;
-    typedef __attribute__((address_space(3))) char *lchar_t;
-    const uint32_t last_row = c.T - 1;
     const uint32_t last_slot = (uint32_t)c.t_end - 1;     // this tile reads slots t_in .. t_end - 1
     auto ring = [](int32_t k) { return (uint32_t)((k % kTpRing + kTpRing) % kTpRing); };
-    constexpr int kRowDmas = Tp2Lds<PITCH, CONTIG>::kRowDmas;   // LDS-DMA instructions per block of rows
     constexpr uint32_t kSlot = Tp2Lds<PITCH, CONTIG>::kSlot;     // LDS bytes of a block of rows
-    static_assert(CONTIG || PITCH == kTpRowBytes, "row-by-row staging uses 256-byte rows");
     auto issue_block = [&](int32_t k) {    // k >= 0
-        const uint32_t tb = (uint32_t)k * kTpBlock, slot = ring(k);
-        lchar_t dst = (lchar_t)(uintptr_t)(c.lds_rows + slot * kSlot);
-        if constexpr (!CONTIG) {
-            const char *rp = c.lp + (size_t)(tb < last_row ? tb : last_row) * c.ld;
-            if (tb + kTpBlock <= c.T) {
-#pragma unroll
-                for (int f = 0; f < kTpBlock; ++f) {
-                    __builtin_amdgcn_global_load_lds((gptr_t)(rp + c.lane_off), (lptr_t)(dst + f * kTpRowBytes), 4, 0, 0);
-                    rp += c.ld;
-                }
-            } else {
-#pragma unroll
-                for (int f = 0; f < kTpBlock; ++f) {
-                    __builtin_amdgcn_global_load_lds((gptr_t)(rp + c.lane_off), (lptr_t)(dst + f * kTpRowBytes), 4, 0, 0);
-                    rp += tb + f < last_row ? c.ld : 0;
-                }
-            }
-        } else {
-            const uint32_t first = tb < last_row ? tb : last_row;
-            const uint32_t rows_there = c.T - first < (uint32_t)kTpBlock ? c.T - first : (uint32_t)kTpBlock;
-            const uint32_t last_chunk = (rows_there * PITCH - 16u) & ~15u;
-            const char *bp = c.lp + (size_t)first * PITCH;
-#pragma unroll
-            for (int j = 0; j < kRowDmas; ++j) {
-                uint32_t off = (uint32_t)j * 1024u + (uint32_t)lane * 16u;
-                off = off < last_chunk ? off : last_chunk;
-                __builtin_amdgcn_global_load_lds((gptr_t)(bp + off), (lptr_t)(dst + j * 1024), 16, 0, 0);
-            }
-        }
-        if (lane < kTpBlock) {
-            uint32_t s = tb + (uint32_t)lane;
-            s = s < (uint32_t)c.t_in ? (uint32_t)c.t_in : (s > last_slot ? last_slot : s);
-            __builtin_amdgcn_global_load_lds((gptr_t)(c.halo_in + (size_t)(s - (uint32_t)c.t_in) * 16), (lptr_t)(lchar_t)(uintptr_t)(c.lds_halo + slot * (kTpBlock * 16)), 16, 0, 16);
-        }
+        const uint32_t slot = ring(k);
+        stage_rows<PITCH, CONTIG>(c, k, c.lds_rows + slot * kSlot, lane);
+        stage_packets(c, k, c.lds_halo + slot * (kTpBlock * 16), last_slot, lane);
         if (lane == 0) __builtin_amdgcn_global_load_lds((gptr_t)c.prog_in, (lptr_t)(lchar_t)(uintptr_t)(lds_poll + slot * 4), 4, 0, 16);
     };
     bool stale = false;
     auto landed_block = [&](int32_t k) {
         const uint32_t slot = ring(k);
-        const uint32_t r = c.lds_rows + slot * kSlot + (uint32_t)lane * 16u;
-        constexpr int kReads = kSlot / 1024;
-        f32x4 v[kReads];
-#pragma unroll
-        for (int j = 0; j < kReads; ++j) v[j] = lds_f32x4(r + j * 1024);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int j = 0; j < kReads; ++j) c.absum += (__builtin_fabsf(v[j][0]) + __builtin_fabsf(v[j][1])) + (__builtin_fabsf(v[j][2]) + __builtin_fabsf(v[j][3]));
+        sum_rows<PITCH, CONTIG>(c, c.lds_rows + slot * kSlot, lane);
         if (verify & 1) {
             const int32_t sidx = k * kTpBlock + (lane & (kTpBlock - 1));
             const f32x4 h = lds_f32x4(c.lds_halo + slot * (kTpBlock * 16) + (uint32_t)(lane & (kTpBlock - 1)) * 16u);
             const bool mine = lane < kTpBlock && sidx >= c.t_in && sidx < c.t_end;
-            const bool bad = mine && (__builtin_bit_cast(uint32_t, h[1]) == kTpSentinel || __builtin_bit_cast(uint32_t, h[2]) == kTpSentinel ||
-                                      __builtin_bit_cast(uint32_t, h[3]) == kTpSentinel);
-            if (__builtin_amdgcn_ballot_w64(bad)) stale = true;
+            if (__builtin_amdgcn_ballot_w64(mine && tp_sentinel_in(h))) stale = true;
         }
     };
     auto need_for = [&](int32_t k) {
@@ -238,12 +356,12 @@ __device__ __forceinline__ void tp2_run_tile(const Lattice &d, const TileTask &t
             // the band bookkeeping of the NEXT block (which positions of the tile enter or leave the band in which frame), for
             // the compute wavefront to pick up after the next barrier: ~60 instructions it does not have to issue
             if (it + 1 >= kb0 && it + 1 <= kb1) {
-                tp_band_block(c, tb + kTpBlock, lane);
+                band_block(c, tb + kTpBlock, lane);
                 const uint32_t bb = lds_band + (uint32_t)((it + 1) & 1) * kTp2BandBytes;
                 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
                 *(__attribute__((address_space(3))) u32x2 *)(uintptr_t)(bb + (uint32_t)lane * 8u) = u32x2{c.KL, c.KE};
                 if (lane == 0) *(lu32_t)(uintptr_t)(bb + 512u) = c.ev;
-                tp_band_advance(c);
+                band_advance(c);
             }
             phase(4);
             // EVERYTHING this wavefront has in flight is waited for, once per iteration: the requests of block it+2 (the compute
@@ -312,19 +430,13 @@ __device__ __forceinline__ void tp2_run_tile(const Lattice &d, const TileTask &t
 
     int32_t *m = meta_of(meta, d.idx);
     if (feeder) {
-        // ---- finiteness (as forward_ck: the scores-only form is valid for finite log-probs of sane magnitude).  Flagged
-        // before the tile reports itself done (barrier below), so that whoever closes the lattice sees the flag.
+        // ---- flagged before the tile reports itself done (barrier below), so that whoever closes the lattice sees the flag
         if ((!fed || stale) && lane == 0) atomicMin(&m[0], kStatusInternal);
-        const uint32_t abits = __builtin_bit_cast(uint32_t, c.absum) & 0x7fffffffu;
-        if (__builtin_amdgcn_ballot_w64(abits > 0x7f800000u)) {
-            if (lane == 0) atomicMin(&m[0], kStatusNaN);
-        } else if (__builtin_amdgcn_ballot_w64(abits >= __builtin_bit_cast(uint32_t, 1e30f))) {
-            if (lane == 0) atomicOr(&m[2], d.W <= kFastMaxBand ? kFlagExact : kFlagDeclined);
-        }
+        flag_finiteness(c.absum, d, m, lane);
         // ---- hand the rest of the upper boundary over: after t_end the whole tile is below the band = -inf ----
         const f32x4 dead = {NINF, NINF, NINF, NINF};
         for (int64_t s = (int64_t)c.t_end + 1 + lane; s <= (int64_t)tk.fill_end; s += 64)
-            asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" : : "v"((uint32_t)((s - c.t_in) * 16)), "v"(dead), "s"(c.halo_out) : "memory");
+            tp_slot_store<0>(c.halo_out, (uint32_t)((s - c.t_in) * 16), dead);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         tp_prog_store(c.prog_out, kTpProgDone);
         __threadfence();
@@ -332,29 +444,23 @@ __device__ __forceinline__ void tp2_run_tile(const Lattice &d, const TileTask &t
     tp2_barrier();
     if (feeder) {
         if ((verify & 4) && lane == 0) {
-            uint32_t hw, xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
             const __attribute__((address_space(3))) uint32_t *sw = (const __attribute__((address_space(3))) uint32_t *)(uintptr_t)stat_lds;
             TpStats st;
-            st.spins = sw[0] | ((unsigned long long)((xcc & 0xf) << 16 | (hw & 0xffff))) << 32;
             st.phase[0] = sw[3] | ((unsigned long long)sw[4] << 32);
             st.phase[1] = sw[5] | ((unsigned long long)sw[6] << 32);
             st.phase[2] = sw[7] | ((unsigned long long)sw[10] << 32);   // (high half: HW_ID of the compute wavefront)
             st.wait_ticks = sw[1] | ((unsigned long long)sw[2] << 32);
             st.extra[0] = sw[8] | ((unsigned long long)sw[2] << 32);    // compute wavefront: cycles at the barrier | cycles inside the frame blocks (+ checkpoint stores)
             st.extra[1] = sw[9];                                         // ... and between a barrier and the block's first frame
-            st.start_tick = __builtin_amdgcn_s_memtime() - stats_out->total_ticks;
-            st.total_ticks = wall_clock64() - stats_out->start_tick;
-            *stats_out = st;
+            tile_stats_close(st, sw[0], stats_out);
         }
         return;
     }
-    // ---- terminal state: the HIGHEST live position of frame T-1 (align.py:99-101), over the tiles alive then ----
+    // ---- terminal state: the highest live position of frame T-1 over the tiles alive then (close_lattice) ----
     if ((uint32_t)c.t_end == c.T) {
         TpMasks mk;   // (the only full band mask of a tile's life: cells above hi may hold leaked scores)
-        const uint32_t q_last = c.L - (c.L + c.T - 1u) / c.T;   // floor(L (T-1) / T) = L - ceil(L / T)
-        const uint32_t lo_last = c.lo_of(q_last), hi_last = c.hi_of(lo_last);
+        uint32_t lo_last, hi_last;
+        c.last_band(lo_last, hi_last);
         tp_masks(mk, (int32_t)lo_last - c.base, (int32_t)hi_last - c.base);
         tp_mask_state(c.S, mk, NINF);
         const float cell[4] = {c.S[0], c.S[2], c.S[1], c.S[3]};
@@ -362,36 +468,12 @@ __device__ __forceinline__ void tp2_run_tile(const Lattice &d, const TileTask &t
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (cell[k] != NINF) key = ((unsigned long long)(uint32_t)(c.base + 4 * lane + k + 1) << 32) | __builtin_bit_cast(uint32_t, cell[k]);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const unsigned long long o = __shfl_xor(key, off);
-            key = o > key ? o : key;
-        }
-        if (lane == 0) {
-            TileAux *a = aux + d.idx;
-            if (key) atomicMax(&a->best, key);
-            __threadfence();
-            const uint32_t n = atomicAdd(&a->arrived, 1u) + 1u;
-            if (n == (uint32_t)d.n_final) {
-                __threadfence();
-                const unsigned long long best = atomicMax(&a->best, 0ull);
-                const int fl = atomicOr(&m[2], 0);
-                if (fl & (kFlagExact | kFlagDeclined)) {
-                    m[1] = -1;   // declined: the exact kernels redo the lattice (or ka_batch_finish hands it to the generic ones)
-                } else if (best == 0) {
-                    m[1] = -1;
-                    atomicMin(&m[0], kStatusEmptyBeam);
-                } else {
-                    m[1] = (int32_t)(best >> 32) - 1;
-                    m[3] = (int32_t)(uint32_t)best;
-                }
-            }
-        }
+        close_lattice(key, d, aux, m, lane);
     }
 }
 
-// One workgroup of TWO wavefronts per tile (40 KB of LDS requested: four workgroups per CU).  Tickets as in
-// forward_tp_kernel: the tile a workgroup runs is drawn from a counter, tasks are sorted by first frame.
+// One workgroup of TWO wavefronts per tile (40 KB of LDS requested: four workgroups per CU).  The tile a workgroup runs is
+// drawn from a ticket counter; tasks are sorted by first frame.
 template <int M, int PITCH, bool CONTIG>
 __global__ __launch_bounds__(128) void forward_tp2_kernel(const Lattice *__restrict__ lats, const TileTask *__restrict__ tasks, int n_tasks,
                                                           int32_t *meta, char *halo, uint32_t *prog, TileAux *aux, uint32_t *ticket, int verify, TpStats *stats)

@@ -68,7 +68,7 @@ struct Lattice {
 // meta[4*idx + {0,1,2,3}] = status, end position, flags (bit0: a transcript label is 0), total score bits
 __device__ __forceinline__ int32_t *meta_of(int32_t *meta, int idx) { return meta + 4 * (size_t)idx; }
 
-// ---- tiled forms (ka_tiled.hpp, ka_tiled2.hpp, ka_tiled_stream.hpp) ----
+// ---- tiled forms (ka_tiled.hpp, ka_tiled256.hpp, ka_tiled128.hpp) ----
 constexpr int kTpCells = 4;                    // cells per lane
 constexpr int kTpTile = 64 * kTpCells;         // positions per tile
 constexpr int kTpBlock = 32;                   // frames per staging block (= the checkpoint interval)
@@ -90,7 +90,7 @@ struct TileTask {
     int32_t fill_end;   // last slot of the upper boundary that the tile above reads (its t_end - 1)
     int32_t prog_in;    // progress word of the tile below (word 0 holds kTpProgDone: nothing below tile 0)
     int32_t prog_out;   // progress word of this tile
-    int32_t below_end;  // t_end of the tile below (tile 0: INT32_MAX): the slots behind it hold -inf by construction (ka_tiled_stream.hpp uses it)
+    int32_t below_end;  // t_end of the tile below (tile 0: INT32_MAX): the slots behind it hold -inf by construction (ka_tiled128.hpp uses it)
 };
 // per lattice, zeroed before every launch: terminal state by 64-bit atomicMax, arrival counter of the last-frame tiles
 struct TileAux {
@@ -106,11 +106,11 @@ struct TpStats {
 };
 
 constexpr unsigned kTpLdsRequest = 40 * 1024;   // used: 32 KB rows + 2 KB packets + 2 KB publish staging
-constexpr int kTp2BandBytes = 64 * 8 + 16;           // per block: KL, KE of 64 lanes + the event mask (worked out by the feeder, tp_band_block)
+constexpr int kTp2BandBytes = 64 * 8 + 16;           // per block: KL, KE of 64 lanes + the event mask (worked out by the feeder, band_block)
 constexpr int kTp2StageBytes = 2 * kTpStageBytes;   // publish staging, double-buffered (the feeder reads block it-1's while block it's is written)
 constexpr int kTnCells = 2;
 constexpr int kTnTile = 64 * kTnCells;
-constexpr int kTgPairBytes = kTpBlock * 64 * 8;   // a block of emission pairs of a 128-position tile (ka_tiled_stream.hpp)
+constexpr int kTgPairBytes = kTpBlock * 64 * 8;   // a block of emission pairs of a 128-position tile (ka_tiled128.hpp)
 
 constexpr int kCuSlots = 2048;      // entries of a per-CU table indexed by cu_slot() (ka_device.hpp): XCC_ID (3 bits) | HW_ID's se, sh, cu (8 bits)
 

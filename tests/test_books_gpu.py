@@ -17,7 +17,7 @@ from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-# "tiled/256", "tiled/128": the tile pipeline with the tile width forced (ka_tiled2.hpp / ka_tiled_stream.hpp; plain "tiled" lets the
+# "tiled/256", "tiled/128": the tile pipeline with the tile width forced (ka_tiled256.hpp / ka_tiled128.hpp; plain "tiled" lets the
 # library choose by the number of tiles alive at once)
 MODES = ["wave", "wave_exact", "tiled/256", "tiled/128", "wave+parallel", "tiled/256+parallel", "tiled/128+parallel", "auto"]
 _oracle_cache = {}
@@ -419,7 +419,7 @@ def test_serial_backtrace_output_forms_on_a_book(books_on_device, gather):
 
 
 def test_halo_sentinel_refill_survives_other_launches_in_between():
-    """ka_tiled_stream.hpp's packets vouch for themselves through a NaN sentinel that the engine refills BEHIND a launch's tiles
+    """ka_tiled128.hpp's packets vouch for themselves through a NaN sentinel that the engine refills BEHIND a launch's tiles
     for the next launch (ka_engine.hip: refill_halo_sentinel).  Every launch lays its regions out from the start of the same
     workspace, so a launch of another kind in between (one wavefront per lattice, the exact form, the generic kernels) writes
     over the refilled slots: the next tiled launch must fill them itself.  A stale slot would pass for a packet."""
