@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define KA_VERSION 102 /* 0.1.2: label occupancy posteriors */
+#define KA_VERSION 103 /* 0.1.3: state posteriors at chosen frames */
 
 /* status codes (per call and per lattice) */
 #define KA_OK 0
@@ -168,6 +168,36 @@ int ka_ctc_label_posteriors_batch_f32(ka_engine *e, int32_t n, const float *cons
 /* device-workspace bytes such a call carves (0 for unsupported arguments); bounded by the lattices resident at once, not by n */
 size_t ka_label_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size,
                                           int32_t max_move, int32_t mem);
+
+/*
+ * State posteriors at chosen frames and the lattice log-likelihood of a terminal: the forward-backward
+ * pass of ka_ctc_label_posteriors (same band, moves, veto, terminal s* and Z), read out per band POSITION at K query frames
+ *   gamma[k, j] = gamma_{f_k}(lo_k + j) = exp(alpha_{f_k}(lo_k + j) + beta_{f_k}(lo_k + j) - Z)   for j in [0, hi_k - lo_k)
+ *   gamma[k, j] = 0                                                                           for j in [hi_k - lo_k, W)
+ *   band_lo[k]  = lo_k, the low end of band f_k;  W = min(beam_size, 2S+1) (at least 1), the widest band
+ * Arguments as ka_ctc_label_posteriors[_batch]_f32, with in place of occupancy
+ *   frames          [K] int64 query frames, strictly increasing in [0, T): HOST arrays in both memory modes (K = 0 is legal:
+ *                   only Z is computed)
+ *   gamma           [K rows of W] float32 output (where `mem` says), row pitch ld_out >= W elements (other columns untouched)
+ *   band_lo         [K] int64 output (where `mem` says)
+ * gamma is formed with the exponent and hardware exp2 of the occupancy: rows sum to 1 within 1e-5, gamma summed by label
+ * value is the occupancy row within 1e-5, and at f_k = T-1 the row is exactly 1.0 at s* and 0 elsewhere.  Only the 32-frame
+ * blocks that hold a query frame are recomputed: a few frames cost about a path-posterior call.  Per lattice: statuses as
+ * ka_ctc_label_posteriors, with NaN rows (columns [0, W)) and band_lo -1 for a failed lattice.  Frames out of order or out
+ * of range, or ld_out < W, fail the call with KA_ERR_BAD_ARGS before anything is launched.
+ */
+int ka_ctc_state_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                int32_t beam_size, int32_t max_move, int64_t terminal, const int64_t *frames, int64_t K, float *gamma,
+                                int64_t ld_out, int64_t *band_lo, double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_state_posteriors_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                      const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                      int32_t max_move, const int64_t *terminal, const int64_t *const *frames, const int64_t *K,
+                                      float *const *gamma, const int64_t *ld_out, int64_t *const *band_lo, double *log_likelihood,
+                                      int32_t *status, int32_t mem, void *stream);
+/* device-workspace bytes such a call carves (0 for unsupported arguments); bounded by the lattices resident at once, plus
+ * the frame lists (and, for KA_MEM_HOST, the staged inputs and outputs) of every lattice */
+size_t ka_state_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t V,
+                                          int32_t beam_size, int32_t max_move, int32_t mem);
 
 /* Kernel form of the fast path.
  *   KA_MODE_WAVE        one wavefront per lattice, checkpointed (throughput; fills the chip from ~4096

@@ -7,8 +7,9 @@ Public surface mirrors the reference (kokoro_align/align.py):
     pandas_read_align(files)                                       align.py:172
 plus batched / device-resident entry points (ctc_best_path_batch, ctc_best_path_device) and the
 forward-backward quality signal of a best path (ctc_path_posteriors[_batch|_device], segment_confidence), the label
-occupancy of every frame (ctc_label_posteriors[_batch|_device], segment_agreement) and the differentiable lattice
-log-likelihood (lattice_log_likelihood).
+occupancy of every frame (ctc_label_posteriors[_batch|_device], segment_agreement), the differentiable lattice
+log-likelihood (lattice_log_likelihood) and the state posteriors at chosen frames behind the confidence of align()'s text
+boundaries (ctc_state_posteriors[_batch|_device], boundary_frames, segment_boundary_confidence).
 
 The DP and backtrace run in the HIP C-ABI library (include/kokoro_align_amd.h); there is no
 CPU fallback — importing works without a GPU, computing does not.
@@ -17,6 +18,7 @@ from . import encoder, transcript  # noqa: F401
 from .align import (  # noqa: F401
     align,
     best_path,
+    boundary_frames,
     ctc_best_path,
     ctc_best_path_batch,
     ctc_best_path_device,
@@ -26,10 +28,14 @@ from .align import (  # noqa: F401
     ctc_path_posteriors,
     ctc_path_posteriors_batch,
     ctc_path_posteriors_device,
+    ctc_state_posteriors,
+    ctc_state_posteriors_batch,
+    ctc_state_posteriors_device,
     lattice_log_likelihood,
     log_softmax_device,
     pandas_read_align,
     segment_agreement,
+    segment_boundary_confidence,
     segment_confidence,
 )
 from ._lib import KAError, build_library, library_path, load_library  # noqa: F401

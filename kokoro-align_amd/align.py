@@ -565,6 +565,158 @@ def segment_agreement(occ, labels, best_path, seg_ends):
     return mean
 
 
+# ------------------------------------------------------------------------------------------
+# state posteriors at chosen frames and the confidence of align()'s text boundaries (same band, same forward-backward)
+# ------------------------------------------------------------------------------------------
+def _frames_of(frames, T):
+    """A query frame list as int64 NumPy, checked: strictly increasing in [0, T)."""
+    if _is_tensor(frames):
+        frames = frames.detach().cpu().numpy()
+    f = np.ascontiguousarray(np.asarray(frames).reshape(-1), dtype=np.int64)
+    if len(f) and (f[0] < 0 or f[-1] >= T or np.any(np.diff(f) <= 0)):
+        raise ValueError(f"frames must be strictly increasing in [0, {T})")
+    return f
+
+
+def _band_width(S, beam_size):
+    """W = max(1, min(beam_size, 2S+1)): the widest band, the row length of a state posterior."""
+    return max(1, min(int(beam_size), 2 * int(S) + 1))
+
+
+def ctc_state_posteriors(log_probs, labels, terminal, frames, beam_size=1000, max_move=4):
+    """Posterior of every band position at chosen frames: (gamma float32 [K, W], band_lo int64 [K], log_likelihood float).
+
+    gamma[k, j] is the probability that frame ``frames[k]`` sits at state band_lo[k] + j, over every path of the band of
+    ``ctc_best_path`` that ends at state ``terminal`` (an int, or a best path whose last value is used); columns past the
+    band's width are 0, each row sums to 1.  W = min(beam_size, 2S+1).  ``frames``: strictly increasing in [0, T).
+    NumPy in -> NumPy out; ROCm torch tensors go to ``ctc_state_posteriors_device``.  Raises as ``ctc_label_posteriors``,
+    and ValueError for bad frames.
+    """
+    if _is_tensor(log_probs):
+        (g, lo, ll), = ctc_state_posteriors_device([log_probs], [labels], [terminal], [frames], beam_size, max_move)
+        return g, lo, ll
+    (g, lo, ll), = ctc_state_posteriors_batch([log_probs], [labels], [terminal], [frames], beam_size, max_move)
+    return g, lo, ll
+
+
+def ctc_state_posteriors_batch(log_probs_list, labels_list, terminals, frames_list, beam_size=1000, max_move=4, device=None,
+                               return_status=False):
+    """State posteriors of many lattices in ONE launch; host NumPy buffers in and out.
+
+    Returns a list of (gamma [K_i, W_i], band_lo [K_i], log_likelihood); with ``return_status`` also the per-lattice status
+    list, in which case failures do not raise (their rows are NaN, band_lo -1, their log-likelihood NaN, or -inf for
+    KA_ERR_ZERO_MASS).
+    """
+    got = _host_lattices(log_probs_list, labels_list, terminals, "terminals")
+    if got is None:
+        return ([], []) if return_status else []
+    if len(frames_list) != len(log_probs_list):
+        raise ValueError("frames must hold one list per lattice")
+    lps, labs, _, V = got
+    frames = [_frames_of(f, x.shape[0]) for f, x in zip(frames_list, lps)]
+    Ws = [_band_width(len(lab), beam_size) for lab in labs]
+    gammas = [np.empty((len(f), W), np.float32) for f, W in zip(frames, Ws)]
+    los = [np.empty(len(f), np.int64) for f in frames]
+    eng = _lib.default_engine(_current_device() if device is None else device)
+    p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
+    p_fr, _k2 = _ptr_array([f.ctypes.data for f in frames])
+    p_K, _k3 = _i64_array([len(f) for f in frames])
+    p_g, _k4 = _ptr_array([g.ctypes.data for g in gammas])
+    p_ldo, _k5 = _i64_array(Ws)
+    p_lo, _k6 = _ptr_array([x.ctypes.data for x in los])
+    got = _run_lattices(eng, "ka_ctc_state_posteriors_batch_f32", "ctc_state_posteriors_batch", [x.ctypes.data for x in lps],
+                        [x.shape[0] for x in lps], V, [V] * len(lps), [x.ctypes.data for x in labs], [x.shape[0] for x in labs],
+                        beam_size, max_move, (p_term, p_fr, p_K, p_g, p_ldo, p_lo), list(zip(gammas, los)), _lib.KA_MEM_HOST, None,
+                        return_status)
+    return _state_results(got, return_status)
+
+
+def _state_results(got, return_status):
+    """_run_lattices' ((gamma, band_lo), z) pairs as (gamma, band_lo, z) triples."""
+    res, st = got if return_status else (got, None)
+    res = [(g, lo, z) for (g, lo), z in res]
+    return (res, st) if return_status else res
+
+
+def ctc_state_posteriors_device(log_probs, labels, terminals, frames, beam_size=1000, max_move=4, out=None, return_status=False):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]), terminals (ints or
+    best paths) and host frame lists (strictly increasing in [0, T_i)); list of (gamma tensor [K_i, W_i], band_lo int64 tensor
+    [K_i], both on the device, log_likelihood float) out, W_i = min(beam_size, 2 S_i + 1).  ``out``: optional list of float32
+    [K_i, W_i] tensors with unit column stride to write gamma into (views into wider tensors keep their other columns).  One
+    launch on torch's current stream."""
+    import torch
+    lps, labs, _, V, dev, dev_index = _device_lattices(log_probs, labels, terminals, "terminals")
+    n = len(lps)
+    if len(frames) != n:
+        raise ValueError("frames must hold one list per lattice")
+    frames = [_frames_of(f, int(x.shape[0])) for f, x in zip(frames, lps)]
+    Ws = [_band_width(x.shape[0], beam_size) for x in labs]
+    if out is None:
+        out = [torch.empty((len(f), W), dtype=torch.float32, device=dev) for f, W in zip(frames, Ws)]
+    else:
+        if len(out) != n:
+            raise ValueError("out must hold one tensor per lattice")
+        for o, f, W in zip(out, frames, Ws):
+            if o.dtype != torch.float32 or o.dim() != 2 or tuple(o.shape) != (len(f), W) or o.stride(1) != 1 or o.device != dev:
+                raise ValueError("out tensors must be float32 [K_i, W_i] on the input's device with unit column stride")
+    los = [torch.empty(len(f), dtype=torch.int64, device=dev) for f in frames]
+    eng = _lib.default_engine(dev_index)
+    p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
+    p_fr, _k2 = _ptr_array([f.ctypes.data for f in frames])
+    p_K, _k3 = _i64_array([len(f) for f in frames])
+    p_g, _k4 = _ptr_array([o.data_ptr() for o in out])
+    p_ldo, _k5 = _i64_array([max(o.stride(0), W) for o, W in zip(out, Ws)])   # (a tensor with no rows may report any stride)
+    p_lo, _k6 = _ptr_array([x.data_ptr() for x in los])
+    with torch.cuda.device(dev):
+        got = _run_lattices(eng, "ka_ctc_state_posteriors_batch_f32", "ctc_state_posteriors_device", [x.data_ptr() for x in lps],
+                            [x.shape[0] for x in lps], V, [x.stride(0) for x in lps], [x.data_ptr() for x in labs],
+                            [x.shape[0] for x in labs], beam_size, max_move, (p_term, p_fr, p_K, p_g, p_ldo, p_lo),
+                            list(zip(out, los)), _lib.KA_MEM_DEVICE, _stream_ptr(dev_index), return_status)
+    return _state_results(got, return_status)
+
+
+def boundary_frames(seg_ends, T):
+    """The frames ``align()`` reads the best path at, sorted and unique: 0 (the first segment's start) and every
+    seg_ends[i] < T (a segment's end, which is also the next one's start).  int64 array."""
+    ends = np.asarray(seg_ends, dtype=np.int64).reshape(-1)
+    return np.unique(np.concatenate([np.zeros(1, np.int64), ends[ends < int(T)]]))
+
+
+def segment_boundary_confidence(gamma, band_lo, frames, best_path, seg_ends, n_phonemes):
+    """How likely each text boundary ``align()`` writes is right, from state posteriors at ``boundary_frames`` (host only).
+
+    For segment i (frames [a, b), a = seg_ends[i-1], 0 for the first, b = seg_ends[i]) ``align()`` writes text_start =
+    min(best_path[a] // 2, n_phonemes) and text_end = min(best_path[b] // 2, n_phonemes), or n_phonemes where b >= T.  With
+    state s read as text index min(s // 2, n_phonemes), p_start[i] is the posterior probability of text_start at frame a and
+    p_end[i] that of text_end at frame b (1.0 where b >= T).  Returns two float64 arrays.  Raises ValueError if a frame it
+    needs is not in ``frames``."""
+    g = np.asarray(gamma.detach().cpu() if _is_tensor(gamma) else gamma, dtype=np.float64)
+    lo = np.asarray(band_lo.detach().cpu() if _is_tensor(band_lo) else band_lo, dtype=np.int64).reshape(-1)
+    fr = np.asarray(frames.detach().cpu() if _is_tensor(frames) else frames, dtype=np.int64).reshape(-1)
+    path = np.asarray(best_path.detach().cpu() if _is_tensor(best_path) else best_path, dtype=np.int64).reshape(-1)
+    ends = np.asarray(seg_ends, dtype=np.int64).reshape(-1)
+    T, n_ph = len(path), int(n_phonemes)
+    row_of = {int(f): k for k, f in enumerate(fr)}
+    cols = np.arange(g.shape[1] if g.ndim == 2 else 0, dtype=np.int64)
+
+    def p_at(t):
+        k = row_of.get(int(t))
+        if k is None:
+            raise ValueError(f"segment_boundary_confidence: frame {int(t)} is not among the query frames")
+        want = min(int(path[t]) // 2, n_ph)
+        text = np.minimum((lo[k] + cols) // 2, n_ph)
+        return float(np.sum(g[k][text == want]))
+
+    p_start = np.empty(len(ends))
+    p_end = np.empty(len(ends))
+    for i in range(len(ends)):
+        a = int(ends[i - 1]) if i > 0 else 0
+        b = int(ends[i])
+        p_start[i] = p_at(a)
+        p_end[i] = p_at(b) if b < T else 1.0
+    return p_start, p_end
+
+
 def log_softmax_device(logits, out=None):
     """Mean-subtracted log-softmax of align.py:116-117 on the device (HIP kernel), float32."""
     import torch

@@ -563,9 +563,10 @@ void redo_declined(ka_engine *e, const std::vector<ka_engine::Redo> &again, std:
     }
 }
 
-// ---- best-path posteriors (ka_posterior.hpp) and label occupancy (ka_occupancy.hpp): their own kernels and workspace layout,
-// whatever the engine's mode.  One driver, fb_impl; a call (PostCall, OccCall) brings what differs: its own arrays and their
-// checks, its planner and launch, the descriptor fields beyond FbLattice, its own staging, and what two statuses mean.
+// ---- best-path posteriors (ka_posterior.hpp), label occupancy (ka_occupancy.hpp) and state posteriors at chosen frames
+// (ka_state_posterior.hpp): their own kernels and workspace layout, whatever the engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall) brings what differs: its own arrays and their
+// checks, its planner and launch, the descriptor fields beyond FbLattice, its own staging (upload: host buffers only;
+// stage: every memory mode), and what two statuses mean.
 struct FbArgs {
     int32_t n;
     const float *const *log_probs;
@@ -612,6 +613,7 @@ struct PostCall {
         KA_HIP(hipMemcpyAsync(ws + c.path, best_path[i], (size_t)a.T[i] * 4, hipMemcpyHostToDevice, a.stream));
         return KA_OK;
     }
+    int stage(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
     int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         KA_HIP(hipMemcpyAsync(posteriors[i], ws + c.post, (size_t)a.T[i] * 4, hipMemcpyDeviceToHost, a.stream));
@@ -652,10 +654,80 @@ struct OccCall {
         d.cw = c.parts.cw;
     }
     int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int stage(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
     int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         KA_HIP(hipMemcpy2DAsync(occupancy[i], (size_t)ld_out[i] * 4, ws + c.occ, (size_t)a.V * 4, (size_t)a.V * 4, (size_t)a.T[i],
                                 hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
+struct StateCall {
+    using Desc = ka::StateLattice;
+    using Carve = ka::plan::StateCarve;
+    static constexpr const char *kName = "state posteriors";
+    static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score reaches the terminal";
+    const int64_t *terminal;
+    const int64_t *const *frames;   // host arrays in both memory modes
+    const int64_t *K;
+    float *const *gamma;
+    const int64_t *ld_out;
+    int64_t *const *band_lo;
+
+    bool arrays() const { return terminal && frames && K && gamma && ld_out && band_lo; }
+    const char *bad_lattice(const FbArgs &a, int32_t i) const
+    {
+        const int64_t k = K[i];
+        if (k > 0 && !frames[i]) return ": NULL frames";
+        for (int64_t j = 0; j < k; ++j) {
+            if (frames[i][j] < 0 || frames[i][j] >= a.T[i]) return ": a frame outside [0, T)";
+            if (j > 0 && frames[i][j] <= frames[i][j - 1]) return ": frames not strictly increasing";
+        }
+        const int64_t W = std::max<int64_t>(1, std::min<int64_t>(a.beam_size, 2 * a.S[i] + 1));
+        return ld_out[i] < W ? ": ld_out < min(beam_size, 2S+1)" : nullptr;
+    }
+    bool buffers(int32_t i) const { return K[i] == 0 || (gamma[i] && band_lo[i]); }
+    size_t plan(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host, Carve *cv,
+                size_t *off_res) const
+    {
+        return ka::plan::state_posterior_workspace(n, T, S, K, V, beam, max_move, host, cv, off_res);   // (0 for K < 0 or K > T)
+    }
+    static constexpr auto launch = ka::launch_state_posteriors;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (a.mem == KA_MEM_HOST) {
+            d.gamma = reinterpret_cast<float *>(ws + c.gamma);
+            d.band_lo = reinterpret_cast<int64_t *>(ws + c.band_lo);
+            d.ld_out = c.W;
+        } else {
+            d.gamma = gamma[i];
+            d.band_lo = band_lo[i];
+            d.ld_out = ld_out[i];
+        }
+        d.frames = reinterpret_cast<const int64_t *>(ws + c.frames);
+        d.ck = reinterpret_cast<double *>(ws + c.slot + c.parts.ck);
+        d.ckcol = reinterpret_cast<double *>(ws + c.slot + c.parts.ckcol);
+        d.slab = reinterpret_cast<double *>(ws + c.slot + c.parts.slab);
+        d.col = reinterpret_cast<double *>(ws + c.slot + c.parts.col);
+        d.K = (int32_t)K[i];
+        d.terminal = (terminal[i] >= 0 && terminal[i] <= INT32_MAX) ? (int32_t)terminal[i] : -1;
+        d.cw = c.parts.cw;
+        d.W = c.W;
+    }
+    int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int stage(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (K[i] > 0) KA_HIP(hipMemcpyAsync(ws + c.frames, frames[i], (size_t)K[i] * 8, hipMemcpyHostToDevice, a.stream));
+        return KA_OK;
+    }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (K[i] == 0) return KA_OK;
+        KA_HIP(hipMemcpy2DAsync(gamma[i], (size_t)ld_out[i] * 4, ws + c.gamma, (size_t)c.W * 4, (size_t)c.W * 4, (size_t)K[i],
+                                hipMemcpyDeviceToHost, a.stream));
+        KA_HIP(hipMemcpyAsync(band_lo[i], ws + c.band_lo, (size_t)K[i] * 8, hipMemcpyDeviceToHost, a.stream));
         return KA_OK;
     }
 };
@@ -675,7 +747,7 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
     if (n == 0) return KA_OK;
     std::vector<typename Call::Carve> cv(n);
     size_t off_res = 0;
-    const size_t total = Call::plan(n, a.T, a.S, V, a.beam_size, a.max_move, host, cv.data(), &off_res);
+    const size_t total = call.plan(n, a.T, a.S, V, a.beam_size, a.max_move, host, cv.data(), &off_res);
     if (total == 0) return fail(KA_ERR_BAD_ARGS, std::string(Call::kName) + ": unsupported T/S/V/beam_size/max_move");
     for (int32_t i = 0; i < n; ++i) {
         if (a.ld[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld < V");
@@ -730,6 +802,8 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
             if (a.S[i] > 0) KA_HIP(hipMemcpyAsync(e->ws + cv[i].lab, a.labels[i], (size_t)a.S[i] * 4, hipMemcpyHostToDevice, stream));
             if ((rc = call.upload(cv[i], a, i, e->ws)) != KA_OK) return rc;
         }
+    for (int32_t i = 0; i < n; ++i)
+        if ((rc = call.stage(cv[i], a, i, e->ws)) != KA_OK) return rc;
     Desc *d_lats = reinterpret_cast<Desc *>(e->ws);
     ka::PostResult *d_res = reinterpret_cast<ka::PostResult *>(e->ws + off_res);
     KA_HIP(hipMemcpyAsync(d_lats, h, (size_t)n * sizeof(Desc), hipMemcpyHostToDevice, stream));
@@ -1060,6 +1134,31 @@ size_t ka_label_posterior_workspace_bytes(int32_t n, const int64_t *T, const int
 {
     if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
     return ka::plan::label_posterior_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+int ka_ctc_state_posteriors_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                      const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                      const int64_t *terminal, const int64_t *const *frames, const int64_t *K, float *const *gamma,
+                                      const int64_t *ld_out, int64_t *const *band_lo, double *log_likelihood, int32_t *status, int32_t mem,
+                                      void *stream)
+{
+    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+                   StateCall{terminal, frames, K, gamma, ld_out, band_lo});
+}
+
+int ka_ctc_state_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                int32_t beam_size, int32_t max_move, int64_t terminal, const int64_t *frames, int64_t K, float *gamma,
+                                int64_t ld_out, int64_t *band_lo, double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+                   StateCall{&terminal, &frames, &K, &gamma, &ld_out, &band_lo});
+}
+
+size_t ka_state_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t V, int32_t beam_size,
+                                          int32_t max_move, int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S || !K)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::state_posterior_workspace(n, T, S, K, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
 int ka_debug_chunk_entries(ka_engine *e, int32_t *out, int32_t max_entries, uint8_t *map0_out, int64_t map0_max)

@@ -1,6 +1,6 @@
 // ka_launch.hpp — the host-callable launch functions of every device translation unit.
 //
-// The library is built from seven translation units so that the device code compiles in parallel (a single unit took three
+// The library is built from ten translation units so that the device code compiles in parallel (a single unit took three
 // minutes): ka_engine.hip is host code only and reaches the kernels through these functions; each kernel family lives in
 // the .hip file named below and nowhere else.  All functions only enqueue; errors surface through hipGetLastError().
 #pragma once
@@ -90,5 +90,9 @@ void launch_posteriors(const PostLattice *lats, int n_fast, int n_generic, int m
 // descriptors [0, n_fast): one wavefront per lattice on min(n_fast, kOccFastSlots) workgroups, lattice i on workgroup
 // i mod grid (its workspace slot); then [n_fast, n_fast + n_generic): 256-thread workgroups, min(n_generic, kOccGenericSlots)
 void launch_label_posteriors(const OccLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+
+// ---- ka_state_posterior.hip: state posteriors at chosen frames (ka_state_posterior.hpp) ----
+// the grid and slot rules of launch_label_posteriors
+void launch_state_posteriors(const StateLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 
 }  // namespace ka

@@ -48,12 +48,6 @@ __device__ __forceinline__ void occ_fail(const OccLattice &d, PostResult *res, i
     }
     fb_fail_result(d, res, status);
 }
-// Z as ka_posterior.hpp forms it (the block offset plus the float-stored relative alpha), in nats: the value the
-// path-posterior call returns for a path that ends at s*
-__device__ __forceinline__ double occ_reported_z(double cb, double ca, double us)
-{
-    return (cb + (double)(float)((ca - cb) + us)) * kLn2;
-}
 
 // ---------------------------------------------------------------------------------------
 // fast form: one wavefront per lattice, band <= kFastMaxBand, V <= 64, M = max_move <= 4; the cell layout of
@@ -127,7 +121,7 @@ __device__ __forceinline__ void occ_fast_one(const OccLattice &d, PostResult *re
         return;
     }
     const double Z = Ca + us;   // log2 alpha_{T-1}(s*), the expression gamma's alpha is formed with
-    const double Zr = occ_reported_z(Cb, Ca, us);
+    const double Zr = fb_reported_z(Cb, Ca, us);
     post_wave_sync();
 
     // ---- backward, a block at a time ----
@@ -289,7 +283,7 @@ __device__ __forceinline__ void occ_gen_one(const OccLattice &d, PostResult *res
         return;
     }
     const double Z = Ca + us;
-    const double Zr = occ_reported_z(Cb, Ca, us);
+    const double Zr = fb_reported_z(Cb, Ca, us);
     __syncthreads();
 
     // ---- backward, a block at a time ----

@@ -710,3 +710,60 @@ inline size_t label_posterior_workspace(int32_t n, const int64_t *T, const int64
 
 }  // namespace plan
 }  // namespace ka
+
+namespace ka {
+namespace plan {
+
+// ---- ka_ctc_state_posteriors_batch_f32 (ka_state_posterior.hpp): workspace layout ----
+// label_posterior_workspace's layout and slots (the slot's V-wide global bins go unused), with StateLattice descriptors, and
+// per lattice its uploaded frame list (K int64, in both memory modes) and, for host buffers, the staged gamma [K, W] and
+// band_lo [K] beside the staged log-probs and labels.
+struct StateCarve : OccCarve {
+    size_t frames;           // uploaded frame list
+    size_t gamma, band_lo;   // host buffers only
+    int32_t W;
+};
+inline size_t state_posterior_workspace(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t V, int32_t beam,
+                                        int32_t max_move, bool host_buffers, StateCarve *cv, size_t *off_res)
+{
+    size_t off = align_up((size_t)n * sizeof(StateLattice));
+    if (off_res) *off_res = off;
+    off += align_up((size_t)n * sizeof(PostResult));
+    int32_t n_fast = 0, n_gen = 0;
+    size_t fast_bytes = 0, gen_bytes = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        Shape sh;
+        if (!shape_of(T[i], S[i], V, beam, max_move, sh) || K[i] < 0 || K[i] > T[i]) return 0;
+        StateCarve c{};
+        c.parts = occ_parts(sh, V, beam, max_move);
+        c.fast = posterior_fast(sh.S, V, beam, max_move);
+        c.W = (int32_t)sh.W;
+        size_t &slot_bytes = c.fast ? fast_bytes : gen_bytes;
+        slot_bytes = std::max(slot_bytes, c.parts.bytes);
+        c.slot = (size_t)(c.fast ? n_fast++ : n_gen++);   // (the lattice's rank in its form until the slots are placed)
+        c.frames = off;
+        off += align_up((size_t)K[i] * 8);
+        if (host_buffers) {
+            carve_staged(off, sh, V, c);
+            c.gamma = off;
+            off += align_up((size_t)K[i] * (size_t)sh.W * 4);
+            c.band_lo = off;
+            off += align_up((size_t)K[i] * 8);
+        }
+        if (cv) cv[i] = c;
+    }
+    const size_t fast_base = off;
+    const int32_t fast_slots = std::min(n_fast, kOccFastSlots), gen_slots = std::min(n_gen, kOccGenericSlots);
+    off += (size_t)fast_slots * fast_bytes;
+    const size_t gen_base = off;
+    off += (size_t)gen_slots * gen_bytes;
+    if (cv)
+        for (int32_t i = 0; i < n; ++i) {
+            StateCarve &c = cv[i];
+            c.slot = c.fast ? fast_base + (c.slot % (size_t)fast_slots) * fast_bytes : gen_base + (c.slot % (size_t)gen_slots) * gen_bytes;
+        }
+    return off;
+}
+
+}  // namespace plan
+}  // namespace ka

@@ -110,6 +110,13 @@ __device__ __forceinline__ float post_value(double cb, float dt, double D, doubl
     return (float)(p < 1.0 ? p : 1.0);
 }
 
+// Z of a terminal as ka_posterior.hpp forms it (the block offset plus the float-stored relative alpha), in nats: the value the
+// path-posterior call returns for a path that ends at s*
+__device__ __forceinline__ double fb_reported_z(double cb, double ca, double us)
+{
+    return (cb + (double)(float)((ca - cb) + us)) * kLn2;
+}
+
 __device__ __forceinline__ double post_block_max(double x, double *red)   // red: 4 values of this frame's parity
 {
     x = post_wave_max(x);

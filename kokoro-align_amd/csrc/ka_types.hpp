@@ -172,7 +172,22 @@ struct OccLattice : FbLattice {
     int32_t terminal;             // s*, or -1 for a value outside int32
     int32_t cw;                   // column stride of ckcol / slab: 1024 (fast form, slot = position & 1023) or the band width
 };
+// ---- state posteriors at chosen frames (ka_state_posterior.hpp): the occupancy's slots and form split ----
+struct StateLattice : FbLattice {
+    float *gamma;                 // [K, ld_out] output, W columns written
+    int64_t *band_lo;             // [K] output: the band's low end at every query frame
+    const int64_t *frames;        // [K] query frames, strictly increasing in [0, T) (workspace)
+    double *ck;                   // as OccLattice (slot)
+    double *ckcol;
+    double *slab;
+    double *col;
+    int64_t ld_out;
+    int32_t K;
+    int32_t terminal;             // s*, or -1 for a value outside int32
+    int32_t cw;                   // column stride of ckcol / slab (as OccLattice)
+    int32_t W;                    // widest band: max(1, min(beam, L))
+};
 // the workspace planners (ka_plan.hpp) carve n descriptors: their sizes are part of the published workspace byte counts
-static_assert(sizeof(PostLattice) == 88 && sizeof(OccLattice) == 120, "descriptor sizes");
+static_assert(sizeof(PostLattice) == 88 && sizeof(OccLattice) == 120 && sizeof(StateLattice) == 136, "descriptor sizes");
 
 }  // namespace ka

@@ -1,9 +1,12 @@
 """Wall time of ka_ctc_path_posteriors_batch_f32 (best-path posteriors + lattice log-likelihood, ka_posterior.hpp) on the
 shapes of DESIGN.md section 4.17: one cfg2 lattice, cfg2 batches of 1024 and 8192, the corpus stand-in (workloads.corpus());
 and of ka_ctc_label_posteriors_batch_f32 (label occupancy, ka_occupancy.hpp, section 4.18) on the same cfg2 shapes, the
-terminal taken from the best path (cases occ_single, occ_b1024, occ_b8192).
+terminal taken from the best path (cases occ_single, occ_b1024, occ_b8192); and of ka_ctc_state_posteriors_batch_f32 (state
+posteriors at chosen frames, ka_state_posterior.hpp, section 4.19) with 200 query frames spread over every lattice (cases
+state_single, state_b1024).
 
     python tools/bench_posteriors.py [--cases single,b1024,b8192,corpus] [--reps 3] [--out profiles/posteriors.jsonl]
+    python tools/bench_posteriors.py --cases state_single,state_b1024 --out profiles/state_posteriors_bench.jsonl
 
 Device-resident inputs (hash-generated); best paths from the library's own best-path call.  The 8192 batch points its
 lattices at the 1024 batch's log-probs, labels and paths eight times over (distinct outputs): 105 GB of log-probs would
@@ -101,6 +104,43 @@ def time_occupancy(lps, labs, paths, reps):
     return ms, st, ll
 
 
+def time_states(lps, labs, paths, reps, K=200):
+    n, V = len(lps), int(lps[0].shape[1])
+    eng = _lib.default_engine(torch.cuda.current_device())
+    W = [min(1000, 2 * int(x.shape[0]) + 1) for x in labs]
+    frames = [np.unique(np.linspace(0, int(x.shape[0]) - 1, K).astype(np.int64)) for x in lps]
+    gammas = [torch.empty((len(f), w), dtype=torch.float32, device="cuda") for f, w in zip(frames, W)]
+    los = [torch.empty(len(f), dtype=torch.int64, device="cuda") for f in frames]
+    ll = np.zeros(n, np.float64)
+    st = np.zeros(n, np.int32)
+    k = [_ptr_array([x.data_ptr() for x in xs]) for xs in (lps, labs, gammas, los)]
+    fr = _ptr_array([f.ctypes.data for f in frames])
+    Ks = _i64_array([len(f) for f in frames])
+    T = _i64_array([x.shape[0] for x in lps])
+    S = _i64_array([x.shape[0] for x in labs])
+    ld = _i64_array([x.stride(0) for x in lps])
+    ldo = _i64_array(W)
+    term = _i64_array(torch.stack([p[-1] for p in paths]).cpu().tolist())
+    stream = _stream_ptr(torch.cuda.current_device())
+
+    def call():
+        rc = eng.lib.ka_ctc_state_posteriors_batch_f32(eng.handle, n, k[0][0], T[0], V, ld[0], k[1][0], S[0], 1000, 4, term[0], fr[0],
+                                                       Ks[0], k[2][0], ldo[0], k[3][0], ll.ctypes.data, st.ctypes.data,
+                                                       _lib.KA_MEM_DEVICE, stream)
+        _lib.check(rc, "ka_ctc_state_posteriors_batch_f32")
+
+    need = eng.lib.ka_state_posterior_workspace_bytes(n, T[0], S[0], Ks[0], V, 1000, 4, _lib.KA_MEM_DEVICE)
+    eng.reserve(need)
+    call()                                   # warm-up
+    ms = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call()                               # (the call synchronises its stream)
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return ms, st, ll
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="single,b1024,b8192,corpus")
@@ -112,8 +152,8 @@ def main():
     cases = a.cases.split(",")
     b1024 = None
     for case in cases:
-        occ = case.startswith("occ_")
-        case_in = case[4:] if occ else case
+        kind = case.split("_")[0] if case.startswith(("occ_", "state_")) else "path"
+        case_in = case[len(kind) + 1:] if kind != "path" else case
         if case_in == "single":
             lps, labs = cfg2(1)
         elif case_in in ("b1024", "b8192"):
@@ -133,7 +173,7 @@ def main():
             raise SystemExit(f"unknown case {case}")
         if case_in in ("single", "corpus"):
             paths = best_paths(lps, labs)
-        ms, st, ll = (time_occupancy if occ else time_posteriors)(lps, labs, paths, a.reps)
+        ms, st, ll = {"path": time_posteriors, "occ": time_occupancy, "state": time_states}[kind](lps, labs, paths, a.reps)
         frames = sum(int(x.shape[0]) for x in lps)
         line = dict(case=case, lattices=len(lps), frames=frames, ms_min=round(min(ms), 3), ms_median=round(float(np.median(ms)), 3),
                     frames_per_s=frames / (min(ms) / 1e3), status_ok=int((st == 0).sum()), reps=a.reps)
