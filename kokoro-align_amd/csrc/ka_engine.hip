@@ -621,6 +621,17 @@ struct PostCall {
     }
 };
 
+// the FbCkLattice fields that both slot calls (OccCall, StateCall) fill alike: the lattice's slot, its terminal, the column stride
+void fill_slot(ka::FbCkLattice &d, const ka::plan::SlotCarve &c, int64_t terminal, char *ws)
+{
+    d.ck = reinterpret_cast<double *>(ws + c.slot + c.parts.ck);
+    d.ckcol = reinterpret_cast<double *>(ws + c.slot + c.parts.ckcol);
+    d.slab = reinterpret_cast<double *>(ws + c.slot + c.parts.slab);
+    d.col = reinterpret_cast<double *>(ws + c.slot + c.parts.col);
+    d.terminal = (terminal >= 0 && terminal <= INT32_MAX) ? (int32_t)terminal : -1;
+    d.cw = c.parts.cw;
+}
+
 struct OccCall {
     using Desc = ka::OccLattice;
     using Carve = ka::plan::OccCarve;
@@ -645,13 +656,8 @@ struct OccCall {
             d.occ = occupancy[i];
             d.ld_out = ld_out[i];
         }
-        d.ck = reinterpret_cast<double *>(ws + c.slot + c.parts.ck);
-        d.ckcol = reinterpret_cast<double *>(ws + c.slot + c.parts.ckcol);
-        d.slab = reinterpret_cast<double *>(ws + c.slot + c.parts.slab);
-        d.col = reinterpret_cast<double *>(ws + c.slot + c.parts.col);
+        fill_slot(d, c, terminal[i], ws);
         d.gbin = reinterpret_cast<unsigned long long *>(ws + c.slot + c.parts.gbin);
-        d.terminal = (terminal[i] >= 0 && terminal[i] <= INT32_MAX) ? (int32_t)terminal[i] : -1;
-        d.cw = c.parts.cw;
     }
     int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
     int stage(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
@@ -706,14 +712,9 @@ struct StateCall {
             d.band_lo = band_lo[i];
             d.ld_out = ld_out[i];
         }
+        fill_slot(d, c, terminal[i], ws);
         d.frames = reinterpret_cast<const int64_t *>(ws + c.frames);
-        d.ck = reinterpret_cast<double *>(ws + c.slot + c.parts.ck);
-        d.ckcol = reinterpret_cast<double *>(ws + c.slot + c.parts.ckcol);
-        d.slab = reinterpret_cast<double *>(ws + c.slot + c.parts.slab);
-        d.col = reinterpret_cast<double *>(ws + c.slot + c.parts.col);
         d.K = (int32_t)K[i];
-        d.terminal = (terminal[i] >= 0 && terminal[i] <= INT32_MAX) ? (int32_t)terminal[i] : -1;
-        d.cw = c.parts.cw;
         d.W = c.W;
     }
     int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }

@@ -666,15 +666,20 @@ inline OccParts occ_parts(const Shape &sh, int32_t V, int32_t beam, int32_t max_
     o.bytes = off;
     return o;
 }
-struct OccCarve : FbCarve {
+struct SlotCarve : FbCarve {
     size_t slot;   // base of this lattice's slot
-    size_t occ;    // host buffers only
     OccParts parts;
 };
-inline size_t label_posterior_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move,
-                                        bool host_buffers, OccCarve *cv, size_t *off_res)
+struct OccCarve : SlotCarve {
+    size_t occ;    // host buffers only
+};
+// the layout both slot planners share: descriptors of desc_bytes each, results, then per lattice what own(i, sh, c, off)
+// carves (false: an unsupported lattice), then the slots
+template <class Carve, class Own>
+inline size_t slot_workspace(int32_t n, size_t desc_bytes, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move,
+                             Carve *cv, size_t *off_res, Own own)
 {
-    size_t off = align_up((size_t)n * sizeof(OccLattice));
+    size_t off = align_up((size_t)n * desc_bytes);
     if (off_res) *off_res = off;
     off += align_up((size_t)n * sizeof(PostResult));
     int32_t n_fast = 0, n_gen = 0;
@@ -682,17 +687,13 @@ inline size_t label_posterior_workspace(int32_t n, const int64_t *T, const int64
     for (int32_t i = 0; i < n; ++i) {
         Shape sh;
         if (!shape_of(T[i], S[i], V, beam, max_move, sh)) return 0;
-        OccCarve c{};
+        Carve c{};
         c.parts = occ_parts(sh, V, beam, max_move);
         c.fast = posterior_fast(sh.S, V, beam, max_move);
         size_t &slot_bytes = c.fast ? fast_bytes : gen_bytes;
         slot_bytes = std::max(slot_bytes, c.parts.bytes);
         c.slot = (size_t)(c.fast ? n_fast++ : n_gen++);   // (the lattice's rank in its form until the slots are placed)
-        if (host_buffers) {
-            carve_staged(off, sh, V, c);
-            c.occ = off;
-            off += align_up((size_t)sh.T * (size_t)V * 4);
-        }
+        if (!own(i, sh, c, off)) return 0;
         if (cv) cv[i] = c;
     }
     const size_t fast_base = off;
@@ -702,10 +703,22 @@ inline size_t label_posterior_workspace(int32_t n, const int64_t *T, const int64
     off += (size_t)gen_slots * gen_bytes;
     if (cv)
         for (int32_t i = 0; i < n; ++i) {
-            OccCarve &c = cv[i];
+            Carve &c = cv[i];
             c.slot = c.fast ? fast_base + (c.slot % (size_t)fast_slots) * fast_bytes : gen_base + (c.slot % (size_t)gen_slots) * gen_bytes;
         }
     return off;
+}
+inline size_t label_posterior_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move,
+                                        bool host_buffers, OccCarve *cv, size_t *off_res)
+{
+    return slot_workspace(n, sizeof(OccLattice), T, S, V, beam, max_move, cv, off_res, [&](int32_t, const Shape &sh, OccCarve &c, size_t &off) {
+        if (host_buffers) {
+            carve_staged(off, sh, V, c);
+            c.occ = off;
+            off += align_up((size_t)sh.T * (size_t)V * 4);
+        }
+        return true;
+    });
 }
 
 }  // namespace plan
@@ -718,7 +731,7 @@ namespace plan {
 // label_posterior_workspace's layout and slots (the slot's V-wide global bins go unused), with StateLattice descriptors, and
 // per lattice its uploaded frame list (K int64, in both memory modes) and, for host buffers, the staged gamma [K, W] and
 // band_lo [K] beside the staged log-probs and labels.
-struct StateCarve : OccCarve {
+struct StateCarve : SlotCarve {
     size_t frames;           // uploaded frame list
     size_t gamma, band_lo;   // host buffers only
     int32_t W;
@@ -726,21 +739,9 @@ struct StateCarve : OccCarve {
 inline size_t state_posterior_workspace(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t V, int32_t beam,
                                         int32_t max_move, bool host_buffers, StateCarve *cv, size_t *off_res)
 {
-    size_t off = align_up((size_t)n * sizeof(StateLattice));
-    if (off_res) *off_res = off;
-    off += align_up((size_t)n * sizeof(PostResult));
-    int32_t n_fast = 0, n_gen = 0;
-    size_t fast_bytes = 0, gen_bytes = 0;
-    for (int32_t i = 0; i < n; ++i) {
-        Shape sh;
-        if (!shape_of(T[i], S[i], V, beam, max_move, sh) || K[i] < 0 || K[i] > T[i]) return 0;
-        StateCarve c{};
-        c.parts = occ_parts(sh, V, beam, max_move);
-        c.fast = posterior_fast(sh.S, V, beam, max_move);
+    return slot_workspace(n, sizeof(StateLattice), T, S, V, beam, max_move, cv, off_res, [&](int32_t i, const Shape &sh, StateCarve &c, size_t &off) {
+        if (K[i] < 0 || K[i] > T[i]) return false;
         c.W = (int32_t)sh.W;
-        size_t &slot_bytes = c.fast ? fast_bytes : gen_bytes;
-        slot_bytes = std::max(slot_bytes, c.parts.bytes);
-        c.slot = (size_t)(c.fast ? n_fast++ : n_gen++);   // (the lattice's rank in its form until the slots are placed)
         c.frames = off;
         off += align_up((size_t)K[i] * 8);
         if (host_buffers) {
@@ -750,19 +751,8 @@ inline size_t state_posterior_workspace(int32_t n, const int64_t *T, const int64
             c.band_lo = off;
             off += align_up((size_t)K[i] * 8);
         }
-        if (cv) cv[i] = c;
-    }
-    const size_t fast_base = off;
-    const int32_t fast_slots = std::min(n_fast, kOccFastSlots), gen_slots = std::min(n_gen, kOccGenericSlots);
-    off += (size_t)fast_slots * fast_bytes;
-    const size_t gen_base = off;
-    off += (size_t)gen_slots * gen_bytes;
-    if (cv)
-        for (int32_t i = 0; i < n; ++i) {
-            StateCarve &c = cv[i];
-            c.slot = c.fast ? fast_base + (c.slot % (size_t)fast_slots) * fast_bytes : gen_base + (c.slot % (size_t)gen_slots) * gen_bytes;
-        }
-    return off;
+        return true;
+    });
 }
 
 }  // namespace plan

@@ -1,6 +1,7 @@
-// ka_posterior_common.hpp — the forward-backward core shared by ka_posterior.hpp (best-path posteriors) and ka_occupancy.hpp
-// (label occupancy posteriors): base-2 log-sum-exp, the band and its walk, status flags, wave and block reductions, and the
-// frame recurrences themselves, one forward and one backward per form (fb_fast_fwd / fb_fast_bwd, fb_gen_fwd / fb_gen_bwd).
+// ka_posterior_common.hpp — the forward-backward core shared by ka_posterior.hpp (best-path posteriors) and ka_fb_ck.hpp
+// (the checkpointed pass of label occupancy and state posteriors): base-2 log-sum-exp, the band and its walk, status flags,
+// wave and block reductions, and the frame recurrences themselves, one forward and one backward per form (fb_fast_fwd /
+// fb_fast_bwd, fb_gen_fwd / fb_gen_bwd).
 // The callers differ only in where a cell's label comes from and what they do with a cell once it is computed; both are
 // template arguments, so each recurrence exists once and every caller runs the same expressions on the same operands.
 #pragma once

@@ -161,33 +161,30 @@ struct PostResult {
 constexpr int kOccFastSlots = 1024;    // fast-form lattices resident at once (four wavefronts per CU): per-slot workspace
 constexpr int kOccGenericSlots = 512;  // generic-form workgroups of one launch, each walking its lattices in turn
 constexpr int kOccLdsBins = 2048;      // generic form: V up to this bins in LDS, above it in a workspace row
-struct OccLattice : FbLattice {
-    float *occ;                   // [T, ld_out] output, V columns written
+// what the checkpointed forward-backward (ka_fb_ck.hpp) reads of a lattice: its slot and terminal
+struct FbCkLattice : FbLattice {
     double *ck;                   // [nblk][2] forward offset C and frame maximum m before the first frame of every block (slot)
     double *ckcol;                // [nblk][cw] alpha column before the first frame of every block, relative to its offset (slot)
     double *slab;                 // [kPostCk][cw] alpha of the block being walked back (slot)
     double *col;                  // generic form only: 4 x L doubles, the working columns (slot)
-    unsigned long long *gbin;     // generic form, V > kOccLdsBins only: [V] fixed-point bins (slot)
     int64_t ld_out;
     int32_t terminal;             // s*, or -1 for a value outside int32
     int32_t cw;                   // column stride of ckcol / slab: 1024 (fast form, slot = position & 1023) or the band width
 };
+struct OccLattice : FbCkLattice {
+    float *occ;                   // [T, ld_out] output, V columns written
+    unsigned long long *gbin;     // generic form, V > kOccLdsBins only: [V] fixed-point bins (slot)
+};
 // ---- state posteriors at chosen frames (ka_state_posterior.hpp): the occupancy's slots and form split ----
-struct StateLattice : FbLattice {
+struct StateLattice : FbCkLattice {
     float *gamma;                 // [K, ld_out] output, W columns written
     int64_t *band_lo;             // [K] output: the band's low end at every query frame
     const int64_t *frames;        // [K] query frames, strictly increasing in [0, T) (workspace)
-    double *ck;                   // as OccLattice (slot)
-    double *ckcol;
-    double *slab;
-    double *col;
-    int64_t ld_out;
     int32_t K;
-    int32_t terminal;             // s*, or -1 for a value outside int32
-    int32_t cw;                   // column stride of ckcol / slab (as OccLattice)
     int32_t W;                    // widest band: max(1, min(beam, L))
 };
 // the workspace planners (ka_plan.hpp) carve n descriptors: their sizes are part of the published workspace byte counts
-static_assert(sizeof(PostLattice) == 88 && sizeof(OccLattice) == 120 && sizeof(StateLattice) == 136, "descriptor sizes");
+static_assert(sizeof(PostLattice) == 88 && sizeof(FbCkLattice) == 104 && sizeof(OccLattice) == 120 && sizeof(StateLattice) == 136,
+              "descriptor sizes");
 
 }  // namespace ka
