@@ -18,10 +18,14 @@ from . import encoder, transcript  # noqa: F401
 from .align import (  # noqa: F401
     align,
     best_path,
-    boundary_frames,
     ctc_best_path,
     ctc_best_path_batch,
     ctc_best_path_device,
+    log_softmax_device,
+    pandas_read_align,
+)
+from .posteriors import (  # noqa: F401
+    boundary_frames,
     ctc_label_posteriors,
     ctc_label_posteriors_batch,
     ctc_label_posteriors_device,
@@ -32,8 +36,6 @@ from .align import (  # noqa: F401
     ctc_state_posteriors_batch,
     ctc_state_posteriors_device,
     lattice_log_likelihood,
-    log_softmax_device,
-    pandas_read_align,
     segment_agreement,
     segment_boundary_confidence,
     segment_confidence,

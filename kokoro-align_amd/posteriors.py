@@ -1,0 +1,460 @@
+"""Forward-backward over the band of ``ctc_best_path``: path posteriors, label occupancy, state posteriors at chosen frames.
+
+The three calls take the same lattices (log-probs, labels, beam_size, max_move) in host or device memory and answer with one
+log-likelihood and one status per lattice.  ``_Lattices`` is that common input, normalised once and aware of its memory mode;
+``_run_lattices`` is the one C call and the one status handling.  What is a call's own (its extra inputs, its outputs, its
+argument tables) is in its private function; ``X_batch`` and ``X_device`` only choose the memory mode.
+"""
+import contextlib
+
+import numpy as np
+
+from . import _lib
+from .align import _current_device, _i64_array, _is_tensor, _ptr_array, _stream_ptr
+
+_POSTERIOR_LATTICE_STATUSES = (_lib.KA_OK, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_NONFINITE, _lib.KA_ERR_BAD_ARGS,
+                               _lib.KA_ERR_ZERO_MASS)
+
+
+# ------------------------------------------------------------------------------------------
+# the lattices of one call and the call itself
+# ------------------------------------------------------------------------------------------
+class _Lattices:
+    """n lattices as one ``ka_ctc_*_posteriors_batch_f32`` call takes them: ``lps`` float32 [T_i, V] with unit column
+    stride, ``labs`` int32 [S_i].  What differs between host and device memory is in the attributes ``mode`` brings:
+    form, mem, dev, ptr(x), ld(x) (row pitch), int32(x) (a per-position input as the call wants it), empty(shape, dtype),
+    engine(), stream(), guard()."""
+
+    def __init__(self, lps, labels, V, **mode):
+        self.__dict__.update(mode)
+        self.lps, self.V, self.n = lps, V, len(lps)
+        self.labs = [self.int32(x) for x in labels]
+        self.T = [int(x.shape[0]) for x in lps]
+        self.S = [int(x.shape[0]) for x in self.labs]
+
+
+def _host_lattices(log_probs_list, labels_list, others, what, device):
+    """The input handling of the ``*_batch`` calls: contiguous NumPy arrays in, NumPy results; None for an empty batch.
+    ``others`` holds the call's own input (one best path or terminal per lattice) and is only counted here."""
+    n = len(log_probs_list)
+    if n != len(labels_list) or n != len(others):
+        raise ValueError(f"log_probs, labels and {what} must be lists of one length")
+    if n == 0:
+        return None
+    lps = [np.ascontiguousarray(x, dtype=np.float32) for x in log_probs_list]
+    V = lps[0].shape[1] if lps[0].ndim == 2 else 0
+    for x in lps:
+        if x.ndim != 2 or x.shape[1] != V:
+            raise ValueError("all log_probs must be [T_i, V] with one V")
+        if x.shape[0] == 0:
+            raise IndexError("list index out of range")
+    return _Lattices(lps, labels_list, V, form="batch", mem=_lib.KA_MEM_HOST, dev=None, ptr=lambda x: x.ctypes.data,
+                     ld=lambda x: x.shape[1], int32=lambda x: np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32),
+                     empty=np.empty, engine=lambda: _lib.default_engine(_current_device() if device is None else device),
+                     stream=lambda: None, guard=contextlib.nullcontext)
+
+
+def _device_lattices(log_probs, labels, others, what):
+    """The input handling of the ``*_device`` calls: tensors on the first log-prob's device in, results there, the call on
+    torch's current stream; ``others`` as in ``_host_lattices``."""
+    import torch
+    n = len(log_probs)
+    if n != len(labels) or n != len(others) or n == 0:
+        raise ValueError(f"log_probs, labels and {what} must be non-empty lists of one length")
+    dev = log_probs[0].device
+    V = int(log_probs[0].shape[1])
+    lps = []
+    for lp in log_probs:
+        if lp.dtype != torch.float32:
+            lp = lp.float()
+        if lp.dim() != 2 or lp.shape[1] != V:
+            raise ValueError("all log_probs must be [T_i, V] tensors with one V")
+        if lp.shape[0] == 0:
+            raise IndexError("list index out of range")
+        if lp.stride(1) != 1:
+            lp = lp.contiguous()
+        lps.append(lp)
+    dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
+    dtypes = {np.float32: torch.float32, np.int64: torch.int64}
+
+    def int32(x):
+        x = x if _is_tensor(x) else torch.as_tensor(np.asarray(x).reshape(-1).astype(np.int32))
+        return x.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+
+    return _Lattices(lps, labels, V, form="device", mem=_lib.KA_MEM_DEVICE, dev=dev, ptr=lambda x: x.data_ptr(),
+                     ld=lambda x: x.stride(0), int32=int32, empty=lambda shape, dtype: torch.empty(shape, dtype=dtypes[dtype], device=dev),
+                     engine=lambda: _lib.default_engine(dev_index), stream=lambda: _stream_ptr(dev_index),
+                     guard=lambda: torch.cuda.device(dev))
+
+
+def _run_lattices(lat, kind, beam_size, max_move, own_args, outs, return_status):
+    """The call ``ka_ctc_<kind>_posteriors_batch_f32``: the arguments all three take around ``own_args`` (the call's own
+    tables), then the results (*outs[i], log_likelihood[i]), ``outs`` a list of tuples, and the status handling of
+    ``return_status``."""
+    name = f"ctc_{kind}_posteriors_{lat.form}"
+    status = np.zeros(lat.n, np.int32)
+    ll = np.zeros(lat.n, np.float64)
+    eng = lat.engine()
+    p_lp, _k1 = _ptr_array([lat.ptr(x) for x in lat.lps])
+    p_lab, _k2 = _ptr_array([lat.ptr(x) for x in lat.labs])
+    p_T, _k3 = _i64_array(lat.T)
+    p_S, _k4 = _i64_array(lat.S)
+    p_ld, _k5 = _i64_array([lat.ld(x) for x in lat.lps])
+    with lat.guard():
+        rc = getattr(eng.lib, f"ka_ctc_{kind}_posteriors_batch_f32")(
+            eng.handle, lat.n, p_lp, p_T, lat.V, p_ld, p_lab, p_S, int(beam_size), int(max_move), *own_args,
+            ll.ctypes.data, status.ctypes.data, lat.mem, lat.stream())
+    results = [(*o, float(z)) for o, z in zip(outs, ll)]
+    if return_status:
+        if rc not in _POSTERIOR_LATTICE_STATUSES:
+            _lib.check(rc, name)
+        return results, status.tolist()
+    _lib.check(rc, name)
+    return results
+
+
+def _outputs(lat, out, shapes, shape_text):
+    """The float32 [rows, columns] outputs of a call: allocated here, or the caller's ``out`` tensors (only the device
+    forms take any) after a check."""
+    if out is None:
+        return [lat.empty(s, np.float32) for s in shapes]
+    import torch
+    if len(out) != lat.n:
+        raise ValueError("out must hold one tensor per lattice")
+    for o, s in zip(out, shapes):
+        if o.dtype != torch.float32 or o.dim() != 2 or tuple(o.shape) != s or o.stride(1) != 1 or o.device != lat.dev:
+            raise ValueError(f"out tensors must be float32 {shape_text} on the input's device with unit column stride")
+    return out
+
+
+def _terminal_of(terminal):
+    """An int, or a best path whose last value is the terminal."""
+    if _is_tensor(terminal):
+        terminal = terminal.detach().reshape(-1)[-1].item() if terminal.dim() > 0 else terminal.item()
+    a = np.asarray(terminal)
+    return int(a.reshape(-1)[-1]) if a.ndim > 0 else int(a)
+
+
+def _segments(seg_ends, T):
+    """(i, a, b) for every segment that ``align()`` writes a line for: frames [a, b) with a = seg_ends[i-1] (0 for the
+    first) and b = seg_ends[i], clipped to the T frames there are."""
+    ends = np.asarray(seg_ends).reshape(-1)
+    return [(i, int(ends[i - 1]) if i > 0 else 0, min(int(ends[i]), T)) for i in range(len(ends))]
+
+
+# ------------------------------------------------------------------------------------------
+# best-path posteriors and lattice log-likelihood
+# ------------------------------------------------------------------------------------------
+def ctc_path_posteriors(log_probs, labels, best_path, beam_size=1000, max_move=4):
+    """How sure the model is of a best path, frame by frame: (posteriors float32 [T], log_likelihood float).
+
+    posteriors[t] is the probability, over every path of the band of ``ctc_best_path`` that ends where ``best_path`` ends,
+    that frame t sits at ``best_path[t]``; log_likelihood is the log of the total probability of those paths (nats).
+    NumPy in -> NumPy out; ROCm torch tensors are handed to ``ctc_path_posteriors_device``.  Raises IndexError for a label
+    outside [0, V), ValueError for NaN / +inf log-probs, a path value outside [0, 2S+1) or a terminal no finite path reaches.
+    """
+    call = ctc_path_posteriors_device if _is_tensor(log_probs) else ctc_path_posteriors_batch
+    (result,) = call([log_probs], [labels], [best_path], beam_size, max_move)
+    return result
+
+
+def _path_posteriors(lat, best_paths, beam_size, max_move, return_status):
+    if lat is None:
+        return ([], []) if return_status else []
+    paths = [lat.int32(x) for x in best_paths]
+    if any(p.shape[0] != T for p, T in zip(paths, lat.T)):
+        raise ValueError("a best path must have one position per frame")
+    posts = [lat.empty(T, np.float32) for T in lat.T]
+    p_path, _k1 = _ptr_array([lat.ptr(x) for x in paths])
+    p_post, _k2 = _ptr_array([lat.ptr(x) for x in posts])
+    return _run_lattices(lat, "path", beam_size, max_move, (p_path, p_post), list(zip(posts)), return_status)
+
+
+def ctc_path_posteriors_batch(log_probs_list, labels_list, best_path_list, beam_size=1000, max_move=4, device=None,
+                              return_status=False):
+    """Posteriors of many lattices in ONE launch; host NumPy buffers in and out.
+
+    Returns a list of (posteriors, log_likelihood); with ``return_status`` also the per-lattice status list, in which case
+    failures do not raise (their posteriors are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    """
+    lat = _host_lattices(log_probs_list, labels_list, best_path_list, "best paths", device)
+    return _path_posteriors(lat, best_path_list, beam_size, max_move, return_status)
+
+
+def ctc_path_posteriors_device(log_probs, labels, best_paths, beam_size=1000, max_move=4, return_status=False):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V], labels [S_i], best paths [T_i] - e.g. the outputs of
+    ``ctc_best_path_device``), list of (posteriors tensor [T_i] on the device, log_likelihood float) out.  One launch on
+    torch's current stream."""
+    lat = _device_lattices(log_probs, labels, best_paths, "best paths")
+    return _path_posteriors(lat, best_paths, beam_size, max_move, return_status)
+
+
+def segment_confidence(posteriors, seg_ends):
+    """Mean and minimum posterior of every segment that ``align()`` writes a line for: frames [a, b) with
+    a = seg_ends[i-1] (0 for the first), b = seg_ends[i], clipped to the posteriors' length.  Returns two float64 arrays
+    (NaN for a segment without frames)."""
+    post = np.asarray(posteriors, dtype=np.float64).reshape(-1)
+    segs = _segments(seg_ends, len(post))
+    mean = np.full(len(segs), np.nan)
+    low = np.full(len(segs), np.nan)
+    for i, a, b in segs:
+        if b > a:
+            mean[i] = post[a:b].mean()
+            low[i] = post[a:b].min()
+    return mean, low
+
+
+# ------------------------------------------------------------------------------------------
+# label occupancy posteriors and a differentiable lattice log-likelihood
+# ------------------------------------------------------------------------------------------
+def ctc_label_posteriors(log_probs, labels, terminal, beam_size=1000, max_move=4):
+    """Per-frame label posteriors of the band's paths that end at ``terminal``: (occ float32 [T, V], log_likelihood float).
+
+    occ[t, v] is the probability that frame t emits label value v (blank = 0), over every path of the band of
+    ``ctc_best_path`` that ends at state ``terminal`` (an int, or a best path whose last value is used); each row sums to 1 and
+    occ equals d log_likelihood / d log_probs.  log_likelihood is the value ``ctc_path_posteriors`` returns for a path that
+    ends there.  NumPy in -> NumPy out; ROCm torch tensors go to ``ctc_label_posteriors_device``.  Raises IndexError for a
+    label outside [0, V), ValueError for NaN / +inf log-probs, a terminal outside [0, 2S+1) or one no finite path reaches.
+    """
+    call = ctc_label_posteriors_device if _is_tensor(log_probs) else ctc_label_posteriors_batch
+    (result,) = call([log_probs], [labels], [terminal], beam_size, max_move)
+    return result
+
+
+def _label_posteriors(lat, terminals, beam_size, max_move, out, return_status):
+    if lat is None:
+        return ([], []) if return_status else []
+    occs = _outputs(lat, out, [(T, lat.V) for T in lat.T], "[T_i, V]")
+    p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
+    p_occ, _k2 = _ptr_array([lat.ptr(x) for x in occs])
+    p_ldo, _k3 = _i64_array([lat.ld(x) for x in occs])
+    return _run_lattices(lat, "label", beam_size, max_move, (p_term, p_occ, p_ldo), list(zip(occs)), return_status)
+
+
+def ctc_label_posteriors_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False):
+    """Label posteriors of many lattices in ONE launch; host NumPy buffers in and out.
+
+    Returns a list of (occ [T_i, V], log_likelihood); with ``return_status`` also the per-lattice status list, in which case
+    failures do not raise (their rows are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    """
+    lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
+    return _label_posteriors(lat, terminals, beam_size, max_move, None, return_status)
+
+
+def ctc_label_posteriors_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]) and terminals (ints
+    or best paths), list of (occ tensor [T_i, V] on the device, log_likelihood float) out.  ``out``: optional list of float32
+    [T_i, V] tensors with unit column stride to write into (views into wider tensors keep their other columns).  One launch
+    on torch's current stream."""
+    lat = _device_lattices(log_probs, labels, terminals, "terminals")
+    return _label_posteriors(lat, terminals, beam_size, max_move, out, return_status)
+
+
+def _lattice_ll_function():
+    import torch
+
+    class LatticeLogLikelihood(torch.autograd.Function):
+        """Z of every lattice (float64 [n]); backward: grad_out[i] * occ_i, the occupancy saved by forward."""
+
+        @staticmethod
+        def forward(ctx, labels, terminals, beam_size, max_move, zero_infinity, *lps):
+            n = len(lps)
+            if lps[0].is_cuda:
+                res, st = ctc_label_posteriors_device([x.detach() for x in lps], labels, terminals, beam_size, max_move,
+                                                      return_status=True)
+            else:
+                res, st = ctc_label_posteriors_batch([x.detach().float().numpy() for x in lps], labels, terminals, beam_size,
+                                                     max_move, return_status=True)
+                res = [(torch.from_numpy(o), z) for o, z in res]
+            for i, s in enumerate(st):
+                if s == _lib.KA_ERR_ZERO_MASS and zero_infinity:
+                    continue
+                if s != _lib.KA_OK:
+                    _raise_lattice_status(s, i)
+            occs, zs = [], []
+            for (o, z), s in zip(res, st):
+                if s == _lib.KA_ERR_ZERO_MASS:
+                    o = torch.zeros_like(o)
+                    z = 0.0
+                occs.append(o)
+                zs.append(z)
+            ctx.occs = occs
+            ctx.dtypes = [x.dtype for x in lps]
+            return torch.tensor(zs, dtype=torch.float64, device=lps[0].device).reshape(n)
+
+        @staticmethod
+        def backward(ctx, grad_out):
+            grads = [(g * o.to(torch.float64)).to(dt) for g, o, dt in zip(grad_out.unbind(0), ctx.occs, ctx.dtypes)]
+            ctx.occs = None
+            return (None, None, None, None, None, *grads)
+
+    return LatticeLogLikelihood
+
+
+_LATTICE_LL = None
+
+
+def _raise_lattice_status(st, i):
+    what = f"lattice_log_likelihood: lattice {i}"
+    if st == _lib.KA_ERR_BAD_LABEL:
+        raise IndexError(f"{what}: label outside [0, V)")
+    if st == _lib.KA_ERR_NAN:
+        raise ValueError(f"{what}: log_probs contain NaN")
+    if st == _lib.KA_ERR_NONFINITE:
+        raise ValueError(f"{what}: a log-prob is +inf")
+    if st == _lib.KA_ERR_BAD_ARGS:
+        raise ValueError(f"{what}: terminal outside [0, 2S+1)")
+    if st == _lib.KA_ERR_ZERO_MASS:
+        raise ValueError(f"{what}: no path of finite score reaches the terminal")
+    raise _lib.KAError(f"{what}: status {st}")
+
+
+def lattice_log_likelihood(log_probs, labels, terminal, beam_size=1000, max_move=4, zero_infinity=False):
+    """Differentiable log-likelihood Z of the band's paths that end at ``terminal`` (this engine's topology: band, moves,
+    label-0 veto), float64 on the input's device.  One [T, V] tensor (labels, terminal for it) -> 0-d; a list of them (lists
+    of labels and terminals) -> [n].  The gradient with respect to the log-probs is the label occupancy (``ctc_label_posteriors``)
+    times the incoming gradient; the forward pass saves it, so backward launches nothing.  With ``zero_infinity``, a lattice
+    whose terminal no finite path reaches gives 0 and a zero gradient (as ``torch.nn.CTCLoss``); otherwise, and for every
+    other failure, this raises as ``ctc_label_posteriors`` does."""
+    global _LATTICE_LL
+    if _LATTICE_LL is None:
+        _LATTICE_LL = _lattice_ll_function()
+    single = _is_tensor(log_probs)
+    lps = [log_probs] if single else list(log_probs)
+    labs = [labels] if single else list(labels)
+    terms = [terminal] if single else list(terminal)
+    if len(lps) == 0 or len(labs) != len(lps) or len(terms) != len(lps):
+        raise ValueError("log_probs, labels and terminals must be non-empty lists of one length")
+    z = _LATTICE_LL.apply(labs, [_terminal_of(s) for s in terms], int(beam_size), int(max_move), bool(zero_infinity), *lps)
+    return z[0] if single else z
+
+
+def segment_agreement(occ, labels, best_path, seg_ends):
+    """Soft transcript agreement of every segment that ``align()`` writes a line for: the mean over its frames [a, b)
+    (a = seg_ends[i-1], 0 for the first, b = seg_ends[i], clipped to the frames) of occ[t, lab'[best_path[t]]], the
+    occupancy of the label the best path emits.  float64 array, NaN for a segment without frames."""
+    occ = np.asarray(occ.detach().cpu() if _is_tensor(occ) else occ, dtype=np.float64)
+    lab = np.zeros(2 * len(np.asarray(labels).reshape(-1)) + 1, np.int64)
+    lab[1::2] = np.asarray(labels).reshape(-1)
+    path = np.asarray(best_path).reshape(-1).astype(np.int64)
+    T = min(len(path), occ.shape[0])
+    agree = occ[np.arange(T), lab[path[:T]]]
+    segs = _segments(seg_ends, T)
+    mean = np.full(len(segs), np.nan)
+    for i, a, b in segs:
+        if b > a:
+            mean[i] = agree[a:b].mean()
+    return mean
+
+
+# ------------------------------------------------------------------------------------------
+# state posteriors at chosen frames and the confidence of align()'s text boundaries
+# ------------------------------------------------------------------------------------------
+def _frames_of(frames, T):
+    """A query frame list as int64 NumPy, checked: strictly increasing in [0, T)."""
+    if _is_tensor(frames):
+        frames = frames.detach().cpu().numpy()
+    f = np.ascontiguousarray(np.asarray(frames).reshape(-1), dtype=np.int64)
+    if len(f) and (f[0] < 0 or f[-1] >= T or np.any(np.diff(f) <= 0)):
+        raise ValueError(f"frames must be strictly increasing in [0, {T})")
+    return f
+
+
+def _band_width(S, beam_size):
+    """W = max(1, min(beam_size, 2S+1)): the widest band, the row length of a state posterior."""
+    return max(1, min(int(beam_size), 2 * int(S) + 1))
+
+
+def ctc_state_posteriors(log_probs, labels, terminal, frames, beam_size=1000, max_move=4):
+    """Posterior of every band position at chosen frames: (gamma float32 [K, W], band_lo int64 [K], log_likelihood float).
+
+    gamma[k, j] is the probability that frame ``frames[k]`` sits at state band_lo[k] + j, over every path of the band of
+    ``ctc_best_path`` that ends at state ``terminal`` (an int, or a best path whose last value is used); columns past the
+    band's width are 0, each row sums to 1.  W = min(beam_size, 2S+1).  ``frames``: strictly increasing in [0, T).
+    NumPy in -> NumPy out; ROCm torch tensors go to ``ctc_state_posteriors_device``.  Raises as ``ctc_label_posteriors``,
+    and ValueError for bad frames.
+    """
+    call = ctc_state_posteriors_device if _is_tensor(log_probs) else ctc_state_posteriors_batch
+    (result,) = call([log_probs], [labels], [terminal], [frames], beam_size, max_move)
+    return result
+
+
+def _state_posteriors(lat, terminals, frames, beam_size, max_move, out, return_status):
+    if lat is None:
+        return ([], []) if return_status else []
+    if len(frames) != lat.n:
+        raise ValueError("frames must hold one list per lattice")
+    frames = [_frames_of(f, T) for f, T in zip(frames, lat.T)]      # (host memory in both forms)
+    Ws = [_band_width(S, beam_size) for S in lat.S]
+    gammas = _outputs(lat, out, [(len(f), W) for f, W in zip(frames, Ws)], "[K_i, W_i]")
+    los = [lat.empty(len(f), np.int64) for f in frames]
+    p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
+    p_fr, _k2 = _ptr_array([f.ctypes.data for f in frames])
+    p_K, _k3 = _i64_array([len(f) for f in frames])
+    p_g, _k4 = _ptr_array([lat.ptr(g) for g in gammas])
+    p_ldo, _k5 = _i64_array([max(lat.ld(g), W) for g, W in zip(gammas, Ws)])   # (a tensor with no rows may report any stride)
+    p_lo, _k6 = _ptr_array([lat.ptr(x) for x in los])
+    return _run_lattices(lat, "state", beam_size, max_move, (p_term, p_fr, p_K, p_g, p_ldo, p_lo), list(zip(gammas, los)),
+                         return_status)
+
+
+def ctc_state_posteriors_batch(log_probs_list, labels_list, terminals, frames_list, beam_size=1000, max_move=4, device=None,
+                               return_status=False):
+    """State posteriors of many lattices in ONE launch; host NumPy buffers in and out.
+
+    Returns a list of (gamma [K_i, W_i], band_lo [K_i], log_likelihood); with ``return_status`` also the per-lattice status
+    list, in which case failures do not raise (their rows are NaN, band_lo -1, their log-likelihood NaN, or -inf for
+    KA_ERR_ZERO_MASS).
+    """
+    lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
+    return _state_posteriors(lat, terminals, frames_list, beam_size, max_move, None, return_status)
+
+
+def ctc_state_posteriors_device(log_probs, labels, terminals, frames, beam_size=1000, max_move=4, out=None, return_status=False):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]), terminals (ints or
+    best paths) and host frame lists (strictly increasing in [0, T_i)); list of (gamma tensor [K_i, W_i], band_lo int64 tensor
+    [K_i], both on the device, log_likelihood float) out, W_i = min(beam_size, 2 S_i + 1).  ``out``: optional list of float32
+    [K_i, W_i] tensors with unit column stride to write gamma into (views into wider tensors keep their other columns).  One
+    launch on torch's current stream."""
+    lat = _device_lattices(log_probs, labels, terminals, "terminals")
+    return _state_posteriors(lat, terminals, frames, beam_size, max_move, out, return_status)
+
+
+def boundary_frames(seg_ends, T):
+    """The frames ``align()`` reads the best path at, sorted and unique: 0 (the first segment's start) and every
+    seg_ends[i] < T (a segment's end, which is also the next one's start).  int64 array."""
+    ends = np.asarray(seg_ends, dtype=np.int64).reshape(-1)
+    return np.unique(np.concatenate([np.zeros(1, np.int64), ends[ends < int(T)]]))
+
+
+def segment_boundary_confidence(gamma, band_lo, frames, best_path, seg_ends, n_phonemes):
+    """How likely each text boundary ``align()`` writes is right, from state posteriors at ``boundary_frames`` (host only).
+
+    For segment i (frames [a, b), a = seg_ends[i-1], 0 for the first, b = seg_ends[i]) ``align()`` writes text_start =
+    min(best_path[a] // 2, n_phonemes) and text_end = min(best_path[b] // 2, n_phonemes), or n_phonemes where b >= T.  With
+    state s read as text index min(s // 2, n_phonemes), p_start[i] is the posterior probability of text_start at frame a and
+    p_end[i] that of text_end at frame b (1.0 where b >= T).  Returns two float64 arrays.  Raises ValueError if a frame it
+    needs is not in ``frames``."""
+    g = np.asarray(gamma.detach().cpu() if _is_tensor(gamma) else gamma, dtype=np.float64)
+    lo = np.asarray(band_lo.detach().cpu() if _is_tensor(band_lo) else band_lo, dtype=np.int64).reshape(-1)
+    fr = np.asarray(frames.detach().cpu() if _is_tensor(frames) else frames, dtype=np.int64).reshape(-1)
+    path = np.asarray(best_path.detach().cpu() if _is_tensor(best_path) else best_path, dtype=np.int64).reshape(-1)
+    T, n_ph = len(path), int(n_phonemes)
+    row_of = {int(f): k for k, f in enumerate(fr)}
+    cols = np.arange(g.shape[1] if g.ndim == 2 else 0, dtype=np.int64)
+
+    def p_at(t):
+        k = row_of.get(int(t))
+        if k is None:
+            raise ValueError(f"segment_boundary_confidence: frame {int(t)} is not among the query frames")
+        want = min(int(path[t]) // 2, n_ph)
+        text = np.minimum((lo[k] + cols) // 2, n_ph)
+        return float(np.sum(g[k][text == want]))
+
+    segs = _segments(np.asarray(seg_ends, dtype=np.int64), T)
+    p_start = np.empty(len(segs))
+    p_end = np.empty(len(segs))
+    for i, a, b in segs:                                # (b is clipped to T: b < T is seg_ends[i] < T)
+        p_start[i] = p_at(a)
+        p_end[i] = p_at(b) if b < T else 1.0
+    return p_start, p_end

@@ -2,7 +2,6 @@
 torch autograd of a dense banded alpha recursion and finite differences of Z, its invariants, and the C-ABI / Python boundary
 of the feature (no compute: there is no GPU)."""
 import ctypes
-import os
 import re
 
 import numpy as np
@@ -10,20 +9,10 @@ import pytest
 
 import occupancy_ref as Q
 import posterior_ref as R
+from fb_harness import assert_declared_exported_bound, header_text, tiny as _tiny
 from oracle import oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("ka_ctc_label_posteriors_f32", "ka_ctc_label_posteriors_batch_f32", "ka_label_posterior_workspace_bytes")
-
-
-def _tiny(rng, T, S, V, zero_label=False, ninf=False):
-    lp = np.log(rng.dirichlet(np.ones(V), size=T)).astype(np.float32)
-    labels = rng.integers(1, V, size=S).astype(np.int32)
-    if zero_label and S:
-        labels[rng.integers(0, S)] = 0
-    if ninf:
-        lp[rng.integers(0, T), rng.integers(0, V)] = -np.inf
-    return lp, labels
 
 
 @pytest.mark.parametrize("mm", [1, 2, 3, 4, 5])
@@ -110,25 +99,10 @@ def test_reference_statuses():
     assert got["status"] == R.ZERO_MASS and got["ll"] == -np.inf and np.isnan(got["occ"]).all()
 
 
-def _declared():
-    text = open(os.path.join(ROOT, "include", "kokoro_align_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return set(re.findall(r"\b(ka_[a-z0-9_]+)\s*\(", text))
-
-
 def test_new_symbols_declared_exported_and_bound():
-    import kokoro_align_amd as ka
-    from kokoro_align_amd import _lib
-    declared = _declared()
-    lib = ctypes.CDLL(ka.build_library())
-    L = _lib.load_library()
-    for name in NEW_SYMBOLS:
-        assert name in declared, name
-        assert hasattr(lib, name), name
-        assert name in _lib.EXPORTS and getattr(L, name).argtypes is not None, name
+    lib = assert_declared_exported_bound(NEW_SYMBOLS)
     assert lib.ka_version() >= 102
-    text = open(os.path.join(ROOT, "include", "kokoro_align_amd.h")).read()
-    assert int(re.search(r"#define KA_VERSION (\d+)", text).group(1)) >= 102
+    assert int(re.search(r"#define KA_VERSION (\d+)", header_text()).group(1)) >= 102
 
 
 def test_workspace_is_bounded_by_resident_lattices():

@@ -1,13 +1,12 @@
 """Label occupancy posteriors and the differentiable lattice log-likelihood on the MI355X, through the C ABI and the Python
 API, against the float64 reference (tests/occupancy_ref.py): |d occ| <= 1e-3, |row sum - 1| <= 1e-4, occ[T-1, lab'[s*]] = 1
 exactly, Z within 1e-9 max(1, |Z|) of ka_ctc_path_posteriors' Z for a path that ends at s*."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import occupancy_ref as Q
 import posterior_ref as R
+from fb_harness import I, engine, label_call as _call, path_z_one as _path_z
 from golden_util import g1_cases, g2_cases, g3_case
 from oracle import oracle as O
 
@@ -16,46 +15,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def env():
-    import torch
-    assert torch.cuda.is_available(), "the GPU tests need a device"
-    import kokoro_align_amd as ka
-    from kokoro_align_amd import _lib
-    eng = _lib.default_engine(torch.cuda.current_device())
-    eng.set_mode("auto")
-    eng.set_backtrace("auto")
-    return ka, _lib, eng
-
-
-P = lambda xs: ctypes.cast((ctypes.c_void_p * len(xs))(*[x.ctypes.data for x in xs]), ctypes.POINTER(ctypes.c_void_p))
-I = lambda xs: (ctypes.c_int64 * len(xs))(*[int(v) for v in xs])
-
-
-def _call(eng, _lib, lps, labs, terms, beam, mm):
-    """The batch entry point on host buffers: (occ list, log-likelihoods, statuses, rc)."""
-    n = len(lps)
-    lps = [np.ascontiguousarray(x, np.float32) for x in lps]
-    labs = [np.ascontiguousarray(x, np.int32) for x in labs]
-    V = lps[0].shape[1]
-    occs = [np.full((x.shape[0], V), -7.0, np.float32) for x in lps]
-    ll = np.zeros(n, np.float64)
-    st = np.full(n, 99, np.int32)
-    rc = eng.lib.ka_ctc_label_posteriors_batch_f32(eng.handle, n, P(lps), I([x.shape[0] for x in lps]), V, I([V] * n), P(labs),
-                                                   I([x.shape[0] for x in labs]), beam, mm, I(terms), P(occs), I([V] * n),
-                                                   ll.ctypes.data, st.ctypes.data, _lib.KA_MEM_HOST, None)
-    return occs, ll, st, rc
-
-
-def _path_z(eng, _lib, lp, labels, terminal, beam, mm):
-    """ka_ctc_path_posteriors' Z for a path that ends at the terminal."""
-    path = np.full(lp.shape[0], terminal, np.int32)
-    post = np.zeros(lp.shape[0], np.float32)
-    ll = np.zeros(1, np.float64)
-    lp = np.ascontiguousarray(lp, np.float32)
-    labels = np.ascontiguousarray(labels, np.int32)
-    eng.lib.ka_ctc_path_posteriors_f32(eng.handle, lp.ctypes.data, lp.shape[0], lp.shape[1], lp.shape[1], labels.ctypes.data,
-                                       labels.shape[0], beam, mm, path.ctypes.data, post.ctypes.data, ll.ctypes.data,
-                                       _lib.KA_MEM_HOST, None)
-    return ll[0]
+    return engine()
 
 
 def _check(occ, ll, lp, labels, terminal, beam, mm, what, eng=None, _lib=None, ref=None):
@@ -278,9 +238,7 @@ def test_cfg2_batch_of_1024(env):
 def test_workspace_bytes_for_8192_cfg2(env):
     ka, _lib, eng = env
     n = 8192
-    T = (ctypes.c_int64 * n)(*[50000] * n)
-    S = (ctypes.c_int64 * n)(*[5000] * n)
-    assert 0 < eng.lib.ka_label_posterior_workspace_bytes(n, T, S, 64, 1000, 4, _lib.KA_MEM_DEVICE) <= 16 << 30
+    assert 0 < eng.lib.ka_label_posterior_workspace_bytes(n, I([50000] * n), I([5000] * n), 64, 1000, 4, _lib.KA_MEM_DEVICE) <= 16 << 30
 
 
 def test_best_path_bits_unchanged_by_a_label_posterior_call(env):

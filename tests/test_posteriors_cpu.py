@@ -1,27 +1,16 @@
 """Best-path posteriors and lattice log-likelihood, CPU side: the float64 reference (tests/posterior_ref.py) against brute-force
 path enumeration and its own invariants, and the C-ABI / Python boundary of the feature (no compute: there is no GPU)."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 
 import posterior_ref as R
+from fb_harness import assert_declared_exported_bound, header_text, tiny as _tiny
 from oracle import oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("ka_ctc_path_posteriors_f32", "ka_ctc_path_posteriors_batch_f32", "ka_posterior_workspace_bytes")
-
-
-def _tiny(rng, T, S, V, zero_label=False, ninf=False):
-    lp = np.log(rng.dirichlet(np.ones(V), size=T)).astype(np.float32)
-    labels = rng.integers(1, V, size=S).astype(np.int32)
-    if zero_label and S:
-        labels[rng.integers(0, S)] = 0
-    if ninf:
-        lp[rng.integers(0, T), rng.integers(0, V)] = -np.inf
-    return lp, labels
 
 
 def _some_path(rng, T, L, beam, mm):
@@ -93,26 +82,12 @@ def test_reference_statuses():
     assert got["status"] == R.ZERO_MASS and got["ll"] == -np.inf and np.isnan(got["post"]).all()
 
 
-def _declared():
-    text = open(os.path.join(ROOT, "include", "kokoro_align_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return set(re.findall(r"\b(ka_[a-z0-9_]+)\s*\(", text))
-
-
 def test_new_symbols_declared_exported_and_bound():
-    import kokoro_align_amd as ka
     from kokoro_align_amd import _lib
-    declared = _declared()
-    lib = ctypes.CDLL(ka.build_library())
-    L = _lib.load_library()
-    for name in NEW_SYMBOLS:
-        assert name in declared, name
-        assert hasattr(lib, name), name
-        assert name in _lib.EXPORTS and getattr(L, name).argtypes is not None, name
+    lib = assert_declared_exported_bound(NEW_SYMBOLS)
     assert lib.ka_version() >= 101
     assert _lib.KA_ERR_ZERO_MASS == -9
-    text = open(os.path.join(ROOT, "include", "kokoro_align_amd.h")).read()
-    assert re.search(r"#define KA_ERR_ZERO_MASS \(-9\)", text)
+    assert re.search(r"#define KA_ERR_ZERO_MASS \(-9\)", header_text())
 
 
 def test_workspace_bytes_without_a_device():

@@ -1,11 +1,10 @@
 """Best-path posteriors and lattice log-likelihood on the MI355X, all through the C ABI, against the float64 reference
 (tests/posterior_ref.py): |d posterior| <= 1e-3, |d log-likelihood| <= 1e-3 + 1e-6 T nats."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import posterior_ref as R
+from fb_harness import engine, path_call as _call
 from golden_util import g1_cases, g2_cases, g3_case
 from oracle import oracle as O
 
@@ -14,34 +13,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def env():
-    import torch
-    assert torch.cuda.is_available(), "the GPU tests need a device"
-    import kokoro_align_amd as ka
-    from kokoro_align_amd import _lib
-    eng = _lib.default_engine(torch.cuda.current_device())
-    eng.set_mode("auto")
-    eng.set_backtrace("auto")
-    return ka, _lib, eng
-
-
-def _call(eng, _lib, lps, labs, paths, beam, mm):
-    """The batch entry point on host buffers: (posteriors list, log-likelihoods, statuses, rc)."""
-    n = len(lps)
-    lps = [np.ascontiguousarray(x, np.float32) for x in lps]
-    labs = [np.ascontiguousarray(x, np.int32) for x in labs]
-    paths = [np.ascontiguousarray(x, np.int32) for x in paths]
-    V = lps[0].shape[1]
-    posts = [np.full(x.shape[0], -7.0, np.float32) for x in lps]
-    ll = np.zeros(n, np.float64)
-    st = np.full(n, 99, np.int32)
-    P = lambda xs: (ctypes.c_void_p * n)(*[x.ctypes.data for x in xs])
-    I = lambda xs: (ctypes.c_int64 * n)(*[int(v) for v in xs])
-    rc = eng.lib.ka_ctc_path_posteriors_batch_f32(
-        eng.handle, n, ctypes.cast(P(lps), ctypes.POINTER(ctypes.c_void_p)), I([x.shape[0] for x in lps]), V, I([V] * n),
-        ctypes.cast(P(labs), ctypes.POINTER(ctypes.c_void_p)), I([x.shape[0] for x in labs]), beam, mm,
-        ctypes.cast(P(paths), ctypes.POINTER(ctypes.c_void_p)), ctypes.cast(P(posts), ctypes.POINTER(ctypes.c_void_p)),
-        ll.ctypes.data, st.ctypes.data, _lib.KA_MEM_HOST, None)
-    return posts, ll, st, rc
+    return engine()
 
 
 def _check(post, ll, lp, labels, path, beam, mm, what):

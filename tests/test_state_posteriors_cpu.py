@@ -2,7 +2,6 @@
 host-only boundary confidence of align()'s text boundaries on hand-built posteriors, and the float64 reference's gamma
 against the occupancy and path-posterior references it must agree with."""
 import ctypes
-import os
 import re
 
 import numpy as np
@@ -10,35 +9,20 @@ import pytest
 
 import occupancy_ref as Q
 import posterior_ref as R
+from fb_harness import assert_declared_exported_bound, header_text
 from oracle import oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("ka_ctc_state_posteriors_f32", "ka_ctc_state_posteriors_batch_f32", "ka_state_posterior_workspace_bytes")
 
 
-def _declared():
-    text = open(os.path.join(ROOT, "include", "kokoro_align_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return set(re.findall(r"\b(ka_[a-z0-9_]+)\s*\(", text))
-
-
 def test_new_symbols_declared_exported_and_bound():
-    import kokoro_align_amd as ka
-    from kokoro_align_amd import _lib
-    declared = _declared()
-    lib = ctypes.CDLL(ka.build_library())
-    L = _lib.load_library()
-    for name in NEW_SYMBOLS:
-        assert name in declared, name
-        assert hasattr(lib, name), name
-        assert name in _lib.EXPORTS and getattr(L, name).argtypes is not None, name
+    assert_declared_exported_bound(NEW_SYMBOLS)
 
 
 def test_version_is_103():
     from kokoro_align_amd import _lib
     assert _lib.load_library().ka_version() == 103
-    text = open(os.path.join(ROOT, "include", "kokoro_align_amd.h")).read()
-    assert int(re.search(r"#define KA_VERSION (\d+)", text).group(1)) == 103
+    assert int(re.search(r"#define KA_VERSION (\d+)", header_text()).group(1)) == 103
 
 
 def _ws(n, T, S, K, V=64, beam=1000, mm=4, mem=1):

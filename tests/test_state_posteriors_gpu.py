@@ -2,12 +2,11 @@
 (tests/posterior_ref.forward_backward(..., full=True)): |d gamma| <= 1e-3, |row sum - 1| <= 1e-4, band_lo equal to the
 reference's lo, Z within 1e-9 max(1, |Z|) of ka_ctc_label_posteriors' Z, gamma at (T-1, s*) exactly 1; cross-checked with
 the label occupancy and the path posteriors of the same lattice, and end to end through the boundary confidence."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import posterior_ref as R
+from fb_harness import band_width as _W, engine, label_call_one as _label_call, state_call as _call, state_call_one
 from golden_util import g1_cases, g2_cases, g3_case
 from oracle import oracle as O
 
@@ -16,54 +15,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def env():
-    import torch
-    assert torch.cuda.is_available(), "the GPU tests need a device"
-    import kokoro_align_amd as ka
-    from kokoro_align_amd import _lib
-    eng = _lib.default_engine(torch.cuda.current_device())
-    eng.set_mode("auto")
-    eng.set_backtrace("auto")
-    return ka, _lib, eng
-
-
-P = lambda xs: ctypes.cast((ctypes.c_void_p * len(xs))(*[x.ctypes.data for x in xs]), ctypes.POINTER(ctypes.c_void_p))
-I = lambda xs: (ctypes.c_int64 * len(xs))(*[int(v) for v in xs])
-
-
-def _W(S, beam):
-    return max(1, min(beam, 2 * S + 1))
-
-
-def _call(eng, _lib, lps, labs, terms, frames, beam, mm, ld_out=None):
-    """The batch entry point on host buffers: (gamma list, band_lo list, log-likelihoods, statuses, rc)."""
-    n = len(lps)
-    lps = [np.ascontiguousarray(x, np.float32) for x in lps]
-    labs = [np.ascontiguousarray(x, np.int32) for x in labs]
-    frs = [np.ascontiguousarray(np.asarray(f).reshape(-1), np.int64) for f in frames]
-    V = lps[0].shape[1]
-    Ws = [_W(len(x), beam) for x in labs]
-    ldo = ld_out or Ws
-    gs = [np.full((len(f), w), -7.0, np.float32) for f, w in zip(frs, Ws)]
-    los = [np.full(len(f), -9, np.int64) for f in frs]
-    ll = np.zeros(n, np.float64)
-    st = np.full(n, 99, np.int32)
-    rc = eng.lib.ka_ctc_state_posteriors_batch_f32(eng.handle, n, P(lps), I([x.shape[0] for x in lps]), V, I([V] * n), P(labs),
-                                                   I([x.shape[0] for x in labs]), beam, mm, I(terms), P(frs), I([len(f) for f in frs]),
-                                                   P(gs), I(ldo), P(los), ll.ctypes.data, st.ctypes.data, _lib.KA_MEM_HOST, None)
-    return gs, los, ll, st, rc
-
-
-def _label_call(eng, _lib, lp, labels, terminal, beam, mm):
-    """ka_ctc_label_posteriors for one lattice: (occ [T, V], Z)."""
-    lp = np.ascontiguousarray(lp, np.float32)
-    labels = np.ascontiguousarray(labels, np.int32)
-    T, V = lp.shape
-    occ = np.zeros((T, V), np.float32)
-    ll = np.zeros(1, np.float64)
-    rc = eng.lib.ka_ctc_label_posteriors_f32(eng.handle, lp.ctypes.data, T, V, V, labels.ctypes.data, labels.shape[0], beam, mm,
-                                             int(terminal), occ.ctypes.data, V, ll.ctypes.data, _lib.KA_MEM_HOST, None)
-    assert rc == 0
-    return occ, ll[0]
+    return engine()
 
 
 def _ref(lp, labels, terminal, beam, mm):
@@ -290,13 +242,8 @@ def test_bad_frames_and_ld_out_fail_the_call(env):
     # a wider pitch is legal: the other columns are left alone
     gs, los, ll, st, rc = _call(eng, _lib, [lp], [labels], [s], [good], beam, mm)
     assert rc == 0
-    wide = np.full((len(good), W + 5), -3.5, np.float32)
-    lo = np.zeros(len(good), np.int64)
-    z = np.zeros(1, np.float64)
-    fr = np.ascontiguousarray(good, np.int64)
-    rc = eng.lib.ka_ctc_state_posteriors_f32(eng.handle, lp.ctypes.data, T, V, V, labels.ctypes.data, S, beam, mm, s, fr.ctypes.data,
-                                             len(fr), wide.ctypes.data, W + 5, lo.ctypes.data, z.ctypes.data, _lib.KA_MEM_HOST, None)
-    assert rc == 0 and z[0] == ll[0] and np.array_equal(lo, los[0])
+    wide, lo, z, rc = state_call_one(eng, _lib, lp, labels, s, good, beam, mm, ld_out=W + 5, fill=-3.5)
+    assert rc == 0 and z == ll[0] and np.array_equal(lo, los[0])
     assert np.array_equal(wide[:, :W].view(np.int32), gs[0].view(np.int32)) and (wide[:, W:] == -3.5).all()
 
 

@@ -44,25 +44,26 @@ def best_paths(lps, labs):
     return b.path
 
 
-def time_posteriors(lps, labs, paths, reps):
+def time_batch(kind, ws_name, lps, labs, own_args, reps, ws_own=()):
+    """ms per call of ka_ctc_<kind>_posteriors_batch_f32 on device buffers: the arguments the three calls share around
+    ``own_args`` (the caller keeps what they point to alive), the workspace reserved first, one warm-up call."""
+    name = f"ka_ctc_{kind}_posteriors_batch_f32"
     n, V = len(lps), int(lps[0].shape[1])
     eng = _lib.default_engine(torch.cuda.current_device())
-    posts = [torch.empty(int(x.shape[0]), dtype=torch.float32, device="cuda") for x in lps]
     ll = np.zeros(n, np.float64)
     st = np.zeros(n, np.int32)
-    k = [_ptr_array([x.data_ptr() for x in xs]) for xs in (lps, labs, paths, posts)]
+    k = [_ptr_array([x.data_ptr() for x in xs]) for xs in (lps, labs)]
     T = _i64_array([x.shape[0] for x in lps])
     S = _i64_array([x.shape[0] for x in labs])
     ld = _i64_array([x.stride(0) for x in lps])
     stream = _stream_ptr(torch.cuda.current_device())
 
     def call():
-        rc = eng.lib.ka_ctc_path_posteriors_batch_f32(eng.handle, n, k[0][0], T[0], V, ld[0], k[1][0], S[0], 1000, 4, k[2][0], k[3][0],
-                                                      ll.ctypes.data, st.ctypes.data, _lib.KA_MEM_DEVICE, stream)
-        _lib.check(rc, "ka_ctc_path_posteriors_batch_f32")
+        rc = getattr(eng.lib, name)(eng.handle, n, k[0][0], T[0], V, ld[0], k[1][0], S[0], 1000, 4, *own_args,
+                                    ll.ctypes.data, st.ctypes.data, _lib.KA_MEM_DEVICE, stream)
+        _lib.check(rc, name)
 
-    need = eng.lib.ka_posterior_workspace_bytes(n, T[0], S[0], V, 1000, 4, _lib.KA_MEM_DEVICE)
-    eng.reserve(need)
+    eng.reserve(getattr(eng.lib, ws_name)(n, T[0], S[0], *ws_own, V, 1000, 4, _lib.KA_MEM_DEVICE))
     call()                                   # warm-up
     ms = []
     for _ in range(reps):
@@ -71,74 +72,35 @@ def time_posteriors(lps, labs, paths, reps):
         call()                               # (the call synchronises its stream)
         ms.append((time.perf_counter() - t0) * 1e3)
     return ms, st, ll
+
+
+def time_posteriors(lps, labs, paths, reps):
+    posts = [torch.empty(int(x.shape[0]), dtype=torch.float32, device="cuda") for x in lps]
+    k = [_ptr_array([x.data_ptr() for x in xs]) for xs in (paths, posts)]
+    return time_batch("path", "ka_posterior_workspace_bytes", lps, labs, (k[0][0], k[1][0]), reps)
 
 
 def time_occupancy(lps, labs, paths, reps):
-    n, V = len(lps), int(lps[0].shape[1])
-    eng = _lib.default_engine(torch.cuda.current_device())
+    V = int(lps[0].shape[1])
     occs = [torch.empty((int(x.shape[0]), V), dtype=torch.float32, device="cuda") for x in lps]
-    ll = np.zeros(n, np.float64)
-    st = np.zeros(n, np.int32)
-    k = [_ptr_array([x.data_ptr() for x in xs]) for xs in (lps, labs, occs)]
-    T = _i64_array([x.shape[0] for x in lps])
-    S = _i64_array([x.shape[0] for x in labs])
-    ld = _i64_array([x.stride(0) for x in lps])
+    p_occ = _ptr_array([x.data_ptr() for x in occs])
     ldo = _i64_array([x.stride(0) for x in occs])
     term = _i64_array(torch.stack([p[-1] for p in paths]).cpu().tolist())
-    stream = _stream_ptr(torch.cuda.current_device())
-
-    def call():
-        rc = eng.lib.ka_ctc_label_posteriors_batch_f32(eng.handle, n, k[0][0], T[0], V, ld[0], k[1][0], S[0], 1000, 4, term[0], k[2][0],
-                                                       ldo[0], ll.ctypes.data, st.ctypes.data, _lib.KA_MEM_DEVICE, stream)
-        _lib.check(rc, "ka_ctc_label_posteriors_batch_f32")
-
-    need = eng.lib.ka_label_posterior_workspace_bytes(n, T[0], S[0], V, 1000, 4, _lib.KA_MEM_DEVICE)
-    eng.reserve(need)
-    call()                                   # warm-up
-    ms = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        call()                               # (the call synchronises its stream)
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return ms, st, ll
+    return time_batch("label", "ka_label_posterior_workspace_bytes", lps, labs, (term[0], p_occ[0], ldo[0]), reps)
 
 
 def time_states(lps, labs, paths, reps, K=200):
-    n, V = len(lps), int(lps[0].shape[1])
-    eng = _lib.default_engine(torch.cuda.current_device())
     W = [min(1000, 2 * int(x.shape[0]) + 1) for x in labs]
     frames = [np.unique(np.linspace(0, int(x.shape[0]) - 1, K).astype(np.int64)) for x in lps]
     gammas = [torch.empty((len(f), w), dtype=torch.float32, device="cuda") for f, w in zip(frames, W)]
     los = [torch.empty(len(f), dtype=torch.int64, device="cuda") for f in frames]
-    ll = np.zeros(n, np.float64)
-    st = np.zeros(n, np.int32)
-    k = [_ptr_array([x.data_ptr() for x in xs]) for xs in (lps, labs, gammas, los)]
+    k = [_ptr_array([x.data_ptr() for x in xs]) for xs in (gammas, los)]
     fr = _ptr_array([f.ctypes.data for f in frames])
     Ks = _i64_array([len(f) for f in frames])
-    T = _i64_array([x.shape[0] for x in lps])
-    S = _i64_array([x.shape[0] for x in labs])
-    ld = _i64_array([x.stride(0) for x in lps])
     ldo = _i64_array(W)
     term = _i64_array(torch.stack([p[-1] for p in paths]).cpu().tolist())
-    stream = _stream_ptr(torch.cuda.current_device())
-
-    def call():
-        rc = eng.lib.ka_ctc_state_posteriors_batch_f32(eng.handle, n, k[0][0], T[0], V, ld[0], k[1][0], S[0], 1000, 4, term[0], fr[0],
-                                                       Ks[0], k[2][0], ldo[0], k[3][0], ll.ctypes.data, st.ctypes.data,
-                                                       _lib.KA_MEM_DEVICE, stream)
-        _lib.check(rc, "ka_ctc_state_posteriors_batch_f32")
-
-    need = eng.lib.ka_state_posterior_workspace_bytes(n, T[0], S[0], Ks[0], V, 1000, 4, _lib.KA_MEM_DEVICE)
-    eng.reserve(need)
-    call()                                   # warm-up
-    ms = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        call()                               # (the call synchronises its stream)
-        ms.append((time.perf_counter() - t0) * 1e3)
-    return ms, st, ll
+    return time_batch("state", "ka_state_posterior_workspace_bytes", lps, labs, (term[0], fr[0], Ks[0], k[0][0], ldo[0], k[1][0]),
+                      reps, ws_own=(Ks[0],))
 
 
 def main():
