@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define KA_VERSION 103 /* 0.1.3: state posteriors at chosen frames */
+#define KA_VERSION 104 /* 0.1.4: the serial backtrace's second output form and its debug switch removed */
 
 /* status codes (per call and per lattice) */
 #define KA_OK 0
@@ -260,10 +260,6 @@ int ka_debug_set_tile_width(ka_engine *e, int32_t positions);
  * the tiled form, gets on a device of n_simd SIMDs; 0 if one of them is not run in the tiled form at all, a negative status for
  * bad arguments. */
 int ka_debug_tile_width_choice(const int64_t *T, const int64_t *S, int32_t n, int32_t V, int32_t beam_size, int32_t max_move, int32_t n_simd);
-/* The serial backtrace's output form: 1 = labels and scores gathered from memory after the walk (fewer vector instructions:
- * launches that fill the chip; by the counters 17 % more HBM traffic per step), 0 or -1 (default) = collected by the walk in
- * registers.  Results are identical. */
-int ka_debug_set_rc_gather(ka_engine *e, int32_t how);
 /* Self-checks of the tiled form's hand-off, a combination of:
  *   1  the halo region is filled with a NaN sentinel before the launch and every packet a tile consumes is checked
  *      against it: a packet read before it was written gives the lattice KA_ERR_INTERNAL (tests)

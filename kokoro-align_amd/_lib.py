@@ -36,7 +36,7 @@ EXPORTS = [
     "ka_debug_tile_stats", "ka_engine_set_backtrace", "ka_debug_chunk_entries", "ka_debug_plan_tiles",
     "ka_engine_set_verify", "ka_stream_create", "ka_stream_destroy",
     "ka_debug_set_split", "ka_engine_workspace_bytes", "ka_debug_set_tile_lds",
-    "ka_debug_auto_split", "ka_debug_set_rc_gather", "ka_lstm_layer0_f32", "ka_debug_set_tile_width", "ka_debug_tile_width_choice", "ka_debug_plan_tiles_width",
+    "ka_debug_auto_split", "ka_lstm_layer0_f32", "ka_debug_set_tile_width", "ka_debug_tile_width_choice", "ka_debug_plan_tiles_width",
     "ka_ctc_path_posteriors_f32", "ka_ctc_path_posteriors_batch_f32", "ka_posterior_workspace_bytes",
     "ka_ctc_label_posteriors_f32", "ka_ctc_label_posteriors_batch_f32", "ka_label_posterior_workspace_bytes",
     "ka_ctc_state_posteriors_f32", "ka_ctc_state_posteriors_batch_f32", "ka_state_posterior_workspace_bytes",
@@ -129,8 +129,6 @@ def load_library():
     L.ka_stream_destroy.argtypes = [i32, vp]
     L.ka_debug_auto_split.restype = ctypes.c_int
     L.ka_debug_auto_split.argtypes = [pi64, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
-    L.ka_debug_set_rc_gather.restype = ctypes.c_int
-    L.ka_debug_set_rc_gather.argtypes = [vp, i32]
     L.ka_debug_set_tile_lds.restype = ctypes.c_int
     L.ka_debug_set_tile_lds.argtypes = [vp, i32]
     L.ka_debug_tile_width_choice.restype = ctypes.c_int
@@ -246,9 +244,6 @@ class Engine:
         """Calibration of the AUTO modes: the longest n_tiled lattices of a launch run tiled, the longest n_parallel are walked
         back chunk-parallel; -1 = the library's cost model."""
         check(self.lib.ka_debug_set_split(self.handle, int(n_tiled), int(n_parallel)), "ka_debug_set_split")
-
-    def set_rc_gather(self, how):
-        check(self.lib.ka_debug_set_rc_gather(self.handle, int(how)), "ka_debug_set_rc_gather")
 
     def set_tile_lds(self, nbytes):
         check(self.lib.ka_debug_set_tile_lds(self.handle, int(nbytes)), "ka_debug_set_tile_lds")

@@ -86,7 +86,6 @@ struct ka_engine {
     std::vector<Redo> redo;
     int32_t last_V = 0, last_beam = 0, last_max_move = 0, last_mem = KA_MEM_DEVICE;
     int32_t verify = 0;                    // ka_engine_set_verify: self-checks of the tiled form's hand-off
-    int32_t rc_gather = -1;                // ka_debug_set_rc_gather: -1 the library's rule, 0 / 1 the serial backtrace's output form
     int32_t tile_width = 0;                // ka_debug_set_tile_width: 0 = the engine chooses, 128 or 256
     int32_t tile_lds = 0;                  // ka_debug_set_tile_lds: LDS bytes a tile workgroup requests (0: the library's choice)
     int32_t split_tiled = -1, split_par = -1;   // ka_debug_set_split: how many of the longest lattices run tiled / are walked back chunk-parallel (-1: cost model)
@@ -376,9 +375,7 @@ int enqueue_backtrace(ka_engine *e, const LaunchPlan &p, const DevicePtrs &dv, h
         const bool two_backtraces = n_par > 0 && n_par < rc_hi;
         if (n_par < rc_hi) {      // one wavefront per lattice, chunk after chunk (skips the chunk-parallel ones)
             if (two_backtraces) KA_HIP(fork_aux(e, stream, 2));
-            // (the gather form is opt-in: 27.2 -> 26.1 ms for 8192 lattices alone on the GPU, nothing with four launches in flight,
-            //  and 47 GB more HBM traffic per step by the counters - DESIGN.md section 8)
-            ka::launch_backtrace_rc_serial(p.max_move, dv.lats, rc_hi, dv.meta, two_backtraces ? e->aux : stream, e->rc_gather == 1);
+            ka::launch_backtrace_rc_serial(p.max_move, dv.lats, rc_hi, dv.meta, two_backtraces ? e->aux : stream);
         }
         if (n_par > 0) {
             ka::launch_chunk_entries(p.max_move, dv.lats, rc_hi, dv.meta, stream, (unsigned)total_chunks, (unsigned)max_seg, (unsigned)max_sup, (unsigned)max_w);
@@ -963,13 +960,6 @@ int ka_engine_set_verify(ka_engine *e, int32_t flags)
     if (!e) return fail(KA_ERR_BAD_ARGS, "engine is NULL");
     if (flags < 0 || flags > 7) return fail(KA_ERR_BAD_ARGS, "ka_engine_set_verify: flags are a combination of 1, 2 and 4");
     e->verify = flags;
-    return KA_OK;
-}
-
-int ka_debug_set_rc_gather(ka_engine *e, int32_t how)
-{
-    if (!e) return fail(KA_ERR_BAD_ARGS, "engine is NULL");
-    e->rc_gather = how < 0 ? -1 : (how ? 1 : 0);
     return KA_OK;
 }
 

@@ -20,8 +20,8 @@ void launch_forward_flagged(int max_move, const Lattice *lats, int n, int32_t *m
 void launch_forward_generic(const Lattice *lats, int n, int32_t *meta, hipStream_t s);
 
 // ---- ka_wave_bt.hip ----
-// serial: one wavefront per lattice (skips Lattice::par ones); gather: labels and scores fetched after the walk
-void launch_backtrace_rc_serial(int max_move, const Lattice *lats, int n, int32_t *meta, hipStream_t s, bool gather);
+// serial: one wavefront per lattice (skips Lattice::par ones)
+void launch_backtrace_rc_serial(int max_move, const Lattice *lats, int n, int32_t *meta, hipStream_t s);
 // one wavefront per chunk of the launch's chunk-parallel lattices (Lattice::entry holds where the path enters each)
 void launch_backtrace_rc_chunks(int max_move, const Lattice *lats, int n, int32_t *meta, hipStream_t s, unsigned total_chunks);
 void launch_backtrace_w16(const Lattice *lats, int n, const int32_t *meta, hipStream_t s, int only_flagged);

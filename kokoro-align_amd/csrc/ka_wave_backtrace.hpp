@@ -5,9 +5,7 @@
 
 namespace ka {
 
-#ifndef KA_RC_MIN_WAVES
-#define KA_RC_MIN_WAVES 8
-#endif
+constexpr int kRcMinWaves = 8;   // __launch_bounds__ of the recompute kernels: wavefronts per SIMD
 
 // ---------------------------------------------------------------------------------------
 // backtrace (best_path), one wavefront per lattice; outputs are gathered by gather_outputs_kernel
@@ -20,15 +18,11 @@ namespace ka {
 // [t/4][block][t%4], so the window of 4 frames is contiguous (128 B), one dword per lane; the
 // next chunk's window is prefetched while the current chunk is walked.
 // ---------------------------------------------------------------------------------------
-#ifndef KA_BT_CHUNK
-#define KA_BT_CHUNK 16
-#endif
-constexpr int kBtChunk = KA_BT_CHUNK;                  // frames per chunk (16 or 32)
+constexpr int kBtChunk = 16;                           // frames per chunk
 constexpr int kBtReach = 3 * 2 * kBtChunk;             // positions a path can drop over two chunks
 constexpr int kBtBlocks = kBtChunk / 2;                // window width in blocks: 16*kBtBlocks >= kBtReach + 16 + 15
 constexpr int kBtRegs = kBtChunk * kBtBlocks / 64;     // VGPRs per chunk: one dword per (frame, window block)
 constexpr int kBtGroupsPerReg = 16 / kBtBlocks;        // 4-frame groups held by one VGPR
-static_assert(kBtChunk == 16 || kBtChunk == 32, "lane layout below");
 static_assert(16 * kBtBlocks >= kBtReach + 31, "window too narrow for the prefetch distance");
 
 // first block of the window that covers every position the path can take in the chunk AFTER
@@ -64,13 +58,6 @@ __device__ __forceinline__ void bt_load_async(uint32_t (&r)[kBtRegs], const char
 #pragma unroll
     for (int v = 0; v < kBtRegs; ++v)
         asm volatile("global_load_dword %0, %1, %2" : "=&v"(r[v]) : "v"(voff), "s"(chunk_base + (size_t)v * kBtGroupsPerReg * 1024) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void bt_wait(uint32_t (&r)[8])
-{
-    asm volatile("s_waitcnt vmcnt(%8)"
-                 : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7])
-                 : "i"(N) : "memory");
 }
 template <int N>
 __device__ __forceinline__ void bt_wait(uint32_t (&r)[2])
@@ -276,20 +263,7 @@ constexpr int kRcLanes = 62;   // lanes 62 and 63 are kept at -inf: they are the
 // [blank hi, blank lo, label hi, label lo], every cell coded 3 - move): pathv[lane f] = position of frame f relative to
 // the window.  One scalar chain per frame: v_readlane -> shift -> 3 & ~code -> subtract.  FULL: all 32 frames, straight
 // line (the `f < n` test of the last, partial chunk costs a compare and a taken branch per frame).
-template <bool FULL>
-__device__ __forceinline__ void rc_walk(const uint32_t (&codes)[kCkFrames / 8], int n, int &qq, int &pathv)
-{
-#pragma unroll
-    for (int f = kCkFrames - 1; f >= 0; --f) {
-        if (FULL || f < n) {
-            const int sh = 4 * (7 - (f & 7)) + ((qq & 1) ? 0 : 2);
-            const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)codes[f >> 3], qq >> 1) >> sh;
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(pathv) : "s"(qq), "i"(f));
-            qq -= bp_decode(w);
-        }
-    }
-}
-// The same walk, also collecting best_labels / best_scores (align.py:105-107) on the way: the label of the path's cell
+// The walk also collects best_labels / best_scores (align.py:105-107) on the way: the label of the path's cell
 // comes out of the window's label register (lane j: 4 * label of position wlo+2j+1; a blank cell: label 0) and the score
 // out of the frame's row register (lane v = lp[t0+f, v]), both with v_readlane at a scalar lane index - two vector
 // instructions more per frame than gathering the scores afterwards with a ds_bpermute per frame, but the LDS pipe, which
@@ -317,13 +291,9 @@ __device__ __forceinline__ void rc_walk_out(const uint32_t (&codes)[kCkFrames / 
 // PAR = false: one wavefront per lattice walks its chunks from the last to the first (the position a chunk is entered
 // at comes out of the chunk above it).  PAR = true: one wavefront per CHUNK, entered at Lattice::entry[chunk], which the
 // chunk-parallel backtrace (ka_parallel_bt.hpp) has worked out for every chunk beforehand; grid = all chunks of the launch.
-// GO ("gather the outputs"): the walk collects the path only, and best_labels / best_scores are fetched afterwards, lane f
-// doing frame t0+f - the label with one ds_bpermute on the window's label register, the score with ONE 4-byte load per frame
-// from the row this wavefront read a few microseconds ago (L2 / Infinity Cache).  Four vector instructions per frame fewer
-// (two v_readlane + two v_writelane of the walk) for one gather per chunk whose latency other wavefronts cover.  Opt-in
-// (ka_debug_set_rc_gather): 27.2 -> 26.1 ms for 8192 lattices alone on the GPU, nothing with several launches in flight, and
-// the gathers read 47 GB more per step by the counters.  GO = false, the default, keeps everything in registers.
-template <int M, bool ZL, bool PAR, bool GO = false>
+// best_labels / best_scores stay in registers all the way.  (Fetching them after the walk instead, with a gather per chunk,
+// was measured and removed: the numbers are in DESIGN.md 8, the code under tools/experiments/.)
+template <int M, bool ZL, bool PAR>
 __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ lats, const int32_t *meta, int n_lats)
 {
     const int which = PAR ? __builtin_amdgcn_readfirstlane(lattice_of_chunk(lats, n_lats, (int64_t)blockIdx.x)) : (int)blockIdx.x;
@@ -522,33 +492,16 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
         int qq = p - wlo;
         // best_path, best_labels = lab'[best_path], best_scores[t] = lp[t, best_labels[t]] (align.py:105-107), lane f
         // does frame t0+f: collected by the walk itself (rc_walk_out)
-        if constexpr (GO) {
-            if (n == kCkFrames)
-                rc_walk<true>(codes, n, qq, pathv);
-            else
-                rc_walk<false>(codes, n, qq, pathv);
-            // lane f: position wlo + pathv; its label sits in lane (pathv >> 1) of the window's label register (odd positions)
-            const int lw = __builtin_amdgcn_ds_bpermute((pathv >> 1) * 4, lab4);
-            if (lane < n) {
-                const int pos = pathv + wlo;
-                const int l4 = (pos & 1) ? lw : 0;
-                const float sv = *(gcf32_t)(lp + (size_t)(t0 + (uint32_t)lane) * ldb + (uint32_t)l4);
-                path[t0 + lane] = pos;
-                lab_out[t0 + lane] = l4 >> 2;
-                sc_out[t0 + lane] = sv;
-            }
-        } else {
-            int labv = 0;
-            float scv = 0.0f;
-            if (n == kCkFrames)
-                rc_walk_out<true>(codes, rows, lab4, n, qq, pathv, labv, scv);
-            else
-                rc_walk_out<false>(codes, rows, lab4, n, qq, pathv, labv, scv);
-            if (lane < n) {
-                path[t0 + lane] = pathv + wlo;
-                lab_out[t0 + lane] = labv;
-                sc_out[t0 + lane] = scv;
-            }
+        int labv = 0;
+        float scv = 0.0f;
+        if (n == kCkFrames)
+            rc_walk_out<true>(codes, rows, lab4, n, qq, pathv, labv, scv);
+        else
+            rc_walk_out<false>(codes, rows, lab4, n, qq, pathv, labv, scv);
+        if (lane < n) {
+            path[t0 + lane] = pathv + wlo;
+            lab_out[t0 + lane] = labv;
+            sc_out[t0 + lane] = scv;
         }
         p = qq + wlo;
         if (PAR || t0 == 0) break;
@@ -560,15 +513,15 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
 }
 
 // PAR = false: two kernels per launch (ZL: the transcript contains label 0), each skips the other's lattices - as in the forward kernels
-template <int M, bool ZL, bool PAR, bool GO = false>
-__global__ __launch_bounds__(64, KA_RC_MIN_WAVES) void backtrace_rc_kernel(const Lattice *__restrict__ lats, const int32_t *meta, int n_lats)
+template <int M, bool ZL, bool PAR>
+__global__ __launch_bounds__(64, kRcMinWaves) void backtrace_rc_kernel(const Lattice *__restrict__ lats, const int32_t *meta, int n_lats)
 {
-    backtrace_rc_body<M, ZL, PAR, GO>(lats, meta, n_lats);
+    backtrace_rc_body<M, ZL, PAR>(lats, meta, n_lats);
 }
 // PAR = true (one wavefront per chunk of every chunk-parallel lattice): ONE kernel, the two instances behind a wave-uniform branch -
 // a grid of 430 000 workgroups that only look their lattice up and leave cost the corpus launch 0.1 ms; 53 / 54 registers
 template <int M>
-__global__ __launch_bounds__(64, KA_RC_MIN_WAVES) void backtrace_rc_chunks_kernel(const Lattice *__restrict__ lats, const int32_t *meta, int n_lats)
+__global__ __launch_bounds__(64, kRcMinWaves) void backtrace_rc_chunks_kernel(const Lattice *__restrict__ lats, const int32_t *meta, int n_lats)
 {
     const Lattice &d = lats[__builtin_amdgcn_readfirstlane(lattice_of_chunk(lats, n_lats, (int64_t)blockIdx.x))];
     const int flags = __builtin_amdgcn_readfirstlane(meta[4 * (size_t)d.idx + 2]);

@@ -5,24 +5,19 @@
 namespace ka {
 
 template <int M>
-static void rc_serial(const Lattice *lats, int n, int32_t *meta, hipStream_t s, bool gather)
+static void rc_serial(const Lattice *lats, int n, int32_t *meta, hipStream_t s)
 {
-    if (gather) {
-        hipLaunchKernelGGL((backtrace_rc_kernel<M, false, false, true>), dim3(n), dim3(64), 0, s, lats, meta, n);
-        hipLaunchKernelGGL((backtrace_rc_kernel<M, true, false, true>), dim3(n), dim3(64), 0, s, lats, meta, n);
-    } else {
-        hipLaunchKernelGGL((backtrace_rc_kernel<M, false, false, false>), dim3(n), dim3(64), 0, s, lats, meta, n);
-        hipLaunchKernelGGL((backtrace_rc_kernel<M, true, false, false>), dim3(n), dim3(64), 0, s, lats, meta, n);
-    }
+    hipLaunchKernelGGL((backtrace_rc_kernel<M, false, false>), dim3(n), dim3(64), 0, s, lats, meta, n);
+    hipLaunchKernelGGL((backtrace_rc_kernel<M, true, false>), dim3(n), dim3(64), 0, s, lats, meta, n);
 }
 
-void launch_backtrace_rc_serial(int max_move, const Lattice *lats, int n, int32_t *meta, hipStream_t s, bool gather)
+void launch_backtrace_rc_serial(int max_move, const Lattice *lats, int n, int32_t *meta, hipStream_t s)
 {
     switch (max_move) {
-    case 1: rc_serial<1>(lats, n, meta, s, gather); break;
-    case 2: rc_serial<2>(lats, n, meta, s, gather); break;
-    case 3: rc_serial<3>(lats, n, meta, s, gather); break;
-    default: rc_serial<4>(lats, n, meta, s, gather); break;
+    case 1: rc_serial<1>(lats, n, meta, s); break;
+    case 2: rc_serial<2>(lats, n, meta, s); break;
+    case 3: rc_serial<3>(lats, n, meta, s); break;
+    default: rc_serial<4>(lats, n, meta, s); break;
     }
 }
 

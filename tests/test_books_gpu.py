@@ -398,10 +398,9 @@ def test_tile_workgroups_per_cu_do_not_change_results(books_on_device, width, ld
         _set(eng, "auto")
 
 
-@pytest.mark.parametrize("gather", [0, 1])
-def test_serial_backtrace_output_forms_on_a_book(books_on_device, gather):
-    """backtrace_rc_kernel<.., GO>: labels and scores collected by the walk in registers (few lattices) or gathered from memory
-    after it (launches that fill the chip; ka_debug_set_rc_gather forces either): the same three outputs, bit for bit."""
+def test_serial_backtrace_outputs_on_a_book(books_on_device):
+    """backtrace_rc_kernel, one wavefront per lattice, behind the wave and the tiled forward: path, labels and scores collected
+    by the walk in registers, the same three outputs and total as the oracle's, bit for bit."""
     from kokoro_align_amd.align import DeviceBatch
     lps, labs = books_on_device("kokoro")
     want = _oracle("kokoro")
@@ -409,12 +408,10 @@ def test_serial_backtrace_output_forms_on_a_book(books_on_device, gather):
     try:
         for mode in ("wave", "tiled"):
             _set(eng, mode)
-            eng.set_rc_gather(gather)
             b = DeviceBatch(lps, labs)
             b.run()
             _check_against_oracle(b, want)
     finally:
-        eng.set_rc_gather(-1)
         _set(eng, "auto")
 
 

@@ -19,10 +19,10 @@ def test_new_symbols_declared_exported_and_bound():
     assert_declared_exported_bound(NEW_SYMBOLS)
 
 
-def test_version_is_103():
+def test_version_is_104():
     from kokoro_align_amd import _lib
-    assert _lib.load_library().ka_version() == 103
-    assert int(re.search(r"#define KA_VERSION (\d+)", header_text()).group(1)) == 103
+    assert _lib.load_library().ka_version() == 104
+    assert int(re.search(r"#define KA_VERSION (\d+)", header_text()).group(1)) == 104
 
 
 def _ws(n, T, S, K, V=64, beam=1000, mm=4, mem=1):
