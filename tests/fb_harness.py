@@ -2,6 +2,7 @@
 through the Python API of kokoro_align_amd/posteriors.py: being independent of it is their point.  Outputs are filled with
 sentinels first (-7.0, -9, status 99), so a test can tell that a call wrote nothing."""
 import ctypes
+import json
 import os
 import re
 
@@ -11,6 +12,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 P = lambda xs: ctypes.cast((ctypes.c_void_p * len(xs))(*[x.ctypes.data for x in xs]), ctypes.POINTER(ctypes.c_void_p))
 I = lambda xs: (ctypes.c_int64 * len(xs))(*[int(v) for v in xs])
+
+
+def record(call, ratio, m):
+    """Prints one figure of the per-cell check (posterior_ref.*_ratio: the worst |kernel - float64| / E of a call's output) and,
+    with KA_ACCURACY_OUT=<file>, appends it to that file as a JSON line (the source of profiles/posterior_accuracy.json);
+    then holds it against m.  The figure is out before the assertion, so a run that fails still measures."""
+    rec = dict(test=os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0], call=call, ratio=float(ratio), m=m)
+    print(json.dumps(rec))
+    path = os.environ.get("KA_ACCURACY_OUT")
+    if path:
+        with open(path, "at") as f:
+            f.write(json.dumps(rec) + "\n")
+    assert ratio <= m, rec
 
 
 def engine():
@@ -97,12 +111,14 @@ def path_z_one(eng, _lib, lp, labels, terminal, beam, mm):
     return ll[0]
 
 
-def label_call_one(eng, _lib, lp, labels, terminal, beam, mm):
-    """ka_ctc_label_posteriors_f32 for one lattice: (occ [T, V], Z)."""
+def label_call_one(eng, _lib, lp, labels, terminal, beam, mm, ld_out=None, fill=0.0):
+    """ka_ctc_label_posteriors_f32 for one lattice into rows of pitch ``ld_out`` (V if None) prefilled with ``fill``:
+    (occ [T, ld_out], Z)."""
     lp, labels, head = _one(lp, labels)
-    occ = np.zeros(lp.shape, np.float32)
+    ld_out = ld_out or lp.shape[1]
+    occ = np.full((lp.shape[0], ld_out), fill, np.float32)
     ll = np.zeros(1, np.float64)
-    rc = eng.lib.ka_ctc_label_posteriors_f32(eng.handle, *head, beam, mm, int(terminal), occ.ctypes.data, lp.shape[1], ll.ctypes.data,
+    rc = eng.lib.ka_ctc_label_posteriors_f32(eng.handle, *head, beam, mm, int(terminal), occ.ctypes.data, ld_out, ll.ctypes.data,
                                              _lib.KA_MEM_HOST, None)
     assert rc == 0
     return occ, ll[0]

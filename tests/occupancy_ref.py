@@ -12,17 +12,18 @@ import posterior_ref as R
 
 
 def occupancy(log_probs, labels, terminal, beam_size=1000, max_move=4):
-    """dict(status, occ float64 [T, V], ll, last_max); occ NaN for a failed lattice."""
+    """dict(status, occ float64 [T, V], ll, last_max, fb); occ NaN for a failed lattice; fb is the forward_backward(full=True)
+    the occupancy was summed from, which posterior_ref.label_ratio takes."""
     lp = np.asarray(log_probs, dtype=np.float64)
     T, V = lp.shape
     lab = R.expand(labels)
     got = R.forward_backward(lp, labels, np.full(T, int(terminal), np.int64), beam_size, max_move, full=True)
     if got["status"] != R.OK:
-        return dict(status=got["status"], occ=np.full((T, V), np.nan), ll=got["ll"], last_max=got.get("last_max"))
+        return dict(status=got["status"], occ=np.full((T, V), np.nan), ll=got["ll"], last_max=got["last_max"], fb=got)
     occ = np.zeros((T, V))
     for t, (lo, g) in enumerate(got["gamma"]):
         np.add.at(occ[t], lab[lo:lo + len(g)], g)
-    return dict(status=R.OK, occ=occ, ll=got["ll"], last_max=got["last_max"])
+    return dict(status=R.OK, occ=occ, ll=got["ll"], last_max=got["last_max"], fb=got)
 
 
 def brute_force(log_probs, labels, terminal, beam_size=1000, max_move=4):

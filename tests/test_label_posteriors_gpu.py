@@ -1,12 +1,14 @@
 """Label occupancy posteriors and the differentiable lattice log-likelihood on the MI355X, through the C ABI and the Python
 API, against the float64 reference (tests/occupancy_ref.py): |d occ| <= 1e-3, |row sum - 1| <= 1e-4, occ[T-1, lab'[s*]] = 1
-exactly, Z within 1e-9 max(1, |Z|) of ka_ctc_path_posteriors' Z for a path that ends at s*."""
+exactly, Z within 1e-9 max(1, |Z|) of ka_ctc_path_posteriors' Z for a path that ends at s*.  Beside those, the per-cell
+check of DESIGN.md section 4.21: every cell within posterior_ref.label_tolerance (M_LABEL x label_error_model) where the
+reference is 2^-120 or more and below 2^-119 elsewhere (posterior_ref.label_ratio), and Z within posterior_ref.z_tolerance."""
 import numpy as np
 import pytest
 
 import occupancy_ref as Q
 import posterior_ref as R
-from fb_harness import I, engine, label_call as _call, path_z_one as _path_z
+from fb_harness import I, engine, label_call as _call, path_z_one as _path_z, record
 from golden_util import g1_cases, g2_cases, g3_case
 from oracle import oracle as O
 
@@ -28,6 +30,8 @@ def _check(occ, ll, lp, labels, terminal, beam, mm, what, eng=None, _lib=None, r
     assert np.max(np.abs(occ.astype(np.float64).sum(1) - 1.0)) <= 1e-4, what
     assert occ[T - 1, R.expand(labels)[terminal]] == 1.0, what
     assert abs(ll - ref["ll"]) <= 1e-3 + 1e-6 * T, (what, ll, ref["ll"])
+    record("label", R.label_ratio(occ, ref["fb"], labels, what), R.M_LABEL)
+    record("z", R.z_ratio(ll, ref["fb"]), R.M_Z)
     if eng is not None:
         z = _path_z(eng, _lib, lp, labels, terminal, beam, mm)
         assert abs(ll - z) <= 1e-9 * max(1.0, abs(z)), (what, ll, z)

@@ -1,10 +1,13 @@
 """Best-path posteriors and lattice log-likelihood on the MI355X, all through the C ABI, against the float64 reference
-(tests/posterior_ref.py): |d posterior| <= 1e-3, |d log-likelihood| <= 1e-3 + 1e-6 T nats."""
+(tests/posterior_ref.py): |d posterior| <= 1e-3, |d log-likelihood| <= 1e-3 + 1e-6 T nats.  Beside those, the per-cell
+check of DESIGN.md section 4.21: every frame's posterior within posterior_ref.path_tolerance (M_PATH x path_error_model)
+where the reference is 2^-120 or more and below 2^-119 elsewhere (posterior_ref.path_ratio), and the log-likelihood within
+posterior_ref.z_tolerance."""
 import numpy as np
 import pytest
 
 import posterior_ref as R
-from fb_harness import engine, path_call as _call
+from fb_harness import engine, path_call as _call, record
 from golden_util import g1_cases, g2_cases, g3_case
 from oracle import oracle as O
 
@@ -24,6 +27,8 @@ def _check(post, ll, lp, labels, path, beam, mm, what):
     err = np.max(np.abs(post.astype(np.float64) - ref["post"]))
     assert err <= 1e-3, (what, err)
     assert abs(ll - ref["ll"]) <= 1e-3 + 1e-6 * T, (what, ll, ref["ll"])
+    record("path", R.path_ratio(post, ref, what), R.M_PATH)
+    record("z", R.z_ratio(ll, ref), R.M_Z)
     assert post[-1] == 1.0, what
     return ref
 

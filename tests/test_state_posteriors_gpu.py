@@ -1,12 +1,15 @@
 """State posteriors at chosen frames on the MI355X, through the C ABI and the Python API, against the float64 reference
 (tests/posterior_ref.forward_backward(..., full=True)): |d gamma| <= 1e-3, |row sum - 1| <= 1e-4, band_lo equal to the
 reference's lo, Z within 1e-9 max(1, |Z|) of ka_ctc_label_posteriors' Z, gamma at (T-1, s*) exactly 1; cross-checked with
-the label occupancy and the path posteriors of the same lattice, and end to end through the boundary confidence."""
+the label occupancy and the path posteriors of the same lattice, and end to end through the boundary confidence.  Beside
+those, the per-cell check of DESIGN.md section 4.21: every cell within posterior_ref.state_tolerance (M_STATE x
+state_error_model) where the reference is 2^-120 or more and below 2^-119 elsewhere (posterior_ref.state_ratio), and Z
+within posterior_ref.z_tolerance."""
 import numpy as np
 import pytest
 
 import posterior_ref as R
-from fb_harness import band_width as _W, engine, label_call_one as _label_call, state_call as _call, state_call_one
+from fb_harness import band_width as _W, engine, label_call_one as _label_call, record, state_call as _call, state_call_one
 from golden_util import g1_cases, g2_cases, g3_case
 from oracle import oracle as O
 
@@ -42,6 +45,8 @@ def _check(g, lo, ll, frames, lp, labels, terminal, beam, mm, what, eng=None, _l
             want[int(terminal) - rlo] = 1.0
             assert np.array_equal(g[k], want), what
     assert abs(ll - ref["ll"]) <= 1e-3 + 1e-6 * T, (what, ll, ref["ll"])
+    record("state", R.state_ratio(g, frames, ref, what), R.M_STATE)
+    record("z", R.z_ratio(ll, ref), R.M_Z)
     if eng is not None:
         _, z = _label_call(eng, _lib, lp, labels, terminal, beam, mm)
         assert abs(ll - z) <= 1e-9 * max(1.0, abs(z)), (what, ll, z)

@@ -1,0 +1,48 @@
+"""Reduces the JSON lines that the posterior GPU tests append under KA_ACCURACY_OUT=<file> (tests/fb_harness.record) to
+profiles/posterior_accuracy.json: per call the worst ratio |kernel - float64| / E of every test, and m = twice the worst of
+them, rounded up to two digits (tests/posterior_ref.py).
+
+    KA_ACCURACY_OUT=ratios.jsonl python -m pytest tests -q -m gpu -k posterior
+    python tools/posterior_accuracy.py ratios.jsonl profiles/posterior_accuracy.json
+"""
+import json
+import math
+import sys
+
+CALLS = ("state", "label", "path", "z")
+
+
+def round_up(x):
+    """x rounded up to two significant digits."""
+    if x <= 0:
+        return 0.0
+    e = math.floor(math.log10(x)) - 1
+    return round(math.ceil(x / 10 ** e - 1e-9) * 10 ** e, 10)
+
+
+def main(src, dst):
+    worst = {c: {} for c in CALLS}
+    with open(src) as f:
+        for line in f:
+            rec = json.loads(line)
+            if rec.get("call") in worst:
+                per = worst[rec["call"]]
+                r = rec["ratio"] if rec["ratio"] == rec["ratio"] else math.inf       # a NaN ratio is a failure, not a figure
+                per[rec["test"]] = max(per.get(rec["test"], 0.0), r)
+    out = {"device": "MI355X (gfx950)",
+           "unit": "max over the cells of a test of |kernel - float64| / E; E = posterior_ref.*_error_model of the float64 reference",
+           "rule": "m = twice the worst measured ratio of its call, rounded up to two digits (tests/posterior_ref.py)",
+           "calls": {}}
+    for c in CALLS:
+        top = max(worst[c].values(), default=0.0)
+        out["calls"][c] = {"m": round_up(2 * top), "worst_ratio": top, "tests": len(worst[c]),
+                           "records": [{"test": t, "ratio": r} for t, r in sorted(worst[c].items())]}
+    with open(dst, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for c in CALLS:
+        print(c, out["calls"][c]["tests"], "tests, worst", out["calls"][c]["worst_ratio"], "m", out["calls"][c]["m"])
+
+
+if __name__ == "__main__":
+    main(sys.argv[1], sys.argv[2])
