@@ -199,6 +199,33 @@ int ka_ctc_state_posteriors_batch_f32(ka_engine *e, int32_t n, const float *cons
 size_t ka_state_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t V,
                                           int32_t beam_size, int32_t max_move, int32_t mem);
 
+/*
+ * Expected state durations and the lattice log-likelihood of a terminal: the forward-backward pass of
+ * ka_ctc_label_posteriors (same band, moves, veto, terminal s* and Z), summed over time per POSITION of the blank-expanded labels
+ *   duration[s] = D(s) = sum over t of gamma_t(s)      expected number of frames spent in s (odd s: phoneme (s-1)/2, even: a blank)
+ *   time_sum[s] = B(s) = sum over t of t gamma_t(s)    its first time moment (B / D: the expected centre frame of s)
+ * The prefix sums of D are the expected boundary frames: with tau_c the first frame whose state is >= c, E[tau_c] = sum over
+ * s < c of D(s).  Arguments as ka_ctc_label_posteriors[_batch]_f32, with in place of occupancy
+ *   duration        [2S+1] float64 output (where `mem` says)
+ *   time_sum        [2S+1] float64 output (where `mem` says); may be NULL (batch: the array, or any of its entries)
+ * gamma is the float the state posteriors write; a position receives one float64 add per frame whose band holds it, in
+ * descending frame order, so the sums are those of a sequential float64 loop over the rows of ka_ctc_state_posteriors at
+ * every frame, bit for bit, and sum_s D(s) = T within 1e-5 T.  Positions no band holds read 0.  Per lattice: statuses as
+ * ka_ctc_label_posteriors, with NaN over [0, 2S+1) for a failed lattice.  Costs a label-posterior call for up to 768 lattices
+ * resident at once (three workgroups of 50 KB LDS per CU), two rounds of it from there to 1536.
+ */
+int ka_ctc_state_durations_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                               int32_t beam_size, int32_t max_move, int64_t terminal, double *duration, double *time_sum,
+                               double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_state_durations_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                     const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                     int32_t max_move, const int64_t *terminal, double *const *duration, double *const *time_sum,
+                                     double *log_likelihood, int32_t *status, int32_t mem, void *stream);
+/* device-workspace bytes such a call carves (0 for unsupported arguments); bounded by the lattices resident at once (and, for
+ * KA_MEM_HOST, the staged inputs and outputs of every lattice) */
+size_t ka_state_duration_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size,
+                                         int32_t max_move, int32_t mem);
+
 /* Kernel form of the fast path.
  *   KA_MODE_WAVE        one wavefront per lattice, checkpointed (throughput; fills the chip from ~4096
  *                       lattices): the forward kernel keeps scores only and stores the score ring every 32

@@ -9,7 +9,9 @@ plus batched / device-resident entry points (ctc_best_path_batch, ctc_best_path_
 forward-backward quality signal of a best path (ctc_path_posteriors[_batch|_device], segment_confidence), the label
 occupancy of every frame (ctc_label_posteriors[_batch|_device], segment_agreement), the differentiable lattice
 log-likelihood (lattice_log_likelihood) and the state posteriors at chosen frames behind the confidence of align()'s text
-boundaries (ctc_state_posteriors[_batch|_device], boundary_frames, segment_boundary_confidence).
+boundaries (ctc_state_posteriors[_batch|_device], boundary_frames, segment_boundary_confidence), and the expected duration of
+every state with the expected frame of every boundary (ctc_state_durations[_batch|_device], phoneme_durations,
+expected_crossing_frames, segment_boundary_shift).
 
 The DP and backtrace run in the HIP C-ABI library (include/kokoro_align_amd.h); there is no
 CPU fallback — importing works without a GPU, computing does not.
@@ -32,12 +34,18 @@ from .posteriors import (  # noqa: F401
     ctc_path_posteriors,
     ctc_path_posteriors_batch,
     ctc_path_posteriors_device,
+    ctc_state_durations,
+    ctc_state_durations_batch,
+    ctc_state_durations_device,
     ctc_state_posteriors,
     ctc_state_posteriors_batch,
     ctc_state_posteriors_device,
+    expected_crossing_frames,
     lattice_log_likelihood,
+    phoneme_durations,
     segment_agreement,
     segment_boundary_confidence,
+    segment_boundary_shift,
     segment_confidence,
 )
 from ._lib import KAError, build_library, library_path, load_library  # noqa: F401

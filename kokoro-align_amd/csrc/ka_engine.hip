@@ -560,8 +560,9 @@ void redo_declined(ka_engine *e, const std::vector<ka_engine::Redo> &again, std:
     }
 }
 
-// ---- best-path posteriors (ka_posterior.hpp), label occupancy (ka_occupancy.hpp) and state posteriors at chosen frames
-// (ka_state_posterior.hpp): their own kernels and workspace layout, whatever the engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall) brings what differs: its own arrays and their
+// ---- best-path posteriors (ka_posterior.hpp), label occupancy (ka_occupancy.hpp), state posteriors at chosen frames
+// (ka_state_posterior.hpp) and expected state durations (ka_duration.hpp): their own kernels and workspace layout, whatever the
+// engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall, DurCall) brings what differs: its own arrays and their
 // checks, its planner and launch, the descriptor fields beyond FbLattice, its own staging (upload: host buffers only;
 // stage: every memory mode), and what two statuses mean.
 struct FbArgs {
@@ -618,7 +619,7 @@ struct PostCall {
     }
 };
 
-// the FbCkLattice fields that both slot calls (OccCall, StateCall) fill alike: the lattice's slot, its terminal, the column stride
+// the FbCkLattice fields that the slot calls (OccCall, StateCall, DurCall) fill alike: the lattice's slot, its terminal, the column stride
 void fill_slot(ka::FbCkLattice &d, const ka::plan::SlotCarve &c, int64_t terminal, char *ws)
 {
     d.ck = reinterpret_cast<double *>(ws + c.slot + c.parts.ck);
@@ -726,6 +727,44 @@ struct StateCall {
         KA_HIP(hipMemcpy2DAsync(gamma[i], (size_t)ld_out[i] * 4, ws + c.gamma, (size_t)c.W * 4, (size_t)c.W * 4, (size_t)K[i],
                                 hipMemcpyDeviceToHost, a.stream));
         KA_HIP(hipMemcpyAsync(band_lo[i], ws + c.band_lo, (size_t)K[i] * 8, hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
+struct DurCall {
+    using Desc = ka::DurLattice;
+    using Carve = ka::plan::DurCarve;
+    static constexpr const char *kName = "state durations";
+    static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score reaches the terminal";
+    const int64_t *terminal;
+    double *const *duration;
+    double *const *time_sum;   // NULL, or an array in which any entry may be NULL: no first moment for that lattice
+
+    bool arrays() const { return terminal && duration; }
+    const char *bad_lattice(const FbArgs &, int32_t) const { return nullptr; }
+    bool buffers(int32_t i) const { return duration[i] != nullptr; }
+    bool moment(int32_t i) const { return time_sum && time_sum[i]; }
+    static constexpr auto plan = ka::plan::state_duration_workspace;
+    static constexpr auto launch = ka::launch_state_durations;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (a.mem == KA_MEM_HOST) {
+            d.dur = reinterpret_cast<double *>(ws + c.dur);
+            d.tsum = moment(i) ? reinterpret_cast<double *>(ws + c.tsum) : nullptr;
+        } else {
+            d.dur = duration[i];
+            d.tsum = moment(i) ? time_sum[i] : nullptr;
+        }
+        fill_slot(d, c, terminal[i], ws);
+    }
+    int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int stage(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        const size_t bytes = (size_t)(2 * a.S[i] + 1) * sizeof(double);
+        KA_HIP(hipMemcpyAsync(duration[i], ws + c.dur, bytes, hipMemcpyDeviceToHost, a.stream));
+        if (moment(i)) KA_HIP(hipMemcpyAsync(time_sum[i], ws + c.tsum, bytes, hipMemcpyDeviceToHost, a.stream));
         return KA_OK;
     }
 };
@@ -1150,6 +1189,30 @@ size_t ka_state_posterior_workspace_bytes(int32_t n, const int64_t *T, const int
 {
     if (n < 0 || (n > 0 && (!T || !S || !K)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
     return ka::plan::state_posterior_workspace(n, T, S, K, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+int ka_ctc_state_durations_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                     const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                     const int64_t *terminal, double *const *duration, double *const *time_sum, double *log_likelihood,
+                                     int32_t *status, int32_t mem, void *stream)
+{
+    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+                   DurCall{terminal, duration, time_sum});
+}
+
+int ka_ctc_state_durations_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                               int32_t beam_size, int32_t max_move, int64_t terminal, double *duration, double *time_sum,
+                               double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+                   DurCall{&terminal, &duration, &time_sum});
+}
+
+size_t ka_state_duration_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                         int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::state_duration_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
 int ka_debug_chunk_entries(ka_engine *e, int32_t *out, int32_t max_entries, uint8_t *map0_out, int64_t map0_max)

@@ -1,5 +1,5 @@
-// ka_fb_ck.hpp — the checkpointed forward-backward that ka_occupancy.hpp (label occupancy) and ka_state_posterior.hpp (state
-// posteriors at chosen frames) share: one driver per form (fb_ck_fast<M, Out>, fb_ck_gen<Out>) and their launch.
+// ka_fb_ck.hpp — the checkpointed forward-backward that ka_occupancy.hpp (label occupancy), ka_state_posterior.hpp (state
+// posteriors at chosen frames) and ka_duration.hpp (expected state durations) share: one driver per form (fb_ck_fast<M, Out>, fb_ck_gen<Out>) and their launch.
 //
 // The posterior kernels keep alpha only at the path; these calls need it at band cells, so the forward pass checkpoints the
 // whole column before the first frame of every 32-frame block (with the offset C and the frame maximum m it runs on), and the
@@ -13,7 +13,7 @@
 //   recompute(t0)                recompute the block that starts at t0?  (if not, the walk is re-seated at t1, where the
 //                                recompute would have left it; beta is still stepped through every frame)
 //   cells(t, lo)                 frame t's action on a cell's gamma: a callable (p, lab, arg), arg() the log2 argument, formed
-//                                only when called
+//                                only when called (asked for once a frame, before the frame's first cell and the fence in front of it)
 //   cells_done(), frame_end(t, lo, hi)   after the frame's cells (before its reduction), and after its bookkeeping (before the
 //                                fast form's end-of-frame fence); a hook owns any barrier or fence that only its kernel needs
 // Storage: lattices walk slots (launch grid = slots, lattice i on slot i mod grid), so the workspace is bounded by the slots,
@@ -22,6 +22,14 @@
 #include "ka_posterior_common.hpp"
 
 namespace ka {
+
+// one cell's gamma as a float from its log2 argument (occ_fix of ka_occupancy.hpp before the fixed-point step): what the state
+// posteriors write and the state durations add
+__device__ __forceinline__ float fb_gamma(double arg)
+{
+    const float g = __builtin_amdgcn_exp2f((float)arg);
+    return g < 1.0f ? g : 1.0f;
+}
 
 // ---------------------------------------------------------------------------------------
 // fast form: one wavefront per lattice, band <= kFastMaxBand, V <= 64, M = max_move <= 4; the cell layout of

@@ -86,11 +86,12 @@ void launch_power_to_db(float *x, int64_t ld, int cols, const int64_t *frame_off
 // n_generic): one 256-thread workgroup per lattice, columns in global memory
 void launch_posteriors(const PostLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 
-// ---- ka_occupancy.hip / ka_state_posterior.hip: label occupancy and state posteriors at chosen frames (ka_occupancy.hpp,
-// ka_state_posterior.hpp), both through launch_fb_ck (ka_fb_ck.hpp): descriptors [0, n_fast): one wavefront per lattice on
+// ---- ka_occupancy.hip / ka_state_posterior.hip / ka_duration.hip: label occupancy, state posteriors at chosen frames and
+// expected state durations (ka_occupancy.hpp, ka_state_posterior.hpp, ka_duration.hpp), all through launch_fb_ck (ka_fb_ck.hpp): descriptors [0, n_fast): one wavefront per lattice on
 // min(n_fast, kOccFastSlots) workgroups, lattice i on workgroup i mod grid (its workspace slot); then [n_fast, n_fast +
 // n_generic): 256-thread workgroups, min(n_generic, kOccGenericSlots)
 void launch_label_posteriors(const OccLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 void launch_state_posteriors(const StateLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+void launch_state_durations(const DurLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 
 }  // namespace ka

@@ -757,3 +757,31 @@ inline size_t state_posterior_workspace(int32_t n, const int64_t *T, const int64
 
 }  // namespace plan
 }  // namespace ka
+
+namespace ka {
+namespace plan {
+
+// ---- ka_ctc_state_durations_batch_f32 (ka_duration.hpp): workspace layout ----
+// label_posterior_workspace's layout and slots (the slot's V-wide global bins go unused), with DurLattice descriptors.  The
+// generic form accumulates in the outputs, so a slot holds nothing more; for host buffers the staged duration and time_sum
+// (2S+1 doubles each) lie beside the staged log-probs and labels.
+struct DurCarve : SlotCarve {
+    size_t dur, tsum;   // host buffers only
+};
+inline size_t state_duration_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move,
+                                       bool host_buffers, DurCarve *cv, size_t *off_res)
+{
+    return slot_workspace(n, sizeof(DurLattice), T, S, V, beam, max_move, cv, off_res, [&](int32_t, const Shape &sh, DurCarve &c, size_t &off) {
+        if (host_buffers) {
+            carve_staged(off, sh, V, c);
+            c.dur = off;
+            off += align_up((size_t)sh.L * sizeof(double));
+            c.tsum = off;
+            off += align_up((size_t)sh.L * sizeof(double));
+        }
+        return true;
+    });
+}
+
+}  // namespace plan
+}  // namespace ka

@@ -17,12 +17,6 @@
 
 namespace ka {
 
-// one cell's gamma from its log2 argument (occ_fix of ka_occupancy.hpp before the fixed-point step)
-__device__ __forceinline__ float st_gamma(double arg)
-{
-    const float g = __builtin_amdgcn_exp2f((float)arg);
-    return g < 1.0f ? g : 1.0f;
-}
 // the query frame at index kq, or -1 below the first
 __device__ __forceinline__ int64_t st_frame(const StateLattice &d, int64_t kq) { return kq >= 0 ? d.frames[kq] : -1; }
 
@@ -49,7 +43,7 @@ struct StOut {
         const bool hit = fq == t;
         float *grow = d.gamma + (size_t)(hit ? kq : 0) * (size_t)d.ld_out;
         return [=](int64_t p, int32_t, auto arg) {
-            if (hit) grow[p - lo] = st_gamma(arg());
+            if (hit) grow[p - lo] = fb_gamma(arg());
         };
     }
     __device__ __forceinline__ void cells_done() {}

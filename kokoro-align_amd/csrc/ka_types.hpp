@@ -183,8 +183,14 @@ struct StateLattice : FbCkLattice {
     int32_t K;
     int32_t W;                    // widest band: max(1, min(beam, L))
 };
+// ---- expected state durations (ka_duration.hpp): the occupancy's slots and form split ----
+struct DurLattice : FbCkLattice {
+    double *dur;                  // [L] output: D(s) = sum over t of gamma_t(s)
+    double *tsum;                 // [L] output, or NULL: B(s) = sum over t of t gamma_t(s)
+};
 // the workspace planners (ka_plan.hpp) carve n descriptors: their sizes are part of the published workspace byte counts
-static_assert(sizeof(PostLattice) == 88 && sizeof(FbCkLattice) == 104 && sizeof(OccLattice) == 120 && sizeof(StateLattice) == 136,
+static_assert(sizeof(PostLattice) == 88 && sizeof(FbCkLattice) == 104 && sizeof(OccLattice) == 120 && sizeof(StateLattice) == 136 &&
+                  sizeof(DurLattice) == 120,
               "descriptor sizes");
 
 }  // namespace ka

@@ -1,6 +1,7 @@
-"""Forward-backward over the band of ``ctc_best_path``: path posteriors, label occupancy, state posteriors at chosen frames.
+"""Forward-backward over the band of ``ctc_best_path``: path posteriors, label occupancy, state posteriors at chosen frames,
+expected state durations.
 
-The three calls take the same lattices (log-probs, labels, beam_size, max_move) in host or device memory and answer with one
+The four calls take the same lattices (log-probs, labels, beam_size, max_move) in host or device memory and answer with one
 log-likelihood and one status per lattice.  ``_Lattices`` is that common input, normalised once and aware of its memory mode;
 ``_run_lattices`` is the one C call and the one status handling.  What is a call's own (its extra inputs, its outputs, its
 argument tables) is in its private function; ``X_batch`` and ``X_device`` only choose the memory mode.
@@ -20,7 +21,7 @@ _POSTERIOR_LATTICE_STATUSES = (_lib.KA_OK, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NA
 # the lattices of one call and the call itself
 # ------------------------------------------------------------------------------------------
 class _Lattices:
-    """n lattices as one ``ka_ctc_*_posteriors_batch_f32`` call takes them: ``lps`` float32 [T_i, V] with unit column
+    """n lattices as one ``ka_ctc_<call>_batch_f32`` call takes them: ``lps`` float32 [T_i, V] with unit column
     stride, ``labs`` int32 [S_i].  What differs between host and device memory is in the attributes ``mode`` brings:
     form, mem, dev, ptr(x), ld(x) (row pitch), int32(x) (a per-position input as the call wants it), empty(shape, dtype),
     engine(), stream(), guard()."""
@@ -75,7 +76,7 @@ def _device_lattices(log_probs, labels, others, what):
             lp = lp.contiguous()
         lps.append(lp)
     dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
-    dtypes = {np.float32: torch.float32, np.int64: torch.int64}
+    dtypes = {np.float32: torch.float32, np.float64: torch.float64, np.int64: torch.int64}
 
     def int32(x):
         x = x if _is_tensor(x) else torch.as_tensor(np.asarray(x).reshape(-1).astype(np.int32))
@@ -87,11 +88,11 @@ def _device_lattices(log_probs, labels, others, what):
                      guard=lambda: torch.cuda.device(dev))
 
 
-def _run_lattices(lat, kind, beam_size, max_move, own_args, outs, return_status):
-    """The call ``ka_ctc_<kind>_posteriors_batch_f32``: the arguments all three take around ``own_args`` (the call's own
-    tables), then the results (*outs[i], log_likelihood[i]), ``outs`` a list of tuples, and the status handling of
-    ``return_status``."""
-    name = f"ctc_{kind}_posteriors_{lat.form}"
+def _run_lattices(lat, call, beam_size, max_move, own_args, outs, return_status):
+    """The call ``ka_ctc_<call>_batch_f32`` (path_posteriors, label_posteriors, state_posteriors, state_durations): the
+    arguments all of them take around ``own_args`` (the call's own tables), then the results (*outs[i], log_likelihood[i]),
+    ``outs`` a list of tuples, and the status handling of ``return_status``."""
+    name = f"ctc_{call}_{lat.form}"
     status = np.zeros(lat.n, np.int32)
     ll = np.zeros(lat.n, np.float64)
     eng = lat.engine()
@@ -101,7 +102,7 @@ def _run_lattices(lat, kind, beam_size, max_move, own_args, outs, return_status)
     p_S, _k4 = _i64_array(lat.S)
     p_ld, _k5 = _i64_array([lat.ld(x) for x in lat.lps])
     with lat.guard():
-        rc = getattr(eng.lib, f"ka_ctc_{kind}_posteriors_batch_f32")(
+        rc = getattr(eng.lib, f"ka_ctc_{call}_batch_f32")(
             eng.handle, lat.n, p_lp, p_T, lat.V, p_ld, p_lab, p_S, int(beam_size), int(max_move), *own_args,
             ll.ctypes.data, status.ctypes.data, lat.mem, lat.stream())
     results = [(*o, float(z)) for o, z in zip(outs, ll)]
@@ -167,7 +168,7 @@ def _path_posteriors(lat, best_paths, beam_size, max_move, return_status):
     posts = [lat.empty(T, np.float32) for T in lat.T]
     p_path, _k1 = _ptr_array([lat.ptr(x) for x in paths])
     p_post, _k2 = _ptr_array([lat.ptr(x) for x in posts])
-    return _run_lattices(lat, "path", beam_size, max_move, (p_path, p_post), list(zip(posts)), return_status)
+    return _run_lattices(lat, "path_posteriors", beam_size, max_move, (p_path, p_post), list(zip(posts)), return_status)
 
 
 def ctc_path_posteriors_batch(log_probs_list, labels_list, best_path_list, beam_size=1000, max_move=4, device=None,
@@ -228,7 +229,7 @@ def _label_posteriors(lat, terminals, beam_size, max_move, out, return_status):
     p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
     p_occ, _k2 = _ptr_array([lat.ptr(x) for x in occs])
     p_ldo, _k3 = _i64_array([lat.ld(x) for x in occs])
-    return _run_lattices(lat, "label", beam_size, max_move, (p_term, p_occ, p_ldo), list(zip(occs)), return_status)
+    return _run_lattices(lat, "label_posteriors", beam_size, max_move, (p_term, p_occ, p_ldo), list(zip(occs)), return_status)
 
 
 def ctc_label_posteriors_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False):
@@ -394,7 +395,7 @@ def _state_posteriors(lat, terminals, frames, beam_size, max_move, out, return_s
     p_g, _k4 = _ptr_array([lat.ptr(g) for g in gammas])
     p_ldo, _k5 = _i64_array([max(lat.ld(g), W) for g, W in zip(gammas, Ws)])   # (a tensor with no rows may report any stride)
     p_lo, _k6 = _ptr_array([lat.ptr(x) for x in los])
-    return _run_lattices(lat, "state", beam_size, max_move, (p_term, p_fr, p_K, p_g, p_ldo, p_lo), list(zip(gammas, los)),
+    return _run_lattices(lat, "state_posteriors", beam_size, max_move, (p_term, p_fr, p_K, p_g, p_ldo, p_lo), list(zip(gammas, los)),
                          return_status)
 
 
@@ -458,3 +459,112 @@ def segment_boundary_confidence(gamma, band_lo, frames, best_path, seg_ends, n_p
         p_start[i] = p_at(a)
         p_end[i] = p_at(b) if b < T else 1.0
     return p_start, p_end
+
+
+# ------------------------------------------------------------------------------------------
+# expected state durations and the expected frame of every text boundary
+# ------------------------------------------------------------------------------------------
+def ctc_state_durations(log_probs, labels, terminal, beam_size=1000, max_move=4):
+    """How long the model expects every state to last: (duration float64 [L], time_sum float64 [L], log_likelihood float),
+    L = 2S+1 positions of the blank-expanded labels (odd position 2i+1: phoneme i, even positions: the blanks around them).
+
+    duration[s] is the expected number of frames spent in state s and time_sum[s] the expected sum of those frames' indices
+    (time_sum / duration: the state's expected centre frame), over every path of the band of ``ctc_best_path`` that ends at
+    state ``terminal`` (an int, or a best path whose last value is used): the state posteriors of ``ctc_state_posteriors``
+    summed over all T frames, without the [T, W] matrix.  duration sums to T.  NumPy in -> NumPy out; ROCm torch tensors go
+    to ``ctc_state_durations_device``.  Raises as ``ctc_label_posteriors``.
+    """
+    call = ctc_state_durations_device if _is_tensor(log_probs) else ctc_state_durations_batch
+    (result,) = call([log_probs], [labels], [terminal], beam_size, max_move)
+    return result
+
+
+def _state_durations(lat, terminals, beam_size, max_move, out, return_status):
+    if lat is None:
+        return ([], []) if return_status else []
+    Ls = [2 * S + 1 for S in lat.S]
+    if out is None:
+        durs = [lat.empty(L, np.float64) for L in Ls]
+        sums = [lat.empty(L, np.float64) for L in Ls]
+    else:
+        import torch
+        if len(out) != lat.n or any(len(o) != 2 for o in out):
+            raise ValueError("out must hold one (duration, time_sum) pair of tensors per lattice")
+        for o, L in zip(out, Ls):
+            if any(x.dtype != torch.float64 or tuple(x.shape) != (L,) or not x.is_contiguous() or x.device != lat.dev for x in o):
+                raise ValueError("out tensors must be contiguous float64 [2 S_i + 1] on the input's device")
+        durs, sums = [o[0] for o in out], [o[1] for o in out]
+    p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
+    p_dur, _k2 = _ptr_array([lat.ptr(x) for x in durs])
+    p_sum, _k3 = _ptr_array([lat.ptr(x) for x in sums])
+    return _run_lattices(lat, "state_durations", beam_size, max_move, (p_term, p_dur, p_sum), list(zip(durs, sums)), return_status)
+
+
+def ctc_state_durations_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False):
+    """State durations of many lattices in ONE launch; host NumPy buffers in and out.
+
+    Returns a list of (duration [L_i], time_sum [L_i], log_likelihood); with ``return_status`` also the per-lattice status
+    list, in which case failures do not raise (their arrays are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    """
+    lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
+    return _state_durations(lat, terminals, beam_size, max_move, None, return_status)
+
+
+def ctc_state_durations_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]) and terminals (ints
+    or best paths), list of (duration, time_sum: float64 tensors [2 S_i + 1] on the device, log_likelihood float) out.
+    ``out``: optional list of (duration, time_sum) pairs of contiguous float64 tensors to write into.  One launch on torch's
+    current stream."""
+    lat = _device_lattices(log_probs, labels, terminals, "terminals")
+    return _state_durations(lat, terminals, beam_size, max_move, out, return_status)
+
+
+def _host_f64(x):
+    return np.asarray(x.detach().cpu() if _is_tensor(x) else x, dtype=np.float64).reshape(-1)
+
+
+def phoneme_durations(duration):
+    """(labels [S], blanks [S+1]) from ``ctc_state_durations``' duration [2S+1]: the expected frames of every phoneme (the odd
+    positions) and of the blanks before, between and after them (the even ones).  float64 arrays (host)."""
+    d = _host_f64(duration)
+    if len(d) % 2 == 0:
+        raise ValueError("duration must have 2S+1 entries")
+    return d[1::2].copy(), d[0::2].copy()
+
+
+def expected_crossing_frames(duration, cuts):
+    """E[tau_c] for every cut position c in ``cuts`` (each in [0, L]), tau_c the first frame whose state is >= c.  Paths only
+    move up, so state_t < c exactly for t < tau_c and E[tau_c] = sum_t P(state_t < c) = sum of duration[s] over s < c: the
+    prefix sum of ``duration`` read at c (0 for c = 0, T for c = L).  float64 array (host)."""
+    d = _host_f64(duration)
+    c = np.asarray(cuts.detach().cpu() if _is_tensor(cuts) else cuts, dtype=np.int64).reshape(-1)
+    if len(c) and (c.min() < 0 or c.max() > len(d)):
+        raise ValueError(f"cuts must lie in [0, {len(d)}]")
+    return np.concatenate([np.zeros(1), np.cumsum(d)])[c]
+
+
+def segment_boundary_shift(duration, best_path, seg_ends, n_phonemes):
+    """How far, in frames, the lattice expects each text boundary of ``align()`` from where the best path puts it (host only).
+
+    For every boundary frame b that ``align()`` reads the best path at - ``boundary_frames(seg_ends, T)``: 0 and every
+    seg_ends[i] < T - the text index is i = min(best_path[b] // 2, n_phonemes) and the cut position c = 2 i.  The best
+    path's crossing frame is the first t with best_path[t] >= c; the expected one is E[tau_c] of
+    ``expected_crossing_frames``.  shift = E[tau_c] - that frame: positive where the lattice expects the boundary later than
+    the best path crosses it.  Returns (start_shift, end_shift), float64 per segment that ``align()`` writes a line for
+    (frames [a, b), a = seg_ends[i-1], 0 for the first, b = seg_ends[i]): the shift of the boundary read at a and of the one
+    read at b, the latter 0 where b >= T - there ``align()`` runs the text to its end whatever the path does."""
+    d = _host_f64(duration)
+    path = np.asarray(best_path.detach().cpu() if _is_tensor(best_path) else best_path, dtype=np.int64).reshape(-1)
+    T, n_ph = len(path), int(n_phonemes)
+    prefix = np.concatenate([np.zeros(1), np.cumsum(d)])
+    reached = np.maximum.accumulate(path) if T else path      # (a best path never moves down; any other path: its running maximum)
+    shift = {}
+    for b in boundary_frames(seg_ends, T):
+        c = 2 * min(int(path[b]) // 2, n_ph)
+        if c > len(d):
+            raise ValueError("segment_boundary_shift: a best-path position outside the duration's positions")
+        shift[int(b)] = float(prefix[c]) - float(np.searchsorted(reached, c, side="left"))
+    segs = _segments(np.asarray(seg_ends, dtype=np.int64), T)
+    start = np.array([shift[a] if a < T else 0.0 for _, a, _ in segs], dtype=np.float64)
+    end = np.array([shift[b] if b < T else 0.0 for _, _, b in segs], dtype=np.float64)   # (b is clipped to T: b < T is seg_ends[i] < T)
+    return start, end

@@ -3,10 +3,13 @@ shapes of DESIGN.md section 4.17: one cfg2 lattice, cfg2 batches of 1024 and 819
 and of ka_ctc_label_posteriors_batch_f32 (label occupancy, ka_occupancy.hpp, section 4.18) on the same cfg2 shapes, the
 terminal taken from the best path (cases occ_single, occ_b1024, occ_b8192); and of ka_ctc_state_posteriors_batch_f32 (state
 posteriors at chosen frames, ka_state_posterior.hpp, section 4.19) with 200 query frames spread over every lattice (cases
-state_single, state_b1024).
+state_single, state_b1024); and of ka_ctc_state_durations_batch_f32 (expected state durations, ka_duration.hpp, section 4.22)
+on the occupancy's shapes and terminals (cases dur_single, dur_b1024).
 
     python tools/bench_posteriors.py [--cases single,b1024,b8192,corpus] [--reps 3] [--out profiles/posteriors.jsonl]
     python tools/bench_posteriors.py --cases state_single,state_b1024 --out profiles/state_posteriors_bench.jsonl
+    python tools/bench_posteriors.py --cases occ_single,dur_single,occ_b1024,dur_b1024,occ_single,dur_single,occ_b1024,dur_b1024 \
+        --out profiles/duration_bench.jsonl
 
 Device-resident inputs (hash-generated); best paths from the library's own best-path call.  The 8192 batch points its
 lattices at the 1024 batch's log-probs, labels and paths eight times over (distinct outputs): 105 GB of log-probs would
@@ -44,10 +47,10 @@ def best_paths(lps, labs):
     return b.path
 
 
-def time_batch(kind, ws_name, lps, labs, own_args, reps, ws_own=()):
-    """ms per call of ka_ctc_<kind>_posteriors_batch_f32 on device buffers: the arguments the three calls share around
+def time_batch(call_name, ws_name, lps, labs, own_args, reps, ws_own=()):
+    """ms per call of ka_ctc_<call_name>_batch_f32 on device buffers: the arguments the four calls share around
     ``own_args`` (the caller keeps what they point to alive), the workspace reserved first, one warm-up call."""
-    name = f"ka_ctc_{kind}_posteriors_batch_f32"
+    name = f"ka_ctc_{call_name}_batch_f32"
     n, V = len(lps), int(lps[0].shape[1])
     eng = _lib.default_engine(torch.cuda.current_device())
     ll = np.zeros(n, np.float64)
@@ -77,7 +80,7 @@ def time_batch(kind, ws_name, lps, labs, own_args, reps, ws_own=()):
 def time_posteriors(lps, labs, paths, reps):
     posts = [torch.empty(int(x.shape[0]), dtype=torch.float32, device="cuda") for x in lps]
     k = [_ptr_array([x.data_ptr() for x in xs]) for xs in (paths, posts)]
-    return time_batch("path", "ka_posterior_workspace_bytes", lps, labs, (k[0][0], k[1][0]), reps)
+    return time_batch("path_posteriors", "ka_posterior_workspace_bytes", lps, labs, (k[0][0], k[1][0]), reps)
 
 
 def time_occupancy(lps, labs, paths, reps):
@@ -86,7 +89,7 @@ def time_occupancy(lps, labs, paths, reps):
     p_occ = _ptr_array([x.data_ptr() for x in occs])
     ldo = _i64_array([x.stride(0) for x in occs])
     term = _i64_array(torch.stack([p[-1] for p in paths]).cpu().tolist())
-    return time_batch("label", "ka_label_posterior_workspace_bytes", lps, labs, (term[0], p_occ[0], ldo[0]), reps)
+    return time_batch("label_posteriors", "ka_label_posterior_workspace_bytes", lps, labs, (term[0], p_occ[0], ldo[0]), reps)
 
 
 def time_states(lps, labs, paths, reps, K=200):
@@ -99,8 +102,16 @@ def time_states(lps, labs, paths, reps, K=200):
     Ks = _i64_array([len(f) for f in frames])
     ldo = _i64_array(W)
     term = _i64_array(torch.stack([p[-1] for p in paths]).cpu().tolist())
-    return time_batch("state", "ka_state_posterior_workspace_bytes", lps, labs, (term[0], fr[0], Ks[0], k[0][0], ldo[0], k[1][0]),
+    return time_batch("state_posteriors", "ka_state_posterior_workspace_bytes", lps, labs, (term[0], fr[0], Ks[0], k[0][0], ldo[0], k[1][0]),
                       reps, ws_own=(Ks[0],))
+
+
+def time_durations(lps, labs, paths, reps):
+    durs = [torch.empty(2 * int(x.shape[0]) + 1, dtype=torch.float64, device="cuda") for x in labs]
+    sums = [torch.empty(2 * int(x.shape[0]) + 1, dtype=torch.float64, device="cuda") for x in labs]
+    k = [_ptr_array([x.data_ptr() for x in xs]) for xs in (durs, sums)]
+    term = _i64_array(torch.stack([p[-1] for p in paths]).cpu().tolist())
+    return time_batch("state_durations", "ka_state_duration_workspace_bytes", lps, labs, (term[0], k[0][0], k[1][0]), reps)
 
 
 def main():
@@ -114,7 +125,7 @@ def main():
     cases = a.cases.split(",")
     b1024 = None
     for case in cases:
-        kind = case.split("_")[0] if case.startswith(("occ_", "state_")) else "path"
+        kind = case.split("_")[0] if case.startswith(("occ_", "state_", "dur_")) else "path"
         case_in = case[len(kind) + 1:] if kind != "path" else case
         if case_in == "single":
             lps, labs = cfg2(1)
@@ -135,7 +146,7 @@ def main():
             raise SystemExit(f"unknown case {case}")
         if case_in in ("single", "corpus"):
             paths = best_paths(lps, labs)
-        ms, st, ll = {"path": time_posteriors, "occ": time_occupancy, "state": time_states}[kind](lps, labs, paths, a.reps)
+        ms, st, ll = {"path": time_posteriors, "occ": time_occupancy, "state": time_states, "dur": time_durations}[kind](lps, labs, paths, a.reps)
         frames = sum(int(x.shape[0]) for x in lps)
         line = dict(case=case, lattices=len(lps), frames=frames, ms_min=round(min(ms), 3), ms_median=round(float(np.median(ms)), 3),
                     frames_per_s=frames / (min(ms) / 1e3), status_ok=int((st == 0).sum()), reps=a.reps)

@@ -4,12 +4,20 @@ them, rounded up to two digits (tests/posterior_ref.py).
 
     KA_ACCURACY_OUT=ratios.jsonl python -m pytest tests -q -m gpu -k posterior
     python tools/posterior_accuracy.py ratios.jsonl profiles/posterior_accuracy.json
+
+The state duration call (tests/test_durations_gpu.py, tests/duration_ref.py) records four figures of
+its own under the multiplier of the state call.  With call names after the two files only those are reduced and every other
+key of the existing file stays as it is:
+
+    KA_ACCURACY_OUT=ratios.jsonl python -m pytest tests/test_durations_gpu.py -q -m gpu
+    python tools/posterior_accuracy.py ratios.jsonl profiles/posterior_accuracy.json duration time_sum duration_sum time_sum_sum
 """
 import json
 import math
 import sys
 
 CALLS = ("state", "label", "path", "z")
+DURATION_CALLS = ("duration", "time_sum", "duration_sum", "time_sum_sum")
 
 
 def round_up(x):
@@ -20,8 +28,10 @@ def round_up(x):
     return round(math.ceil(x / 10 ** e - 1e-9) * 10 ** e, 10)
 
 
-def main(src, dst):
-    worst = {c: {} for c in CALLS}
+def main(src, dst, only=()):
+    calls = tuple(only) or CALLS
+    assert all(c in CALLS + DURATION_CALLS for c in calls), calls
+    worst = {c: {} for c in calls}
     with open(src) as f:
         for line in f:
             rec = json.loads(line)
@@ -33,16 +43,21 @@ def main(src, dst):
            "unit": "max over the cells of a test of |kernel - float64| / E; E = posterior_ref.*_error_model of the float64 reference",
            "rule": "m = twice the worst measured ratio of its call, rounded up to two digits (tests/posterior_ref.py)",
            "calls": {}}
-    for c in CALLS:
+    if only:                                     # the file as it is, with the named calls replaced
+        with open(dst) as f:
+            out = json.load(f)
+    for c in calls:
         top = max(worst[c].values(), default=0.0)
-        out["calls"][c] = {"m": round_up(2 * top), "worst_ratio": top, "tests": len(worst[c]),
+        # (the duration figures are held against the state call's multiplier: their model is a sum of its per-cell model)
+        m = out["calls"]["state"]["m"] if c in DURATION_CALLS and "state" in out["calls"] else round_up(2 * top)
+        out["calls"][c] = {"m": m, "worst_ratio": top, "tests": len(worst[c]),
                            "records": [{"test": t, "ratio": r} for t, r in sorted(worst[c].items())]}
     with open(dst, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")
-    for c in CALLS:
+    for c in calls:
         print(c, out["calls"][c]["tests"], "tests, worst", out["calls"][c]["worst_ratio"], "m", out["calls"][c]["m"])
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2])
+    main(sys.argv[1], sys.argv[2], sys.argv[3:])
