@@ -70,11 +70,11 @@ while time.time() < t_end and len(bad) < 10:
         for i, (r, st, w) in enumerate(zip(res, status, wants)):
             if w is None:
                 if st != -1:
-                    bad.append((mode, bt, width, gather, shapes[i], V, beam, mm, "status", int(st)))
+                    bad.append((mode, bt, width, shapes[i], V, beam, mm, "status", int(st)))
             elif st != 0 or not (np.array_equal(r[0], w[0]) and np.array_equal(r[1], w[1]) and
                                  np.array_equal(r[2].view(np.int32), w[2].view(np.int32))):
                 first = int(np.argmax(r[0] != w[0])) if st == 0 and r[0].shape == w[0].shape else -1
-                bad.append((mode, bt, width, gather, shapes[i], V, beam, mm, "zero" if zero_labels else "", "ties" if quantised else "", int(st), first))
+                bad.append((mode, bt, width, shapes[i], V, beam, mm, "zero" if zero_labels else "", "ties" if quantised else "", int(st), first))
 eng.set_mode("auto")
 eng.set_backtrace("auto")
 eng.set_tile_width(0)
