@@ -1,0 +1,419 @@
+// ka_engine_fb.hip — the forward-backward calls of the C ABI: best-path posteriors (ka_posterior.hpp), label occupancy
+// (ka_occupancy.hpp), state posteriors at chosen frames (ka_state_posterior.hpp) and expected state durations (ka_duration.hpp).
+// Host code only.  They use the engine's workspace and pinned buffer, with their own kernels and workspace layout, whatever
+// the engine's mode, and run to the end inside the call: no batch stays in flight.
+#include "ka_engine.hpp"
+
+#include <algorithm>
+#include <cstring>
+
+namespace {
+
+using namespace ka::host;
+using ka::plan::align_up;
+
+// ---- best-path posteriors (ka_posterior.hpp), label occupancy (ka_occupancy.hpp), state posteriors at chosen frames
+// (ka_state_posterior.hpp) and expected state durations (ka_duration.hpp): their own kernels and workspace layout, whatever the
+// engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall, DurCall) brings what differs: its own arrays and their
+// checks, its planner and launch, the descriptor fields beyond FbLattice, its own staging (upload: host buffers only;
+// stage: every memory mode), and what two statuses mean.
+struct FbArgs {
+    int32_t n;
+    const float *const *log_probs;
+    const int64_t *T;
+    int32_t V;
+    const int64_t *ld;
+    const int32_t *const *labels;
+    const int64_t *S;
+    int32_t beam_size, max_move;
+    double *log_likelihood;
+    int32_t *status;
+    int32_t mem;
+    hipStream_t stream;
+};
+
+struct PostCall {
+    using Desc = ka::PostLattice;
+    using Carve = ka::plan::PostCarve;
+    static constexpr const char *kName = "posteriors";
+    static constexpr const char *kBadArgs = ": a best-path position outside [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score reaches the best path's terminal";
+    const int32_t *const *best_path;
+    float *const *posteriors;
+
+    bool arrays() const { return best_path && posteriors; }
+    const char *bad_lattice(const FbArgs &, int32_t) const { return nullptr; }
+    bool buffers(int32_t i) const { return best_path[i] && posteriors[i]; }
+    static constexpr auto plan = ka::plan::posterior_workspace;
+    static constexpr auto launch = ka::launch_posteriors;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (a.mem == KA_MEM_HOST) {
+            d.path = reinterpret_cast<const int32_t *>(ws + c.path);
+            d.post = reinterpret_cast<float *>(ws + c.post);
+        } else {
+            d.path = best_path[i];
+            d.post = posteriors[i];
+        }
+        d.ck = reinterpret_cast<double *>(ws + c.ck);
+        d.col = reinterpret_cast<double *>(ws + c.col);
+    }
+    int upload(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        KA_HIP(hipMemcpyAsync(ws + c.path, best_path[i], (size_t)a.T[i] * 4, hipMemcpyHostToDevice, a.stream));
+        return KA_OK;
+    }
+    int stage(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        KA_HIP(hipMemcpyAsync(posteriors[i], ws + c.post, (size_t)a.T[i] * 4, hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
+// the FbCkLattice fields that the slot calls (OccCall, StateCall, DurCall) fill alike: the lattice's slot, its terminal, the column stride
+void fill_slot(ka::FbCkLattice &d, const ka::plan::SlotCarve &c, int64_t terminal, char *ws)
+{
+    d.ck = reinterpret_cast<double *>(ws + c.slot + c.parts.ck);
+    d.ckcol = reinterpret_cast<double *>(ws + c.slot + c.parts.ckcol);
+    d.slab = reinterpret_cast<double *>(ws + c.slot + c.parts.slab);
+    d.col = reinterpret_cast<double *>(ws + c.slot + c.parts.col);
+    d.terminal = (terminal >= 0 && terminal <= INT32_MAX) ? (int32_t)terminal : -1;
+    d.cw = c.parts.cw;
+}
+
+struct OccCall {
+    using Desc = ka::OccLattice;
+    using Carve = ka::plan::OccCarve;
+    static constexpr const char *kName = "label posteriors";
+    static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score reaches the terminal";
+    const int64_t *terminal;
+    float *const *occupancy;
+    const int64_t *ld_out;
+
+    bool arrays() const { return terminal && occupancy && ld_out; }
+    const char *bad_lattice(const FbArgs &a, int32_t i) const { return ld_out[i] < a.V ? ": ld_out < V" : nullptr; }
+    bool buffers(int32_t i) const { return occupancy[i] != nullptr; }
+    static constexpr auto plan = ka::plan::label_posterior_workspace;
+    static constexpr auto launch = ka::launch_label_posteriors;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (a.mem == KA_MEM_HOST) {
+            d.occ = reinterpret_cast<float *>(ws + c.occ);
+            d.ld_out = a.V;
+        } else {
+            d.occ = occupancy[i];
+            d.ld_out = ld_out[i];
+        }
+        fill_slot(d, c, terminal[i], ws);
+        d.gbin = reinterpret_cast<unsigned long long *>(ws + c.slot + c.parts.gbin);
+    }
+    int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int stage(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        KA_HIP(hipMemcpy2DAsync(occupancy[i], (size_t)ld_out[i] * 4, ws + c.occ, (size_t)a.V * 4, (size_t)a.V * 4, (size_t)a.T[i],
+                                hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
+struct StateCall {
+    using Desc = ka::StateLattice;
+    using Carve = ka::plan::StateCarve;
+    static constexpr const char *kName = "state posteriors";
+    static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score reaches the terminal";
+    const int64_t *terminal;
+    const int64_t *const *frames;   // host arrays in both memory modes
+    const int64_t *K;
+    float *const *gamma;
+    const int64_t *ld_out;
+    int64_t *const *band_lo;
+
+    bool arrays() const { return terminal && frames && K && gamma && ld_out && band_lo; }
+    const char *bad_lattice(const FbArgs &a, int32_t i) const
+    {
+        const int64_t k = K[i];
+        if (k > 0 && !frames[i]) return ": NULL frames";
+        for (int64_t j = 0; j < k; ++j) {
+            if (frames[i][j] < 0 || frames[i][j] >= a.T[i]) return ": a frame outside [0, T)";
+            if (j > 0 && frames[i][j] <= frames[i][j - 1]) return ": frames not strictly increasing";
+        }
+        const int64_t W = std::max<int64_t>(1, std::min<int64_t>(a.beam_size, 2 * a.S[i] + 1));
+        return ld_out[i] < W ? ": ld_out < min(beam_size, 2S+1)" : nullptr;
+    }
+    bool buffers(int32_t i) const { return K[i] == 0 || (gamma[i] && band_lo[i]); }
+    size_t plan(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host, Carve *cv,
+                size_t *off_res) const
+    {
+        return ka::plan::state_posterior_workspace(n, T, S, K, V, beam, max_move, host, cv, off_res);   // (0 for K < 0 or K > T)
+    }
+    static constexpr auto launch = ka::launch_state_posteriors;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (a.mem == KA_MEM_HOST) {
+            d.gamma = reinterpret_cast<float *>(ws + c.gamma);
+            d.band_lo = reinterpret_cast<int64_t *>(ws + c.band_lo);
+            d.ld_out = c.W;
+        } else {
+            d.gamma = gamma[i];
+            d.band_lo = band_lo[i];
+            d.ld_out = ld_out[i];
+        }
+        fill_slot(d, c, terminal[i], ws);
+        d.frames = reinterpret_cast<const int64_t *>(ws + c.frames);
+        d.K = (int32_t)K[i];
+        d.W = c.W;
+    }
+    int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int stage(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (K[i] > 0) KA_HIP(hipMemcpyAsync(ws + c.frames, frames[i], (size_t)K[i] * 8, hipMemcpyHostToDevice, a.stream));
+        return KA_OK;
+    }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (K[i] == 0) return KA_OK;
+        KA_HIP(hipMemcpy2DAsync(gamma[i], (size_t)ld_out[i] * 4, ws + c.gamma, (size_t)c.W * 4, (size_t)c.W * 4, (size_t)K[i],
+                                hipMemcpyDeviceToHost, a.stream));
+        KA_HIP(hipMemcpyAsync(band_lo[i], ws + c.band_lo, (size_t)K[i] * 8, hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
+struct DurCall {
+    using Desc = ka::DurLattice;
+    using Carve = ka::plan::DurCarve;
+    static constexpr const char *kName = "state durations";
+    static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score reaches the terminal";
+    const int64_t *terminal;
+    double *const *duration;
+    double *const *time_sum;   // NULL, or an array in which any entry may be NULL: no first moment for that lattice
+
+    bool arrays() const { return terminal && duration; }
+    const char *bad_lattice(const FbArgs &, int32_t) const { return nullptr; }
+    bool buffers(int32_t i) const { return duration[i] != nullptr; }
+    bool moment(int32_t i) const { return time_sum && time_sum[i]; }
+    static constexpr auto plan = ka::plan::state_duration_workspace;
+    static constexpr auto launch = ka::launch_state_durations;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (a.mem == KA_MEM_HOST) {
+            d.dur = reinterpret_cast<double *>(ws + c.dur);
+            d.tsum = moment(i) ? reinterpret_cast<double *>(ws + c.tsum) : nullptr;
+        } else {
+            d.dur = duration[i];
+            d.tsum = moment(i) ? time_sum[i] : nullptr;
+        }
+        fill_slot(d, c, terminal[i], ws);
+    }
+    int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int stage(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        const size_t bytes = (size_t)(2 * a.S[i] + 1) * sizeof(double);
+        KA_HIP(hipMemcpyAsync(duration[i], ws + c.dur, bytes, hipMemcpyDeviceToHost, a.stream));
+        if (moment(i)) KA_HIP(hipMemcpyAsync(time_sum[i], ws + c.tsum, bytes, hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
+template <class Call>
+int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
+{
+    using Desc = typename Call::Desc;
+    const int32_t n = a.n, V = a.V;
+    const hipStream_t stream = a.stream;
+    const bool host = a.mem == KA_MEM_HOST;
+    if (!e) return fail(KA_ERR_BAD_ARGS, "engine is NULL");
+    if (e->batch.pending) return fail(KA_ERR_BAD_ARGS, "a batch is already enqueued: call ka_batch_finish first");
+    if (n < 0 || (n > 0 && (!a.log_probs || !a.T || !a.ld || !a.labels || !a.S || !call.arrays())))
+        return fail(KA_ERR_BAD_ARGS, std::string(Call::kName) + ": NULL array argument");
+    if (a.mem != KA_MEM_HOST && a.mem != KA_MEM_DEVICE) return fail(KA_ERR_BAD_ARGS, "mem must be KA_MEM_HOST or KA_MEM_DEVICE");
+    if (n == 0) return KA_OK;
+    std::vector<typename Call::Carve> cv(n);
+    size_t off_res = 0;
+    const size_t total = call.plan(n, a.T, a.S, V, a.beam_size, a.max_move, host, cv.data(), &off_res);
+    if (total == 0) return fail(KA_ERR_BAD_ARGS, std::string(Call::kName) + ": unsupported T/S/V/beam_size/max_move");
+    for (int32_t i = 0; i < n; ++i) {
+        if (a.ld[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld < V");
+        if (const char *why = call.bad_lattice(a, i)) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + why);
+        if (!a.log_probs[i] || !call.buffers(i) || (a.S[i] > 0 && !a.labels[i]))
+            return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": NULL buffer");
+    }
+    DeviceGuard guard;
+    KA_HIP(guard.enter(e->device));
+    int rc = ensure_ws(e, total);
+    if (rc != KA_OK) return rc;
+    const size_t desc_bytes = align_up((size_t)n * sizeof(Desc));
+    rc = ensure_pin(e, desc_bytes + (size_t)n * sizeof(ka::PostResult));
+    if (rc != KA_OK) return rc;
+    // the workspace is shared with the best-path calls: wait for the refill behind their last tile launch, and what it left
+    // clean is clean no more
+    if (e->res.refill_done) KA_HIP(hipStreamWaitEvent(stream, e->res.refill_done, 0));
+    e->clean.invalidate();
+    e->dbg = ka_engine::DebugView();
+    // descriptors: fast-form lattices first, then the generic ones, each in batch order (the order occupancy slots assume)
+    Desc *h = reinterpret_cast<Desc *>(e->res.pin);
+    ka::PostResult *h_res = reinterpret_cast<ka::PostResult *>(e->res.pin + desc_bytes);
+    int32_t n_fast = 0;
+    for (int32_t i = 0; i < n; ++i) n_fast += cv[i].fast ? 1 : 0;
+    int32_t k_fast = 0, k_gen = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const auto &c = cv[i];
+        Desc &d = h[c.fast ? k_fast++ : n_fast + k_gen++];
+        std::memset(&d, 0, sizeof(d));
+        if (host) {
+            d.lp = reinterpret_cast<const float *>(e->res.ws + c.lp);
+            d.labels = reinterpret_cast<const int32_t *>(e->res.ws + c.lab);
+            d.ld = V;
+        } else {
+            d.lp = a.log_probs[i];
+            d.labels = a.labels[i];
+            d.ld = a.ld[i];
+        }
+        d.T = (int32_t)a.T[i];
+        d.S = (int32_t)a.S[i];
+        d.L = (int32_t)(2 * a.S[i] + 1);
+        d.V = V;
+        d.beam = a.beam_size;
+        d.max_move = a.max_move;
+        d.idx = i;
+        call.fill(d, c, a, i, e->res.ws);
+    }
+    if (host)
+        for (int32_t i = 0; i < n; ++i) {
+            KA_HIP(hipMemcpy2DAsync(e->res.ws + cv[i].lp, (size_t)V * 4, a.log_probs[i], (size_t)a.ld[i] * 4, (size_t)V * 4, (size_t)a.T[i],
+                                    hipMemcpyHostToDevice, stream));
+            if (a.S[i] > 0) KA_HIP(hipMemcpyAsync(e->res.ws + cv[i].lab, a.labels[i], (size_t)a.S[i] * 4, hipMemcpyHostToDevice, stream));
+            if ((rc = call.upload(cv[i], a, i, e->res.ws)) != KA_OK) return rc;
+        }
+    for (int32_t i = 0; i < n; ++i)
+        if ((rc = call.stage(cv[i], a, i, e->res.ws)) != KA_OK) return rc;
+    Desc *d_lats = reinterpret_cast<Desc *>(e->res.ws);
+    ka::PostResult *d_res = reinterpret_cast<ka::PostResult *>(e->res.ws + off_res);
+    KA_HIP(hipMemcpyAsync(d_lats, h, (size_t)n * sizeof(Desc), hipMemcpyHostToDevice, stream));
+    Call::launch(d_lats, n_fast, n - n_fast, a.max_move, d_res, stream);
+    KA_HIP(hipGetLastError());
+    KA_HIP(hipMemcpyAsync(h_res, d_res, (size_t)n * sizeof(ka::PostResult), hipMemcpyDeviceToHost, stream));
+    if (host)
+        for (int32_t i = 0; i < n; ++i)
+            if ((rc = call.download(cv[i], a, i, e->res.ws)) != KA_OK) return rc;
+    KA_HIP(hipStreamSynchronize(stream));
+    int first_bad = KA_OK;
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t st = h_res[i].status;
+        if (a.status) a.status[i] = st;
+        if (a.log_likelihood) a.log_likelihood[i] = h_res[i].log_likelihood;
+        if (st != KA_OK && first_bad == KA_OK) {
+            first_bad = st;
+            g_err = "lattice " + std::to_string(i) + status_message(st, {nullptr, nullptr, ": a log-prob is +inf", Call::kBadArgs, Call::kZeroMass});
+        }
+    }
+    return first_bad;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ka_ctc_path_posteriors_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                     const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                     const int32_t *const *best_path, float *const *posteriors, double *log_likelihood, int32_t *status,
+                                     int32_t mem, void *stream)
+{
+    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+                   PostCall{best_path, posteriors});
+}
+
+int ka_ctc_path_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                               int32_t beam_size, int32_t max_move, const int32_t *best_path, float *posteriors, double *log_likelihood,
+                               int32_t mem, void *stream)
+{
+    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+                   PostCall{&best_path, &posteriors});
+}
+
+size_t ka_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::posterior_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+int ka_ctc_label_posteriors_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                      const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                      const int64_t *terminal, float *const *occupancy, const int64_t *ld_out, double *log_likelihood,
+                                      int32_t *status, int32_t mem, void *stream)
+{
+    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+                   OccCall{terminal, occupancy, ld_out});
+}
+
+int ka_ctc_label_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                int32_t beam_size, int32_t max_move, int64_t terminal, float *occupancy, int64_t ld_out,
+                                double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+                   OccCall{&terminal, &occupancy, &ld_out});
+}
+
+size_t ka_label_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                          int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::label_posterior_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+int ka_ctc_state_posteriors_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                      const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                      const int64_t *terminal, const int64_t *const *frames, const int64_t *K, float *const *gamma,
+                                      const int64_t *ld_out, int64_t *const *band_lo, double *log_likelihood, int32_t *status, int32_t mem,
+                                      void *stream)
+{
+    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+                   StateCall{terminal, frames, K, gamma, ld_out, band_lo});
+}
+
+int ka_ctc_state_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                int32_t beam_size, int32_t max_move, int64_t terminal, const int64_t *frames, int64_t K, float *gamma,
+                                int64_t ld_out, int64_t *band_lo, double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+                   StateCall{&terminal, &frames, &K, &gamma, &ld_out, &band_lo});
+}
+
+size_t ka_state_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t V, int32_t beam_size,
+                                          int32_t max_move, int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S || !K)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::state_posterior_workspace(n, T, S, K, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+int ka_ctc_state_durations_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                     const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                     const int64_t *terminal, double *const *duration, double *const *time_sum, double *log_likelihood,
+                                     int32_t *status, int32_t mem, void *stream)
+{
+    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+                   DurCall{terminal, duration, time_sum});
+}
+
+int ka_ctc_state_durations_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                               int32_t beam_size, int32_t max_move, int64_t terminal, double *duration, double *time_sum,
+                               double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+                   DurCall{&terminal, &duration, &time_sum});
+}
+
+size_t ka_state_duration_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                         int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::state_duration_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+}  // extern "C"

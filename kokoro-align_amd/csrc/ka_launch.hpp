@@ -1,8 +1,9 @@
 // ka_launch.hpp — the host-callable launch functions of every device translation unit.
 //
-// The library is built from ten translation units so that the device code compiles in parallel (a single unit took three
-// minutes): ka_engine.hip is host code only and reaches the kernels through these functions; each kernel family lives in
-// the .hip file named below and nowhere else.  All functions only enqueue; errors surface through hipGetLastError().
+// The library is built from thirteen translation units so that the device code compiles in parallel (a single unit took three
+// minutes): ka_engine.hip, ka_engine_fb.hip and ka_entry_misc.hip are host code only and reach the kernels through these
+// functions; each kernel family lives in the .hip file named below and nowhere else.  All functions only enqueue; errors
+// surface through hipGetLastError().
 #pragma once
 #include "ka_types.hpp"
 

@@ -321,7 +321,7 @@ struct LaunchPlan {
     std::vector<Carve> cv;         // by the caller's index
 
     int32_t n_ring() const { return n_tiled + n_fast; }   // lattices whose checkpointed results backtrace_rc walks / the exact kernels may redo
-    size_t pinned_bytes() const { return align_up((size_t)n * sizeof(Lattice)) + align_up((size_t)n * 16) + align_up(n_tasks * sizeof(TileTask)); }
+    size_t pinned_bytes() const { return align_up((size_t)n * sizeof(Lattice)) + align_up((size_t)n * sizeof(LatticeMeta)) + align_up(n_tasks * sizeof(TileTask)); }
 };
 
 // Step 1.  Returns the caller's index of the first lattice with an unsupported shape, or -1.

@@ -65,7 +65,15 @@ struct Lattice {
     int32_t pad_;
 };
 
-// meta[4*idx + {0,1,2,3}] = status, end position, flags (bit0: a transcript label is 0), total score bits
+// The status record of one lattice, 16 bytes.  The host reads its copy of the records through this struct; device code
+// addresses the same words as meta[4*idx + {0,1,2,3}] (meta_of).
+struct LatticeMeta {
+    int32_t status;     // kStatus* (the public header's KA_OK / KA_ERR_*)
+    int32_t end;        // end position of the best path
+    int32_t flags;      // kFlag* (bit0: a transcript label is 0)
+    float score;        // total score
+};
+static_assert(sizeof(LatticeMeta) == 16, "four 32-bit words per lattice, as the kernels index them");
 __device__ __forceinline__ int32_t *meta_of(int32_t *meta, int idx) { return meta + 4 * (size_t)idx; }
 
 // ---- tiled forms (ka_tiled.hpp, ka_tiled256.hpp, ka_tiled128.hpp) ----
