@@ -226,6 +226,37 @@ int ka_ctc_state_durations_batch_f32(ka_engine *e, int32_t n, const float *const
 size_t ka_state_duration_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size,
                                          int32_t max_move, int32_t mem);
 
+/*
+ * Alignments sampled from the band posterior, and the lattice log-likelihood of a terminal: forward
+ * filter, backward sample on the lattice of ka_ctc_label_posteriors (same band [lo_t, hi_t), moves j in [0, max_move), label-0
+ * veto, terminal s*, statuses and Z).  With u_t(s) the forward value and lab' the blank-expanded labels, sample k is the path
+ *   s_{T-1} = s*;  for t = T-1 ... 1, p = s_t:
+ *     x_j = u_{t-1}(p - j) if p - j is in [lo_{t-1}, hi_{t-1}) and not (j even, j >= 2, lab'[p] == 0), else -inf
+ *     w_j = 2^(x_j - max_j x_j);  tot = w_0 + ... + w_{M-1} (ascending j, float64);  r = U(k, t-1) tot
+ *     s_{t-1} = p - j*, j* the smallest j with w_0 + ... + w_j > r (if rounding leaves none: the largest j with w_j > 0)
+ *   U(k, t) = (mix(seed, k T + t) >> 11) 2^-53, mix the 64-bit generator of ka_hash_logprobs_f32
+ * so a path is drawn with its share of Z, and sample k has the same bits whatever n_samples is and whether its lattice is sent
+ * alone or in a batch.  Arguments as ka_ctc_label_posteriors[_batch]_f32, with in place of occupancy
+ *   n_samples       in [1, 64]
+ *   seed            the lattice's own 64-bit seed (more than 64 samples: further calls with other seeds)
+ *   paths           [n_samples rows of T] int32 output (where `mem` says): row k is sample k's position at every frame, row
+ *                   pitch ld_paths >= T elements (columns [T, ld_paths) untouched)
+ * Per lattice: statuses and log-likelihood as ka_ctc_label_posteriors (the same bits), with -1 over [0, T) of every row of a
+ * failed lattice.  n_samples outside [1, 64] or ld_paths < T fail the call with KA_ERR_BAD_ARGS before anything is launched.
+ */
+int ka_ctc_sample_paths_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                            int32_t beam_size, int32_t max_move, int64_t terminal, int32_t n_samples, uint64_t seed, int32_t *paths,
+                            int64_t ld_paths, double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_sample_paths_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                  const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                  int32_t max_move, const int64_t *terminal, const int32_t *n_samples, const uint64_t *seed,
+                                  int32_t *const *paths, const int64_t *ld_paths, double *log_likelihood, int32_t *status, int32_t mem,
+                                  void *stream);
+/* device-workspace bytes such a call carves (0 for unsupported arguments); bounded by the lattices resident at once (and, for
+ * KA_MEM_HOST, the staged inputs and outputs of every lattice) */
+size_t ka_sample_paths_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int32_t *n_samples, int32_t V,
+                                       int32_t beam_size, int32_t max_move, int32_t mem);
+
 /* Kernel form of the fast path.
  *   KA_MODE_WAVE        one wavefront per lattice, checkpointed (throughput; fills the chip from ~4096
  *                       lattices): the forward kernel keeps scores only and stores the score ring every 32

@@ -11,7 +11,8 @@ occupancy of every frame (ctc_label_posteriors[_batch|_device], segment_agreemen
 log-likelihood (lattice_log_likelihood) and the state posteriors at chosen frames behind the confidence of align()'s text
 boundaries (ctc_state_posteriors[_batch|_device], boundary_frames, segment_boundary_confidence), and the expected duration of
 every state with the expected frame of every boundary (ctc_state_durations[_batch|_device], phoneme_durations,
-expected_crossing_frames, segment_boundary_shift).
+expected_crossing_frames, segment_boundary_shift), and whole alignments sampled from the posterior over the band's paths with
+the spread of every boundary (ctc_sample_paths[_batch|_device], sampled_crossing_frames, segment_boundary_spread).
 
 The DP and backtrace run in the HIP C-ABI library (include/kokoro_align_amd.h); there is no
 CPU fallback — importing works without a GPU, computing does not.
@@ -34,6 +35,9 @@ from .posteriors import (  # noqa: F401
     ctc_path_posteriors,
     ctc_path_posteriors_batch,
     ctc_path_posteriors_device,
+    ctc_sample_paths,
+    ctc_sample_paths_batch,
+    ctc_sample_paths_device,
     ctc_state_durations,
     ctc_state_durations_batch,
     ctc_state_durations_device,
@@ -43,9 +47,11 @@ from .posteriors import (  # noqa: F401
     expected_crossing_frames,
     lattice_log_likelihood,
     phoneme_durations,
+    sampled_crossing_frames,
     segment_agreement,
     segment_boundary_confidence,
     segment_boundary_shift,
+    segment_boundary_spread,
     segment_confidence,
 )
 from ._lib import KAError, build_library, library_path, load_library  # noqa: F401

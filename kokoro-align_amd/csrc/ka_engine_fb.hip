@@ -1,6 +1,7 @@
 // ka_engine_fb.hip — the forward-backward calls of the C ABI: best-path posteriors (ka_posterior.hpp), label occupancy
-// (ka_occupancy.hpp), state posteriors at chosen frames (ka_state_posterior.hpp) and expected state durations (ka_duration.hpp).
-// Host code only.  They use the engine's workspace and pinned buffer, with their own kernels and workspace layout, whatever
+// (ka_occupancy.hpp), state posteriors at chosen frames (ka_state_posterior.hpp), expected state durations (ka_duration.hpp)
+// and alignments sampled from the band posterior (ka_sample.hpp).  Host code only.
+// They use the engine's workspace and pinned buffer, with their own kernels and workspace layout, whatever
 // the engine's mode, and run to the end inside the call: no batch stays in flight.
 #include "ka_engine.hpp"
 
@@ -14,7 +15,8 @@ using ka::plan::align_up;
 
 // ---- best-path posteriors (ka_posterior.hpp), label occupancy (ka_occupancy.hpp), state posteriors at chosen frames
 // (ka_state_posterior.hpp) and expected state durations (ka_duration.hpp): their own kernels and workspace layout, whatever the
-// engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall, DurCall) brings what differs: its own arrays and their
+// engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall, DurCall, SampleCall) brings what differs: its
+// own arrays and their
 // checks, its planner and launch, the descriptor fields beyond FbLattice, its own staging (upload: host buffers only;
 // stage: every memory mode), and what two statuses mean.
 struct FbArgs {
@@ -71,7 +73,8 @@ struct PostCall {
     }
 };
 
-// the FbCkLattice fields that the slot calls (OccCall, StateCall, DurCall) fill alike: the lattice's slot, its terminal, the column stride
+// the FbCkLattice fields that the slot calls (OccCall, StateCall, DurCall, SampleCall) fill alike: the lattice's slot, its
+// terminal, the column stride
 void fill_slot(ka::FbCkLattice &d, const ka::plan::SlotCarve &c, int64_t terminal, char *ws)
 {
     d.ck = reinterpret_cast<double *>(ws + c.slot + c.parts.ck);
@@ -217,6 +220,54 @@ struct DurCall {
         const size_t bytes = (size_t)(2 * a.S[i] + 1) * sizeof(double);
         KA_HIP(hipMemcpyAsync(duration[i], ws + c.dur, bytes, hipMemcpyDeviceToHost, a.stream));
         if (moment(i)) KA_HIP(hipMemcpyAsync(time_sum[i], ws + c.tsum, bytes, hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
+struct SampleCall {
+    using Desc = ka::SampleLattice;
+    using Carve = ka::plan::SampleCarve;
+    static constexpr const char *kName = "sample paths";
+    static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score reaches the terminal";
+    const int64_t *terminal;
+    const int32_t *n_samples;
+    const uint64_t *seed;
+    int32_t *const *paths;
+    const int64_t *ld_paths;
+
+    bool arrays() const { return terminal && n_samples && seed && paths && ld_paths; }
+    const char *bad_lattice(const FbArgs &a, int32_t i) const
+    {
+        if (n_samples[i] < 1 || n_samples[i] > ka::kMaxSamples) return ": n_samples outside [1, 64]";
+        return ld_paths[i] < a.T[i] ? ": ld_paths < T" : nullptr;
+    }
+    bool buffers(int32_t i) const { return paths[i] != nullptr; }
+    size_t plan(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host, Carve *cv,
+                size_t *off_res) const
+    {
+        return ka::plan::sample_paths_workspace(n, T, S, n_samples, V, beam, max_move, host, cv, off_res);
+    }
+    static constexpr auto launch = ka::launch_sample_paths;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (a.mem == KA_MEM_HOST) {
+            d.paths = reinterpret_cast<int32_t *>(ws + c.paths);
+            d.ld_out = a.T[i];
+        } else {
+            d.paths = paths[i];
+            d.ld_out = ld_paths[i];
+        }
+        fill_slot(d, c, terminal[i], ws);
+        d.seed = seed[i];
+        d.n_samples = n_samples[i];
+    }
+    int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int stage(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        KA_HIP(hipMemcpy2DAsync(paths[i], (size_t)ld_paths[i] * 4, ws + c.paths, (size_t)a.T[i] * 4, (size_t)a.T[i] * 4, (size_t)n_samples[i],
+                                hipMemcpyDeviceToHost, a.stream));
         return KA_OK;
     }
 };
@@ -414,6 +465,32 @@ size_t ka_state_duration_workspace_bytes(int32_t n, const int64_t *T, const int6
 {
     if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
     return ka::plan::state_duration_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+int ka_ctc_sample_paths_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                  const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                  const int64_t *terminal, const int32_t *n_samples, const uint64_t *seed, int32_t *const *paths,
+                                  const int64_t *ld_paths, double *log_likelihood, int32_t *status, int32_t mem, void *stream)
+{
+    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+                   SampleCall{terminal, n_samples, seed, paths, ld_paths});
+}
+
+int ka_ctc_sample_paths_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                            int32_t beam_size, int32_t max_move, int64_t terminal, int32_t n_samples, uint64_t seed, int32_t *paths,
+                            int64_t ld_paths, double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+                   SampleCall{&terminal, &n_samples, &seed, &paths, &ld_paths});
+}
+
+size_t ka_sample_paths_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int32_t *n_samples, int32_t V, int32_t beam_size,
+                                       int32_t max_move, int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S || !n_samples)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    for (int32_t i = 0; i < n; ++i)
+        if (n_samples[i] < 1 || n_samples[i] > ka::kMaxSamples) return 0;
+    return ka::plan::sample_paths_workspace(n, T, S, n_samples, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
 }  // extern "C"

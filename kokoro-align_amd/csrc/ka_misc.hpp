@@ -33,13 +33,7 @@ __global__ __launch_bounds__(256) void log_softmax_kernel(const float *__restric
 // ---------------------------------------------------------------------------------------
 // hash generator of synthetic inputs (definition: include/kokoro_align_amd.h)
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t mix64(uint64_t seed, uint64_t idx)
-{
-    uint64_t z = (seed * 0x9E3779B97F4A7C15ull + idx + 1ull) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// (mix64 itself: ka_types.hpp, shared with the path sampler)
 // blockIdx.y = lattice: lattice i lives at base + i*stride elements and uses seed + i
 __global__ __launch_bounds__(256) void hash_logprobs_kernel(float *lp0, int64_t T, int V, int64_t ld, uint64_t seed0,
                                                             int64_t lattice_stride)

@@ -785,3 +785,32 @@ inline size_t state_duration_workspace(int32_t n, const int64_t *T, const int64_
 
 }  // namespace plan
 }  // namespace ka
+
+namespace ka {
+namespace plan {
+
+// ---- ka_ctc_sample_paths_batch_f32 (ka_sample.hpp): workspace layout ----
+// label_posterior_workspace's layout and slots (the slot's V-wide global bins and two of the generic form's four columns go
+// unused), with SampleLattice descriptors; for host buffers the staged paths (n_samples rows of T int32) lie beside the staged
+// log-probs and labels.  The slot is the shared one (occ_parts) on purpose: the bins exist only for the generic form above
+// kOccLdsBins labels and the two spare columns are 2 L doubles of a generic slot, against ceil(T / 32) + 32 columns of
+// checkpoints and slab, so every slot call publishes one byte count per shape.  n_samples is the caller's to check (the
+// engine rejects values outside [1, kMaxSamples] before it plans); here it is clamped to that range.
+struct SampleCarve : SlotCarve {
+    size_t paths;   // host buffers only
+};
+inline size_t sample_paths_workspace(int32_t n, const int64_t *T, const int64_t *S, const int32_t *n_samples, int32_t V, int32_t beam,
+                                     int32_t max_move, bool host_buffers, SampleCarve *cv, size_t *off_res)
+{
+    return slot_workspace(n, sizeof(SampleLattice), T, S, V, beam, max_move, cv, off_res, [&](int32_t i, const Shape &sh, SampleCarve &c, size_t &off) {
+        if (host_buffers) {
+            carve_staged(off, sh, V, c);
+            c.paths = off;
+            off += align_up((size_t)std::min(std::max(n_samples[i], 1), kMaxSamples) * (size_t)sh.T * 4);
+        }
+        return true;
+    });
+}
+
+}  // namespace plan
+}  // namespace ka

@@ -18,6 +18,15 @@ typedef KA_GLOBAL uint32_t *gu32_t;
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef KA_GLOBAL const v4i_t *gci4_t;
 
+// the 64-bit hash generator of the synthetic inputs and of the path sampler's uniforms (definition: include/kokoro_align_amd.h)
+__device__ __forceinline__ uint64_t mix64(uint64_t seed, uint64_t idx)
+{
+    uint64_t z = (seed * 0x9E3779B97F4A7C15ull + idx + 1ull) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 constexpr int kStatusOk = 0;
 constexpr int kStatusEmptyBeam = -1;
 constexpr int kStatusBadLabel = -5;
@@ -196,9 +205,17 @@ struct DurLattice : FbCkLattice {
     double *dur;                  // [L] output: D(s) = sum over t of gamma_t(s)
     double *tsum;                 // [L] output, or NULL: B(s) = sum over t of t gamma_t(s)
 };
+// ---- alignments sampled from the band posterior (ka_sample.hpp): the occupancy's slots and form split ----
+constexpr int kMaxSamples = 64;   // samples per lattice and call: one per lane of the fast form
+struct SampleLattice : FbCkLattice {
+    int32_t *paths;               // [n_samples, ld_out] output: row k is sample k's position at every frame, T columns written
+    uint64_t seed;                // the lattice's own seed: U(k, t) = (mix64(seed, k T + t) >> 11) 2^-53
+    int32_t n_samples;            // in [1, kMaxSamples]
+    int32_t pad_;
+};
 // the workspace planners (ka_plan.hpp) carve n descriptors: their sizes are part of the published workspace byte counts
 static_assert(sizeof(PostLattice) == 88 && sizeof(FbCkLattice) == 104 && sizeof(OccLattice) == 120 && sizeof(StateLattice) == 136 &&
-                  sizeof(DurLattice) == 120,
+                  sizeof(DurLattice) == 120 && sizeof(SampleLattice) == 128,
               "descriptor sizes");
 
 }  // namespace ka

@@ -1,7 +1,7 @@
 """Forward-backward over the band of ``ctc_best_path``: path posteriors, label occupancy, state posteriors at chosen frames,
-expected state durations.
+expected state durations, alignments sampled from the posterior.
 
-The four calls take the same lattices (log-probs, labels, beam_size, max_move) in host or device memory and answer with one
+The five calls take the same lattices (log-probs, labels, beam_size, max_move) in host or device memory and answer with one
 log-likelihood and one status per lattice.  ``_Lattices`` is that common input, normalised once and aware of its memory mode;
 ``_run_lattices`` is the one C call and the one status handling.  What is a call's own (its extra inputs, its outputs, its
 argument tables) is in its private function; ``X_batch`` and ``X_device`` only choose the memory mode.
@@ -76,7 +76,7 @@ def _device_lattices(log_probs, labels, others, what):
             lp = lp.contiguous()
         lps.append(lp)
     dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
-    dtypes = {np.float32: torch.float32, np.float64: torch.float64, np.int64: torch.int64}
+    dtypes = {np.float32: torch.float32, np.float64: torch.float64, np.int64: torch.int64, np.int32: torch.int32}
 
     def int32(x):
         x = x if _is_tensor(x) else torch.as_tensor(np.asarray(x).reshape(-1).astype(np.int32))
@@ -89,7 +89,7 @@ def _device_lattices(log_probs, labels, others, what):
 
 
 def _run_lattices(lat, call, beam_size, max_move, own_args, outs, return_status):
-    """The call ``ka_ctc_<call>_batch_f32`` (path_posteriors, label_posteriors, state_posteriors, state_durations): the
+    """The call ``ka_ctc_<call>_batch_f32`` (path_posteriors, label_posteriors, state_posteriors, state_durations, sample_paths): the
     arguments all of them take around ``own_args`` (the call's own tables), then the results (*outs[i], log_likelihood[i]),
     ``outs`` a list of tuples, and the status handling of ``return_status``."""
     name = f"ctc_{call}_{lat.form}"
@@ -114,17 +114,18 @@ def _run_lattices(lat, call, beam_size, max_move, own_args, outs, return_status)
     return results
 
 
-def _outputs(lat, out, shapes, shape_text):
-    """The float32 [rows, columns] outputs of a call: allocated here, or the caller's ``out`` tensors (only the device
-    forms take any) after a check."""
+def _outputs(lat, out, shapes, shape_text, dtype=np.float32):
+    """The [rows, columns] outputs of a call (float32, or ``dtype``): allocated here, or the caller's ``out`` tensors (only the
+    device forms take any) after a check."""
     if out is None:
-        return [lat.empty(s, np.float32) for s in shapes]
+        return [lat.empty(s, dtype) for s in shapes]
     import torch
     if len(out) != lat.n:
         raise ValueError("out must hold one tensor per lattice")
+    name = np.dtype(dtype).name
     for o, s in zip(out, shapes):
-        if o.dtype != torch.float32 or o.dim() != 2 or tuple(o.shape) != s or o.stride(1) != 1 or o.device != lat.dev:
-            raise ValueError(f"out tensors must be float32 {shape_text} on the input's device with unit column stride")
+        if o.dtype != getattr(torch, name) or o.dim() != 2 or tuple(o.shape) != s or o.stride(1) != 1 or o.device != lat.dev:
+            raise ValueError(f"out tensors must be {name} {shape_text} on the input's device with unit column stride")
     return out
 
 
@@ -568,3 +569,125 @@ def segment_boundary_shift(duration, best_path, seg_ends, n_phonemes):
     start = np.array([shift[a] if a < T else 0.0 for _, a, _ in segs], dtype=np.float64)
     end = np.array([shift[b] if b < T else 0.0 for _, _, b in segs], dtype=np.float64)   # (b is clipped to T: b < T is seg_ends[i] < T)
     return start, end
+
+
+# ------------------------------------------------------------------------------------------
+# alignments sampled from the band posterior, and the spread of every text boundary
+# ------------------------------------------------------------------------------------------
+MAX_SAMPLES = 64
+
+
+def ctc_sample_paths(log_probs, labels, terminal, n_samples=64, seed=0, beam_size=1000, max_move=4):
+    """Whole alignments drawn from the posterior over the band's paths: (paths int32 [n_samples, T], log_likelihood float).
+
+    Row k is one path of the band of ``ctc_best_path`` that ends at state ``terminal`` (an int, or a best path whose last
+    value is used), drawn with probability proportional to its score - its share of the lattice likelihood - by forward
+    filtering and backward sampling; paths[k, t] is its position in the blank-expanded labels at frame t.  Any statistic of a
+    path (a boundary's spread, a segment's duration, whether two cuts move together) is a sample statistic of the rows.
+    Sample k depends on ``seed`` and k alone: it has the same bits whatever ``n_samples`` is, and whether the lattice is sent
+    alone or in a batch.  One call draws at most 64 samples; more are the caller's loop over seeds (each seed gives 64 fresh,
+    independent paths).  NumPy in -> NumPy out; ROCm torch tensors go to ``ctc_sample_paths_device``.  Raises as
+    ``ctc_label_posteriors``, and ValueError for ``n_samples`` outside [1, 64].
+    """
+    call = ctc_sample_paths_device if _is_tensor(log_probs) else ctc_sample_paths_batch
+    (result,) = call([log_probs], [labels], [terminal], n_samples, seed, beam_size, max_move)
+    return result
+
+
+def _per_lattice(x, n, what):
+    """An int for every lattice, or one per lattice."""
+    xs = [int(x)] * n if np.ndim(x) == 0 else [int(v) for v in x]
+    if len(xs) != n:
+        raise ValueError(f"{what} must be an int or hold one per lattice")
+    return xs
+
+
+def _sample_paths(lat, terminals, n_samples, seed, beam_size, max_move, out, return_status):
+    if lat is None:
+        return ([], []) if return_status else []
+    Ks = _per_lattice(n_samples, lat.n, "n_samples")
+    seeds = [v & 0xFFFFFFFFFFFFFFFF for v in _per_lattice(seed, lat.n, "seed")]
+    if any(K < 1 or K > MAX_SAMPLES for K in Ks):
+        raise ValueError(f"n_samples must lie in [1, {MAX_SAMPLES}]: draw more with further seeds")
+    paths = _outputs(lat, out, [(K, T) for K, T in zip(Ks, lat.T)], "[n_samples_i, T_i]", np.int32)
+    p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
+    a_K = np.asarray(Ks, np.int32)
+    a_seed = np.asarray(seeds, np.uint64)
+    p_paths, _k2 = _ptr_array([lat.ptr(x) for x in paths])
+    p_ld, _k3 = _i64_array([max(lat.ld(x), T) for x, T in zip(paths, lat.T)])   # (a tensor with one row may report any stride)
+    return _run_lattices(lat, "sample_paths", beam_size, max_move, (p_term, a_K.ctypes.data, a_seed.ctypes.data, p_paths, p_ld),
+                         list(zip(paths)), return_status)
+
+
+def ctc_sample_paths_batch(log_probs_list, labels_list, terminals, n_samples=64, seed=0, beam_size=1000, max_move=4, device=None,
+                           return_status=False):
+    """Sampled paths of many lattices in ONE launch; host NumPy buffers in and out.  ``n_samples`` and ``seed``: an int for
+    every lattice, or one per lattice.
+
+    Returns a list of (paths [n_samples_i, T_i], log_likelihood); with ``return_status`` also the per-lattice status list, in
+    which case failures do not raise (their paths are -1, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    """
+    lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
+    return _sample_paths(lat, terminals, n_samples, seed, beam_size, max_move, None, return_status)
+
+
+def ctc_sample_paths_device(log_probs, labels, terminals, n_samples=64, seed=0, beam_size=1000, max_move=4, out=None, return_status=False):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]) and terminals (ints
+    or best paths), list of (paths int32 tensor [n_samples_i, T_i] on the device, log_likelihood float) out.  ``n_samples``
+    and ``seed``: an int for every lattice, or one per lattice.  ``out``: optional list of int32 [n_samples_i, T_i] tensors
+    with unit column stride to write into (views into wider tensors keep their other columns).  One launch on torch's current
+    stream."""
+    lat = _device_lattices(log_probs, labels, terminals, "terminals")
+    return _sample_paths(lat, terminals, n_samples, seed, beam_size, max_move, out, return_status)
+
+
+def _host_paths(paths):
+    p = np.asarray(paths.detach().cpu() if _is_tensor(paths) else paths, dtype=np.int64)
+    if p.ndim != 2:
+        raise ValueError("paths must be [n_samples, T]")
+    return p
+
+
+def sampled_crossing_frames(paths, cuts):
+    """tau_c of every sampled path for every cut position c in ``cuts``: the first frame whose state is >= c, and T if there
+    is none - the tau_c of ``expected_crossing_frames``, whose value is the mean of a column here.  int64 [K, len(cuts)]
+    (host)."""
+    p = _host_paths(paths)
+    c = np.asarray(cuts.detach().cpu() if _is_tensor(cuts) else cuts, dtype=np.int64).reshape(-1)
+    reached = np.maximum.accumulate(p, axis=1) if p.shape[1] else p      # (a path never moves down: state_t < c exactly for t < tau_c)
+    return np.sum(reached[:, :, None] < c[None, None, :], axis=1, dtype=np.int64)
+
+
+def segment_boundary_spread(paths, best_path, seg_ends, n_phonemes, q=(0.05, 0.5, 0.95)):
+    """How widely the lattice spreads each text boundary of ``align()``, from sampled paths (host only): the sample quantiles
+    and the standard deviation of tau_c, the number the closed form of ``segment_boundary_shift`` cannot give.
+
+    The cuts are those of ``segment_boundary_shift``: for every boundary frame b of ``boundary_frames(seg_ends, T)`` the text
+    index is i = min(best_path[b] // 2, n_phonemes) and the cut c = 2 i; tau_c of a sample is ``sampled_crossing_frames``.
+    Returns (start_quantiles [n_seg, len(q)], start_std [n_seg], end_quantiles [n_seg, len(q)], end_std [n_seg]), float64 per
+    segment that ``align()`` writes a line for (frames [a, b), a = seg_ends[i-1], 0 for the first, b = seg_ends[i]): the
+    boundary read at a and the one read at b.  Where b >= T ``align()`` runs the text to its end whatever the path does: the
+    quantiles are T and the deviation 0."""
+    p = _host_paths(paths)
+    path = np.asarray(best_path.detach().cpu() if _is_tensor(best_path) else best_path, dtype=np.int64).reshape(-1)
+    T, n_ph = len(path), int(n_phonemes)
+    if p.shape[1] != T:
+        raise ValueError("segment_boundary_spread: paths and best_path must have one position per frame")
+    qs = np.asarray(q, dtype=np.float64).reshape(-1)
+    frames = boundary_frames(seg_ends, T)
+    cuts = np.array([2 * min(int(path[b]) // 2, n_ph) for b in frames], dtype=np.int64)
+    tau = sampled_crossing_frames(p, cuts).astype(np.float64)          # [K, boundaries]
+    col = {int(b): k for k, b in enumerate(frames)}
+    at_end = (np.full(len(qs), float(T)), 0.0)
+
+    def spread(b):
+        if b >= T:
+            return at_end
+        x = tau[:, col[int(b)]]
+        return np.quantile(x, qs), float(np.std(x))
+
+    segs = _segments(np.asarray(seg_ends, dtype=np.int64), T)
+    start = [spread(a) for _, a, _ in segs]
+    end = [spread(b) for _, _, b in segs]
+    stack = lambda rows: np.array([r[0] for r in rows], dtype=np.float64).reshape(len(rows), len(qs))
+    return (stack(start), np.array([r[1] for r in start], dtype=np.float64), stack(end), np.array([r[1] for r in end], dtype=np.float64))

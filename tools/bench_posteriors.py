@@ -4,12 +4,16 @@ and of ka_ctc_label_posteriors_batch_f32 (label occupancy, ka_occupancy.hpp, sec
 terminal taken from the best path (cases occ_single, occ_b1024, occ_b8192); and of ka_ctc_state_posteriors_batch_f32 (state
 posteriors at chosen frames, ka_state_posterior.hpp, section 4.19) with 200 query frames spread over every lattice (cases
 state_single, state_b1024); and of ka_ctc_state_durations_batch_f32 (expected state durations, ka_duration.hpp, section 4.22)
-on the occupancy's shapes and terminals (cases dur_single, dur_b1024).
+on the occupancy's shapes and terminals (cases dur_single, dur_b1024); and of ka_ctc_sample_paths_batch_f32 (64 alignments
+sampled from the band posterior per lattice, ka_sample.hpp, section 4.24) on the same shapes and terminals (cases smp_single,
+smp_b1024).
 
     python tools/bench_posteriors.py [--cases single,b1024,b8192,corpus] [--reps 3] [--out profiles/posteriors.jsonl]
     python tools/bench_posteriors.py --cases state_single,state_b1024 --out profiles/state_posteriors_bench.jsonl
     python tools/bench_posteriors.py --cases occ_single,dur_single,occ_b1024,dur_b1024,occ_single,dur_single,occ_b1024,dur_b1024 \
         --out profiles/duration_bench.jsonl
+    python tools/bench_posteriors.py --cases occ_single,smp_single,occ_b1024,smp_b1024,occ_single,smp_single,occ_b1024,smp_b1024 \
+        --out profiles/sample_bench.jsonl
 
 Device-resident inputs (hash-generated); best paths from the library's own best-path call.  The 8192 batch points its
 lattices at the 1024 batch's log-probs, labels and paths eight times over (distinct outputs): 105 GB of log-probs would
@@ -48,7 +52,7 @@ def best_paths(lps, labs):
 
 
 def time_batch(call_name, ws_name, lps, labs, own_args, reps, ws_own=()):
-    """ms per call of ka_ctc_<call_name>_batch_f32 on device buffers: the arguments the four calls share around
+    """ms per call of ka_ctc_<call_name>_batch_f32 on device buffers: the arguments the five calls share around
     ``own_args`` (the caller keeps what they point to alive), the workspace reserved first, one warm-up call."""
     name = f"ka_ctc_{call_name}_batch_f32"
     n, V = len(lps), int(lps[0].shape[1])
@@ -114,6 +118,17 @@ def time_durations(lps, labs, paths, reps):
     return time_batch("state_durations", "ka_state_duration_workspace_bytes", lps, labs, (term[0], k[0][0], k[1][0]), reps)
 
 
+def time_samples(lps, labs, paths, reps, K=64):
+    outs = [torch.empty((K, int(x.shape[0])), dtype=torch.int32, device="cuda") for x in lps]
+    p_out = _ptr_array([x.data_ptr() for x in outs])
+    ldp = _i64_array([x.stride(0) for x in outs])
+    term = _i64_array(torch.stack([p[-1] for p in paths]).cpu().tolist())
+    Ks = np.full(len(lps), K, np.int32)
+    seeds = np.arange(len(lps), dtype=np.uint64) + np.uint64(1)
+    return time_batch("sample_paths", "ka_sample_paths_workspace_bytes", lps, labs, (term[0], Ks.ctypes.data, seeds.ctypes.data, p_out[0], ldp[0]),
+                      reps, ws_own=(Ks.ctypes.data,))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="single,b1024,b8192,corpus")
@@ -125,7 +140,7 @@ def main():
     cases = a.cases.split(",")
     b1024 = None
     for case in cases:
-        kind = case.split("_")[0] if case.startswith(("occ_", "state_", "dur_")) else "path"
+        kind = case.split("_")[0] if case.startswith(("occ_", "state_", "dur_", "smp_")) else "path"
         case_in = case[len(kind) + 1:] if kind != "path" else case
         if case_in == "single":
             lps, labs = cfg2(1)
@@ -146,7 +161,7 @@ def main():
             raise SystemExit(f"unknown case {case}")
         if case_in in ("single", "corpus"):
             paths = best_paths(lps, labs)
-        ms, st, ll = {"path": time_posteriors, "occ": time_occupancy, "state": time_states, "dur": time_durations}[kind](lps, labs, paths, a.reps)
+        ms, st, ll = {"path": time_posteriors, "occ": time_occupancy, "state": time_states, "dur": time_durations, "smp": time_samples}[kind](lps, labs, paths, a.reps)
         frames = sum(int(x.shape[0]) for x in lps)
         line = dict(case=case, lattices=len(lps), frames=frames, ms_min=round(min(ms), 3), ms_median=round(float(np.median(ms)), 3),
                     frames_per_s=frames / (min(ms) / 1e3), status_ok=int((st == 0).sum()), reps=a.reps)
