@@ -4,14 +4,14 @@
 //   D(s) = sum over t of gamma_t(s)       expected number of frames spent in s
 //   B(s) = sum over t of t gamma_t(s)     (B / D: the expected centre frame of s)
 //
-// Same lattice, band, moves, veto, statuses and form split as ka_occupancy.hpp (DESIGN.md sections 4.18 and 4.22): the two
-// drivers of ka_fb_ck.hpp with DurOut, which recomputes every block as the occupancy does and adds every cell's gamma - the
+// Same lattice, band, moves, veto, statuses and form split as ka_occupancy.hpp (DESIGN.md sections 4.18 and 4.22): the
+// driver of ka_fb_ck.hpp with DurOut, which recomputes every block as the occupancy does and adds every cell's gamma - the
 // float the state posteriors write (fb_gamma) - to two float64 accumulators of its position.  The backward pass visits the
 // frames T-1 ... 0, so a position receives one add per frame whose band holds it, in descending frame order: the sums are those
 // of a sequential float64 loop over the rows of ka_ctc_state_posteriors, bit for bit.
 //
 // Where the accumulators live.  Fast form: lane l owns lo + l + 64 k, so a position's owner changes whenever lo moves; the
-// accumulators are two more LDS rings (position p at slot p & 1023, as the columns), which one wavefront reads and writes in
+// accumulators are two more LDS rings (position p at the form's column slot, p & 1023), which one wavefront reads and writes in
 // program order.  Going back the band slides down: before frame t's cells the positions [hi_t, hi_{t+1}) have left the band
 // for good and are retired - written to the outputs, their slots zeroed - so a live position (the band is at most 1009 wide)
 // never shares a slot with a sum that is still held.  After frame 0, [0, hi_0) is written.  Positions no band holds get 0.
@@ -22,16 +22,17 @@
 
 namespace ka {
 
-// fb_ck_fast / fb_ck_gen's policy (NT threads per lattice: 64 in the fast form, 256 in the generic one)
-template <int NT>
+// fb_ck's policy.  The forms differ in where the accumulators live (above); a position's place in them is the form's column slot.
+template <class Form>
 struct DurOut {
+    static constexpr int NT = Form::NT;
     const DurLattice &d;
     double *accD, *accB;   // fast form: the LDS rings; generic: the outputs (accB NULL without a time_sum)
     int64_t nlo, nhi;      // fast form: the band of frame t + 1 ([L, L) above the last frame)
     __device__ __forceinline__ DurOut(const DurLattice &d_, double *ringD, double *ringB)
-        : d(d_), accD(NT == 64 ? ringD : d_.dur), accB(NT == 64 ? ringB : d_.tsum), nlo(d_.L), nhi(d_.L)
+        : d(d_), accD(Form::kWave ? ringD : d_.dur), accB(Form::kWave ? ringB : d_.tsum), nlo(d_.L), nhi(d_.L)
     {
-        if (NT == 64) {   // (whatever the slot's last lattice left)
+        if (Form::kWave) {   // (whatever the slot's last lattice left)
             for (int s = threadIdx.x; s < 1024; s += NT) {
                 accD[s] = 0.0;
                 accB[s] = 0.0;
@@ -59,7 +60,7 @@ struct DurOut {
     {
         for (int64_t p = hi + threadIdx.x; p < nhi; p += NT) {
             const bool held = p >= nlo;
-            const int s = (int)(p & 1023);
+            const int s = (int)Form::cslot(p);
             d.dur[p] = held ? accD[s] : 0.0;
             if (d.tsum) d.tsum[p] = held ? accB[s] : 0.0;
             if (held) {
@@ -72,7 +73,7 @@ struct DurOut {
     }
     __device__ __forceinline__ auto cells(int64_t t, int64_t lo)
     {
-        if (NT == 64) {
+        if (Form::kWave) {
             const int64_t hi = (d.L - lo < d.beam) ? (int64_t)d.L : lo + d.beam;   // hi_t from lo_t, as post_band forms it
             retire(lo, hi);
         }
@@ -80,46 +81,35 @@ struct DurOut {
         double *aD = accD, *aB = accB;
         return [=](int64_t p, int32_t, auto arg) {
             const double g = (double)fb_gamma(arg());
-            const int64_t s = NT == 64 ? (p & 1023) : p;
+            const int64_t s = Form::cslot(p);
             aD[s] += g;
-            if (NT == 64 || aB) aB[s] += tt * g;
+            if (Form::kWave || aB) aB[s] += tt * g;
         };
     }
     __device__ __forceinline__ void cells_done() {}
     __device__ __forceinline__ void frame_end(int64_t t, int64_t lo, int64_t hi)
     {
-        if (NT != 64 || t != 0) return;
+        if (!Form::kWave || t != 0) return;
         post_wave_sync();   // frame 0's adds, made by the lanes that own the cells, before the lanes that write them out
         for (int64_t p = lo + threadIdx.x; p < hi; p += NT) {
-            d.dur[p] = accD[p & 1023];
-            if (d.tsum) d.tsum[p] = accB[p & 1023];
+            d.dur[p] = accD[Form::cslot(p)];
+            if (d.tsum) d.tsum[p] = accB[Form::cslot(p)];
         }
     }
 };
 
-template <int M>
-__global__ __launch_bounds__(64) void duration_fast_kernel(const DurLattice *__restrict__ lats, int n, PostResult *res)
+template <class Form>
+__global__ __launch_bounds__(Form::NT) void duration_kernel(const DurLattice *__restrict__ lats, int n, PostResult *res)
 {
-    __shared__ double col[4][1024];
-    __shared__ double row[64];
+    __shared__ typename Form::template Shared<4> sh;
     __shared__ double cav[kPostCk];
-    __shared__ double ringD[1024];
-    __shared__ double ringB[1024];
+    __shared__ double ringD[1024];   // (the rings are the fast form's: the generic kernel never names them, and they take none
+    __shared__ double ringB[1024];   //  of its LDS)
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        DurOut<64> out(lats[i], ringD, ringB);
-        fb_ck_fast<M>(lats[i], res, col, row, cav, out);
-        post_wave_sync();
-    }
-}
-
-__global__ __launch_bounds__(256) void duration_generic_kernel(const DurLattice *__restrict__ lats, int n, PostResult *res)
-{
-    __shared__ double red[2][4];
-    __shared__ double cav[kPostCk];
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        DurOut<256> out(lats[i], nullptr, nullptr);
-        fb_ck_gen(lats[i], res, red, cav, out);
-        __syncthreads();
+        Form f(lats[i], sh);
+        DurOut<Form> out(lats[i], ringD, ringB);
+        fb_ck(f, res, cav, out);
+        f.sync();
     }
 }
 

@@ -4,7 +4,7 @@
 // Same lattice, band, moves, veto and numerics as ka_posterior.hpp:
 //   occ[t, v] = sum over s in [lo_t, hi_t) with lab'[s] = v of gamma_t(s),  gamma_t(s) = 2^(alpha_t(s) + beta_t(s) - Z)
 // which is also dZ / d log_probs[t, v].  The checkpointed forward-backward of ka_fb_ck.hpp computes gamma at every band cell;
-// the kernels here are its two drivers with OccOut, which recomputes every block and bins every cell.
+// the kernel here is its driver with OccOut, which recomputes every block and bins every cell.
 // Binning: gamma is formed in double, rounded to float and raised by the hardware exp2 (an output in [0, 1] needs no more),
 // then added as an unsigned 32.32 fixed-point integer, so the row's bits do not depend on the order of the adds: blank cells
 // (even positions) through a register sum and a wave reduction, the other cells through 64-bit LDS atomics (the generic
@@ -33,17 +33,19 @@ __device__ __forceinline__ unsigned long long occ_wave_sum(unsigned long long x)
     return x;
 }
 
-// fb_ck_fast / fb_ck_gen's policy (NT threads per lattice: 64 in the fast form, 256 in the generic one): every block
-// recomputed, gamma binned per label value, a row of occ per frame
-template <int NT>
+// fb_ck's policy: every block recomputed, gamma binned per label value, a row of occ per frame.  The forms differ in how a
+// frame's bins are summed and emptied: one wavefront sums its blank cells in registers and owns bin `lane`, a workgroup goes
+// through atomics and a barrier.
+template <class Form>
 struct OccOut {
+    static constexpr int NT = Form::NT;
     const OccLattice &d;
     unsigned long long *bins;   // fast form: 64 in LDS; generic: V in LDS up to kOccLdsBins, above it the slot's global row
     unsigned long long blank;   // this thread's blank cells of the frame
     __device__ __forceinline__ OccOut(const OccLattice &d_, unsigned long long *lbins)
-        : d(d_), bins(NT == 64 || d_.V <= kOccLdsBins ? lbins : d_.gbin), blank(0)
+        : d(d_), bins(Form::kWave || d_.V <= kOccLdsBins ? lbins : d_.gbin), blank(0)
     {
-        if (NT == 64) bins[threadIdx.x] = 0;
+        if (Form::kWave) bins[threadIdx.x] = 0;
         else for (int64_t v = threadIdx.x; v < d.V; v += NT) atomicExch(&bins[v], 0ull);
     }
     // a lattice without a result: NaN rows, and the status and log-likelihood of fb_fail_result
@@ -67,12 +69,12 @@ struct OccOut {
     }
     __device__ __forceinline__ void cells_done()
     {
-        if (NT == 64) blank = occ_wave_sum(blank);
+        if (Form::kWave) blank = occ_wave_sum(blank);
         else if (blank) atomicAdd(&bins[0], blank);   // (the reduction's barrier closes the frame's atomics)
     }
     __device__ __forceinline__ void frame_end(int64_t t, int64_t, int64_t)
     {
-        if (NT == 64) {
+        if (Form::kWave) {
             const int lane = threadIdx.x;
             post_wave_sync();
             if (lane < d.V) {
@@ -89,29 +91,17 @@ struct OccOut {
     }
 };
 
-template <int M>
-__global__ __launch_bounds__(64) void occupancy_fast_kernel(const OccLattice *__restrict__ lats, int n, PostResult *res)
+template <class Form>
+__global__ __launch_bounds__(Form::NT) void occupancy_kernel(const OccLattice *__restrict__ lats, int n, PostResult *res)
 {
-    __shared__ double col[4][1024];
-    __shared__ double row[64];
+    __shared__ typename Form::template Shared<4> sh;
     __shared__ double cav[kPostCk];
-    __shared__ unsigned long long bins[64];
+    __shared__ unsigned long long bins[Form::kWave ? 64 : kOccLdsBins];
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        OccOut<64> out(lats[i], bins);
-        fb_ck_fast<M>(lats[i], res, col, row, cav, out);
-        post_wave_sync();
-    }
-}
-
-__global__ __launch_bounds__(256) void occupancy_generic_kernel(const OccLattice *__restrict__ lats, int n, PostResult *res)
-{
-    __shared__ double red[2][4];
-    __shared__ double cav[kPostCk];
-    __shared__ unsigned long long lbins[kOccLdsBins];
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        OccOut<256> out(lats[i], lbins);
-        fb_ck_gen(lats[i], res, red, cav, out);
-        __syncthreads();
+        Form f(lats[i], sh);
+        OccOut<Form> out(lats[i], bins);
+        fb_ck(f, res, cav, out);
+        f.sync();
     }
 }
 

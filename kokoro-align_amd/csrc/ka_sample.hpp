@@ -4,7 +4,7 @@
 //
 // Same lattice, band, moves, veto, statuses, Z and form split as ka_occupancy.hpp (DESIGN.md sections 4.18 and 4.24).  The
 // forward pass with its checkpoints and the recompute of a block's alpha into the slab are those of ka_fb_ck.hpp
-// (fb_ck_*_forward, fb_ck_*_recompute: the functions its drivers call); there is no beta pass.  Walking the blocks last to
+// (fb_ck_forward, fb_ck_recompute: the functions its driver calls); there is no beta pass.  Walking the blocks last to
 // first, lane (thread) k owns sample k: its state is one integer in a register, and for t = T-1 ... 1 it draws s_{t-1} given
 // p = s_t from
 //   x_j = u_{t-1}(p - j) for j in [0, max_move) with p - j in band t-1 and the move not vetoed, else -inf;  w_j = 2^(x_j - max x)
@@ -14,9 +14,9 @@
 // alpha of t0 - 1 over the band of t0 - 1.  A path's probability is its share of Z.
 //
 // Ordering.  The slab is global memory; the cells of a row were stored by the lanes that own them in that frame, and the walk
-// reads them from whichever lane holds the sample: across lanes, unlike fb_ck_fast's beta step, which reads a cell from the
-// lane that wrote it.  One wavefront (fast form): every frame of the recompute ends in post_wave_sync, a sequentially
-// consistent fence at wavefront scope over every address space - what the drivers of ka_fb_ck.hpp already place between the
+// reads them from whichever lane holds the sample: across lanes, unlike fb_ck's beta step, which reads a cell from the
+// lane that wrote it.  One wavefront (fast form): every frame of the recompute ends in FbFast's fence(), post_wave_sync: a
+// sequentially consistent fence at wavefront scope over every address space - what the driver of ka_fb_ck.hpp already places between the
 // slab's stores and its loads.  At that scope it costs no instruction: a wavefront issues its vector memory operations in
 // order to the one L1 of its CU, which its own stores write through, so a later load of the wavefront sees them whichever
 // lane issued them; the fence keeps the compiler from moving the accesses.  This leans on the slab's stores being plain ones:
@@ -24,7 +24,7 @@
 // cache action) between the recompute and its first load.  Nothing but bit-equality to the reference tests it.  The next
 // block's recompute overwrites the slab only after the walk has used every value it loaded (the last state of the block goes
 // to the LDS tile before the tile is written out).
-// Generic form: the barrier that ends fb_ck_gen_recompute, and the one behind the tile's write-out.
+// Generic form: the barrier that ends fb_ck_recompute (FbGen's sync()), and the one behind the tile's write-out.
 //
 // Output.  A block's positions are staged in LDS, [64 samples][32 frames] int32 (rows padded by one word: lane k writes row
 // k, and 32-word rows would put all 64 lanes on one bank), and written after the block's walk, each sample's 32 frames as
@@ -58,7 +58,8 @@ __device__ __forceinline__ double sample_uniform(const SampleLattice &d, int k, 
 // mx is finite, the predecessor that attains it has w = 2^0 = 1 and tot >= 1.  A predecessor with w_j = 0 is never chosen:
 // the running sum does not move at it, so it cannot be the first to exceed r, and the fallback takes a j with w_j > 0.  The
 // chosen u_{t-1}(p - j*) is therefore above -inf, and below +inf as every alpha is.  (sample_pick and sample_draw below.)
-// The draw itself from the M weights' exponents x (fast form: M <= 4 registers, each weight exponentiated once).
+// The draw itself from the M weights' exponents x (fast form: M <= 4 registers, each weight exponentiated once).  The two
+// draws are two on purpose, and the walk takes the one of its form.
 template <int M>
 __device__ __forceinline__ int32_t sample_pick(int32_t p, const double (&x)[M], double u01)
 {
@@ -130,99 +131,47 @@ __device__ __forceinline__ void sample_flush(const SampleLattice &d, int64_t t0,
         if (t0 + f < t1) d.paths[(size_t)k * (size_t)d.ld_out + (size_t)(t0 + f)] = tile[k][f];
 }
 
-// ---------------------------------------------------------------------------------------
-// fast form: one wavefront per lattice (band <= kFastMaxBand, V <= 64, M = max_move <= 4), lane k owns sample k
-// ---------------------------------------------------------------------------------------
-template <int M>
-__device__ __forceinline__ void sample_fast(const SampleLattice &d, PostResult *res, double (*col)[1024], double *row,
-                                            int32_t (*tile)[kSampleTilePitch])
-{
-    const int lane = threadIdx.x;
-    const int64_t T = d.T;
-    auto lab_of = [&](int64_t p) { return fb_lab(d, p); };
-    BandWalk bw(d.L, d.beam, T);
-    double Z, Zr;
-    const int status = fb_ck_fast_forward<M>(d, col, row, bw, lab_of, Z, Zr);
-    if (status != kStatusOk) {
-        sample_fail<64>(d, res, status);
-        return;
-    }
-    const bool mine = lane < d.n_samples;
-    int32_t p = d.terminal;   // s_{T-1} = s*
-    for (int64_t k = (T - 1) / kPostCk; k >= 0; --k) {
-        const int64_t t0 = k * kPostCk, t1 = (t0 + kPostCk < T) ? t0 + kPostCk : T;
-        fb_ck_fast_recompute<M>(d, k, t0, t1, bw, col[0], col[1], row, lab_of, [](int64_t, double) {});
-        // (the recompute's last frame ended in post_wave_sync: the slab's stores are ordered before the loads below)
-        const double *ckc = d.ckcol + k * 1024;
-        for (int64_t t = t1 - 1; t >= t0; --t) {   // bw stands at t + 1
-            bw.prev();
-            if (mine) tile[lane][t - t0] = p;
-            if (t == 0) break;
-            bw.prev();
-            int64_t plo, phi;
-            bw.band(plo, phi);   // the band of t - 1
-            bw.next();
-            const double *al = t > t0 ? d.slab + (t - 1 - t0) * 1024 : ckc;
-            if (mine)
-                p = sample_draw_small<M>(p, lab_of(p), plo, phi, sample_uniform(d, lane, t - 1), [&](int64_t u) { return al[u & 1023]; });
-        }
-        post_wave_sync();   // the tile's rows, written by the lanes that own the samples, before the lanes that write them out
-        sample_flush<64>(d, t0, t1, tile);
-        post_wave_sync();
-    }
-    if (lane == 0) {
-        res[d.idx].status = kStatusOk;
-        res[d.idx].log_likelihood = Zr;
-    }
-}
-
-template <int M>
-__global__ __launch_bounds__(64) void sample_fast_kernel(const SampleLattice *__restrict__ lats, int n, PostResult *res)
-{
-    __shared__ double col[2][1024];
-    __shared__ double row[64];
-    __shared__ int32_t tile[kMaxSamples][kSampleTilePitch];
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        sample_fast<M>(lats[i], res, col, row, tile);
-        post_wave_sync();
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// generic form: any band, any V, max_move <= 255; a 256-thread workgroup, thread k < n_samples owns sample k
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void sample_gen(const SampleLattice &d, PostResult *res, double (*red)[4], int32_t (*tile)[kSampleTilePitch])
+// The block walk, once over the form: thread k < n_samples owns sample k (a lane of the one wavefront, or one of the first 64
+// threads of the workgroup).  The form's working columns 0 and 1 serve the forward pass and every recompute.
+template <class Form>
+__device__ __forceinline__ void sample_walk(Form &f, const SampleLattice &d, PostResult *res, int32_t (*tile)[kSampleTilePitch])
 {
     const int tid = threadIdx.x;
-    const int64_t T = d.T, L = d.L, cw = d.cw;
-    int ph = 0;
-    BandWalk bw(L, d.beam, T);
+    const int64_t T = d.T;
+    BandWalk bw(d.L, d.beam, T);
     double Z, Zr;
-    const int status = fb_ck_gen_forward(d, d.col, d.col + L, red, ph, bw, Z, Zr);
+    const int status = fb_ck_forward(f, bw, Z, Zr);   // (ends behind f.sync())
     if (status != kStatusOk) {
-        sample_fail<256>(d, res, status);
+        sample_fail<Form::NT>(d, res, status);
         return;
     }
     const bool mine = tid < d.n_samples;
-    int32_t p = d.terminal;
+    int32_t p = d.terminal;   // s_{T-1} = s*
     for (int64_t k = (T - 1) / kPostCk; k >= 0; --k) {
         const int64_t t0 = k * kPostCk, t1 = (t0 + kPostCk < T) ? t0 + kPostCk : T;
-        fb_ck_gen_recompute(d, k, t0, t1, bw, d.col, d.col + L, red, ph, [](int64_t, double) {});   // (ends behind a barrier)
-        for (int64_t t = t1 - 1; t >= t0; --t) {
+        fb_ck_recompute(f, k, t0, t1, bw, f.col(0), f.col(1), [](int64_t, double) {});
+        // (the recompute ended in the fast form's fence, or behind the generic form's barrier: the slab's stores are ordered
+        //  before the loads below)
+        const double *ckc = d.ckcol + k * f.cw();
+        for (int64_t t = t1 - 1; t >= t0; --t) {   // bw stands at t + 1
             bw.prev();
             if (mine) tile[tid][t - t0] = p;
             if (t == 0) break;
             bw.prev();
             int64_t plo, phi;
-            bw.band(plo, phi);
+            bw.band(plo, phi);   // the band of t - 1, which the slab row and the checkpoint column are both laid out by
             bw.next();
-            const double *al = t > t0 ? d.slab + (t - 1 - t0) * cw : d.ckcol + k * cw;   // both relative to the low end of band t - 1
-            if (mine)
-                p = sample_draw(d.max_move, p, fb_lab(d, p), plo, phi, sample_uniform(d, tid, t - 1), [&](int64_t u) { return al[u - plo]; });
+            const double *al = t > t0 ? d.slab + (t - 1 - t0) * f.cw() : ckc;
+            if (mine) {
+                const double u01 = sample_uniform(d, tid, t - 1);
+                auto alpha_at = [&](int64_t u) { return al[Form::slot(u, plo)]; };
+                if constexpr (Form::kWave) p = sample_draw_small<Form::kMoves>(p, fb_lab(d, p), plo, phi, u01, alpha_at);
+                else p = sample_draw(d.max_move, p, fb_lab(d, p), plo, phi, u01, alpha_at);
+            }
         }
-        __syncthreads();
-        sample_flush<256>(d, t0, t1, tile);
-        __syncthreads();   // the tile, and the slab, before the next block rewrites them
+        f.sync();   // the tile's rows, written by the threads that own the samples, before the threads that write them out
+        sample_flush<Form::NT>(d, t0, t1, tile);
+        f.sync();   // the tile, and the slab, before the next block rewrites them
     }
     if (tid == 0) {
         res[d.idx].status = kStatusOk;
@@ -230,13 +179,15 @@ __device__ __forceinline__ void sample_gen(const SampleLattice &d, PostResult *r
     }
 }
 
-__global__ __launch_bounds__(256) void sample_generic_kernel(const SampleLattice *__restrict__ lats, int n, PostResult *res)
+template <class Form>
+__global__ __launch_bounds__(Form::NT) void sample_kernel(const SampleLattice *__restrict__ lats, int n, PostResult *res)
 {
-    __shared__ double red[2][4];
+    __shared__ typename Form::template Shared<2> sh;
     __shared__ int32_t tile[kMaxSamples][kSampleTilePitch];
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        sample_gen(lats[i], res, red, tile);
-        __syncthreads();
+        Form f(lats[i], sh);
+        sample_walk(f, lats[i], res, tile);
+        f.sync();
     }
 }
 

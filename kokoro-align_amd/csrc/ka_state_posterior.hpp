@@ -2,8 +2,8 @@
 // band position, over the band's paths that end at a caller-given terminal s*, and Z = alpha_{T-1}(s*).  Included by
 // ka_state_posterior.hip only.
 //
-// Same lattice, band, moves, veto, statuses and form split as ka_occupancy.hpp (DESIGN.md sections 4.18 and 4.19): the two
-// drivers of ka_fb_ck.hpp with StOut, which differs from the occupancy's policy in two ways:
+// Same lattice, band, moves, veto, statuses and form split as ka_occupancy.hpp (DESIGN.md sections 4.18 and 4.19): the
+// driver of ka_fb_ck.hpp with StOut, which differs from the occupancy's policy in two ways:
 //   - the backward pass recomputes alpha only for the 32-frame blocks that hold a query frame; beta is still stepped
 //     through every frame (it carries from block to block), so a call costs the two passes of the path posterior plus one
 //     recomputed block per query block;
@@ -20,9 +20,10 @@ namespace ka {
 // the query frame at index kq, or -1 below the first
 __device__ __forceinline__ int64_t st_frame(const StateLattice &d, int64_t kq) { return kq >= 0 ? d.frames[kq] : -1; }
 
-// fb_ck_fast / fb_ck_gen's policy (NT threads per lattice: 64 in the fast form, 256 in the generic one)
-template <int NT>
+// fb_ck's policy; the same in both forms but for the threads a row's tail is zeroed with
+template <class Form>
 struct StOut {
+    static constexpr int NT = Form::NT;
     const StateLattice &d;
     int64_t kq, fq;   // the next query frame down: its index and frame
     __device__ __forceinline__ StOut(const StateLattice &d_) : d(d_), kq((int64_t)d_.K - 1), fq(st_frame(d_, (int64_t)d_.K - 1)) {}
@@ -57,27 +58,16 @@ struct StOut {
     }
 };
 
-template <int M>
-__global__ __launch_bounds__(64) void state_posterior_fast_kernel(const StateLattice *__restrict__ lats, int n, PostResult *res)
+template <class Form>
+__global__ __launch_bounds__(Form::NT) void state_posterior_kernel(const StateLattice *__restrict__ lats, int n, PostResult *res)
 {
-    __shared__ double col[4][1024];
-    __shared__ double row[64];
+    __shared__ typename Form::template Shared<4> sh;
     __shared__ double cav[kPostCk];
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        StOut<64> out(lats[i]);
-        fb_ck_fast<M>(lats[i], res, col, row, cav, out);
-        post_wave_sync();
-    }
-}
-
-__global__ __launch_bounds__(256) void state_posterior_generic_kernel(const StateLattice *__restrict__ lats, int n, PostResult *res)
-{
-    __shared__ double red[2][4];
-    __shared__ double cav[kPostCk];
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        StOut<256> out(lats[i]);
-        fb_ck_gen(lats[i], res, red, cav, out);
-        __syncthreads();
+        Form f(lats[i], sh);
+        StOut<Form> out(lats[i]);
+        fb_ck(f, res, cav, out);
+        f.sync();
     }
 }
 

@@ -153,7 +153,7 @@ constexpr int kStatusBadArgs = -2;     // a best-path position outside [0, L)
 constexpr int kStatusNonFinite = -7;   // a log-prob is +inf
 constexpr int kStatusZeroMass = -9;    // no path of finite score ends at the best path's terminal
 constexpr int kPostCk = 32;            // frames per forward offset checkpoint
-// what both forward-backward calls describe of a lattice; the shared device code (ka_posterior_common.hpp) takes this part
+// what every forward-backward call describes of a lattice; the shared device code (ka_posterior_common.hpp) takes this part
 struct FbLattice {
     const float *lp;         // [T, ld] log-probs (device)
     const int32_t *labels;   // [S] caller labels (device)
