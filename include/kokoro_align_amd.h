@@ -333,6 +333,13 @@ int ka_debug_tile_stats(ka_engine *e, uint64_t *out, int32_t max_tasks);
  * last frame of every chunk followed by that of every super-chunk (returns how many values), and optionally its
  * chunk maps (one row of ring-size bytes per chunk). */
 int ka_debug_chunk_entries(ka_engine *e, int32_t *out, int32_t max_entries, uint8_t *map0_out, int64_t map0_max);
+/* Diagnostics of the forward pass: for the first lattice of the last finished batch, the score rows its checkpointed
+ * forward kernel stored, row k after frame 32 (k + 1) - 1, (T - 1) / 32 rows of *pitch bytes; position p lies at float
+ * p & (*pitch / 4 - 1) of its row when the label axis is longer than a row (always in the one-wavefront form: 1024
+ * slots), else at float p.  Only the band of that frame is defined.  Copies at most max_floats values and returns the
+ * number of rows: 0 (and *pitch = 0) where no checkpoints were stored - the exact and generic forms, and a lattice that
+ * the checkpointed forms declined (non-finite log-probs). */
+int ka_debug_checkpoints(ka_engine *e, float *out, int64_t max_floats, int64_t *pitch);
 /* Host-side probe of the tiled form's plan (no GPU needed): for a lattice of T frames, S phonemes, V classes the
  * 256-position tiles the band of align.py:64-65 ever touches and the frames [t_in, t_end) each of them is alive in.
  * Returns the number of tiles (t_in / t_end are filled up to max_tiles), 0 if the shape is not run in the tiled form,

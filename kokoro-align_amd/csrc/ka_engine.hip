@@ -110,6 +110,12 @@ ka_engine::DebugView debug_view_of(const LaunchPlan &p)
     v.entry_n = sh.par_bt ? (size_t)(chunks_of_T(sh.T) + supers_of_T(sh.T)) : 0;
     v.map0 = cv.map0;
     v.map0_bytes = sh.par_bt ? (size_t)chunks_of_T(sh.T) * ((sh.tiled ? sh.ck_pitch : 4096) / 4) : 0;
+    // checkpoint rows: the tiled forms, and the one-wavefront form unless it stores back-pointers (enqueue_forward)
+    const bool checkpointed = sh.tiled || (sh.fast && p.checkpointed_waves && sh.T < (int64_t(1) << 26));
+    v.ck = cv.bp;
+    v.ck_pitch = sh.tiled ? sh.ck_pitch : 4096;
+    v.ck_bytes = checkpointed ? (size_t)(chunks_of_T(sh.T) - 1) * v.ck_pitch : 0;
+    v.ck_idx = p.order[0];
     v.tasks = p.off_tasks;
     v.stats = p.off_stats;
     v.n_tasks = p.n_tasks;
@@ -652,6 +658,7 @@ int ka_batch_finish(ka_engine *e, float *total_score, int32_t *status)
     if (e->set.profiling && b.n > 0) b.have_times = true;
     // (a copy: the redo lays its own descriptors and status records over the pinned ones)
     std::vector<ka::LatticeMeta> meta(b.meta, b.meta + (size_t)b.n);
+    if (e->dbg.ck_idx < b.n && (meta[e->dbg.ck_idx].flags & (ka::kFlagExact | ka::kFlagDeclined))) e->dbg.ck_bytes = 0;
     // wide tiled lattices the scores-only form declined: KA_MODE_AUTO redoes them through the generic kernels, an explicit
     // KA_MODE_TILED reports KA_ERR_NONFINITE
     std::vector<ka_engine::Redo> again;
@@ -717,6 +724,18 @@ int ka_debug_chunk_entries(ka_engine *e, int32_t *out, int32_t max_entries, uint
     if (map0_out && map0_max > 0 && e->dbg.map0_bytes)
         KA_HIP(hipMemcpy(map0_out, e->res.ws + e->dbg.map0, std::min<size_t>(e->dbg.map0_bytes, (size_t)map0_max), hipMemcpyDeviceToHost));
     return (int)n;
+}
+
+int ka_debug_checkpoints(ka_engine *e, float *out, int64_t max_floats, int64_t *pitch)
+{
+    if (!e || max_floats < 0 || (max_floats > 0 && !out)) return fail(KA_ERR_BAD_ARGS, "ka_debug_checkpoints: bad arguments");
+    if (e->batch.pending) return fail(KA_ERR_BAD_ARGS, "ka_debug_checkpoints: a batch is enqueued and not finished");
+    DeviceGuard guard;
+    KA_HIP(guard.enter(e->device));
+    if (pitch) *pitch = e->dbg.ck_bytes ? (int64_t)e->dbg.ck_pitch : 0;
+    const size_t n = std::min<size_t>(e->dbg.ck_bytes / 4, (size_t)max_floats);
+    if (n) KA_HIP(hipMemcpy(out, e->res.ws + e->dbg.ck, n * 4, hipMemcpyDeviceToHost));
+    return e->dbg.ck_bytes ? (int)(e->dbg.ck_bytes / e->dbg.ck_pitch) : 0;
 }
 
 int ka_debug_plan_tiles_width(int64_t T, int64_t S, int32_t V, int32_t beam_size, int32_t max_move, int32_t positions, int32_t *t_in, int32_t *t_end,

@@ -97,10 +97,14 @@ struct ka_engine {
         void invalidate() { lo = hi = 0; }
     } clean;
 
-    // workspace offsets of the last launch, for ka_debug_chunk_entries (descriptor 0: chunk entries and chunk maps) and
+    // workspace offsets of the last launch, for ka_debug_chunk_entries (descriptor 0: chunk entries and chunk maps),
+    // ka_debug_checkpoints (descriptor 0: the checkpoint rows of the forward pass; ck_bytes = 0 where it stored none: the exact
+    // and generic forms, and a lattice the checkpointed forms declined - ka_batch_finish sees that in its flags) and
     // ka_debug_tile_stats (the tile tasks and their timing records)
     struct DebugView {
         size_t entry = 0, entry_n = 0, map0 = 0, map0_bytes = 0;
+        size_t ck = 0, ck_bytes = 0, ck_pitch = 0;
+        int32_t ck_idx = 0;      // the caller's index of descriptor 0
         size_t tasks = 0, stats = 0, n_tasks = 0;
     } dbg;
 };

@@ -29,6 +29,11 @@ WAVE_RING = 1024
 # position higher wherever it has left 0;  rise_short: the rise is measured to the first frame of the chunk instead of the last
 # frame of the chunk before (one move too few);  no_ring_mask: a map row is indexed with p instead of p & (R - 1)
 FAULTS = ("last_max", "no_veto", "lo_plus_one", "rise_short", "no_ring_mask")
+# ... and four more for the band edges of the forward pass (tests/bestpath_cases.py; kept apart so that the
+# map tests' table of faults stays what it was).  hi_minus_one / hi_plus_one: the band ends one position lower / higher wherever
+# its end is a real edge (hi < L);  lo_minus_one: it starts one position lower wherever it has left 0;  stale_label: a position
+# that enters the band at the upper edge keeps the label of position - 1024 (the slot's last owner in a ring of 1024) for one frame
+EDGE_FAULTS = ("hi_minus_one", "hi_plus_one", "lo_minus_one", "stale_label")
 
 NEG = np.float32(-np.inf)
 
@@ -45,7 +50,14 @@ def band(T, L, beam, fault=None):
     lo = np.maximum(0, L * t // T - beam // 2)
     if fault == "lo_plus_one":
         lo = np.where(lo > 0, lo + 1, lo)
-    return lo, np.minimum(lo + beam, L)
+    hi = np.minimum(lo + beam, L)
+    if fault == "hi_minus_one":
+        hi = np.where(hi < L, np.maximum(hi - 1, lo + 1), hi)
+    elif fault == "hi_plus_one":
+        hi = np.where(hi < L, hi + 1, hi)
+    elif fault == "lo_minus_one":
+        lo = np.where(lo > 0, lo - 1, lo)
+    return lo, hi
 
 
 def chunk_last_frames(T):
@@ -60,11 +72,14 @@ def super_last_frames(T):
 
 
 class Ref:
-    """What best_path_with_moves returns; rise[c] / reachable[c] are indexed by p - lo[te[c]] (None for chunk 0)."""
+    """What best_path_with_moves returns; rise[c] / reachable[c] are indexed by p - lo[te[c]] (None for chunk 0); rows[k] is
+    the score row after frame 32 (k + 1) - 1, indexed by p - lo of that frame: checkpoint k of the forward kernels."""
 
 
-def best_path_with_moves(log_probs, labels, beam_size=1000, max_move=4, fault=None):
-    assert fault is None or fault in FAULTS, fault
+def best_path_with_moves(log_probs, labels, beam_size=1000, max_move=4, fault=None, maps=True):
+    """maps=False leaves the rises out (rise and reachable stay [None]): half the time, for callers that want the path, the
+    total and the checkpoint rows only."""
+    assert fault is None or fault in FAULTS + EDGE_FAULTS, fault
     lp = np.ascontiguousarray(log_probs, np.float32)
     ext = expand(labels)
     T, L = lp.shape[0], ext.shape[0]
@@ -76,15 +91,22 @@ def best_path_with_moves(log_probs, labels, beam_size=1000, max_move=4, fault=No
     pad = max_move - 1
     prev = np.full(L + pad, NEG, np.float32)     # prev[pad + p]: score of position p after the frame before
     prev[pad] = 0.0
+    rows = []
     for t in range(T):
         a, b = int(lo[t]), int(hi[t])
         w = b - a
-        e = lp[t, ext[a:b]]
+        lab_t, veto_t = ext[a:b], vetoed[a:b]
+        if fault == "stale_label" and t > 0 and b > max(int(hi[t - 1]), WAVE_RING):
+            fresh = np.arange(max(int(hi[t - 1]), WAVE_RING, a), b)
+            lab_t, veto_t = lab_t.copy(), veto_t.copy()
+            lab_t[fresh - a] = ext[fresh - WAVE_RING]
+            veto_t[fresh - a] = vetoed[fresh - WAVE_RING]
+        e = lp[t, lab_t]
         cand = np.full((max_move, w), NEG, np.float32)
         for j in range(max_move):
             cand[j] = prev[pad + a - j:pad + b - j] + e
             if j > 0 and j % 2 == 0:
-                cand[j, vetoed[a:b]] = NEG
+                cand[j, veto_t] = NEG
         if fault == "last_max":
             mv = max_move - 1 - np.argmax(cand[::-1], axis=0)
         else:
@@ -94,9 +116,11 @@ def best_path_with_moves(log_probs, labels, beam_size=1000, max_move=4, fault=No
         finite[t, :w] = np.isfinite(sc)
         prev = np.full(L + pad, NEG, np.float32)
         prev[pad + a:pad + b] = sc
+        if t % CK == (CK - 2 if fault == "rise_short" else CK - 1) and t < T - 1 and len(rows) < (T - 1) // CK:
+            rows.append(sc)      # (rise_short: the same off-by-one in the forward pass - the row is taken a frame early)
     r = Ref()
     r.T, r.L, r.W, r.beam, r.max_move = T, L, max(1, min(beam_size, L)), beam_size, max_move
-    r.lo, r.hi, r.moves, r.finite = lo, hi, moves, finite
+    r.lo, r.hi, r.moves, r.finite, r.rows = lo, hi, moves, finite, rows
     live = np.nonzero(finite[T - 1])[0]
     if live.size == 0:
         raise ValueError("attempt to get argmax of an empty sequence")
@@ -109,11 +133,13 @@ def best_path_with_moves(log_probs, labels, beam_size=1000, max_move=4, fault=No
         p -= int(moves[t, p - lo[t]])
     r.path = path
     r.labels = ext[path].astype(np.int32)
-    r.scores = lp[np.arange(T), r.labels]
+    r.scores = lp[np.arange(T), r.labels]      # (stale_label: the labels and scores of the positions, as the output gather reads them)
     r.te = chunk_last_frames(T)
     r.entries = path[r.te].astype(np.int32)
     r.super_entries = path[super_last_frames(T)].astype(np.int32)
     r.rise, r.reachable = [None], [None]
+    if not maps:
+        return r
     short = 1 if fault == "rise_short" else 0
     for c in range(1, len(r.te)):
         te = int(r.te[c])

@@ -18,7 +18,8 @@ def _declared():
 def test_header_declares_the_boundary():
     names = _declared()
     for must in ("ka_ctc_best_path_f32", "ka_ctc_best_path_batch_f32", "ka_ctc_best_path_batch_enqueue_f32",
-                 "ka_batch_finish", "ka_engine_create", "ka_engine_destroy", "ka_last_error", "ka_log_softmax_f32"):
+                 "ka_batch_finish", "ka_engine_create", "ka_engine_destroy", "ka_last_error", "ka_log_softmax_f32",
+                 "ka_debug_chunk_entries", "ka_debug_checkpoints"):
         assert must in names
 
 
