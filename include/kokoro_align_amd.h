@@ -257,6 +257,38 @@ int ka_ctc_sample_paths_batch_f32(ka_engine *e, int32_t n, const float *const *l
 size_t ka_sample_paths_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int32_t *n_samples, int32_t V,
                                        int32_t beam_size, int32_t max_move, int32_t mem);
 
+/*
+ * The maximum-expected-accuracy alignment (posterior-decoded path) and the lattice log-likelihood of a terminal (DESIGN.md
+ * section 4.26): on the lattice of ka_ctc_label_posteriors (same band [lo_t, hi_t), moves j in [0, max_move), label-0 veto,
+ * terminal s*, statuses and Z), the band path that ends at s* with the most frames at the right state in expectation,
+ *   path = argmax over paths of sum over t of gamma_t(path[t]),   gamma the float ka_ctc_state_posteriors writes.
+ * With lab' the blank-expanded labels, in float64 (one add per cell, so the sums have no order dependence):
+ *   W_{T-1}(p) = gamma_{T-1}(p) if p = s*, else -inf
+ *   W_t(p)     = gamma_t(p) + max over j in [0, max_move) with p + j in [lo_{t+1}, hi_{t+1}) and not (j even, j >= 2,
+ *                lab'[p + j] == 0) of W_{t+1}(p + j)   (-inf where no such j has a finite W);  c_t(p) = the SMALLEST such j
+ *   path[0]    = the smallest j < max_move in [lo_0, hi_0), not (j even, j >= 2, lab'[j] == 0), that maximises W_0(j)
+ *   path[t+1]  = path[t] + c_t(path[t]);   expected_accuracy = W_0(path[0])
+ * so the path and expected_accuracy equal that recursion run on the rows of ka_ctc_state_posteriors at every frame, bit for
+ * bit, without the [T, W] matrix.  expected_accuracy / T is the expected fraction of correctly placed frames.
+ * Arguments as ka_ctc_label_posteriors[_batch]_f32, with in place of occupancy
+ *   path               [T] int32 output (where `mem` says): the path's position in the blank-expanded labels at every frame
+ *   expected_accuracy  float64 output, HOST memory in both modes (batch: [n]); may be NULL
+ * Per lattice: statuses and log-likelihood as ka_ctc_label_posteriors (the same bits), with -1 over [0, T) of the path and NaN
+ * as the expected accuracy of a failed lattice.  Measured at 1.03 (1024 lattices) to 1.08 (one lattice) times a state-duration
+ * call; like it, up to 768 lattices are resident at once and 769 to 1536 run in two rounds.
+ */
+int ka_ctc_mea_path_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                        int32_t beam_size, int32_t max_move, int64_t terminal, int32_t *path, double *expected_accuracy,
+                        double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_mea_path_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                              const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                              const int64_t *terminal, int32_t *const *path, double *expected_accuracy, double *log_likelihood,
+                              int32_t *status, int32_t mem, void *stream);
+/* device-workspace bytes such a call carves (0 for unsupported arguments): the slots of ka_label_posterior_workspace_bytes plus,
+ * per slot, the back-pointers of the longest lattice it serves (256 bytes per frame in the one-wavefront form) */
+size_t ka_mea_path_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                   int32_t mem);
+
 /* Kernel form of the fast path.
  *   KA_MODE_WAVE        one wavefront per lattice, checkpointed (throughput; fills the chip from ~4096
  *                       lattices): the forward kernel keeps scores only and stores the score ring every 32

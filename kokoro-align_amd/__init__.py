@@ -12,7 +12,9 @@ log-likelihood (lattice_log_likelihood) and the state posteriors at chosen frame
 boundaries (ctc_state_posteriors[_batch|_device], boundary_frames, segment_boundary_confidence), and the expected duration of
 every state with the expected frame of every boundary (ctc_state_durations[_batch|_device], phoneme_durations,
 expected_crossing_frames, segment_boundary_shift), and whole alignments sampled from the posterior over the band's paths with
-the spread of every boundary (ctc_sample_paths[_batch|_device], sampled_crossing_frames, segment_boundary_spread).
+the spread of every boundary (ctc_sample_paths[_batch|_device], sampled_crossing_frames, segment_boundary_spread), and the
+alignment with the most frames at the right state in expectation (ctc_mea_path[_batch|_device], path_outputs,
+segment_path_disagreement).
 
 The DP and backtrace run in the HIP C-ABI library (include/kokoro_align_amd.h); there is no
 CPU fallback — importing works without a GPU, computing does not.
@@ -32,6 +34,9 @@ from .posteriors import (  # noqa: F401
     ctc_label_posteriors,
     ctc_label_posteriors_batch,
     ctc_label_posteriors_device,
+    ctc_mea_path,
+    ctc_mea_path_batch,
+    ctc_mea_path_device,
     ctc_path_posteriors,
     ctc_path_posteriors_batch,
     ctc_path_posteriors_device,
@@ -46,6 +51,7 @@ from .posteriors import (  # noqa: F401
     ctc_state_posteriors_device,
     expected_crossing_frames,
     lattice_log_likelihood,
+    path_outputs,
     phoneme_durations,
     sampled_crossing_frames,
     segment_agreement,
@@ -53,6 +59,7 @@ from .posteriors import (  # noqa: F401
     segment_boundary_shift,
     segment_boundary_spread,
     segment_confidence,
+    segment_path_disagreement,
 )
 from ._lib import KAError, build_library, library_path, load_library  # noqa: F401
 

@@ -42,6 +42,7 @@ EXPORTS = [
     "ka_ctc_state_posteriors_f32", "ka_ctc_state_posteriors_batch_f32", "ka_state_posterior_workspace_bytes",
     "ka_ctc_state_durations_f32", "ka_ctc_state_durations_batch_f32", "ka_state_duration_workspace_bytes",
     "ka_ctc_sample_paths_f32", "ka_ctc_sample_paths_batch_f32", "ka_sample_paths_workspace_bytes",
+    "ka_ctc_mea_path_f32", "ka_ctc_mea_path_batch_f32", "ka_mea_path_workspace_bytes",
 ]
 
 
@@ -133,6 +134,12 @@ def load_library():
     L.ka_ctc_sample_paths_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pi64, vp, vp, pp, pi64, vp, vp, i32, vp]
     L.ka_sample_paths_workspace_bytes.restype = sz
     L.ka_sample_paths_workspace_bytes.argtypes = [i32, pi64, pi64, vp, i32, i32, i32, i32]
+    L.ka_ctc_mea_path_f32.restype = ctypes.c_int
+    L.ka_ctc_mea_path_f32.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i64, vp, vp, vp, i32, vp]
+    L.ka_ctc_mea_path_batch_f32.restype = ctypes.c_int
+    L.ka_ctc_mea_path_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pi64, pp, vp, vp, vp, i32, vp]
+    L.ka_mea_path_workspace_bytes.restype = sz
+    L.ka_mea_path_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
     L.ka_engine_set_mode.restype = ctypes.c_int
     L.ka_engine_set_mode.argtypes = [vp, i32]
     L.ka_engine_set_backtrace.restype = ctypes.c_int

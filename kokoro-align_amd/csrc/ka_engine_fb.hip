@@ -1,6 +1,7 @@
 // ka_engine_fb.hip — the forward-backward calls of the C ABI: best-path posteriors (ka_posterior.hpp), label occupancy
-// (ka_occupancy.hpp), state posteriors at chosen frames (ka_state_posterior.hpp), expected state durations (ka_duration.hpp)
-// and alignments sampled from the band posterior (ka_sample.hpp).  Host code only.
+// (ka_occupancy.hpp), state posteriors at chosen frames (ka_state_posterior.hpp), expected state durations (ka_duration.hpp),
+// alignments sampled from the band posterior (ka_sample.hpp) and the maximum-expected-accuracy alignment (ka_mea.hpp).  Host
+// code only.
 // They use the engine's workspace and pinned buffer, with their own kernels and workspace layout, whatever
 // the engine's mode, and run to the end inside the call: no batch stays in flight.
 #include "ka_engine.hpp"
@@ -15,8 +16,8 @@ using ka::plan::align_up;
 
 // ---- best-path posteriors (ka_posterior.hpp), label occupancy (ka_occupancy.hpp), state posteriors at chosen frames
 // (ka_state_posterior.hpp) and expected state durations (ka_duration.hpp): their own kernels and workspace layout, whatever the
-// engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall, DurCall, SampleCall) brings what differs: its
-// own arrays and their
+// engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall, DurCall, SampleCall, MeaCall) brings what
+// differs: its own arrays and their
 // checks, its planner and launch, the descriptor fields beyond FbLattice, its own staging (upload: host buffers only;
 // stage: every memory mode), and what two statuses mean.
 struct FbArgs {
@@ -272,6 +273,52 @@ struct SampleCall {
     }
 };
 
+struct MeaCall {
+    using Desc = ka::MeaLattice;
+    using Carve = ka::plan::MeaCarve;
+    static constexpr const char *kName = "mea path";
+    static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score reaches the terminal";
+    const int64_t *terminal;
+    int32_t *const *path;
+    double *expected_accuracy;   // host array in both memory modes, as log_likelihood is; may be NULL
+
+    bool arrays() const { return terminal && path; }
+    const char *bad_lattice(const FbArgs &, int32_t) const { return nullptr; }
+    bool buffers(int32_t i) const { return path[i] != nullptr; }
+    static constexpr auto plan = ka::plan::mea_path_workspace;
+    static constexpr auto launch = ka::launch_mea_path;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        d.path = a.mem == KA_MEM_HOST ? reinterpret_cast<int32_t *>(ws + c.path) : path[i];
+        fill_slot(d, c, terminal[i], ws);
+        d.ea = reinterpret_cast<double *>(ws + c.ea);
+        d.bp = ws + c.bp;
+        d.wcol = reinterpret_cast<double *>(ws + c.wcol);
+    }
+    int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int stage(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        KA_HIP(hipMemcpyAsync(path[i], ws + c.path, (size_t)a.T[i] * 4, hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
+// what a call reads back per lattice besides PostResult, in both memory modes, enqueued behind the launch: nothing, but for
+// the expected accuracies of MeaCall (one double per lattice, consecutive from lattice 0's)
+template <class Call>
+int fb_readback(const Call &, const typename Call::Carve *, const FbArgs &, char *)
+{
+    return KA_OK;
+}
+int fb_readback(const MeaCall &call, const ka::plan::MeaCarve *cv, const FbArgs &a, char *ws)
+{
+    if (call.expected_accuracy)
+        KA_HIP(hipMemcpyAsync(call.expected_accuracy, ws + cv[0].ea, (size_t)a.n * sizeof(double), hipMemcpyDeviceToHost, a.stream));
+    return KA_OK;
+}
+
 template <class Call>
 int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
 {
@@ -350,6 +397,7 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
     Call::launch(d_lats, n_fast, n - n_fast, a.max_move, d_res, stream);
     KA_HIP(hipGetLastError());
     KA_HIP(hipMemcpyAsync(h_res, d_res, (size_t)n * sizeof(ka::PostResult), hipMemcpyDeviceToHost, stream));
+    if ((rc = fb_readback(call, cv.data(), a, e->res.ws)) != KA_OK) return rc;
     if (host)
         for (int32_t i = 0; i < n; ++i)
             if ((rc = call.download(cv[i], a, i, e->res.ws)) != KA_OK) return rc;
@@ -491,6 +539,29 @@ size_t ka_sample_paths_workspace_bytes(int32_t n, const int64_t *T, const int64_
     for (int32_t i = 0; i < n; ++i)
         if (n_samples[i] < 1 || n_samples[i] > ka::kMaxSamples) return 0;
     return ka::plan::sample_paths_workspace(n, T, S, n_samples, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+int ka_ctc_mea_path_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                              const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move, const int64_t *terminal,
+                              int32_t *const *path, double *expected_accuracy, double *log_likelihood, int32_t *status, int32_t mem,
+                              void *stream)
+{
+    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+                   MeaCall{terminal, path, expected_accuracy});
+}
+
+int ka_ctc_mea_path_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                        int32_t beam_size, int32_t max_move, int64_t terminal, int32_t *path, double *expected_accuracy,
+                        double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+                   MeaCall{&terminal, &path, expected_accuracy});
+}
+
+size_t ka_mea_path_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::mea_path_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
 }  // extern "C"

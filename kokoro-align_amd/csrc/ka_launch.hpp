@@ -1,6 +1,6 @@
 // ka_launch.hpp — the host-callable launch functions of every device translation unit.
 //
-// The library is built from fourteen translation units so that the device code compiles in parallel (a single unit took three
+// The library is built from fifteen translation units so that the device code compiles in parallel (a single unit took three
 // minutes): ka_engine.hip, ka_engine_fb.hip and ka_entry_misc.hip are host code only and reach the kernels through these
 // functions; each kernel family lives in the .hip file named below and nowhere else.  All functions only enqueue; errors
 // surface through hipGetLastError().
@@ -98,5 +98,9 @@ void launch_state_durations(const DurLattice *lats, int n_fast, int n_generic, i
 // ---- ka_sample.hip: alignments sampled from the band posterior (ka_sample.hpp): ka_fb_ck.hpp's forward pass and block
 // recompute, launch_fb_ck's form split, grid and slots ----
 void launch_sample_paths(const SampleLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+
+// ---- ka_mea.hip: the maximum-expected-accuracy alignment (ka_mea.hpp): ka_fb_ck.hpp's driver with one more policy,
+// launch_fb_ck's form split, grid and slots ----
+void launch_mea_path(const MeaLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 
 }  // namespace ka

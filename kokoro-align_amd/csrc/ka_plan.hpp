@@ -814,3 +814,66 @@ inline size_t sample_paths_workspace(int32_t n, const int64_t *T, const int64_t 
 
 }  // namespace plan
 }  // namespace ka
+
+namespace ka {
+namespace plan {
+
+// ---- ka_ctc_mea_path_batch_f32 (ka_mea.hpp): workspace layout ----
+// label_posterior_workspace's layout and slots (the slot's V-wide global bins go unused), with MeaLattice descriptors; for host
+// buffers the staged path (T int32) lies beside the staged log-probs and labels.  Behind the shared slots: the expected
+// accuracies (a double per lattice, which the host reads in both memory modes), then a second region per slot with what the
+// shared slot does not hold: the back-pointers of the whole lattice (fast form: 256 bytes per frame; generic: cw bytes per
+// frame) and the generic form's two W columns (2 L doubles).  A slot's region is as large as the largest lattice that the
+// slot serves in this call needs (lattice of rank r in its form on slot r mod slots, as launch_fb_ck walks them).
+struct MeaCarve : SlotCarve {
+    size_t path;   // host buffers only
+    size_t ea, bp, wcol;
+};
+inline size_t mea_path_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
+                                 MeaCarve *cv, size_t *off_res)
+{
+    struct Need {
+        bool fast;
+        size_t rank, bp, w;
+    };
+    std::vector<Need> need;
+    need.reserve((size_t)std::max(n, 0));
+    size_t n_form[2] = {0, 0};   // lattices per form
+    size_t off = slot_workspace(n, sizeof(MeaLattice), T, S, V, beam, max_move, cv, off_res, [&](int32_t, const Shape &sh, MeaCarve &c, size_t &o) {
+        if (host_buffers) {
+            carve_staged(o, sh, V, c);
+            c.path = o;
+            o += align_up((size_t)sh.T * 4);
+        }
+        ++n_form[c.fast ? 0 : 1];
+        need.push_back({c.fast, c.slot /* slot_workspace's rank of the lattice in its form */, align_up((size_t)sh.T * (c.fast ? 256 : (size_t)c.parts.cw)),
+                        c.fast ? 0 : align_up((size_t)sh.L * 2 * sizeof(double))});
+        return true;
+    });
+    if (off == 0) return 0;
+    const size_t ea_base = off;
+    off += align_up((size_t)n * sizeof(double));
+    const size_t slots[2] = {std::min<size_t>(n_form[0], kOccFastSlots), std::min<size_t>(n_form[1], kOccGenericSlots)};
+    std::vector<size_t> base[2] = {std::vector<size_t>(slots[0], 0), std::vector<size_t>(slots[1], 0)};   // a slot's bytes, then its offset
+    for (const Need &x : need) {
+        size_t &b = base[x.fast ? 0 : 1][x.rank % slots[x.fast ? 0 : 1]];
+        b = std::max(b, x.bp + x.w);
+    }
+    for (auto &form : base)
+        for (size_t &b : form) {
+            const size_t bytes = b;
+            b = off;
+            off += bytes;
+        }
+    if (cv)
+        for (int32_t i = 0; i < n; ++i) {
+            const Need &x = need[(size_t)i];
+            cv[i].ea = ea_base + (size_t)i * sizeof(double);
+            cv[i].bp = base[x.fast ? 0 : 1][x.rank % slots[x.fast ? 0 : 1]];
+            cv[i].wcol = cv[i].bp + x.bp;
+        }
+    return off;
+}
+
+}  // namespace plan
+}  // namespace ka

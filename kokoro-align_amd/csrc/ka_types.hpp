@@ -213,6 +213,14 @@ struct SampleLattice : FbCkLattice {
     int32_t n_samples;            // in [1, kMaxSamples]
     int32_t pad_;
 };
+// ---- the maximum-expected-accuracy alignment (ka_mea.hpp): the occupancy's slots and form split ----
+struct MeaLattice : FbCkLattice {
+    int32_t *path;                // [T] output: the path's position at every frame
+    double *ea;                   // one double: sum over t of gamma_t(path[t]) (workspace; the host copies it out)
+    void *bp;                     // back-pointers of every cell: uint32 [T][64] (fast form, 2 bits per cell) or uint8 [T][cw] (slot)
+    double *wcol;                 // generic form only: 2 x L doubles, W of frame t+1 and of frame t (slot)
+};
+static_assert(sizeof(MeaLattice) == 136, "descriptor sizes");
 // the workspace planners (ka_plan.hpp) carve n descriptors: their sizes are part of the published workspace byte counts
 static_assert(sizeof(PostLattice) == 88 && sizeof(FbCkLattice) == 104 && sizeof(OccLattice) == 120 && sizeof(StateLattice) == 136 &&
                   sizeof(DurLattice) == 120 && sizeof(SampleLattice) == 128,

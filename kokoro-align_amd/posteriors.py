@@ -1,7 +1,7 @@
 """Forward-backward over the band of ``ctc_best_path``: path posteriors, label occupancy, state posteriors at chosen frames,
-expected state durations, alignments sampled from the posterior.
+expected state durations, alignments sampled from the posterior, the maximum-expected-accuracy alignment.
 
-The five calls take the same lattices (log-probs, labels, beam_size, max_move) in host or device memory and answer with one
+The six calls take the same lattices (log-probs, labels, beam_size, max_move) in host or device memory and answer with one
 log-likelihood and one status per lattice.  ``_Lattices`` is that common input, normalised once and aware of its memory mode;
 ``_run_lattices`` is the one C call and the one status handling.  What is a call's own (its extra inputs, its outputs, its
 argument tables) is in its private function; ``X_batch`` and ``X_device`` only choose the memory mode.
@@ -89,7 +89,7 @@ def _device_lattices(log_probs, labels, others, what):
 
 
 def _run_lattices(lat, call, beam_size, max_move, own_args, outs, return_status):
-    """The call ``ka_ctc_<call>_batch_f32`` (path_posteriors, label_posteriors, state_posteriors, state_durations, sample_paths): the
+    """The call ``ka_ctc_<call>_batch_f32`` (path_posteriors, label_posteriors, state_posteriors, state_durations, sample_paths, mea_path): the
     arguments all of them take around ``own_args`` (the call's own tables), then the results (*outs[i], log_likelihood[i]),
     ``outs`` a list of tuples, and the status handling of ``return_status``."""
     name = f"ctc_{call}_{lat.form}"
@@ -691,3 +691,110 @@ def segment_boundary_spread(paths, best_path, seg_ends, n_phonemes, q=(0.05, 0.5
     end = [spread(b) for _, _, b in segs]
     stack = lambda rows: np.array([r[0] for r in rows], dtype=np.float64).reshape(len(rows), len(qs))
     return (stack(start), np.array([r[1] for r in start], dtype=np.float64), stack(end), np.array([r[1] for r in end], dtype=np.float64))
+
+
+# ------------------------------------------------------------------------------------------
+# the maximum-expected-accuracy alignment (posterior-decoded path), and where it leaves the best path
+# ------------------------------------------------------------------------------------------
+def ctc_mea_path(log_probs, labels, terminal, beam_size=1000, max_move=4):
+    """The alignment with the most frames at the right state in expectation: (path int32 [T], expected_accuracy float,
+    log_likelihood float).
+
+    Among the paths of the band of ``ctc_best_path`` that end at state ``terminal`` (an int, or a best path whose last value is
+    used), ``path`` maximises the sum over the frames of the state posterior gamma_t(path[t]) of ``ctc_state_posteriors``,
+    where the best path maximises the probability of the whole path; path[t] is its position in the blank-expanded labels.
+    ``expected_accuracy`` is that sum - divided by T, the expected fraction of correctly placed frames, a one-number quality
+    score of the lattice.  Ties go to the smallest move.  Equals the recursion run on ``ctc_state_posteriors`` at every frame
+    bit for bit, without the [T, W] matrix.  NumPy in -> NumPy out; ROCm torch tensors go to ``ctc_mea_path_device``.  Raises
+    as ``ctc_label_posteriors``.
+    """
+    call = ctc_mea_path_device if _is_tensor(log_probs) else ctc_mea_path_batch
+    (result,) = call([log_probs], [labels], [terminal], beam_size, max_move)
+    return result
+
+
+def _mea_path(lat, terminals, beam_size, max_move, out, return_status):
+    if lat is None:
+        return ([], []) if return_status else []
+    if out is None:
+        paths = [lat.empty(T, np.int32) for T in lat.T]
+    else:
+        import torch
+        if len(out) != lat.n:
+            raise ValueError("out must hold one tensor per lattice")
+        for o, T in zip(out, lat.T):
+            if o.dtype != torch.int32 or tuple(o.shape) != (T,) or not o.is_contiguous() or o.device != lat.dev:
+                raise ValueError("out tensors must be contiguous int32 [T_i] on the input's device")
+        paths = out
+    ea = np.zeros(lat.n, np.float64)
+    p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
+    p_path, _k2 = _ptr_array([lat.ptr(x) for x in paths])
+    # (the expected accuracies are a host array the call fills: zipped as 0-d views, made floats once it has returned)
+    got = _run_lattices(lat, "mea_path", beam_size, max_move, (p_term, p_path, ea.ctypes.data), list(zip(paths, ea.reshape(-1, 1))),
+                        return_status)
+    results = [(p, float(v[0]), z) for p, v, z in (got[0] if return_status else got)]
+    return (results, got[1]) if return_status else results
+
+
+def ctc_mea_path_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False):
+    """Maximum-expected-accuracy paths of many lattices in ONE launch; host NumPy buffers in and out.
+
+    Returns a list of (path [T_i], expected_accuracy, log_likelihood); with ``return_status`` also the per-lattice status list,
+    in which case failures do not raise (their paths are -1, their expected accuracy NaN, their log-likelihood NaN, or -inf for
+    KA_ERR_ZERO_MASS).
+    """
+    lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
+    return _mea_path(lat, terminals, beam_size, max_move, None, return_status)
+
+
+def ctc_mea_path_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]) and terminals (ints
+    or best paths), list of (path int32 tensor [T_i] on the device, expected_accuracy float, log_likelihood float) out.
+    ``out``: optional list of contiguous int32 [T_i] tensors to write the paths into.  One launch on torch's current stream."""
+    lat = _device_lattices(log_probs, labels, terminals, "terminals")
+    return _mea_path(lat, terminals, beam_size, max_move, out, return_status)
+
+
+def path_outputs(log_probs, labels, path):
+    """The (path, labels, scores) triple of ``ctc_best_path`` for any path over the blank-expanded labels (host only): path
+    int32 [T], labels[t] = lab'[path[t]] int32, scores[t] = log_probs[t, labels[t]] float32.  Saved as
+    ``np.savez(file, best_path=..., best_labels=..., best_scores=...)`` it is a ``best_path.npz`` that ``align()`` takes
+    unchanged - e.g. for the path of ``ctc_mea_path``."""
+    lp = np.asarray(log_probs.detach().cpu() if _is_tensor(log_probs) else log_probs, dtype=np.float32)
+    lab = np.asarray(labels.detach().cpu() if _is_tensor(labels) else labels).reshape(-1)
+    p = np.ascontiguousarray(np.asarray(path.detach().cpu() if _is_tensor(path) else path).reshape(-1), dtype=np.int32)
+    expanded = np.zeros(2 * len(lab) + 1, np.int32)
+    expanded[1::2] = lab
+    if lp.ndim != 2 or len(p) != lp.shape[0]:
+        raise ValueError("path_outputs: path must have one position per frame of log_probs [T, V]")
+    if len(p) and (p.min() < 0 or p.max() >= len(expanded)):
+        raise ValueError("path_outputs: a path position outside [0, 2S+1)")
+    out_labels = expanded[p]
+    return p, out_labels, np.ascontiguousarray(lp[np.arange(len(p)), out_labels], dtype=np.float32)
+
+
+def segment_path_disagreement(best_path, mea_path, seg_ends, n_phonemes):
+    """Where two alignments of one lattice - the best path and the path of ``ctc_mea_path`` - differ, per segment that
+    ``align()`` writes a line for (host only): (boundary_shift int64 [boundaries], differing float64 [n_seg]).
+
+    boundary_shift[k] belongs to frame b = ``boundary_frames(seg_ends, T)``[k]: with the cut of ``segment_boundary_shift``,
+    c = 2 min(best_path[b] // 2, n_phonemes), it is the first frame at which ``mea_path`` reaches c minus the first frame at
+    which ``best_path`` does (T for a path that never reaches it): positive where the posterior-decoded path crosses the text
+    boundary later.  differing[i] is the share of the segment's frames [a, b) (a = seg_ends[i-1], 0 for the first,
+    b = seg_ends[i], clipped to T) whose text index min(state // 2, n_phonemes) differs between the two paths; NaN for a
+    segment without frames."""
+    bp = np.asarray(best_path.detach().cpu() if _is_tensor(best_path) else best_path, dtype=np.int64).reshape(-1)
+    mp = np.asarray(mea_path.detach().cpu() if _is_tensor(mea_path) else mea_path, dtype=np.int64).reshape(-1)
+    T, n_ph = len(bp), int(n_phonemes)
+    if len(mp) != T:
+        raise ValueError("segment_path_disagreement: the two paths must have one position per frame")
+    frames = boundary_frames(seg_ends, T)
+    cuts = np.array([2 * min(int(bp[b]) // 2, n_ph) for b in frames], dtype=np.int64)
+    both = sampled_crossing_frames(np.stack([bp, mp]), cuts) if T else np.zeros((2, len(cuts)), np.int64)
+    differs = np.minimum(bp // 2, n_ph) != np.minimum(mp // 2, n_ph)
+    segs = _segments(np.asarray(seg_ends, dtype=np.int64), T)
+    share = np.full(len(segs), np.nan)
+    for i, a, b in segs:
+        if b > a:
+            share[i] = differs[a:b].mean()
+    return (both[1] - both[0]).astype(np.int64), share

@@ -6,7 +6,8 @@ posteriors at chosen frames, ka_state_posterior.hpp, section 4.19) with 200 quer
 state_single, state_b1024); and of ka_ctc_state_durations_batch_f32 (expected state durations, ka_duration.hpp, section 4.22)
 on the occupancy's shapes and terminals (cases dur_single, dur_b1024); and of ka_ctc_sample_paths_batch_f32 (64 alignments
 sampled from the band posterior per lattice, ka_sample.hpp, section 4.24) on the same shapes and terminals (cases smp_single,
-smp_b1024).
+smp_b1024); and of ka_ctc_mea_path_batch_f32 (the maximum-expected-accuracy alignment, ka_mea.hpp, section 4.26) on the same
+shapes and terminals (cases mea_single, mea_b1024).
 
     python tools/bench_posteriors.py [--cases single,b1024,b8192,corpus] [--reps 3] [--out profiles/posteriors.jsonl]
     python tools/bench_posteriors.py --cases state_single,state_b1024 --out profiles/state_posteriors_bench.jsonl
@@ -14,6 +15,8 @@ smp_b1024).
         --out profiles/duration_bench.jsonl
     python tools/bench_posteriors.py --cases occ_single,smp_single,occ_b1024,smp_b1024,occ_single,smp_single,occ_b1024,smp_b1024 \
         --out profiles/sample_bench.jsonl
+    python tools/bench_posteriors.py --out profiles/mea_bench.jsonl --cases \
+        occ_single,dur_single,mea_single,occ_b1024,dur_b1024,mea_b1024,occ_single,dur_single,mea_single,occ_b1024,dur_b1024,mea_b1024,occ_single,dur_single,mea_single,occ_b1024,dur_b1024,mea_b1024
 
 Device-resident inputs (hash-generated); best paths from the library's own best-path call.  The 8192 batch points its
 lattices at the 1024 batch's log-probs, labels and paths eight times over (distinct outputs): 105 GB of log-probs would
@@ -52,7 +55,7 @@ def best_paths(lps, labs):
 
 
 def time_batch(call_name, ws_name, lps, labs, own_args, reps, ws_own=()):
-    """ms per call of ka_ctc_<call_name>_batch_f32 on device buffers: the arguments the five calls share around
+    """ms per call of ka_ctc_<call_name>_batch_f32 on device buffers: the arguments the six calls share around
     ``own_args`` (the caller keeps what they point to alive), the workspace reserved first, one warm-up call."""
     name = f"ka_ctc_{call_name}_batch_f32"
     n, V = len(lps), int(lps[0].shape[1])
@@ -129,6 +132,14 @@ def time_samples(lps, labs, paths, reps, K=64):
                       reps, ws_own=(Ks.ctypes.data,))
 
 
+def time_mea(lps, labs, paths, reps):
+    outs = [torch.empty(int(x.shape[0]), dtype=torch.int32, device="cuda") for x in lps]
+    p_out = _ptr_array([x.data_ptr() for x in outs])
+    ea = np.zeros(len(lps), np.float64)
+    term = _i64_array(torch.stack([p[-1] for p in paths]).cpu().tolist())
+    return time_batch("mea_path", "ka_mea_path_workspace_bytes", lps, labs, (term[0], p_out[0], ea.ctypes.data), reps)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="single,b1024,b8192,corpus")
@@ -140,7 +151,7 @@ def main():
     cases = a.cases.split(",")
     b1024 = None
     for case in cases:
-        kind = case.split("_")[0] if case.startswith(("occ_", "state_", "dur_", "smp_")) else "path"
+        kind = case.split("_")[0] if case.startswith(("occ_", "state_", "dur_", "smp_", "mea_")) else "path"
         case_in = case[len(kind) + 1:] if kind != "path" else case
         if case_in == "single":
             lps, labs = cfg2(1)
@@ -161,7 +172,8 @@ def main():
             raise SystemExit(f"unknown case {case}")
         if case_in in ("single", "corpus"):
             paths = best_paths(lps, labs)
-        ms, st, ll = {"path": time_posteriors, "occ": time_occupancy, "state": time_states, "dur": time_durations, "smp": time_samples}[kind](lps, labs, paths, a.reps)
+        ms, st, ll = {"path": time_posteriors, "occ": time_occupancy, "state": time_states, "dur": time_durations, "smp": time_samples,
+                       "mea": time_mea}[kind](lps, labs, paths, a.reps)
         frames = sum(int(x.shape[0]) for x in lps)
         line = dict(case=case, lattices=len(lps), frames=frames, ms_min=round(min(ms), 3), ms_median=round(float(np.median(ms)), 3),
                     frames_per_s=frames / (min(ms) / 1e3), status_ok=int((st == 0).sum()), reps=a.reps)
