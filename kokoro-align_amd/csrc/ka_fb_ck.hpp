@@ -223,7 +223,7 @@ void launch_fb_ck(const FbCkKernel<Desc> (&fast)[4], FbCkKernel<Desc> generic, c
     }
     if (n_generic > 0) {
         const dim3 grid(n_generic < kOccGenericSlots ? n_generic : kOccGenericSlots);
-        hipLaunchKernelGGL(generic, grid, dim3(FbGen::NT), 0, s, lats + n_fast, n_generic, res);
+        hipLaunchKernelGGL(generic, grid, dim3(FbGen<>::NT), 0, s, lats + n_fast, n_generic, res);
     }
 }
 

@@ -1,5 +1,6 @@
-// ka_fb_form.hpp — the two forms of the checkpointed forward-backward (ka_fb_ck.hpp) as a policy: FbFast<M> and FbGen own
-// what differs between a one-wavefront and a workgroup pass, and every layer above them is written once.
+// ka_fb_form.hpp — the two forms of the forward-backward as a policy: FbFast<M> and FbGen own what differs between a
+// one-wavefront and a workgroup pass, and every layer above them is written once: the checkpointed pass of ka_fb_ck.hpp on an
+// FbCkLattice (the default descriptor) and the path-posterior kernel of ka_posterior.hpp on a PostLattice.
 //                      FbFast<M>: band <= kFastMaxBand, V <= 64, M = max_move <= 4    FbGen: any band, any V, max_move <= 255
 //   threads            NT = 64, one wavefront (kWave)                                 NT = 256
 //   sync()             post_wave_sync                                                 __syncthreads
@@ -12,30 +13,107 @@
 //   row_prefetch(t),   a float of row t per lane, loaded a frame ahead; row() puts    nothing; row() points at d.lp + t ld, read
 //   row(t, tn, more)   it into LDS in log2 units and loads row tn if `more`           in place
 //   row(..., true)     returns the bad bits of the prefetched value                   returns those of a strided loop over the row
-//   fwd, bwd           fb_fast_fwd<M>, fb_fast_bwd<M>                                 fb_gen_fwd, fb_gen_bwd
+//   lab                the label source, LabDirect or LabRing (below)                 LabDirect
+//   fwd, bwd           fb_fast_fwd<M>, fb_fast_bwd<M> with lab as their lab_at        fb_gen_fwd, fb_gen_bwd
+// slot, cw, ck_store and ck_load touch what only an FbCkLattice has; like every member of a class template they are compiled
+// where they are called, so a form on a PostLattice does without them.
 // A form is built per lattice from the kernel's `__shared__ typename Form::template Shared<N>` (N working columns).  The
-// recurrences stay the two pairs of ka_posterior_common.hpp, which the path-posterior kernels (ka_posterior.hpp) call directly:
-// they sum their log-sum-exp terms in differently written loops, and a form's outputs keep the bits they have.
+// recurrences stay the two pairs of ka_posterior_common.hpp: they sum their log-sum-exp terms in differently written loops,
+// and a form's outputs keep the bits they have.
 #pragma once
 #include "ka_posterior_common.hpp"
 
 namespace ka {
 
-template <int M>
+// Where a cell's label comes from: a member `lab` of the form, called as lab(p), with a hook at every place of a pass where a
+// source that runs ahead of the band has work to do.  LabDirect reads the label where it lies; its hooks are empty.
+struct LabDirect {
+    struct Store {};
+    const FbLattice &d;
+    __device__ __forceinline__ LabDirect(const FbLattice &d_, Store &) : d(d_) {}
+    __device__ __forceinline__ int32_t operator()(int64_t p) const { return fb_lab(d, p); }
+    __device__ __forceinline__ void fill() {}
+    __device__ __forceinline__ void fwd_request(int64_t) {}
+    __device__ __forceinline__ void fwd_commit() {}
+    __device__ __forceinline__ void turn(int64_t) {}
+    __device__ __forceinline__ void bwd_request(int64_t, bool) {}
+    __device__ __forceinline__ void bwd_commit() {}
+};
+// LabRing (fast form only): the labels of 1024 consecutive positions in LDS, position p at slot p & 1023, refilled as the band
+// slides: [lfill - 1024, lfill) on the way forward, [lbot, lbot + 1024) on the way back.  A frame asks for what the next
+// frame's band needs before its own fence (64 global loads, a frame ahead of their use) and stores it after its cells; a band
+// that moved more than 64 positions (L > 64 T) is caught up with in the commit.
+struct LabRing {
+    struct Store {
+        int32_t ring[1024];
+    };
+    const FbLattice &d;
+    int32_t *const ring;
+    int64_t lfill, lbot;
+    int64_t want, np;   // the request in flight: the end the ring has to reach, this lane's position
+    int32_t nlab;       // and its label
+    __device__ __forceinline__ LabRing(const FbLattice &d_, Store &st) : d(d_), ring(st.ring), lfill(0), lbot(0), want(0), np(0), nlab(0) {}
+    __device__ __forceinline__ int32_t operator()(int64_t p) const { return ring[p & 1023]; }
+
+    __device__ __forceinline__ void fill()   // before frame 0
+    {
+        lfill = d.L < 1024 ? d.L : 1024;
+        for (int64_t p = threadIdx.x; p < lfill; p += 64) ring[p] = fb_lab(d, p);
+    }
+    __device__ __forceinline__ void fwd_request(int64_t lon)   // lon: the low end of the next frame's band
+    {
+        want = (lon + 1024 < d.L) ? lon + 1024 : d.L;
+        np = lfill + threadIdx.x;
+        nlab = np < want ? fb_lab(d, np) : 0;
+    }
+    __device__ __forceinline__ void fwd_commit()
+    {
+        if (np < want) ring[np & 1023] = nlab;
+        lfill = (lfill + 64 < want) ? lfill + 64 : (want > lfill ? want : lfill);
+        for (int64_t p = lfill + threadIdx.x; lfill < want; p = lfill + threadIdx.x) {
+            if (p < want) ring[p & 1023] = fb_lab(d, p);
+            lfill = (lfill + 64 < want) ? lfill + 64 : want;
+        }
+    }
+    __device__ __forceinline__ void turn(int64_t lo)   // between the passes; lo: the low end of frame T-1's band, which must be in
+    {
+        lbot = lfill - 1024 > 0 ? lfill - 1024 : 0;
+        for (int64_t p = lo + threadIdx.x; p < lbot && p < lo + 1024; p += 64) ring[p & 1023] = fb_lab(d, p);
+        if (lo < lbot) lbot = lo;
+    }
+    __device__ __forceinline__ void bwd_request(int64_t lon, bool more)   // lon: the low end of the previous frame's band, if `more`
+    {
+        want = more ? lon : lbot;
+        np = lbot - 1 - threadIdx.x;
+        nlab = np >= want ? fb_lab(d, np) : 0;
+    }
+    __device__ __forceinline__ void bwd_commit()
+    {
+        if (np >= want) ring[np & 1023] = nlab;
+        lbot = (lbot - 64 > want) ? lbot - 64 : (want < lbot ? want : lbot);
+        for (int64_t p = lbot - 1 - threadIdx.x; lbot > want; p = lbot - 1 - threadIdx.x) {
+            if (p >= want) ring[p & 1023] = fb_lab(d, p);
+            lbot = (lbot - 64 > want) ? lbot - 64 : want;
+        }
+    }
+};
+
+template <int M, class Desc = FbCkLattice, class Lab = LabDirect>
 struct FbFast {
     static constexpr int NT = 64, kMoves = M;
     static constexpr bool kWave = true;
     template <int N>
-    struct Shared {
+    struct Shared : Lab::Store {   // (an empty Store adds no byte)
         double col[N][1024];
         double row[64];
     };
-    const FbCkLattice &d;
+    const Desc &d;
     double (*const cols)[1024];
     double *const lds_row;
     float rv;   // this lane's entry of the prefetched row
+    Lab lab;
     template <int N>
-    __device__ __forceinline__ FbFast(const FbCkLattice &d_, Shared<N> &sh) : d(d_), cols(sh.col), lds_row(sh.row), rv(0.0f) {}
+    __device__ __forceinline__ FbFast(const Desc &d_, Shared<N> &sh) : d(d_), cols(sh.col), lds_row(sh.row), rv(0.0f), lab(d_, sh) {}
 
     __device__ __forceinline__ void sync() const { post_wave_sync(); }
     __device__ __forceinline__ void fence() const { post_wave_sync(); }
@@ -76,31 +154,32 @@ struct FbFast {
     __device__ __forceinline__ double fwd(int64_t lo, int64_t hi, int64_t plo, int64_t phi, const double *prev, double *cur, double mprev,
                                           Cell cell) const
     {
-        return fb_fast_fwd<M>(lo, hi, plo, phi, prev, cur, lds_row, mprev, [this](int64_t p) { return fb_lab(d, p); }, cell);
+        return fb_fast_fwd<M>(lo, hi, plo, phi, prev, cur, lds_row, mprev, lab, cell);
     }
     template <class Cell>
     __device__ __forceinline__ double bwd(int64_t lo, int64_t hi, int64_t nlo, int64_t nhi, const double *gn, const double *vn, double *gc,
                                           double *vc, double nprev, bool last, int64_t sstar, Cell cell) const
     {
-        return fb_fast_bwd<M>(lo, hi, nlo, nhi, gn, vn, gc, vc, lds_row, nprev, last, sstar, [this](int64_t p) { return fb_lab(d, p); },
-                              cell);
+        return fb_fast_bwd<M>(lo, hi, nlo, nhi, gn, vn, gc, vc, lds_row, nprev, last, sstar, lab, cell);
     }
 };
 
 // A correctness path, not tuned.
+template <class Desc = FbCkLattice>
 struct FbGen {
     static constexpr int NT = 256;
     static constexpr bool kWave = false;
     template <int N>
-    struct Shared {
+    struct Shared : LabDirect::Store {
         double red[2][4];
     };
-    const FbCkLattice &d;
+    const Desc &d;
     double (*const red)[4];
     int ph;              // parity of the reduction slots
     const float *lrow;   // the frame's log-prob row
+    LabDirect lab;       // (the recurrences read fb_lab themselves; here for its hooks)
     template <int N>
-    __device__ __forceinline__ FbGen(const FbCkLattice &d_, Shared<N> &sh) : d(d_), red(sh.red), ph(0), lrow(nullptr) {}
+    __device__ __forceinline__ FbGen(const Desc &d_, Shared<N> &sh) : d(d_), red(sh.red), ph(0), lrow(nullptr), lab(d_, sh) {}
 
     __device__ __forceinline__ void sync() const { __syncthreads(); }
     __device__ __forceinline__ void fence() const {}

@@ -5,17 +5,16 @@
 
 namespace ka {
 
+// descriptors [0, n_fast) in the fast form (fast[M - 1], M = max_move, 4 above 3), then n_generic in the generic form; one
+// workgroup per lattice
 void launch_posteriors(const PostLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
 {
-    if (n_fast > 0) {
-        switch (max_move) {
-        case 1: hipLaunchKernelGGL(posterior_fast_kernel<1>, dim3(n_fast), dim3(64), 0, s, lats, res); break;
-        case 2: hipLaunchKernelGGL(posterior_fast_kernel<2>, dim3(n_fast), dim3(64), 0, s, lats, res); break;
-        case 3: hipLaunchKernelGGL(posterior_fast_kernel<3>, dim3(n_fast), dim3(64), 0, s, lats, res); break;
-        default: hipLaunchKernelGGL(posterior_fast_kernel<4>, dim3(n_fast), dim3(64), 0, s, lats, res); break;
-        }
-    }
-    if (n_generic > 0) hipLaunchKernelGGL(posterior_generic_kernel, dim3(n_generic), dim3(256), 0, s, lats + n_fast, res);
+    using Kernel = void (*)(const PostLattice *, PostResult *);
+    static constexpr Kernel fast[4] = {posterior_kernel<PostFast<1>>, posterior_kernel<PostFast<2>>, posterior_kernel<PostFast<3>>,
+                                       posterior_kernel<PostFast<4>>};
+    if (n_fast > 0)
+        hipLaunchKernelGGL(fast[(max_move >= 1 && max_move <= 3 ? max_move : 4) - 1], dim3(n_fast), dim3(PostFast<1>::NT), 0, s, lats, res);
+    if (n_generic > 0) hipLaunchKernelGGL(posterior_kernel<PostGen>, dim3(n_generic), dim3(PostGen::NT), 0, s, lats + n_fast, res);
 }
 
 }  // namespace ka

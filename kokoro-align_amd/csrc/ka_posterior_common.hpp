@@ -1,11 +1,11 @@
-// ka_posterior_common.hpp — the forward-backward core under all five calls: ka_posterior.hpp (best-path posteriors) uses it
-// directly, ka_fb_ck.hpp (the checkpointed pass of label occupancy, state posteriors, state durations and sampled paths)
-// through the form policy of ka_fb_form.hpp.  Base-2 log-sum-exp, the band and its walk, status flags, wave and block
-// reductions, and the frame recurrences themselves, one forward and one backward per form (fb_fast_fwd / fb_fast_bwd,
+// ka_posterior_common.hpp — the forward-backward core under all six calls, which reach it through the form policy of
+// ka_fb_form.hpp: ka_posterior.hpp (best-path posteriors) and ka_fb_ck.hpp (the checkpointed pass of label occupancy, state
+// posteriors, state durations, sampled paths and the MEA path).  Base-2 log-sum-exp, the band and its walk, status flags, wave
+// and block reductions, and the frame recurrences themselves, one forward and one backward per form (fb_fast_fwd / fb_fast_bwd,
 // fb_gen_fwd / fb_gen_bwd), which FbFast<M> and FbGen wrap as their fwd / bwd.
-// The callers differ only in where a cell's label comes from and what they do with a cell once it is computed; both are
-// template arguments, so each recurrence exists once and every caller runs the same expressions on the same operands.  What
-// a call does with a finished cell of the checkpointed pass is its Out policy's business (ka_fb_ck.hpp).
+// The callers differ only in where a cell's label comes from (the form's label policy) and what they do with a cell once it is
+// computed; both are template arguments, so each recurrence exists once and every caller runs the same expressions on the same
+// operands.  What a call does with a finished cell of the checkpointed pass is its Out policy's business (ka_fb_ck.hpp).
 #pragma once
 #include "ka_types.hpp"
 

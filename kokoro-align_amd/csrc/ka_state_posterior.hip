@@ -9,7 +9,7 @@ void launch_state_posteriors(const StateLattice *lats, int n_fast, int n_generic
 {
     launch_fb_ck<StateLattice>({state_posterior_kernel<FbFast<1>>, state_posterior_kernel<FbFast<2>>, state_posterior_kernel<FbFast<3>>,
                                 state_posterior_kernel<FbFast<4>>},
-                               state_posterior_kernel<FbGen>, lats, n_fast, n_generic, max_move, res, s);
+                               state_posterior_kernel<FbGen<>>, lats, n_fast, n_generic, max_move, res, s);
 }
 
 }  // namespace ka

@@ -6,8 +6,7 @@ follows a longer one, a wider one, one that failed (NaN, bad label, zero mass) a
 none of the blocks it asks for, or all but those.  Every lattice's outputs and Z must have the bits of the same lattice
 sent alone, and one lattice of every kind must match the float64 reference per cell (posterior_ref.*_ratio).
 
-The path-posterior launch walks no slots: posterior_fast_kernel and posterior_generic_kernel take lats[blockIdx.x], one
-workgroup per lattice, and plan::posterior_workspace carves offsets and columns per lattice.  The same batches go through
+The path-posterior launch walks no slots: posterior_kernel<Form> takes lats[blockIdx.x], one workgroup per lattice, and plan::posterior_workspace carves offsets and columns per lattice.  The same batches go through
 it all the same, so that more than 1024 workgroups of it have run once, and are held to the same bit-equality."""
 import numpy as np
 import pytest

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import posterior_ref as R
-from fb_harness import engine, path_call as _call, record
+from fb_harness import engine, path_call as _call, record, tiny
 from golden_util import g1_cases, g2_cases, g3_case
 from oracle import oracle as O
 
@@ -211,3 +211,33 @@ def test_best_path_bits_unchanged_by_a_posterior_call(env):
         after = ka.ctc_best_path(lp, labels, beam_size=beam, max_move=mm, verbose=False)
         for b, a in zip(before, after):
             assert np.array_equal(b.view(np.int32), a.view(np.int32))
+
+
+@pytest.mark.parametrize("V", [39, 80])
+@pytest.mark.parametrize("beam", [64, 1009])
+def test_band_that_jumps_past_the_label_ring_beside_neighbours(env, beam, V):
+    """L = 1201 over T = 16: the band moves 75 positions a frame, more than the 64 labels a frame's request brings into the
+    fast form's ring, so the ring's catch-up loop runs (V = 80 takes the generic form, which has no ring).  Such a band outruns
+    every path (at most 3 positions a frame), so the lattice can only answer zero mass; its neighbours in the launch must be
+    what they are alone."""
+    ka, _lib, eng = env
+    mm = 4
+    rng = np.random.default_rng(1201)
+    lats = [tiny(rng, 40, 12, 39), R.sloped(16, 600, 39, 1201), tiny(rng, 40, 12, 39)]
+    paths = []
+    for k, (lp, labels) in enumerate(lats):
+        T, L = lp.shape[0], 2 * len(labels) + 1
+        path = np.minimum(L - 1, (L * np.arange(T)) // T).astype(np.int32)
+        if k != 1:
+            path[-1] = R.live_terminals(lp, labels, beam, mm)[0]
+        paths.append(path)
+    assert R.forward_backward(*lats[1], paths[1], beam, mm)["status"] == R.ZERO_MASS == -9
+    lps = [R.pad_vocabulary(lp, V) if V != 39 else lp for lp, _ in lats]
+    posts, ll, st, rc = _call(eng, _lib, lps, [labels for _, labels in lats], paths, beam, mm)
+    assert st.tolist() == [0, -9, 0] and rc == -9
+    assert np.isnan(posts[1]).all() and ll[1] == -np.inf
+    for k in (0, 2):
+        ref = R.forward_backward(*lats[k], paths[k], beam, mm)
+        assert ref["status"] == R.OK
+        record("path", R.path_ratio(posts[k], ref, k), R.M_PATH)
+        record("z", R.z_ratio(ll[k], ref), R.M_Z)

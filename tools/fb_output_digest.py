@@ -1,15 +1,16 @@
 #!/usr/bin/env python3
-"""One SHA-256 per (case, call) over what the five forward-backward calls write: the output bytes, then the log-likelihood and
+"""One SHA-256 per (case, call) over what the six forward-backward calls write: the output bytes, then the log-likelihood and
 status bytes.  For a change of the kernels that must not move a bit: run it on the library before and after and diff.
 
     python tools/fb_output_digest.py [--library path/to/libkokoro_align_amd.so] > digest.txt
 
-The calls go through the raw ctypes callers of tests/fb_harness.py, tests/duration_harness.py and tests/sample_harness.py:
-path posteriors, label occupancy, state posteriors at posterior_ref.query_frames(T), durations with time_sum, and 64 sampled
-paths with a fixed seed.  The cases are the smallest at which a slot mapping, a checkpoint extent or a block boundary can go
-wrong: every case of posterior_ref.edge_cases(), the one-wavefront ones once more in the generic form (V padded to 80), tiny
-lattices round the 32-frame block, every max_move with a label 0 and a -inf, a band that jumps (L > T), the bands on either
-side of the form boundary, and one batch per form with more lattices than the form has slots."""
+The calls go through the raw ctypes callers of tests/fb_harness.py, tests/duration_harness.py, tests/sample_harness.py and
+tests/mea_harness.py: path posteriors, label occupancy, state posteriors at posterior_ref.query_frames(T), durations with
+time_sum, 64 sampled paths with a fixed seed, and the maximum-expected-accuracy path with its expected accuracy.  The cases
+are the smallest at which a slot mapping, a checkpoint extent or a block boundary can go wrong: every case of posterior_ref.edge_cases(), the one-wavefront ones once more in the generic form (V padded to 80), tiny
+lattices round the 32-frame block, every max_move with a label 0 and a -inf, a band that jumps (L > T), one that jumps more
+than 64 positions a frame (L > 64 T: past the label ring's request; every call answers zero mass), the bands on either side of
+the form boundary, and one batch per form with more lattices than the form has slots."""
 import argparse
 import hashlib
 import os
@@ -48,6 +49,9 @@ def cases(R, H):
     lp, labels = R.sloped(60, 70, 39, SEED)
     one("jumping_band", lp, labels, 16, 4)
     one("jumping_band_as_V80", R.pad_vocabulary(lp, 80), labels, 16, 4)
+    lp, labels = R.sloped(16, 600, 39, 1201)
+    one("ring_jump", lp, labels, 64, 4)
+    one("ring_jump_as_V80", R.pad_vocabulary(lp, 80), labels, 64, 4)
     lp, labels = R.sloped(400, 520, 39, SEED + 1)
     for beam in (1009, 1010):
         one("band_%d" % beam, lp, labels, beam, 4)
@@ -75,6 +79,7 @@ def main():
         os.environ["KA_LIBRARY"] = os.path.abspath(a.library)      # (read when the package is imported)
     import duration_harness as D
     import fb_harness as H
+    import mea_harness as M
     import posterior_ref as R
     import sample_harness as S
     _, _lib, eng = H.engine()
@@ -92,6 +97,8 @@ def main():
         results["durations"] = (durs + sums, ll, st)
         paths, ll, st, _ = S.sample_call(eng, _lib, lps, labs, terms, SAMPLES, SEED, beam, mm)
         results["samples"] = (paths, ll, st)
+        paths, ea, ll, st, _ = M.mea_call(eng, _lib, lps, labs, terms, beam, mm)
+        results["mea"] = (paths + [ea], ll, st)
         for call, (outs, ll, st) in results.items():
             h = hashlib.sha256()
             for x in list(outs) + [ll, st]:
