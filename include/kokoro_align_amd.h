@@ -227,6 +227,40 @@ size_t ka_state_duration_workspace_bytes(int32_t n, const int64_t *T, const int6
                                          int32_t max_move, int32_t mem);
 
 /*
+ * State visit probabilities and the lattice log-likelihood of a terminal: on the lattice of
+ * ka_ctc_label_posteriors (same band [lo_t, hi_t), moves j in [0, max_move), label-0 veto, terminal s*, statuses and Z), per
+ * POSITION of the blank-expanded labels, with exit_t(s) = P(state_t = s and (t = T-1 or state_{t+1} != s)) = gamma_t(s) r_t(s):
+ *   visit[s]     = V(s) = sum over t of exit_t(s)     the probability that the path passes through s (paths only move up, so a
+ *                                                     position is left once or never: V(s) is in [0, 1])
+ *   exit_time[s] = X(s) = sum over t of t exit_t(s)   X / V: the expected LAST frame of s, given that it is visited
+ * gamma_t(s) is the float the state posteriors write, widened to double.  r_t(s) is the share of the backward recurrence's
+ * log-sum-exp at (t, s) that does not come from the stay j = 0; with x_j the recurrence's terms (-inf for s+j outside band t+1
+ * or a vetoed move): r = 1 at t = T-1; r = 1 exactly when x_0 is -inf; r = 0 exactly when no x_j with j >= 1 is finite;
+ * otherwise r = 1 - 2^(x_0 - lse_j x_j) in float64, clamped to [0, 1].  A cell with gamma = 0 adds exactly 0.0.  A position
+ * receives one float64 add per frame whose band holds it, in descending frame order, as the durations do; so visit[s*] = 1.0,
+ * visit[s] = 0.0 for s > s* and for a position no band holds, 0 <= visit[s] <= duration[s] and exit_time[s] <= time_sum[s]
+ * against ka_ctc_state_durations on the same input without any tolerance, and visit[s] has the bits of duration[s] for a
+ * position that a single frame's band holds.  The expected first frame follows from the two calls: E[first; visited] =
+ * X - D + V.  Arguments as ka_ctc_state_durations[_batch]_f32, with in place of duration and time_sum
+ *   visit           [2S+1] float64 output (where `mem` says)
+ *   exit_time       [2S+1] float64 output (where `mem` says); may be NULL (batch: the array, or any of its entries)
+ * Per lattice: statuses as ka_ctc_label_posteriors, with NaN over [0, 2S+1) for a failed lattice; nothing is written beyond
+ * [0, 2S+1).  Resources as the state durations' (50 KB of LDS, three workgroups per CU); measured at 1.05 (1024 lattices) to
+ * 1.08 (one lattice) times a state-duration call.
+ */
+int ka_ctc_state_visits_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                            int32_t beam_size, int32_t max_move, int64_t terminal, double *visit, double *exit_time,
+                            double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_state_visits_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                  const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                  int32_t max_move, const int64_t *terminal, double *const *visit, double *const *exit_time,
+                                  double *log_likelihood, int32_t *status, int32_t mem, void *stream);
+/* device-workspace bytes such a call carves (0 for unsupported arguments); bounded by the lattices resident at once (and, for
+ * KA_MEM_HOST, the staged inputs and outputs of every lattice) */
+size_t ka_state_visit_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                      int32_t mem);
+
+/*
  * Alignments sampled from the band posterior, and the lattice log-likelihood of a terminal: forward
  * filter, backward sample on the lattice of ka_ctc_label_posteriors (same band [lo_t, hi_t), moves j in [0, max_move), label-0
  * veto, terminal s*, statuses and Z).  With u_t(s) the forward value and lab' the blank-expanded labels, sample k is the path

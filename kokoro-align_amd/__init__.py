@@ -14,7 +14,9 @@ every state with the expected frame of every boundary (ctc_state_durations[_batc
 expected_crossing_frames, segment_boundary_shift), and whole alignments sampled from the posterior over the band's paths with
 the spread of every boundary (ctc_sample_paths[_batch|_device], sampled_crossing_frames, segment_boundary_spread), and the
 alignment with the most frames at the right state in expectation (ctc_mea_path[_batch|_device], path_outputs,
-segment_path_disagreement).
+segment_path_disagreement), and the probability that the path passes through every phoneme at all, the soft form of the
+reference's keep-or-drop test of a segment (ctc_state_visits[_batch|_device], phoneme_visits, phoneme_spans,
+segment_expected_match).
 
 The DP and backtrace run in the HIP C-ABI library (include/kokoro_align_amd.h); there is no
 CPU fallback — importing works without a GPU, computing does not.
@@ -49,16 +51,22 @@ from .posteriors import (  # noqa: F401
     ctc_state_posteriors,
     ctc_state_posteriors_batch,
     ctc_state_posteriors_device,
+    ctc_state_visits,
+    ctc_state_visits_batch,
+    ctc_state_visits_device,
     expected_crossing_frames,
     lattice_log_likelihood,
     path_outputs,
     phoneme_durations,
+    phoneme_spans,
+    phoneme_visits,
     sampled_crossing_frames,
     segment_agreement,
     segment_boundary_confidence,
     segment_boundary_shift,
     segment_boundary_spread,
     segment_confidence,
+    segment_expected_match,
     segment_path_disagreement,
 )
 from ._lib import KAError, build_library, library_path, load_library  # noqa: F401

@@ -42,6 +42,7 @@ EXPORTS = [
     "ka_ctc_state_posteriors_f32", "ka_ctc_state_posteriors_batch_f32", "ka_state_posterior_workspace_bytes",
     "ka_ctc_state_durations_f32", "ka_ctc_state_durations_batch_f32", "ka_state_duration_workspace_bytes",
     "ka_ctc_sample_paths_f32", "ka_ctc_sample_paths_batch_f32", "ka_sample_paths_workspace_bytes",
+    "ka_ctc_state_visits_f32", "ka_ctc_state_visits_batch_f32", "ka_state_visit_workspace_bytes",
     "ka_ctc_mea_path_f32", "ka_ctc_mea_path_batch_f32", "ka_mea_path_workspace_bytes",
 ]
 
@@ -128,6 +129,12 @@ def load_library():
     L.ka_ctc_state_durations_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pi64, pp, pp, vp, vp, i32, vp]
     L.ka_state_duration_workspace_bytes.restype = sz
     L.ka_state_duration_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
+    L.ka_ctc_state_visits_f32.restype = ctypes.c_int
+    L.ka_ctc_state_visits_f32.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i64, vp, vp, vp, i32, vp]
+    L.ka_ctc_state_visits_batch_f32.restype = ctypes.c_int
+    L.ka_ctc_state_visits_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pi64, pp, pp, vp, vp, i32, vp]
+    L.ka_state_visit_workspace_bytes.restype = sz
+    L.ka_state_visit_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
     L.ka_ctc_sample_paths_f32.restype = ctypes.c_int
     L.ka_ctc_sample_paths_f32.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i64, i32, u64, vp, i64, vp, i32, vp]
     L.ka_ctc_sample_paths_batch_f32.restype = ctypes.c_int

@@ -1,6 +1,7 @@
 // ka_engine_fb.hip — the forward-backward calls of the C ABI: best-path posteriors (ka_posterior.hpp), label occupancy
 // (ka_occupancy.hpp), state posteriors at chosen frames (ka_state_posterior.hpp), expected state durations (ka_duration.hpp),
-// alignments sampled from the band posterior (ka_sample.hpp) and the maximum-expected-accuracy alignment (ka_mea.hpp).  Host
+// state visit probabilities (ka_visit.hpp), alignments sampled from the band posterior (ka_sample.hpp) and the
+// maximum-expected-accuracy alignment (ka_mea.hpp).  Host
 // code only.
 // They use the engine's workspace and pinned buffer, with their own kernels and workspace layout, whatever
 // the engine's mode, and run to the end inside the call: no batch stays in flight.
@@ -16,7 +17,7 @@ using ka::plan::align_up;
 
 // ---- best-path posteriors (ka_posterior.hpp), label occupancy (ka_occupancy.hpp), state posteriors at chosen frames
 // (ka_state_posterior.hpp) and expected state durations (ka_duration.hpp): their own kernels and workspace layout, whatever the
-// engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall, DurCall, SampleCall, MeaCall) brings what
+// engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall, DurCall, VisitCall, SampleCall, MeaCall) brings what
 // differs: its own arrays and their
 // checks, its planner and launch, the descriptor fields beyond FbLattice, its own staging (upload: host buffers only;
 // stage: every memory mode), and what two statuses mean.
@@ -221,6 +222,44 @@ struct DurCall {
         const size_t bytes = (size_t)(2 * a.S[i] + 1) * sizeof(double);
         KA_HIP(hipMemcpyAsync(duration[i], ws + c.dur, bytes, hipMemcpyDeviceToHost, a.stream));
         if (moment(i)) KA_HIP(hipMemcpyAsync(time_sum[i], ws + c.tsum, bytes, hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
+struct VisitCall {
+    using Desc = ka::VisitLattice;
+    using Carve = ka::plan::VisitCarve;
+    static constexpr const char *kName = "state visits";
+    static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score reaches the terminal";
+    const int64_t *terminal;
+    double *const *visit;
+    double *const *exit_time;   // NULL, or an array in which any entry may be NULL: no time moment for that lattice
+
+    bool arrays() const { return terminal && visit; }
+    const char *bad_lattice(const FbArgs &, int32_t) const { return nullptr; }
+    bool buffers(int32_t i) const { return visit[i] != nullptr; }
+    bool moment(int32_t i) const { return exit_time && exit_time[i]; }
+    static constexpr auto plan = ka::plan::state_visit_workspace;
+    static constexpr auto launch = ka::launch_state_visits;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (a.mem == KA_MEM_HOST) {
+            d.visit = reinterpret_cast<double *>(ws + c.visit);
+            d.xtime = moment(i) ? reinterpret_cast<double *>(ws + c.xtime) : nullptr;
+        } else {
+            d.visit = visit[i];
+            d.xtime = moment(i) ? exit_time[i] : nullptr;
+        }
+        fill_slot(d, c, terminal[i], ws);
+    }
+    int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int stage(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        const size_t bytes = (size_t)(2 * a.S[i] + 1) * sizeof(double);
+        KA_HIP(hipMemcpyAsync(visit[i], ws + c.visit, bytes, hipMemcpyDeviceToHost, a.stream));
+        if (moment(i)) KA_HIP(hipMemcpyAsync(exit_time[i], ws + c.xtime, bytes, hipMemcpyDeviceToHost, a.stream));
         return KA_OK;
     }
 };
@@ -513,6 +552,29 @@ size_t ka_state_duration_workspace_bytes(int32_t n, const int64_t *T, const int6
 {
     if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
     return ka::plan::state_duration_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+int ka_ctc_state_visits_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                  const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                  const int64_t *terminal, double *const *visit, double *const *exit_time, double *log_likelihood,
+                                  int32_t *status, int32_t mem, void *stream)
+{
+    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+                   VisitCall{terminal, visit, exit_time});
+}
+
+int ka_ctc_state_visits_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                            int32_t beam_size, int32_t max_move, int64_t terminal, double *visit, double *exit_time, double *log_likelihood,
+                            int32_t mem, void *stream)
+{
+    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+                   VisitCall{&terminal, &visit, &exit_time});
+}
+
+size_t ka_state_visit_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::state_visit_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
 int ka_ctc_sample_paths_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,

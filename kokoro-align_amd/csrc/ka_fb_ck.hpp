@@ -1,7 +1,8 @@
 // ka_fb_ck.hpp — the checkpointed forward-backward that ka_occupancy.hpp (label occupancy), ka_state_posterior.hpp (state
-// posteriors at chosen frames) and ka_duration.hpp (expected state durations) share, and whose forward half ka_sample.hpp
-// (sampled alignments) reuses: fb_ck_forward<Form>, fb_ck_recompute<Form> and the driver fb_ck<Form, Out>, each written once
-// over two policies, and the launch of the four calls' kernels.
+// posteriors at chosen frames), ka_duration.hpp (expected state durations), ka_mea.hpp (the MEA path) and ka_visit.hpp (state
+// visit probabilities) share, and whose forward half ka_sample.hpp (sampled alignments) reuses: fb_ck_forward<Form>,
+// fb_ck_recompute<Form> and the driver fb_ck<Form, Out>, each written once over two policies, and the launch of the calls'
+// kernels.
 //
 // The posterior kernels keep alpha only at the path; these calls need it at band cells, so the forward pass checkpoints the
 // whole column before the first frame of every 32-frame block (with the offset C and the frame maximum m it runs on), and the
@@ -20,6 +21,10 @@
 //                                recompute would have left it; beta is still stepped through every frame)
 //   cells(t, lo)                 frame t's action on a cell's gamma: a callable (p, lab, arg), arg() the log2 argument, formed
 //                                only when called (asked for once a frame, before the frame's first cell and the fence in front of it)
+//   kNextColumn, next_column(gn, vn, nprev, last)   opt-in, for a call that looks at a pair of frames: an Out that declares
+//                                kNextColumn is handed, before cells(t, lo), the column of frame t + 1 as the recurrence is about
+//                                to read it (G_{t+1}, its vetoable copy, the maximum taken off its log-sum-exp; last: t = T-1, no
+//                                such column), and its cells are called as (p, lab, w, arg), w the recurrence's value
 //   cells_done(), frame_end(t, lo, hi)   after the frame's cells (before its reduction), and after its bookkeeping (before the
 //                                fast form's end-of-frame fence); a hook owns any barrier or fence that only its kernel needs
 // An Out is templated on the form: it branches on Form::kWave where the forms really differ (an LDS ring or the outputs
@@ -28,9 +33,17 @@
 // Storage: lattices walk slots (launch grid = slots, lattice i on slot i mod grid), so the workspace is bounded by the slots,
 // not by the batch.
 #pragma once
+#include <type_traits>
+
 #include "ka_fb_form.hpp"
 
 namespace ka {
+
+// does an Out opt into the next column (kNextColumn, above)?
+template <class Out, class = void>
+struct fb_next_column : std::false_type {};
+template <class Out>
+struct fb_next_column<Out, std::void_t<decltype(Out::kNextColumn)>> : std::true_type {};
 
 // one cell's gamma as a float from its log2 argument (occ_fix of ka_occupancy.hpp before the fixed-point step): what the state
 // posteriors write and the state durations add
@@ -143,7 +156,7 @@ __device__ __forceinline__ void fb_ck_recompute(Form &f, int64_t k, int64_t t0, 
     if (!Form::kWave) f.sync();
 }
 
-// The driver of the three calls that need gamma; cav: kPostCk doubles of LDS, the offsets of the block's frames.
+// The driver of the calls that need gamma; cav: kPostCk doubles of LDS, the offsets of the block's frames.
 template <class Form, class Out>
 __device__ __forceinline__ void fb_ck(Form &f, PostResult *res, double *cav, Out &out)
 {
@@ -184,10 +197,15 @@ __device__ __forceinline__ void fb_ck(Form &f, PostResult *res, double *cav, Out
             f.row(t, t - 1, t > t0);
             const double ca = cav[t - t0];
             const double *al = d.slab + (t - t0) * f.cw();
+            if constexpr (fb_next_column<Out>::value) out.next_column(gn, vn, nprev, t == T - 1);
             auto cell = out.cells(t, lo);
             f.fence();
             const double mymax = f.bwd(lo, hi, nlo, nhi, gn, vn, gc, vc, nprev, t == T - 1, sstar, [&](int64_t p, int32_t lab, double w) {
-                cell(p, lab, [&] { return ((ca + al[Form::slot(p, lo)]) + (D + w)) - Z; });
+                auto arg = [&] { return ((ca + al[Form::slot(p, lo)]) + (D + w)) - Z; };
+                if constexpr (fb_next_column<Out>::value)
+                    cell(p, lab, w, arg);
+                else
+                    cell(p, lab, arg);
             });
             out.cells_done();
             double n = f.max(mymax);   // (the generic form's barrier also closes the frame's cells before frame_end)
@@ -208,7 +226,7 @@ __device__ __forceinline__ void fb_ck(Form &f, PostResult *res, double *cav, Out
     }
 }
 
-// the launch of any of the four calls: descriptors [0, n_fast) on min(n_fast, kOccFastSlots) one-wavefront workgroups (fast[M - 1],
+// the launch of any of these calls: descriptors [0, n_fast) on min(n_fast, kOccFastSlots) one-wavefront workgroups (fast[M - 1],
 // M = max_move, 4 above 3), lattice i on workgroup i mod grid (its slot); then [n_fast, n_fast + n_generic) on
 // min(n_generic, kOccGenericSlots) 256-thread workgroups
 template <class Desc>

@@ -103,4 +103,8 @@ void launch_sample_paths(const SampleLattice *lats, int n_fast, int n_generic, i
 // launch_fb_ck's form split, grid and slots ----
 void launch_mea_path(const MeaLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 
+// ---- ka_visit.hip: state visit probabilities (ka_visit.hpp): ka_fb_ck.hpp's driver with one more policy, launch_fb_ck's form
+// split, grid and slots ----
+void launch_state_visits(const VisitLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+
 }  // namespace ka

@@ -783,6 +783,27 @@ inline size_t state_duration_workspace(int32_t n, const int64_t *T, const int64_
     });
 }
 
+// ---- ka_ctc_state_visits_batch_f32 (ka_visit.hpp): workspace layout ----
+// state_duration_workspace's layout with VisitLattice descriptors: the generic form accumulates in the outputs, and for host
+// buffers the staged visit and exit_time (2S+1 doubles each) lie beside the staged log-probs and labels.
+struct VisitCarve : SlotCarve {
+    size_t visit, xtime;   // host buffers only
+};
+inline size_t state_visit_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
+                                    VisitCarve *cv, size_t *off_res)
+{
+    return slot_workspace(n, sizeof(VisitLattice), T, S, V, beam, max_move, cv, off_res, [&](int32_t, const Shape &sh, VisitCarve &c, size_t &off) {
+        if (host_buffers) {
+            carve_staged(off, sh, V, c);
+            c.visit = off;
+            off += align_up((size_t)sh.L * sizeof(double));
+            c.xtime = off;
+            off += align_up((size_t)sh.L * sizeof(double));
+        }
+        return true;
+    });
+}
+
 }  // namespace plan
 }  // namespace ka
 

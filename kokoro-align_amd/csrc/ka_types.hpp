@@ -205,6 +205,11 @@ struct DurLattice : FbCkLattice {
     double *dur;                  // [L] output: D(s) = sum over t of gamma_t(s)
     double *tsum;                 // [L] output, or NULL: B(s) = sum over t of t gamma_t(s)
 };
+// ---- state visit probabilities (ka_visit.hpp): the occupancy's slots and form split ----
+struct VisitLattice : FbCkLattice {
+    double *visit;                // [L] output: V(s) = sum over t of gamma_t(s) r_t(s), the probability of passing through s
+    double *xtime;                // [L] output, or NULL: X(s) = sum over t of t gamma_t(s) r_t(s)
+};
 // ---- alignments sampled from the band posterior (ka_sample.hpp): the occupancy's slots and form split ----
 constexpr int kMaxSamples = 64;   // samples per lattice and call: one per lane of the fast form
 struct SampleLattice : FbCkLattice {
@@ -223,7 +228,7 @@ struct MeaLattice : FbCkLattice {
 static_assert(sizeof(MeaLattice) == 136, "descriptor sizes");
 // the workspace planners (ka_plan.hpp) carve n descriptors: their sizes are part of the published workspace byte counts
 static_assert(sizeof(PostLattice) == 88 && sizeof(FbCkLattice) == 104 && sizeof(OccLattice) == 120 && sizeof(StateLattice) == 136 &&
-                  sizeof(DurLattice) == 120 && sizeof(SampleLattice) == 128,
+                  sizeof(DurLattice) == 120 && sizeof(SampleLattice) == 128 && sizeof(VisitLattice) == 120,
               "descriptor sizes");
 
 }  // namespace ka

@@ -1,5 +1,5 @@
 """Forward-backward over the band of ``ctc_best_path``: path posteriors, label occupancy, state posteriors at chosen frames,
-expected state durations, alignments sampled from the posterior, the maximum-expected-accuracy alignment.
+expected state durations, state visit probabilities, alignments sampled from the posterior, the maximum-expected-accuracy alignment.
 
 The six calls take the same lattices (log-probs, labels, beam_size, max_move) in host or device memory and answer with one
 log-likelihood and one status per lattice.  ``_Lattices`` is that common input, normalised once and aware of its memory mode;
@@ -89,7 +89,8 @@ def _device_lattices(log_probs, labels, others, what):
 
 
 def _run_lattices(lat, call, beam_size, max_move, own_args, outs, return_status):
-    """The call ``ka_ctc_<call>_batch_f32`` (path_posteriors, label_posteriors, state_posteriors, state_durations, sample_paths, mea_path): the
+    """The call ``ka_ctc_<call>_batch_f32`` (path_posteriors, label_posteriors, state_posteriors, state_durations, state_visits, sample_paths,
+    mea_path): the
     arguments all of them take around ``own_args`` (the call's own tables), then the results (*outs[i], log_likelihood[i]),
     ``outs`` a list of tuples, and the status handling of ``return_status``."""
     name = f"ctc_{call}_{lat.form}"
@@ -569,6 +570,119 @@ def segment_boundary_shift(duration, best_path, seg_ends, n_phonemes):
     start = np.array([shift[a] if a < T else 0.0 for _, a, _ in segs], dtype=np.float64)
     end = np.array([shift[b] if b < T else 0.0 for _, _, b in segs], dtype=np.float64)   # (b is clipped to T: b < T is seg_ends[i] < T)
     return start, end
+
+
+# ------------------------------------------------------------------------------------------
+# state visit probabilities: which phonemes the path passes through at all
+# ------------------------------------------------------------------------------------------
+def ctc_state_visits(log_probs, labels, terminal, beam_size=1000, max_move=4):
+    """Which states the audio really holds: (visit float64 [L], exit_time float64 [L], log_likelihood float), L = 2S+1
+    positions of the blank-expanded labels (odd position 2i+1: phoneme i, even positions: the blanks around them).
+
+    visit[s] = V(s) = sum_t exit_t(s) is the probability that a path passes through state s at all, exit_t(s) the posterior
+    probability of being in s at frame t and not at t+1, and exit_time[s] = X(s) = sum_t t exit_t(s) is its unnormalised first
+    time moment (exit_time / visit: the state's expected last frame, given that it is visited), over every path of the band of ``ctc_best_path`` that ends at state ``terminal`` (an int, or a best path whose last value is
+    used).  With ``max_move`` > 2 a path may jump over a phoneme; a phoneme the reader did not say shows as a low visit[2i+1].
+    visit <= duration of ``ctc_state_durations`` position by position, and visit[terminal] is 1.  NumPy in -> NumPy out;
+    ROCm torch tensors go to ``ctc_state_visits_device``.  Raises as ``ctc_label_posteriors``.
+    """
+    call = ctc_state_visits_device if _is_tensor(log_probs) else ctc_state_visits_batch
+    (result,) = call([log_probs], [labels], [terminal], beam_size, max_move)
+    return result
+
+
+def _state_visits(lat, terminals, beam_size, max_move, out, return_status):
+    if lat is None:
+        return ([], []) if return_status else []
+    Ls = [2 * S + 1 for S in lat.S]
+    if out is None:
+        visits = [lat.empty(L, np.float64) for L in Ls]
+        exits = [lat.empty(L, np.float64) for L in Ls]
+    else:
+        import torch
+        if len(out) != lat.n or any(len(o) != 2 for o in out):
+            raise ValueError("out must hold one (visit, exit_time) pair of tensors per lattice")
+        for o, L in zip(out, Ls):
+            if any(x.dtype != torch.float64 or tuple(x.shape) != (L,) or not x.is_contiguous() or x.device != lat.dev for x in o):
+                raise ValueError("out tensors must be contiguous float64 [2 S_i + 1] on the input's device")
+        visits, exits = [o[0] for o in out], [o[1] for o in out]
+    p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
+    p_vis, _k2 = _ptr_array([lat.ptr(x) for x in visits])
+    p_exit, _k3 = _ptr_array([lat.ptr(x) for x in exits])
+    return _run_lattices(lat, "state_visits", beam_size, max_move, (p_term, p_vis, p_exit), list(zip(visits, exits)), return_status)
+
+
+def ctc_state_visits_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False):
+    """State visit probabilities of many lattices in ONE launch; host NumPy buffers in and out.
+
+    Returns a list of (visit [L_i], exit_time [L_i], log_likelihood); with ``return_status`` also the per-lattice status
+    list, in which case failures do not raise (their arrays are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    """
+    lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
+    return _state_visits(lat, terminals, beam_size, max_move, None, return_status)
+
+
+def ctc_state_visits_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]) and terminals (ints
+    or best paths), list of (visit, exit_time: float64 tensors [2 S_i + 1] on the device, log_likelihood float) out.
+    ``out``: optional list of (visit, exit_time) pairs of contiguous float64 tensors to write into.  One launch on torch's
+    current stream."""
+    lat = _device_lattices(log_probs, labels, terminals, "terminals")
+    return _state_visits(lat, terminals, beam_size, max_move, out, return_status)
+
+
+def phoneme_visits(visit):
+    """(labels [S], blanks [S+1]) from ``ctc_state_visits``' visit [2S+1]: the probability that the path passes through every
+    phoneme (the odd positions) and through the blanks before, between and after them (the even ones).  float64 arrays (host)."""
+    v = _host_f64(visit)
+    if len(v) % 2 == 0:
+        raise ValueError("visit must have 2S+1 entries")
+    return v[1::2].copy(), v[0::2].copy()
+
+
+def phoneme_spans(visit, exit_time, duration):
+    """(first, last), float64 [2S+1] (host): the expected first and last frame of every state, given that the path visits it.
+
+    last = X / V with X = ``exit_time`` and V = ``visit`` of ``ctc_state_visits``.  On a path the frames spent in a state
+    number last - first + 1, so with D = ``duration`` of ``ctc_state_durations`` on the same input E[first; visited] =
+    X - D + V and first = (X - D + V) / V.  NaN where V == 0."""
+    v, x, d = _host_f64(visit), _host_f64(exit_time), _host_f64(duration)
+    if not (len(v) == len(x) == len(d)) or len(v) % 2 == 0:
+        raise ValueError("visit, exit_time and duration must have the same 2S+1 entries")
+    seen = v > 0
+    first, last = np.full(len(v), np.nan), np.full(len(v), np.nan)
+    last[seen] = x[seen] / v[seen]
+    first[seen] = (x[seen] - d[seen] + v[seen]) / v[seen]
+    return first, last
+
+
+def segment_expected_match(visit, labels, best_path, seg_ends):
+    """The soft form of the reference's keep-or-drop test of a segment (host only): (expected float64, count int64) per segment
+    that ``align()`` writes a line for.
+
+    For segment i (frames [a, b), a = seg_ends[i-1], 0 for the first, b = seg_ends[i]) ``align()`` writes the transcript's
+    phonemes [text_start, text_end), text_start = min(best_path[a] // 2, S) and text_end = min(best_path[b] // 2, S), or S
+    where b >= T.  count[i] is the number of k in that range with labels[k] != 0 and expected[i] the sum of visit[2k+1] over
+    them, so expected / count stands where the reference asks whether the phonemes decoded from the segment's best path are
+    more than 70 % of the transcript's.  visit[2k+1] is the probability of passing through phoneme k ANYWHERE in the audio,
+    not within the segment's frames: a phoneme said, but outside [a, b), still counts."""
+    v = _host_f64(visit)
+    lab = np.asarray(labels.detach().cpu() if _is_tensor(labels) else labels, dtype=np.int64).reshape(-1)
+    S = len(lab)
+    if len(v) != 2 * S + 1:
+        raise ValueError("visit must have 2S+1 entries for the S labels")
+    path = np.asarray(best_path.detach().cpu() if _is_tensor(best_path) else best_path, dtype=np.int64).reshape(-1)
+    T = len(path)
+    segs = _segments(np.asarray(seg_ends, dtype=np.int64), T)
+    expected, count = np.zeros(len(segs), np.float64), np.zeros(len(segs), np.int64)
+    for i, a, b in segs:
+        start = min(int(path[a]) // 2, S) if a < T else S
+        end = min(int(path[b]) // 2, S) if b < T else S
+        k = np.arange(start, max(start, end))
+        k = k[lab[k] != 0]
+        count[i] = len(k)
+        expected[i] = v[2 * k + 1].sum()
+    return expected, count
 
 
 # ------------------------------------------------------------------------------------------

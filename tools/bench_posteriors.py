@@ -7,7 +7,8 @@ state_single, state_b1024); and of ka_ctc_state_durations_batch_f32 (expected st
 on the occupancy's shapes and terminals (cases dur_single, dur_b1024); and of ka_ctc_sample_paths_batch_f32 (64 alignments
 sampled from the band posterior per lattice, ka_sample.hpp, section 4.24) on the same shapes and terminals (cases smp_single,
 smp_b1024); and of ka_ctc_mea_path_batch_f32 (the maximum-expected-accuracy alignment, ka_mea.hpp, section 4.26) on the same
-shapes and terminals (cases mea_single, mea_b1024).
+shapes and terminals (cases mea_single, mea_b1024); and of ka_ctc_state_visits_batch_f32 (state visit probabilities,
+ka_visit.hpp, section 4.27) on the same shapes and terminals (cases vis_single, vis_b1024).
 
     python tools/bench_posteriors.py [--cases single,b1024,b8192,corpus] [--reps 3] [--out profiles/posteriors.jsonl]
     python tools/bench_posteriors.py --cases state_single,state_b1024 --out profiles/state_posteriors_bench.jsonl
@@ -17,6 +18,8 @@ shapes and terminals (cases mea_single, mea_b1024).
         --out profiles/sample_bench.jsonl
     python tools/bench_posteriors.py --out profiles/mea_bench.jsonl --cases \
         occ_single,dur_single,mea_single,occ_b1024,dur_b1024,mea_b1024,occ_single,dur_single,mea_single,occ_b1024,dur_b1024,mea_b1024,occ_single,dur_single,mea_single,occ_b1024,dur_b1024,mea_b1024
+    python tools/bench_posteriors.py --out profiles/visit_bench.jsonl --cases \
+        occ_single,dur_single,vis_single,occ_b1024,dur_b1024,vis_b1024,occ_single,dur_single,vis_single,occ_b1024,dur_b1024,vis_b1024,occ_single,dur_single,vis_single,occ_b1024,dur_b1024,vis_b1024
 
 Device-resident inputs (hash-generated); best paths from the library's own best-path call.  The 8192 batch points its
 lattices at the 1024 batch's log-probs, labels and paths eight times over (distinct outputs): 105 GB of log-probs would
@@ -121,6 +124,14 @@ def time_durations(lps, labs, paths, reps):
     return time_batch("state_durations", "ka_state_duration_workspace_bytes", lps, labs, (term[0], k[0][0], k[1][0]), reps)
 
 
+def time_visits(lps, labs, paths, reps):
+    visits = [torch.empty(2 * int(x.shape[0]) + 1, dtype=torch.float64, device="cuda") for x in labs]
+    exits = [torch.empty(2 * int(x.shape[0]) + 1, dtype=torch.float64, device="cuda") for x in labs]
+    k = [_ptr_array([x.data_ptr() for x in xs]) for xs in (visits, exits)]
+    term = _i64_array(torch.stack([p[-1] for p in paths]).cpu().tolist())
+    return time_batch("state_visits", "ka_state_visit_workspace_bytes", lps, labs, (term[0], k[0][0], k[1][0]), reps)
+
+
 def time_samples(lps, labs, paths, reps, K=64):
     outs = [torch.empty((K, int(x.shape[0])), dtype=torch.int32, device="cuda") for x in lps]
     p_out = _ptr_array([x.data_ptr() for x in outs])
@@ -151,7 +162,7 @@ def main():
     cases = a.cases.split(",")
     b1024 = None
     for case in cases:
-        kind = case.split("_")[0] if case.startswith(("occ_", "state_", "dur_", "smp_", "mea_")) else "path"
+        kind = case.split("_")[0] if case.startswith(("occ_", "state_", "dur_", "smp_", "mea_", "vis_")) else "path"
         case_in = case[len(kind) + 1:] if kind != "path" else case
         if case_in == "single":
             lps, labs = cfg2(1)
@@ -173,7 +184,7 @@ def main():
         if case_in in ("single", "corpus"):
             paths = best_paths(lps, labs)
         ms, st, ll = {"path": time_posteriors, "occ": time_occupancy, "state": time_states, "dur": time_durations, "smp": time_samples,
-                       "mea": time_mea}[kind](lps, labs, paths, a.reps)
+                       "mea": time_mea, "vis": time_visits}[kind](lps, labs, paths, a.reps)
         frames = sum(int(x.shape[0]) for x in lps)
         line = dict(case=case, lattices=len(lps), frames=frames, ms_min=round(min(ms), 3), ms_median=round(float(np.median(ms)), 3),
                     frames_per_s=frames / (min(ms) / 1e3), status_ok=int((st == 0).sum()), reps=a.reps)

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""One SHA-256 per (case, call) over what the six forward-backward calls write: the output bytes, then the log-likelihood and
+"""One SHA-256 per (case, call) over what the seven forward-backward calls write: the output bytes, then the log-likelihood and
 status bytes.  For a change of the kernels that must not move a bit: run it on the library before and after and diff.
 
     python tools/fb_output_digest.py [--library path/to/libkokoro_align_amd.so] > digest.txt
 
 The calls go through the raw ctypes callers of tests/fb_harness.py, tests/duration_harness.py, tests/sample_harness.py and
 tests/mea_harness.py: path posteriors, label occupancy, state posteriors at posterior_ref.query_frames(T), durations with
-time_sum, 64 sampled paths with a fixed seed, and the maximum-expected-accuracy path with its expected accuracy.  The cases
+time_sum, 64 sampled paths with a fixed seed, the maximum-expected-accuracy path with its expected accuracy, and (tests/visit_harness.py)
+the state visits with exit_time.  The cases
 are the smallest at which a slot mapping, a checkpoint extent or a block boundary can go wrong: every case of posterior_ref.edge_cases(), the one-wavefront ones once more in the generic form (V padded to 80), tiny
 lattices round the 32-frame block, every max_move with a label 0 and a -inf, a band that jumps (L > T), one that jumps more
 than 64 positions a frame (L > 64 T: past the label ring's request; every call answers zero mass), the bands on either side of
@@ -82,6 +83,7 @@ def main():
     import mea_harness as M
     import posterior_ref as R
     import sample_harness as S
+    import visit_harness as VH
     _, _lib, eng = H.engine()
     for name, lats, beam, mm in cases(R, H):
         lps, labs, terms = ([x[i] for x in lats] for i in range(3))
@@ -99,6 +101,8 @@ def main():
         results["samples"] = (paths, ll, st)
         paths, ea, ll, st, _ = M.mea_call(eng, _lib, lps, labs, terms, beam, mm)
         results["mea"] = (paths + [ea], ll, st)
+        visits, exits, ll, st, _ = VH.visit_call(eng, _lib, lps, labs, terms, beam, mm, exit_time=True)
+        results["visits"] = (visits + exits, ll, st)
         for call, (outs, ll, st) in results.items():
             h = hashlib.sha256()
             for x in list(outs) + [ll, st]:

@@ -18,6 +18,13 @@ most E), and taken here from the records the tests wrote:
 
     KA_ACCURACY_OUT=ratios.jsonl python -m pytest tests/test_mea_path_gpu.py -q -m gpu
     python tools/posterior_accuracy.py ratios.jsonl profiles/posterior_accuracy.json mea mea_total mea_value
+
+The state visit call (tests/test_state_visits_gpu.py, tests/visit_ref.py) records visit and exit_time
+against a model and a multiplier of their own, set by the rule above, and z, whose records join those the file holds (a test's
+earlier record is replaced, every other one stays):
+
+    KA_ACCURACY_OUT=ratios.jsonl python -m pytest tests/test_state_visits_gpu.py -q -m gpu
+    python tools/posterior_accuracy.py ratios.jsonl profiles/posterior_accuracy.json visit exit_time z
 """
 import json
 import math
@@ -26,6 +33,7 @@ import sys
 CALLS = ("state", "label", "path", "z")
 DURATION_CALLS = ("duration", "time_sum", "duration_sum", "time_sum_sum")
 MEA_CALLS = ("mea", "mea_total", "mea_value")
+VISIT_CALLS = ("visit", "exit_time")
 
 
 def round_up(x):
@@ -38,7 +46,7 @@ def round_up(x):
 
 def main(src, dst, only=()):
     calls = tuple(only) or CALLS
-    assert all(c in CALLS + DURATION_CALLS + MEA_CALLS for c in calls), calls
+    assert all(c in CALLS + DURATION_CALLS + MEA_CALLS + VISIT_CALLS for c in calls), calls
     worst = {c: {} for c in calls}
     held = {}                                    # the multiplier the tests held a call against (every record carries it)
     with open(src) as f:
@@ -57,6 +65,8 @@ def main(src, dst, only=()):
         with open(dst) as f:
             out = json.load(f)
     for c in calls:
+        if only and c in CALLS and c in out["calls"]:        # one more file's records of a call the file already holds
+            worst[c] = {**{r["test"]: r["ratio"] for r in out["calls"][c]["records"]}, **worst[c]}
         top = max(worst[c].values(), default=0.0)
         # (the duration figures are held against the state call's multiplier: their model is a sum of its per-cell model)
         m = out["calls"]["state"]["m"] if c in DURATION_CALLS and "state" in out["calls"] else held[c] if c in MEA_CALLS else round_up(2 * top)
