@@ -261,6 +261,46 @@ size_t ka_state_visit_workspace_bytes(int32_t n, const int64_t *T, const int64_t
                                       int32_t mem);
 
 /*
+ * Exact boundary-time quantiles and the lattice log-likelihood of a terminal: on the lattice of
+ * ka_ctc_label_posteriors (same band [lo_t, hi_t), moves j in [0, max_move), label-0 veto, terminal s*, statuses and Z), with
+ * L = 2S+1 and tau_c the first frame whose state is >= c (as expected_crossing_frames reads it): paths only move up, so
+ * P(tau_c <= t) = P(state_t >= c) = sum over s >= c of gamma_t(s), and a quantile of tau_c is the first frame at which that sum
+ * passes a level.  The sum is taken in the occupancy's 32.32 fixed point, an integer, so the result does not depend on the
+ * order of the adds and is defined bit for bit by the rows of ka_ctc_state_posteriors:
+ *   F_t(c) = 2^32 where c <= lo_t (the whole band lies at or above the cut: every path is there), 0 where c >= hi_t, else the
+ *            sum over p in [c, hi_t) of fix(gamma_t(p)), fix(g) = (uint64_t)(g 2^32), gamma the float the state posteriors write
+ *   thr_m  = (uint64_t)ceil(levels[m] 2^32), computed on the host in double
+ *   quantile[k, m] = the smallest t in [0, T) with F_t(cuts[k]) >= thr_m, and T if there is none
+ * a minimum over ALL frames (F need not be monotone in t in float).  c = 0 gives 0; c > s* or c = L gives T; quantile[k, m] <=
+ * quantile[k, m+1] and quantile[k, m] <= quantile[k+1, m] hold without tolerance.  Arguments as ka_ctc_state_durations[_batch]_f32,
+ * with in place of duration and time_sum
+ *   cuts            [K] int64 HOST array in both memory modes (as the state posteriors' frames): strictly increasing in [0, L];
+ *                   K = 0 is legal, and then only Z is computed
+ *   levels, M       [M] double HOST array, 1 <= M <= 8, strictly increasing in [2^-10, 1 - 2^-10] (the upper limit keeps every
+ *                   threshold clear of a row's own sum, which is 1 within 1e-5); one array for every lattice of a batch
+ *   quantile, ld_q  [K, ld_q] int32 output (where `mem` says), ld_q >= M the row pitch; columns [0, M) are written, others untouched
+ * Per lattice: statuses as ka_ctc_label_posteriors, with -1 over [K, M] for a failed lattice.  KA_ERR_BAD_ARGS before anything is
+ * launched for cuts out of order or range, M outside [1, 8], a level outside its interval, levels out of order, ld_q < M.
+ * Resources: the state durations' slots; 42 496 B of LDS in the one-wavefront form (three workgroups per CU), no scratch.
+ * Measured at 1.04 (one lattice) to 1.05 (768 lattices) times a state-duration call with the ~100 cuts of a file's text
+ * boundaries, and at 1.09 to 1.11 times with a cut at every even position (5001 cuts): a dense cut list costs about twice the
+ * excess of a sparse one.
+ */
+int ka_ctc_boundary_quantiles_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                  int32_t beam_size, int32_t max_move, int64_t terminal, const int64_t *cuts, int64_t K,
+                                  const double *levels, int32_t M, int32_t *quantile, int64_t ld_q, double *log_likelihood, int32_t mem,
+                                  void *stream);
+int ka_ctc_boundary_quantiles_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                        const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                        int32_t max_move, const int64_t *terminal, const int64_t *const *cuts, const int64_t *K,
+                                        const double *levels, int32_t M, int32_t *const *quantile, const int64_t *ld_q,
+                                        double *log_likelihood, int32_t *status, int32_t mem, void *stream);
+/* device-workspace bytes such a call carves (0 for unsupported arguments): the state durations' slots, the cuts and start frames of
+ * every lattice, the thresholds, one row of 64-bit words per generic slot (and, for KA_MEM_HOST, the staged inputs and outputs) */
+size_t ka_boundary_quantile_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t M, int32_t V,
+                                            int32_t beam_size, int32_t max_move, int32_t mem);
+
+/*
  * Alignments sampled from the band posterior, and the lattice log-likelihood of a terminal: forward
  * filter, backward sample on the lattice of ka_ctc_label_posteriors (same band [lo_t, hi_t), moves j in [0, max_move), label-0
  * veto, terminal s*, statuses and Z).  With u_t(s) the forward value and lab' the blank-expanded labels, sample k is the path

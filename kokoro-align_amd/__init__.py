@@ -16,7 +16,8 @@ the spread of every boundary (ctc_sample_paths[_batch|_device], sampled_crossing
 alignment with the most frames at the right state in expectation (ctc_mea_path[_batch|_device], path_outputs,
 segment_path_disagreement), and the probability that the path passes through every phoneme at all, the soft form of the
 reference's keep-or-drop test of a segment (ctc_state_visits[_batch|_device], phoneme_visits, phoneme_spans,
-segment_expected_match).
+segment_expected_match), and the exact quantiles of every boundary's frame, the interval a cut lies in with a given probability
+(ctc_boundary_quantiles[_batch|_device], boundary_cuts, segment_boundary_interval).
 
 The DP and backtrace run in the HIP C-ABI library (include/kokoro_align_amd.h); there is no
 CPU fallback — importing works without a GPU, computing does not.
@@ -32,7 +33,11 @@ from .align import (  # noqa: F401
     pandas_read_align,
 )
 from .posteriors import (  # noqa: F401
+    boundary_cuts,
     boundary_frames,
+    ctc_boundary_quantiles,
+    ctc_boundary_quantiles_batch,
+    ctc_boundary_quantiles_device,
     ctc_label_posteriors,
     ctc_label_posteriors_batch,
     ctc_label_posteriors_device,
@@ -63,6 +68,7 @@ from .posteriors import (  # noqa: F401
     sampled_crossing_frames,
     segment_agreement,
     segment_boundary_confidence,
+    segment_boundary_interval,
     segment_boundary_shift,
     segment_boundary_spread,
     segment_confidence,

@@ -44,6 +44,7 @@ EXPORTS = [
     "ka_ctc_sample_paths_f32", "ka_ctc_sample_paths_batch_f32", "ka_sample_paths_workspace_bytes",
     "ka_ctc_state_visits_f32", "ka_ctc_state_visits_batch_f32", "ka_state_visit_workspace_bytes",
     "ka_ctc_mea_path_f32", "ka_ctc_mea_path_batch_f32", "ka_mea_path_workspace_bytes",
+    "ka_ctc_boundary_quantiles_f32", "ka_ctc_boundary_quantiles_batch_f32", "ka_boundary_quantile_workspace_bytes",
 ]
 
 
@@ -135,6 +136,13 @@ def load_library():
     L.ka_ctc_state_visits_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pi64, pp, pp, vp, vp, i32, vp]
     L.ka_state_visit_workspace_bytes.restype = sz
     L.ka_state_visit_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
+    L.ka_ctc_boundary_quantiles_f32.restype = ctypes.c_int
+    L.ka_ctc_boundary_quantiles_f32.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i64, vp, i64, vp, i32, vp, i64, vp, i32, vp]
+    L.ka_ctc_boundary_quantiles_batch_f32.restype = ctypes.c_int
+    L.ka_ctc_boundary_quantiles_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pi64, pp, pi64, vp, i32, pp, pi64, vp, vp,
+                                                      i32, vp]
+    L.ka_boundary_quantile_workspace_bytes.restype = sz
+    L.ka_boundary_quantile_workspace_bytes.argtypes = [i32, pi64, pi64, pi64, i32, i32, i32, i32, i32]
     L.ka_ctc_sample_paths_f32.restype = ctypes.c_int
     L.ka_ctc_sample_paths_f32.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i64, i32, u64, vp, i64, vp, i32, vp]
     L.ka_ctc_sample_paths_batch_f32.restype = ctypes.c_int

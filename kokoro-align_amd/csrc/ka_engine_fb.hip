@@ -1,13 +1,14 @@
 // ka_engine_fb.hip — the forward-backward calls of the C ABI: best-path posteriors (ka_posterior.hpp), label occupancy
 // (ka_occupancy.hpp), state posteriors at chosen frames (ka_state_posterior.hpp), expected state durations (ka_duration.hpp),
-// state visit probabilities (ka_visit.hpp), alignments sampled from the band posterior (ka_sample.hpp) and the
-// maximum-expected-accuracy alignment (ka_mea.hpp).  Host
+// state visit probabilities (ka_visit.hpp), exact boundary-time quantiles (ka_quantile.hpp), alignments sampled from the band
+// posterior (ka_sample.hpp) and the maximum-expected-accuracy alignment (ka_mea.hpp).  Host
 // code only.
 // They use the engine's workspace and pinned buffer, with their own kernels and workspace layout, whatever
 // the engine's mode, and run to the end inside the call: no batch stays in flight.
 #include "ka_engine.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 namespace {
@@ -17,7 +18,7 @@ using ka::plan::align_up;
 
 // ---- best-path posteriors (ka_posterior.hpp), label occupancy (ka_occupancy.hpp), state posteriors at chosen frames
 // (ka_state_posterior.hpp) and expected state durations (ka_duration.hpp): their own kernels and workspace layout, whatever the
-// engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall, DurCall, VisitCall, SampleCall, MeaCall) brings what
+// engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall, DurCall, VisitCall, QuantCall, SampleCall, MeaCall) brings what
 // differs: its own arrays and their
 // checks, its planner and launch, the descriptor fields beyond FbLattice, its own staging (upload: host buffers only;
 // stage: every memory mode), and what two statuses mean.
@@ -263,6 +264,103 @@ struct VisitCall {
         return KA_OK;
     }
 };
+
+struct QuantCall {
+    using Desc = ka::QuantLattice;
+    using Carve = ka::plan::QuantCarve;
+    static constexpr const char *kName = "boundary quantiles";
+    static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score reaches the terminal";
+    const int64_t *terminal;
+    const int64_t *const *cuts;   // host arrays in both memory modes
+    const int64_t *K;
+    int32_t *const *quantile;
+    const int64_t *ld_q;
+    int32_t M;
+    unsigned long long thr[ka::kMaxLevels];   // the levels as thresholds (quant_thresholds)
+    mutable std::vector<std::vector<char>> staged;   // per lattice: its cuts and, behind them, their start frames, until the call's end
+
+    bool arrays() const { return terminal && cuts && K && quantile && ld_q; }
+    const char *bad_lattice(const FbArgs &a, int32_t i) const
+    {
+        const int64_t k = K[i], L = 2 * a.S[i] + 1;
+        if (k > 0 && !cuts[i]) return ": NULL cuts";
+        for (int64_t j = 0; j < k; ++j) {
+            if (cuts[i][j] < 0 || cuts[i][j] > L) return ": a cut outside [0, 2S+1]";
+            if (j > 0 && cuts[i][j] <= cuts[i][j - 1]) return ": cuts not strictly increasing";
+        }
+        return ld_q[i] < M ? ": ld_q < M" : nullptr;
+    }
+    bool buffers(int32_t i) const { return K[i] == 0 || quantile[i] != nullptr; }
+    size_t plan(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host, Carve *cv,
+                size_t *off_res) const
+    {
+        return ka::plan::boundary_quantile_workspace(n, T, S, K, M, V, beam, max_move, host, cv, off_res);   // (0 for K < 0 or K > 2S+2)
+    }
+    static constexpr auto launch = ka::launch_boundary_quantiles;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (a.mem == KA_MEM_HOST) {
+            d.quant = reinterpret_cast<int32_t *>(ws + c.quant);
+            d.ld_out = M;
+        } else {
+            d.quant = quantile[i];
+            d.ld_out = ld_q[i];
+        }
+        fill_slot(d, c, terminal[i], ws);
+        d.cuts = reinterpret_cast<const int64_t *>(ws + c.cuts);
+        d.start = reinterpret_cast<const int32_t *>(ws + c.start);
+        d.thr = reinterpret_cast<const unsigned long long *>(ws + c.thr);
+        d.frow = reinterpret_cast<unsigned long long *>(ws + c.frow);
+        d.K = (int32_t)K[i];
+        d.M = M;
+    }
+    int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int stage(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (i == 0) {
+            staged.assign((size_t)a.n, {});
+            KA_HIP(hipMemcpyAsync(ws + c.thr, thr, sizeof(thr), hipMemcpyHostToDevice, a.stream));
+        }
+        const size_t k = (size_t)K[i];
+        if (k == 0) return KA_OK;
+        std::vector<char> &buf = staged[(size_t)i];
+        buf.resize(k * 12);
+        std::memcpy(buf.data(), cuts[i], k * 8);
+        int32_t *start = reinterpret_cast<int32_t *>(buf.data() + k * 8);
+        for (size_t j = 0; j < k; ++j)
+            start[j] = (int32_t)ka::plan::quantile_start_frame(cuts[i][j], a.T[i], 2 * a.S[i] + 1, a.beam_size);
+        KA_HIP(hipMemcpyAsync(ws + c.cuts, buf.data(), buf.size(), hipMemcpyHostToDevice, a.stream));
+        return KA_OK;
+    }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (K[i] == 0) return KA_OK;
+        KA_HIP(hipMemcpy2DAsync(quantile[i], (size_t)ld_q[i] * 4, ws + c.quant, (size_t)M * 4, (size_t)M * 4, (size_t)K[i], hipMemcpyDeviceToHost,
+                                a.stream));
+        return KA_OK;
+    }
+};
+// the levels of a boundary-quantile call as thresholds: thr_m = ceil(levels[m] 2^32), for 1 <= M <= kMaxLevels strictly increasing
+// levels in [2^-10, 1 - 2^-10]; else the reason they are refused
+const char *quant_thresholds(const double *levels, int32_t M, unsigned long long *thr)
+{
+    if (M < 1 || M > ka::kMaxLevels) return "boundary quantiles: M outside [1, 8]";
+    if (!levels) return "boundary quantiles: NULL levels";
+    const double lim = 1.0 / 1024.0;
+    for (int32_t m = 0; m < ka::kMaxLevels; ++m) thr[m] = ~0ull;
+    for (int32_t m = 0; m < M; ++m) {
+        // (a NaN is found by its bits, hidden from the optimiser: the library is built with -fno-honor-nans)
+        uint64_t b;
+        std::memcpy(&b, &levels[m], sizeof(b));
+        asm volatile("" : "+r"(b));
+        if ((b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) return "boundary quantiles: a level is NaN";
+        if (!(levels[m] >= lim && levels[m] <= 1.0 - lim)) return "boundary quantiles: a level outside [2^-10, 1 - 2^-10]";
+        if (m > 0 && !(levels[m] > levels[m - 1])) return "boundary quantiles: levels not strictly increasing";
+        thr[m] = (unsigned long long)std::ceil(levels[m] * 4294967296.0);
+    }
+    return nullptr;
+}
 
 struct SampleCall {
     using Desc = ka::SampleLattice;
@@ -575,6 +673,33 @@ size_t ka_state_visit_workspace_bytes(int32_t n, const int64_t *T, const int64_t
 {
     if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
     return ka::plan::state_visit_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+int ka_ctc_boundary_quantiles_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                        const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                        const int64_t *terminal, const int64_t *const *cuts, const int64_t *K, const double *levels, int32_t M,
+                                        int32_t *const *quantile, const int64_t *ld_q, double *log_likelihood, int32_t *status, int32_t mem,
+                                        void *stream)
+{
+    QuantCall call{terminal, cuts, K, quantile, ld_q, M, {}, {}};
+    if (const char *why = quant_thresholds(levels, M, call.thr)) return fail(KA_ERR_BAD_ARGS, why);
+    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream}, call);
+}
+
+int ka_ctc_boundary_quantiles_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                  int32_t beam_size, int32_t max_move, int64_t terminal, const int64_t *cuts, int64_t K, const double *levels,
+                                  int32_t M, int32_t *quantile, int64_t ld_q, double *log_likelihood, int32_t mem, void *stream)
+{
+    QuantCall call{&terminal, &cuts, &K, &quantile, &ld_q, M, {}, {}};
+    if (const char *why = quant_thresholds(levels, M, call.thr)) return fail(KA_ERR_BAD_ARGS, why);
+    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream}, call);
+}
+
+size_t ka_boundary_quantile_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t M, int32_t V,
+                                            int32_t beam_size, int32_t max_move, int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S || !K)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::boundary_quantile_workspace(n, T, S, K, M, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
 int ka_ctc_sample_paths_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,

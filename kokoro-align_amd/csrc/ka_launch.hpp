@@ -107,4 +107,8 @@ void launch_mea_path(const MeaLattice *lats, int n_fast, int n_generic, int max_
 // split, grid and slots ----
 void launch_state_visits(const VisitLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 
+// ---- ka_quantile.hip: exact boundary-time quantiles (ka_quantile.hpp): ka_fb_ck.hpp's driver with one more policy,
+// launch_fb_ck's form split, grid and slots ----
+void launch_boundary_quantiles(const QuantLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+
 }  // namespace ka

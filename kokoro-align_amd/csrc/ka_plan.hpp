@@ -804,6 +804,60 @@ inline size_t state_visit_workspace(int32_t n, const int64_t *T, const int64_t *
     });
 }
 
+// ---- ka_ctc_boundary_quantiles_batch_f32 (ka_quantile.hpp): workspace layout ----
+// state_duration_workspace's layout and slots with QuantLattice descriptors, and per lattice, in both memory modes, its
+// uploaded cuts (K int64) with their start frames behind them (K int32), and for host buffers the staged quantiles [K, M]
+// beside the staged log-probs and labels.  Behind the shared slots: the call's thresholds (kMaxLevels 64-bit words), then one
+// row of 64-bit words per generic slot, as wide as the widest band among the call's generic lattices.
+struct QuantCarve : SlotCarve {
+    size_t cuts, start;   // uploaded cuts and start frames (one copy: start lies behind the cuts)
+    size_t quant;         // host buffers only
+    size_t thr, frow;
+};
+// the first frame whose band lies at or above cut c: lo_t = max(0, floor(L t / T) - beam / 2) >= c, which is frame 0 for c = 0
+// and else the first t with L t >= (c + beam / 2) T; T if there is none
+inline int64_t quantile_start_frame(int64_t c, int64_t T, int64_t L, int64_t beam)
+{
+    if (c <= 0) return 0;
+    const int64_t t = ((c + beam / 2) * T + L - 1) / L;
+    return t < T ? t : T;
+}
+inline size_t boundary_quantile_workspace(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t M, int32_t V, int32_t beam,
+                                          int32_t max_move, bool host_buffers, QuantCarve *cv, size_t *off_res)
+{
+    if (M < 1 || M > kMaxLevels) return 0;
+    std::vector<size_t> rank((size_t)std::max(n, 0));
+    size_t n_gen = 0, row_bytes = 0;
+    size_t off = slot_workspace(n, sizeof(QuantLattice), T, S, V, beam, max_move, cv, off_res, [&](int32_t i, const Shape &sh, QuantCarve &c, size_t &o) {
+        if (K[i] < 0 || K[i] > sh.L + 1) return false;
+        c.cuts = o;
+        c.start = o + (size_t)K[i] * 8;
+        o += align_up((size_t)K[i] * 12);
+        if (host_buffers) {
+            carve_staged(o, sh, V, c);
+            c.quant = o;
+            o += align_up((size_t)K[i] * (size_t)M * 4);
+        }
+        rank[(size_t)i] = c.slot;   // (slot_workspace's rank of the lattice in its form)
+        if (!c.fast) {
+            ++n_gen;
+            row_bytes = std::max(row_bytes, align_up((size_t)c.parts.cw * 8));
+        }
+        return true;
+    });
+    if (off == 0) return 0;
+    const size_t thr = off;
+    off += align_up((size_t)kMaxLevels * 8);
+    const size_t rows = off, gen_slots = std::min<size_t>(n_gen, kOccGenericSlots);
+    off += gen_slots * row_bytes;
+    if (cv)
+        for (int32_t i = 0; i < n; ++i) {
+            cv[i].thr = thr;
+            cv[i].frow = cv[i].fast ? rows : rows + (rank[(size_t)i] % gen_slots) * row_bytes;
+        }
+    return off;
+}
+
 }  // namespace plan
 }  // namespace ka
 

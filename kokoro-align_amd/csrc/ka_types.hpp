@@ -210,6 +210,16 @@ struct VisitLattice : FbCkLattice {
     double *visit;                // [L] output: V(s) = sum over t of gamma_t(s) r_t(s), the probability of passing through s
     double *xtime;                // [L] output, or NULL: X(s) = sum over t of t gamma_t(s) r_t(s)
 };
+// ---- exact boundary-time quantiles (ka_quantile.hpp): the occupancy's slots and form split ----
+constexpr int kMaxLevels = 8;     // levels per call
+struct QuantLattice : FbCkLattice {
+    int32_t *quant;               // [K, ld_out] output, M columns written: the first frame at which F_t(cuts[k]) reaches thr[m]
+    const int64_t *cuts;          // [K] cut positions, strictly increasing in [0, L] (workspace)
+    const int32_t *start;         // [K] the first frame whose band lies at or above the cut, T if none: what the output starts from (workspace)
+    const unsigned long long *thr;   // [M] the levels as 32.32 fixed-point thresholds, ascending (workspace, one array per call)
+    unsigned long long *frow;     // generic form only: [cw] the frame's fixed-point row, then its prefix sums (slot)
+    int32_t K, M;
+};
 // ---- alignments sampled from the band posterior (ka_sample.hpp): the occupancy's slots and form split ----
 constexpr int kMaxSamples = 64;   // samples per lattice and call: one per lane of the fast form
 struct SampleLattice : FbCkLattice {
@@ -228,7 +238,8 @@ struct MeaLattice : FbCkLattice {
 static_assert(sizeof(MeaLattice) == 136, "descriptor sizes");
 // the workspace planners (ka_plan.hpp) carve n descriptors: their sizes are part of the published workspace byte counts
 static_assert(sizeof(PostLattice) == 88 && sizeof(FbCkLattice) == 104 && sizeof(OccLattice) == 120 && sizeof(StateLattice) == 136 &&
-                  sizeof(DurLattice) == 120 && sizeof(SampleLattice) == 128 && sizeof(VisitLattice) == 120,
+                  sizeof(DurLattice) == 120 && sizeof(SampleLattice) == 128 && sizeof(VisitLattice) == 120 &&
+                  sizeof(QuantLattice) == 152,
               "descriptor sizes");
 
 }  // namespace ka

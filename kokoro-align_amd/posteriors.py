@@ -1,5 +1,6 @@
 """Forward-backward over the band of ``ctc_best_path``: path posteriors, label occupancy, state posteriors at chosen frames,
-expected state durations, state visit probabilities, alignments sampled from the posterior, the maximum-expected-accuracy alignment.
+expected state durations, state visit probabilities, exact boundary-time quantiles, alignments sampled from the posterior, the
+maximum-expected-accuracy alignment.
 
 The six calls take the same lattices (log-probs, labels, beam_size, max_move) in host or device memory and answer with one
 log-likelihood and one status per lattice.  ``_Lattices`` is that common input, normalised once and aware of its memory mode;
@@ -89,8 +90,8 @@ def _device_lattices(log_probs, labels, others, what):
 
 
 def _run_lattices(lat, call, beam_size, max_move, own_args, outs, return_status):
-    """The call ``ka_ctc_<call>_batch_f32`` (path_posteriors, label_posteriors, state_posteriors, state_durations, state_visits, sample_paths,
-    mea_path): the
+    """The call ``ka_ctc_<call>_batch_f32`` (path_posteriors, label_posteriors, state_posteriors, state_durations, state_visits, boundary_quantiles,
+    sample_paths, mea_path): the
     arguments all of them take around ``own_args`` (the call's own tables), then the results (*outs[i], log_likelihood[i]),
     ``outs`` a list of tuples, and the status handling of ``return_status``."""
     name = f"ctc_{call}_{lat.form}"
@@ -683,6 +684,133 @@ def segment_expected_match(visit, labels, best_path, seg_ends):
         count[i] = len(k)
         expected[i] = v[2 * k + 1].sum()
     return expected, count
+
+
+# ------------------------------------------------------------------------------------------
+# exact boundary-time quantiles: the interval a text boundary lies in
+# ------------------------------------------------------------------------------------------
+MAX_LEVELS = 8
+_LEVEL_MIN = 2.0 ** -10
+
+
+def _levels_of(q):
+    """The levels of a quantile call as float64, checked: 1 to 8 of them, strictly increasing in [2^-10, 1 - 2^-10]."""
+    lv = np.ascontiguousarray(np.asarray(q, dtype=np.float64).reshape(-1))
+    if not 1 <= len(lv) <= MAX_LEVELS:
+        raise ValueError(f"q must hold 1 to {MAX_LEVELS} levels")
+    if not np.all((lv >= _LEVEL_MIN) & (lv <= 1.0 - _LEVEL_MIN)) or np.any(np.diff(lv) <= 0):      # (a NaN fails the first test)
+        raise ValueError("q must be strictly increasing in [2^-10, 1 - 2^-10]")
+    return lv
+
+
+def _cuts_of(cuts, S):
+    """A cut list as int64 NumPy, checked: strictly increasing in [0, 2S+1]."""
+    if _is_tensor(cuts):
+        cuts = cuts.detach().cpu().numpy()
+    c = np.ascontiguousarray(np.asarray(cuts).reshape(-1), dtype=np.int64)
+    if len(c) and (c[0] < 0 or c[-1] > 2 * S + 1 or np.any(np.diff(c) <= 0)):
+        raise ValueError(f"cuts must be strictly increasing in [0, {2 * S + 1}]")
+    return c
+
+
+def ctc_boundary_quantiles(log_probs, labels, terminal, cuts, q=(0.05, 0.5, 0.95), beam_size=1000, max_move=4):
+    """The interval every boundary lies in: (quantile int32 [K, M], log_likelihood float) for K cut positions and M levels.
+
+    tau_c is the first frame whose state is >= c (``expected_crossing_frames``), over every path of the band of
+    ``ctc_best_path`` that ends at state ``terminal`` (an int, or a best path whose last value is used).  quantile[k, m] is
+    the q[m]-quantile of tau at ``cuts[k]``: the first frame t at which P(tau_c <= t) = sum of the state posteriors at
+    positions >= c reaches q[m], and T if none does - so the cut lies in [quantile[k, 0], quantile[k, -1]] with probability
+    about q[-1] - q[0].  This is the exact form of what ``segment_boundary_spread`` estimates from 64 sampled paths: the sum is
+    taken in 32.32 fixed point over the rows ``ctc_state_posteriors`` would write, so it is reproducible bit for bit, and no
+    [T, W] or [64, T] matrix exists.  ``cuts``: strictly increasing in [0, 2S+1] (``boundary_cuts``); ``q``: 1 to 8 levels,
+    strictly increasing in [2^-10, 1 - 2^-10].  Rows and columns ascend.  NumPy in -> NumPy out; ROCm torch tensors go to
+    ``ctc_boundary_quantiles_device``.  Raises as ``ctc_label_posteriors``, and ValueError for bad cuts or levels.
+    """
+    call = ctc_boundary_quantiles_device if _is_tensor(log_probs) else ctc_boundary_quantiles_batch
+    (result,) = call([log_probs], [labels], [terminal], [cuts], q, beam_size, max_move)
+    return result
+
+
+def _boundary_quantiles(lat, terminals, cuts, q, beam_size, max_move, out, return_status):
+    levels = _levels_of(q)
+    if lat is None:
+        return ([], []) if return_status else []
+    if len(cuts) != lat.n:
+        raise ValueError("cuts must hold one list per lattice")
+    cuts = [_cuts_of(c, S) for c, S in zip(cuts, lat.S)]      # (host memory in both forms)
+    M = len(levels)
+    quants = _outputs(lat, out, [(len(c), M) for c in cuts], "[K_i, M]", np.int32)
+    p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
+    p_cut, _k2 = _ptr_array([c.ctypes.data for c in cuts])
+    p_K, _k3 = _i64_array([len(c) for c in cuts])
+    p_q, _k4 = _ptr_array([lat.ptr(x) for x in quants])
+    p_ld, _k5 = _i64_array([max(lat.ld(x), M) for x in quants])   # (a tensor with at most one row may report any stride)
+    return _run_lattices(lat, "boundary_quantiles", beam_size, max_move, (p_term, p_cut, p_K, levels.ctypes.data, M, p_q, p_ld),
+                         list(zip(quants)), return_status)
+
+
+def ctc_boundary_quantiles_batch(log_probs_list, labels_list, terminals, cuts_list, q=(0.05, 0.5, 0.95), beam_size=1000, max_move=4,
+                                 device=None, return_status=False):
+    """Boundary quantiles of many lattices in ONE launch; host NumPy buffers in and out.  ``q`` is one list of levels for
+    every lattice.
+
+    Returns a list of (quantile [K_i, M], log_likelihood); with ``return_status`` also the per-lattice status list, in which
+    case failures do not raise (their quantiles are -1, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    """
+    lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
+    return _boundary_quantiles(lat, terminals, cuts_list, q, beam_size, max_move, None, return_status)
+
+
+def ctc_boundary_quantiles_device(log_probs, labels, terminals, cuts, q=(0.05, 0.5, 0.95), beam_size=1000, max_move=4, out=None,
+                                  return_status=False):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]), terminals (ints or
+    best paths) and host cut lists (strictly increasing in [0, 2 S_i + 1]); list of (quantile int32 tensor [K_i, M] on the
+    device, log_likelihood float) out.  ``out``: optional list of int32 [K_i, M] tensors with unit column stride to write into
+    (views into wider tensors keep their other columns).  One launch on torch's current stream."""
+    lat = _device_lattices(log_probs, labels, terminals, "terminals")
+    return _boundary_quantiles(lat, terminals, cuts, q, beam_size, max_move, out, return_status)
+
+
+def _boundary_cut(path, b, n_ph):
+    return 2 * min(int(path[b]) // 2, n_ph)
+
+
+def boundary_cuts(best_path, seg_ends, n_phonemes):
+    """The cut positions of ``align()``'s text boundaries, sorted and unique (int64): for every boundary frame b of
+    ``boundary_frames(seg_ends, T)`` the text index is i = min(best_path[b] // 2, n_phonemes) and the cut c = 2 i - the cuts
+    of ``segment_boundary_shift``, as ``ctc_boundary_quantiles`` takes them."""
+    path = np.asarray(best_path.detach().cpu() if _is_tensor(best_path) else best_path, dtype=np.int64).reshape(-1)
+    n_ph = int(n_phonemes)
+    return np.unique(np.array([_boundary_cut(path, b, n_ph) for b in boundary_frames(seg_ends, len(path))], dtype=np.int64))
+
+
+def segment_boundary_interval(quantile, cuts, best_path, seg_ends, n_phonemes):
+    """The quantile frames of every text boundary of ``align()`` (host only): (start_q [n_seg, M], end_q [n_seg, M]), int64 per
+    segment that ``align()`` writes a line for (frames [a, b), a = seg_ends[i-1], 0 for the first, b = seg_ends[i]): the
+    quantiles of the boundary read at a and of the one read at b, laid out as ``segment_boundary_spread``'s.  ``quantile`` and
+    ``cuts`` are those of ``ctc_boundary_quantiles`` (``boundary_cuts``, or any list that holds them).  Where b >= T
+    ``align()`` runs the text to its end whatever the path does: the quantiles are T.  Raises ValueError if a cut it needs is
+    not in ``cuts``."""
+    qt = np.asarray(quantile.detach().cpu() if _is_tensor(quantile) else quantile, dtype=np.int64)
+    c = np.asarray(cuts.detach().cpu() if _is_tensor(cuts) else cuts, dtype=np.int64).reshape(-1)
+    if qt.ndim != 2 or qt.shape[0] != len(c):
+        raise ValueError("quantile must be [len(cuts), M]")
+    path = np.asarray(best_path.detach().cpu() if _is_tensor(best_path) else best_path, dtype=np.int64).reshape(-1)
+    T, n_ph = len(path), int(n_phonemes)
+    row_of = {int(v): k for k, v in enumerate(c)}
+    at_end = np.full(qt.shape[1], T, dtype=np.int64)
+
+    def rows(b):
+        if b >= T:
+            return at_end
+        k = row_of.get(_boundary_cut(path, b, n_ph))
+        if k is None:
+            raise ValueError(f"segment_boundary_interval: cut {_boundary_cut(path, b, n_ph)} (frame {int(b)}) is not among the cuts")
+        return qt[k]
+
+    segs = _segments(np.asarray(seg_ends, dtype=np.int64), T)
+    stack = lambda r: np.array(r, dtype=np.int64).reshape(len(r), qt.shape[1])
+    return stack([rows(a) for _, a, _ in segs]), stack([rows(b) for _, _, b in segs])
 
 
 # ------------------------------------------------------------------------------------------

@@ -8,7 +8,10 @@ on the occupancy's shapes and terminals (cases dur_single, dur_b1024); and of ka
 sampled from the band posterior per lattice, ka_sample.hpp, section 4.24) on the same shapes and terminals (cases smp_single,
 smp_b1024); and of ka_ctc_mea_path_batch_f32 (the maximum-expected-accuracy alignment, ka_mea.hpp, section 4.26) on the same
 shapes and terminals (cases mea_single, mea_b1024); and of ka_ctc_state_visits_batch_f32 (state visit probabilities,
-ka_visit.hpp, section 4.27) on the same shapes and terminals (cases vis_single, vis_b1024).
+ka_visit.hpp, section 4.27) on the same shapes and terminals (cases vis_single, vis_b1024); and of
+ka_ctc_boundary_quantiles_batch_f32 (exact boundary-time quantiles, ka_quantile.hpp, section 4.28) at the levels 0.05, 0.5 and
+0.95, with the cuts of boundary_cuts for a segment end every 500 frames of the best path (cases quant_single, quant_b768) and
+with cuts at every even position (cases quantd_single, quantd_b768); b768 is a cfg2 batch of 768, three lattices per CU.
 
     python tools/bench_posteriors.py [--cases single,b1024,b8192,corpus] [--reps 3] [--out profiles/posteriors.jsonl]
     python tools/bench_posteriors.py --cases state_single,state_b1024 --out profiles/state_posteriors_bench.jsonl
@@ -20,6 +23,8 @@ ka_visit.hpp, section 4.27) on the same shapes and terminals (cases vis_single, 
         occ_single,dur_single,mea_single,occ_b1024,dur_b1024,mea_b1024,occ_single,dur_single,mea_single,occ_b1024,dur_b1024,mea_b1024,occ_single,dur_single,mea_single,occ_b1024,dur_b1024,mea_b1024
     python tools/bench_posteriors.py --out profiles/visit_bench.jsonl --cases \
         occ_single,dur_single,vis_single,occ_b1024,dur_b1024,vis_b1024,occ_single,dur_single,vis_single,occ_b1024,dur_b1024,vis_b1024,occ_single,dur_single,vis_single,occ_b1024,dur_b1024,vis_b1024
+    python tools/bench_posteriors.py --reps 5 --out profiles/quantile_bench.jsonl --cases \
+        dur_single,quant_single,quantd_single,dur_b768,quant_b768,quantd_b768,dur_single,quant_single,quantd_single,dur_b768,quant_b768,quantd_b768,dur_single,quant_single,quantd_single,dur_b768,quant_b768,quantd_b768
 
 Device-resident inputs (hash-generated); best paths from the library's own best-path call.  The 8192 batch points its
 lattices at the 1024 batch's log-probs, labels and paths eight times over (distinct outputs): 105 GB of log-probs would
@@ -132,6 +137,22 @@ def time_visits(lps, labs, paths, reps):
     return time_batch("state_visits", "ka_state_visit_workspace_bytes", lps, labs, (term[0], k[0][0], k[1][0]), reps)
 
 
+def time_quantiles(lps, labs, paths, reps, dense, levels=(0.05, 0.5, 0.95)):
+    if dense:
+        cuts = [np.arange(0, 2 * int(x.shape[0]) + 2, 2, dtype=np.int64) for x in labs]
+    else:
+        cuts = [ka.boundary_cuts(p.cpu().numpy(), np.arange(500, int(p.shape[0]), 500), int(x.shape[0])) for p, x in zip(paths, labs)]
+    lv = np.asarray(levels, np.float64)
+    outs = [torch.empty((len(c), len(lv)), dtype=torch.int32, device="cuda") for c in cuts]
+    p_out = _ptr_array([x.data_ptr() for x in outs])
+    p_cut = _ptr_array([c.ctypes.data for c in cuts])
+    Ks = _i64_array([len(c) for c in cuts])
+    ldq = _i64_array([len(lv)] * len(cuts))
+    term = _i64_array(torch.stack([p[-1] for p in paths]).cpu().tolist())
+    return time_batch("boundary_quantiles", "ka_boundary_quantile_workspace_bytes", lps, labs,
+                      (term[0], p_cut[0], Ks[0], lv.ctypes.data, len(lv), p_out[0], ldq[0]), reps, ws_own=(Ks[0], len(lv)))
+
+
 def time_samples(lps, labs, paths, reps, K=64):
     outs = [torch.empty((K, int(x.shape[0])), dtype=torch.int32, device="cuda") for x in lps]
     p_out = _ptr_array([x.data_ptr() for x in outs])
@@ -160,9 +181,9 @@ def main():
     torch.cuda.set_device(0)
     lines = []
     cases = a.cases.split(",")
-    b1024 = None
+    b1024 = b768 = None
     for case in cases:
-        kind = case.split("_")[0] if case.startswith(("occ_", "state_", "dur_", "smp_", "mea_", "vis_")) else "path"
+        kind = case.split("_")[0] if case.startswith(("occ_", "state_", "dur_", "smp_", "mea_", "vis_", "quant_", "quantd_")) else "path"
         case_in = case[len(kind) + 1:] if kind != "path" else case
         if case_in == "single":
             lps, labs = cfg2(1)
@@ -173,6 +194,11 @@ def main():
             lps, labs, paths = b1024
             if case_in == "b8192":
                 lps, labs, paths = lps * 8, labs * 8, paths * 8
+        elif case_in == "b768":
+            if b768 is None:
+                lps, labs = cfg2(768)
+                b768 = (lps, labs, best_paths(lps, labs))
+            lps, labs, paths = b768
         elif case_in == "corpus":
             lps, labs = [], []
             for k, (name, shapes) in enumerate(workloads.corpus()):
@@ -184,7 +210,8 @@ def main():
         if case_in in ("single", "corpus"):
             paths = best_paths(lps, labs)
         ms, st, ll = {"path": time_posteriors, "occ": time_occupancy, "state": time_states, "dur": time_durations, "smp": time_samples,
-                       "mea": time_mea, "vis": time_visits}[kind](lps, labs, paths, a.reps)
+                       "mea": time_mea, "vis": time_visits, "quant": lambda *x: time_quantiles(*x, dense=False),
+                       "quantd": lambda *x: time_quantiles(*x, dense=True)}[kind](lps, labs, paths, a.reps)
         frames = sum(int(x.shape[0]) for x in lps)
         line = dict(case=case, lattices=len(lps), frames=frames, ms_min=round(min(ms), 3), ms_median=round(float(np.median(ms)), 3),
                     frames_per_s=frames / (min(ms) / 1e3), status_ok=int((st == 0).sum()), reps=a.reps)

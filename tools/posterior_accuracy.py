@@ -25,6 +25,14 @@ earlier record is replaced, every other one stays):
 
     KA_ACCURACY_OUT=ratios.jsonl python -m pytest tests/test_state_visits_gpu.py -q -m gpu
     python tools/posterior_accuracy.py ratios.jsonl profiles/posterior_accuracy.json visit exit_time z
+
+The boundary-quantile call (tests/test_boundary_quantiles_gpu.py, tests/quantile_ref.py) is an integer
+result: its keys are shares of a case's (cut, level) pairs - those left out of the comparison with the float64 frames because F
+comes within twice its margin of the level (held against the cap of 0.02), and those of the others that differ (held against 0) -
+and z, which joins the file's records:
+
+    KA_ACCURACY_OUT=ratios.jsonl python -m pytest tests/test_boundary_quantiles_gpu.py -q -m gpu
+    python tools/posterior_accuracy.py ratios.jsonl profiles/posterior_accuracy.json quantile_left_out quantile_mismatch z
 """
 import json
 import math
@@ -34,6 +42,7 @@ CALLS = ("state", "label", "path", "z")
 DURATION_CALLS = ("duration", "time_sum", "duration_sum", "time_sum_sum")
 MEA_CALLS = ("mea", "mea_total", "mea_value")
 VISIT_CALLS = ("visit", "exit_time")
+QUANTILE_CALLS = ("quantile_left_out", "quantile_mismatch")
 
 
 def round_up(x):
@@ -46,7 +55,7 @@ def round_up(x):
 
 def main(src, dst, only=()):
     calls = tuple(only) or CALLS
-    assert all(c in CALLS + DURATION_CALLS + MEA_CALLS + VISIT_CALLS for c in calls), calls
+    assert all(c in CALLS + DURATION_CALLS + MEA_CALLS + VISIT_CALLS + QUANTILE_CALLS for c in calls), calls
     worst = {c: {} for c in calls}
     held = {}                                    # the multiplier the tests held a call against (every record carries it)
     with open(src) as f:
@@ -69,7 +78,7 @@ def main(src, dst, only=()):
             worst[c] = {**{r["test"]: r["ratio"] for r in out["calls"][c]["records"]}, **worst[c]}
         top = max(worst[c].values(), default=0.0)
         # (the duration figures are held against the state call's multiplier: their model is a sum of its per-cell model)
-        m = out["calls"]["state"]["m"] if c in DURATION_CALLS and "state" in out["calls"] else held[c] if c in MEA_CALLS else round_up(2 * top)
+        m = out["calls"]["state"]["m"] if c in DURATION_CALLS and "state" in out["calls"] else held[c] if c in MEA_CALLS + QUANTILE_CALLS else round_up(2 * top)
         out["calls"][c] = {"m": m, "worst_ratio": top, "tests": len(worst[c]),
                            "records": [{"test": t, "ratio": r} for t, r in sorted(worst[c].items())]}
     with open(dst, "w") as f:
