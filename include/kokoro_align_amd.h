@@ -363,6 +363,41 @@ int ka_ctc_mea_path_batch_f32(ka_engine *e, int32_t n, const float *const *log_p
 size_t ka_mea_path_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
                                    int32_t mem);
 
+/*
+ * Best path over a caller-given band: ka_ctc_best_path with the band's low end read from a table
+ * instead of the diagonal of align.py:64-65.  With lab' the blank-expanded labels, L = 2S+1, A_{-1} = {0}, sc_{-1}[0] = 0:
+ *   frame t:  lo_t = band_lo[t],  hi_t = min(lo_t + beam_size, L)
+ *     p in [lo_t, hi_t):  c_j = sc_{t-1}[p-j] (+) lp[t, lab'[p]] for j in [0, max_move) with p-j live after frame t-1, else -inf
+ *                         (float32 add, then compare);  j even, j >= 2, lab'[p] == 0  ->  c_j = -inf
+ *                         j* = the first j attaining the maximum;  p is live iff p-j* is;  sc_t[p] = c_j*
+ *   end = the highest live position of frame T-1 (none: KA_ERR_EMPTY_BEAM); the path is walked back over the j*.
+ * A valid table holds 0 <= band_lo[t] < L and band_lo[t] <= band_lo[t+1]; the step is not limited (one that leaves frame t+1
+ * without a live predecessor is legal and ends in KA_ERR_EMPTY_BEAM).  With band_lo[t] = max(0, L t / T - beam_size / 2) the
+ * call returns the bits of ka_ctc_best_path_f32: path, labels, scores, total score and status.
+ * Arguments and return convention as ka_ctc_best_path[_batch]_f32, plus
+ *   band_lo   [T] int32, where `mem` says (batch: a HOST array of n such pointers)
+ * Per lattice: KA_ERR_BAD_ARGS for an invalid table (checked on the device before any value of it is used; the lattice's
+ * outputs are left untouched), KA_ERR_BAD_LABEL, KA_ERR_NAN, KA_ERR_EMPTY_BEAM; -inf log-probs are legal.  A batch answers
+ * its other lattices and returns the status of the first that failed.  The call uses its own kernels (ka_engine_set_mode /
+ * ka_engine_set_backtrace do not apply): one wavefront per lattice for min(beam_size, L) <= 1009, V <= 64, max_move <= 4, else
+ * one 256-thread workgroup per lattice (any band, any V, max_move <= 255; not tuned).  It synchronises `stream` before it
+ * returns.  Cost against ka_ctc_best_path_batch_f32 in KA_MODE_WAVE_EXACT with KA_BACKTRACE_SERIAL on the diagonal table
+ * (tools/bench_banded.py, profiles/banded_bench.jsonl; MI355X): 1.08 times that call for one cfg2 lattice (33.35 against 30.94 ms),
+ * 1.26 times for 1024 (42.69 against 33.96 ms).
+ */
+int ka_ctc_best_path_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                int32_t beam_size, int32_t max_move, const int32_t *band_lo, int32_t *best_path, int32_t *best_labels,
+                                float *best_scores, float *total_score, int32_t mem, void *stream);
+int ka_ctc_best_path_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                      const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                      const int32_t *const *band_lo, int32_t *const *best_path, int32_t *const *best_labels,
+                                      float *const *best_scores, float *total_score, int32_t *status, int32_t mem, void *stream);
+/* device-workspace bytes such a call carves (0 for unsupported arguments): per lattice the prepared labels and, in the
+ * one-wavefront form, a copy of the table and 256 bytes of codes per frame (generic: a byte per band cell and four columns);
+ * for KA_MEM_HOST also the staged inputs and outputs */
+size_t ka_banded_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                 int32_t mem);
+
 /* Kernel form of the fast path.
  *   KA_MODE_WAVE        one wavefront per lattice, checkpointed (throughput; fills the chip from ~4096
  *                       lattices): the forward kernel keeps scores only and stores the score ring every 32

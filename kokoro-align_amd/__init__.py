@@ -5,7 +5,8 @@ Public surface mirrors the reference (kokoro_align/align.py):
     best_path(input_file, voca_file, output_file)                  align.py:112
     align(best_path_file, mfcc_file, voca_file, align_file, remove_wordsep)   align.py:127
     pandas_read_align(files)                                       align.py:172
-plus batched / device-resident entry points (ctc_best_path_batch, ctc_best_path_device) and the
+plus batched / device-resident entry points (ctc_best_path_batch, ctc_best_path_device), the best path over a band the caller
+gives (ctc_best_path_banded[_batch|_device], diagonal_band, anchored_band, band_around_path, band_edge_contact) and the
 forward-backward quality signal of a best path (ctc_path_posteriors[_batch|_device], segment_confidence), the label
 occupancy of every frame (ctc_label_posteriors[_batch|_device], segment_agreement), the differentiable lattice
 log-likelihood (lattice_log_likelihood) and the state posteriors at chosen frames behind the confidence of align()'s text
@@ -25,10 +26,17 @@ CPU fallback — importing works without a GPU, computing does not.
 from . import encoder, transcript  # noqa: F401
 from .align import (  # noqa: F401
     align,
+    anchored_band,
+    band_around_path,
+    band_edge_contact,
     best_path,
     ctc_best_path,
+    ctc_best_path_banded,
+    ctc_best_path_banded_batch,
+    ctc_best_path_banded_device,
     ctc_best_path_batch,
     ctc_best_path_device,
+    diagonal_band,
     log_softmax_device,
     pandas_read_align,
 )

@@ -45,6 +45,7 @@ EXPORTS = [
     "ka_ctc_state_visits_f32", "ka_ctc_state_visits_batch_f32", "ka_state_visit_workspace_bytes",
     "ka_ctc_mea_path_f32", "ka_ctc_mea_path_batch_f32", "ka_mea_path_workspace_bytes",
     "ka_ctc_boundary_quantiles_f32", "ka_ctc_boundary_quantiles_batch_f32", "ka_boundary_quantile_workspace_bytes",
+    "ka_ctc_best_path_banded_f32", "ka_ctc_best_path_banded_batch_f32", "ka_banded_workspace_bytes",
 ]
 
 
@@ -155,6 +156,12 @@ def load_library():
     L.ka_ctc_mea_path_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pi64, pp, vp, vp, vp, i32, vp]
     L.ka_mea_path_workspace_bytes.restype = sz
     L.ka_mea_path_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
+    L.ka_ctc_best_path_banded_f32.restype = ctypes.c_int
+    L.ka_ctc_best_path_banded_f32.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    L.ka_ctc_best_path_banded_batch_f32.restype = ctypes.c_int
+    L.ka_ctc_best_path_banded_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pp, pp, pp, pp, vp, vp, i32, vp]
+    L.ka_banded_workspace_bytes.restype = sz
+    L.ka_banded_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
     L.ka_engine_set_mode.restype = ctypes.c_int
     L.ka_engine_set_mode.argtypes = [vp, i32]
     L.ka_engine_set_backtrace.restype = ctypes.c_int

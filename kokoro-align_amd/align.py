@@ -6,7 +6,9 @@
     pandas_read_align(files)                                          <- align.py:172-190
 
 plus what the reference has no name for: many lattices in one launch (ctc_best_path_batch, DeviceBatch,
-ctc_best_path_device) and the log-softmax of align.py:116-117 on the device (log_softmax_device).
+ctc_best_path_device), the log-softmax of align.py:116-117 on the device (log_softmax_device) and the best path over a band
+the caller gives (ctc_best_path_banded[_batch|_device] with the tables diagonal_band, anchored_band, band_around_path and the
+diagnostic band_edge_contact).
 
 The DP + backtrace (the reference's per-frame NumPy loop) run in the HIP library through the C
 ABI of include/kokoro_align_amd.h.  NumPy arrays are handed over as host buffers; torch tensors
@@ -239,6 +241,204 @@ def ctc_best_path_device(log_probs, labels, beam_size=1000, max_move=4, verbose=
         batch = DeviceBatch(log_probs, labels, beam_size, max_move)
         batch.run()
     return batch.results()
+
+
+# ------------------------------------------------------------------------------------------
+# best path over a caller-given band
+# ------------------------------------------------------------------------------------------
+def diagonal_band(T, L, beam_size):
+    """The reference's band as a table: lo_t = max(0, L t // T - beam_size // 2) (align.py:64), int64 [T]."""
+    t = np.arange(int(T), dtype=np.int64)
+    return np.maximum(0, np.int64(L) * t // np.int64(T) - np.int64(int(beam_size) // 2))
+
+
+def anchored_band(T, L, anchors, beam_size):
+    """A band of width ``beam_size`` centred on the broken line through ``anchors``: (frame, position) pairs, strictly increasing
+    in frame and non-decreasing in position, between the implied (0, 0) and (T, L).  The centre is interpolated with floor
+    division between neighbours; lo = clip(centre - beam_size // 2, 0, L - 1).  Without anchors it is ``diagonal_band``."""
+    T, L = int(T), int(L)
+    pts = [(0, 0)] + [(int(f), int(p)) for f, p in anchors] + [(T, L)]
+    for (f0, p0), (f1, p1) in zip(pts[:-1], pts[1:]):
+        if f1 <= f0 or p1 < p0:
+            raise ValueError("anchors must be strictly increasing in frame within (0, T) and non-decreasing in position within [0, L]")
+    lo = np.zeros(T, np.int64)
+    for (f0, p0), (f1, p1) in zip(pts[:-1], pts[1:]):
+        t = np.arange(f0, f1, dtype=np.int64)
+        lo[f0:f1] = np.int64(p0) + np.int64(p1 - p0) * (t - f0) // np.int64(f1 - f0) - np.int64(int(beam_size) // 2)
+    return np.clip(lo, 0, L - 1)
+
+
+def band_around_path(path, L, beam_size):
+    """lo_t = clip(path[t] - beam_size // 2, 0, L - 1): the band of a second pass around a first pass's path (monotone because
+    paths only move up)."""
+    return np.clip(np.asarray(path, dtype=np.int64) - np.int64(int(beam_size) // 2), 0, int(L) - 1)
+
+
+def band_edge_contact(best_path, band_lo, beam_size, L, max_move=4):
+    """Frames at which ``best_path`` lies within ``max_move - 1`` positions of the band's low edge lo_t (where lo_t > 0) or of
+    its high edge hi_t - 1 (where hi_t < L): where the band, not the log-probs, may have decided the path.  An edge clamped to
+    the lattice's own end does not count.  Works on any table, ``diagonal_band`` included."""
+    p = np.asarray(best_path, dtype=np.int64)
+    lo = np.asarray(band_lo, dtype=np.int64)
+    hi = np.minimum(lo + np.int64(int(beam_size)), np.int64(int(L)))
+    reach = int(max_move) - 1
+    low = (lo > 0) & (p - lo <= reach)
+    high = (hi < int(L)) & (hi - 1 - p <= reach)
+    return np.nonzero(low | high)[0]
+
+
+def _banded_call(eng, lps, labs, bands, lds, V, beam_size, max_move, paths, louts, souts, mem, stream):
+    """One ka_ctc_best_path_banded_batch_f32 over buffers given by address; returns (rc, status, total)."""
+    n = len(lps)
+    status = np.zeros(n, np.int32)
+    total = np.zeros(n, np.float32)
+    p_lp, _k1 = _ptr_array([x[0] for x in lps])
+    p_lab, _k2 = _ptr_array([x[0] for x in labs])
+    p_band, _k3 = _ptr_array(bands)
+    p_path, _k4 = _ptr_array(paths)
+    p_lout, _k5 = _ptr_array(louts)
+    p_sout, _k6 = _ptr_array(souts)
+    p_T, _k7 = _i64_array([x[1] for x in lps])
+    p_S, _k8 = _i64_array([x[1] for x in labs])
+    p_ld, _k9 = _i64_array(lds)
+    rc = eng.lib.ka_ctc_best_path_banded_batch_f32(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size), int(max_move),
+                                                   p_band, p_path, p_lout, p_sout, total.ctypes.data, status.ctypes.data, mem, stream)
+    return rc, status, total
+
+
+def _host_rows(x):
+    """float32 [T, V] rows as they lie if their columns are adjacent (a view with a row stride is handed over with its ld),
+    else a contiguous copy"""
+    x = np.asarray(x)
+    if x.dtype == np.float32 and x.ndim == 2 and x.shape[1] > 0 and x.strides[1] == 4 and x.strides[0] % 4 == 0 and \
+            x.strides[0] >= 4 * x.shape[1]:
+        return x
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def _check_band(band, T):
+    b = np.asarray(band)
+    if b.ndim != 1 or b.shape[0] != T:
+        raise ValueError("band_lo must hold one entry per frame")
+    if b.size and (b.min() < -2 ** 31 or b.max() >= 2 ** 31):
+        raise ValueError("band_lo: entries must fit int32")
+    return np.ascontiguousarray(b, dtype=np.int32)
+
+
+def ctc_best_path_banded_batch(log_probs_list, labels_list, band_lo_list, beam_size=1000, max_move=4, device=None,
+                               return_status=False, outputs=None):
+    """``ctc_best_path_batch`` over caller-given bands: frame t of lattice i searches positions [band_lo[t], min(band_lo[t] +
+    beam_size, 2S+1)).  Host NumPy buffers in and out.  A table must be non-decreasing with entries in [0, 2S+1) (status -2,
+    ValueError); a band that loses every live state raises ValueError like the reference's empty beam (status -1).  With
+    ``return_status`` failures do not raise and (results, statuses, totals) are returned; a failed lattice's arrays are not written.
+    ``outputs``: (paths, labels, scores), lists of contiguous int32 / int32 / float32 arrays of T_i elements to write into."""
+    n = len(log_probs_list)
+    assert n == len(labels_list) == len(band_lo_list)
+    if n == 0:
+        return ([], [], []) if return_status else []
+    lps = [_host_rows(x) for x in log_probs_list]
+    labs = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32) for x in labels_list]
+    V = lps[0].shape[1] if lps[0].ndim == 2 else 0
+    for x in lps:
+        if x.ndim != 2 or x.shape[1] != V:
+            raise ValueError("all log_probs must be [T_i, V] with one V")
+        if x.shape[0] == 0:
+            raise IndexError("list index out of range")
+    bands = [_check_band(b, x.shape[0]) for b, x in zip(band_lo_list, lps)]
+    if outputs is None:
+        paths = [np.empty(x.shape[0], np.int32) for x in lps]
+        louts = [np.empty(x.shape[0], np.int32) for x in lps]
+        souts = [np.empty(x.shape[0], np.float32) for x in lps]
+    else:
+        paths, louts, souts = outputs
+        for arrs, dt in ((paths, np.int32), (louts, np.int32), (souts, np.float32)):
+            for a, x in zip(arrs, lps):
+                if a.dtype != dt or a.shape != (x.shape[0],) or not a.flags.c_contiguous:
+                    raise ValueError("outputs must be contiguous arrays of T_i elements: int32 paths and labels, float32 scores")
+    eng = _lib.default_engine(_current_device() if device is None else device)
+    rc, status, total = _banded_call(eng, [(x.ctypes.data, x.shape[0]) for x in lps], [(x.ctypes.data, x.shape[0]) for x in labs],
+                                     [b.ctypes.data for b in bands], [max(V, x.strides[0] // 4) for x in lps], V, beam_size, max_move,
+                                     [x.ctypes.data for x in paths], [x.ctypes.data for x in louts], [x.ctypes.data for x in souts],
+                                     _lib.KA_MEM_HOST, None)
+    results = list(zip(paths, louts, souts))
+    if return_status:
+        if rc not in (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_BAD_ARGS) or \
+                (rc == _lib.KA_ERR_BAD_ARGS and not np.any(status == _lib.KA_ERR_BAD_ARGS)):
+            _lib.check(rc, "ctc_best_path_banded_batch")
+        return results, status.tolist(), total
+    _lib.check(rc, "ctc_best_path_banded_batch")
+    return results
+
+
+def ctc_best_path_banded_device(log_probs, labels, band_lo, beam_size=1000, max_move=4, return_status=False, outputs=None):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V], integer labels [S_i], integer tables [T_i]; labels and tables
+    may also be NumPy arrays), list of (best_path, best_labels, best_scores) tensors out.  One launch for the whole list; a table
+    built on the device from a device-resident path needs no round trip.  ``outputs``: (paths, labels, scores), lists of contiguous
+    int32 / int32 / float32 tensors of T_i elements on the same device to write into."""
+    import torch
+    n = len(log_probs)
+    assert n == len(labels) == len(band_lo) and n > 0
+    dev = log_probs[0].device
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    V = int(log_probs[0].shape[1])
+    lps, labs, bands = [], [], []
+    for lp, lab, band in zip(log_probs, labels, band_lo):
+        if lp.dim() != 2 or lp.shape[1] != V:
+            raise ValueError("all log_probs must be [T_i, V] with one V")
+        if lp.shape[0] == 0:
+            raise IndexError("list index out of range")
+        if lp.dtype != torch.float32:
+            lp = lp.float()
+        if lp.stride(1) != 1:
+            lp = lp.contiguous()
+        if not _is_tensor(lab):
+            lab = torch.as_tensor(np.asarray(lab).reshape(-1).astype(np.int32))
+        if not _is_tensor(band):
+            band = torch.as_tensor(_check_band(band, lp.shape[0]))
+        if band.dim() != 1 or band.shape[0] != lp.shape[0]:
+            raise ValueError("band_lo must hold one entry per frame")
+        lps.append(lp)
+        labs.append(lab.reshape(-1).to(device=dev, dtype=torch.int32).contiguous())
+        bands.append(band.to(device=dev, dtype=torch.int32).contiguous())
+    if outputs is None:
+        paths = [torch.empty(x.shape[0], dtype=torch.int32, device=dev) for x in lps]
+        louts = [torch.empty(x.shape[0], dtype=torch.int32, device=dev) for x in lps]
+        souts = [torch.empty(x.shape[0], dtype=torch.float32, device=dev) for x in lps]
+    else:
+        paths, louts, souts = outputs
+        for arrs, dt in ((paths, torch.int32), (louts, torch.int32), (souts, torch.float32)):
+            for a, x in zip(arrs, lps):
+                if a.dtype != dt or tuple(a.shape) != (x.shape[0],) or not a.is_contiguous() or a.device != dev:
+                    raise ValueError("outputs must be contiguous tensors of T_i elements on the inputs' device")
+    eng = _lib.default_engine(idx)
+    with torch.cuda.device(dev):
+        rc, status, total = _banded_call(eng, [(x.data_ptr(), x.shape[0]) for x in lps], [(x.data_ptr(), x.shape[0]) for x in labs],
+                                         [b.data_ptr() for b in bands], [x.stride(0) for x in lps], V, beam_size, max_move,
+                                         [x.data_ptr() for x in paths], [x.data_ptr() for x in louts], [x.data_ptr() for x in souts],
+                                         _lib.KA_MEM_DEVICE, _stream_ptr(idx))
+    results = list(zip(paths, louts, souts))
+    if return_status:
+        if rc not in (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_BAD_ARGS) or \
+                (rc == _lib.KA_ERR_BAD_ARGS and not np.any(status == _lib.KA_ERR_BAD_ARGS)):
+            _lib.check(rc, "ctc_best_path_banded_device")
+        return results, status.tolist(), total
+    _lib.check(rc, "ctc_best_path_banded_device")
+    return results
+
+
+def ctc_best_path_banded(log_probs, labels, band_lo, beam_size=1000, max_move=4):
+    """``ctc_best_path`` over a caller-given band: frame t searches positions [band_lo[t], min(band_lo[t] + beam_size, 2S+1))
+    instead of the reference's diagonal (align.py:64-65); everything else is the reference's.  ``band_lo`` [T] integers,
+    non-decreasing, in [0, 2S+1): ``diagonal_band`` (the reference's, and then the result is ``ctc_best_path``'s bit for bit),
+    ``anchored_band``, ``band_around_path`` or any table of the caller's.  NumPy in -> NumPy out; ROCm torch tensors in ->
+    torch tensors out.  Raises ValueError where ``ctc_best_path`` does (no live state in the last frame) and for an invalid
+    table; ``band_edge_contact`` says whether the path it returns leant on the band."""
+    if _is_tensor(log_probs):
+        return ctc_best_path_banded_device([log_probs], [labels], [band_lo], beam_size, max_move)[0]
+    lp = np.asarray(log_probs)
+    if lp.ndim != 2:
+        raise ValueError("log_probs must be [T, V]")
+    return ctc_best_path_banded_batch([lp], [labels], [band_lo], beam_size, max_move)[0]
 
 
 def log_softmax_device(logits, out=None):

@@ -1,8 +1,8 @@
 // ka_engine_fb.hip — the forward-backward calls of the C ABI: best-path posteriors (ka_posterior.hpp), label occupancy
 // (ka_occupancy.hpp), state posteriors at chosen frames (ka_state_posterior.hpp), expected state durations (ka_duration.hpp),
 // state visit probabilities (ka_visit.hpp), exact boundary-time quantiles (ka_quantile.hpp), alignments sampled from the band
-// posterior (ka_sample.hpp) and the maximum-expected-accuracy alignment (ka_mea.hpp).  Host
-// code only.
+// posterior (ka_sample.hpp) and the maximum-expected-accuracy alignment (ka_mea.hpp); and, with a driver of its own
+// (banded_impl), the best path over a caller-given band (ka_banded.hpp).  Host code only.
 // They use the engine's workspace and pinned buffer, with their own kernels and workspace layout, whatever
 // the engine's mode, and run to the end inside the call: no batch stays in flight.
 #include "ka_engine.hpp"
@@ -552,9 +552,149 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
     return first_bad;
 }
 
+
+// ---- best path over a caller-given band (ka_banded.hpp): its own kernels and workspace layout, whatever the engine's mode ----
+int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move, const int32_t *const *band_lo,
+                int32_t *const *best_path, int32_t *const *best_labels, float *const *best_scores, float *total_score, int32_t *status,
+                int32_t mem, hipStream_t stream)
+{
+    using Desc = ka::BandLattice;
+    const bool host = mem == KA_MEM_HOST;
+    if (!e) return fail(KA_ERR_BAD_ARGS, "engine is NULL");
+    if (e->batch.pending) return fail(KA_ERR_BAD_ARGS, "a batch is already enqueued: call ka_batch_finish first");
+    if (n < 0 || (n > 0 && (!log_probs || !T || !ld || !labels || !S || !band_lo || !best_path || !best_labels || !best_scores)))
+        return fail(KA_ERR_BAD_ARGS, "banded best path: NULL array argument");
+    if (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE) return fail(KA_ERR_BAD_ARGS, "mem must be KA_MEM_HOST or KA_MEM_DEVICE");
+    if (n == 0) return KA_OK;
+    std::vector<ka::plan::BandCarve> cv(n);
+    size_t off_meta = 0;
+    const size_t total = ka::plan::banded_workspace(n, T, S, V, beam_size, max_move, host, cv.data(), &off_meta);
+    if (total == 0) return fail(KA_ERR_BAD_ARGS, "banded best path: unsupported T/S/V/beam_size/max_move");
+    for (int32_t i = 0; i < n; ++i) {
+        if (ld[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld < V");
+        if (!log_probs[i] || !band_lo[i] || !best_path[i] || !best_labels[i] || !best_scores[i] || (S[i] > 0 && !labels[i]))
+            return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": NULL buffer");
+    }
+    DeviceGuard guard;
+    KA_HIP(guard.enter(e->device));
+    int rc = ensure_ws(e, total);
+    if (rc != KA_OK) return rc;
+    const size_t desc_bytes = align_up((size_t)n * sizeof(Desc));
+    rc = ensure_pin(e, desc_bytes + (size_t)n * sizeof(ka::LatticeMeta));
+    if (rc != KA_OK) return rc;
+    // the workspace is shared with the best-path calls (see fb_impl)
+    if (e->res.refill_done) KA_HIP(hipStreamWaitEvent(stream, e->res.refill_done, 0));
+    e->clean.invalidate();
+    e->dbg = ka_engine::DebugView();
+    char *ws = e->res.ws;
+    Desc *h = reinterpret_cast<Desc *>(e->res.pin);
+    ka::LatticeMeta *h_meta = reinterpret_cast<ka::LatticeMeta *>(e->res.pin + desc_bytes);
+    int32_t n_fast = 0;
+    for (int32_t i = 0; i < n; ++i) n_fast += cv[i].fast ? 1 : 0;
+    int32_t k_fast = 0, k_gen = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const ka::plan::BandCarve &c = cv[i];
+        Desc &d = h[c.fast ? k_fast++ : n_fast + k_gen++];
+        std::memset(&d, 0, sizeof(d));
+        if (host) {
+            d.lp = reinterpret_cast<const float *>(ws + c.lp);
+            d.labels = reinterpret_cast<const int32_t *>(ws + c.lab);
+            d.band_lo = reinterpret_cast<const int32_t *>(ws + c.band);
+            d.path = reinterpret_cast<int32_t *>(ws + c.path);
+            d.lab_out = reinterpret_cast<int32_t *>(ws + c.lab_out);
+            d.sc_out = reinterpret_cast<float *>(ws + c.sc_out);
+            d.ld = V;
+        } else {
+            d.lp = log_probs[i];
+            d.labels = labels[i];
+            d.band_lo = band_lo[i];
+            d.path = best_path[i];
+            d.lab_out = best_labels[i];
+            d.sc_out = best_scores[i];
+            d.ld = ld[i];
+        }
+        d.labx = reinterpret_cast<int32_t *>(ws + c.labx);
+        d.tab = c.fast ? reinterpret_cast<int32_t *>(ws + c.tab) : nullptr;
+        d.bp = ws + c.bp;
+        d.col = c.fast ? nullptr : reinterpret_cast<float *>(ws + c.col);
+        d.T = (int32_t)T[i];
+        d.S = (int32_t)S[i];
+        d.L = (int32_t)(2 * S[i] + 1);
+        d.V = V;
+        d.beam = beam_size;
+        d.max_move = max_move;
+        d.labx_len = c.labx_len;
+        d.W = c.W;
+        d.tab_len = c.tab_len;
+        d.idx = i;
+    }
+    if (host)
+        for (int32_t i = 0; i < n; ++i) {
+            KA_HIP(hipMemcpy2DAsync(ws + cv[i].lp, (size_t)V * 4, log_probs[i], (size_t)ld[i] * 4, (size_t)V * 4, (size_t)T[i], hipMemcpyHostToDevice,
+                                    stream));
+            if (S[i] > 0) KA_HIP(hipMemcpyAsync(ws + cv[i].lab, labels[i], (size_t)S[i] * 4, hipMemcpyHostToDevice, stream));
+            KA_HIP(hipMemcpyAsync(ws + cv[i].band, band_lo[i], (size_t)T[i] * 4, hipMemcpyHostToDevice, stream));
+        }
+    Desc *d_lats = reinterpret_cast<Desc *>(ws);
+    int32_t *d_meta = reinterpret_cast<int32_t *>(ws + off_meta);
+    KA_HIP(hipMemcpyAsync(d_lats, h, (size_t)n * sizeof(Desc), hipMemcpyHostToDevice, stream));
+    KA_HIP(hipMemsetAsync(d_meta, 0, (size_t)n * sizeof(ka::LatticeMeta), stream));
+    ka::launch_best_path_banded(d_lats, n_fast, n - n_fast, max_move, d_meta, stream);
+    KA_HIP(hipGetLastError());
+    KA_HIP(hipMemcpyAsync(h_meta, d_meta, (size_t)n * sizeof(ka::LatticeMeta), hipMemcpyDeviceToHost, stream));
+    KA_HIP(hipStreamSynchronize(stream));
+    if (host) {   // only what succeeded is copied out: a failed lattice's outputs stay as the caller left them
+        for (int32_t i = 0; i < n; ++i) {
+            if (h_meta[i].status != KA_OK) continue;
+            const size_t bytes = (size_t)T[i] * 4;
+            KA_HIP(hipMemcpyAsync(best_path[i], ws + cv[i].path, bytes, hipMemcpyDeviceToHost, stream));
+            KA_HIP(hipMemcpyAsync(best_labels[i], ws + cv[i].lab_out, bytes, hipMemcpyDeviceToHost, stream));
+            KA_HIP(hipMemcpyAsync(best_scores[i], ws + cv[i].sc_out, bytes, hipMemcpyDeviceToHost, stream));
+        }
+        KA_HIP(hipStreamSynchronize(stream));
+    }
+    int first_bad = KA_OK;
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t st = h_meta[i].status;
+        if (status) status[i] = st;
+        if (total_score) total_score[i] = h_meta[i].score;
+        if (st != KA_OK && first_bad == KA_OK) {
+            first_bad = st;
+            g_err = "lattice " + std::to_string(i) +
+                    status_message(st, {": no live state in the last frame", nullptr, nullptr,
+                                        ": band_lo must hold non-decreasing values in [0, 2S+1)", nullptr});
+        }
+    }
+    return first_bad;
+}
+
 }  // namespace
 
 extern "C" {
+
+int ka_ctc_best_path_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                      const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                      const int32_t *const *band_lo, int32_t *const *best_path, int32_t *const *best_labels,
+                                      float *const *best_scores, float *total_score, int32_t *status, int32_t mem, void *stream)
+{
+    return banded_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, band_lo, best_path, best_labels, best_scores, total_score,
+                       status, mem, (hipStream_t)stream);
+}
+
+int ka_ctc_best_path_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                int32_t beam_size, int32_t max_move, const int32_t *band_lo, int32_t *best_path, int32_t *best_labels,
+                                float *best_scores, float *total_score, int32_t mem, void *stream)
+{
+    return banded_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo, &best_path, &best_labels, &best_scores,
+                       total_score, nullptr, mem, (hipStream_t)stream);
+}
+
+size_t ka_banded_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::banded_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
 
 int ka_ctc_path_posteriors_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
                                      const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,

@@ -1,6 +1,6 @@
 // ka_launch.hpp — the host-callable launch functions of every device translation unit.
 //
-// The library is built from fifteen translation units so that the device code compiles in parallel (a single unit took three
+// The library is built from eighteen translation units so that the device code compiles in parallel (a single unit took three
 // minutes): ka_engine.hip, ka_engine_fb.hip and ka_entry_misc.hip are host code only and reach the kernels through these
 // functions; each kernel family lives in the .hip file named below and nowhere else.  All functions only enqueue; errors
 // surface through hipGetLastError().
@@ -110,5 +110,10 @@ void launch_state_visits(const VisitLattice *lats, int n_fast, int n_generic, in
 // ---- ka_quantile.hip: exact boundary-time quantiles (ka_quantile.hpp): ka_fb_ck.hpp's driver with one more policy,
 // launch_fb_ck's form split, grid and slots ----
 void launch_boundary_quantiles(const QuantLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+
+// ---- ka_banded.hip: best path over a caller-given band (ka_banded.hpp).  Descriptors [0, n_fast): one wavefront per lattice
+// (band <= kFastMaxBand, V <= 64, max_move <= 4), then [n_fast, n_fast + n_generic): one 256-thread workgroup per lattice.
+// `meta` (zeroed by the caller): a LatticeMeta per lattice of the batch ----
+void launch_best_path_banded(const BandLattice *lats, int n_fast, int n_generic, int max_move, int32_t *meta, hipStream_t s);
 
 }  // namespace ka

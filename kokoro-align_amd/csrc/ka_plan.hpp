@@ -952,3 +952,57 @@ inline size_t mea_path_workspace(int32_t n, const int64_t *T, const int64_t *S, 
 
 }  // namespace plan
 }  // namespace ka
+
+namespace ka {
+namespace plan {
+
+// ---- ka_ctc_best_path_banded_batch_f32 (ka_banded.hpp): workspace layout ----
+// descriptors, a LatticeMeta per lattice, then per lattice: the prepared labels, in the one-wavefront form the shifted and
+// padded table (4 ceil(T/4) + 4 int32) and the codes (256 bytes per frame, whole groups of four frames), in the generic form a
+// byte per band cell and the two score / two liveness columns; for host buffers the staged log-probs, labels, table and the three
+// outputs of every lattice.
+struct BandCarve {
+    size_t lp, lab, band, path, lab_out, sc_out;   // host buffers only
+    size_t labx, tab, bp, col;
+    int32_t labx_len, tab_len, W;
+    bool fast;
+};
+inline size_t banded_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
+                               BandCarve *cv, size_t *off_meta)
+{
+    size_t off = align_up((size_t)n * sizeof(BandLattice));
+    if (off_meta) *off_meta = off;
+    off += align_up((size_t)n * sizeof(LatticeMeta));
+    for (int32_t i = 0; i < n; ++i) {
+        Shape sh;
+        if (!shape_of(T[i], S[i], V, beam, max_move, sh)) return 0;
+        BandCarve c{};
+        c.fast = sh.fast;
+        c.labx_len = sh.labx_len;
+        c.W = (int32_t)sh.W;
+        c.tab_len = (int32_t)(((sh.T + 3) / 4) * 4 + 4);
+        c.labx = off;
+        off += align_up((size_t)sh.labx_len * 4);
+        c.tab = off;
+        if (c.fast) off += align_up((size_t)c.tab_len * 4);
+        c.bp = off;
+        off += align_up(c.fast ? (((size_t)sh.T + 3) / 4) * 1024 : (size_t)sh.T * (size_t)sh.W);
+        c.col = off;
+        if (!c.fast) off += align_up((size_t)sh.L * 2 * sizeof(float) + (size_t)sh.L * 2);
+        if (host_buffers) {
+            c.lp = off;
+            off += align_up((size_t)sh.T * (size_t)V * 4);
+            c.lab = off;
+            off += align_up((size_t)sh.S * 4);
+            for (size_t *x : {&c.band, &c.path, &c.lab_out, &c.sc_out}) {
+                *x = off;
+                off += align_up((size_t)sh.T * 4);
+            }
+        }
+        if (cv) cv[i] = c;
+    }
+    return off;
+}
+
+}  // namespace plan
+}  // namespace ka

@@ -242,4 +242,25 @@ static_assert(sizeof(PostLattice) == 88 && sizeof(FbCkLattice) == 104 && sizeof(
                   sizeof(QuantLattice) == 152,
               "descriptor sizes");
 
+// ---- best path over a caller-given band (ka_banded.hpp) ----
+struct BandLattice {
+    const float *lp;          // [T, ld] log-probs (device)
+    const int32_t *labels;    // [S] caller labels (device)
+    const int32_t *band_lo;   // [T] the caller's table (device): lo_t
+    int32_t *labx;            // [labx_len] 4*label of odd position 2i+1, zero padded (workspace)
+    int32_t *tab;             // one-wavefront form: [tab_len] band_lo[min(i+1, T-1)], 16-byte aligned (workspace); generic: NULL
+    void *bp;                 // one-wavefront form: uint32 [ceil(T/4)][64 lanes][4 frames]; generic: uint8 [T][W]
+    float *col;               // generic only: 2 x L float scores followed by 2 x L present bytes
+    int32_t *path;            // [T] outputs (device)
+    int32_t *lab_out;
+    float *sc_out;
+    int64_t ld;
+    int32_t T, S, L, V;
+    int32_t beam, max_move;
+    int32_t labx_len, W;      // W = max(1, min(beam, L))
+    int32_t tab_len;          // 4 ceil(T/4) + 4
+    int32_t idx;              // index of this lattice in the caller's batch (its LatticeMeta)
+};
+static_assert(sizeof(BandLattice) == 128, "descriptor sizes");
+
 }  // namespace ka
