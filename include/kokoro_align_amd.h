@@ -398,6 +398,62 @@ int ka_ctc_best_path_banded_batch_f32(ka_engine *e, int32_t n, const float *cons
 size_t ka_banded_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
                                  int32_t mem);
 
+/*
+ * Forward-backward posteriors over a caller-given band: ka_ctc_path_posteriors, ka_ctc_label_posteriors,
+ * ka_ctc_state_posteriors and ka_ctc_state_durations on the band of ka_ctc_best_path_banded instead of the reference's
+ * diagonal, so that a path found under a table can be judged under the same table.  Each call is its sibling with one
+ * argument added behind max_move, the table:
+ *   single call   const int32_t *band_lo          [T] int32, where `mem` says
+ *   batch call    const int32_t *const *band_lo   a HOST array of n such pointers
+ * (the state-posterior calls name it band_table: their band_lo is the output they always had, which now holds the table's
+ * value at every query frame).  lo_t = band_lo[t], hi_t = min(lo_t + beam_size, 2S+1); a valid table holds
+ * 0 <= band_lo[t] < 2S+1 and band_lo[t] <= band_lo[t+1], with steps of any size.  Everything else - the recurrences, the veto,
+ * the statuses, the outputs of a failed lattice, the stream synchronisation, the Z bits the calls share - is as the sibling
+ * documents.  The table is checked on the device before any of its values is used: an invalid one gives its lattice
+ * KA_ERR_BAD_ARGS and the sibling's failure outputs (NaN outputs, band_lo -1, log-likelihood NaN) while the other lattices of
+ * the batch are answered; a step that leaves a frame without a live predecessor ends in KA_ERR_ZERO_MASS.  A position that no
+ * frame's band holds has duration and time_sum 0.  A NULL array or entry fails the call with KA_ERR_BAD_ARGS before anything is
+ * launched.  With the reference's diagonal as the table every call returns its sibling's bits.
+ */
+int ka_ctc_path_posteriors_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels,
+                                      int64_t S, int32_t beam_size, int32_t max_move, const int32_t *band_lo, const int32_t *best_path,
+                                      float *posteriors, double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_path_posteriors_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                            const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                            int32_t max_move, const int32_t *const *band_lo, const int32_t *const *best_path,
+                                            float *const *posteriors, double *log_likelihood, int32_t *status, int32_t mem,
+                                            void *stream);
+int ka_ctc_label_posteriors_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels,
+                                       int64_t S, int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal,
+                                       float *occupancy, int64_t ld_out, double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_label_posteriors_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                             const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                             int32_t max_move, const int32_t *const *band_lo, const int64_t *terminal,
+                                             float *const *occupancy, const int64_t *ld_out, double *log_likelihood, int32_t *status,
+                                             int32_t mem, void *stream);
+int ka_ctc_state_posteriors_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels,
+                                       int64_t S, int32_t beam_size, int32_t max_move, const int32_t *band_table, int64_t terminal,
+                                       const int64_t *frames, int64_t K, float *gamma, int64_t ld_out, int64_t *band_lo,
+                                       double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_state_posteriors_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                             const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                             int32_t max_move, const int32_t *const *band_table, const int64_t *terminal,
+                                             const int64_t *const *frames, const int64_t *K, float *const *gamma,
+                                             const int64_t *ld_out, int64_t *const *band_lo, double *log_likelihood, int32_t *status,
+                                             int32_t mem, void *stream);
+int ka_ctc_state_durations_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels,
+                                      int64_t S, int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal,
+                                      double *duration, double *time_sum, double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_state_durations_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                            const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                            int32_t max_move, const int32_t *const *band_lo, const int64_t *terminal,
+                                            double *const *duration, double *const *time_sum, double *log_likelihood, int32_t *status,
+                                            int32_t mem, void *stream);
+/* device-workspace bytes a banded call carves BEYOND its sibling's ka_*_workspace_bytes figure (the descriptors that carry the
+ * table and, for KA_MEM_HOST, the staged tables): reserving the sum keeps the call free of allocations.  0 for unsupported
+ * arguments. */
+size_t ka_band_table_workspace_bytes(int32_t n, const int64_t *T, int32_t mem);
+
 /* Kernel form of the fast path.
  *   KA_MODE_WAVE        one wavefront per lattice, checkpointed (throughput; fills the chip from ~4096
  *                       lattices): the forward kernel keeps scores only and stores the score ring every 32

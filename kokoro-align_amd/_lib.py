@@ -46,6 +46,10 @@ EXPORTS = [
     "ka_ctc_mea_path_f32", "ka_ctc_mea_path_batch_f32", "ka_mea_path_workspace_bytes",
     "ka_ctc_boundary_quantiles_f32", "ka_ctc_boundary_quantiles_batch_f32", "ka_boundary_quantile_workspace_bytes",
     "ka_ctc_best_path_banded_f32", "ka_ctc_best_path_banded_batch_f32", "ka_banded_workspace_bytes",
+    "ka_ctc_path_posteriors_banded_f32", "ka_ctc_path_posteriors_banded_batch_f32",
+    "ka_ctc_label_posteriors_banded_f32", "ka_ctc_label_posteriors_banded_batch_f32",
+    "ka_ctc_state_posteriors_banded_f32", "ka_ctc_state_posteriors_banded_batch_f32",
+    "ka_ctc_state_durations_banded_f32", "ka_ctc_state_durations_banded_batch_f32", "ka_band_table_workspace_bytes",
 ]
 
 
@@ -162,6 +166,16 @@ def load_library():
     L.ka_ctc_best_path_banded_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pp, pp, pp, pp, vp, vp, i32, vp]
     L.ka_banded_workspace_bytes.restype = sz
     L.ka_banded_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
+    # the forward-backward calls over a caller-given band: their siblings' arguments with the table behind max_move (the
+    # tenth argument of a single call, a pointer; the eleventh of a batch call, an array of pointers)
+    for call in ("path_posteriors", "label_posteriors", "state_posteriors", "state_durations"):
+        for form, at, kind in (("", 9, vp), ("_batch", 10, pp)):
+            sibling = getattr(L, f"ka_ctc_{call}{form}_f32")
+            banded = getattr(L, f"ka_ctc_{call}_banded{form}_f32")
+            banded.restype = ctypes.c_int
+            banded.argtypes = sibling.argtypes[:at] + [kind] + sibling.argtypes[at:]
+    L.ka_band_table_workspace_bytes.restype = sz
+    L.ka_band_table_workspace_bytes.argtypes = [i32, pi64, i32]
     L.ka_engine_set_mode.restype = ctypes.c_int
     L.ka_engine_set_mode.argtypes = [vp, i32]
     L.ka_engine_set_backtrace.restype = ctypes.c_int

@@ -1,6 +1,6 @@
 // ka_duration.hpp — expected state durations: for every position s of the blank-expanded labels the time-marginal of the
 // posterior gamma_t(s) and its first time moment, over the band's paths that end at a caller-given terminal s*, and
-// Z = alpha_{T-1}(s*).  Included by ka_duration.hip only.
+// Z = alpha_{T-1}(s*).  Included by ka_duration.hip and ka_duration_banded.hip.
 //   D(s) = sum over t of gamma_t(s)       expected number of frames spent in s
 //   B(s) = sum over t of t gamma_t(s)     (B / D: the expected centre frame of s)
 //
@@ -14,7 +14,9 @@
 // accumulators are two more LDS rings (position p at the form's column slot, p & 1023), which one wavefront reads and writes in
 // program order.  Going back the band slides down: before frame t's cells the positions [hi_t, hi_{t+1}) have left the band
 // for good and are retired - written to the outputs, their slots zeroed - so a live position (the band is at most 1009 wide)
-// never shares a slot with a sum that is still held.  After frame 0, [0, hi_0) is written.  Positions no band holds get 0.
+// never shares a slot with a sum that is still held.  After frame 0, [lo_0, hi_0) is written, and under a caller's table, whose
+// lo_0 may lie above 0, zeros below it.  Positions no band holds get 0: the retiring loop runs over all of [hi_t, hi_{t+1}),
+// however far a table's band jumped, and tells what frame t + 1 held from what it jumped over.
 // Generic form: the outputs themselves at absolute positions, zeroed first, ordered from frame to frame by the barrier of
 // the frame's reduction (as the working columns are).
 #pragma once
@@ -23,7 +25,7 @@
 namespace ka {
 
 // fb_ck's policy.  The forms differ in where the accumulators live (above); a position's place in them is the form's column slot.
-template <class Form>
+template <class Form, class Band = BandWalk>
 struct DurOut {
     static constexpr int NT = Form::NT;
     const DurLattice &d;
@@ -95,6 +97,11 @@ struct DurOut {
             d.dur[p] = accD[Form::cslot(p)];
             if (d.tsum) d.tsum[p] = accB[Form::cslot(p)];
         }
+        if constexpr (Band::kTable)   // a table may start above 0: no band holds [0, lo_0)
+            for (int64_t p = threadIdx.x; p < lo; p += NT) {
+                d.dur[p] = 0.0;
+                if (d.tsum) d.tsum[p] = 0.0;
+            }
     }
 };
 
@@ -109,6 +116,21 @@ __global__ __launch_bounds__(Form::NT) void duration_kernel(const DurLattice *__
         Form f(lats[i], sh);
         DurOut<Form> out(lats[i], ringD, ringB);
         fb_ck(f, res, cav, out);
+        f.sync();
+    }
+}
+// ... over the caller's table (ka_duration_banded.hip)
+template <class Form>
+__global__ __launch_bounds__(Form::NT) void duration_banded_kernel(const Banded<DurLattice> *__restrict__ lats, int n, PostResult *res)
+{
+    __shared__ typename Form::template Shared<4> sh;
+    __shared__ double cav[kPostCk];
+    __shared__ double ringD[1024];
+    __shared__ double ringB[1024];
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        Form f(lats[i], sh);
+        DurOut<Form, BandTable> out(lats[i], ringD, ringB);
+        fb_ck<Form, DurOut<Form, BandTable>, BandTable>(f, res, cav, out, lats[i].band_lo);
         f.sync();
     }
 }

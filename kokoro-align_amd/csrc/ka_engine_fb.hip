@@ -2,7 +2,8 @@
 // (ka_occupancy.hpp), state posteriors at chosen frames (ka_state_posterior.hpp), expected state durations (ka_duration.hpp),
 // state visit probabilities (ka_visit.hpp), exact boundary-time quantiles (ka_quantile.hpp), alignments sampled from the band
 // posterior (ka_sample.hpp) and the maximum-expected-accuracy alignment (ka_mea.hpp); and, with a driver of its own
-// (banded_impl), the best path over a caller-given band (ka_banded.hpp).  Host code only.
+// (banded_impl), the best path over a caller-given band (ka_banded.hpp).  The first four also run over a caller-given band
+// (ka_ctc_*_banded_*: fb_impl<Call, true>, the same driver on Banded<Desc> descriptors).  Host code only.
 // They use the engine's workspace and pinned buffer, with their own kernels and workspace layout, whatever
 // the engine's mode, and run to the end inside the call: no batch stays in flight.
 #include "ka_engine.hpp"
@@ -10,6 +11,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 namespace {
 
@@ -35,6 +37,7 @@ struct FbArgs {
     int32_t *status;
     int32_t mem;
     hipStream_t stream;
+    const int32_t *const *band_lo;   // NULL: the reference's diagonal band; else a table per lattice ([T] int32, where `mem` says)
 };
 
 struct PostCall {
@@ -51,6 +54,7 @@ struct PostCall {
     bool buffers(int32_t i) const { return best_path[i] && posteriors[i]; }
     static constexpr auto plan = ka::plan::posterior_workspace;
     static constexpr auto launch = ka::launch_posteriors;
+    static constexpr auto launch_banded = ka::launch_posteriors_banded;
     void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         if (a.mem == KA_MEM_HOST) {
@@ -103,6 +107,7 @@ struct OccCall {
     bool buffers(int32_t i) const { return occupancy[i] != nullptr; }
     static constexpr auto plan = ka::plan::label_posterior_workspace;
     static constexpr auto launch = ka::launch_label_posteriors;
+    static constexpr auto launch_banded = ka::launch_label_posteriors_banded;
     void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         if (a.mem == KA_MEM_HOST) {
@@ -157,6 +162,7 @@ struct StateCall {
         return ka::plan::state_posterior_workspace(n, T, S, K, V, beam, max_move, host, cv, off_res);   // (0 for K < 0 or K > T)
     }
     static constexpr auto launch = ka::launch_state_posteriors;
+    static constexpr auto launch_banded = ka::launch_state_posteriors_banded;
     void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         if (a.mem == KA_MEM_HOST) {
@@ -205,6 +211,7 @@ struct DurCall {
     bool moment(int32_t i) const { return time_sum && time_sum[i]; }
     static constexpr auto plan = ka::plan::state_duration_workspace;
     static constexpr auto launch = ka::launch_state_durations;
+    static constexpr auto launch_banded = ka::launch_state_durations_banded;
     void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         if (a.mem == KA_MEM_HOST) {
@@ -456,27 +463,37 @@ int fb_readback(const MeaCall &call, const ka::plan::MeaCarve *cv, const FbArgs 
     return KA_OK;
 }
 
-template <class Call>
+// A call with a table (FbArgs::band_lo) runs as fb_impl<Call, true>: the same steps on Banded<Desc> descriptors, which lie with
+// the staged tables behind the sibling's workspace (plan::band_table_workspace), and Call::launch_banded's kernels.
+template <class Call, bool kBanded = false>
 int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
 {
-    using Desc = typename Call::Desc;
+    using Desc = std::conditional_t<kBanded, ka::Banded<typename Call::Desc>, typename Call::Desc>;
+    static_assert(sizeof(Desc) <= ka::kBandedDescBytes || !kBanded, "descriptor sizes");
     const int32_t n = a.n, V = a.V;
     const hipStream_t stream = a.stream;
     const bool host = a.mem == KA_MEM_HOST;
     if (!e) return fail(KA_ERR_BAD_ARGS, "engine is NULL");
     if (e->batch.pending) return fail(KA_ERR_BAD_ARGS, "a batch is already enqueued: call ka_batch_finish first");
-    if (n < 0 || (n > 0 && (!a.log_probs || !a.T || !a.ld || !a.labels || !a.S || !call.arrays())))
+    if (n < 0 || (n > 0 && (!a.log_probs || !a.T || !a.ld || !a.labels || !a.S || !call.arrays() || (kBanded && !a.band_lo))))
         return fail(KA_ERR_BAD_ARGS, std::string(Call::kName) + ": NULL array argument");
     if (a.mem != KA_MEM_HOST && a.mem != KA_MEM_DEVICE) return fail(KA_ERR_BAD_ARGS, "mem must be KA_MEM_HOST or KA_MEM_DEVICE");
     if (n == 0) return KA_OK;
     std::vector<typename Call::Carve> cv(n);
     size_t off_res = 0;
-    const size_t total = call.plan(n, a.T, a.S, V, a.beam_size, a.max_move, host, cv.data(), &off_res);
+    size_t total = call.plan(n, a.T, a.S, V, a.beam_size, a.max_move, host, cv.data(), &off_res);
     if (total == 0) return fail(KA_ERR_BAD_ARGS, std::string(Call::kName) + ": unsupported T/S/V/beam_size/max_move");
+    size_t off_desc = 0;            // the descriptors: at the head of the workspace, a banded call's behind the sibling's bytes
+    std::vector<size_t> off_tab;    // banded, host buffers: the staged tables
+    if (kBanded) {
+        off_desc = total = align_up(total);
+        off_tab.resize((size_t)n);
+        total += ka::plan::band_table_workspace(n, a.T, host, off_tab.data());
+    }
     for (int32_t i = 0; i < n; ++i) {
         if (a.ld[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld < V");
         if (const char *why = call.bad_lattice(a, i)) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + why);
-        if (!a.log_probs[i] || !call.buffers(i) || (a.S[i] > 0 && !a.labels[i]))
+        if (!a.log_probs[i] || !call.buffers(i) || (a.S[i] > 0 && !a.labels[i]) || (kBanded && !a.band_lo[i]))
             return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": NULL buffer");
     }
     DeviceGuard guard;
@@ -518,6 +535,8 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
         d.max_move = a.max_move;
         d.idx = i;
         call.fill(d, c, a, i, e->res.ws);
+        if constexpr (kBanded)
+            d.band_lo = host ? reinterpret_cast<const int32_t *>(e->res.ws + off_desc + off_tab[(size_t)i]) : a.band_lo[i];
     }
     if (host)
         for (int32_t i = 0; i < n; ++i) {
@@ -525,13 +544,18 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
                                     hipMemcpyHostToDevice, stream));
             if (a.S[i] > 0) KA_HIP(hipMemcpyAsync(e->res.ws + cv[i].lab, a.labels[i], (size_t)a.S[i] * 4, hipMemcpyHostToDevice, stream));
             if ((rc = call.upload(cv[i], a, i, e->res.ws)) != KA_OK) return rc;
+            if (kBanded)
+                KA_HIP(hipMemcpyAsync(e->res.ws + off_desc + off_tab[(size_t)i], a.band_lo[i], (size_t)a.T[i] * 4, hipMemcpyHostToDevice, stream));
         }
     for (int32_t i = 0; i < n; ++i)
         if ((rc = call.stage(cv[i], a, i, e->res.ws)) != KA_OK) return rc;
-    Desc *d_lats = reinterpret_cast<Desc *>(e->res.ws);
+    Desc *d_lats = reinterpret_cast<Desc *>(e->res.ws + off_desc);
     ka::PostResult *d_res = reinterpret_cast<ka::PostResult *>(e->res.ws + off_res);
     KA_HIP(hipMemcpyAsync(d_lats, h, (size_t)n * sizeof(Desc), hipMemcpyHostToDevice, stream));
-    Call::launch(d_lats, n_fast, n - n_fast, a.max_move, d_res, stream);
+    if constexpr (kBanded)
+        Call::launch_banded(d_lats, n_fast, n - n_fast, a.max_move, d_res, stream);
+    else
+        Call::launch(d_lats, n_fast, n - n_fast, a.max_move, d_res, stream);
     KA_HIP(hipGetLastError());
     KA_HIP(hipMemcpyAsync(h_res, d_res, (size_t)n * sizeof(ka::PostResult), hipMemcpyDeviceToHost, stream));
     if ((rc = fb_readback(call, cv.data(), a, e->res.ws)) != KA_OK) return rc;
@@ -547,6 +571,7 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
         if (st != KA_OK && first_bad == KA_OK) {
             first_bad = st;
             g_err = "lattice " + std::to_string(i) + status_message(st, {nullptr, nullptr, ": a log-prob is +inf", Call::kBadArgs, Call::kZeroMass});
+            if (kBanded && st == KA_ERR_BAD_ARGS) g_err += ", or band_lo does not hold non-decreasing values in [0, 2S+1)";
         }
     }
     return first_bad;
@@ -790,6 +815,93 @@ size_t ka_state_duration_workspace_bytes(int32_t n, const int64_t *T, const int6
 {
     if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
     return ka::plan::state_duration_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+// ---- the four calls over a caller-given band: their siblings' arguments with band_lo behind max_move ----
+int ka_ctc_path_posteriors_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                            const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                            int32_t max_move, const int32_t *const *band_lo, const int32_t *const *best_path,
+                                            float *const *posteriors, double *log_likelihood, int32_t *status, int32_t mem, void *stream)
+{
+    if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "posteriors: NULL band_lo");
+    return fb_impl<PostCall, true>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
+                                   PostCall{best_path, posteriors});
+}
+
+int ka_ctc_path_posteriors_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                      int32_t beam_size, int32_t max_move, const int32_t *band_lo, const int32_t *best_path,
+                                      float *posteriors, double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl<PostCall, true>(
+        e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo},
+        PostCall{&best_path, &posteriors});
+}
+
+int ka_ctc_label_posteriors_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                             const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                             int32_t max_move, const int32_t *const *band_lo, const int64_t *terminal,
+                                             float *const *occupancy, const int64_t *ld_out, double *log_likelihood, int32_t *status,
+                                             int32_t mem, void *stream)
+{
+    if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "label posteriors: NULL band_lo");
+    return fb_impl<OccCall, true>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
+                                  OccCall{terminal, occupancy, ld_out});
+}
+
+int ka_ctc_label_posteriors_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                       int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal, float *occupancy,
+                                       int64_t ld_out, double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl<OccCall, true>(
+        e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo},
+        OccCall{&terminal, &occupancy, &ld_out});
+}
+
+int ka_ctc_state_posteriors_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                             const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                             int32_t max_move, const int32_t *const *band_table, const int64_t *terminal,
+                                             const int64_t *const *frames, const int64_t *K, float *const *gamma, const int64_t *ld_out,
+                                             int64_t *const *band_lo, double *log_likelihood, int32_t *status, int32_t mem, void *stream)
+{
+    if (n > 0 && !band_table) return fail(KA_ERR_BAD_ARGS, "state posteriors: NULL band table");
+    return fb_impl<StateCall, true>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_table},
+                                    StateCall{terminal, frames, K, gamma, ld_out, band_lo});
+}
+
+int ka_ctc_state_posteriors_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                       int32_t beam_size, int32_t max_move, const int32_t *band_table, int64_t terminal, const int64_t *frames,
+                                       int64_t K, float *gamma, int64_t ld_out, int64_t *band_lo, double *log_likelihood, int32_t mem,
+                                       void *stream)
+{
+    return fb_impl<StateCall, true>(
+        e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_table},
+        StateCall{&terminal, &frames, &K, &gamma, &ld_out, &band_lo});
+}
+
+int ka_ctc_state_durations_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                            const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                            int32_t max_move, const int32_t *const *band_lo, const int64_t *terminal,
+                                            double *const *duration, double *const *time_sum, double *log_likelihood, int32_t *status,
+                                            int32_t mem, void *stream)
+{
+    if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "state durations: NULL band_lo");
+    return fb_impl<DurCall, true>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
+                                  DurCall{terminal, duration, time_sum});
+}
+
+int ka_ctc_state_durations_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                      int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal, double *duration,
+                                      double *time_sum, double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl<DurCall, true>(
+        e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo},
+        DurCall{&terminal, &duration, &time_sum});
+}
+
+size_t ka_band_table_workspace_bytes(int32_t n, const int64_t *T, int32_t mem)
+{
+    if (n < 0 || (n > 0 && !T) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::band_table_workspace(n, T, mem == KA_MEM_HOST, nullptr);
 }
 
 int ka_ctc_state_visits_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,

@@ -1,8 +1,8 @@
 // ka_fb_ck.hpp — the checkpointed forward-backward that ka_occupancy.hpp (label occupancy), ka_state_posterior.hpp (state
 // posteriors at chosen frames), ka_duration.hpp (expected state durations), ka_mea.hpp (the MEA path) and ka_visit.hpp (state
 // visit probabilities) share, and whose forward half ka_sample.hpp (sampled alignments) reuses: fb_ck_forward<Form>,
-// fb_ck_recompute<Form> and the driver fb_ck<Form, Out>, each written once over two policies, and the launch of the calls'
-// kernels.
+// fb_ck_recompute<Form> and the driver fb_ck<Form, Out>, each written once over three policies (the form, the call's Out and
+// the band: BandWalk, the reference's diagonal, or BandTable, a caller's table), and the launch of the calls' kernels.
 //
 // The posterior kernels keep alpha only at the path; these calls need it at band cells, so the forward pass checkpoints the
 // whole column before the first frame of every 32-frame block (with the offset C and the frame maximum m it runs on), and the
@@ -57,14 +57,15 @@ __device__ __forceinline__ float fb_gamma(double arg)
 // zero-mass checks, Z (log2 alpha_{T-1}(s*), the expression gamma's alpha is formed with) and Zr (fb_reported_z).  Returns
 // kStatusOk or the status the lattice fails with; col(0) / col(1) are its working columns, bw ends at frame T.  It ends behind
 // f.sync(): in the generic form a barrier, which also orders the sampler's first slab.
-template <class Form>
-__device__ __forceinline__ int fb_ck_forward(Form &f, BandWalk &bw, double &Z, double &Zr)
+template <class Form, class Band>
+__device__ __forceinline__ int fb_ck_forward(Form &f, Band &bw, double &Z, double &Zr)
 {
     const FbCkLattice &d = f.d;
     const int tid = threadIdx.x;
     const int64_t T = d.T, L = d.L;
     const double NINF = post_dninf();
     if (fb_labels_bad(d)) return kStatusBadLabel;
+    if (!bw.start()) return kStatusBadArgs;   // (a caller's table that is no band: before any of its values places a cell)
     auto no_cell = [](int64_t, double) {};
     double *prev = f.col(0), *cur = f.col(1);
     if (tid == 0) prev[0] = 0.0;   // virtual state before frame 0
@@ -114,8 +115,8 @@ __device__ __forceinline__ int fb_ck_forward(Form &f, BandWalk &bw, double &Z, d
 // forward pass's frame function on the forward pass's operands, pv / cu the working columns; note(t - t0, C) is handed every
 // frame's offset before the frame runs.  bw ends at frame t1.  A cell's slab entry is written by the thread that owns the
 // cell in that frame.  The generic form ends behind a barrier; the fast form's last frame ends in its fence.
-template <class Form, class Note>
-__device__ __forceinline__ void fb_ck_recompute(Form &f, int64_t k, int64_t t0, int64_t t1, BandWalk &bw, double *pv, double *cu, Note note)
+template <class Form, class Band, class Note>
+__device__ __forceinline__ void fb_ck_recompute(Form &f, int64_t k, int64_t t0, int64_t t1, Band &bw, double *pv, double *cu, Note note)
 {
     const FbCkLattice &d = f.d;
     const double NINF = post_dninf();
@@ -156,9 +157,10 @@ __device__ __forceinline__ void fb_ck_recompute(Form &f, int64_t k, int64_t t0, 
     if (!Form::kWave) f.sync();
 }
 
-// The driver of the calls that need gamma; cav: kPostCk doubles of LDS, the offsets of the block's frames.
-template <class Form, class Out>
-__device__ __forceinline__ void fb_ck(Form &f, PostResult *res, double *cav, Out &out)
+// The driver of the calls that need gamma; cav: kPostCk doubles of LDS, the offsets of the block's frames; Band: the band
+// (BandWalk, or BandTable of ka_posterior_common.hpp on `tab`, the caller's table).
+template <class Form, class Out, class Band = BandWalk>
+__device__ __forceinline__ void fb_ck(Form &f, PostResult *res, double *cav, Out &out, const int32_t *tab = nullptr)
 {
     const FbCkLattice &d = f.d;
     const int tid = threadIdx.x;
@@ -166,7 +168,7 @@ __device__ __forceinline__ void fb_ck(Form &f, PostResult *res, double *cav, Out
     const double NINF = post_dninf();
 
     // ---- forward: Z, and a checkpoint before every block ----
-    BandWalk bw(d.L, d.beam, T);
+    Band bw(d.L, d.beam, T, tab);
     double Z, Zr;
     const int status = fb_ck_forward(f, bw, Z, Zr);
     if (status != kStatusOk) {

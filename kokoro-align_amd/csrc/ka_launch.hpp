@@ -1,6 +1,6 @@
 // ka_launch.hpp — the host-callable launch functions of every device translation unit.
 //
-// The library is built from eighteen translation units so that the device code compiles in parallel (a single unit took three
+// The library is built from twenty-two translation units so that the device code compiles in parallel (a single unit took three
 // minutes): ka_engine.hip, ka_engine_fb.hip and ka_entry_misc.hip are host code only and reach the kernels through these
 // functions; each kernel family lives in the .hip file named below and nowhere else.  All functions only enqueue; errors
 // surface through hipGetLastError().
@@ -94,6 +94,13 @@ void launch_posteriors(const PostLattice *lats, int n_fast, int n_generic, int m
 void launch_label_posteriors(const OccLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 void launch_state_posteriors(const StateLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 void launch_state_durations(const DurLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+
+// ---- ka_posterior_banded.hip / ka_occupancy_banded.hip / ka_state_posterior_banded.hip / ka_duration_banded.hip: the four calls
+// above over a caller-given band, Banded<>::band_lo in place of the diagonal; each its sibling's split, grid and slots ----
+void launch_posteriors_banded(const Banded<PostLattice> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+void launch_label_posteriors_banded(const Banded<OccLattice> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+void launch_state_posteriors_banded(const Banded<StateLattice> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+void launch_state_durations_banded(const Banded<DurLattice> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 
 // ---- ka_sample.hip: alignments sampled from the band posterior (ka_sample.hpp): ka_fb_ck.hpp's forward pass and block
 // recompute, launch_fb_ck's form split, grid and slots ----

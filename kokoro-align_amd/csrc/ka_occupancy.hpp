@@ -1,5 +1,5 @@
 // ka_occupancy.hpp — label occupancy posteriors: for every frame the probability of each label value, over the band's paths
-// that end at a caller-given terminal s*, and Z = alpha_{T-1}(s*).  Included by ka_occupancy.hip only.
+// that end at a caller-given terminal s*, and Z = alpha_{T-1}(s*).  Included by ka_occupancy.hip and ka_occupancy_banded.hip.
 //
 // Same lattice, band, moves, veto and numerics as ka_posterior.hpp:
 //   occ[t, v] = sum over s in [lo_t, hi_t) with lab'[s] = v of gamma_t(s),  gamma_t(s) = 2^(alpha_t(s) + beta_t(s) - Z)
@@ -101,6 +101,20 @@ __global__ __launch_bounds__(Form::NT) void occupancy_kernel(const OccLattice *_
         Form f(lats[i], sh);
         OccOut<Form> out(lats[i], bins);
         fb_ck(f, res, cav, out);
+        f.sync();
+    }
+}
+// ... over the caller's table (ka_occupancy_banded.hip)
+template <class Form>
+__global__ __launch_bounds__(Form::NT) void occupancy_banded_kernel(const Banded<OccLattice> *__restrict__ lats, int n, PostResult *res)
+{
+    __shared__ typename Form::template Shared<4> sh;
+    __shared__ double cav[kPostCk];
+    __shared__ unsigned long long bins[Form::kWave ? 64 : kOccLdsBins];
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        Form f(lats[i], sh);
+        OccOut<Form> out(lats[i], bins);
+        fb_ck<Form, OccOut<Form>, BandTable>(f, res, cav, out, lats[i].band_lo);
         f.sync();
     }
 }

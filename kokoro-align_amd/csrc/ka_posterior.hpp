@@ -1,5 +1,5 @@
 // ka_posterior.hpp — forward-backward over the band of align.py:64-65: the posterior of the caller's best path at every frame
-// and the lattice log-likelihood.  Included by ka_posterior.hip only.
+// and the lattice log-likelihood.  Included by ka_posterior.hip and ka_posterior_banded.hip.
 //
 // What is computed, with lab'[2i] = 0, lab'[2i+1] = labels[i], L = 2S+1 and the band and moves of
 // the best-path DP (the label-VALUE-0 veto of align.py:80-81 included):
@@ -18,7 +18,8 @@
 // No alpha lattice is stored: the forward pass writes alpha_t(p_t) - C_{32k-1} (k = t / 32) into the caller's posterior
 // buffer as a float and C_{32k-1} into a double per 32 frames; the backward pass carries beta across the band and
 // overwrites the buffer with the posterior, combining the two halves and Z in double before the one exp.
-// One kernel, posterior_kernel<Form>, over the form policy of ka_fb_form.hpp on a PostLattice: the fast form with the label
+// One pass, posterior_lattice<Form, Band>, behind two kernels (posterior_kernel<Form> on the reference's diagonal band,
+// posterior_banded_kernel<Form> on a caller's table), over the form policy of ka_fb_form.hpp on a PostLattice: the fast form with the label
 // ring (PostFast<M>) and the generic form (PostGen).  The form brings the threads, the columns, the row, the labels and the
 // frame recurrences; the kernel brings the band walk, the path prefetches and what happens at the path.
 #pragma once
@@ -40,11 +41,10 @@ using PostGen = FbGen<PostLattice>;
 
 // One workgroup per lattice.  Global loads (the next row, the next path value, the next stored alpha, the labels entering the
 // ring) are issued a frame before their use.
-template <class Form>
-__global__ __launch_bounds__(Form::NT) void posterior_kernel(const PostLattice *__restrict__ lats, PostResult *res)
+// Band: the band (BandWalk, or BandTable of ka_posterior_common.hpp on `tab`, the caller's table).
+template <class Form, class Band>
+__device__ __forceinline__ void posterior_lattice(const PostLattice &d, typename Form::template Shared<4> &sh, const int32_t *tab, PostResult *res)
 {
-    const PostLattice &d = lats[blockIdx.x];
-    __shared__ typename Form::template Shared<4> sh;
     Form f(d, sh);
     const int tid = threadIdx.x;
     const int64_t T = d.T, L = d.L;
@@ -59,7 +59,11 @@ __global__ __launch_bounds__(Form::NT) void posterior_kernel(const PostLattice *
     double *prev = f.col(0), *cur = f.col(1);
     if (tid == 0) prev[0] = 0.0;   // virtual state before frame 0
     int64_t plo = 0, phi = 1;
-    BandWalk bw(L, d.beam, T);
+    Band bw(L, d.beam, T, tab);
+    if (!bw.start()) {   // (a caller's table that is no band: before any of its values places a cell)
+        post_fail(d, res, kStatusBadArgs);
+        return;
+    }
     double C = 0.0, Cb = 0.0, mprev = 0.0;
     int flags = 0;
     f.row_prefetch(0);
@@ -161,6 +165,22 @@ __global__ __launch_bounds__(Form::NT) void posterior_kernel(const PostLattice *
         res[d.idx].status = kStatusOk;
         res[d.idx].log_likelihood = Z * kLn2;
     }
+}
+
+template <class Form>
+__global__ __launch_bounds__(Form::NT) void posterior_kernel(const PostLattice *__restrict__ lats, PostResult *res)
+{
+    const PostLattice &d = lats[blockIdx.x];
+    __shared__ typename Form::template Shared<4> sh;
+    posterior_lattice<Form, BandWalk>(d, sh, nullptr, res);
+}
+// ... over the caller's table (ka_posterior_banded.hip)
+template <class Form>
+__global__ __launch_bounds__(Form::NT) void posterior_banded_kernel(const Banded<PostLattice> *__restrict__ lats, PostResult *res)
+{
+    const Banded<PostLattice> &d = lats[blockIdx.x];
+    __shared__ typename Form::template Shared<4> sh;
+    posterior_lattice<Form, BandTable>(d, sh, d.band_lo, res);
 }
 
 }  // namespace ka

@@ -51,10 +51,23 @@ __device__ __forceinline__ void post_band(int64_t q, int64_t L, int64_t B, int64
     lo = lo < 0 ? 0 : lo;
     hi = (L - lo < B) ? L : lo + B;
 }
-// q = floor(L t / T) of frame t, stepped one frame at a time (Bresenham: q + r / T = L t / T with 0 <= r < T)
+// The band as a policy of the passes above (posterior_lattice, fb_ck_forward, fb_ck_recompute, fb_ck), two of them, both
+// built as Band(L, beam, T, table):
+//   start()        before frame 0 and before any use of the band: is the band valid?  The walk then stands at frame 0.
+//   seek(t)        stand at frame t, any t in [0, T]
+//   next(), prev() one frame on or back; the passes step one frame past either end (to T from T-1, to -1 from 0)
+//   band(lo, hi)   the band of the frame the walk stands at
+//   kTable         does the band come from a caller's table (positions below lo_0 are then held by no band)?
+// BandWalk: the reference's diagonal, q = floor(L t / T) of frame t, stepped one frame at a time (Bresenham: q + r / T = L t / T
+// with 0 <= r < T)
 struct BandWalk {
+    static constexpr bool kTable = false;
     int64_t q, r, dq, dr, T, L, B;
-    __device__ __forceinline__ BandWalk(int64_t L_, int64_t B_, int64_t T_) : q(0), r(0), dq(L_ / T_), dr(L_ % T_), T(T_), L(L_), B(B_) {}
+    __device__ __forceinline__ BandWalk(int64_t L_, int64_t B_, int64_t T_, const int32_t * = nullptr)   // (no table to walk)
+        : q(0), r(0), dq(L_ / T_), dr(L_ % T_), T(T_), L(L_), B(B_)
+    {
+    }
+    __device__ __forceinline__ bool start() const { return true; }
     __device__ __forceinline__ void seek(int64_t t)
     {
         q = (L * t) / T;
@@ -73,6 +86,64 @@ struct BandWalk {
         if (r < 0) { r += T; --q; }
     }
     __device__ __forceinline__ void band(int64_t &lo, int64_t &hi) const { post_band(q, L, B, lo, hi); }
+};
+// BandTable: the caller's table, lo_t = tab[t], hi_t = min(lo_t + B, L) (post_band's rule for hi).  A valid table holds
+// 0 <= tab[t] < L, non-decreasing, any step; start() checks all of it with the whole workgroup before a value is used.
+// The walk keeps the values of frames t-1, t and t+1; a step moves them along and loads the one that enters, so the value a
+// frame's band is formed from was asked for a whole frame earlier.  The loads are scalar (constant address space: the table
+// does not change under the kernel) and so count against lgkmcnt, not against the vmcnt of the row a form prefetches.
+// No index leaves [0, T): frames past either end read the end's entry (at), which is what the passes' steps past the ends,
+// fb_ck_recompute's seek(t0); prev() and fb_ck's seek(t1) with t1 = T come down to.
+typedef __attribute__((address_space(4))) const int32_t *cci32_t;
+struct BandTable {
+    static constexpr bool kTable = true;
+    const int32_t *const src;
+    const cci32_t tab;
+    const int32_t T, L, B;
+    int32_t t, vp, v, vn;   // the frame the walk stands at; tab at t-1, t, t+1
+    __device__ __forceinline__ BandTable(int64_t L_, int64_t B_, int64_t T_, const int32_t *tab_)
+        : src(tab_), tab((cci32_t)(uintptr_t)tab_), T((int32_t)T_), L((int32_t)L_), B((int32_t)B_), t(0), vp(0), v(0), vn(0)
+    {
+    }
+    __device__ __forceinline__ int32_t at(int32_t i) const { return tab[i < 0 ? 0 : (i < T ? i : T - 1)]; }
+    __device__ __forceinline__ bool start()
+    {
+        int bad = 0;
+        for (int32_t i = threadIdx.x; i < T; i += blockDim.x) {
+            const int32_t x = src[i];
+            bad |= (x < 0 || x >= L) ? 1 : 0;
+            bad |= (i > 0 && src[i - 1] > x) ? 1 : 0;
+        }
+        if (__syncthreads_or(bad)) return false;
+        seek(0);
+        return true;
+    }
+    __device__ __forceinline__ void seek(int64_t t_)
+    {
+        t = (int32_t)t_;
+        vp = at(t - 1);
+        v = at(t);
+        vn = at(t + 1);
+    }
+    __device__ __forceinline__ void next()
+    {
+        ++t;
+        vp = v;
+        v = vn;
+        vn = at(t + 1);
+    }
+    __device__ __forceinline__ void prev()
+    {
+        --t;
+        vn = v;
+        v = vp;
+        vp = at(t - 1);
+    }
+    __device__ __forceinline__ void band(int64_t &lo, int64_t &hi) const
+    {
+        lo = v;
+        hi = ((int64_t)L - lo < B) ? (int64_t)L : lo + B;
+    }
 };
 // error flags -> status: a bad label is reported before anything runs; then NaN, +inf, a path value outside [0, L)
 __device__ __forceinline__ int post_status_of(int flags)

@@ -1,6 +1,6 @@
 // ka_state_posterior.hpp — state posteriors at chosen frames: for every query frame f_k the posterior gamma_{f_k}(s) of every
 // band position, over the band's paths that end at a caller-given terminal s*, and Z = alpha_{T-1}(s*).  Included by
-// ka_state_posterior.hip only.
+// ka_state_posterior.hip and ka_state_posterior_banded.hip.
 //
 // Same lattice, band, moves, veto, statuses and form split as ka_occupancy.hpp (DESIGN.md sections 4.18 and 4.19): the
 // driver of ka_fb_ck.hpp with StOut, which differs from the occupancy's policy in two ways:
@@ -67,6 +67,19 @@ __global__ __launch_bounds__(Form::NT) void state_posterior_kernel(const StateLa
         Form f(lats[i], sh);
         StOut<Form> out(lats[i]);
         fb_ck(f, res, cav, out);
+        f.sync();
+    }
+}
+// ... over the caller's table (ka_state_posterior_banded.hip): band_lo[k] is then the table's value at f_k
+template <class Form>
+__global__ __launch_bounds__(Form::NT) void state_posterior_banded_kernel(const Banded<StateLattice> *__restrict__ lats, int n, PostResult *res)
+{
+    __shared__ typename Form::template Shared<4> sh;
+    __shared__ double cav[kPostCk];
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        Form f(lats[i], sh);
+        StOut<Form> out(lats[i]);
+        fb_ck<Form, StOut<Form>, BandTable>(f, res, cav, out, lats[i].band_lo);
         f.sync();
     }
 }

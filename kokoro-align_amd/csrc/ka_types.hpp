@@ -242,6 +242,17 @@ static_assert(sizeof(PostLattice) == 88 && sizeof(FbCkLattice) == 104 && sizeof(
                   sizeof(QuantLattice) == 152,
               "descriptor sizes");
 
+// ---- the forward-backward calls over a caller-given band: a call's descriptor and, behind it, the caller's table.  Only the
+// banded kernels read these; the descriptors above keep their sizes ----
+template <class Desc>
+struct Banded : Desc {
+    const int32_t *band_lo;   // [T] the caller's table (device): lo_t
+};
+constexpr size_t kBandedDescBytes = 144;   // the largest of them: what ka_band_table_workspace_bytes reserves per lattice
+static_assert(sizeof(Banded<PostLattice>) == 96 && sizeof(Banded<OccLattice>) == 128 && sizeof(Banded<StateLattice>) == kBandedDescBytes &&
+                  sizeof(Banded<DurLattice>) == 128,
+              "descriptor sizes");
+
 // ---- best path over a caller-given band (ka_banded.hpp) ----
 struct BandLattice {
     const float *lp;          // [T, ld] log-probs (device)

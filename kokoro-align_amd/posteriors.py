@@ -89,11 +89,29 @@ def _device_lattices(log_probs, labels, others, what):
                      guard=lambda: torch.cuda.device(dev))
 
 
-def _run_lattices(lat, call, beam_size, max_move, own_args, outs, return_status):
+def _band_tables(lat, band_lo):
+    """The tables of a banded call as the call wants them: one per lattice, int32 where the lattices are, T_i entries.  They
+    may come as int64 (as ``diagonal_band`` and the other table builders return them) or as tensors."""
+    if len(band_lo) != lat.n:
+        raise ValueError("band_lo must hold one table per lattice")
+    if lat.form == "batch":
+        band_lo = [x.detach().cpu().numpy() if _is_tensor(x) else x for x in band_lo]
+    tables = [lat.int32(x) for x in band_lo]
+    if any(b.shape[0] != T for b, T in zip(tables, lat.T)):
+        raise ValueError("a band table must have one entry per frame")
+    return tables
+
+
+def _run_lattices(lat, call, beam_size, max_move, own_args, outs, return_status, band_lo=None):
     """The call ``ka_ctc_<call>_batch_f32`` (path_posteriors, label_posteriors, state_posteriors, state_durations, state_visits, boundary_quantiles,
     sample_paths, mea_path): the
     arguments all of them take around ``own_args`` (the call's own tables), then the results (*outs[i], log_likelihood[i]),
-    ``outs`` a list of tuples, and the status handling of ``return_status``."""
+    ``outs`` a list of tuples, and the status handling of ``return_status``.  With ``band_lo`` (a table per lattice) the call is
+    ``ka_ctc_<call>_banded_batch_f32``, which takes the tables behind ``max_move``; without, today's symbol and arguments."""
+    if band_lo is not None:
+        tables = _band_tables(lat, band_lo)
+        p_band, _k0 = _ptr_array([lat.ptr(x) for x in tables])
+        call, own_args = f"{call}_banded", (p_band, *own_args)
     name = f"ctc_{call}_{lat.form}"
     status = np.zeros(lat.n, np.int32)
     ll = np.zeros(lat.n, np.float64)
@@ -149,20 +167,28 @@ def _segments(seg_ends, T):
 # ------------------------------------------------------------------------------------------
 # best-path posteriors and lattice log-likelihood
 # ------------------------------------------------------------------------------------------
-def ctc_path_posteriors(log_probs, labels, best_path, beam_size=1000, max_move=4):
+def ctc_path_posteriors(log_probs, labels, best_path, beam_size=1000, max_move=4, band_lo=None):
     """How sure the model is of a best path, frame by frame: (posteriors float32 [T], log_likelihood float).
 
     posteriors[t] is the probability, over every path of the band of ``ctc_best_path`` that ends where ``best_path`` ends,
     that frame t sits at ``best_path[t]``; log_likelihood is the log of the total probability of those paths (nats).
     NumPy in -> NumPy out; ROCm torch tensors are handed to ``ctc_path_posteriors_device``.  Raises IndexError for a label
     outside [0, V), ValueError for NaN / +inf log-probs, a path value outside [0, 2S+1) or a terminal no finite path reaches.
+    ``band_lo``: a table [T] as ``ctc_best_path_banded`` takes it (``diagonal_band``, ``anchored_band``, ``band_around_path``):
+    the band is then [band_lo[t], min(band_lo[t] + beam_size, 2S+1)) - the band to judge a path found under that table with;
+    an invalid table raises ValueError.
     """
     call = ctc_path_posteriors_device if _is_tensor(log_probs) else ctc_path_posteriors_batch
-    (result,) = call([log_probs], [labels], [best_path], beam_size, max_move)
+    (result,) = call([log_probs], [labels], [best_path], beam_size, max_move, band_lo=_one_table(band_lo))
     return result
 
 
-def _path_posteriors(lat, best_paths, beam_size, max_move, return_status):
+def _one_table(band_lo):
+    """The ``band_lo`` of a single-lattice call as the list its batch form takes."""
+    return None if band_lo is None else [band_lo]
+
+
+def _path_posteriors(lat, best_paths, beam_size, max_move, return_status, band_lo=None):
     if lat is None:
         return ([], []) if return_status else []
     paths = [lat.int32(x) for x in best_paths]
@@ -171,26 +197,27 @@ def _path_posteriors(lat, best_paths, beam_size, max_move, return_status):
     posts = [lat.empty(T, np.float32) for T in lat.T]
     p_path, _k1 = _ptr_array([lat.ptr(x) for x in paths])
     p_post, _k2 = _ptr_array([lat.ptr(x) for x in posts])
-    return _run_lattices(lat, "path_posteriors", beam_size, max_move, (p_path, p_post), list(zip(posts)), return_status)
+    return _run_lattices(lat, "path_posteriors", beam_size, max_move, (p_path, p_post), list(zip(posts)), return_status, band_lo)
 
 
 def ctc_path_posteriors_batch(log_probs_list, labels_list, best_path_list, beam_size=1000, max_move=4, device=None,
-                              return_status=False):
+                              return_status=False, band_lo=None):
     """Posteriors of many lattices in ONE launch; host NumPy buffers in and out.
 
     Returns a list of (posteriors, log_likelihood); with ``return_status`` also the per-lattice status list, in which case
     failures do not raise (their posteriors are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    ``band_lo``: a list of tables, one per lattice (``ctc_path_posteriors``).
     """
     lat = _host_lattices(log_probs_list, labels_list, best_path_list, "best paths", device)
-    return _path_posteriors(lat, best_path_list, beam_size, max_move, return_status)
+    return _path_posteriors(lat, best_path_list, beam_size, max_move, return_status, band_lo)
 
 
-def ctc_path_posteriors_device(log_probs, labels, best_paths, beam_size=1000, max_move=4, return_status=False):
+def ctc_path_posteriors_device(log_probs, labels, best_paths, beam_size=1000, max_move=4, return_status=False, band_lo=None):
     """Lists of ROCm torch tensors in (float32 log-probs [T_i, V], labels [S_i], best paths [T_i] - e.g. the outputs of
     ``ctc_best_path_device``), list of (posteriors tensor [T_i] on the device, log_likelihood float) out.  One launch on
-    torch's current stream."""
+    torch's current stream.  ``band_lo``: a list of tables, one per lattice, tensors on the device or host arrays."""
     lat = _device_lattices(log_probs, labels, best_paths, "best paths")
-    return _path_posteriors(lat, best_paths, beam_size, max_move, return_status)
+    return _path_posteriors(lat, best_paths, beam_size, max_move, return_status, band_lo)
 
 
 def segment_confidence(posteriors, seg_ends):
@@ -211,7 +238,7 @@ def segment_confidence(posteriors, seg_ends):
 # ------------------------------------------------------------------------------------------
 # label occupancy posteriors and a differentiable lattice log-likelihood
 # ------------------------------------------------------------------------------------------
-def ctc_label_posteriors(log_probs, labels, terminal, beam_size=1000, max_move=4):
+def ctc_label_posteriors(log_probs, labels, terminal, beam_size=1000, max_move=4, band_lo=None):
     """Per-frame label posteriors of the band's paths that end at ``terminal``: (occ float32 [T, V], log_likelihood float).
 
     occ[t, v] is the probability that frame t emits label value v (blank = 0), over every path of the band of
@@ -219,39 +246,43 @@ def ctc_label_posteriors(log_probs, labels, terminal, beam_size=1000, max_move=4
     occ equals d log_likelihood / d log_probs.  log_likelihood is the value ``ctc_path_posteriors`` returns for a path that
     ends there.  NumPy in -> NumPy out; ROCm torch tensors go to ``ctc_label_posteriors_device``.  Raises IndexError for a
     label outside [0, V), ValueError for NaN / +inf log-probs, a terminal outside [0, 2S+1) or one no finite path reaches.
+    ``band_lo``: the band as a table [T], as ``ctc_path_posteriors`` takes it.
     """
     call = ctc_label_posteriors_device if _is_tensor(log_probs) else ctc_label_posteriors_batch
-    (result,) = call([log_probs], [labels], [terminal], beam_size, max_move)
+    (result,) = call([log_probs], [labels], [terminal], beam_size, max_move, band_lo=_one_table(band_lo))
     return result
 
 
-def _label_posteriors(lat, terminals, beam_size, max_move, out, return_status):
+def _label_posteriors(lat, terminals, beam_size, max_move, out, return_status, band_lo=None):
     if lat is None:
         return ([], []) if return_status else []
     occs = _outputs(lat, out, [(T, lat.V) for T in lat.T], "[T_i, V]")
     p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
     p_occ, _k2 = _ptr_array([lat.ptr(x) for x in occs])
     p_ldo, _k3 = _i64_array([lat.ld(x) for x in occs])
-    return _run_lattices(lat, "label_posteriors", beam_size, max_move, (p_term, p_occ, p_ldo), list(zip(occs)), return_status)
+    return _run_lattices(lat, "label_posteriors", beam_size, max_move, (p_term, p_occ, p_ldo), list(zip(occs)), return_status,
+                         band_lo)
 
 
-def ctc_label_posteriors_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False):
+def ctc_label_posteriors_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False,
+                               band_lo=None):
     """Label posteriors of many lattices in ONE launch; host NumPy buffers in and out.
 
     Returns a list of (occ [T_i, V], log_likelihood); with ``return_status`` also the per-lattice status list, in which case
     failures do not raise (their rows are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    ``band_lo``: a list of tables, one per lattice (``ctc_path_posteriors``).
     """
     lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
-    return _label_posteriors(lat, terminals, beam_size, max_move, None, return_status)
+    return _label_posteriors(lat, terminals, beam_size, max_move, None, return_status, band_lo)
 
 
-def ctc_label_posteriors_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False):
+def ctc_label_posteriors_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False, band_lo=None):
     """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]) and terminals (ints
     or best paths), list of (occ tensor [T_i, V] on the device, log_likelihood float) out.  ``out``: optional list of float32
     [T_i, V] tensors with unit column stride to write into (views into wider tensors keep their other columns).  One launch
-    on torch's current stream."""
+    on torch's current stream.  ``band_lo``: a list of tables, one per lattice, tensors on the device or host arrays."""
     lat = _device_lattices(log_probs, labels, terminals, "terminals")
-    return _label_posteriors(lat, terminals, beam_size, max_move, out, return_status)
+    return _label_posteriors(lat, terminals, beam_size, max_move, out, return_status, band_lo)
 
 
 def _lattice_ll_function():
@@ -261,14 +292,14 @@ def _lattice_ll_function():
         """Z of every lattice (float64 [n]); backward: grad_out[i] * occ_i, the occupancy saved by forward."""
 
         @staticmethod
-        def forward(ctx, labels, terminals, beam_size, max_move, zero_infinity, *lps):
+        def forward(ctx, labels, terminals, beam_size, max_move, zero_infinity, band_lo, *lps):
             n = len(lps)
             if lps[0].is_cuda:
                 res, st = ctc_label_posteriors_device([x.detach() for x in lps], labels, terminals, beam_size, max_move,
-                                                      return_status=True)
+                                                      return_status=True, band_lo=band_lo)
             else:
                 res, st = ctc_label_posteriors_batch([x.detach().float().numpy() for x in lps], labels, terminals, beam_size,
-                                                     max_move, return_status=True)
+                                                     max_move, return_status=True, band_lo=band_lo)
                 res = [(torch.from_numpy(o), z) for o, z in res]
             for i, s in enumerate(st):
                 if s == _lib.KA_ERR_ZERO_MASS and zero_infinity:
@@ -290,7 +321,7 @@ def _lattice_ll_function():
         def backward(ctx, grad_out):
             grads = [(g * o.to(torch.float64)).to(dt) for g, o, dt in zip(grad_out.unbind(0), ctx.occs, ctx.dtypes)]
             ctx.occs = None
-            return (None, None, None, None, None, *grads)
+            return (None, None, None, None, None, None, *grads)
 
     return LatticeLogLikelihood
 
@@ -307,19 +338,20 @@ def _raise_lattice_status(st, i):
     if st == _lib.KA_ERR_NONFINITE:
         raise ValueError(f"{what}: a log-prob is +inf")
     if st == _lib.KA_ERR_BAD_ARGS:
-        raise ValueError(f"{what}: terminal outside [0, 2S+1)")
+        raise ValueError(f"{what}: terminal outside [0, 2S+1), or band_lo not non-decreasing in [0, 2S+1)")
     if st == _lib.KA_ERR_ZERO_MASS:
         raise ValueError(f"{what}: no path of finite score reaches the terminal")
     raise _lib.KAError(f"{what}: status {st}")
 
 
-def lattice_log_likelihood(log_probs, labels, terminal, beam_size=1000, max_move=4, zero_infinity=False):
+def lattice_log_likelihood(log_probs, labels, terminal, beam_size=1000, max_move=4, zero_infinity=False, band_lo=None):
     """Differentiable log-likelihood Z of the band's paths that end at ``terminal`` (this engine's topology: band, moves,
     label-0 veto), float64 on the input's device.  One [T, V] tensor (labels, terminal for it) -> 0-d; a list of them (lists
     of labels and terminals) -> [n].  The gradient with respect to the log-probs is the label occupancy (``ctc_label_posteriors``)
     times the incoming gradient; the forward pass saves it, so backward launches nothing.  With ``zero_infinity``, a lattice
     whose terminal no finite path reaches gives 0 and a zero gradient (as ``torch.nn.CTCLoss``); otherwise, and for every
-    other failure, this raises as ``ctc_label_posteriors`` does."""
+    other failure, this raises as ``ctc_label_posteriors`` does.  ``band_lo``: the band as a table (one for one tensor, a list
+    for a list), as ``ctc_label_posteriors`` takes it; value and gradient are then those of that band."""
     global _LATTICE_LL
     if _LATTICE_LL is None:
         _LATTICE_LL = _lattice_ll_function()
@@ -329,7 +361,8 @@ def lattice_log_likelihood(log_probs, labels, terminal, beam_size=1000, max_move
     terms = [terminal] if single else list(terminal)
     if len(lps) == 0 or len(labs) != len(lps) or len(terms) != len(lps):
         raise ValueError("log_probs, labels and terminals must be non-empty lists of one length")
-    z = _LATTICE_LL.apply(labs, [_terminal_of(s) for s in terms], int(beam_size), int(max_move), bool(zero_infinity), *lps)
+    bands = None if band_lo is None else ([band_lo] if single else list(band_lo))
+    z = _LATTICE_LL.apply(labs, [_terminal_of(s) for s in terms], int(beam_size), int(max_move), bool(zero_infinity), bands, *lps)
     return z[0] if single else z
 
 
@@ -369,21 +402,22 @@ def _band_width(S, beam_size):
     return max(1, min(int(beam_size), 2 * int(S) + 1))
 
 
-def ctc_state_posteriors(log_probs, labels, terminal, frames, beam_size=1000, max_move=4):
+def ctc_state_posteriors(log_probs, labels, terminal, frames, beam_size=1000, max_move=4, band_lo=None):
     """Posterior of every band position at chosen frames: (gamma float32 [K, W], band_lo int64 [K], log_likelihood float).
 
     gamma[k, j] is the probability that frame ``frames[k]`` sits at state band_lo[k] + j, over every path of the band of
     ``ctc_best_path`` that ends at state ``terminal`` (an int, or a best path whose last value is used); columns past the
     band's width are 0, each row sums to 1.  W = min(beam_size, 2S+1).  ``frames``: strictly increasing in [0, T).
     NumPy in -> NumPy out; ROCm torch tensors go to ``ctc_state_posteriors_device``.  Raises as ``ctc_label_posteriors``,
-    and ValueError for bad frames.
+    and ValueError for bad frames.  ``band_lo``: the band as a table [T], as ``ctc_path_posteriors`` takes it; the band_lo
+    returned then holds the table's values at ``frames``.
     """
     call = ctc_state_posteriors_device if _is_tensor(log_probs) else ctc_state_posteriors_batch
-    (result,) = call([log_probs], [labels], [terminal], [frames], beam_size, max_move)
+    (result,) = call([log_probs], [labels], [terminal], [frames], beam_size, max_move, band_lo=_one_table(band_lo))
     return result
 
 
-def _state_posteriors(lat, terminals, frames, beam_size, max_move, out, return_status):
+def _state_posteriors(lat, terminals, frames, beam_size, max_move, out, return_status, band_lo=None):
     if lat is None:
         return ([], []) if return_status else []
     if len(frames) != lat.n:
@@ -399,29 +433,30 @@ def _state_posteriors(lat, terminals, frames, beam_size, max_move, out, return_s
     p_ldo, _k5 = _i64_array([max(lat.ld(g), W) for g, W in zip(gammas, Ws)])   # (a tensor with no rows may report any stride)
     p_lo, _k6 = _ptr_array([lat.ptr(x) for x in los])
     return _run_lattices(lat, "state_posteriors", beam_size, max_move, (p_term, p_fr, p_K, p_g, p_ldo, p_lo), list(zip(gammas, los)),
-                         return_status)
+                         return_status, band_lo)
 
 
 def ctc_state_posteriors_batch(log_probs_list, labels_list, terminals, frames_list, beam_size=1000, max_move=4, device=None,
-                               return_status=False):
+                               return_status=False, band_lo=None):
     """State posteriors of many lattices in ONE launch; host NumPy buffers in and out.
 
     Returns a list of (gamma [K_i, W_i], band_lo [K_i], log_likelihood); with ``return_status`` also the per-lattice status
     list, in which case failures do not raise (their rows are NaN, band_lo -1, their log-likelihood NaN, or -inf for
-    KA_ERR_ZERO_MASS).
+    KA_ERR_ZERO_MASS).  ``band_lo``: a list of tables, one per lattice (``ctc_path_posteriors``).
     """
     lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
-    return _state_posteriors(lat, terminals, frames_list, beam_size, max_move, None, return_status)
+    return _state_posteriors(lat, terminals, frames_list, beam_size, max_move, None, return_status, band_lo)
 
 
-def ctc_state_posteriors_device(log_probs, labels, terminals, frames, beam_size=1000, max_move=4, out=None, return_status=False):
+def ctc_state_posteriors_device(log_probs, labels, terminals, frames, beam_size=1000, max_move=4, out=None, return_status=False,
+                                band_lo=None):
     """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]), terminals (ints or
     best paths) and host frame lists (strictly increasing in [0, T_i)); list of (gamma tensor [K_i, W_i], band_lo int64 tensor
     [K_i], both on the device, log_likelihood float) out, W_i = min(beam_size, 2 S_i + 1).  ``out``: optional list of float32
     [K_i, W_i] tensors with unit column stride to write gamma into (views into wider tensors keep their other columns).  One
-    launch on torch's current stream."""
+    launch on torch's current stream.  ``band_lo``: a list of tables, one per lattice, tensors on the device or host arrays."""
     lat = _device_lattices(log_probs, labels, terminals, "terminals")
-    return _state_posteriors(lat, terminals, frames, beam_size, max_move, out, return_status)
+    return _state_posteriors(lat, terminals, frames, beam_size, max_move, out, return_status, band_lo)
 
 
 def boundary_frames(seg_ends, T):
@@ -467,7 +502,7 @@ def segment_boundary_confidence(gamma, band_lo, frames, best_path, seg_ends, n_p
 # ------------------------------------------------------------------------------------------
 # expected state durations and the expected frame of every text boundary
 # ------------------------------------------------------------------------------------------
-def ctc_state_durations(log_probs, labels, terminal, beam_size=1000, max_move=4):
+def ctc_state_durations(log_probs, labels, terminal, beam_size=1000, max_move=4, band_lo=None):
     """How long the model expects every state to last: (duration float64 [L], time_sum float64 [L], log_likelihood float),
     L = 2S+1 positions of the blank-expanded labels (odd position 2i+1: phoneme i, even positions: the blanks around them).
 
@@ -475,14 +510,15 @@ def ctc_state_durations(log_probs, labels, terminal, beam_size=1000, max_move=4)
     (time_sum / duration: the state's expected centre frame), over every path of the band of ``ctc_best_path`` that ends at
     state ``terminal`` (an int, or a best path whose last value is used): the state posteriors of ``ctc_state_posteriors``
     summed over all T frames, without the [T, W] matrix.  duration sums to T.  NumPy in -> NumPy out; ROCm torch tensors go
-    to ``ctc_state_durations_device``.  Raises as ``ctc_label_posteriors``.
+    to ``ctc_state_durations_device``.  Raises as ``ctc_label_posteriors``.  ``band_lo``: the band as a table [T], as
+    ``ctc_path_posteriors`` takes it; a position no frame's band holds has duration 0.
     """
     call = ctc_state_durations_device if _is_tensor(log_probs) else ctc_state_durations_batch
-    (result,) = call([log_probs], [labels], [terminal], beam_size, max_move)
+    (result,) = call([log_probs], [labels], [terminal], beam_size, max_move, band_lo=_one_table(band_lo))
     return result
 
 
-def _state_durations(lat, terminals, beam_size, max_move, out, return_status):
+def _state_durations(lat, terminals, beam_size, max_move, out, return_status, band_lo=None):
     if lat is None:
         return ([], []) if return_status else []
     Ls = [2 * S + 1 for S in lat.S]
@@ -500,26 +536,29 @@ def _state_durations(lat, terminals, beam_size, max_move, out, return_status):
     p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
     p_dur, _k2 = _ptr_array([lat.ptr(x) for x in durs])
     p_sum, _k3 = _ptr_array([lat.ptr(x) for x in sums])
-    return _run_lattices(lat, "state_durations", beam_size, max_move, (p_term, p_dur, p_sum), list(zip(durs, sums)), return_status)
+    return _run_lattices(lat, "state_durations", beam_size, max_move, (p_term, p_dur, p_sum), list(zip(durs, sums)), return_status,
+                         band_lo)
 
 
-def ctc_state_durations_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False):
+def ctc_state_durations_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False,
+                              band_lo=None):
     """State durations of many lattices in ONE launch; host NumPy buffers in and out.
 
     Returns a list of (duration [L_i], time_sum [L_i], log_likelihood); with ``return_status`` also the per-lattice status
     list, in which case failures do not raise (their arrays are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    ``band_lo``: a list of tables, one per lattice (``ctc_path_posteriors``).
     """
     lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
-    return _state_durations(lat, terminals, beam_size, max_move, None, return_status)
+    return _state_durations(lat, terminals, beam_size, max_move, None, return_status, band_lo)
 
 
-def ctc_state_durations_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False):
+def ctc_state_durations_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False, band_lo=None):
     """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]) and terminals (ints
     or best paths), list of (duration, time_sum: float64 tensors [2 S_i + 1] on the device, log_likelihood float) out.
     ``out``: optional list of (duration, time_sum) pairs of contiguous float64 tensors to write into.  One launch on torch's
-    current stream."""
+    current stream.  ``band_lo``: a list of tables, one per lattice, tensors on the device or host arrays."""
     lat = _device_lattices(log_probs, labels, terminals, "terminals")
-    return _state_durations(lat, terminals, beam_size, max_move, out, return_status)
+    return _state_durations(lat, terminals, beam_size, max_move, out, return_status, band_lo)
 
 
 def _host_f64(x):
