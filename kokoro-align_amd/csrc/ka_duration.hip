@@ -5,10 +5,6 @@
 
 namespace ka {
 
-void launch_state_durations(const DurLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
-{
-    launch_fb_ck<DurLattice>({duration_kernel<FbFast<1>>, duration_kernel<FbFast<2>>, duration_kernel<FbFast<3>>, duration_kernel<FbFast<4>>},
-                           duration_kernel<FbGen<>>, lats, n_fast, n_generic, max_move, res, s);
-}
+template void launch_state_durations<BandWalk>(const DurLattice *, int, int, int, PostResult *, hipStream_t);
 
 }  // namespace ka

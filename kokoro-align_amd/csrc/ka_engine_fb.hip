@@ -3,7 +3,7 @@
 // state visit probabilities (ka_visit.hpp), exact boundary-time quantiles (ka_quantile.hpp), alignments sampled from the band
 // posterior (ka_sample.hpp) and the maximum-expected-accuracy alignment (ka_mea.hpp); and, with a driver of its own
 // (banded_impl), the best path over a caller-given band (ka_banded.hpp).  The first four also run over a caller-given band
-// (ka_ctc_*_banded_*: fb_impl<Call, true>, the same driver on Banded<Desc> descriptors).  Host code only.
+// (ka_ctc_*_banded_*: fb_impl<Call, ka::BandTable>, the same driver on Banded<Desc> descriptors).  Host code only.
 // They use the engine's workspace and pinned buffer, with their own kernels and workspace layout, whatever
 // the engine's mode, and run to the end inside the call: no batch stays in flight.
 #include "ka_engine.hpp"
@@ -20,10 +20,10 @@ using ka::plan::align_up;
 
 // ---- best-path posteriors (ka_posterior.hpp), label occupancy (ka_occupancy.hpp), state posteriors at chosen frames
 // (ka_state_posterior.hpp) and expected state durations (ka_duration.hpp): their own kernels and workspace layout, whatever the
-// engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall, DurCall, VisitCall, QuantCall, SampleCall, MeaCall) brings what
-// differs: its own arrays and their
-// checks, its planner and launch, the descriptor fields beyond FbLattice, its own staging (upload: host buffers only;
-// stage: every memory mode), and what two statuses mean.
+// engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall, QuantCall, SampleCall, MeaCall, and PairCall as
+// DurCall and VisitCall) brings what differs: its own arrays and their checks, its planner and its launch (launch<Band>, one
+// for either band), the descriptor fields beyond FbLattice, its own staging (upload: host buffers only; stage: every memory
+// mode), and what two statuses mean.
 struct FbArgs {
     int32_t n;
     const float *const *log_probs;
@@ -53,8 +53,8 @@ struct PostCall {
     const char *bad_lattice(const FbArgs &, int32_t) const { return nullptr; }
     bool buffers(int32_t i) const { return best_path[i] && posteriors[i]; }
     static constexpr auto plan = ka::plan::posterior_workspace;
-    static constexpr auto launch = ka::launch_posteriors;
-    static constexpr auto launch_banded = ka::launch_posteriors_banded;
+    template <class Band>
+    static constexpr auto launch = ka::launch_posteriors<Band>;
     void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         if (a.mem == KA_MEM_HOST) {
@@ -106,8 +106,8 @@ struct OccCall {
     const char *bad_lattice(const FbArgs &a, int32_t i) const { return ld_out[i] < a.V ? ": ld_out < V" : nullptr; }
     bool buffers(int32_t i) const { return occupancy[i] != nullptr; }
     static constexpr auto plan = ka::plan::label_posterior_workspace;
-    static constexpr auto launch = ka::launch_label_posteriors;
-    static constexpr auto launch_banded = ka::launch_label_posteriors_banded;
+    template <class Band>
+    static constexpr auto launch = ka::launch_label_posteriors<Band>;
     void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         if (a.mem == KA_MEM_HOST) {
@@ -161,8 +161,8 @@ struct StateCall {
     {
         return ka::plan::state_posterior_workspace(n, T, S, K, V, beam, max_move, host, cv, off_res);   // (0 for K < 0 or K > T)
     }
-    static constexpr auto launch = ka::launch_state_posteriors;
-    static constexpr auto launch_banded = ka::launch_state_posteriors_banded;
+    template <class Band>
+    static constexpr auto launch = ka::launch_state_posteriors<Band>;
     void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         if (a.mem == KA_MEM_HOST) {
@@ -195,69 +195,50 @@ struct StateCall {
     }
 };
 
-struct DurCall {
+// The expected state durations and the state visit probabilities: one call over what differs, the descriptor's type, the
+// launch and the error texts.  Both take a terminal and two output arrays of 2S+1 doubles, the second optional.
+struct DurKind {
     using Desc = ka::DurLattice;
-    using Carve = ka::plan::DurCarve;
     static constexpr const char *kName = "state durations";
     static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
     static constexpr const char *kZeroMass = ": no path of finite score reaches the terminal";
-    const int64_t *terminal;
-    double *const *duration;
-    double *const *time_sum;   // NULL, or an array in which any entry may be NULL: no first moment for that lattice
-
-    bool arrays() const { return terminal && duration; }
-    const char *bad_lattice(const FbArgs &, int32_t) const { return nullptr; }
-    bool buffers(int32_t i) const { return duration[i] != nullptr; }
-    bool moment(int32_t i) const { return time_sum && time_sum[i]; }
-    static constexpr auto plan = ka::plan::state_duration_workspace;
-    static constexpr auto launch = ka::launch_state_durations;
-    static constexpr auto launch_banded = ka::launch_state_durations_banded;
-    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
-    {
-        if (a.mem == KA_MEM_HOST) {
-            d.dur = reinterpret_cast<double *>(ws + c.dur);
-            d.tsum = moment(i) ? reinterpret_cast<double *>(ws + c.tsum) : nullptr;
-        } else {
-            d.dur = duration[i];
-            d.tsum = moment(i) ? time_sum[i] : nullptr;
-        }
-        fill_slot(d, c, terminal[i], ws);
-    }
-    int upload(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
-    int stage(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
-    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
-    {
-        const size_t bytes = (size_t)(2 * a.S[i] + 1) * sizeof(double);
-        KA_HIP(hipMemcpyAsync(duration[i], ws + c.dur, bytes, hipMemcpyDeviceToHost, a.stream));
-        if (moment(i)) KA_HIP(hipMemcpyAsync(time_sum[i], ws + c.tsum, bytes, hipMemcpyDeviceToHost, a.stream));
-        return KA_OK;
-    }
+    template <class Band>
+    static constexpr auto launch = ka::launch_state_durations<Band>;
 };
-
-struct VisitCall {
+struct VisitKind {
     using Desc = ka::VisitLattice;
-    using Carve = ka::plan::VisitCarve;
     static constexpr const char *kName = "state visits";
     static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
     static constexpr const char *kZeroMass = ": no path of finite score reaches the terminal";
+    template <class Band>
+    static constexpr auto launch = ka::launch_state_visits<Band>;
+};
+template <class Kind>
+struct PairCall {
+    using Desc = typename Kind::Desc;
+    using Carve = ka::plan::PairCarve;
+    static constexpr const char *kName = Kind::kName;
+    static constexpr const char *kBadArgs = Kind::kBadArgs;
+    static constexpr const char *kZeroMass = Kind::kZeroMass;
     const int64_t *terminal;
-    double *const *visit;
-    double *const *exit_time;   // NULL, or an array in which any entry may be NULL: no time moment for that lattice
+    double *const *sum;    // duration, or visit
+    double *const *tsum;   // time_sum, or exit_time: NULL, or an array in which any entry may be NULL: no time moment for that lattice
 
-    bool arrays() const { return terminal && visit; }
+    bool arrays() const { return terminal && sum; }
     const char *bad_lattice(const FbArgs &, int32_t) const { return nullptr; }
-    bool buffers(int32_t i) const { return visit[i] != nullptr; }
-    bool moment(int32_t i) const { return exit_time && exit_time[i]; }
-    static constexpr auto plan = ka::plan::state_visit_workspace;
-    static constexpr auto launch = ka::launch_state_visits;
+    bool buffers(int32_t i) const { return sum[i] != nullptr; }
+    bool moment(int32_t i) const { return tsum && tsum[i]; }
+    static constexpr auto plan = ka::plan::pair_sum_workspace;
+    template <class Band>
+    static constexpr auto launch = Kind::template launch<Band>;
     void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         if (a.mem == KA_MEM_HOST) {
-            d.visit = reinterpret_cast<double *>(ws + c.visit);
-            d.xtime = moment(i) ? reinterpret_cast<double *>(ws + c.xtime) : nullptr;
+            d.sum = reinterpret_cast<double *>(ws + c.sum);
+            d.tsum = moment(i) ? reinterpret_cast<double *>(ws + c.tsum) : nullptr;
         } else {
-            d.visit = visit[i];
-            d.xtime = moment(i) ? exit_time[i] : nullptr;
+            d.sum = sum[i];
+            d.tsum = moment(i) ? tsum[i] : nullptr;
         }
         fill_slot(d, c, terminal[i], ws);
     }
@@ -266,11 +247,13 @@ struct VisitCall {
     int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         const size_t bytes = (size_t)(2 * a.S[i] + 1) * sizeof(double);
-        KA_HIP(hipMemcpyAsync(visit[i], ws + c.visit, bytes, hipMemcpyDeviceToHost, a.stream));
-        if (moment(i)) KA_HIP(hipMemcpyAsync(exit_time[i], ws + c.xtime, bytes, hipMemcpyDeviceToHost, a.stream));
+        KA_HIP(hipMemcpyAsync(sum[i], ws + c.sum, bytes, hipMemcpyDeviceToHost, a.stream));
+        if (moment(i)) KA_HIP(hipMemcpyAsync(tsum[i], ws + c.tsum, bytes, hipMemcpyDeviceToHost, a.stream));
         return KA_OK;
     }
 };
+using DurCall = PairCall<DurKind>;
+using VisitCall = PairCall<VisitKind>;
 
 struct QuantCall {
     using Desc = ka::QuantLattice;
@@ -304,7 +287,8 @@ struct QuantCall {
     {
         return ka::plan::boundary_quantile_workspace(n, T, S, K, M, V, beam, max_move, host, cv, off_res);   // (0 for K < 0 or K > 2S+2)
     }
-    static constexpr auto launch = ka::launch_boundary_quantiles;
+    template <class Band>
+    static constexpr auto launch = ka::launch_boundary_quantiles<Band>;
     void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         if (a.mem == KA_MEM_HOST) {
@@ -393,7 +377,8 @@ struct SampleCall {
     {
         return ka::plan::sample_paths_workspace(n, T, S, n_samples, V, beam, max_move, host, cv, off_res);
     }
-    static constexpr auto launch = ka::launch_sample_paths;
+    template <class Band>
+    static constexpr auto launch = ka::launch_sample_paths;   // (the diagonal only)
     void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         if (a.mem == KA_MEM_HOST) {
@@ -431,7 +416,8 @@ struct MeaCall {
     const char *bad_lattice(const FbArgs &, int32_t) const { return nullptr; }
     bool buffers(int32_t i) const { return path[i] != nullptr; }
     static constexpr auto plan = ka::plan::mea_path_workspace;
-    static constexpr auto launch = ka::launch_mea_path;
+    template <class Band>
+    static constexpr auto launch = ka::launch_mea_path<Band>;
     void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         d.path = a.mem == KA_MEM_HOST ? reinterpret_cast<int32_t *>(ws + c.path) : path[i];
@@ -463,12 +449,14 @@ int fb_readback(const MeaCall &call, const ka::plan::MeaCarve *cv, const FbArgs 
     return KA_OK;
 }
 
-// A call with a table (FbArgs::band_lo) runs as fb_impl<Call, true>: the same steps on Banded<Desc> descriptors, which lie with
-// the staged tables behind the sibling's workspace (plan::band_table_workspace), and Call::launch_banded's kernels.
-template <class Call, bool kBanded = false>
+// A call with a table (FbArgs::band_lo) runs as fb_impl<Call, ka::BandTable>: the same steps on Banded<Desc> descriptors, which
+// lie with the staged tables behind the sibling's workspace (plan::band_table_workspace), and the kernels of
+// Call::launch<ka::BandTable>.  Call::launch<Band> is the call's one launch; a band whose unit does not exist does not link.
+template <class Call, class Band = ka::BandWalk>
 int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
 {
-    using Desc = std::conditional_t<kBanded, ka::Banded<typename Call::Desc>, typename Call::Desc>;
+    constexpr bool kBanded = std::is_same_v<Band, ka::BandTable>;
+    using Desc = ka::BandDesc<typename Call::Desc, Band>;
     static_assert(sizeof(Desc) <= ka::kBandedDescBytes || !kBanded, "descriptor sizes");
     const int32_t n = a.n, V = a.V;
     const hipStream_t stream = a.stream;
@@ -552,10 +540,7 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
     Desc *d_lats = reinterpret_cast<Desc *>(e->res.ws + off_desc);
     ka::PostResult *d_res = reinterpret_cast<ka::PostResult *>(e->res.ws + off_res);
     KA_HIP(hipMemcpyAsync(d_lats, h, (size_t)n * sizeof(Desc), hipMemcpyHostToDevice, stream));
-    if constexpr (kBanded)
-        Call::launch_banded(d_lats, n_fast, n - n_fast, a.max_move, d_res, stream);
-    else
-        Call::launch(d_lats, n_fast, n - n_fast, a.max_move, d_res, stream);
+    Call::template launch<Band>(d_lats, n_fast, n - n_fast, a.max_move, d_res, stream);
     KA_HIP(hipGetLastError());
     KA_HIP(hipMemcpyAsync(h_res, d_res, (size_t)n * sizeof(ka::PostResult), hipMemcpyDeviceToHost, stream));
     if ((rc = fb_readback(call, cv.data(), a, e->res.ws)) != KA_OK) return rc;
@@ -814,7 +799,7 @@ size_t ka_state_duration_workspace_bytes(int32_t n, const int64_t *T, const int6
                                          int32_t mem)
 {
     if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
-    return ka::plan::state_duration_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+    return ka::plan::pair_sum_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
 // ---- the four calls over a caller-given band: their siblings' arguments with band_lo behind max_move ----
@@ -824,7 +809,7 @@ int ka_ctc_path_posteriors_banded_batch_f32(ka_engine *e, int32_t n, const float
                                             float *const *posteriors, double *log_likelihood, int32_t *status, int32_t mem, void *stream)
 {
     if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "posteriors: NULL band_lo");
-    return fb_impl<PostCall, true>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
+    return fb_impl<PostCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
                                    PostCall{best_path, posteriors});
 }
 
@@ -832,7 +817,7 @@ int ka_ctc_path_posteriors_banded_f32(ka_engine *e, const float *log_probs, int6
                                       int32_t beam_size, int32_t max_move, const int32_t *band_lo, const int32_t *best_path,
                                       float *posteriors, double *log_likelihood, int32_t mem, void *stream)
 {
-    return fb_impl<PostCall, true>(
+    return fb_impl<PostCall, ka::BandTable>(
         e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo},
         PostCall{&best_path, &posteriors});
 }
@@ -844,7 +829,7 @@ int ka_ctc_label_posteriors_banded_batch_f32(ka_engine *e, int32_t n, const floa
                                              int32_t mem, void *stream)
 {
     if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "label posteriors: NULL band_lo");
-    return fb_impl<OccCall, true>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
+    return fb_impl<OccCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
                                   OccCall{terminal, occupancy, ld_out});
 }
 
@@ -852,7 +837,7 @@ int ka_ctc_label_posteriors_banded_f32(ka_engine *e, const float *log_probs, int
                                        int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal, float *occupancy,
                                        int64_t ld_out, double *log_likelihood, int32_t mem, void *stream)
 {
-    return fb_impl<OccCall, true>(
+    return fb_impl<OccCall, ka::BandTable>(
         e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo},
         OccCall{&terminal, &occupancy, &ld_out});
 }
@@ -864,7 +849,7 @@ int ka_ctc_state_posteriors_banded_batch_f32(ka_engine *e, int32_t n, const floa
                                              int64_t *const *band_lo, double *log_likelihood, int32_t *status, int32_t mem, void *stream)
 {
     if (n > 0 && !band_table) return fail(KA_ERR_BAD_ARGS, "state posteriors: NULL band table");
-    return fb_impl<StateCall, true>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_table},
+    return fb_impl<StateCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_table},
                                     StateCall{terminal, frames, K, gamma, ld_out, band_lo});
 }
 
@@ -873,7 +858,7 @@ int ka_ctc_state_posteriors_banded_f32(ka_engine *e, const float *log_probs, int
                                        int64_t K, float *gamma, int64_t ld_out, int64_t *band_lo, double *log_likelihood, int32_t mem,
                                        void *stream)
 {
-    return fb_impl<StateCall, true>(
+    return fb_impl<StateCall, ka::BandTable>(
         e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_table},
         StateCall{&terminal, &frames, &K, &gamma, &ld_out, &band_lo});
 }
@@ -885,7 +870,7 @@ int ka_ctc_state_durations_banded_batch_f32(ka_engine *e, int32_t n, const float
                                             int32_t mem, void *stream)
 {
     if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "state durations: NULL band_lo");
-    return fb_impl<DurCall, true>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
+    return fb_impl<DurCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
                                   DurCall{terminal, duration, time_sum});
 }
 
@@ -893,7 +878,7 @@ int ka_ctc_state_durations_banded_f32(ka_engine *e, const float *log_probs, int6
                                       int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal, double *duration,
                                       double *time_sum, double *log_likelihood, int32_t mem, void *stream)
 {
-    return fb_impl<DurCall, true>(
+    return fb_impl<DurCall, ka::BandTable>(
         e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo},
         DurCall{&terminal, &duration, &time_sum});
 }
@@ -924,7 +909,7 @@ int ka_ctc_state_visits_f32(ka_engine *e, const float *log_probs, int64_t T, int
 size_t ka_state_visit_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
 {
     if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
-    return ka::plan::state_visit_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+    return ka::plan::pair_sum_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
 int ka_ctc_boundary_quantiles_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,

@@ -2,7 +2,8 @@
 // posteriors at chosen frames), ka_duration.hpp (expected state durations), ka_mea.hpp (the MEA path) and ka_visit.hpp (state
 // visit probabilities) share, and whose forward half ka_sample.hpp (sampled alignments) reuses: fb_ck_forward<Form>,
 // fb_ck_recompute<Form> and the driver fb_ck<Form, Out>, each written once over three policies (the form, the call's Out and
-// the band: BandWalk, the reference's diagonal, or BandTable, a caller's table), and the launch of the calls' kernels.
+// the band: BandWalk, the reference's diagonal, or BandTable, a caller's table), and the one kernel and the one launch of
+// the calls (fb_ck_kernel, launch_fb_ck).
 //
 // The posterior kernels keep alpha only at the path; these calls need it at band cells, so the forward pass checkpoints the
 // whole column before the first frame of every 32-frame block (with the offset C and the frame maximum m it runs on), and the
@@ -14,8 +15,14 @@
 // Form (FbFast<M> or FbGen of ka_fb_form.hpp, built per lattice) owns how a lattice is run: the threads and how they
 // synchronise, the frame maximum, where a position lives in a column, a checkpoint and the slab, how the frame's log-prob
 // row reaches a cell, and the frame recurrences.  Its table is at the head of ka_fb_form.hpp.
-// Out (the driver's only) owns what a call does with gamma.  It holds the call's outputs and has a hook for each place where
-// the calls differ:
+// Out (the driver's only) owns what a call does with gamma.  It is a template <class Form, class Band> (every call's, so that
+// one launch can name the kernels of all five forms; the band is used where the call needs it), names
+//   Form, Desc                   its form and the call's descriptor
+//   Lds                          what its kernel holds in LDS beyond the form's Shared and the driver's cav: bins, rings, a
+//                                tile.  Sized per form (a ring is the fast form's only and takes none of the generic kernel's
+//                                LDS); empty where a call needs none
+// is built per lattice as Out(descriptor, form, lds), holds the call's outputs and has a hook for each place where the calls
+// differ:
 //   fail(res, status)            a lattice without a result: fill the outputs with NaN, then fb_fail_result
 //   recompute(t0)                recompute the block that starts at t0?  (if not, the walk is re-seated at t1, where the
 //                                recompute would have left it; beta is still stepped through every frame)
@@ -27,8 +34,12 @@
 //                                such column), and its cells are called as (p, lab, w, arg), w the recurrence's value
 //   cells_done(), frame_end(t, lo, hi)   after the frame's cells (before its reduction), and after its bookkeeping (before the
 //                                fast form's end-of-frame fence); a hook owns any barrier or fence that only its kernel needs
-// An Out is templated on the form: it branches on Form::kWave where the forms really differ (an LDS ring or the outputs
-// themselves as accumulators, a register sum or atomics) and takes slots and strides from the form everywhere else.
+// An Out branches on Form::kWave where the forms really differ (an LDS ring or the outputs themselves as accumulators, a
+// register sum or atomics) and takes slots and strides from the form everywhere else.
+// One kernel, fb_ck_kernel<Out, Band>, runs every call: it takes BandDesc<Out::Desc, Band> descriptors (Banded<Desc> under
+// BandTable), and fb_table() is the only place where its body meets the band.  One launch, launch_fb_ck<Out, Band>, names the
+// five kernels of a call and a band; a call's header wraps it in the function ka_launch.hpp declares, and a translation unit
+// holds that function's explicit instantiation for its band.
 // The path sampler (ka_sample.hpp) needs alpha and no beta: it calls fb_ck_forward and fb_ck_recompute and has no Out.
 // Storage: lattices walk slots (launch grid = slots, lattice i on slot i mod grid), so the workspace is bounded by the slots,
 // not by the batch.
@@ -228,14 +239,42 @@ __device__ __forceinline__ void fb_ck(Form &f, PostResult *res, double *cav, Out
     }
 }
 
-// the launch of any of these calls: descriptors [0, n_fast) on min(n_fast, kOccFastSlots) one-wavefront workgroups (fast[M - 1],
+// two rings of 1024 doubles (a position at the form's column slot) for an Out's Lds: the fast form's only, and no byte of the
+// generic kernel's LDS
+template <bool kWave>
+struct FbRings {
+    double r[2][1024];
+    __device__ __forceinline__ double *ring(int i) { return r[i]; }
+};
+template <>
+struct FbRings<false> {
+    __device__ __forceinline__ double *ring(int) { return nullptr; }
+};
+
+// The kernel of every call that goes through fb_ck: lattices walk slots (lattice i on workgroup i mod grid).
+template <class Out, class Band>
+__global__ __launch_bounds__(Out::Form::NT) void fb_ck_kernel(const BandDesc<typename Out::Desc, Band> *__restrict__ lats, int n, PostResult *res)
+{
+    using Form = typename Out::Form;
+    __shared__ typename Form::template Shared<4> sh;
+    __shared__ double cav[kPostCk];
+    __shared__ typename Out::Lds lds;
+    for (int i = blockIdx.x; i < n; i += gridDim.x) {
+        Form f(lats[i], sh);
+        Out out(lats[i], f, lds);
+        fb_ck<Form, Out, Band>(f, res, cav, out, fb_table(lats[i]));
+        f.sync();
+    }
+}
+
+// the launch of kernels that walk slots: descriptors [0, n_fast) on min(n_fast, kOccFastSlots) one-wavefront workgroups (fast[M - 1],
 // M = max_move, 4 above 3), lattice i on workgroup i mod grid (its slot); then [n_fast, n_fast + n_generic) on
 // min(n_generic, kOccGenericSlots) 256-thread workgroups
 template <class Desc>
 using FbCkKernel = void (*)(const Desc *, int, PostResult *);
 template <class Desc>
-void launch_fb_ck(const FbCkKernel<Desc> (&fast)[4], FbCkKernel<Desc> generic, const Desc *lats, int n_fast, int n_generic, int max_move,
-                  PostResult *res, hipStream_t s)
+void launch_fb_slots(const FbCkKernel<Desc> (&fast)[4], FbCkKernel<Desc> generic, const Desc *lats, int n_fast, int n_generic, int max_move,
+                     PostResult *res, hipStream_t s)
 {
     if (n_fast > 0) {
         const dim3 grid(n_fast < kOccFastSlots ? n_fast : kOccFastSlots);
@@ -245,6 +284,16 @@ void launch_fb_ck(const FbCkKernel<Desc> (&fast)[4], FbCkKernel<Desc> generic, c
         const dim3 grid(n_generic < kOccGenericSlots ? n_generic : kOccGenericSlots);
         hipLaunchKernelGGL(generic, grid, dim3(FbGen<>::NT), 0, s, lats + n_fast, n_generic, res);
     }
+}
+// ... of a call's Out over a band: the five kernels are fb_ck_kernel's
+template <template <class, class> class Out, class Band>
+void launch_fb_ck(const BandDesc<typename Out<FbGen<>, Band>::Desc, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res,
+                  hipStream_t s)
+{
+    using Desc = BandDesc<typename Out<FbGen<>, Band>::Desc, Band>;
+    launch_fb_slots<Desc>({fb_ck_kernel<Out<FbFast<1>, Band>, Band>, fb_ck_kernel<Out<FbFast<2>, Band>, Band>, fb_ck_kernel<Out<FbFast<3>, Band>, Band>,
+                           fb_ck_kernel<Out<FbFast<4>, Band>, Band>},
+                          fb_ck_kernel<Out<FbGen<>, Band>, Band>, lats, n_fast, n_generic, max_move, res, s);
 }
 
 }  // namespace ka

@@ -2,8 +2,9 @@
 //
 // The library is built from twenty-two translation units so that the device code compiles in parallel (a single unit took three
 // minutes): ka_engine.hip, ka_engine_fb.hip and ka_entry_misc.hip are host code only and reach the kernels through these
-// functions; each kernel family lives in the .hip file named below and nowhere else.  All functions only enqueue; errors
-// surface through hipGetLastError().
+// functions; each kernel family lives in the .hip file named below and nowhere else.  A forward-backward call's launch is a
+// template over the band, defined in the call's header; its units hold nothing but that template's explicit instantiation, one
+// band each.  All functions only enqueue; errors surface through hipGetLastError().
 #pragma once
 #include "ka_types.hpp"
 
@@ -82,41 +83,40 @@ void launch_stft_frames(const float *y, const int64_t *seg_start, const int64_t 
 void launch_power(const float *reim, int64_t ld_in, float *power, int64_t ld_out, int64_t n, int nf, hipStream_t s);
 void launch_power_to_db(float *x, int64_t ld, int cols, const int64_t *frame_off, unsigned grid_x, unsigned nseg, float top_db, float *segmax, hipStream_t s);
 
-// ---- ka_posterior.hip: forward-backward over the band, posteriors of the caller's best path (ka_posterior.hpp) ----
-// descriptors [0, n_fast): one wavefront per lattice (band <= kFastMaxBand, V <= 64, max_move <= 4), then [n_fast, n_fast +
-// n_generic): one 256-thread workgroup per lattice, columns in global memory
-void launch_posteriors(const PostLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
-
-// ---- ka_occupancy.hip / ka_state_posterior.hip / ka_duration.hip: label occupancy, state posteriors at chosen frames and
-// expected state durations (ka_occupancy.hpp, ka_state_posterior.hpp, ka_duration.hpp), all through launch_fb_ck (ka_fb_ck.hpp): descriptors [0, n_fast): one wavefront per lattice on
-// min(n_fast, kOccFastSlots) workgroups, lattice i on workgroup i mod grid (its workspace slot); then [n_fast, n_fast +
-// n_generic): 256-thread workgroups, min(n_generic, kOccGenericSlots)
-void launch_label_posteriors(const OccLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
-void launch_state_posteriors(const StateLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
-void launch_state_durations(const DurLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
-
-// ---- ka_posterior_banded.hip / ka_occupancy_banded.hip / ka_state_posterior_banded.hip / ka_duration_banded.hip: the four calls
-// above over a caller-given band, Banded<>::band_lo in place of the diagonal; each its sibling's split, grid and slots ----
-void launch_posteriors_banded(const Banded<PostLattice> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
-void launch_label_posteriors_banded(const Banded<OccLattice> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
-void launch_state_posteriors_banded(const Banded<StateLattice> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
-void launch_state_durations_banded(const Banded<DurLattice> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+// ---- the forward-backward calls: one launch per call, a template over the band (BandWalk: the reference's diagonal, on the
+// call's descriptors; BandTable: a caller's table, on Banded<> descriptors, Banded<>::band_lo in place of the diagonal, with
+// the same split, grid and slots).  A call's header defines the template; the unit named holds the instantiation of a band, and
+// a band with no unit does not link ----
+// ka_posterior.hip, ka_posterior_banded.hip: posteriors of the caller's best path (ka_posterior.hpp).  Descriptors [0, n_fast):
+// one wavefront per lattice (band <= kFastMaxBand, V <= 64, max_move <= 4), then [n_fast, n_fast + n_generic): one 256-thread
+// workgroup per lattice, columns in global memory
+template <class Band>
+void launch_posteriors(const BandDesc<PostLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+// The calls below go through launch_fb_ck (ka_fb_ck.hpp): descriptors [0, n_fast): one wavefront per lattice on min(n_fast,
+// kOccFastSlots) workgroups, lattice i on workgroup i mod grid (its workspace slot); then [n_fast, n_fast + n_generic):
+// 256-thread workgroups, min(n_generic, kOccGenericSlots)
+// ka_occupancy.hip, ka_occupancy_banded.hip: label occupancy (ka_occupancy.hpp)
+template <class Band>
+void launch_label_posteriors(const BandDesc<OccLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+// ka_state_posterior.hip, ka_state_posterior_banded.hip: state posteriors at chosen frames (ka_state_posterior.hpp)
+template <class Band>
+void launch_state_posteriors(const BandDesc<StateLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+// ka_duration.hip, ka_duration_banded.hip: expected state durations (ka_duration.hpp)
+template <class Band>
+void launch_state_durations(const BandDesc<DurLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+// ka_visit.hip: state visit probabilities (ka_visit.hpp)
+template <class Band>
+void launch_state_visits(const BandDesc<VisitLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+// ka_quantile.hip: exact boundary-time quantiles (ka_quantile.hpp)
+template <class Band>
+void launch_boundary_quantiles(const BandDesc<QuantLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+// ka_mea.hip: the maximum-expected-accuracy alignment (ka_mea.hpp)
+template <class Band>
+void launch_mea_path(const BandDesc<MeaLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 
 // ---- ka_sample.hip: alignments sampled from the band posterior (ka_sample.hpp): ka_fb_ck.hpp's forward pass and block
-// recompute, launch_fb_ck's form split, grid and slots ----
+// recompute, launch_fb_ck's form split, grid and slots; on the diagonal only ----
 void launch_sample_paths(const SampleLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
-
-// ---- ka_mea.hip: the maximum-expected-accuracy alignment (ka_mea.hpp): ka_fb_ck.hpp's driver with one more policy,
-// launch_fb_ck's form split, grid and slots ----
-void launch_mea_path(const MeaLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
-
-// ---- ka_visit.hip: state visit probabilities (ka_visit.hpp): ka_fb_ck.hpp's driver with one more policy, launch_fb_ck's form
-// split, grid and slots ----
-void launch_state_visits(const VisitLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
-
-// ---- ka_quantile.hip: exact boundary-time quantiles (ka_quantile.hpp): ka_fb_ck.hpp's driver with one more policy,
-// launch_fb_ck's form split, grid and slots ----
-void launch_boundary_quantiles(const QuantLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 
 // ---- ka_banded.hip: best path over a caller-given band (ka_banded.hpp).  Descriptors [0, n_fast): one wavefront per lattice
 // (band <= kFastMaxBand, V <= 64, max_move <= 4), then [n_fast, n_fast + n_generic): one 256-thread workgroup per lattice.

@@ -6,10 +6,6 @@
 
 namespace ka {
 
-void launch_mea_path(const MeaLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
-{
-    launch_fb_ck<MeaLattice>({mea_kernel<FbFast<1>>, mea_kernel<FbFast<2>>, mea_kernel<FbFast<3>>, mea_kernel<FbFast<4>>}, mea_kernel<FbGen<>>,
-                             lats, n_fast, n_generic, max_move, res, s);
-}
+template void launch_mea_path<BandWalk>(const MeaLattice *, int, int, int, PostResult *, hipStream_t);
 
 }  // namespace ka

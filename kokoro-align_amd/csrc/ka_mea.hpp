@@ -56,8 +56,13 @@ __device__ __forceinline__ double mea_ring_value(double v, bool skip)
 }
 
 // fb_ck's policy.  The forms differ in where W and the codes live (above); a position's place in W is the form's column slot.
-template <class Form>
+template <class Form_, class Band>
 struct MeaOut {
+    using Form = Form_;
+    using Desc = MeaLattice;
+    struct Lds : FbRings<Form::kWave> {   // W_{t+1} and W_t
+        int32_t tile[kPostCk];
+    };
     static constexpr int NT = Form::NT;
     const MeaLattice &d;
     Form &f;
@@ -65,8 +70,8 @@ struct MeaOut {
     int32_t *tile;        // kPostCk positions of the path (LDS)
     int64_t nlo, nhi;     // the band of frame t + 1
     uint32_t word;        // fast form: the codes of this lane's cells of the frame
-    __device__ __forceinline__ MeaOut(const MeaLattice &d_, Form &f_, double *ring0, double *ring1, int32_t *tile_)
-        : d(d_), f(f_), wn(Form::kWave ? ring0 : d_.wcol), wc(Form::kWave ? ring1 : d_.wcol + d_.L), tile(tile_), nlo(0), nhi(0), word(0)
+    __device__ __forceinline__ MeaOut(const MeaLattice &d_, Form &f_, Lds &lds)
+        : d(d_), f(f_), wn(Form::kWave ? lds.ring(0) : d_.wcol), wc(Form::kWave ? lds.ring(1) : d_.wcol + d_.L), tile(lds.tile), nlo(0), nhi(0), word(0)
     {
     }
     // a lattice without a result: -1 over [0, T) of the path, NaN as the expected accuracy, and the status and
@@ -142,6 +147,7 @@ struct MeaOut {
     {
         const int tid = threadIdx.x;
         const int64_t T = d.T;
+        static_assert(!Band::kTable, "the walk below steps the diagonal: over a table it needs the table");
         f.sync();   // frame 0's W (and, generic form, every frame's codes), stored by the threads that own the cells, before the thread that walks
         BandWalk bw(d.L, d.beam, T);
         int32_t s = 0;
@@ -186,20 +192,10 @@ struct MeaOut {
     }
 };
 
-template <class Form>
-__global__ __launch_bounds__(Form::NT) void mea_kernel(const MeaLattice *__restrict__ lats, int n, PostResult *res)
+template <class Band>
+void launch_mea_path(const BandDesc<MeaLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
 {
-    __shared__ typename Form::template Shared<4> sh;
-    __shared__ double cav[kPostCk];
-    __shared__ double ring0[1024];   // (the rings are the fast form's: the generic kernel never names them, and they take none
-    __shared__ double ring1[1024];   //  of its LDS)
-    __shared__ int32_t tile[kPostCk];
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        Form f(lats[i], sh);
-        MeaOut<Form> out(lats[i], f, ring0, ring1, tile);
-        fb_ck(f, res, cav, out);
-        f.sync();
-    }
+    launch_fb_ck<MeaOut, Band>(lats, n_fast, n_generic, max_move, res, s);
 }
 
 }  // namespace ka

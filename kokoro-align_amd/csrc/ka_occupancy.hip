@@ -5,10 +5,6 @@
 
 namespace ka {
 
-void launch_label_posteriors(const OccLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
-{
-    launch_fb_ck<OccLattice>({occupancy_kernel<FbFast<1>>, occupancy_kernel<FbFast<2>>, occupancy_kernel<FbFast<3>>, occupancy_kernel<FbFast<4>>},
-                           occupancy_kernel<FbGen<>>, lats, n_fast, n_generic, max_move, res, s);
-}
+template void launch_label_posteriors<BandWalk>(const OccLattice *, int, int, int, PostResult *, hipStream_t);
 
 }  // namespace ka

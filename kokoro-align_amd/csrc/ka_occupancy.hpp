@@ -36,14 +36,19 @@ __device__ __forceinline__ unsigned long long occ_wave_sum(unsigned long long x)
 // fb_ck's policy: every block recomputed, gamma binned per label value, a row of occ per frame.  The forms differ in how a
 // frame's bins are summed and emptied: one wavefront sums its blank cells in registers and owns bin `lane`, a workgroup goes
 // through atomics and a barrier.
-template <class Form>
+template <class Form_, class Band>
 struct OccOut {
+    using Form = Form_;
+    using Desc = OccLattice;
+    struct Lds {
+        unsigned long long bins[Form::kWave ? 64 : kOccLdsBins];
+    };
     static constexpr int NT = Form::NT;
     const OccLattice &d;
     unsigned long long *bins;   // fast form: 64 in LDS; generic: V in LDS up to kOccLdsBins, above it the slot's global row
     unsigned long long blank;   // this thread's blank cells of the frame
-    __device__ __forceinline__ OccOut(const OccLattice &d_, unsigned long long *lbins)
-        : d(d_), bins(Form::kWave || d_.V <= kOccLdsBins ? lbins : d_.gbin), blank(0)
+    __device__ __forceinline__ OccOut(const OccLattice &d_, Form &, Lds &lds)
+        : d(d_), bins(Form::kWave || d_.V <= kOccLdsBins ? lds.bins : d_.gbin), blank(0)
     {
         if (Form::kWave) bins[threadIdx.x] = 0;
         else for (int64_t v = threadIdx.x; v < d.V; v += NT) atomicExch(&bins[v], 0ull);
@@ -91,32 +96,10 @@ struct OccOut {
     }
 };
 
-template <class Form>
-__global__ __launch_bounds__(Form::NT) void occupancy_kernel(const OccLattice *__restrict__ lats, int n, PostResult *res)
+template <class Band>
+void launch_label_posteriors(const BandDesc<OccLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
 {
-    __shared__ typename Form::template Shared<4> sh;
-    __shared__ double cav[kPostCk];
-    __shared__ unsigned long long bins[Form::kWave ? 64 : kOccLdsBins];
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        Form f(lats[i], sh);
-        OccOut<Form> out(lats[i], bins);
-        fb_ck(f, res, cav, out);
-        f.sync();
-    }
-}
-// ... over the caller's table (ka_occupancy_banded.hip)
-template <class Form>
-__global__ __launch_bounds__(Form::NT) void occupancy_banded_kernel(const Banded<OccLattice> *__restrict__ lats, int n, PostResult *res)
-{
-    __shared__ typename Form::template Shared<4> sh;
-    __shared__ double cav[kPostCk];
-    __shared__ unsigned long long bins[Form::kWave ? 64 : kOccLdsBins];
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        Form f(lats[i], sh);
-        OccOut<Form> out(lats[i], bins);
-        fb_ck<Form, OccOut<Form>, BandTable>(f, res, cav, out, lats[i].band_lo);
-        f.sync();
-    }
+    launch_fb_ck<OccOut, Band>(lats, n_fast, n_generic, max_move, res, s);
 }
 
 }  // namespace ka

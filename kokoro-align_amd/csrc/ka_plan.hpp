@@ -761,20 +761,21 @@ inline size_t state_posterior_workspace(int32_t n, const int64_t *T, const int64
 namespace ka {
 namespace plan {
 
-// ---- ka_ctc_state_durations_batch_f32 (ka_duration.hpp): workspace layout ----
-// label_posterior_workspace's layout and slots (the slot's V-wide global bins go unused), with DurLattice descriptors.  The
-// generic form accumulates in the outputs, so a slot holds nothing more; for host buffers the staged duration and time_sum
-// (2S+1 doubles each) lie beside the staged log-probs and labels.
-struct DurCarve : SlotCarve {
-    size_t dur, tsum;   // host buffers only
+// ---- ka_ctc_state_durations_batch_f32 (ka_duration.hpp) and ka_ctc_state_visits_batch_f32 (ka_visit.hpp): workspace layout ----
+// label_posterior_workspace's layout and slots (the slot's V-wide global bins go unused), with PairLattice descriptors (a
+// DurLattice or a VisitLattice, the same bytes).  The generic form accumulates in the outputs, so a slot holds nothing more;
+// for host buffers the two staged outputs (duration and time_sum, or visit and exit_time: 2S+1 doubles each) lie beside the
+// staged log-probs and labels.
+struct PairCarve : SlotCarve {
+    size_t sum, tsum;   // host buffers only
 };
-inline size_t state_duration_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move,
-                                       bool host_buffers, DurCarve *cv, size_t *off_res)
+inline size_t pair_sum_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
+                                 PairCarve *cv, size_t *off_res)
 {
-    return slot_workspace(n, sizeof(DurLattice), T, S, V, beam, max_move, cv, off_res, [&](int32_t, const Shape &sh, DurCarve &c, size_t &off) {
+    return slot_workspace(n, sizeof(PairLattice), T, S, V, beam, max_move, cv, off_res, [&](int32_t, const Shape &sh, PairCarve &c, size_t &off) {
         if (host_buffers) {
             carve_staged(off, sh, V, c);
-            c.dur = off;
+            c.sum = off;
             off += align_up((size_t)sh.L * sizeof(double));
             c.tsum = off;
             off += align_up((size_t)sh.L * sizeof(double));
@@ -783,29 +784,8 @@ inline size_t state_duration_workspace(int32_t n, const int64_t *T, const int64_
     });
 }
 
-// ---- ka_ctc_state_visits_batch_f32 (ka_visit.hpp): workspace layout ----
-// state_duration_workspace's layout with VisitLattice descriptors: the generic form accumulates in the outputs, and for host
-// buffers the staged visit and exit_time (2S+1 doubles each) lie beside the staged log-probs and labels.
-struct VisitCarve : SlotCarve {
-    size_t visit, xtime;   // host buffers only
-};
-inline size_t state_visit_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
-                                    VisitCarve *cv, size_t *off_res)
-{
-    return slot_workspace(n, sizeof(VisitLattice), T, S, V, beam, max_move, cv, off_res, [&](int32_t, const Shape &sh, VisitCarve &c, size_t &off) {
-        if (host_buffers) {
-            carve_staged(off, sh, V, c);
-            c.visit = off;
-            off += align_up((size_t)sh.L * sizeof(double));
-            c.xtime = off;
-            off += align_up((size_t)sh.L * sizeof(double));
-        }
-        return true;
-    });
-}
-
 // ---- ka_ctc_boundary_quantiles_batch_f32 (ka_quantile.hpp): workspace layout ----
-// state_duration_workspace's layout and slots with QuantLattice descriptors, and per lattice, in both memory modes, its
+// pair_sum_workspace's layout and slots with QuantLattice descriptors, and per lattice, in both memory modes, its
 // uploaded cuts (K int64) with their start frames behind them (K int32), and for host buffers the staged quantiles [K, M]
 // beside the staged log-probs and labels.  Behind the shared slots: the call's thresholds (kMaxLevels 64-bit words), then one
 // row of 64-bit words per generic slot, as wide as the widest band among the call's generic lattices.

@@ -18,8 +18,8 @@
 // No alpha lattice is stored: the forward pass writes alpha_t(p_t) - C_{32k-1} (k = t / 32) into the caller's posterior
 // buffer as a float and C_{32k-1} into a double per 32 frames; the backward pass carries beta across the band and
 // overwrites the buffer with the posterior, combining the two halves and Z in double before the one exp.
-// One pass, posterior_lattice<Form, Band>, behind two kernels (posterior_kernel<Form> on the reference's diagonal band,
-// posterior_banded_kernel<Form> on a caller's table), over the form policy of ka_fb_form.hpp on a PostLattice: the fast form with the label
+// One pass, posterior_lattice<Form, Band>, behind one kernel, posterior_kernel<Form, Band> (BandWalk: the reference's diagonal
+// band; BandTable: a caller's table, on Banded<PostLattice> descriptors), over the form policy of ka_fb_form.hpp on a PostLattice: the fast form with the label
 // ring (PostFast<M>) and the generic form (PostGen).  The form brings the threads, the columns, the row, the labels and the
 // frame recurrences; the kernel brings the band walk, the path prefetches and what happens at the path.
 #pragma once
@@ -167,20 +167,25 @@ __device__ __forceinline__ void posterior_lattice(const PostLattice &d, typename
     }
 }
 
-template <class Form>
-__global__ __launch_bounds__(Form::NT) void posterior_kernel(const PostLattice *__restrict__ lats, PostResult *res)
+template <class Form, class Band>
+__global__ __launch_bounds__(Form::NT) void posterior_kernel(const BandDesc<PostLattice, Band> *__restrict__ lats, PostResult *res)
 {
-    const PostLattice &d = lats[blockIdx.x];
+    const BandDesc<PostLattice, Band> &d = lats[blockIdx.x];
     __shared__ typename Form::template Shared<4> sh;
-    posterior_lattice<Form, BandWalk>(d, sh, nullptr, res);
+    posterior_lattice<Form, Band>(d, sh, fb_table(d), res);
 }
-// ... over the caller's table (ka_posterior_banded.hip)
-template <class Form>
-__global__ __launch_bounds__(Form::NT) void posterior_banded_kernel(const Banded<PostLattice> *__restrict__ lats, PostResult *res)
+
+// descriptors [0, n_fast) in the fast form (fast[M - 1], M = max_move, 4 above 3), then n_generic in the generic form; one
+// workgroup per lattice
+template <class Band>
+void launch_posteriors(const BandDesc<PostLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
 {
-    const Banded<PostLattice> &d = lats[blockIdx.x];
-    __shared__ typename Form::template Shared<4> sh;
-    posterior_lattice<Form, BandTable>(d, sh, d.band_lo, res);
+    using Kernel = void (*)(const BandDesc<PostLattice, Band> *, PostResult *);
+    static constexpr Kernel fast[4] = {posterior_kernel<PostFast<1>, Band>, posterior_kernel<PostFast<2>, Band>, posterior_kernel<PostFast<3>, Band>,
+                                       posterior_kernel<PostFast<4>, Band>};
+    if (n_fast > 0)
+        hipLaunchKernelGGL(fast[(max_move >= 1 && max_move <= 3 ? max_move : 4) - 1], dim3(n_fast), dim3(PostFast<1>::NT), 0, s, lats, res);
+    if (n_generic > 0) hipLaunchKernelGGL((posterior_kernel<PostGen, Band>), dim3(n_generic), dim3(PostGen::NT), 0, s, lats + n_fast, res);
 }
 
 }  // namespace ka

@@ -145,6 +145,14 @@ struct BandTable {
         hi = ((int64_t)L - lo < B) ? (int64_t)L : lo + B;
     }
 };
+// the table a descriptor brings: none for a call's own descriptor (BandWalk), Banded<>::band_lo (BandTable).  The one place
+// where a kernel's body meets the band.
+__device__ __forceinline__ const int32_t *fb_table(const FbLattice &) { return nullptr; }
+template <class Desc>
+__device__ __forceinline__ const int32_t *fb_table(const Banded<Desc> &d)
+{
+    return d.band_lo;
+}
 // error flags -> status: a bad label is reported before anything runs; then NaN, +inf, a path value outside [0, L)
 __device__ __forceinline__ int post_status_of(int flags)
 {

@@ -6,10 +6,6 @@
 
 namespace ka {
 
-void launch_boundary_quantiles(const QuantLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
-{
-    launch_fb_ck<QuantLattice>({quantile_kernel<FbFast<1>>, quantile_kernel<FbFast<2>>, quantile_kernel<FbFast<3>>, quantile_kernel<FbFast<4>>},
-                               quantile_kernel<FbGen<>>, lats, n_fast, n_generic, max_move, res, s);
-}
+template void launch_boundary_quantiles<BandWalk>(const QuantLattice *, int, int, int, PostResult *, hipStream_t);
 
 }  // namespace ka

@@ -51,8 +51,13 @@ __device__ __forceinline__ unsigned long long quant_wave_scan(unsigned long long
 }
 
 // fb_ck's policy.  The forms differ in where the frame's row lives and in how wide the scan is.
-template <class Form>
+template <class Form_, class Band>
 struct QuantOut {
+    using Form = Form_;
+    using Desc = QuantLattice;
+    struct Lds {   // the fast form's ring, or the generic form's totals of its wavefronts
+        unsigned long long w[Form::kWave ? kQuantRing : Form::NT / 64];
+    };
     static constexpr int NT = Form::NT;
     const QuantLattice &d;
     unsigned long long *row;    // fast form: the LDS ring; generic: the slot's workspace row
@@ -60,8 +65,8 @@ struct QuantOut {
     unsigned long long thr[kMaxLevels];   // the thresholds; those past M can never be reached
     int64_t ka, kb;             // the cuts inside the band of the frame last seen: indices [ka, kb)
     bool dna, dnb;              // this lane's look below ka and kb for the frame in flight (asked for before the frame's cells)
-    __device__ __forceinline__ QuantOut(const QuantLattice &d_, unsigned long long *ring, unsigned long long *part_)
-        : d(d_), row(Form::kWave ? ring : d_.frow), part(part_), ka(d_.K), kb(d_.K), dna(false), dnb(false)
+    __device__ __forceinline__ QuantOut(const QuantLattice &d_, Form &, Lds &lds)
+        : d(d_), row(Form::kWave ? lds.w : d_.frow), part(lds.w), ka(d_.K), kb(d_.K), dna(false), dnb(false)
     {
 #pragma unroll
         for (int m = 0; m < kMaxLevels; ++m) thr[m] = m < d.M ? d.thr[m] : ~0ull;
@@ -182,19 +187,10 @@ struct QuantOut {
     }
 };
 
-template <class Form>
-__global__ __launch_bounds__(Form::NT) void quantile_kernel(const QuantLattice *__restrict__ lats, int n, PostResult *res)
+template <class Band>
+void launch_boundary_quantiles(const BandDesc<QuantLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
 {
-    __shared__ typename Form::template Shared<4> sh;
-    __shared__ double cav[kPostCk];
-    __shared__ unsigned long long ring[Form::kWave ? kQuantRing : 1];   // (the ring is the fast form's, the totals the generic one's)
-    __shared__ unsigned long long part[Form::kWave ? 1 : Form::NT / 64];
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        Form f(lats[i], sh);
-        QuantOut<Form> out(lats[i], ring, part);
-        fb_ck(f, res, cav, out);
-        f.sync();
-    }
+    launch_fb_ck<QuantOut, Band>(lats, n_fast, n_generic, max_move, res, s);
 }
 
 }  // namespace ka

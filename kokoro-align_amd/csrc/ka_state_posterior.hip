@@ -5,11 +5,6 @@
 
 namespace ka {
 
-void launch_state_posteriors(const StateLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
-{
-    launch_fb_ck<StateLattice>({state_posterior_kernel<FbFast<1>>, state_posterior_kernel<FbFast<2>>, state_posterior_kernel<FbFast<3>>,
-                                state_posterior_kernel<FbFast<4>>},
-                               state_posterior_kernel<FbGen<>>, lats, n_fast, n_generic, max_move, res, s);
-}
+template void launch_state_posteriors<BandWalk>(const StateLattice *, int, int, int, PostResult *, hipStream_t);
 
 }  // namespace ka

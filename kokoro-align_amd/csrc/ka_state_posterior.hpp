@@ -21,12 +21,15 @@ namespace ka {
 __device__ __forceinline__ int64_t st_frame(const StateLattice &d, int64_t kq) { return kq >= 0 ? d.frames[kq] : -1; }
 
 // fb_ck's policy; the same in both forms but for the threads a row's tail is zeroed with
-template <class Form>
+template <class Form_, class Band>
 struct StOut {
+    using Form = Form_;
+    using Desc = StateLattice;
+    struct Lds {};
     static constexpr int NT = Form::NT;
     const StateLattice &d;
     int64_t kq, fq;   // the next query frame down: its index and frame
-    __device__ __forceinline__ StOut(const StateLattice &d_) : d(d_), kq((int64_t)d_.K - 1), fq(st_frame(d_, (int64_t)d_.K - 1)) {}
+    __device__ __forceinline__ StOut(const StateLattice &d_, Form &, Lds &) : d(d_), kq((int64_t)d_.K - 1), fq(st_frame(d_, (int64_t)d_.K - 1)) {}
     // a lattice without a result: NaN rows over [0, W), band_lo -1, and the status and log-likelihood of fb_fail_result
     __device__ __forceinline__ void fail(PostResult *res, int status)
     {
@@ -58,30 +61,11 @@ struct StOut {
     }
 };
 
-template <class Form>
-__global__ __launch_bounds__(Form::NT) void state_posterior_kernel(const StateLattice *__restrict__ lats, int n, PostResult *res)
+// (over a caller's table, band_lo[k] is the table's value at f_k)
+template <class Band>
+void launch_state_posteriors(const BandDesc<StateLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
 {
-    __shared__ typename Form::template Shared<4> sh;
-    __shared__ double cav[kPostCk];
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        Form f(lats[i], sh);
-        StOut<Form> out(lats[i]);
-        fb_ck(f, res, cav, out);
-        f.sync();
-    }
-}
-// ... over the caller's table (ka_state_posterior_banded.hip): band_lo[k] is then the table's value at f_k
-template <class Form>
-__global__ __launch_bounds__(Form::NT) void state_posterior_banded_kernel(const Banded<StateLattice> *__restrict__ lats, int n, PostResult *res)
-{
-    __shared__ typename Form::template Shared<4> sh;
-    __shared__ double cav[kPostCk];
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        Form f(lats[i], sh);
-        StOut<Form> out(lats[i]);
-        fb_ck<Form, StOut<Form>, BandTable>(f, res, cav, out, lats[i].band_lo);
-        f.sync();
-    }
+    launch_fb_ck<StOut, Band>(lats, n_fast, n_generic, max_move, res, s);
 }
 
 }  // namespace ka

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace ka {
 
 // Pointers read from a descriptor in memory are generic ("flat") to the compiler; everything
@@ -201,15 +203,14 @@ struct StateLattice : FbCkLattice {
     int32_t W;                    // widest band: max(1, min(beam, L))
 };
 // ---- expected state durations (ka_duration.hpp): the occupancy's slots and form split ----
-struct DurLattice : FbCkLattice {
-    double *dur;                  // [L] output: D(s) = sum over t of gamma_t(s)
-    double *tsum;                 // [L] output, or NULL: B(s) = sum over t of t gamma_t(s)
+// and state visit probabilities (ka_visit.hpp): both sum a value e_t(s) of every band cell and its first time moment per
+// position (ka_pair_acc.hpp), so they share the descriptor and differ in the type alone
+struct PairLattice : FbCkLattice {
+    double *sum;                  // [L] output: sum over t of e_t(s)
+    double *tsum;                 // [L] output, or NULL: sum over t of t e_t(s)
 };
-// ---- state visit probabilities (ka_visit.hpp): the occupancy's slots and form split ----
-struct VisitLattice : FbCkLattice {
-    double *visit;                // [L] output: V(s) = sum over t of gamma_t(s) r_t(s), the probability of passing through s
-    double *xtime;                // [L] output, or NULL: X(s) = sum over t of t gamma_t(s) r_t(s)
-};
+struct DurLattice : PairLattice {};     // e = gamma_t(s): D(s) and B(s)
+struct VisitLattice : PairLattice {};   // e = gamma_t(s) r_t(s): V(s), the probability of passing through s, and X(s)
 // ---- exact boundary-time quantiles (ka_quantile.hpp): the occupancy's slots and form split ----
 constexpr int kMaxLevels = 8;     // levels per call
 struct QuantLattice : FbCkLattice {
@@ -248,6 +249,12 @@ template <class Desc>
 struct Banded : Desc {
     const int32_t *band_lo;   // [T] the caller's table (device): lo_t
 };
+// the band policies of the device code (ka_posterior_common.hpp: the reference's diagonal, a caller's table) name the
+// descriptor a kernel and its launch take
+struct BandWalk;
+struct BandTable;
+template <class Desc, class Band>
+using BandDesc = std::conditional_t<std::is_same_v<Band, BandTable>, Banded<Desc>, Desc>;
 constexpr size_t kBandedDescBytes = 144;   // the largest of them: what ka_band_table_workspace_bytes reserves per lattice
 static_assert(sizeof(Banded<PostLattice>) == 96 && sizeof(Banded<OccLattice>) == 128 && sizeof(Banded<StateLattice>) == kBandedDescBytes &&
                   sizeof(Banded<DurLattice>) == 128,

@@ -5,10 +5,6 @@
 
 namespace ka {
 
-void launch_state_visits(const VisitLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
-{
-    launch_fb_ck<VisitLattice>({visit_kernel<FbFast<1>>, visit_kernel<FbFast<2>>, visit_kernel<FbFast<3>>, visit_kernel<FbFast<4>>},
-                             visit_kernel<FbGen<>>, lats, n_fast, n_generic, max_move, res, s);
-}
+template void launch_state_visits<BandWalk>(const VisitLattice *, int, int, int, PostResult *, hipStream_t);
 
 }  // namespace ka

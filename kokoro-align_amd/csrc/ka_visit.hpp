@@ -19,51 +19,23 @@
 // A cell with gamma = 0 adds exactly 0.0.  r <= 1 and the operand is the duration call's float, so V <= D and X <= B hold bit
 // for bit, and a position that one frame's band holds has D's bits.
 //
-// Where the accumulators live: as in ka_duration.hpp.  Fast form: two LDS rings at the form's column slot, positions
-// [hi_t, hi_{t+1}) retired before frame t's cells; generic form: the outputs themselves, zeroed first.
+// Where the accumulators live, how positions retire from them and what no band holds: PairAcc (ka_pair_acc.hpp), as for the
+// durations.
 #pragma once
-#include "ka_fb_ck.hpp"
+#include "ka_pair_acc.hpp"
 
 namespace ka {
 
-template <class Form>
-struct VisitOut {
-    static constexpr int NT = Form::NT;
+// fb_ck's policy: PairAcc's hooks, the next column, and the value added per cell, gamma r
+template <class Form, class Band>
+struct VisitOut : PairAcc<Form, Band> {
+    using Desc = VisitLattice;
     static constexpr bool kNextColumn = true;   // fb_ck hands next_column() the column of frame t + 1 before frame t's cells
-    const VisitLattice &d;
-    double *accV, *accX;   // fast form: the LDS rings; generic: the outputs (accX NULL without an exit_time)
-    int64_t nlo, nhi;      // the band of frame t + 1 ([L, L) above the last frame)
-    const double *gn, *vn;   // G_{t+1} and its vetoable copy
-    double nprev;            // the maximum the recurrence takes off frame t + 1's log-sum-exp
-    bool last;               // t = T-1: no frame above
-    __device__ __forceinline__ VisitOut(const VisitLattice &d_, double *ringV, double *ringX)
-        : d(d_), accV(Form::kWave ? ringV : d_.visit), accX(Form::kWave ? ringX : d_.xtime), nlo(d_.L), nhi(d_.L), gn(nullptr), vn(nullptr),
-          nprev(0.0), last(true)
-    {
-        if (Form::kWave) {   // (whatever the slot's last lattice left)
-            for (int s = threadIdx.x; s < 1024; s += NT) {
-                accV[s] = 0.0;
-                accX[s] = 0.0;
-            }
-        } else {
-            for (int64_t p = threadIdx.x; p < d.L; p += NT) {
-                accV[p] = 0.0;
-                if (accX) accX[p] = 0.0;
-            }
-        }
-    }
-    // a lattice without a result: NaN over [0, L), and the status and log-likelihood of fb_fail_result
-    __device__ __forceinline__ void fail(PostResult *res, int status)
-    {
-        for (int64_t p = threadIdx.x; p < d.L; p += NT) {
-            reinterpret_cast<uint64_t *>(d.visit)[p] = kNaN64;
-            if (d.xtime) reinterpret_cast<uint64_t *>(d.xtime)[p] = kNaN64;
-        }
-        fb_fail_result(d, res, status);
-    }
-    __device__ __forceinline__ bool recompute(int64_t) const { return true; }
-    // the driver's hook, once a frame before cells(t, lo): frame t + 1's column and maximum (its band is kept here, as the
-    // retire rule needs it)
+    const double *gn = nullptr, *vn = nullptr;   // G_{t+1} and its vetoable copy
+    double nprev = 0.0;                           // the maximum the recurrence takes off frame t + 1's log-sum-exp
+    bool last = true;                             // t = T-1: no frame above
+    using PairAcc<Form, Band>::PairAcc;
+    // the driver's hook, once a frame before cells(t, lo): frame t + 1's column and maximum (PairAcc keeps its band)
     __device__ __forceinline__ void next_column(const double *gn_, const double *vn_, double nprev_, bool last_)
     {
         gn = gn_;
@@ -71,33 +43,15 @@ struct VisitOut {
         nprev = nprev_;
         last = last_;
     }
-    // fast form, before frame t's cells: the positions [hi_t, hi_{t+1}) go to the outputs - the sums of those frame t + 1
-    // held, 0 for those the band jumped over - and their slots are zeroed
-    __device__ __forceinline__ void retire(int64_t hi)
-    {
-        for (int64_t p = hi + threadIdx.x; p < nhi; p += NT) {
-            const bool held = p >= nlo;
-            const int s = (int)Form::cslot(p);
-            d.visit[p] = held ? accV[s] : 0.0;
-            if (d.xtime) d.xtime[p] = held ? accX[s] : 0.0;
-            if (held) {
-                accV[s] = 0.0;
-                accX[s] = 0.0;
-            }
-        }
-    }
     __device__ __forceinline__ auto cells(int64_t t, int64_t lo)
     {
-        const int64_t hi = (d.L - lo < d.beam) ? (int64_t)d.L : lo + d.beam;   // hi_t from lo_t, as post_band forms it
-        if (Form::kWave) retire(hi);
-        const int64_t blo = nlo, bhi = nhi;   // band t + 1, which the cells' terms lie in
-        nlo = lo;
-        nhi = hi;
-        const double tt = (double)t, np = nprev, NINF = post_dninf();
+        const int64_t blo = this->nlo, bhi = this->nhi;   // band t + 1, which the cells' terms lie in
+        this->retire(lo);
+        const auto add = this->adder(t);
+        const double np = nprev, NINF = post_dninf();
         const bool top = last;
         const double *g1 = gn, *v1 = vn;
-        double *aV = accV, *aX = accX;
-        int M = d.max_move;
+        int M = this->d.max_move;
         if constexpr (Form::kWave) M = Form::kMoves;
         return [=](int64_t p, int32_t, double w, auto arg) {
             const double g = (double)fb_gamma(arg());
@@ -117,36 +71,15 @@ struct VisitOut {
                 }
                 e = g * r;
             }
-            const int64_t s = Form::cslot(p);
-            aV[s] += e;
-            if (Form::kWave || aX) aX[s] += tt * e;
+            add(p, e);
         };
-    }
-    __device__ __forceinline__ void cells_done() {}
-    __device__ __forceinline__ void frame_end(int64_t t, int64_t lo, int64_t hi)
-    {
-        if (!Form::kWave || t != 0) return;
-        post_wave_sync();   // frame 0's adds, made by the lanes that own the cells, before the lanes that write them out
-        for (int64_t p = lo + threadIdx.x; p < hi; p += NT) {
-            d.visit[p] = accV[Form::cslot(p)];
-            if (d.xtime) d.xtime[p] = accX[Form::cslot(p)];
-        }
     }
 };
 
-template <class Form>
-__global__ __launch_bounds__(Form::NT) void visit_kernel(const VisitLattice *__restrict__ lats, int n, PostResult *res)
+template <class Band>
+void launch_state_visits(const BandDesc<VisitLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
 {
-    __shared__ typename Form::template Shared<4> sh;
-    __shared__ double cav[kPostCk];
-    __shared__ double ringV[1024];   // (the rings are the fast form's: the generic kernel never names them, and they take none
-    __shared__ double ringX[1024];   //  of its LDS)
-    for (int i = blockIdx.x; i < n; i += gridDim.x) {
-        Form f(lats[i], sh);
-        VisitOut<Form> out(lats[i], ringV, ringX);
-        fb_ck(f, res, cav, out);
-        f.sync();
-    }
+    launch_fb_ck<VisitOut, Band>(lats, n_fast, n_generic, max_move, res, s);
 }
 
 }  // namespace ka

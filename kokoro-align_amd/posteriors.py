@@ -518,26 +518,26 @@ def ctc_state_durations(log_probs, labels, terminal, beam_size=1000, max_move=4,
     return result
 
 
-def _state_durations(lat, terminals, beam_size, max_move, out, return_status, band_lo=None):
+def _state_pairs(call, pair, lat, terminals, beam_size, max_move, out, return_status, band_lo=None):
+    """The calls that write two float64 [2S+1] arrays per lattice, ``pair`` their names: "state_durations" and "state_visits"."""
     if lat is None:
         return ([], []) if return_status else []
     Ls = [2 * S + 1 for S in lat.S]
     if out is None:
-        durs = [lat.empty(L, np.float64) for L in Ls]
         sums = [lat.empty(L, np.float64) for L in Ls]
+        moments = [lat.empty(L, np.float64) for L in Ls]
     else:
         import torch
         if len(out) != lat.n or any(len(o) != 2 for o in out):
-            raise ValueError("out must hold one (duration, time_sum) pair of tensors per lattice")
+            raise ValueError(f"out must hold one ({pair[0]}, {pair[1]}) pair of tensors per lattice")
         for o, L in zip(out, Ls):
             if any(x.dtype != torch.float64 or tuple(x.shape) != (L,) or not x.is_contiguous() or x.device != lat.dev for x in o):
                 raise ValueError("out tensors must be contiguous float64 [2 S_i + 1] on the input's device")
-        durs, sums = [o[0] for o in out], [o[1] for o in out]
+        sums, moments = [o[0] for o in out], [o[1] for o in out]
     p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
-    p_dur, _k2 = _ptr_array([lat.ptr(x) for x in durs])
-    p_sum, _k3 = _ptr_array([lat.ptr(x) for x in sums])
-    return _run_lattices(lat, "state_durations", beam_size, max_move, (p_term, p_dur, p_sum), list(zip(durs, sums)), return_status,
-                         band_lo)
+    p_sum, _k2 = _ptr_array([lat.ptr(x) for x in sums])
+    p_mom, _k3 = _ptr_array([lat.ptr(x) for x in moments])
+    return _run_lattices(lat, call, beam_size, max_move, (p_term, p_sum, p_mom), list(zip(sums, moments)), return_status, band_lo)
 
 
 def ctc_state_durations_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False,
@@ -549,7 +549,7 @@ def ctc_state_durations_batch(log_probs_list, labels_list, terminals, beam_size=
     ``band_lo``: a list of tables, one per lattice (``ctc_path_posteriors``).
     """
     lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
-    return _state_durations(lat, terminals, beam_size, max_move, None, return_status, band_lo)
+    return _state_pairs("state_durations", ("duration", "time_sum"), lat, terminals, beam_size, max_move, None, return_status, band_lo)
 
 
 def ctc_state_durations_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False, band_lo=None):
@@ -558,7 +558,7 @@ def ctc_state_durations_device(log_probs, labels, terminals, beam_size=1000, max
     ``out``: optional list of (duration, time_sum) pairs of contiguous float64 tensors to write into.  One launch on torch's
     current stream.  ``band_lo``: a list of tables, one per lattice, tensors on the device or host arrays."""
     lat = _device_lattices(log_probs, labels, terminals, "terminals")
-    return _state_durations(lat, terminals, beam_size, max_move, out, return_status, band_lo)
+    return _state_pairs("state_durations", ("duration", "time_sum"), lat, terminals, beam_size, max_move, out, return_status, band_lo)
 
 
 def _host_f64(x):
@@ -631,27 +631,6 @@ def ctc_state_visits(log_probs, labels, terminal, beam_size=1000, max_move=4):
     return result
 
 
-def _state_visits(lat, terminals, beam_size, max_move, out, return_status):
-    if lat is None:
-        return ([], []) if return_status else []
-    Ls = [2 * S + 1 for S in lat.S]
-    if out is None:
-        visits = [lat.empty(L, np.float64) for L in Ls]
-        exits = [lat.empty(L, np.float64) for L in Ls]
-    else:
-        import torch
-        if len(out) != lat.n or any(len(o) != 2 for o in out):
-            raise ValueError("out must hold one (visit, exit_time) pair of tensors per lattice")
-        for o, L in zip(out, Ls):
-            if any(x.dtype != torch.float64 or tuple(x.shape) != (L,) or not x.is_contiguous() or x.device != lat.dev for x in o):
-                raise ValueError("out tensors must be contiguous float64 [2 S_i + 1] on the input's device")
-        visits, exits = [o[0] for o in out], [o[1] for o in out]
-    p_term, _k1 = _i64_array([_terminal_of(s) for s in terminals])
-    p_vis, _k2 = _ptr_array([lat.ptr(x) for x in visits])
-    p_exit, _k3 = _ptr_array([lat.ptr(x) for x in exits])
-    return _run_lattices(lat, "state_visits", beam_size, max_move, (p_term, p_vis, p_exit), list(zip(visits, exits)), return_status)
-
-
 def ctc_state_visits_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False):
     """State visit probabilities of many lattices in ONE launch; host NumPy buffers in and out.
 
@@ -659,7 +638,7 @@ def ctc_state_visits_batch(log_probs_list, labels_list, terminals, beam_size=100
     list, in which case failures do not raise (their arrays are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
     """
     lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
-    return _state_visits(lat, terminals, beam_size, max_move, None, return_status)
+    return _state_pairs("state_visits", ("visit", "exit_time"), lat, terminals, beam_size, max_move, None, return_status)
 
 
 def ctc_state_visits_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False):
@@ -668,7 +647,7 @@ def ctc_state_visits_device(log_probs, labels, terminals, beam_size=1000, max_mo
     ``out``: optional list of (visit, exit_time) pairs of contiguous float64 tensors to write into.  One launch on torch's
     current stream."""
     lat = _device_lattices(log_probs, labels, terminals, "terminals")
-    return _state_visits(lat, terminals, beam_size, max_move, out, return_status)
+    return _state_pairs("state_visits", ("visit", "exit_time"), lat, terminals, beam_size, max_move, out, return_status)
 
 
 def phoneme_visits(visit):

@@ -7,19 +7,11 @@ bit for bit.
 Every output lies in a buffer filled with a sentinel (-7.0, band_lo -9, status 99) that is GUARD entries longer than the output,
 and two-dimensional outputs have rows GUARD columns wider than what a call may write: ``Result.guards_intact()`` tells whether a
 call wrote outside an output's extent."""
-import ctypes
-
 import numpy as np
 
-from fb_harness import I, P, _lattices, band_width
+from fb_harness import GUARD, SENTINEL, I, P, _addresses, _lattices, band_width
 
-GUARD = 4
-SENTINEL = -7.0
 KINDS = ("path_posteriors", "label_posteriors", "state_posteriors", "state_durations")
-
-
-def _addresses(xs):
-    return ctypes.cast((ctypes.c_void_p * len(xs))(*xs), ctypes.POINTER(ctypes.c_void_p))
 
 
 class Result:

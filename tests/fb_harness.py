@@ -12,6 +12,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 P = lambda xs: ctypes.cast((ctypes.c_void_p * len(xs))(*[x.ctypes.data for x in xs]), ctypes.POINTER(ctypes.c_void_p))
 I = lambda xs: (ctypes.c_int64 * len(xs))(*[int(v) for v in xs])
+GUARD = 4          # what a float output's buffer is longer than the output, filled with ...
+SENTINEL = -7.0    # ... the value no call writes (statuses: 99), so a test can tell what a call wrote and that it stayed inside
+
+
+def _addresses(xs):
+    return ctypes.cast((ctypes.c_void_p * len(xs))(*xs), ctypes.POINTER(ctypes.c_void_p))
 
 
 def record(call, ratio, m):

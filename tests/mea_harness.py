@@ -2,19 +2,12 @@
 the posterior calls: they go to the C ABI through ``eng.lib`` and never through kokoro_align_amd/posteriors.py.  A path buffer
 holds T + GUARD int32 values filled with the sentinel -77, the expected accuracies are filled with -7.0 and the statuses with
 99, so a test can tell what a call wrote, and that it wrote nothing past T."""
-import ctypes
-
 import numpy as np
 
-from fb_harness import I, P, _lattices, _one
+from fb_harness import GUARD, I, P, _addresses, _lattices, _one
 
-GUARD = 4
 SENTINEL = -77
 EA_SENTINEL = -7.0
-
-
-def _addresses(xs):
-    return ctypes.cast((ctypes.c_void_p * len(xs))(*xs), ctypes.POINTER(ctypes.c_void_p))
 
 
 def mea_call(eng, _lib, lps, labs, terms, beam, mm, device=False):

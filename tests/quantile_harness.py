@@ -2,18 +2,12 @@
 of the posterior calls and with its engine set-up: they go to the C ABI through ``eng.lib`` and never through
 kokoro_align_amd/posteriors.py.  Outputs are int32 buffers of K_i + GUARD rows of M + ``pad`` values (row pitch ld_q = M + pad)
 filled with the sentinel -77 (status 99), so a test can tell what a call wrote, and that it wrote nothing beside [K, M]."""
-import ctypes
-
 import numpy as np
 
-from fb_harness import I, P, _lattices, _one
+from fb_harness import I, P, _addresses, _lattices, _one
 
 GUARD = 2
 SENTINEL = -77
-
-
-def _addresses(xs):
-    return ctypes.cast((ctypes.c_void_p * len(xs))(*xs), ctypes.POINTER(ctypes.c_void_p))
 
 
 def quant_call(eng, _lib, lps, labs, terms, cuts, levels, beam, mm, pad=0, device=False, ld_q=None, M=None):
