@@ -260,39 +260,73 @@ constexpr int kRcLanes = 62;   // lanes 62 and 63 are kept at -inf: they are the
                                // wave_ror hands to lanes 0 and 1 (window width 124 >= 97 + slack)
 
 // The walk over one chunk's codes (4 bits per lane and frame, frame f in nibble 7 - f%8 of codes[f/8]; per nibble
-// [blank hi, blank lo, label hi, label lo], every cell coded 3 - move): pathv[lane f] = position of frame f relative to
-// the window.  One scalar chain per frame: v_readlane -> shift -> 3 & ~code -> subtract.  FULL: all 32 frames, straight
-// line (the `f < n` test of the last, partial chunk costs a compare and a taken branch per frame).
-// The walk also collects best_labels / best_scores (align.py:105-107) on the way: the label of the path's cell
-// comes out of the window's label register (lane j: 4 * label of position wlo+2j+1; a blank cell: label 0) and the score
-// out of the frame's row register (lane v = lp[t0+f, v]), both with v_readlane at a scalar lane index - two vector
-// instructions more per frame than gathering the scores afterwards with a ds_bpermute per frame, but the LDS pipe, which
-// the CU's four SIMDs share and the frame loop's emission gather needs, is left alone.
+// [blank hi, blank lo, label hi, label lo], every cell coded 3 - move), from position qq (relative to the window) at the
+// chunk's last frame down to the position the chunk below is entered at.  It touches the vector unit only for what
+// changes from frame to frame:
+//   * the lane j = qq >> 1 holds both cells the path can be on while it stays; its four code words and its label are
+//     kept in scalar registers and read again (v_readlane) only when j changes.  A frame on which the path stays is
+//     scalar shifts, one compare-and-branch, and the score;
+//   * the positions are not written per frame: a frame on which the path moves sets its bit in two masks (low and high
+//     bit of the move, bit f <-> frame f), and afterwards lane f subtracts the moves of the frames above it from the
+//     entry position - two population counts, once per chunk;
+//   * best_labels = lab'[best_path] (align.py:105-107) likewise once per chunk: lane f fetches the label of its position
+//     from the window's label register (lane j: 4 * label of position wlo+2j+1; a blank cell: label 0) with one ds_bpermute
+//     - one LDS instruction per 32 frames, next to the frame loop's 32 gathers;
+//   * best_scores[t] = lp[t, label] is the one thing every frame needs the vector unit for: v_readlane of the frame's row
+//     register (lane v = lp[t0+f, v]) at the label kept in a scalar register, and a v_writelane.
+// FULL: all 32 frames, straight line.  Otherwise frames f >= n (past T-1, last chunk only) are left out: no moves, and
+// their lanes' results are not stored.
 template <bool FULL>
 __device__ __forceinline__ void rc_walk_out(const uint32_t (&codes)[kCkFrames / 8], const float (&rows)[kCkFrames], int lab4, int n,
-                                            int &qq, int &pathv, int &labv, float &scv)
+                                            int lane, int &qq, int &pathv, int &labv, float &scv)
 {
+    constexpr int G = kCkFrames / 8;
+    static_assert(kCkFrames == 32, "one bit per frame in a 32-bit move mask");
+    const int q_in = qq;
+    int j = qq >> 1;
+    uint32_t cw[G];                                  // codes[g] at lane j
+#pragma unroll
+    for (int g = 0; g < G; ++g) cw[g] = (uint32_t)__builtin_amdgcn_readlane((int)codes[g], j);
+    int cl = __builtin_amdgcn_readlane(lab4, j);     // lab4 at lane j
+    int col = (qq & 1) ? cl >> 2 : 0;                // label of the path's cell
+    uint32_t par = (qq & 1) ? 0u : 2u;               // where the cell's code sits in its nibble
+    uint32_t mlo = 0, mhi = 0;
 #pragma unroll
     for (int f = kCkFrames - 1; f >= 0; --f) {
         if (FULL || f < n) {
-            const int j = qq >> 1;
-            const int sh = 4 * (7 - (f & 7)) + ((qq & 1) ? 0 : 2);
-            const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)codes[f >> 3], j) >> sh;
-            const int col = (qq & 1) ? __builtin_amdgcn_readlane(lab4, j) >> 2 : 0;
             const int sc = __builtin_amdgcn_readlane(__builtin_bit_cast(int, rows[f]), col);
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(pathv) : "s"(qq), "i"(f));
-            asm("v_writelane_b32 %0, %1, %2" : "+v"(labv) : "s"(col), "i"(f));
             asm("v_writelane_b32 %0, %1, %2" : "+v"(scv) : "s"(sc), "i"(f));
-            qq -= bp_decode(w);
+            const uint32_t mv = (uint32_t)bp_decode(cw[f >> 3] >> (4 * (7 - (f & 7)) + par));
+            if (mv != 0) {
+                qq -= (int)mv;
+                mlo |= (mv & 1u) << f;
+                mhi |= (mv >> 1) << f;
+                if (f > 0) {                         // (what follows serves the frames below)
+                    par = (qq & 1) ? 0u : 2u;
+                    if ((qq >> 1) != j) {
+                        j = qq >> 1;
+#pragma unroll
+                        for (int g = 0; g <= (f - 1) >> 3; ++g) cw[g] = (uint32_t)__builtin_amdgcn_readlane((int)codes[g], j);
+                        cl = __builtin_amdgcn_readlane(lab4, j);
+                    }
+                    col = (qq & 1) ? cl >> 2 : 0;
+                }
+            }
         }
     }
+    // position of frame f = entry position - moves of the frames above f (the masks' bits f+1 .. 31)
+    const uint32_t above_lo = (mlo >> 1) >> (lane & 31), above_hi = (mhi >> 1) >> (lane & 31);   // (lanes 32 .. 63 are not stored)
+    pathv = q_in - (__builtin_popcount(above_lo) + 2 * __builtin_popcount(above_hi));
+    const int l4 = __builtin_amdgcn_ds_bpermute((pathv >> 1) << 2, lab4);
+    labv = (pathv & 1) ? l4 >> 2 : 0;
 }
 
 // PAR = false: one wavefront per lattice walks its chunks from the last to the first (the position a chunk is entered
 // at comes out of the chunk above it).  PAR = true: one wavefront per CHUNK, entered at Lattice::entry[chunk], which the
 // chunk-parallel backtrace (ka_parallel_bt.hpp) has worked out for every chunk beforehand; grid = all chunks of the launch.
-// best_labels / best_scores stay in registers all the way.  (Fetching them after the walk instead, with a gather per chunk,
-// was measured and removed: the numbers are in DESIGN.md 8, the code under tools/experiments/.)
+// best_labels / best_scores stay in registers all the way: the labels come out of the window's label register after the walk,
+// the scores out of the row registers during it (rc_walk_out).  (Fetching both from memory after the walk instead, with a
+// gather per chunk, was measured and removed: the numbers are in DESIGN.md 8, the code under tools/experiments/.)
 template <int M, bool ZL, bool PAR>
 __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ lats, const int32_t *meta, int n_lats)
 {
@@ -491,13 +525,13 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
         int pathv = 0;
         int qq = p - wlo;
         // best_path, best_labels = lab'[best_path], best_scores[t] = lp[t, best_labels[t]] (align.py:105-107), lane f
-        // does frame t0+f: collected by the walk itself (rc_walk_out)
+        // does frame t0+f: the scores are collected by the walk itself, positions and labels come out of it (rc_walk_out)
         int labv = 0;
         float scv = 0.0f;
         if (n == kCkFrames)
-            rc_walk_out<true>(codes, rows, lab4, n, qq, pathv, labv, scv);
+            rc_walk_out<true>(codes, rows, lab4, n, lane, qq, pathv, labv, scv);
         else
-            rc_walk_out<false>(codes, rows, lab4, n, qq, pathv, labv, scv);
+            rc_walk_out<false>(codes, rows, lab4, n, lane, qq, pathv, labv, scv);
         if (lane < n) {
             path[t0 + lane] = pathv + wlo;
             lab_out[t0 + lane] = labv;
