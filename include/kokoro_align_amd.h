@@ -451,8 +451,66 @@ int ka_ctc_state_durations_banded_batch_f32(ka_engine *e, int32_t n, const float
                                             int32_t mem, void *stream);
 /* device-workspace bytes a banded call carves BEYOND its sibling's ka_*_workspace_bytes figure (the descriptors that carry the
  * table and, for KA_MEM_HOST, the staged tables): reserving the sum keeps the call free of allocations.  0 for unsupported
- * arguments. */
+ * arguments.  For the four calls above and, of the block below, the visits, the samples and the MEA path; the banded boundary
+ * quantiles have a figure of their own (ka_boundary_quantile_band_table_workspace_bytes). */
 size_t ka_band_table_workspace_bytes(int32_t n, const int64_t *T, int32_t mem);
+
+/*
+ * State visits, boundary quantiles, sampled paths and the MEA path over a caller-given band: the
+ * other half of the forward-backward family on the table of the block above, by the same rule.  Each call is its sibling with
+ * the table behind max_move (single call: const int32_t *band_lo, [T] int32 where `mem` says; batch call: a HOST array of n
+ * such pointers); lo_t, hi_t, what a valid table is, the device-side check, the NULL rules and everything the sibling
+ * documents - recurrences, veto, terminal, statuses, stream synchronisation, the Z bits the family shares - are as above.
+ * A lattice that fails (an invalid table: KA_ERR_BAD_ARGS for that lattice alone) gets its sibling's failure outputs: NaN over
+ * [0, 2S+1) of visit and exit_time; -1 over [K, M] of quantile; -1 over [0, T) of every sampled row; a -1 path and a NaN
+ * expected accuracy.  What the table changes in the outputs:
+ *   visits      a position that no frame's band holds, and every position below band_lo[0], has visit and exit_time 0
+ *   quantiles   F_t(c) is 2^32 from the first t with band_lo[t] >= c on, so a cut at or below band_lo[0] (not only cut 0)
+ *               reads 0 at every level, and a cut that the band's low end never reaches reads its own crossing, or T.  The
+ *               start frames are found on the device from the accepted table; nothing of the table is read on the host
+ *   samples     every draw into frame t-1 is over the band of frame t-1, band_lo[t-1]; sample k keeps its bits whatever the
+ *               batch and n_samples, as in the sibling
+ *   MEA path    path[0] is the smallest allowed j < max_move inside [band_lo[0], hi_0), so it may lie above 0; a table with
+ *               band_lo[0] >= max_move is KA_ERR_ZERO_MASS
+ * With the reference's diagonal as the table every call returns its sibling's bits: outputs, log-likelihood, status, return code.
+ * Workspace beyond the sibling's ka_*_workspace_bytes figure: ka_band_table_workspace_bytes for the visits, the samples and
+ * the MEA path; ka_boundary_quantile_band_table_workspace_bytes for the quantiles, whose descriptor is larger.
+ */
+int ka_ctc_state_visits_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                   int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal, double *visit,
+                                   double *exit_time, double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_state_visits_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                         const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                         int32_t max_move, const int32_t *const *band_lo, const int64_t *terminal, double *const *visit,
+                                         double *const *exit_time, double *log_likelihood, int32_t *status, int32_t mem, void *stream);
+int ka_ctc_boundary_quantiles_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels,
+                                         int64_t S, int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal,
+                                         const int64_t *cuts, int64_t K, const double *levels, int32_t M, int32_t *quantile, int64_t ld_q,
+                                         double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_boundary_quantiles_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                               const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                               int32_t max_move, const int32_t *const *band_lo, const int64_t *terminal,
+                                               const int64_t *const *cuts, const int64_t *K, const double *levels, int32_t M,
+                                               int32_t *const *quantile, const int64_t *ld_q, double *log_likelihood, int32_t *status,
+                                               int32_t mem, void *stream);
+int ka_ctc_sample_paths_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                   int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal, int32_t n_samples,
+                                   uint64_t seed, int32_t *paths, int64_t ld_paths, double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_sample_paths_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                         const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                         int32_t max_move, const int32_t *const *band_lo, const int64_t *terminal,
+                                         const int32_t *n_samples, const uint64_t *seed, int32_t *const *paths, const int64_t *ld_paths,
+                                         double *log_likelihood, int32_t *status, int32_t mem, void *stream);
+int ka_ctc_mea_path_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                               int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal, int32_t *path,
+                               double *expected_accuracy, double *log_likelihood, int32_t mem, void *stream);
+int ka_ctc_mea_path_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                     const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                     const int32_t *const *band_lo, const int64_t *terminal, int32_t *const *path,
+                                     double *expected_accuracy, double *log_likelihood, int32_t *status, int32_t mem, void *stream);
+/* ka_band_table_workspace_bytes for ka_ctc_boundary_quantiles_banded_*: the bytes that call carves beyond
+ * ka_boundary_quantile_workspace_bytes (its descriptors carry the cuts' arrays as well as the table).  0 for unsupported arguments. */
+size_t ka_boundary_quantile_band_table_workspace_bytes(int32_t n, const int64_t *T, int32_t mem);
 
 /* Kernel form of the fast path.
  *   KA_MODE_WAVE        one wavefront per lattice, checkpointed (throughput; fills the chip from ~4096

@@ -50,6 +50,10 @@ EXPORTS = [
     "ka_ctc_label_posteriors_banded_f32", "ka_ctc_label_posteriors_banded_batch_f32",
     "ka_ctc_state_posteriors_banded_f32", "ka_ctc_state_posteriors_banded_batch_f32",
     "ka_ctc_state_durations_banded_f32", "ka_ctc_state_durations_banded_batch_f32", "ka_band_table_workspace_bytes",
+    "ka_ctc_state_visits_banded_f32", "ka_ctc_state_visits_banded_batch_f32",
+    "ka_ctc_boundary_quantiles_banded_f32", "ka_ctc_boundary_quantiles_banded_batch_f32",
+    "ka_ctc_sample_paths_banded_f32", "ka_ctc_sample_paths_banded_batch_f32",
+    "ka_ctc_mea_path_banded_f32", "ka_ctc_mea_path_banded_batch_f32", "ka_boundary_quantile_band_table_workspace_bytes",
 ]
 
 
@@ -168,7 +172,8 @@ def load_library():
     L.ka_banded_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
     # the forward-backward calls over a caller-given band: their siblings' arguments with the table behind max_move (the
     # tenth argument of a single call, a pointer; the eleventh of a batch call, an array of pointers)
-    for call in ("path_posteriors", "label_posteriors", "state_posteriors", "state_durations"):
+    for call in ("path_posteriors", "label_posteriors", "state_posteriors", "state_durations",
+                 "state_visits", "boundary_quantiles", "sample_paths", "mea_path"):
         for form, at, kind in (("", 9, vp), ("_batch", 10, pp)):
             sibling = getattr(L, f"ka_ctc_{call}{form}_f32")
             banded = getattr(L, f"ka_ctc_{call}_banded{form}_f32")
@@ -176,6 +181,8 @@ def load_library():
             banded.argtypes = sibling.argtypes[:at] + [kind] + sibling.argtypes[at:]
     L.ka_band_table_workspace_bytes.restype = sz
     L.ka_band_table_workspace_bytes.argtypes = [i32, pi64, i32]
+    L.ka_boundary_quantile_band_table_workspace_bytes.restype = sz
+    L.ka_boundary_quantile_band_table_workspace_bytes.argtypes = [i32, pi64, i32]
     L.ka_engine_set_mode.restype = ctypes.c_int
     L.ka_engine_set_mode.argtypes = [vp, i32]
     L.ka_engine_set_backtrace.restype = ctypes.c_int

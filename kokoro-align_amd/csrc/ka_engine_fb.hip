@@ -23,7 +23,7 @@ using ka::plan::align_up;
 // engine's mode.  One driver, fb_impl; a call (PostCall, OccCall, StateCall, QuantCall, SampleCall, MeaCall, and PairCall as
 // DurCall and VisitCall) brings what differs: its own arrays and their checks, its planner and its launch (launch<Band>, one
 // for either band), the descriptor fields beyond FbLattice, its own staging (upload: host buffers only; stage: every memory
-// mode), and what two statuses mean.
+// mode), what two statuses mean, and kBandedGranule, the bytes a lattice's Banded<Desc> descriptor is carved as.
 struct FbArgs {
     int32_t n;
     const float *const *log_probs;
@@ -42,6 +42,7 @@ struct FbArgs {
 
 struct PostCall {
     using Desc = ka::PostLattice;
+    static constexpr size_t kBandedGranule = ka::kBandedDescBytes;
     using Carve = ka::plan::PostCarve;
     static constexpr const char *kName = "posteriors";
     static constexpr const char *kBadArgs = ": a best-path position outside [0, 2S+1)";
@@ -94,6 +95,7 @@ void fill_slot(ka::FbCkLattice &d, const ka::plan::SlotCarve &c, int64_t termina
 
 struct OccCall {
     using Desc = ka::OccLattice;
+    static constexpr size_t kBandedGranule = ka::kBandedDescBytes;
     using Carve = ka::plan::OccCarve;
     static constexpr const char *kName = "label posteriors";
     static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
@@ -132,6 +134,7 @@ struct OccCall {
 
 struct StateCall {
     using Desc = ka::StateLattice;
+    static constexpr size_t kBandedGranule = ka::kBandedDescBytes;
     using Carve = ka::plan::StateCarve;
     static constexpr const char *kName = "state posteriors";
     static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
@@ -216,6 +219,7 @@ struct VisitKind {
 template <class Kind>
 struct PairCall {
     using Desc = typename Kind::Desc;
+    static constexpr size_t kBandedGranule = ka::kBandedDescBytes;
     using Carve = ka::plan::PairCarve;
     static constexpr const char *kName = Kind::kName;
     static constexpr const char *kBadArgs = Kind::kBadArgs;
@@ -257,6 +261,7 @@ using VisitCall = PairCall<VisitKind>;
 
 struct QuantCall {
     using Desc = ka::QuantLattice;
+    static constexpr size_t kBandedGranule = ka::kBandedQuantDescBytes;   // (ka_boundary_quantile_band_table_workspace_bytes)
     using Carve = ka::plan::QuantCarve;
     static constexpr const char *kName = "boundary quantiles";
     static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
@@ -268,7 +273,7 @@ struct QuantCall {
     const int64_t *ld_q;
     int32_t M;
     unsigned long long thr[ka::kMaxLevels];   // the levels as thresholds (quant_thresholds)
-    mutable std::vector<std::vector<char>> staged;   // per lattice: its cuts and, behind them, their start frames, until the call's end
+    mutable std::vector<std::vector<char>> staged;   // per lattice: its cuts and, behind them (the diagonal only), their start frames, until the call's end
 
     bool arrays() const { return terminal && cuts && K && quantile && ld_q; }
     const char *bad_lattice(const FbArgs &a, int32_t i) const
@@ -316,10 +321,11 @@ struct QuantCall {
         const size_t k = (size_t)K[i];
         if (k == 0) return KA_OK;
         std::vector<char> &buf = staged[(size_t)i];
-        buf.resize(k * 12);
+        const bool table = a.band_lo != nullptr;   // a table's start frames are the kernel's to find (QuantOut::begin): cuts only
+        buf.resize(table ? k * 8 : k * 12);
         std::memcpy(buf.data(), cuts[i], k * 8);
         int32_t *start = reinterpret_cast<int32_t *>(buf.data() + k * 8);
-        for (size_t j = 0; j < k; ++j)
+        for (size_t j = 0; j < k && !table; ++j)
             start[j] = (int32_t)ka::plan::quantile_start_frame(cuts[i][j], a.T[i], 2 * a.S[i] + 1, a.beam_size);
         KA_HIP(hipMemcpyAsync(ws + c.cuts, buf.data(), buf.size(), hipMemcpyHostToDevice, a.stream));
         return KA_OK;
@@ -355,6 +361,7 @@ const char *quant_thresholds(const double *levels, int32_t M, unsigned long long
 
 struct SampleCall {
     using Desc = ka::SampleLattice;
+    static constexpr size_t kBandedGranule = ka::kBandedDescBytes;
     using Carve = ka::plan::SampleCarve;
     static constexpr const char *kName = "sample paths";
     static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
@@ -378,7 +385,7 @@ struct SampleCall {
         return ka::plan::sample_paths_workspace(n, T, S, n_samples, V, beam, max_move, host, cv, off_res);
     }
     template <class Band>
-    static constexpr auto launch = ka::launch_sample_paths;   // (the diagonal only)
+    static constexpr auto launch = ka::launch_sample_paths<Band>;
     void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         if (a.mem == KA_MEM_HOST) {
@@ -404,6 +411,7 @@ struct SampleCall {
 
 struct MeaCall {
     using Desc = ka::MeaLattice;
+    static constexpr size_t kBandedGranule = ka::kBandedDescBytes;
     using Carve = ka::plan::MeaCarve;
     static constexpr const char *kName = "mea path";
     static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1)";
@@ -457,7 +465,7 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
 {
     constexpr bool kBanded = std::is_same_v<Band, ka::BandTable>;
     using Desc = ka::BandDesc<typename Call::Desc, Band>;
-    static_assert(sizeof(Desc) <= ka::kBandedDescBytes || !kBanded, "descriptor sizes");
+    static_assert(sizeof(Desc) <= Call::kBandedGranule || !kBanded, "descriptor sizes");
     const int32_t n = a.n, V = a.V;
     const hipStream_t stream = a.stream;
     const bool host = a.mem == KA_MEM_HOST;
@@ -476,7 +484,7 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
     if (kBanded) {
         off_desc = total = align_up(total);
         off_tab.resize((size_t)n);
-        total += ka::plan::band_table_workspace(n, a.T, host, off_tab.data());
+        total += ka::plan::band_table_workspace(n, a.T, host, off_tab.data(), Call::kBandedGranule);
     }
     for (int32_t i = 0; i < n; ++i) {
         if (a.ld[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld < V");
@@ -889,6 +897,12 @@ size_t ka_band_table_workspace_bytes(int32_t n, const int64_t *T, int32_t mem)
     return ka::plan::band_table_workspace(n, T, mem == KA_MEM_HOST, nullptr);
 }
 
+size_t ka_boundary_quantile_band_table_workspace_bytes(int32_t n, const int64_t *T, int32_t mem)
+{
+    if (n < 0 || (n > 0 && !T) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::band_table_workspace(n, T, mem == KA_MEM_HOST, nullptr, ka::kBandedQuantDescBytes);
+}
+
 int ka_ctc_state_visits_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
                                   const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
                                   const int64_t *terminal, double *const *visit, double *const *exit_time, double *log_likelihood,
@@ -986,6 +1000,79 @@ size_t ka_mea_path_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S
 {
     if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
     return ka::plan::mea_path_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+// ---- and the other four over a caller-given band ----
+int ka_ctc_state_visits_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                         const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                         const int32_t *const *band_lo, const int64_t *terminal, double *const *visit,
+                                         double *const *exit_time, double *log_likelihood, int32_t *status, int32_t mem, void *stream)
+{
+    if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "state visits: NULL band_lo");
+    return fb_impl<VisitCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo}, VisitCall{terminal, visit, exit_time});
+}
+
+int ka_ctc_state_visits_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                   int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal, double *visit,
+                                   double *exit_time, double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl<VisitCall, ka::BandTable>(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo}, VisitCall{&terminal, &visit, &exit_time});
+}
+
+int ka_ctc_boundary_quantiles_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                               const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                               int32_t max_move, const int32_t *const *band_lo, const int64_t *terminal,
+                                               const int64_t *const *cuts, const int64_t *K, const double *levels, int32_t M,
+                                               int32_t *const *quantile, const int64_t *ld_q, double *log_likelihood, int32_t *status,
+                                               int32_t mem, void *stream)
+{
+    QuantCall call{terminal, cuts, K, quantile, ld_q, M, {}, {}};
+    if (const char *why = quant_thresholds(levels, M, call.thr)) return fail(KA_ERR_BAD_ARGS, why);
+    if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "boundary quantiles: NULL band_lo");
+    return fb_impl<QuantCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo}, call);
+}
+
+int ka_ctc_boundary_quantiles_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels,
+                                         int64_t S, int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal,
+                                         const int64_t *cuts, int64_t K, const double *levels, int32_t M, int32_t *quantile, int64_t ld_q,
+                                         double *log_likelihood, int32_t mem, void *stream)
+{
+    QuantCall call{&terminal, &cuts, &K, &quantile, &ld_q, M, {}, {}};
+    if (const char *why = quant_thresholds(levels, M, call.thr)) return fail(KA_ERR_BAD_ARGS, why);
+    return fb_impl<QuantCall, ka::BandTable>(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo}, call);
+}
+
+int ka_ctc_sample_paths_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                         const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                         const int32_t *const *band_lo, const int64_t *terminal, const int32_t *n_samples,
+                                         const uint64_t *seed, int32_t *const *paths, const int64_t *ld_paths, double *log_likelihood,
+                                         int32_t *status, int32_t mem, void *stream)
+{
+    if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "sample paths: NULL band_lo");
+    return fb_impl<SampleCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo}, SampleCall{terminal, n_samples, seed, paths, ld_paths});
+}
+
+int ka_ctc_sample_paths_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                   int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal, int32_t n_samples,
+                                   uint64_t seed, int32_t *paths, int64_t ld_paths, double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl<SampleCall, ka::BandTable>(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo}, SampleCall{&terminal, &n_samples, &seed, &paths, &ld_paths});
+}
+
+int ka_ctc_mea_path_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                     const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                     const int32_t *const *band_lo, const int64_t *terminal, int32_t *const *path,
+                                     double *expected_accuracy, double *log_likelihood, int32_t *status, int32_t mem, void *stream)
+{
+    if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "mea path: NULL band_lo");
+    return fb_impl<MeaCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo}, MeaCall{terminal, path, expected_accuracy});
+}
+
+int ka_ctc_mea_path_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                               int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal, int32_t *path,
+                               double *expected_accuracy, double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl<MeaCall, ka::BandTable>(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo}, MeaCall{&terminal, &path, expected_accuracy});
 }
 
 }  // extern "C"

@@ -24,6 +24,8 @@
 // is built per lattice as Out(descriptor, form, lds), holds the call's outputs and has a hook for each place where the calls
 // differ:
 //   fail(res, status)            a lattice without a result: fill the outputs with NaN, then fb_fail_result
+//   begin()                      opt-in, once a lattice behind the forward pass (the band is accepted, Z is known) and before the
+//                                first block: for what an Out may place only by an accepted band's values
 //   recompute(t0)                recompute the block that starts at t0?  (if not, the walk is re-seated at t1, where the
 //                                recompute would have left it; beta is still stepped through every frame)
 //   cells(t, lo)                 frame t's action on a cell's gamma: a callable (p, lab, arg), arg() the log2 argument, formed
@@ -55,6 +57,12 @@ template <class Out, class = void>
 struct fb_next_column : std::false_type {};
 template <class Out>
 struct fb_next_column<Out, std::void_t<decltype(Out::kNextColumn)>> : std::true_type {};
+
+// does an Out opt into begin() (above)?
+template <class Out, class = void>
+struct fb_begin : std::false_type {};
+template <class Out>
+struct fb_begin<Out, std::void_t<decltype(&Out::begin)>> : std::true_type {};
 
 // one cell's gamma as a float from its log2 argument (occ_fix of ka_occupancy.hpp before the fixed-point step): what the state
 // posteriors write and the state durations add
@@ -187,6 +195,7 @@ __device__ __forceinline__ void fb_ck(Form &f, PostResult *res, double *cav, Out
         return;
     }
     const int64_t sstar = d.terminal;
+    if constexpr (fb_begin<Out>::value) out.begin();
 
     // ---- backward, a block at a time ----
     double *gn = f.col(0), *vn = f.col(1), *gc = f.col(2), *vc = f.col(3);   // G_{t+1} and its vetoable copy; scratch

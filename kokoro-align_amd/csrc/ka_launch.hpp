@@ -104,19 +104,20 @@ void launch_state_posteriors(const BandDesc<StateLattice, Band> *lats, int n_fas
 // ka_duration.hip, ka_duration_banded.hip: expected state durations (ka_duration.hpp)
 template <class Band>
 void launch_state_durations(const BandDesc<DurLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
-// ka_visit.hip: state visit probabilities (ka_visit.hpp)
+// ka_visit.hip, ka_visit_banded.hip: state visit probabilities (ka_visit.hpp)
 template <class Band>
 void launch_state_visits(const BandDesc<VisitLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
-// ka_quantile.hip: exact boundary-time quantiles (ka_quantile.hpp)
+// ka_quantile.hip, ka_quantile_banded.hip: exact boundary-time quantiles (ka_quantile.hpp)
 template <class Band>
 void launch_boundary_quantiles(const BandDesc<QuantLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
-// ka_mea.hip: the maximum-expected-accuracy alignment (ka_mea.hpp)
+// ka_mea.hip, ka_mea_banded.hip: the maximum-expected-accuracy alignment (ka_mea.hpp)
 template <class Band>
 void launch_mea_path(const BandDesc<MeaLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 
-// ---- ka_sample.hip: alignments sampled from the band posterior (ka_sample.hpp): ka_fb_ck.hpp's forward pass and block
-// recompute, launch_fb_ck's form split, grid and slots; on the diagonal only ----
-void launch_sample_paths(const SampleLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+// ka_sample.hip, ka_sample_banded.hip: alignments sampled from the band posterior (ka_sample.hpp): ka_fb_ck.hpp's forward pass
+// and block recompute with kernels of its own, launch_fb_ck's form split, grid and slots
+template <class Band>
+void launch_sample_paths(const BandDesc<SampleLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 
 // ---- ka_banded.hip: best path over a caller-given band (ka_banded.hpp).  Descriptors [0, n_fast): one wavefront per lattice
 // (band <= kFastMaxBand, V <= 64, max_move <= 4), then [n_fast, n_fast + n_generic): one 256-thread workgroup per lattice.

@@ -1,6 +1,6 @@
 // ka_mea.hpp — the maximum-expected-accuracy alignment (posterior-decoded path): the one path s_0 ... s_{T-1} of the band that
 // ends at a caller-given terminal s* and maximises sum over t of gamma_t(s_t), that sum (the expected number of correctly
-// placed frames), and Z = alpha_{T-1}(s*).  Included by ka_mea.hip only.
+// placed frames), and Z = alpha_{T-1}(s*).  Included by ka_mea.hip and ka_mea_banded.hip only.
 //
 // Same lattice, band, moves, veto, statuses and form split as ka_occupancy.hpp (DESIGN.md sections 4.18 and 4.26): the
 // driver of ka_fb_ck.hpp with MeaOut, which recomputes every block as the occupancy does and runs a Viterbi recursion over
@@ -10,7 +10,7 @@
 //   c_t(p)     = the smallest j that attains the maximum (0 where every successor is -inf: such a cell is never walked)
 // in float64, one add per cell: the maximum is exact, so W has no order dependence and equals a sequential float64 loop over
 // the rows of ka_ctc_state_posteriors, bit for bit.  After frame 0 the path is walked forward from the virtual state 0:
-//   s_0 = the smallest j < max_move in band 0, not fb_vetoed(j, lab'[j]), that maximises W_0(j);  s_{t+1} = s_t + c_t(s_t)
+//   s_0 = the smallest j < max_move in band 0 (which a table may start above 0), not fb_vetoed(j, lab'[j]), that maximises W_0(j);  s_{t+1} = s_t + c_t(s_t)
 //   expected_accuracy = W_0(s_0)
 //
 // W columns.  Fast form: two LDS rings (position p at the form's column slot, p & 1023), W_{t+1} and W_t, swapped per frame.
@@ -70,8 +70,11 @@ struct MeaOut {
     int32_t *tile;        // kPostCk positions of the path (LDS)
     int64_t nlo, nhi;     // the band of frame t + 1
     uint32_t word;        // fast form: the codes of this lane's cells of the frame
-    __device__ __forceinline__ MeaOut(const MeaLattice &d_, Form &f_, Lds &lds)
-        : d(d_), f(f_), wn(Form::kWave ? lds.ring(0) : d_.wcol), wc(Form::kWave ? lds.ring(1) : d_.wcol + d_.L), tile(lds.tile), nlo(0), nhi(0), word(0)
+    const int32_t *tab;   // the caller's table (BandTable), which the forward walk steps as the passes did
+    template <class D>
+    __device__ __forceinline__ MeaOut(const D &d_, Form &f_, Lds &lds)
+        : d(d_), f(f_), wn(Form::kWave ? lds.ring(0) : d_.wcol), wc(Form::kWave ? lds.ring(1) : d_.wcol + d_.L), tile(lds.tile), nlo(0), nhi(0), word(0),
+          tab(fb_table(d_))
     {
     }
     // a lattice without a result: -1 over [0, T) of the path, NaN as the expected accuracy, and the status and
@@ -147,9 +150,12 @@ struct MeaOut {
     {
         const int tid = threadIdx.x;
         const int64_t T = d.T;
-        static_assert(!Band::kTable, "the walk below steps the diagonal: over a table it needs the table");
         f.sync();   // frame 0's W (and, generic form, every frame's codes), stored by the threads that own the cells, before the thread that walks
-        BandWalk bw(d.L, d.beam, T);
+        // the band every frame's codes were stored under: a code lies at p - lo_t, so the walk takes lo_t from the driver's own
+        // Band.  A table was accepted by the forward pass (start(), a whole-workgroup step): here it is only seated, by every
+        // thread alike, and thread 0 alone steps it.
+        Band bw(d.L, d.beam, T, tab);
+        if constexpr (Band::kTable) bw.seek(0);
         int32_t s = 0;
         if (tid == 0) {
             int64_t lo, hi;

@@ -991,12 +991,13 @@ namespace ka {
 namespace plan {
 
 // ---- the forward-backward calls over a caller-given band (ka_ctc_*_banded_*): what they carve beyond their sibling's
-// workspace, placed behind it: the derived descriptors (Banded<Desc>, kBandedDescBytes each whatever the call; the sibling's
-// descriptor region stays unused) and, for host buffers, every lattice's staged table (T int32).  tab[i]: the offset of lattice
-// i's staged table from the start of this region.  0 for a T below 1.
-inline size_t band_table_workspace(int32_t n, const int64_t *T, bool host_buffers, size_t *tab)
+// workspace, placed behind it: the derived descriptors (Banded<Desc>, desc_bytes each: the call's granule, kBandedDescBytes for
+// every call but the boundary quantiles, whose descriptor is kBandedQuantDescBytes; the sibling's descriptor region stays
+// unused) and, for host buffers, every lattice's staged table (T int32).  tab[i]: the offset of lattice i's staged table from
+// the start of this region.  0 for a T below 1.
+inline size_t band_table_workspace(int32_t n, const int64_t *T, bool host_buffers, size_t *tab, size_t desc_bytes = kBandedDescBytes)
 {
-    size_t off = align_up((size_t)n * kBandedDescBytes);
+    size_t off = align_up((size_t)n * desc_bytes);
     for (int32_t i = 0; i < n; ++i) {
         if (T[i] < 1 || T[i] > INT32_MAX) return 0;
         if (tab) tab[i] = off;

@@ -1,6 +1,6 @@
 // ka_quantile.hpp — exact boundary-time quantiles: for every cut position c_k of the blank-expanded labels and every level
 // q_m the first frame at which the posterior mass at or above the cut reaches the level, over the band's paths that end at a
-// caller-given terminal s*, and Z = alpha_{T-1}(s*).  Included by ka_quantile.hip only.
+// caller-given terminal s*, and Z = alpha_{T-1}(s*).  Included by ka_quantile.hip and ka_quantile_banded.hip only.
 //   tau_c = the first frame whose state is >= c; paths only move up, so P(tau_c <= t) = P(state_t >= c) = sum_{s >= c} gamma_t(s)
 //   F_t(c) = 2^32 where c <= lo_t, 0 where c >= hi_t, else the sum over p in [c, hi_t) of occ_fix of the cell: an unsigned
 //            32.32 fixed-point integer, so it does not depend on the order of the adds and is defined bit for bit by the rows
@@ -23,6 +23,9 @@
 // The sweep runs T-1 ... 0, so the last store to a word is the minimum over the frames whose band holds the cut.  The frames
 // whose band lies at or above the cut (F = 2^32) are those from the first t with lo_t >= c_k on: the planner's closed form,
 // uploaded beside the cuts (start), is the value a cut's words hold before the sweep - T where there is no such frame.
+// Under a caller's table (BandTable) there is no closed form and the table may lie in device memory: the same value, the first
+// t with tab[t] >= c_k or T, is a lower-bound search of the non-decreasing table by the cut's owner thread, in begin() - behind
+// the forward pass, whose start() accepted the table, and before the sweep's first store.  A cut at or below lo_0 so starts at 0.
 // Ownership: cut k belongs to thread k mod NT in every frame (the run's low end is rounded down to a multiple of NT), and that
 // thread also writes the start value and, for a failed lattice, the -1: all stores to one output word come from one thread in
 // program order, and no ring of candidates or retire step is needed.
@@ -65,12 +68,31 @@ struct QuantOut {
     unsigned long long thr[kMaxLevels];   // the thresholds; those past M can never be reached
     int64_t ka, kb;             // the cuts inside the band of the frame last seen: indices [ka, kb)
     bool dna, dnb;              // this lane's look below ka and kb for the frame in flight (asked for before the frame's cells)
-    __device__ __forceinline__ QuantOut(const QuantLattice &d_, Form &, Lds &lds)
-        : d(d_), row(Form::kWave ? lds.w : d_.frow), part(lds.w), ka(d_.K), kb(d_.K), dna(false), dnb(false)
+    const int32_t *tab;         // the caller's table (BandTable): where begin() finds the cuts' start frames
+    template <class D>
+    __device__ __forceinline__ QuantOut(const D &d_, Form &, Lds &lds)
+        : d(d_), row(Form::kWave ? lds.w : d_.frow), part(lds.w), ka(d_.K), kb(d_.K), dna(false), dnb(false), tab(fb_table(d_))
     {
 #pragma unroll
         for (int m = 0; m < kMaxLevels; ++m) thr[m] = m < d.M ? d.thr[m] : ~0ull;
-        for (int64_t k = threadIdx.x; k < d.K; k += NT) fill(k, d.start[k]);
+        if constexpr (!Band::kTable)
+            for (int64_t k = threadIdx.x; k < d.K; k += NT) fill(k, d.start[k]);
+    }
+    // fb_ck's opt-in hook behind the forward pass: under a table, every cut's start frame from the accepted table - the first t
+    // with tab[t] >= c_k, T if there is none - stored by the cut's owner.  (The diagonal's came from the host, in the constructor.)
+    __device__ __forceinline__ void begin() const
+    {
+        if constexpr (Band::kTable)
+            for (int64_t k = threadIdx.x; k < d.K; k += NT) {
+                const int64_t c = d.cuts[k];
+                int32_t a = 0, b = d.T;   // tab[t] < c below a, tab[t] >= c from b on
+                while (a < b) {
+                    const int32_t mid = a + ((b - a) >> 1);
+                    if ((int64_t)tab[mid] >= c) b = mid;
+                    else a = mid + 1;
+                }
+                fill(k, a);
+            }
     }
     __device__ __forceinline__ void fill(int64_t k, int32_t v) const
     {

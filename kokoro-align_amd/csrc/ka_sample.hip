@@ -5,10 +5,6 @@
 
 namespace ka {
 
-void launch_sample_paths(const SampleLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
-{
-    launch_fb_slots<SampleLattice>({sample_kernel<FbFast<1>>, sample_kernel<FbFast<2>>, sample_kernel<FbFast<3>>, sample_kernel<FbFast<4>>},
-                                   sample_kernel<FbGen<>>, lats, n_fast, n_generic, max_move, res, s);
-}
+template void launch_sample_paths<BandWalk>(const SampleLattice *, int, int, int, PostResult *, hipStream_t);
 
 }  // namespace ka

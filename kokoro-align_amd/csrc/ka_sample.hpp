@@ -1,6 +1,6 @@
 // ka_sample.hpp — alignments sampled from the band posterior (forward filter, backward sample): n_samples <= 64 whole paths
 // s_0 ... s_{T-1} per lattice, drawn from the posterior over the band's paths that end at a caller-given terminal s*, and
-// Z = alpha_{T-1}(s*).  Included by ka_sample.hip only.
+// Z = alpha_{T-1}(s*).  Included by ka_sample.hip and ka_sample_banded.hip only.
 //
 // Same lattice, band, moves, veto, statuses, Z and form split as ka_occupancy.hpp (DESIGN.md sections 4.18 and 4.24).  The
 // forward pass with its checkpoints and the recompute of a block's alpha into the slab are those of ka_fb_ck.hpp
@@ -132,13 +132,15 @@ __device__ __forceinline__ void sample_flush(const SampleLattice &d, int64_t t0,
 }
 
 // The block walk, once over the form: thread k < n_samples owns sample k (a lane of the one wavefront, or one of the first 64
-// threads of the workgroup).  The form's working columns 0 and 1 serve the forward pass and every recompute.
-template <class Form>
-__device__ __forceinline__ void sample_walk(Form &f, const SampleLattice &d, PostResult *res, int32_t (*tile)[kSampleTilePitch])
+// threads of the workgroup).  The form's working columns 0 and 1 serve the forward pass and every recompute.  Band: the band
+// of the forward pass, every recompute and every draw (BandWalk, or BandTable on `tab`, the caller's table).
+template <class Form, class Band>
+__device__ __forceinline__ void sample_walk(Form &f, const SampleLattice &d, PostResult *res, int32_t (*tile)[kSampleTilePitch],
+                                            const int32_t *tab)
 {
     const int tid = threadIdx.x;
     const int64_t T = d.T;
-    BandWalk bw(d.L, d.beam, T);
+    Band bw(d.L, d.beam, T, tab);
     double Z, Zr;
     const int status = fb_ck_forward(f, bw, Z, Zr);   // (ends behind f.sync())
     if (status != kStatusOk) {
@@ -159,7 +161,8 @@ __device__ __forceinline__ void sample_walk(Form &f, const SampleLattice &d, Pos
             if (t == 0) break;
             bw.prev();
             int64_t plo, phi;
-            bw.band(plo, phi);   // the band of t - 1, which the slab row and the checkpoint column are both laid out by
+            bw.band(plo, phi);   // the band of t - 1, which the slab row and the checkpoint column are both laid out by: the
+                                 // walk's own frame t - 1 (a table's entry t - 1, also across a block's edge), never one formed from t
             bw.next();
             const double *al = t > t0 ? d.slab + (t - 1 - t0) * f.cw() : ckc;
             if (mine) {
@@ -179,16 +182,26 @@ __device__ __forceinline__ void sample_walk(Form &f, const SampleLattice &d, Pos
     }
 }
 
-template <class Form>
-__global__ __launch_bounds__(Form::NT) void sample_kernel(const SampleLattice *__restrict__ lats, int n, PostResult *res)
+template <class Form, class Band>
+__global__ __launch_bounds__(Form::NT) void sample_kernel(const BandDesc<SampleLattice, Band> *__restrict__ lats, int n, PostResult *res)
 {
     __shared__ typename Form::template Shared<2> sh;
     __shared__ int32_t tile[kMaxSamples][kSampleTilePitch];
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
         Form f(lats[i], sh);
-        sample_walk(f, lats[i], res, tile);
+        sample_walk<Form, Band>(f, lats[i], res, tile, fb_table(lats[i]));
         f.sync();
     }
+}
+
+// launch_fb_ck's form split, grid and slots over the sampler's five kernels of a band
+template <class Band>
+void launch_sample_paths(const BandDesc<SampleLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s)
+{
+    using Desc = BandDesc<SampleLattice, Band>;
+    launch_fb_slots<Desc>({sample_kernel<FbFast<1>, Band>, sample_kernel<FbFast<2>, Band>, sample_kernel<FbFast<3>, Band>,
+                           sample_kernel<FbFast<4>, Band>},
+                          sample_kernel<FbGen<>, Band>, lats, n_fast, n_generic, max_move, res, s);
 }
 
 }  // namespace ka

@@ -255,9 +255,11 @@ struct BandWalk;
 struct BandTable;
 template <class Desc, class Band>
 using BandDesc = std::conditional_t<std::is_same_v<Band, BandTable>, Banded<Desc>, Desc>;
-constexpr size_t kBandedDescBytes = 144;   // the largest of them: what ka_band_table_workspace_bytes reserves per lattice
+constexpr size_t kBandedDescBytes = 144;   // the largest of them but the quantiles': what ka_band_table_workspace_bytes reserves per lattice
+constexpr size_t kBandedQuantDescBytes = 160;   // ... and ka_boundary_quantile_band_table_workspace_bytes, for Banded<QuantLattice>
 static_assert(sizeof(Banded<PostLattice>) == 96 && sizeof(Banded<OccLattice>) == 128 && sizeof(Banded<StateLattice>) == kBandedDescBytes &&
-                  sizeof(Banded<DurLattice>) == 128,
+                  sizeof(Banded<DurLattice>) == 128 && sizeof(Banded<VisitLattice>) == 128 && sizeof(Banded<SampleLattice>) == 136 &&
+                  sizeof(Banded<MeaLattice>) == kBandedDescBytes && sizeof(Banded<QuantLattice>) == kBandedQuantDescBytes,
               "descriptor sizes");
 
 // ---- best path over a caller-given band (ka_banded.hpp) ----

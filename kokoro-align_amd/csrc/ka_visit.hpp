@@ -1,6 +1,6 @@
 // ka_visit.hpp — state visit probabilities: for every position s of the blank-expanded labels the probability that the path
 // passes through s at all and the first time moment of the frame at which it leaves s, over the band's paths that end at a
-// caller-given terminal s*, and Z = alpha_{T-1}(s*).  Included by ka_visit.hip only.
+// caller-given terminal s*, and Z = alpha_{T-1}(s*).  Included by ka_visit.hip and ka_visit_banded.hip only.
 //   exit_t(s) = P(state_t = s and (t = T-1 or state_{t+1} != s)) = gamma_t(s) r_t(s)
 //   V(s) = sum over t of exit_t(s)        paths only move up, so a position is left once or never: V(s) in [0, 1]
 //   X(s) = sum over t of t exit_t(s)      (X / V: the expected last frame of s, given that it is visited)
@@ -45,7 +45,8 @@ struct VisitOut : PairAcc<Form, Band> {
     }
     __device__ __forceinline__ auto cells(int64_t t, int64_t lo)
     {
-        const int64_t blo = this->nlo, bhi = this->nhi;   // band t + 1, which the cells' terms lie in
+        const int64_t blo = this->nlo, bhi = this->nhi;   // band t + 1, which the cells' terms lie in: what the driver's walk handed
+                                                          // retire() a frame ago, so a stepping table's own value of t + 1
         this->retire(lo);
         const auto add = this->adder(t);
         const double np = nprev, NINF = post_dninf();

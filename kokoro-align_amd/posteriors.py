@@ -615,7 +615,7 @@ def segment_boundary_shift(duration, best_path, seg_ends, n_phonemes):
 # ------------------------------------------------------------------------------------------
 # state visit probabilities: which phonemes the path passes through at all
 # ------------------------------------------------------------------------------------------
-def ctc_state_visits(log_probs, labels, terminal, beam_size=1000, max_move=4):
+def ctc_state_visits(log_probs, labels, terminal, beam_size=1000, max_move=4, band_lo=None):
     """Which states the audio really holds: (visit float64 [L], exit_time float64 [L], log_likelihood float), L = 2S+1
     positions of the blank-expanded labels (odd position 2i+1: phoneme i, even positions: the blanks around them).
 
@@ -624,30 +624,33 @@ def ctc_state_visits(log_probs, labels, terminal, beam_size=1000, max_move=4):
     time moment (exit_time / visit: the state's expected last frame, given that it is visited), over every path of the band of ``ctc_best_path`` that ends at state ``terminal`` (an int, or a best path whose last value is
     used).  With ``max_move`` > 2 a path may jump over a phoneme; a phoneme the reader did not say shows as a low visit[2i+1].
     visit <= duration of ``ctc_state_durations`` position by position, and visit[terminal] is 1.  NumPy in -> NumPy out;
-    ROCm torch tensors go to ``ctc_state_visits_device``.  Raises as ``ctc_label_posteriors``.
+    ROCm torch tensors go to ``ctc_state_visits_device``.  Raises as ``ctc_label_posteriors``.  ``band_lo``: the band as a
+    table [T], as ``ctc_path_posteriors`` takes it; a position no band holds, or below band_lo[0], has visit 0.
     """
     call = ctc_state_visits_device if _is_tensor(log_probs) else ctc_state_visits_batch
-    (result,) = call([log_probs], [labels], [terminal], beam_size, max_move)
+    (result,) = call([log_probs], [labels], [terminal], beam_size, max_move, band_lo=_one_table(band_lo))
     return result
 
 
-def ctc_state_visits_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False):
+def ctc_state_visits_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False,
+                           band_lo=None):
     """State visit probabilities of many lattices in ONE launch; host NumPy buffers in and out.
 
     Returns a list of (visit [L_i], exit_time [L_i], log_likelihood); with ``return_status`` also the per-lattice status
     list, in which case failures do not raise (their arrays are NaN, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    ``band_lo``: a list of tables, one per lattice (``ctc_path_posteriors``).
     """
     lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
-    return _state_pairs("state_visits", ("visit", "exit_time"), lat, terminals, beam_size, max_move, None, return_status)
+    return _state_pairs("state_visits", ("visit", "exit_time"), lat, terminals, beam_size, max_move, None, return_status, band_lo)
 
 
-def ctc_state_visits_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False):
+def ctc_state_visits_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False, band_lo=None):
     """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]) and terminals (ints
     or best paths), list of (visit, exit_time: float64 tensors [2 S_i + 1] on the device, log_likelihood float) out.
     ``out``: optional list of (visit, exit_time) pairs of contiguous float64 tensors to write into.  One launch on torch's
-    current stream."""
+    current stream.  ``band_lo``: a list of tables, one per lattice, tensors on the device or host arrays."""
     lat = _device_lattices(log_probs, labels, terminals, "terminals")
-    return _state_pairs("state_visits", ("visit", "exit_time"), lat, terminals, beam_size, max_move, out, return_status)
+    return _state_pairs("state_visits", ("visit", "exit_time"), lat, terminals, beam_size, max_move, out, return_status, band_lo)
 
 
 def phoneme_visits(visit):
@@ -731,7 +734,7 @@ def _cuts_of(cuts, S):
     return c
 
 
-def ctc_boundary_quantiles(log_probs, labels, terminal, cuts, q=(0.05, 0.5, 0.95), beam_size=1000, max_move=4):
+def ctc_boundary_quantiles(log_probs, labels, terminal, cuts, q=(0.05, 0.5, 0.95), beam_size=1000, max_move=4, band_lo=None):
     """The interval every boundary lies in: (quantile int32 [K, M], log_likelihood float) for K cut positions and M levels.
 
     tau_c is the first frame whose state is >= c (``expected_crossing_frames``), over every path of the band of
@@ -743,13 +746,14 @@ def ctc_boundary_quantiles(log_probs, labels, terminal, cuts, q=(0.05, 0.5, 0.95
     [T, W] or [64, T] matrix exists.  ``cuts``: strictly increasing in [0, 2S+1] (``boundary_cuts``); ``q``: 1 to 8 levels,
     strictly increasing in [2^-10, 1 - 2^-10].  Rows and columns ascend.  NumPy in -> NumPy out; ROCm torch tensors go to
     ``ctc_boundary_quantiles_device``.  Raises as ``ctc_label_posteriors``, and ValueError for bad cuts or levels.
+    ``band_lo``: the band as a table [T], as ``ctc_path_posteriors`` takes it; a cut at or below band_lo[0] then reads 0.
     """
     call = ctc_boundary_quantiles_device if _is_tensor(log_probs) else ctc_boundary_quantiles_batch
-    (result,) = call([log_probs], [labels], [terminal], [cuts], q, beam_size, max_move)
+    (result,) = call([log_probs], [labels], [terminal], [cuts], q, beam_size, max_move, band_lo=_one_table(band_lo))
     return result
 
 
-def _boundary_quantiles(lat, terminals, cuts, q, beam_size, max_move, out, return_status):
+def _boundary_quantiles(lat, terminals, cuts, q, beam_size, max_move, out, return_status, band_lo=None):
     levels = _levels_of(q)
     if lat is None:
         return ([], []) if return_status else []
@@ -764,29 +768,31 @@ def _boundary_quantiles(lat, terminals, cuts, q, beam_size, max_move, out, retur
     p_q, _k4 = _ptr_array([lat.ptr(x) for x in quants])
     p_ld, _k5 = _i64_array([max(lat.ld(x), M) for x in quants])   # (a tensor with at most one row may report any stride)
     return _run_lattices(lat, "boundary_quantiles", beam_size, max_move, (p_term, p_cut, p_K, levels.ctypes.data, M, p_q, p_ld),
-                         list(zip(quants)), return_status)
+                         list(zip(quants)), return_status, band_lo)
 
 
 def ctc_boundary_quantiles_batch(log_probs_list, labels_list, terminals, cuts_list, q=(0.05, 0.5, 0.95), beam_size=1000, max_move=4,
-                                 device=None, return_status=False):
+                                 device=None, return_status=False, band_lo=None):
     """Boundary quantiles of many lattices in ONE launch; host NumPy buffers in and out.  ``q`` is one list of levels for
     every lattice.
 
     Returns a list of (quantile [K_i, M], log_likelihood); with ``return_status`` also the per-lattice status list, in which
     case failures do not raise (their quantiles are -1, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    ``band_lo``: a list of tables, one per lattice (``ctc_path_posteriors``).
     """
     lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
-    return _boundary_quantiles(lat, terminals, cuts_list, q, beam_size, max_move, None, return_status)
+    return _boundary_quantiles(lat, terminals, cuts_list, q, beam_size, max_move, None, return_status, band_lo)
 
 
 def ctc_boundary_quantiles_device(log_probs, labels, terminals, cuts, q=(0.05, 0.5, 0.95), beam_size=1000, max_move=4, out=None,
-                                  return_status=False):
+                                  return_status=False, band_lo=None):
     """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]), terminals (ints or
     best paths) and host cut lists (strictly increasing in [0, 2 S_i + 1]); list of (quantile int32 tensor [K_i, M] on the
     device, log_likelihood float) out.  ``out``: optional list of int32 [K_i, M] tensors with unit column stride to write into
-    (views into wider tensors keep their other columns).  One launch on torch's current stream."""
+    (views into wider tensors keep their other columns).  One launch on torch's current stream.  ``band_lo``: a list of tables,
+    one per lattice, tensors on the device or host arrays."""
     lat = _device_lattices(log_probs, labels, terminals, "terminals")
-    return _boundary_quantiles(lat, terminals, cuts, q, beam_size, max_move, out, return_status)
+    return _boundary_quantiles(lat, terminals, cuts, q, beam_size, max_move, out, return_status, band_lo)
 
 
 def _boundary_cut(path, b, n_ph):
@@ -837,7 +843,7 @@ def segment_boundary_interval(quantile, cuts, best_path, seg_ends, n_phonemes):
 MAX_SAMPLES = 64
 
 
-def ctc_sample_paths(log_probs, labels, terminal, n_samples=64, seed=0, beam_size=1000, max_move=4):
+def ctc_sample_paths(log_probs, labels, terminal, n_samples=64, seed=0, beam_size=1000, max_move=4, band_lo=None):
     """Whole alignments drawn from the posterior over the band's paths: (paths int32 [n_samples, T], log_likelihood float).
 
     Row k is one path of the band of ``ctc_best_path`` that ends at state ``terminal`` (an int, or a best path whose last
@@ -847,10 +853,11 @@ def ctc_sample_paths(log_probs, labels, terminal, n_samples=64, seed=0, beam_siz
     Sample k depends on ``seed`` and k alone: it has the same bits whatever ``n_samples`` is, and whether the lattice is sent
     alone or in a batch.  One call draws at most 64 samples; more are the caller's loop over seeds (each seed gives 64 fresh,
     independent paths).  NumPy in -> NumPy out; ROCm torch tensors go to ``ctc_sample_paths_device``.  Raises as
-    ``ctc_label_posteriors``, and ValueError for ``n_samples`` outside [1, 64].
+    ``ctc_label_posteriors``, and ValueError for ``n_samples`` outside [1, 64].  ``band_lo``: the band as a table [T], as
+    ``ctc_path_posteriors`` takes it: every row is then a path of that band.
     """
     call = ctc_sample_paths_device if _is_tensor(log_probs) else ctc_sample_paths_batch
-    (result,) = call([log_probs], [labels], [terminal], n_samples, seed, beam_size, max_move)
+    (result,) = call([log_probs], [labels], [terminal], n_samples, seed, beam_size, max_move, band_lo=_one_table(band_lo))
     return result
 
 
@@ -862,7 +869,7 @@ def _per_lattice(x, n, what):
     return xs
 
 
-def _sample_paths(lat, terminals, n_samples, seed, beam_size, max_move, out, return_status):
+def _sample_paths(lat, terminals, n_samples, seed, beam_size, max_move, out, return_status, band_lo=None):
     if lat is None:
         return ([], []) if return_status else []
     Ks = _per_lattice(n_samples, lat.n, "n_samples")
@@ -876,29 +883,31 @@ def _sample_paths(lat, terminals, n_samples, seed, beam_size, max_move, out, ret
     p_paths, _k2 = _ptr_array([lat.ptr(x) for x in paths])
     p_ld, _k3 = _i64_array([max(lat.ld(x), T) for x, T in zip(paths, lat.T)])   # (a tensor with one row may report any stride)
     return _run_lattices(lat, "sample_paths", beam_size, max_move, (p_term, a_K.ctypes.data, a_seed.ctypes.data, p_paths, p_ld),
-                         list(zip(paths)), return_status)
+                         list(zip(paths)), return_status, band_lo)
 
 
 def ctc_sample_paths_batch(log_probs_list, labels_list, terminals, n_samples=64, seed=0, beam_size=1000, max_move=4, device=None,
-                           return_status=False):
+                           return_status=False, band_lo=None):
     """Sampled paths of many lattices in ONE launch; host NumPy buffers in and out.  ``n_samples`` and ``seed``: an int for
     every lattice, or one per lattice.
 
     Returns a list of (paths [n_samples_i, T_i], log_likelihood); with ``return_status`` also the per-lattice status list, in
     which case failures do not raise (their paths are -1, their log-likelihood NaN, or -inf for KA_ERR_ZERO_MASS).
+    ``band_lo``: a list of tables, one per lattice (``ctc_path_posteriors``).
     """
     lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
-    return _sample_paths(lat, terminals, n_samples, seed, beam_size, max_move, None, return_status)
+    return _sample_paths(lat, terminals, n_samples, seed, beam_size, max_move, None, return_status, band_lo)
 
 
-def ctc_sample_paths_device(log_probs, labels, terminals, n_samples=64, seed=0, beam_size=1000, max_move=4, out=None, return_status=False):
+def ctc_sample_paths_device(log_probs, labels, terminals, n_samples=64, seed=0, beam_size=1000, max_move=4, out=None, return_status=False,
+                            band_lo=None):
     """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]) and terminals (ints
     or best paths), list of (paths int32 tensor [n_samples_i, T_i] on the device, log_likelihood float) out.  ``n_samples``
     and ``seed``: an int for every lattice, or one per lattice.  ``out``: optional list of int32 [n_samples_i, T_i] tensors
     with unit column stride to write into (views into wider tensors keep their other columns).  One launch on torch's current
-    stream."""
+    stream.  ``band_lo``: a list of tables, one per lattice, tensors on the device or host arrays."""
     lat = _device_lattices(log_probs, labels, terminals, "terminals")
-    return _sample_paths(lat, terminals, n_samples, seed, beam_size, max_move, out, return_status)
+    return _sample_paths(lat, terminals, n_samples, seed, beam_size, max_move, out, return_status, band_lo)
 
 
 def _host_paths(paths):
@@ -956,7 +965,7 @@ def segment_boundary_spread(paths, best_path, seg_ends, n_phonemes, q=(0.05, 0.5
 # ------------------------------------------------------------------------------------------
 # the maximum-expected-accuracy alignment (posterior-decoded path), and where it leaves the best path
 # ------------------------------------------------------------------------------------------
-def ctc_mea_path(log_probs, labels, terminal, beam_size=1000, max_move=4):
+def ctc_mea_path(log_probs, labels, terminal, beam_size=1000, max_move=4, band_lo=None):
     """The alignment with the most frames at the right state in expectation: (path int32 [T], expected_accuracy float,
     log_likelihood float).
 
@@ -966,14 +975,15 @@ def ctc_mea_path(log_probs, labels, terminal, beam_size=1000, max_move=4):
     ``expected_accuracy`` is that sum - divided by T, the expected fraction of correctly placed frames, a one-number quality
     score of the lattice.  Ties go to the smallest move.  Equals the recursion run on ``ctc_state_posteriors`` at every frame
     bit for bit, without the [T, W] matrix.  NumPy in -> NumPy out; ROCm torch tensors go to ``ctc_mea_path_device``.  Raises
-    as ``ctc_label_posteriors``.
+    as ``ctc_label_posteriors``.  ``band_lo``: the band as a table [T], as ``ctc_path_posteriors`` takes it: the path is then
+    a path of that band (path[0] may lie above 0), decoded from that band's posteriors.
     """
     call = ctc_mea_path_device if _is_tensor(log_probs) else ctc_mea_path_batch
-    (result,) = call([log_probs], [labels], [terminal], beam_size, max_move)
+    (result,) = call([log_probs], [labels], [terminal], beam_size, max_move, band_lo=_one_table(band_lo))
     return result
 
 
-def _mea_path(lat, terminals, beam_size, max_move, out, return_status):
+def _mea_path(lat, terminals, beam_size, max_move, out, return_status, band_lo=None):
     if lat is None:
         return ([], []) if return_status else []
     if out is None:
@@ -991,28 +1001,30 @@ def _mea_path(lat, terminals, beam_size, max_move, out, return_status):
     p_path, _k2 = _ptr_array([lat.ptr(x) for x in paths])
     # (the expected accuracies are a host array the call fills: zipped as 0-d views, made floats once it has returned)
     got = _run_lattices(lat, "mea_path", beam_size, max_move, (p_term, p_path, ea.ctypes.data), list(zip(paths, ea.reshape(-1, 1))),
-                        return_status)
+                        return_status, band_lo)
     results = [(p, float(v[0]), z) for p, v, z in (got[0] if return_status else got)]
     return (results, got[1]) if return_status else results
 
 
-def ctc_mea_path_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False):
+def ctc_mea_path_batch(log_probs_list, labels_list, terminals, beam_size=1000, max_move=4, device=None, return_status=False,
+                       band_lo=None):
     """Maximum-expected-accuracy paths of many lattices in ONE launch; host NumPy buffers in and out.
 
     Returns a list of (path [T_i], expected_accuracy, log_likelihood); with ``return_status`` also the per-lattice status list,
     in which case failures do not raise (their paths are -1, their expected accuracy NaN, their log-likelihood NaN, or -inf for
-    KA_ERR_ZERO_MASS).
+    KA_ERR_ZERO_MASS).  ``band_lo``: a list of tables, one per lattice (``ctc_path_posteriors``).
     """
     lat = _host_lattices(log_probs_list, labels_list, terminals, "terminals", device)
-    return _mea_path(lat, terminals, beam_size, max_move, None, return_status)
+    return _mea_path(lat, terminals, beam_size, max_move, None, return_status, band_lo)
 
 
-def ctc_mea_path_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False):
+def ctc_mea_path_device(log_probs, labels, terminals, beam_size=1000, max_move=4, out=None, return_status=False, band_lo=None):
     """Lists of ROCm torch tensors in (float32 log-probs [T_i, V] with unit column stride, labels [S_i]) and terminals (ints
     or best paths), list of (path int32 tensor [T_i] on the device, expected_accuracy float, log_likelihood float) out.
-    ``out``: optional list of contiguous int32 [T_i] tensors to write the paths into.  One launch on torch's current stream."""
+    ``out``: optional list of contiguous int32 [T_i] tensors to write the paths into.  One launch on torch's current stream.
+    ``band_lo``: a list of tables, one per lattice, tensors on the device or host arrays."""
     lat = _device_lattices(log_probs, labels, terminals, "terminals")
-    return _mea_path(lat, terminals, beam_size, max_move, out, return_status)
+    return _mea_path(lat, terminals, beam_size, max_move, out, return_status, band_lo)
 
 
 def path_outputs(log_probs, labels, path):

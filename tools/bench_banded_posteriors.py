@@ -1,9 +1,11 @@
-"""Wall time of the four forward-backward calls over a caller-given band (ka_ctc_{path_posteriors, label_posteriors,
-state_posteriors, state_durations}_banded_batch_f32) with the reference's own band as the table,
-against their unbanded siblings, whose kernels differ from theirs only in the band policy.  One cfg2 lattice and 768 cfg2
-lattices (three per CU), in the fast form (V = 64) and the generic form (V = 65); device-resident hash-generated inputs; the
-terminal is the last position, the path the diagonal itself, the state call asks for 200 frames.  The two calls alternate in one
-process, 3 repetitions, the minimum counts.  The outputs of the two calls are compared bit for bit while they are there.
+"""Wall time of the eight forward-backward calls over a caller-given band (ka_ctc_{path_posteriors, label_posteriors,
+state_posteriors, state_durations, state_visits, boundary_quantiles, sample_paths, mea_path}_banded_batch_f32, DESIGN.md
+sections 4.30 and 4.31) with the reference's own band as the table, against their unbanded siblings, whose kernels differ from
+theirs only in the band policy.  One cfg2 lattice and 768 cfg2 lattices (three per CU), in the fast form (V = 64) and the generic
+form (V = 65); device-resident hash-generated inputs; the terminal is the last position, the path the diagonal itself, the state
+call asks for 200 frames, the quantile call for 100 cuts at text boundaries (even positions) and three levels, the sampler for
+64 paths.  The two calls alternate in one process, 3 repetitions, the minimum counts.  The outputs of the two calls are compared
+bit for bit while they are there.
 
     python tools/bench_banded_posteriors.py [--cases single,b768] [--forms fast,generic] [--calls path_posteriors,...] [--reps 3]
                                             [--out profiles/banded_posteriors_bench.jsonl]
@@ -27,7 +29,9 @@ from kokoro_align_amd import _lib  # noqa: E402
 from kokoro_align_amd.align import _i64_array, _ptr_array, _stream_ptr  # noqa: E402
 
 BEAM, MAX_MOVE, QUERIES = 1000, 4, 200
-CALLS = ("path_posteriors", "label_posteriors", "state_posteriors", "state_durations")
+CUTS, LEVELS, SAMPLES, SEED = 100, (0.05, 0.5, 0.95), 64, 20240
+CALLS = ("path_posteriors", "label_posteriors", "state_posteriors", "state_durations",
+         "state_visits", "boundary_quantiles", "sample_paths", "mea_path")
 
 
 def cfg2(n, V, seed0=9000, T=50000, S=5000):
@@ -63,7 +67,23 @@ def own_arguments(call, n, T, S, V):
         outs, los = dev((len(frames), W), torch.float32), dev(len(frames), torch.int64)
         k = (_ptr_array([frames.ctypes.data] * n), _i64_array([len(frames)] * n), ptrs(outs), _i64_array([W] * n), ptrs(los))
         return (terms[0], k[0][0], k[1][0], k[2][0], k[3][0], k[4][0]), outs + los, (k, terms, frames)
-    outs, sums = dev(L, torch.float64), dev(L, torch.float64)
+    if call == "boundary_quantiles":
+        cuts = np.unique(2 * np.linspace(0, S, CUTS).astype(np.int64))
+        levels = np.asarray(LEVELS, np.float64)
+        outs = dev((len(cuts), len(levels)), torch.int32)
+        k = (_ptr_array([cuts.ctypes.data] * n), _i64_array([len(cuts)] * n), ptrs(outs), _i64_array([len(levels)] * n))
+        return (terms[0], k[0][0], k[1][0], levels.ctypes.data, len(levels), k[2][0], k[3][0]), outs, (k, terms, cuts, levels)
+    if call == "sample_paths":
+        ks, seeds = np.full(n, SAMPLES, np.int32), np.full(n, SEED, np.uint64)
+        outs = dev((SAMPLES, T), torch.int32)
+        k = (ptrs(outs), _i64_array([T] * n))
+        return (terms[0], ks.ctypes.data, seeds.ctypes.data, k[0][0], k[1][0]), outs, (k, terms, ks, seeds)
+    if call == "mea_path":
+        ea = np.zeros(n, np.float64)
+        outs = dev(T, torch.int32)
+        k = (ptrs(outs),)
+        return (terms[0], k[0][0], ea.ctypes.data), outs, (k, terms, ea)
+    outs, sums = dev(L, torch.float64), dev(L, torch.float64)      # state_durations, state_visits
     k = (ptrs(outs), ptrs(sums))
     return (terms[0], k[0][0], k[1][0]), outs + sums, (k, terms)
 

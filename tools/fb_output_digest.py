@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""One SHA-256 per (case, call) over what the eight forward-backward calls and the four calls over a caller-given band write:
+"""One SHA-256 per (case, call) over what the eight forward-backward calls and the eight calls over a caller-given band write:
 the output bytes, then the log-likelihood and status bytes; behind it the number of lattices with status 0, and what the call's
 *_workspace_bytes function answers for host and for device memory (a banded call: its sibling's plus
-ka_band_table_workspace_bytes).  For a change of the kernels that must not move a bit: run it on the library before and after
+ka_band_table_workspace_bytes, or ka_boundary_quantile_band_table_workspace_bytes for the quantiles).  For a change of the kernels that must not move a bit: run it on the library before and after
 and diff.
 
     python tools/fb_output_digest.py [--library path/to/libkokoro_align_amd.so] > digest.txt
@@ -16,7 +16,7 @@ The calls go through the raw ctypes callers of tests/fb_harness.py, tests/durati
 tests/mea_harness.py: path posteriors, label occupancy, state posteriors at posterior_ref.query_frames(T), durations with
 time_sum, 64 sampled paths with a fixed seed, the maximum-expected-accuracy path with its expected accuracy, and (tests/visit_harness.py)
 the state visits with exit_time, (tests/quantile_harness.py) the boundary quantiles at cuts spread over [0, L] and the levels
-0.05, 0.5 and 0.95, and (tests/banded_fb_harness.py) the four banded calls, each once with the diagonal as a table and once with a
+0.05, 0.5 and 0.95, and (tests/banded_fb_harness.py, tests/banded_fb2_harness.py) the eight banded calls, each once with the diagonal as a table and once with a
 stepping table of banded_fb_ref.random_table whose first low end lies above 0, so that the zeros below it are hashed.  The cases
 are the smallest at which a slot mapping, a checkpoint extent or a block boundary can go wrong: every case of posterior_ref.edge_cases(), the one-wavefront ones once more in the generic form (V padded to 80), tiny
 lattices round the 32-frame block, every max_move with a label 0 and a -inf, a band that jumps (L > T), one that jumps more
@@ -94,13 +94,14 @@ def tables_of(R, B, rng, lats, beam):
     return {"diagonal": diag, "stepping": step}
 
 
-def workspace(L, _lib, fn, n, T, S, own, V, beam, mm, table=False):
-    """"host=... device=..." of the *_workspace_bytes function ``fn`` (``own``: its arguments between S and V)"""
+def workspace(L, _lib, fn, n, T, S, own, V, beam, mm, table=None):
+    """"host=... device=..." of the *_workspace_bytes function ``fn`` (``own``: its arguments between S and V); ``table``: the
+    function that answers a banded call's add-on"""
     arr = lambda xs: (ctypes.c_int64 * n)(*[int(x) for x in xs])
     got = []
     for mem in (_lib.KA_MEM_HOST, _lib.KA_MEM_DEVICE):
         b = getattr(L, fn)(n, arr(T), arr(S), *own, V, beam, mm, mem)
-        got.append(b + (L.ka_band_table_workspace_bytes(n, arr(T), mem) if table else 0))
+        got.append(b + (getattr(L, table)(n, arr(T), mem) if table else 0))
     return "host=%d device=%d" % tuple(got)
 
 
@@ -126,6 +127,7 @@ def main():
         return fold(a.fold)
     if a.library:
         os.environ["KA_LIBRARY"] = os.path.abspath(a.library)      # (read when the package is imported)
+    import banded_fb2_harness as BH2
     import banded_fb_harness as BH
     import banded_fb_ref as B
     import duration_harness as D
@@ -169,7 +171,18 @@ def main():
                                          ("state_posteriors", (terms, frames), "ka_state_posterior_workspace_bytes", (i64(len(f) for f in frames),)),
                                          ("state_durations", terms, "ka_state_duration_workspace_bytes", ())):
                 r = BH.run(eng, _lib, kind, lps, labs, own, beam, mm, tables=tabs)
-                results["%s_banded_%s" % (kind, tname)] = ([x for bufs in r.raw for x in bufs], r.ll, r.st, ws(fn, *extra, table=True))
+                results["%s_banded_%s" % (kind, tname)] = ([x for bufs in r.raw for x in bufs], r.ll, r.st,
+                                                           ws(fn, *extra, table="ka_band_table_workspace_bytes"))
+            k_samples = (ctypes.c_int32 * n)(*[SAMPLES] * n)
+            for kind, own, fn, extra, add_on in (
+                    ("state_visits", terms, "ka_state_visit_workspace_bytes", (), "ka_band_table_workspace_bytes"),
+                    ("boundary_quantiles", (terms, cuts), "ka_boundary_quantile_workspace_bytes", (i64(len(c) for c in cuts), len(LEVELS)),
+                     "ka_boundary_quantile_band_table_workspace_bytes"),
+                    ("sample_paths", (terms, [SAMPLES] * n, [SEED] * n), "ka_sample_paths_workspace_bytes", (k_samples,), "ka_band_table_workspace_bytes"),
+                    ("mea_path", terms, "ka_mea_path_workspace_bytes", (), "ka_band_table_workspace_bytes")):
+                r = BH2.run(eng, _lib, kind, lps, labs, own, beam, mm, tables=tabs, levels=LEVELS)
+                outs = [x for bufs in r.raw for x in bufs] + ([r.ea] if r.ea is not None else [])
+                results["%s_banded_%s" % (kind, tname)] = (outs, r.ll, r.st, ws(fn, *extra, table=add_on))
         for call, (outs, ll, st, bytes_) in results.items():
             h = hashlib.sha256()
             for x in list(outs) + [ll, st]:
