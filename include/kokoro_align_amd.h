@@ -399,6 +399,60 @@ size_t ka_banded_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, 
                                  int32_t mem);
 
 /*
+ * Best path over a self-steering band: ka_ctc_best_path_banded with the table computed on the fly and
+ * returned.  Every `period` frames the band is re-centred on the best-scoring live cell, so it waits while the reader pauses
+ * and moves as fast as they read.  With L = 2S+1, B = beam_size, P = period, and "the scores after frame k" the live cells and
+ * float32 scores of the banded recurrence after frame k (after frame -1: the virtual state {0: 0.0}):
+ *   lo_0 = 0
+ *   t > 0, t % P != 0:  lo_t = lo_{t-1}
+ *   t > 0, t % P == 0:  c = the position of the FIRST maximum of the scores after frame t-2 over the live cells, in ascending
+ *                       position (ties to the lowest position, values compared as floats, an all -inf list gives its lowest
+ *                       live position);  lo_t = min(max(lo_{t-1}, c - B / 2), L - 1);  no live cell: lo_t = lo_{t-1}
+ *   hi_t = min(lo_t + B, L);  everything else is the frame of ka_ctc_best_path_banded (moves, float32 add then compare, first
+ *   maximum, the veto on the label value, liveness, outputs, total score).
+ * The lag of two frames is the kernel's: where it needs the band of frame t it holds the scores after frame t-2.
+ *   period    a multiple of 4 in [4, 65536], else KA_ERR_BAD_ARGS before anything is launched
+ *   end_rule  0: the path ends at the highest live position of frame T-1 (the reference's rule); 1: at the first maximum of the
+ *             scores after frame T-1 over the live cells (audio that ends before the text does: under a tracking band the
+ *             highest live cell is just the band's top); anything else KA_ERR_BAD_ARGS
+ *   band_lo_out  [T] int32 output, where `mem` says (batch: a HOST array of n such pointers): the table the call walked.
+ *             Required: NULL is KA_ERR_BAD_ARGS.
+ * Other arguments, memory modes, return convention and stream synchronisation as ka_ctc_best_path_banded[_batch]_f32.
+ * What follows, exactly:
+ *   1. the table is valid for ka_ctc_best_path_banded and its posterior siblings: non-decreasing, in [0, L), constant
+ *      between multiples of P;
+ *   2. with end_rule 0, ka_ctc_best_path_banded over the returned table returns the same path, labels, scores, total score
+ *      and status, bit for bit;
+ *   3. with B >= 2L the table is all zeros and every output is ka_ctc_best_path_f32's at the same beam_size, for any period;
+ *   4. the arg-max cell of frame t-2 can stay (a move of 0 is never vetoed) and is never below the new lo, so a lattice with
+ *      valid labels, no NaN and B >= 1 never ends in KA_ERR_EMPTY_BEAM (the status is kept for the ABI's symmetry);
+ *   5. a lattice gives the same bits alone or inside a batch.
+ * Per lattice: KA_ERR_BAD_LABEL, KA_ERR_NAN, KA_ERR_EMPTY_BEAM.  A failed lattice's three path outputs are left as the banded
+ * call leaves them; its band_lo_out may hold anything within its own T elements.  A NaN never becomes an index: the retarget is
+ * clamped to [lo_{t-1}, L - 1] whatever the floats are, and the lattice is rejected at the end.
+ * Rule of thumb: the path is kept while period x (positions the reader advances per frame) < beam_size / 2.  The steering is
+ * greedy: a long passage of audio that the text does not hold can pull the band away, and nothing pulls it back.
+ * band_edge_contact (Python) on the returned table shows when that happened.
+ * Forms as ka_ctc_best_path_banded: one wavefront per lattice for min(beam_size, L) <= 1009, V <= 64, max_move <= 4 (a retarget
+ * is one cross-lane arg-max per period on top of the banded frame loop), else one 256-thread workgroup per lattice (not tuned).
+ * Cost against ka_ctc_best_path_banded_batch_f32 fed the returned table (tools/bench_tracking.py, profiles/tracking_bench.jsonl;
+ * MI355X, cfg2): one lattice 1.009 times that call at period 16 (31.59 against 31.32 ms) and 0.955 times at period 64; 1024
+ * lattices 0.996 times at period 16 (33.92 against 34.07 ms) and 0.947 times at period 64.
+ */
+int ka_ctc_best_path_tracking_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                  int32_t beam_size, int32_t max_move, int32_t period, int32_t end_rule, int32_t *best_path,
+                                  int32_t *best_labels, float *best_scores, int32_t *band_lo_out, float *total_score, int32_t mem,
+                                  void *stream);
+int ka_ctc_best_path_tracking_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                        const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move, int32_t period,
+                                        int32_t end_rule, int32_t *const *best_path, int32_t *const *best_labels, float *const *best_scores,
+                                        int32_t *const *band_lo_out, float *total_score, int32_t *status, int32_t mem, void *stream);
+/* device-workspace bytes such a call carves (0 for unsupported arguments): ka_banded_workspace_bytes without the copy of the
+ * table; for KA_MEM_HOST the staged table is the fourth staged output */
+size_t ka_tracking_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                   int32_t mem);
+
+/*
  * Forward-backward posteriors over a caller-given band: ka_ctc_path_posteriors, ka_ctc_label_posteriors,
  * ka_ctc_state_posteriors and ka_ctc_state_durations on the band of ka_ctc_best_path_banded instead of the reference's
  * diagonal, so that a path found under a table can be judged under the same table.  Each call is its sibling with one

@@ -6,7 +6,8 @@ Public surface mirrors the reference (kokoro_align/align.py):
     align(best_path_file, mfcc_file, voca_file, align_file, remove_wordsep)   align.py:127
     pandas_read_align(files)                                       align.py:172
 plus batched / device-resident entry points (ctc_best_path_batch, ctc_best_path_device), the best path over a band the caller
-gives (ctc_best_path_banded[_batch|_device], diagonal_band, anchored_band, band_around_path, band_edge_contact) and the
+gives (ctc_best_path_banded[_batch|_device], diagonal_band, anchored_band, band_around_path, band_edge_contact) or that steers
+itself by the scores and returns the table it walked (ctc_best_path_tracking[_batch|_device]) and the
 forward-backward quality signal of a best path (ctc_path_posteriors[_batch|_device], segment_confidence), the label
 occupancy of every frame (ctc_label_posteriors[_batch|_device], segment_agreement), the differentiable lattice
 log-likelihood (lattice_log_likelihood) and the state posteriors at chosen frames behind the confidence of align()'s text
@@ -36,6 +37,9 @@ from .align import (  # noqa: F401
     ctc_best_path_banded_device,
     ctc_best_path_batch,
     ctc_best_path_device,
+    ctc_best_path_tracking,
+    ctc_best_path_tracking_batch,
+    ctc_best_path_tracking_device,
     diagonal_band,
     log_softmax_device,
     pandas_read_align,

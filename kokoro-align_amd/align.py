@@ -441,6 +441,146 @@ def ctc_best_path_banded(log_probs, labels, band_lo, beam_size=1000, max_move=4)
     return ctc_best_path_banded_batch([lp], [labels], [band_lo], beam_size, max_move)[0]
 
 
+# ------------------------------------------------------------------------------------------
+# best path over a self-steering band
+# ------------------------------------------------------------------------------------------
+END_RULES = {"highest": 0, "best": 1}
+
+
+def _end_rule(end_rule):
+    return END_RULES[end_rule] if isinstance(end_rule, str) else int(end_rule)
+
+
+def _tracking_call(eng, lps, labs, lds, V, beam_size, max_move, period, end_rule, paths, louts, souts, bands, mem, stream):
+    """One ka_ctc_best_path_tracking_batch_f32 over buffers given by address; returns (rc, status, total)."""
+    n = len(lps)
+    status = np.zeros(n, np.int32)
+    total = np.zeros(n, np.float32)
+    p_lp, _k1 = _ptr_array([x[0] for x in lps])
+    p_lab, _k2 = _ptr_array([x[0] for x in labs])
+    p_band, _k3 = _ptr_array(bands)
+    p_path, _k4 = _ptr_array(paths)
+    p_lout, _k5 = _ptr_array(louts)
+    p_sout, _k6 = _ptr_array(souts)
+    p_T, _k7 = _i64_array([x[1] for x in lps])
+    p_S, _k8 = _i64_array([x[1] for x in labs])
+    p_ld, _k9 = _i64_array(lds)
+    rc = eng.lib.ka_ctc_best_path_tracking_batch_f32(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size), int(max_move), int(period),
+                                                     _end_rule(end_rule), p_path, p_lout, p_sout, p_band, total.ctypes.data,
+                                                     status.ctypes.data, mem, stream)
+    return rc, status, total
+
+
+def _tracking_result(rc, status, total, results, return_status, what):
+    if return_status:
+        if rc not in (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN):
+            _lib.check(rc, what)
+        return results, status.tolist(), total
+    _lib.check(rc, what)
+    return results
+
+
+def ctc_best_path_tracking_batch(log_probs_list, labels_list, beam_size=1000, max_move=4, period=16, end_rule="highest", device=None,
+                                 return_status=False, outputs=None):
+    """``ctc_best_path_tracking`` for a list of lattices in one call.  Host NumPy buffers in and out: a list of (best_path,
+    best_labels, best_scores, band_lo).  With ``return_status`` failures of single lattices do not raise and (results, statuses,
+    totals) are returned; a failed lattice's path arrays are not written.  ``outputs``: (paths, labels, scores, tables), lists
+    of contiguous int32 / int32 / float32 / int32 arrays of T_i elements to write into."""
+    n = len(log_probs_list)
+    assert n == len(labels_list)
+    if n == 0:
+        return ([], [], []) if return_status else []
+    lps = [_host_rows(x) for x in log_probs_list]
+    labs = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32) for x in labels_list]
+    V = lps[0].shape[1] if lps[0].ndim == 2 else 0
+    for x in lps:
+        if x.ndim != 2 or x.shape[1] != V:
+            raise ValueError("all log_probs must be [T_i, V] with one V")
+        if x.shape[0] == 0:
+            raise IndexError("list index out of range")
+    if outputs is None:
+        paths = [np.empty(x.shape[0], np.int32) for x in lps]
+        louts = [np.empty(x.shape[0], np.int32) for x in lps]
+        souts = [np.empty(x.shape[0], np.float32) for x in lps]
+        bands = [np.empty(x.shape[0], np.int32) for x in lps]
+    else:
+        paths, louts, souts, bands = outputs
+        for arrs, dt in ((paths, np.int32), (louts, np.int32), (souts, np.float32), (bands, np.int32)):
+            for a, x in zip(arrs, lps):
+                if a.dtype != dt or a.shape != (x.shape[0],) or not a.flags.c_contiguous:
+                    raise ValueError("outputs must be contiguous arrays of T_i elements: int32 paths, labels and tables, float32 scores")
+    eng = _lib.default_engine(_current_device() if device is None else device)
+    rc, status, total = _tracking_call(eng, [(x.ctypes.data, x.shape[0]) for x in lps], [(x.ctypes.data, x.shape[0]) for x in labs],
+                                       [max(V, x.strides[0] // 4) for x in lps], V, beam_size, max_move, period, end_rule,
+                                       [x.ctypes.data for x in paths], [x.ctypes.data for x in louts], [x.ctypes.data for x in souts],
+                                       [x.ctypes.data for x in bands], _lib.KA_MEM_HOST, None)
+    return _tracking_result(rc, status, total, list(zip(paths, louts, souts, bands)), return_status, "ctc_best_path_tracking_batch")
+
+
+def ctc_best_path_tracking_device(log_probs, labels, beam_size=1000, max_move=4, period=16, end_rule="highest", return_status=False,
+                                  outputs=None):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V], integer labels [S_i], which may also be NumPy arrays), list of
+    (best_path, best_labels, best_scores, band_lo) tensors out.  One launch for the whole list; the tables stay on the device
+    for the banded posterior calls (``band_lo=``).  ``outputs``: (paths, labels, scores, tables), lists of contiguous int32 /
+    int32 / float32 / int32 tensors of T_i elements on the same device to write into."""
+    import torch
+    n = len(log_probs)
+    assert n == len(labels) and n > 0
+    dev = log_probs[0].device
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    V = int(log_probs[0].shape[1])
+    lps, labs = [], []
+    for lp, lab in zip(log_probs, labels):
+        if lp.dim() != 2 or lp.shape[1] != V:
+            raise ValueError("all log_probs must be [T_i, V] with one V")
+        if lp.shape[0] == 0:
+            raise IndexError("list index out of range")
+        if lp.dtype != torch.float32:
+            lp = lp.float()
+        if lp.stride(1) != 1:
+            lp = lp.contiguous()
+        if not _is_tensor(lab):
+            lab = torch.as_tensor(np.asarray(lab).reshape(-1).astype(np.int32))
+        lps.append(lp)
+        labs.append(lab.reshape(-1).to(device=dev, dtype=torch.int32).contiguous())
+    if outputs is None:
+        paths = [torch.empty(x.shape[0], dtype=torch.int32, device=dev) for x in lps]
+        louts = [torch.empty(x.shape[0], dtype=torch.int32, device=dev) for x in lps]
+        souts = [torch.empty(x.shape[0], dtype=torch.float32, device=dev) for x in lps]
+        bands = [torch.empty(x.shape[0], dtype=torch.int32, device=dev) for x in lps]
+    else:
+        paths, louts, souts, bands = outputs
+        for arrs, dt in ((paths, torch.int32), (louts, torch.int32), (souts, torch.float32), (bands, torch.int32)):
+            for a, x in zip(arrs, lps):
+                if a.dtype != dt or tuple(a.shape) != (x.shape[0],) or not a.is_contiguous() or a.device != dev:
+                    raise ValueError("outputs must be contiguous tensors of T_i elements on the inputs' device")
+    eng = _lib.default_engine(idx)
+    with torch.cuda.device(dev):
+        rc, status, total = _tracking_call(eng, [(x.data_ptr(), x.shape[0]) for x in lps], [(x.data_ptr(), x.shape[0]) for x in labs],
+                                           [x.stride(0) for x in lps], V, beam_size, max_move, period, end_rule,
+                                           [x.data_ptr() for x in paths], [x.data_ptr() for x in louts], [x.data_ptr() for x in souts],
+                                           [x.data_ptr() for x in bands], _lib.KA_MEM_DEVICE, _stream_ptr(idx))
+    return _tracking_result(rc, status, total, list(zip(paths, louts, souts, bands)), return_status, "ctc_best_path_tracking_device")
+
+
+def ctc_best_path_tracking(log_probs, labels, beam_size=1000, max_move=4, period=16, end_rule="highest"):
+    """``ctc_best_path_banded`` with a band that steers itself: every ``period`` frames (a multiple of 4 in [4, 65536]) the band
+    is re-centred on the best-scoring live cell of two frames before, lo_t = min(max(lo_{t-1}, c - beam_size // 2), 2S), and
+    never moves back.  It waits while the reader pauses and follows as fast as they read, where the reference's diagonal assumes
+    a uniform rate.  Returns (best_path, best_labels, best_scores, band_lo): ``band_lo`` is the table that was walked, valid for
+    ``ctc_best_path_banded`` (which returns the same path under it) and for every posterior call's ``band_lo=``.
+    ``end_rule``: "highest" ends the path at the highest live position of the last frame (the reference's rule), "best" at the
+    best-scoring one (audio that ends before the text does).  The path is kept while period x (positions advanced per frame) <
+    beam_size / 2; the steering is greedy, and ``band_edge_contact`` on the returned table shows where the band may have
+    decided the path.  NumPy in -> NumPy out; ROCm torch tensors in -> torch tensors out."""
+    if _is_tensor(log_probs):
+        return ctc_best_path_tracking_device([log_probs], [labels], beam_size, max_move, period, end_rule)[0]
+    lp = np.asarray(log_probs)
+    if lp.ndim != 2:
+        raise ValueError("log_probs must be [T, V]")
+    return ctc_best_path_tracking_batch([lp], [labels], beam_size, max_move, period, end_rule)[0]
+
+
 def log_softmax_device(logits, out=None):
     """Mean-subtracted log-softmax of align.py:116-117 on the device (HIP kernel), float32."""
     import torch
@@ -467,18 +607,30 @@ def _host_log_softmax(logits):
     return centred - np.log(np.sum(np.exp(centred), axis=-1, keepdims=True))
 
 
-def best_path(input_file, voca_file, output_file, device_softmax=False):
+def best_path(input_file, voca_file, output_file, device_softmax=False, track_period=None):
     """``*.logits.npz`` + ``*.voca.txt`` -> ``*.best_path.npz`` (reference: align.py:112-124).
 
     Keys/dtypes of the output: best_path int32, best_labels int32, best_scores float32.
     ``device_softmax=True`` computes the log-softmax with the HIP kernel (1e-6 of the NumPy
     formula) and keeps the log-probs on the device; the default reproduces the reference's
     host NumPy arithmetic bit for bit and hands the DP a host buffer.
+    ``track_period``: a period for ``ctc_best_path_tracking`` instead of the reference's diagonal band; the table it walked is
+    stored as a fourth key, band_lo int32 (``align`` reads its three keys as before).  None changes nothing.
     """
     from .transcript import read_transcript
     with np.load(input_file) as f:
         logits = f['data']
     labels = read_transcript(voca_file)
+    if track_period is not None:
+        if device_softmax:
+            import torch
+            dev = torch.device("cuda", _current_device())
+            lp = log_softmax_device(torch.from_numpy(np.ascontiguousarray(logits, np.float32)).to(dev))
+            p, l, s, b = (x.cpu().numpy() for x in ctc_best_path_tracking(lp, labels, period=track_period))
+        else:
+            p, l, s, b = ctc_best_path_tracking(_host_log_softmax(logits), labels, period=track_period)
+        np.savez(output_file, best_path=p, best_labels=l, best_scores=s, band_lo=b)
+        return
     if device_softmax:
         import torch
         dev = torch.device("cuda", _current_device())

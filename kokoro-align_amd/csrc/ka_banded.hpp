@@ -1,5 +1,6 @@
 // ka_banded.hpp — best path over a caller-given band (ka_ctc_best_path_banded[_batch]_f32).
-// Included by ka_banded.hip only (it holds non-template kernels).
+// Included by ka_banded.hip, which holds the table's own kernels (preparation, the two walks back), and by ka_tracking.hip for
+// the self-steering band of ka_ctc_best_path_tracking (section 4.32): what the two share lives here.
 //
 // The recurrence is ka_device.hpp's with ONE change: the band's low end comes from a table,
 //   frame t:  lo = band_lo[t], hi = min(lo + B, L)         (align.py:64-65 replaced; everything else align.py:62-107)
@@ -34,13 +35,9 @@ constexpr int kBandMinWaves = 4;       // __launch_bounds__ of the one-wavefront
 
 typedef __attribute__((address_space(4))) const v4i_t *cc4_t;   // constant address space: scalar loads
 
-// ---------------------------------------------------------------------------------------
-// preparation: labels (validate, scale by 4, zero-pad), the band table (validate, shift, pad)
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void prep_banded_kernel(const BandLattice *__restrict__ lats, int32_t *meta)
+// labels of one lattice: validate, scale by 4, zero-pad (every thread of a 256-thread workgroup)
+__device__ __forceinline__ void prep_labels(const BandLattice &d, int32_t *m)
 {
-    const BandLattice &d = lats[blockIdx.x];
-    int32_t *m = meta_of(meta, d.idx);
     int bad = 0, zero = 0;
     for (int i = threadIdx.x; i < d.labx_len; i += blockDim.x) {
         int v = 0;
@@ -54,30 +51,119 @@ __global__ __launch_bounds__(256) void prep_banded_kernel(const BandLattice *__r
     }
     if (bad) atomicMin(&m[0], kStatusBadLabel);
     if (zero) atomicOr(&m[2], kFlagZeroLabel);
-    // the table: in range and non-decreasing
-    int bad_tab = 0;
-    for (int i = threadIdx.x; i < d.T; i += blockDim.x) {
-        const int v = d.band_lo[i];
-        if (v < 0 || v >= d.L) bad_tab = 1;
-        if (i > 0 && d.band_lo[i - 1] > v) bad_tab = 1;
-    }
-    if (__syncthreads_or(bad_tab)) {
-        if (threadIdx.x == 0) {
-            atomicMin(&m[0], kStatusBadArgs);
-            atomicOr(&m[2], kBandFlagBadTable);
-            m[1] = -1;
-        }
-        return;
-    }
-    if (d.tab)
-        for (int i = threadIdx.x; i < d.tab_len; i += blockDim.x) d.tab[i] = d.band_lo[i + 1 < d.T ? i + 1 : d.T - 1];
 }
+
+// ---------------------------------------------------------------------------------------
+// where the band's low end comes from: the frame loops below ask a policy for the low end of frame t+1 while sc[] / pres2
+// hold the cells of frame t-1
+// ---------------------------------------------------------------------------------------
+// First maximum of the scores over the live cells of a wavefront's ring, in ascending position (np.argmax over the compacted
+// live list: ties to the lowest position, -0.0 == +0.0, an all -inf list gives its lowest live position); -1 without a live
+// cell.  Per lane a float compare from the top cell down, then six butterfly steps over one orderable 64-bit key: the float's
+// order-preserving bits above, ~position below.  The result is a position some lane holds live, whatever the floats are.
+__device__ __forceinline__ int wave_best_live(const float (&sc)[16], uint32_t pres2, int blk)
+{
+    float best = 0.0f;
+    int bk = -1;
+#pragma unroll
+    for (int k = 15; k >= 0; --k) {
+        const bool take = ((pres2 >> (2 * k)) & 1u) != 0 && (bk < 0 || sc[k] >= best);
+        best = take ? sc[k] : best;
+        bk = take ? k : bk;
+    }
+    uint32_t b = __builtin_bit_cast(uint32_t, best);
+    b = b == 0x80000000u ? 0u : b;   // -0.0 orders as +0.0
+    uint32_t kh = b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
+    uint32_t kl = ~(uint32_t)(blk * 16 + bk);
+    kh = bk < 0 ? 0u : kh;   // (a live cell's key is never 0: kl = 0 would be position 2^32 - 1)
+    kl = bk < 0 ? 0u : kl;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t oh = (uint32_t)__shfl_xor((int)kh, off), ol = (uint32_t)__shfl_xor((int)kl, off);
+        const bool g = oh > kh || (oh == kh && ol > kl);
+        kh = g ? oh : kh;
+        kl = g ? ol : kl;
+    }
+    const uint32_t h = (uint32_t)__builtin_amdgcn_readfirstlane((int)kh), l = (uint32_t)__builtin_amdgcn_readfirstlane((int)kl);
+    return (h | l) == 0u ? -1 : (int)~l;
+}
+
+// the caller's table: prep shifted and padded it, one aligned scalar load per group of four frames, a group ahead of its use
+struct BandFromTable {
+    static constexpr bool kTracking = false;
+    typedef v4i_t Group;   // low ends of the four frames behind a group's first
+    cc4_t tab;
+    v4i_t step_next;
+    static __device__ __forceinline__ uint32_t first_lo(const BandLattice &d) { return (uint32_t)__builtin_amdgcn_readfirstlane(d.band_lo[0]); }
+    __device__ __forceinline__ void begin(const BandLattice &d)
+    {
+        tab = (cc4_t)(uintptr_t)d.tab;
+        step_next = tab[0];
+    }
+    __device__ __forceinline__ Group group(uint32_t tb, uint32_t, uint32_t, int)
+    {
+        const v4i_t step = step_next;
+        step_next = tab[(tb >> 2) + 1];
+        return step;
+    }
+    __device__ __forceinline__ uint32_t next_lo(const Group &step, int dd, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, const float (&)[16],
+                                                uint32_t, int)
+    {
+        return (uint32_t)(dd == 0 ? step.x : dd == 1 ? step.y : dd == 2 ? step.z : step.w);
+    }
+    __device__ __forceinline__ bool end_at_best() const { return false; }
+};
+
+// the self-steering band (ka_ctc_best_path_tracking): lo_0 = 0; frame t > 0 with t % period == 0 takes
+//   lo_t = min(max(lo_{t-1}, c - B / 2), L - 1),   c = the first maximum of the scores after frame t-2 over the live cells
+// (no live cell: lo_{t-1}); every other frame keeps lo_{t-1}.  The lag of two frames is what the loop has at hand where it needs
+// the next low end: in step A of frame t-1, sc[] holds the scores after frame t-2.  period is a multiple of 4, so a retarget
+// falls on the last frame of a group: a scalar compare per group, nothing in the other three frames, and the four frames of
+// a group share one low end, which lanes 0..3 write to the table the call returns (band_lo, here an output).
+struct BandTracking {
+    static constexpr bool kTracking = true;
+    struct Group {};
+    uint32_t period, next_rt;
+    int end_rule;
+    int32_t *out;
+    static __device__ __forceinline__ uint32_t first_lo(const BandLattice &) { return 0u; }
+    __device__ __forceinline__ void begin(const BandLattice &d)
+    {
+        out = const_cast<int32_t *>(d.band_lo);
+        next_rt = period;
+    }
+    __device__ __forceinline__ Group group(uint32_t tb, uint32_t lo, uint32_t T, int lane)
+    {
+        if (lane < 4 && tb + (uint32_t)lane < T) out[tb + (uint32_t)lane] = (int32_t)lo;
+        return Group();
+    }
+    __device__ __forceinline__ uint32_t next_lo(const Group &, int dd, uint32_t tb, uint32_t lo, uint32_t T, uint32_t L, uint32_t B, const float (&sc)[16],
+                                                uint32_t pres2, int blk)
+    {
+        uint32_t nlo = lo;
+        if (dd == kRowDepth - 1 && __builtin_expect(tb + kRowDepth == next_rt, 0)) {
+            asm volatile("" ::: "memory");  // a real branch: the common group pays a compare and a jump
+            next_rt += period;
+            if (tb + kRowDepth < T) {   // (no step into frame T)
+                const int c = wave_best_live(sc, pres2, blk);
+                if (c >= 0) {
+                    int v = c - (int)(B >> 1);
+                    v = v > (int)lo ? v : (int)lo;
+                    v = v < (int)L - 1 ? v : (int)L - 1;   // unconditional: whatever the floats were, lo stays in [0, L)
+                    nlo = (uint32_t)v;
+                }
+            }
+        }
+        return nlo;
+    }
+    __device__ __forceinline__ bool end_at_best() const { return end_rule == 1; }
+};
 
 // ---------------------------------------------------------------------------------------
 // forward DP, one wavefront per lattice, every cell's code stored
 // ---------------------------------------------------------------------------------------
-template <int M, bool ZL>
-__device__ __forceinline__ void forward_banded_wave(const BandLattice &d, int32_t *meta)
+template <int M, bool ZL, class Src>
+__device__ __forceinline__ void forward_banded_wave(const BandLattice &d, int32_t *meta, Src src)
 {
     constexpr int D = kRowDepth;
     const int lane = threadIdx.x;
@@ -86,7 +172,7 @@ __device__ __forceinline__ void forward_banded_wave(const BandLattice &d, int32_
     const uint32_t B = (uint32_t)__builtin_amdgcn_readfirstlane(d.beam);
     const float NINF = ninf();
 
-    uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane(d.band_lo[0]);   // band of frame 0 (the table is valid: prep)
+    uint32_t lo = Src::first_lo(d);   // band of frame 0 (a table is valid: prep)
     uint32_t hi = (L - lo < B) ? L : lo + B;
     uint32_t blo = lo >> 4;
     int blk = (int)blo + ((lane - (int)blo) & 63);   // block of 16 positions this lane currently owns
@@ -135,14 +221,13 @@ __device__ __forceinline__ void forward_banded_wave(const BandLattice &d, int32_
     const uint32_t *bp = reinterpret_cast<const uint32_t *>(d.bp);   // wave-uniform row base
     const uint32_t lane_store_off = (uint32_t)lane * 16u;            // codes: [t/4][lane][t%4] dwords
 
-    // low ends of frames tb+1 .. tb+4, one aligned scalar load per group, the next group's in flight (prep padded the table)
-    cc4_t tab = (cc4_t)(uintptr_t)d.tab;
-    v4i_t step_next = tab[0];
+    // low ends of frames tb+1 .. tb+4: the table's, one aligned scalar load per group, the next group's in flight (prep padded
+    // the table), or the tracking band's
+    src.begin(d);
 
     const char *row_ahead = lp + (size_t)(D < T ? D : T - 1) * ld;   // row min(t+D, T-1) of the current frame t
     for (uint32_t tb = 0; tb < T; tb += D) {
-        const v4i_t step = step_next;
-        step_next = tab[(tb >> 2) + 1];
+        const typename Src::Group step = src.group(tb, lo, T, lane);
         uint32_t gw[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) asm("" : "=v"(gw[i]));
@@ -167,8 +252,8 @@ __device__ __forceinline__ void forward_banded_wave(const BandLattice &d, int32_
                     prev_blk = blk;
                     pend_reset = false;
                 }
-                // A. band of frame t+1 from the table; re-label the lanes whose block lo has passed
-                const uint32_t nlo = (uint32_t)(dd == 0 ? step.x : dd == 1 ? step.y : dd == 2 ? step.z : step.w);
+                // A. band of frame t+1 from its source; re-label the lanes whose block lo has passed
+                const uint32_t nlo = src.next_lo(step, dd, tb, lo, T, L, B, sc, pres2, blk);
                 bool moved = false;
                 if (__builtin_expect(nlo != lo, 0)) {   // (prep repeats the last low end behind frame T-1: no step into frame T)
                     asm volatile("" ::: "memory");  // a real branch: the common frame pays a compare and a jump
@@ -236,13 +321,17 @@ __device__ __forceinline__ void forward_banded_wave(const BandLattice &d, int32_
         }
         return;
     }
-    // terminal state: the HIGHEST live position of frame T-1 (align.py:99-101)
+    // terminal state: the HIGHEST live position of frame T-1 (align.py:99-101), or on request the tracking call's best one
     int best = -1;
-    if (pres2) best = blk * 16 + ((31 - __clz((int)pres2)) >> 1);
+    if (Src::kTracking && src.end_at_best()) {
+        best = wave_best_live(sc, pres2, blk);
+    } else {
+        if (pres2) best = blk * 16 + ((31 - __clz((int)pres2)) >> 1);
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const int o = __shfl_xor(best, off);
-        best = o > best ? o : best;
+        for (int off = 32; off >= 1; off >>= 1) {
+            const int o = __shfl_xor(best, off);
+            best = o > best ? o : best;
+        }
     }
     if (best < 0) {
         if (lane == 0) {
@@ -266,91 +355,57 @@ __global__ __launch_bounds__(64, kBandMinWaves) void forward_banded_wave_kernel(
     const int flags = __builtin_amdgcn_readfirstlane(meta_of(meta, d.idx)[2]);
     if (flags & kBandFlagBadTable) return;
     if (((flags & kFlagZeroLabel) != 0) != ZL) return;
-    forward_banded_wave<M, ZL>(d, meta);
+    forward_banded_wave<M, ZL>(d, meta, BandFromTable());
 }
 
-// ---------------------------------------------------------------------------------------
-// the walk back, one wavefront per lattice: path, labels and scores of 16 frames at a time
-//
-// A path drops at most 3 positions per frame.  The chunk entered at position p (its last frame) stays within [p - 45, p];
-// the chunk below it within [p - 93, p]: its window of 8 blocks from block (p - 96) >> 4 is loaded while the current
-// chunk is walked.  Window register r[v]: lane = (f & 7) * 8 + j holds the code dword of frame 8 v + (f & 7), block j.
-// ---------------------------------------------------------------------------------------
-constexpr int kBandBtChunk = 16;
-__device__ __forceinline__ int band_bt_window(int p_entry)
-{
-    const int lo = p_entry - 6 * kBandBtChunk;
-    return (lo > 0 ? lo : 0) >> 4;
-}
-__device__ __forceinline__ void band_bt_load(uint32_t (&r)[2], gcu32_t bp, int t0, int n, int w0, int lane)
-{
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-        const int f = 8 * v + (lane >> 3);
-        const int t = t0 + f;
-        const size_t at = (size_t)(t >> 2) * 256 + (size_t)((w0 + (lane & 7)) & 63) * 4 + (size_t)(t & 3);
-        r[v] = f < n ? bp[at] : 0u;
-    }
-}
-__global__ __launch_bounds__(64) void backtrace_banded_wave_kernel(const BandLattice *__restrict__ lats, const int32_t *meta)
+// ... and the same pair over the self-steering band: no table to check, period and end rule are the call's
+template <int M, bool ZL>
+__global__ __launch_bounds__(64, kBandMinWaves) void forward_tracking_wave_kernel(const BandLattice *__restrict__ lats, int32_t *meta,
+                                                                                  uint32_t period, int end_rule)
 {
     const BandLattice &d = lats[blockIdx.x];
-    const int lane = threadIdx.x;
-    int p = __builtin_amdgcn_readfirstlane(meta[4 * (size_t)d.idx + 1]);
-    if (p < 0) return;   // no path: the status says why
-    const int T = __builtin_amdgcn_readfirstlane(d.T);
-    gcu32_t bp = (gcu32_t)d.bp;
-    gci32_t labx = (gci32_t)d.labx;
-    gcf32_t lp = (gcf32_t)d.lp;
-    const size_t ld = (size_t)d.ld;
-    int t0 = ((T - 1) / kBandBtChunk) * kBandBtChunk;
-    int n = T - t0;
-    int w = band_bt_window(p + 3 * kBandBtChunk);   // the tail chunk is entered at the end position itself
-    uint32_t cur[2], nxt[2] = {0u, 0u};
-    band_bt_load(cur, bp, t0, n, w, lane);
-    for (;;) {
-        const int t1 = t0 - kBandBtChunk;
-        const int wn = band_bt_window(p);
-        if (t1 >= 0) band_bt_load(nxt, bp, t1, kBandBtChunk, wn, lane);
-        const uint32_t c0 = blank_to_uniform(cur[0]), c1 = blank_to_uniform(cur[1]);
-        int q = p - 16 * w;   // position relative to the window: 0 .. 127
-        int pathv = 0;
-#pragma unroll
-        for (int f = kBandBtChunk - 1; f >= 0; --f) {
-            if (f < n) {
-                const uint32_t word = (uint32_t)__builtin_amdgcn_readlane((int)(f >= 8 ? c1 : c0), (f & 7) * 8 + (q >> 4));
-                pathv = lane == f ? q : pathv;
-                q -= bp_decode(word >> ((q * 2) & 31));
-            }
-        }
-        if (lane < n) {
-            const int pos = pathv + 16 * w;
-            const int t = t0 + lane;
-            const int lab = (pos & 1) ? (labx[pos >> 1] >> 2) : 0;
-            ((gi32_t)d.path)[t] = pos;
-            ((gi32_t)d.lab_out)[t] = lab;
-            ((gf32_t)d.sc_out)[t] = lp[(size_t)t * ld + (size_t)lab];
-        }
-        if (t1 < 0) break;
-        p = q + 16 * w;
-        cur[0] = nxt[0];
-        cur[1] = nxt[1];
-        w = wn;
-        t0 = t1;
-        n = kBandBtChunk;
-    }
+    const int flags = __builtin_amdgcn_readfirstlane(meta_of(meta, d.idx)[2]);
+    if (((flags & kFlagZeroLabel) != 0) != ZL) return;
+    BandTracking src;
+    src.period = period;
+    src.end_rule = end_rule;
+    forward_banded_wave<M, ZL>(d, meta, src);
 }
+
 
 // ---------------------------------------------------------------------------------------
 // generic form: any band, any V, max_move <= 255.  One 256-thread workgroup per lattice, score columns double-buffered in
 // global memory, one byte of back-pointer per band cell (forward_generic_kernel's scheme with the table).  Not tuned.
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void forward_banded_generic_kernel(const BandLattice *__restrict__ lats, int32_t *meta)
+// First maximum of a score column over its live cells in ascending position, as wave_best_live: the largest key
+// (order-preserving float bits, ~position), 0 without a live cell.  All 256 threads; `key` is shared memory.
+__device__ __forceinline__ unsigned long long block_best_live(const float *sc, const uint8_t *pr, int64_t plo, int64_t phi,
+                                                              unsigned long long *key)
 {
-    const BandLattice &d = lats[blockIdx.x];
+    if (threadIdx.x == 0) *key = 0ull;
+    __syncthreads();
+    unsigned long long mine = 0ull;
+    for (int64_t p = plo + threadIdx.x; p < phi; p += 256)
+        if (pr[p]) {
+            uint32_t b = __builtin_bit_cast(uint32_t, sc[p]);
+            b = b == 0x80000000u ? 0u : b;
+            const uint32_t kh = b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
+            const unsigned long long k = ((unsigned long long)kh << 32) | (uint32_t)~(uint32_t)p;
+            mine = k > mine ? k : mine;
+        }
+    if (mine) atomicMax(key, mine);
+    __syncthreads();
+    return *key;
+}
+
+// kTrack: the self-steering band of BandTracking instead of the table.  The arg-max of frame t-2 is taken at the end of frame
+// t-2, when its column is the current one, and held in shared memory for two frames; thread 0 writes the table.
+template <bool kTrack>
+__device__ __forceinline__ void forward_banded_generic(const BandLattice &d, int32_t *meta, int period, int end_rule)
+{
     const int tid = threadIdx.x;
     int32_t *m = meta_of(meta, d.idx);
-    if (m[2] & kBandFlagBadTable) return;
+    if (!kTrack && (m[2] & kBandFlagBadTable)) return;
     const int64_t T = d.T, L = d.L, B = d.beam;
     const int M = d.max_move;
     const int64_t W = d.W;
@@ -375,8 +430,19 @@ __global__ __launch_bounds__(256) void forward_banded_generic_kernel(const BandL
     if (tid == 0) { scA[0] = 0.0f; prA[0] = 1; }
     __syncthreads();
     int64_t plo = 0, phi = 1;
+    __shared__ unsigned long long s_key;
+    int64_t lo_track = 0;
     for (int64_t t = 0; t < T; ++t) {
-        const int64_t lo = d.band_lo[t];
+        if (kTrack) {
+            if (t > 0 && t % period == 0 && s_key != 0ull) {
+                const int64_t c = (int64_t)(uint32_t)~(uint32_t)s_key;
+                int64_t v = c - B / 2;
+                v = v > lo_track ? v : lo_track;
+                lo_track = v < L - 1 ? v : L - 1;   // unconditional: whatever the floats were, lo stays in [0, L)
+            }
+            if (tid == 0) const_cast<int32_t *>(d.band_lo)[t] = (int32_t)lo_track;
+        }
+        const int64_t lo = kTrack ? lo_track : (int64_t)d.band_lo[t];
         const int64_t hi = (L - lo < B) ? L : lo + B;
         const float *row = d.lp + (size_t)t * (size_t)d.ld;
         for (int64_t p = lo + tid; p < hi; p += 256) {
@@ -402,15 +468,21 @@ __global__ __launch_bounds__(256) void forward_banded_generic_kernel(const BandL
         { uint8_t *x = prA; prA = prB; prB = x; }
         plo = lo;
         phi = hi;
+        if (kTrack && t + 2 < T && (t + 2) % period == 0) block_best_live(scA, prA, plo, phi, &s_key);
     }
-    // highest live position of the last frame
+    // highest live position of the last frame (the tracking call's end rule 1: the best one)
     __shared__ int64_t s_best;
-    if (tid == 0) s_best = -1;
-    __syncthreads();
-    int64_t mine = -1;
-    for (int64_t p = plo + tid; p < phi; p += 256)
-        if (prA[p]) mine = p;
-    if (mine >= 0) atomicMax((long long *)&s_best, (long long)mine);
+    if (kTrack && end_rule == 1) {
+        const unsigned long long k = block_best_live(scA, prA, plo, phi, &s_key);
+        if (tid == 0) s_best = k ? (int64_t)(uint32_t)~(uint32_t)k : -1;
+    } else {
+        if (tid == 0) s_best = -1;
+        __syncthreads();
+        int64_t mine = -1;
+        for (int64_t p = plo + tid; p < phi; p += 256)
+            if (prA[p]) mine = p;
+        if (mine >= 0) atomicMax((long long *)&s_best, (long long)mine);
+    }
     __syncthreads();
     if (tid == 0) {
         if (s_best < 0) {
@@ -420,22 +492,6 @@ __global__ __launch_bounds__(256) void forward_banded_generic_kernel(const BandL
             m[1] = (int32_t)s_best;
             m[3] = __builtin_bit_cast(int32_t, scA[s_best]);
         }
-    }
-}
-
-__global__ __launch_bounds__(64) void backtrace_banded_generic_kernel(const BandLattice *__restrict__ lats, const int32_t *meta)
-{
-    const BandLattice &d = lats[blockIdx.x];
-    int64_t p = meta[4 * (size_t)d.idx + 1];
-    if (p < 0 || threadIdx.x != 0) return;
-    const int64_t T = d.T, W = d.W;
-    const uint8_t *bp = reinterpret_cast<const uint8_t *>(d.bp);
-    for (int64_t t = T - 1; t >= 0; --t) {
-        const int lab = (p & 1) ? (d.labx[p >> 1] >> 2) : 0;
-        d.path[t] = (int32_t)p;
-        d.lab_out[t] = lab;
-        d.sc_out[t] = d.lp[(size_t)t * (size_t)d.ld + (size_t)lab];
-        p -= bp[(size_t)t * (size_t)W + (size_t)(p - d.band_lo[t])];
     }
 }
 

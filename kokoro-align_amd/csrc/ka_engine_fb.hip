@@ -571,14 +571,16 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
 }
 
 
-// ---- best path over a caller-given band (ka_banded.hpp): its own kernels and workspace layout, whatever the engine's mode ----
+// ---- best path over a caller-given band (ka_banded.hpp): its own kernels and workspace layout, whatever the engine's mode.
+// period > 0: the self-steering band (ka_ctc_best_path_tracking): band_lo is then the table the call WRITES, a fourth output ----
 int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
                 const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move, const int32_t *const *band_lo,
                 int32_t *const *best_path, int32_t *const *best_labels, float *const *best_scores, float *total_score, int32_t *status,
-                int32_t mem, hipStream_t stream)
+                int32_t mem, hipStream_t stream, int32_t period = 0, int32_t end_rule = 0)
 {
     using Desc = ka::BandLattice;
     const bool host = mem == KA_MEM_HOST;
+    const bool tracking = period > 0;
     if (!e) return fail(KA_ERR_BAD_ARGS, "engine is NULL");
     if (e->batch.pending) return fail(KA_ERR_BAD_ARGS, "a batch is already enqueued: call ka_batch_finish first");
     if (n < 0 || (n > 0 && (!log_probs || !T || !ld || !labels || !S || !band_lo || !best_path || !best_labels || !best_scores)))
@@ -587,7 +589,7 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
     if (n == 0) return KA_OK;
     std::vector<ka::plan::BandCarve> cv(n);
     size_t off_meta = 0;
-    const size_t total = ka::plan::banded_workspace(n, T, S, V, beam_size, max_move, host, cv.data(), &off_meta);
+    const size_t total = ka::plan::banded_workspace(n, T, S, V, beam_size, max_move, host, cv.data(), &off_meta, tracking);
     if (total == 0) return fail(KA_ERR_BAD_ARGS, "banded best path: unsupported T/S/V/beam_size/max_move");
     for (int32_t i = 0; i < n; ++i) {
         if (ld[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld < V");
@@ -633,7 +635,7 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
             d.ld = ld[i];
         }
         d.labx = reinterpret_cast<int32_t *>(ws + c.labx);
-        d.tab = c.fast ? reinterpret_cast<int32_t *>(ws + c.tab) : nullptr;
+        d.tab = c.fast && !tracking ? reinterpret_cast<int32_t *>(ws + c.tab) : nullptr;
         d.bp = ws + c.bp;
         d.col = c.fast ? nullptr : reinterpret_cast<float *>(ws + c.col);
         d.T = (int32_t)T[i];
@@ -652,13 +654,14 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
             KA_HIP(hipMemcpy2DAsync(ws + cv[i].lp, (size_t)V * 4, log_probs[i], (size_t)ld[i] * 4, (size_t)V * 4, (size_t)T[i], hipMemcpyHostToDevice,
                                     stream));
             if (S[i] > 0) KA_HIP(hipMemcpyAsync(ws + cv[i].lab, labels[i], (size_t)S[i] * 4, hipMemcpyHostToDevice, stream));
-            KA_HIP(hipMemcpyAsync(ws + cv[i].band, band_lo[i], (size_t)T[i] * 4, hipMemcpyHostToDevice, stream));
+            if (!tracking) KA_HIP(hipMemcpyAsync(ws + cv[i].band, band_lo[i], (size_t)T[i] * 4, hipMemcpyHostToDevice, stream));
         }
     Desc *d_lats = reinterpret_cast<Desc *>(ws);
     int32_t *d_meta = reinterpret_cast<int32_t *>(ws + off_meta);
     KA_HIP(hipMemcpyAsync(d_lats, h, (size_t)n * sizeof(Desc), hipMemcpyHostToDevice, stream));
     KA_HIP(hipMemsetAsync(d_meta, 0, (size_t)n * sizeof(ka::LatticeMeta), stream));
-    ka::launch_best_path_banded(d_lats, n_fast, n - n_fast, max_move, d_meta, stream);
+    if (tracking) ka::launch_best_path_tracking(d_lats, n_fast, n - n_fast, max_move, period, end_rule, d_meta, stream);
+    else ka::launch_best_path_banded(d_lats, n_fast, n - n_fast, max_move, d_meta, stream);
     KA_HIP(hipGetLastError());
     KA_HIP(hipMemcpyAsync(h_meta, d_meta, (size_t)n * sizeof(ka::LatticeMeta), hipMemcpyDeviceToHost, stream));
     KA_HIP(hipStreamSynchronize(stream));
@@ -669,6 +672,7 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
             KA_HIP(hipMemcpyAsync(best_path[i], ws + cv[i].path, bytes, hipMemcpyDeviceToHost, stream));
             KA_HIP(hipMemcpyAsync(best_labels[i], ws + cv[i].lab_out, bytes, hipMemcpyDeviceToHost, stream));
             KA_HIP(hipMemcpyAsync(best_scores[i], ws + cv[i].sc_out, bytes, hipMemcpyDeviceToHost, stream));
+            if (tracking) KA_HIP(hipMemcpyAsync(const_cast<int32_t *>(band_lo[i]), ws + cv[i].band, bytes, hipMemcpyDeviceToHost, stream));
         }
         KA_HIP(hipStreamSynchronize(stream));
     }
@@ -685,6 +689,14 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
         }
     }
     return first_bad;
+}
+
+// the two arguments ka_ctc_best_path_tracking adds: checked before anything is launched
+int tracking_args(int32_t period, int32_t end_rule)
+{
+    if (period < 4 || period > 65536 || period % 4 != 0) return fail(KA_ERR_BAD_ARGS, "tracking best path: period must be a multiple of 4 in [4, 65536]");
+    if (end_rule != 0 && end_rule != 1) return fail(KA_ERR_BAD_ARGS, "tracking best path: end_rule must be 0 (highest live) or 1 (best live)");
+    return KA_OK;
 }
 
 }  // namespace
@@ -706,6 +718,33 @@ int ka_ctc_best_path_banded_f32(ka_engine *e, const float *log_probs, int64_t T,
 {
     return banded_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo, &best_path, &best_labels, &best_scores,
                        total_score, nullptr, mem, (hipStream_t)stream);
+}
+
+int ka_ctc_best_path_tracking_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                        const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move, int32_t period,
+                                        int32_t end_rule, int32_t *const *best_path, int32_t *const *best_labels, float *const *best_scores,
+                                        int32_t *const *band_lo_out, float *total_score, int32_t *status, int32_t mem, void *stream)
+{
+    const int rc = tracking_args(period, end_rule);
+    if (rc != KA_OK) return rc;
+    return banded_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, band_lo_out, best_path, best_labels, best_scores, total_score,
+                       status, mem, (hipStream_t)stream, period, end_rule);
+}
+
+int ka_ctc_best_path_tracking_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                  int32_t beam_size, int32_t max_move, int32_t period, int32_t end_rule, int32_t *best_path,
+                                  int32_t *best_labels, float *best_scores, int32_t *band_lo_out, float *total_score, int32_t mem, void *stream)
+{
+    const int rc = tracking_args(period, end_rule);
+    if (rc != KA_OK) return rc;
+    return banded_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo_out, &best_path, &best_labels, &best_scores,
+                       total_score, nullptr, mem, (hipStream_t)stream, period, end_rule);
+}
+
+size_t ka_tracking_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::banded_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr, true);
 }
 
 size_t ka_banded_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)

@@ -123,5 +123,11 @@ void launch_sample_paths(const BandDesc<SampleLattice, Band> *lats, int n_fast, 
 // (band <= kFastMaxBand, V <= 64, max_move <= 4), then [n_fast, n_fast + n_generic): one 256-thread workgroup per lattice.
 // `meta` (zeroed by the caller): a LatticeMeta per lattice of the batch ----
 void launch_best_path_banded(const BandLattice *lats, int n_fast, int n_generic, int max_move, int32_t *meta, hipStream_t s);
+// ... its walk back alone, over a table some forward pass has used
+void launch_backtrace_banded(const BandLattice *lats, int n_fast, int n_generic, const int32_t *meta, hipStream_t s);
+// ---- ka_tracking.hip: best path over a self-steering band (ka_banded.hpp's BandTracking): the same descriptors, band_lo
+// the table the forward kernels WRITE; period a multiple of 4, end_rule 0 (highest live position) or 1 (best live position) ----
+void launch_best_path_tracking(const BandLattice *lats, int n_fast, int n_generic, int max_move, int period, int end_rule, int32_t *meta,
+                               hipStream_t s);
 
 }  // namespace ka

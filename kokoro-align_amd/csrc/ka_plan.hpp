@@ -940,7 +940,8 @@ namespace plan {
 // descriptors, a LatticeMeta per lattice, then per lattice: the prepared labels, in the one-wavefront form the shifted and
 // padded table (4 ceil(T/4) + 4 int32) and the codes (256 bytes per frame, whole groups of four frames), in the generic form a
 // byte per band cell and the two score / two liveness columns; for host buffers the staged log-probs, labels, table and the three
-// outputs of every lattice.
+// outputs of every lattice.  `tracking` (ka_ctc_best_path_tracking_batch_f32): the same without the shifted table; the staged
+// table is then the call's fourth output.
 struct BandCarve {
     size_t lp, lab, band, path, lab_out, sc_out;   // host buffers only
     size_t labx, tab, bp, col;
@@ -948,7 +949,7 @@ struct BandCarve {
     bool fast;
 };
 inline size_t banded_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
-                               BandCarve *cv, size_t *off_meta)
+                               BandCarve *cv, size_t *off_meta, bool tracking = false)
 {
     size_t off = align_up((size_t)n * sizeof(BandLattice));
     if (off_meta) *off_meta = off;
@@ -964,7 +965,7 @@ inline size_t banded_workspace(int32_t n, const int64_t *T, const int64_t *S, in
         c.labx = off;
         off += align_up((size_t)sh.labx_len * 4);
         c.tab = off;
-        if (c.fast) off += align_up((size_t)c.tab_len * 4);
+        if (c.fast && !tracking) off += align_up((size_t)c.tab_len * 4);
         c.bp = off;
         off += align_up(c.fast ? (((size_t)sh.T + 3) / 4) * 1024 : (size_t)sh.T * (size_t)sh.W);
         c.col = off;
