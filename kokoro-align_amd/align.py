@@ -12,38 +12,17 @@ diagnostic band_edge_contact).
 
 The DP + backtrace (the reference's per-frame NumPy loop) run in the HIP library through the C
 ABI of include/kokoro_align_amd.h.  NumPy arrays are handed over as host buffers; torch tensors
-on a ROCm device are handed over by pointer and the results stay on the device.  The forward-backward
-calls over the same band (posteriors.py) borrow the ctypes table helpers below.
+on a ROCm device are handed over by pointer and the results stay on the device.  The batch calls take their
+lattices through _lattices.py, as the forward-backward calls over the same band (posteriors.py) do.
 """
-import ctypes
 import os
 
 import numpy as np
 
 from . import _lib
+from ._lattices import (_band_tables, _current_device, _device_lattices, _host_lattices, _i64_array, _is_tensor,  # noqa: F401
+                        _ptr_array, _stream_ptr)
 from .encoder import decode_text, merge_repeated
-
-
-# ------------------------------------------------------------------------------------------
-# helpers
-# ------------------------------------------------------------------------------------------
-def _is_tensor(x):
-    return hasattr(x, "data_ptr") and hasattr(x, "device")
-
-
-def _stream_ptr(device_index):
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream(device_index).cuda_stream)
-
-
-def _ptr_array(ptrs):
-    arr = (ctypes.c_void_p * len(ptrs))(*ptrs)
-    return ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p)), arr
-
-
-def _i64_array(vals):
-    arr = (ctypes.c_int64 * len(vals))(*[int(v) for v in vals])
-    return ctypes.cast(arr, ctypes.POINTER(ctypes.c_int64)), arr
 
 
 # ------------------------------------------------------------------------------------------
@@ -85,17 +64,63 @@ def ctc_best_path(log_probs, labels, beam_size=1000, max_move=4, verbose=True):
     return path, lout, sout
 
 
-def _current_device():
-    dev = os.environ.get("KA_DEVICE")
-    if dev is not None:
-        return int(dev)
-    try:
-        import torch
-        if torch.cuda.is_available():
-            return torch.cuda.current_device()
-    except ImportError:
-        pass
-    return 0
+# ------------------------------------------------------------------------------------------
+# the batch calls: plain, over a caller-given band, over a self-steering band
+# ------------------------------------------------------------------------------------------
+END_RULES = {"highest": 0, "best": 1}
+
+# per call: the dtypes of its outputs, and the statuses that ``return_status`` lets through without raising
+_BEST_PATH_CALLS = {
+    "": ((np.int32, np.int32, np.float32), (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_NONFINITE)),
+    "_banded": ((np.int32, np.int32, np.float32), (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_BAD_ARGS)),
+    "_tracking": ((np.int32, np.int32, np.float32, np.int32), (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN)),
+}
+
+
+def _run_best_path(lat, call, beam_size, max_move, own_args, outputs, return_status):
+    """The call ``ka_ctc_best_path<call>_batch_f32`` ("", "_banded", "_tracking"): the arguments all three take, ``own_args``
+    behind ``max_move`` (the band tables; period and end rule), then the outputs (paths, labels, scores and, for tracking, the
+    tables walked: allocated here, or the caller's ``outputs`` after a check), totals and statuses, and the status handling
+    of ``return_status``.  KA_ERR_BAD_ARGS is let through only as a lattice's own status (a bad table), not as the call's."""
+    dtypes, let_through = _BEST_PATH_CALLS[call]
+    if outputs is None:
+        outputs = [[lat.empty(T, dt) for T in lat.T] for dt in dtypes]
+    elif len(outputs) != len(dtypes) or any(len(arrs) != lat.n or not all(lat.is_out(a, (T,), dt) for a, T in zip(arrs, lat.T))
+                                            for arrs, dt in zip(outputs, dtypes)):
+        raise ValueError(f"outputs must be {len(dtypes)} lists of contiguous {' / '.join(np.dtype(dt).name for dt in dtypes)} "
+                         "arrays of T_i elements where the inputs are")
+    name = f"ctc_best_path{call}_{lat.form}"
+    status = np.zeros(lat.n, np.int32)
+    total = np.zeros(lat.n, np.float32)
+    eng = lat.engine()
+    p_lp, _k1 = _ptr_array([lat.ptr(x) for x in lat.lps])
+    p_lab, _k2 = _ptr_array([lat.ptr(x) for x in lat.labs])
+    p_T, _k3 = _i64_array(lat.T)
+    p_S, _k4 = _i64_array(lat.S)
+    p_ld, _k5 = _i64_array([lat.ld(x) for x in lat.lps])
+    p_outs = [_ptr_array([lat.ptr(x) for x in arrs]) for arrs in outputs]
+    with lat.guard():
+        rc = getattr(eng.lib, f"ka_ctc_best_path{call}_batch_f32")(
+            eng.handle, lat.n, p_lp, p_T, lat.V, p_ld, p_lab, p_S, int(beam_size), int(max_move), *own_args,
+            *[p for p, _ in p_outs], total.ctypes.data, status.ctypes.data, lat.mem, lat.stream())
+    results = list(zip(*outputs))
+    if return_status:
+        if rc not in let_through or (rc == _lib.KA_ERR_BAD_ARGS and not np.any(status == _lib.KA_ERR_BAD_ARGS)):
+            _lib.check(rc, name)
+        return results, status.tolist(), total
+    _lib.check(rc, name)
+    return results
+
+
+def _best_path_banded(lat, band_lo, beam_size, max_move, outputs, return_status):
+    tables = _band_tables(lat, band_lo)         # (held until the call has returned: the addresses below are theirs)
+    p_band, _k = _ptr_array([lat.ptr(x) for x in tables])
+    return _run_best_path(lat, "_banded", beam_size, max_move, (p_band,), outputs, return_status)
+
+
+def _best_path_tracking(lat, beam_size, max_move, period, end_rule, outputs, return_status):
+    end_rule = END_RULES[end_rule] if isinstance(end_rule, str) else int(end_rule)
+    return _run_best_path(lat, "_tracking", beam_size, max_move, (int(period), end_rule), outputs, return_status)
 
 
 def ctc_best_path_batch(log_probs_list, labels_list, beam_size=1000, max_move=4, device=None,
@@ -106,44 +131,10 @@ def ctc_best_path_batch(log_probs_list, labels_list, beam_size=1000, max_move=4,
     per-lattice status list (0 ok, -1 empty beam = the reference's ValueError) and total scores,
     in which case failures do not raise.
     """
-    n = len(log_probs_list)
-    assert n == len(labels_list)
-    if n == 0:
+    lat = _host_lattices(log_probs_list, labels_list, None, None, device)
+    if lat is None:
         return ([], [], []) if return_status else []
-    lps = [np.ascontiguousarray(x, dtype=np.float32) for x in log_probs_list]
-    labs = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32) for x in labels_list]
-    V = lps[0].shape[1]
-    for x in lps:
-        if x.ndim != 2 or x.shape[1] != V:
-            raise ValueError("all log_probs must be [T_i, V] with one V")
-        if x.shape[0] == 0:
-            raise IndexError("list index out of range")
-    Ts = [x.shape[0] for x in lps]
-    Ss = [x.shape[0] for x in labs]
-    paths = [np.empty(t, np.int32) for t in Ts]
-    louts = [np.empty(t, np.int32) for t in Ts]
-    souts = [np.empty(t, np.float32) for t in Ts]
-    status = np.zeros(n, np.int32)
-    total = np.zeros(n, np.float32)
-    eng = _lib.default_engine(_current_device() if device is None else device)
-    p_lp, _k1 = _ptr_array([x.ctypes.data for x in lps])
-    p_lab, _k2 = _ptr_array([x.ctypes.data for x in labs])
-    p_path, _k3 = _ptr_array([x.ctypes.data for x in paths])
-    p_lout, _k4 = _ptr_array([x.ctypes.data for x in louts])
-    p_sout, _k5 = _ptr_array([x.ctypes.data for x in souts])
-    p_T, _k6 = _i64_array(Ts)
-    p_S, _k7 = _i64_array(Ss)
-    p_ld, _k8 = _i64_array([V] * n)
-    rc = eng.lib.ka_ctc_best_path_batch_f32(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size),
-                                            int(max_move), p_path, p_lout, p_sout, total.ctypes.data,
-                                            status.ctypes.data, _lib.KA_MEM_HOST, None)
-    results = list(zip(paths, louts, souts))
-    if return_status:
-        if rc not in (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_NONFINITE):
-            _lib.check(rc, "ctc_best_path_batch")
-        return results, status.tolist(), total
-    _lib.check(rc, "ctc_best_path_batch")
-    return results
+    return _run_best_path(lat, "", beam_size, max_move, (), None, return_status)
 
 
 class DeviceBatch:
@@ -287,44 +278,6 @@ def band_edge_contact(best_path, band_lo, beam_size, L, max_move=4):
     return np.nonzero(low | high)[0]
 
 
-def _banded_call(eng, lps, labs, bands, lds, V, beam_size, max_move, paths, louts, souts, mem, stream):
-    """One ka_ctc_best_path_banded_batch_f32 over buffers given by address; returns (rc, status, total)."""
-    n = len(lps)
-    status = np.zeros(n, np.int32)
-    total = np.zeros(n, np.float32)
-    p_lp, _k1 = _ptr_array([x[0] for x in lps])
-    p_lab, _k2 = _ptr_array([x[0] for x in labs])
-    p_band, _k3 = _ptr_array(bands)
-    p_path, _k4 = _ptr_array(paths)
-    p_lout, _k5 = _ptr_array(louts)
-    p_sout, _k6 = _ptr_array(souts)
-    p_T, _k7 = _i64_array([x[1] for x in lps])
-    p_S, _k8 = _i64_array([x[1] for x in labs])
-    p_ld, _k9 = _i64_array(lds)
-    rc = eng.lib.ka_ctc_best_path_banded_batch_f32(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size), int(max_move),
-                                                   p_band, p_path, p_lout, p_sout, total.ctypes.data, status.ctypes.data, mem, stream)
-    return rc, status, total
-
-
-def _host_rows(x):
-    """float32 [T, V] rows as they lie if their columns are adjacent (a view with a row stride is handed over with its ld),
-    else a contiguous copy"""
-    x = np.asarray(x)
-    if x.dtype == np.float32 and x.ndim == 2 and x.shape[1] > 0 and x.strides[1] == 4 and x.strides[0] % 4 == 0 and \
-            x.strides[0] >= 4 * x.shape[1]:
-        return x
-    return np.ascontiguousarray(x, dtype=np.float32)
-
-
-def _check_band(band, T):
-    b = np.asarray(band)
-    if b.ndim != 1 or b.shape[0] != T:
-        raise ValueError("band_lo must hold one entry per frame")
-    if b.size and (b.min() < -2 ** 31 or b.max() >= 2 ** 31):
-        raise ValueError("band_lo: entries must fit int32")
-    return np.ascontiguousarray(b, dtype=np.int32)
-
-
 def ctc_best_path_banded_batch(log_probs_list, labels_list, band_lo_list, beam_size=1000, max_move=4, device=None,
                                return_status=False, outputs=None):
     """``ctc_best_path_batch`` over caller-given bands: frame t of lattice i searches positions [band_lo[t], min(band_lo[t] +
@@ -332,42 +285,10 @@ def ctc_best_path_banded_batch(log_probs_list, labels_list, band_lo_list, beam_s
     ValueError); a band that loses every live state raises ValueError like the reference's empty beam (status -1).  With
     ``return_status`` failures do not raise and (results, statuses, totals) are returned; a failed lattice's arrays are not written.
     ``outputs``: (paths, labels, scores), lists of contiguous int32 / int32 / float32 arrays of T_i elements to write into."""
-    n = len(log_probs_list)
-    assert n == len(labels_list) == len(band_lo_list)
-    if n == 0:
+    lat = _host_lattices(log_probs_list, labels_list, band_lo_list, "band_lo", device)
+    if lat is None:
         return ([], [], []) if return_status else []
-    lps = [_host_rows(x) for x in log_probs_list]
-    labs = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32) for x in labels_list]
-    V = lps[0].shape[1] if lps[0].ndim == 2 else 0
-    for x in lps:
-        if x.ndim != 2 or x.shape[1] != V:
-            raise ValueError("all log_probs must be [T_i, V] with one V")
-        if x.shape[0] == 0:
-            raise IndexError("list index out of range")
-    bands = [_check_band(b, x.shape[0]) for b, x in zip(band_lo_list, lps)]
-    if outputs is None:
-        paths = [np.empty(x.shape[0], np.int32) for x in lps]
-        louts = [np.empty(x.shape[0], np.int32) for x in lps]
-        souts = [np.empty(x.shape[0], np.float32) for x in lps]
-    else:
-        paths, louts, souts = outputs
-        for arrs, dt in ((paths, np.int32), (louts, np.int32), (souts, np.float32)):
-            for a, x in zip(arrs, lps):
-                if a.dtype != dt or a.shape != (x.shape[0],) or not a.flags.c_contiguous:
-                    raise ValueError("outputs must be contiguous arrays of T_i elements: int32 paths and labels, float32 scores")
-    eng = _lib.default_engine(_current_device() if device is None else device)
-    rc, status, total = _banded_call(eng, [(x.ctypes.data, x.shape[0]) for x in lps], [(x.ctypes.data, x.shape[0]) for x in labs],
-                                     [b.ctypes.data for b in bands], [max(V, x.strides[0] // 4) for x in lps], V, beam_size, max_move,
-                                     [x.ctypes.data for x in paths], [x.ctypes.data for x in louts], [x.ctypes.data for x in souts],
-                                     _lib.KA_MEM_HOST, None)
-    results = list(zip(paths, louts, souts))
-    if return_status:
-        if rc not in (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_BAD_ARGS) or \
-                (rc == _lib.KA_ERR_BAD_ARGS and not np.any(status == _lib.KA_ERR_BAD_ARGS)):
-            _lib.check(rc, "ctc_best_path_banded_batch")
-        return results, status.tolist(), total
-    _lib.check(rc, "ctc_best_path_banded_batch")
-    return results
+    return _best_path_banded(lat, band_lo_list, beam_size, max_move, outputs, return_status)
 
 
 def ctc_best_path_banded_device(log_probs, labels, band_lo, beam_size=1000, max_move=4, return_status=False, outputs=None):
@@ -375,55 +296,8 @@ def ctc_best_path_banded_device(log_probs, labels, band_lo, beam_size=1000, max_
     may also be NumPy arrays), list of (best_path, best_labels, best_scores) tensors out.  One launch for the whole list; a table
     built on the device from a device-resident path needs no round trip.  ``outputs``: (paths, labels, scores), lists of contiguous
     int32 / int32 / float32 tensors of T_i elements on the same device to write into."""
-    import torch
-    n = len(log_probs)
-    assert n == len(labels) == len(band_lo) and n > 0
-    dev = log_probs[0].device
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    V = int(log_probs[0].shape[1])
-    lps, labs, bands = [], [], []
-    for lp, lab, band in zip(log_probs, labels, band_lo):
-        if lp.dim() != 2 or lp.shape[1] != V:
-            raise ValueError("all log_probs must be [T_i, V] with one V")
-        if lp.shape[0] == 0:
-            raise IndexError("list index out of range")
-        if lp.dtype != torch.float32:
-            lp = lp.float()
-        if lp.stride(1) != 1:
-            lp = lp.contiguous()
-        if not _is_tensor(lab):
-            lab = torch.as_tensor(np.asarray(lab).reshape(-1).astype(np.int32))
-        if not _is_tensor(band):
-            band = torch.as_tensor(_check_band(band, lp.shape[0]))
-        if band.dim() != 1 or band.shape[0] != lp.shape[0]:
-            raise ValueError("band_lo must hold one entry per frame")
-        lps.append(lp)
-        labs.append(lab.reshape(-1).to(device=dev, dtype=torch.int32).contiguous())
-        bands.append(band.to(device=dev, dtype=torch.int32).contiguous())
-    if outputs is None:
-        paths = [torch.empty(x.shape[0], dtype=torch.int32, device=dev) for x in lps]
-        louts = [torch.empty(x.shape[0], dtype=torch.int32, device=dev) for x in lps]
-        souts = [torch.empty(x.shape[0], dtype=torch.float32, device=dev) for x in lps]
-    else:
-        paths, louts, souts = outputs
-        for arrs, dt in ((paths, torch.int32), (louts, torch.int32), (souts, torch.float32)):
-            for a, x in zip(arrs, lps):
-                if a.dtype != dt or tuple(a.shape) != (x.shape[0],) or not a.is_contiguous() or a.device != dev:
-                    raise ValueError("outputs must be contiguous tensors of T_i elements on the inputs' device")
-    eng = _lib.default_engine(idx)
-    with torch.cuda.device(dev):
-        rc, status, total = _banded_call(eng, [(x.data_ptr(), x.shape[0]) for x in lps], [(x.data_ptr(), x.shape[0]) for x in labs],
-                                         [b.data_ptr() for b in bands], [x.stride(0) for x in lps], V, beam_size, max_move,
-                                         [x.data_ptr() for x in paths], [x.data_ptr() for x in louts], [x.data_ptr() for x in souts],
-                                         _lib.KA_MEM_DEVICE, _stream_ptr(idx))
-    results = list(zip(paths, louts, souts))
-    if return_status:
-        if rc not in (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_BAD_ARGS) or \
-                (rc == _lib.KA_ERR_BAD_ARGS and not np.any(status == _lib.KA_ERR_BAD_ARGS)):
-            _lib.check(rc, "ctc_best_path_banded_device")
-        return results, status.tolist(), total
-    _lib.check(rc, "ctc_best_path_banded_device")
-    return results
+    lat = _device_lattices(log_probs, labels, band_lo, "band_lo")
+    return _best_path_banded(lat, band_lo, beam_size, max_move, outputs, return_status)
 
 
 def ctc_best_path_banded(log_probs, labels, band_lo, beam_size=1000, max_move=4):
@@ -444,77 +318,16 @@ def ctc_best_path_banded(log_probs, labels, band_lo, beam_size=1000, max_move=4)
 # ------------------------------------------------------------------------------------------
 # best path over a self-steering band
 # ------------------------------------------------------------------------------------------
-END_RULES = {"highest": 0, "best": 1}
-
-
-def _end_rule(end_rule):
-    return END_RULES[end_rule] if isinstance(end_rule, str) else int(end_rule)
-
-
-def _tracking_call(eng, lps, labs, lds, V, beam_size, max_move, period, end_rule, paths, louts, souts, bands, mem, stream):
-    """One ka_ctc_best_path_tracking_batch_f32 over buffers given by address; returns (rc, status, total)."""
-    n = len(lps)
-    status = np.zeros(n, np.int32)
-    total = np.zeros(n, np.float32)
-    p_lp, _k1 = _ptr_array([x[0] for x in lps])
-    p_lab, _k2 = _ptr_array([x[0] for x in labs])
-    p_band, _k3 = _ptr_array(bands)
-    p_path, _k4 = _ptr_array(paths)
-    p_lout, _k5 = _ptr_array(louts)
-    p_sout, _k6 = _ptr_array(souts)
-    p_T, _k7 = _i64_array([x[1] for x in lps])
-    p_S, _k8 = _i64_array([x[1] for x in labs])
-    p_ld, _k9 = _i64_array(lds)
-    rc = eng.lib.ka_ctc_best_path_tracking_batch_f32(eng.handle, n, p_lp, p_T, V, p_ld, p_lab, p_S, int(beam_size), int(max_move), int(period),
-                                                     _end_rule(end_rule), p_path, p_lout, p_sout, p_band, total.ctypes.data,
-                                                     status.ctypes.data, mem, stream)
-    return rc, status, total
-
-
-def _tracking_result(rc, status, total, results, return_status, what):
-    if return_status:
-        if rc not in (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN):
-            _lib.check(rc, what)
-        return results, status.tolist(), total
-    _lib.check(rc, what)
-    return results
-
-
 def ctc_best_path_tracking_batch(log_probs_list, labels_list, beam_size=1000, max_move=4, period=16, end_rule="highest", device=None,
                                  return_status=False, outputs=None):
     """``ctc_best_path_tracking`` for a list of lattices in one call.  Host NumPy buffers in and out: a list of (best_path,
     best_labels, best_scores, band_lo).  With ``return_status`` failures of single lattices do not raise and (results, statuses,
     totals) are returned; a failed lattice's path arrays are not written.  ``outputs``: (paths, labels, scores, tables), lists
     of contiguous int32 / int32 / float32 / int32 arrays of T_i elements to write into."""
-    n = len(log_probs_list)
-    assert n == len(labels_list)
-    if n == 0:
+    lat = _host_lattices(log_probs_list, labels_list, None, None, device)
+    if lat is None:
         return ([], [], []) if return_status else []
-    lps = [_host_rows(x) for x in log_probs_list]
-    labs = [np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32) for x in labels_list]
-    V = lps[0].shape[1] if lps[0].ndim == 2 else 0
-    for x in lps:
-        if x.ndim != 2 or x.shape[1] != V:
-            raise ValueError("all log_probs must be [T_i, V] with one V")
-        if x.shape[0] == 0:
-            raise IndexError("list index out of range")
-    if outputs is None:
-        paths = [np.empty(x.shape[0], np.int32) for x in lps]
-        louts = [np.empty(x.shape[0], np.int32) for x in lps]
-        souts = [np.empty(x.shape[0], np.float32) for x in lps]
-        bands = [np.empty(x.shape[0], np.int32) for x in lps]
-    else:
-        paths, louts, souts, bands = outputs
-        for arrs, dt in ((paths, np.int32), (louts, np.int32), (souts, np.float32), (bands, np.int32)):
-            for a, x in zip(arrs, lps):
-                if a.dtype != dt or a.shape != (x.shape[0],) or not a.flags.c_contiguous:
-                    raise ValueError("outputs must be contiguous arrays of T_i elements: int32 paths, labels and tables, float32 scores")
-    eng = _lib.default_engine(_current_device() if device is None else device)
-    rc, status, total = _tracking_call(eng, [(x.ctypes.data, x.shape[0]) for x in lps], [(x.ctypes.data, x.shape[0]) for x in labs],
-                                       [max(V, x.strides[0] // 4) for x in lps], V, beam_size, max_move, period, end_rule,
-                                       [x.ctypes.data for x in paths], [x.ctypes.data for x in louts], [x.ctypes.data for x in souts],
-                                       [x.ctypes.data for x in bands], _lib.KA_MEM_HOST, None)
-    return _tracking_result(rc, status, total, list(zip(paths, louts, souts, bands)), return_status, "ctc_best_path_tracking_batch")
+    return _best_path_tracking(lat, beam_size, max_move, period, end_rule, outputs, return_status)
 
 
 def ctc_best_path_tracking_device(log_probs, labels, beam_size=1000, max_move=4, period=16, end_rule="highest", return_status=False,
@@ -523,44 +336,8 @@ def ctc_best_path_tracking_device(log_probs, labels, beam_size=1000, max_move=4,
     (best_path, best_labels, best_scores, band_lo) tensors out.  One launch for the whole list; the tables stay on the device
     for the banded posterior calls (``band_lo=``).  ``outputs``: (paths, labels, scores, tables), lists of contiguous int32 /
     int32 / float32 / int32 tensors of T_i elements on the same device to write into."""
-    import torch
-    n = len(log_probs)
-    assert n == len(labels) and n > 0
-    dev = log_probs[0].device
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    V = int(log_probs[0].shape[1])
-    lps, labs = [], []
-    for lp, lab in zip(log_probs, labels):
-        if lp.dim() != 2 or lp.shape[1] != V:
-            raise ValueError("all log_probs must be [T_i, V] with one V")
-        if lp.shape[0] == 0:
-            raise IndexError("list index out of range")
-        if lp.dtype != torch.float32:
-            lp = lp.float()
-        if lp.stride(1) != 1:
-            lp = lp.contiguous()
-        if not _is_tensor(lab):
-            lab = torch.as_tensor(np.asarray(lab).reshape(-1).astype(np.int32))
-        lps.append(lp)
-        labs.append(lab.reshape(-1).to(device=dev, dtype=torch.int32).contiguous())
-    if outputs is None:
-        paths = [torch.empty(x.shape[0], dtype=torch.int32, device=dev) for x in lps]
-        louts = [torch.empty(x.shape[0], dtype=torch.int32, device=dev) for x in lps]
-        souts = [torch.empty(x.shape[0], dtype=torch.float32, device=dev) for x in lps]
-        bands = [torch.empty(x.shape[0], dtype=torch.int32, device=dev) for x in lps]
-    else:
-        paths, louts, souts, bands = outputs
-        for arrs, dt in ((paths, torch.int32), (louts, torch.int32), (souts, torch.float32), (bands, torch.int32)):
-            for a, x in zip(arrs, lps):
-                if a.dtype != dt or tuple(a.shape) != (x.shape[0],) or not a.is_contiguous() or a.device != dev:
-                    raise ValueError("outputs must be contiguous tensors of T_i elements on the inputs' device")
-    eng = _lib.default_engine(idx)
-    with torch.cuda.device(dev):
-        rc, status, total = _tracking_call(eng, [(x.data_ptr(), x.shape[0]) for x in lps], [(x.data_ptr(), x.shape[0]) for x in labs],
-                                           [x.stride(0) for x in lps], V, beam_size, max_move, period, end_rule,
-                                           [x.data_ptr() for x in paths], [x.data_ptr() for x in louts], [x.data_ptr() for x in souts],
-                                           [x.data_ptr() for x in bands], _lib.KA_MEM_DEVICE, _stream_ptr(idx))
-    return _tracking_result(rc, status, total, list(zip(paths, louts, souts, bands)), return_status, "ctc_best_path_tracking_device")
+    lat = _device_lattices(log_probs, labels, None, None)
+    return _best_path_tracking(lat, beam_size, max_move, period, end_rule, outputs, return_status)
 
 
 def ctc_best_path_tracking(log_probs, labels, beam_size=1000, max_move=4, period=16, end_rule="highest"):

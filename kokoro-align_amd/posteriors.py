@@ -3,105 +3,23 @@ expected state durations, state visit probabilities, exact boundary-time quantil
 maximum-expected-accuracy alignment.
 
 The six calls take the same lattices (log-probs, labels, beam_size, max_move) in host or device memory and answer with one
-log-likelihood and one status per lattice.  ``_Lattices`` is that common input, normalised once and aware of its memory mode;
-``_run_lattices`` is the one C call and the one status handling.  What is a call's own (its extra inputs, its outputs, its
-argument tables) is in its private function; ``X_batch`` and ``X_device`` only choose the memory mode.
+log-likelihood and one status per lattice.  ``_Lattices`` (_lattices.py, shared with the best-path batch calls of align.py) is
+that common input, normalised once and aware of its memory mode; ``_run_lattices`` is the one C call and the one status
+handling.  What is a call's own (its extra inputs, its outputs, its argument tables) is in its private function; ``X_batch``
+and ``X_device`` only choose the memory mode.
 """
-import contextlib
-
 import numpy as np
 
 from . import _lib
-from .align import _current_device, _i64_array, _is_tensor, _ptr_array, _stream_ptr
+from ._lattices import _band_tables, _device_lattices, _host_lattices, _i64_array, _is_tensor, _ptr_array
 
 _POSTERIOR_LATTICE_STATUSES = (_lib.KA_OK, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_NONFINITE, _lib.KA_ERR_BAD_ARGS,
                                _lib.KA_ERR_ZERO_MASS)
 
 
 # ------------------------------------------------------------------------------------------
-# the lattices of one call and the call itself
+# the call itself
 # ------------------------------------------------------------------------------------------
-class _Lattices:
-    """n lattices as one ``ka_ctc_<call>_batch_f32`` call takes them: ``lps`` float32 [T_i, V] with unit column
-    stride, ``labs`` int32 [S_i].  What differs between host and device memory is in the attributes ``mode`` brings:
-    form, mem, dev, ptr(x), ld(x) (row pitch), int32(x) (a per-position input as the call wants it), empty(shape, dtype),
-    engine(), stream(), guard()."""
-
-    def __init__(self, lps, labels, V, **mode):
-        self.__dict__.update(mode)
-        self.lps, self.V, self.n = lps, V, len(lps)
-        self.labs = [self.int32(x) for x in labels]
-        self.T = [int(x.shape[0]) for x in lps]
-        self.S = [int(x.shape[0]) for x in self.labs]
-
-
-def _host_lattices(log_probs_list, labels_list, others, what, device):
-    """The input handling of the ``*_batch`` calls: contiguous NumPy arrays in, NumPy results; None for an empty batch.
-    ``others`` holds the call's own input (one best path or terminal per lattice) and is only counted here."""
-    n = len(log_probs_list)
-    if n != len(labels_list) or n != len(others):
-        raise ValueError(f"log_probs, labels and {what} must be lists of one length")
-    if n == 0:
-        return None
-    lps = [np.ascontiguousarray(x, dtype=np.float32) for x in log_probs_list]
-    V = lps[0].shape[1] if lps[0].ndim == 2 else 0
-    for x in lps:
-        if x.ndim != 2 or x.shape[1] != V:
-            raise ValueError("all log_probs must be [T_i, V] with one V")
-        if x.shape[0] == 0:
-            raise IndexError("list index out of range")
-    return _Lattices(lps, labels_list, V, form="batch", mem=_lib.KA_MEM_HOST, dev=None, ptr=lambda x: x.ctypes.data,
-                     ld=lambda x: x.shape[1], int32=lambda x: np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32),
-                     empty=np.empty, engine=lambda: _lib.default_engine(_current_device() if device is None else device),
-                     stream=lambda: None, guard=contextlib.nullcontext)
-
-
-def _device_lattices(log_probs, labels, others, what):
-    """The input handling of the ``*_device`` calls: tensors on the first log-prob's device in, results there, the call on
-    torch's current stream; ``others`` as in ``_host_lattices``."""
-    import torch
-    n = len(log_probs)
-    if n != len(labels) or n != len(others) or n == 0:
-        raise ValueError(f"log_probs, labels and {what} must be non-empty lists of one length")
-    dev = log_probs[0].device
-    V = int(log_probs[0].shape[1])
-    lps = []
-    for lp in log_probs:
-        if lp.dtype != torch.float32:
-            lp = lp.float()
-        if lp.dim() != 2 or lp.shape[1] != V:
-            raise ValueError("all log_probs must be [T_i, V] tensors with one V")
-        if lp.shape[0] == 0:
-            raise IndexError("list index out of range")
-        if lp.stride(1) != 1:
-            lp = lp.contiguous()
-        lps.append(lp)
-    dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
-    dtypes = {np.float32: torch.float32, np.float64: torch.float64, np.int64: torch.int64, np.int32: torch.int32}
-
-    def int32(x):
-        x = x if _is_tensor(x) else torch.as_tensor(np.asarray(x).reshape(-1).astype(np.int32))
-        return x.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
-
-    return _Lattices(lps, labels, V, form="device", mem=_lib.KA_MEM_DEVICE, dev=dev, ptr=lambda x: x.data_ptr(),
-                     ld=lambda x: x.stride(0), int32=int32, empty=lambda shape, dtype: torch.empty(shape, dtype=dtypes[dtype], device=dev),
-                     engine=lambda: _lib.default_engine(dev_index), stream=lambda: _stream_ptr(dev_index),
-                     guard=lambda: torch.cuda.device(dev))
-
-
-def _band_tables(lat, band_lo):
-    """The tables of a banded call as the call wants them: one per lattice, int32 where the lattices are, T_i entries.  They
-    may come as int64 (as ``diagonal_band`` and the other table builders return them) or as tensors."""
-    if len(band_lo) != lat.n:
-        raise ValueError("band_lo must hold one table per lattice")
-    if lat.form == "batch":
-        band_lo = [x.detach().cpu().numpy() if _is_tensor(x) else x for x in band_lo]
-    tables = [lat.int32(x) for x in band_lo]
-    if any(b.shape[0] != T for b, T in zip(tables, lat.T)):
-        raise ValueError("a band table must have one entry per frame")
-    return tables
-
-
 def _run_lattices(lat, call, beam_size, max_move, own_args, outs, return_status, band_lo=None):
     """The call ``ka_ctc_<call>_batch_f32`` (path_posteriors, label_posteriors, state_posteriors, state_durations, state_visits, boundary_quantiles,
     sample_paths, mea_path): the

@@ -183,7 +183,7 @@ def bad_tables(lo, L):
 def test_invalid_table_is_a_status_of_its_lattice(env, mode, form):
     ka, eng = env
     from kokoro_align_amd import _lib
-    from kokoro_align_amd.align import _banded_call
+    from bestpath_harness import banded_call
     lp, lab, lo, beam, mm = C.case("shifted")
     lp2, lab2, lo2, _, _ = C.case("const0")
     if form == "generic":
@@ -207,7 +207,7 @@ def test_invalid_table_is_a_status_of_its_lattice(env, mode, form):
         lpc = np.ascontiguousarray(lp)
         bands = [np.ascontiguousarray(b, np.int32) for b in order]
         outs = [[np.full(T, SENTINEL, dt) for _ in range(2)] for dt in (np.int32, np.int32, np.float32)]
-        rc, status, _ = _banded_call(eng, [(lpc.ctypes.data, T)] * 2, [(lab.ctypes.data, len(lab))] * 2, [b.ctypes.data for b in bands],
+        rc, status, _ = banded_call(eng, [(lpc.ctypes.data, T)] * 2, [(lab.ctypes.data, len(lab))] * 2, [b.ctypes.data for b in bands],
                                        [lpc.shape[1]] * 2, lpc.shape[1], beam, mm, *[[a.ctypes.data for a in o] for o in outs], _lib.KA_MEM_HOST, None)
         assert rc == first and sorted(status.tolist()) == [_lib.KA_ERR_BAD_ARGS, _lib.KA_ERR_EMPTY_BEAM]
         assert all(np.all(a == SENTINEL) for o in outs for a in o)
@@ -285,7 +285,7 @@ def test_workspace_bytes_cover_the_call(env):
     import torch
     ka, _ = env
     from kokoro_align_amd import _lib
-    from kokoro_align_amd.align import _banded_call
+    from bestpath_harness import banded_call
     shapes = [(300, 200, "wave"), (401, 500, "wave"), (400, 520, "generic")]
     beam = {"wave": 1000, "generic": 1100}
     for mem in (_lib.KA_MEM_HOST, _lib.KA_MEM_DEVICE):
@@ -311,7 +311,7 @@ def test_workspace_bytes_cover_the_call(env):
                 ka.ctc_best_path_banded_batch([lp], [lab], [lo], beam[form], 4)   # (the kernels' code is on the device before memory is counted)
                 torch.cuda.synchronize()
                 free0 = torch.cuda.mem_get_info()[0]
-                rc, status, _ = _banded_call(eng, [(ptr[0], T)], [(ptr[1], S)], [ptr[2]], [39], 39, beam[form], 4, [ptr[3]], [ptr[4]], [ptr[5]], mem,
+                rc, status, _ = banded_call(eng, [(ptr[0], T)], [(ptr[1], S)], [ptr[2]], [39], 39, beam[form], 4, [ptr[3]], [ptr[4]], [ptr[5]], mem,
                                                None)
                 assert rc == 0 and torch.cuda.mem_get_info()[0] == free0, (T, S, form, mem)
                 got = [x.cpu().numpy() for x in keep[3:]] if mem == _lib.KA_MEM_DEVICE else outs

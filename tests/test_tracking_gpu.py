@@ -235,7 +235,7 @@ def test_a_nan_is_a_status_and_never_an_index(env, form):
 def test_bad_arguments_write_nothing(env):
     import torch
     from kokoro_align_amd import _lib
-    from kokoro_align_amd.align import _tracking_call
+    from bestpath_harness import tracking_call
     ka, _ = env
     eng = _lib.default_engine(torch.cuda.current_device())
     lp, lab, beam, mm, _, _ = K.case("mm3")
@@ -246,7 +246,7 @@ def test_bad_arguments_write_nothing(env):
         ptrs = [[a.ctypes.data] for a in outs]
         if null_table:
             ptrs[3] = [None]
-        rc, status, _ = _tracking_call(eng, [(lpc.ctypes.data, T)], [(lab.ctypes.data, len(lab))], [lpc.shape[1]], lpc.shape[1], beam, mm, period,
+        rc, status, _ = tracking_call(eng, [(lpc.ctypes.data, T)], [(lab.ctypes.data, len(lab))], [lpc.shape[1]], lpc.shape[1], beam, mm, period,
                                        end_rule, *ptrs, _lib.KA_MEM_HOST, None)
         assert all(np.all(a == SENTINEL) for a in outs), (period, end_rule, null_table)
         return rc
@@ -271,7 +271,7 @@ def test_workspace_bytes_cover_the_call(env):
     import torch
     ka, _ = env
     from kokoro_align_amd import _lib
-    from kokoro_align_amd.align import _tracking_call
+    from bestpath_harness import tracking_call
     from oracle import oracle as O
     shapes = [(300, 200, "wave"), (401, 500, "wave"), (400, 520, "generic")]
     beam = {"wave": 1000, "generic": 1100}
@@ -296,7 +296,7 @@ def test_workspace_bytes_cover_the_call(env):
                 want = ka.ctc_best_path_tracking_batch([lp], [lab], beam[form], 4, 16)[0]   # (the kernels' code is on the device before memory is counted)
                 torch.cuda.synchronize()
                 free0 = torch.cuda.mem_get_info()[0]
-                rc, status, _ = _tracking_call(eng, [(ptr[0], T)], [(ptr[1], S)], [39], 39, beam[form], 4, 16, 0, [ptr[2]], [ptr[3]], [ptr[4]], [ptr[5]],
+                rc, status, _ = tracking_call(eng, [(ptr[0], T)], [(ptr[1], S)], [39], 39, beam[form], 4, 16, 0, [ptr[2]], [ptr[3]], [ptr[4]], [ptr[5]],
                                                mem, None)
                 assert rc == 0 and torch.cuda.mem_get_info()[0] == free0, (T, S, form, mem)
                 got = [x.cpu().numpy() for x in keep[2:]] if mem == _lib.KA_MEM_DEVICE else outs
