@@ -74,6 +74,11 @@ __device__ __forceinline__ float first_lane(float x)
 {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
 }
+// x of lane `l` (a constant), as a scalar
+__device__ __forceinline__ float lane_of(float x, int l)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l));
+}
 
 // Log-prob row loads are issued from inline asm so that hipcc does not track them: with a store
 // and a load of different kinds in flight it would wait vmcnt(0) before every row use, draining
@@ -108,6 +113,20 @@ __device__ __forceinline__ u32x4 lp_descriptor(const void *base, uint64_t bytes)
 __device__ __forceinline__ void row_reload_buf(float &r, uint32_t lane_byte_off, u32x4 rsrc /* wave-uniform */, uint32_t row_byte_off /* wave-uniform */)
 {
     asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "+v"(r) : "v"(lane_byte_off), "s"(rsrc), "s"(row_byte_off) : "memory");
+}
+// Four consecutive rows of a lattice with ld == 64 are one contiguous 1-KB run: lane l takes its bytes 16 l .. 16 l + 15.  The
+// whole byte offset (block + lane) is the VECTOR offset, which the descriptor's range check covers for certain: a block that
+// reaches past the lattice's last row comes back as zeros, dword by dword, and touches no memory.  Destination tied as in
+// row_reload.
+__device__ __forceinline__ void block_reload(f32x4 &r, uint32_t byte_off, u32x4 rsrc /* wave-uniform */)
+{
+    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "+v"(r) : "v"(byte_off), "s"(rsrc) : "memory");
+}
+// wait for everything: the only operations that can be younger than a block request are checkpoint stores and label reloads,
+// which are there in some frames and not in others, so no count above zero is safe
+__device__ __forceinline__ void block_wait(f32x4 &r)
+{
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(r) : : "memory");
 }
 // wait until at most N younger vector-memory operations are outstanding, then release `r`
 template <int N>

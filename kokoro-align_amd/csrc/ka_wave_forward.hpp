@@ -251,12 +251,24 @@ __device__ __forceinline__ void forward_w16(const Lattice &d, int32_t *meta)
 //     every eighth (narrow gap: fourth) frame; checkpoints are taken there.  In between, cells above hi pick
 //     up "leaked" scores from the live cells below them, M-1 cells further per frame; moves only go up, so a
 //     leak cannot reach a live cell except around the ring, through the >= 15 dead slots between hi and lo:
-//     at most 3 frames x 3 cells + the 3 cells lo reads (7 frames when there are >= 24 dead slots).
+//     at most 3 frames x 3 cells + the 3 cells lo reads (7 frames when there are >= 24 dead slots).  Where the band steps
+//     at least that often for the whole lattice the periodic pass is dropped except on checkpoint frames (steps_mask).
+//
+// Log-prob rows reach the loop in one of two ways (BLK; forward_ck chooses per lattice, see there):
+//   * row by row: one 256-byte load per frame, four rows in flight, each dropped into LDS (ds_write_b32) one frame ahead;
+//   * in blocks of four rows (ld == 64: rows 4b..4b+3 are one contiguous 1-KB run): one 16-byte load and one ds_write_b128
+//     per lane per FOUR frames, LDS as [2 buffers][4 rows][64], block b in buffer b & 1.  Block b+1 is written before frame
+//     4b+3 gathers the emissions of frame 4b+4 and block b+2 is requested right behind, into the same four registers.  The
+//     loop is unrolled by eight frames, so buffer and row of every gather are the immediate offset of its ds_read_b32.
+//     Lane 16 r of a block register's first component holds lp[4b+r, 0]: the four blank emissions are read (v_readlane)
+//     when the block is written.  The finiteness sum takes each lane's four components: every element of the lattice is
+//     in exactly one lane's sum, as before; rows past T-1 come back as zeros (block_reload).
 // ---------------------------------------------------------------------------------------
-template <int M, bool ZL>
-__device__ __forceinline__ void forward_ck(const Lattice &d, int32_t *meta)
+template <int M, bool ZL, bool BLK>
+__device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta, float *lrow)
 {
     constexpr int D = kRowDepth;
+    constexpr int U = BLK ? 2 * D : D;      // frames per trip of the loop
     const int lane = threadIdx.x;
     const uint32_t T = (uint32_t)__builtin_amdgcn_readfirstlane(d.T);
     const uint32_t L = (uint32_t)__builtin_amdgcn_readfirstlane(d.L);
@@ -269,7 +281,7 @@ __device__ __forceinline__ void forward_ck(const Lattice &d, int32_t *meta)
 #pragma unroll
     for (int k = 0; k < 16; ++k) KA_P(P, k) = NINF;
     if (lane == 0) KA_P(P, 0) = 0.0f;       // virtual state before frame 0 (align.py:57-58)
-    float absum = 0.0f;                     // sum over frames of |lp[t, lane]| (finiteness check)
+    float absum = 0.0f;                     // this lane's share of the sum of all |lp| (finiteness check)
 
     int blk = lane;                         // block of 16 positions this lane currently owns
     uint32_t blo = 0;                       // lo >> 4
@@ -288,55 +300,110 @@ __device__ __forceinline__ void forward_ck(const Lattice &d, int32_t *meta)
     const uint32_t lane_off = (lane < d.V ? (uint32_t)lane : 0u) * 4u;
     const char *lp = reinterpret_cast<const char *>(d.lp);
     const size_t ld = (size_t)d.ld * 4;  // row pitch in bytes
-    float rows[D];
+    const u32x4 lp_rsrc = lp_descriptor(d.lp, (uint64_t)T * ld);
+    [[maybe_unused]] float rows[D];         // row by row: rows t+1 .. t+D-1 and the request for row t+D
+    [[maybe_unused]] f32x4 rblk;            // blocks: block (t+1)/4 + 1, requested when block (t+1)/4 went to LDS
+    [[maybe_unused]] uint32_t blk_off = (uint32_t)lane * 16u;   // byte offset of this lane's part of the block that is requested next
+    f32x2 E[4];                             // emissions of the label cells (see frame_scores)
+    float e0[BLK ? 8 : 2];                  // blank emissions: of frame t and t+1 by frame parity; blocks: [buffer][row]
+    if constexpr (BLK) {
+        asm("" : "=v"(rblk));
+        block_reload(rblk, blk_off, lp_rsrc);
+        block_wait(rblk);
+        *reinterpret_cast<f32x4 *>(lrow + lane * 4) = rblk;
 #pragma unroll
-    for (int i = 0; i < D; ++i) {
-        const uint32_t tt = (uint32_t)i < T ? (uint32_t)i : T - 1;
-        rows[i] = row_load(lane_off, lp + (size_t)tt * ld);
+        for (int r = 0; r < 4; ++r) e0[r] = lane_of(rblk[0], 16 * r);
+        absum = __builtin_fabsf(rblk[0]) + __builtin_fabsf(rblk[1]) + __builtin_fabsf(rblk[2]) + __builtin_fabsf(rblk[3]);
+        blk_off += 1024u;
+        __builtin_amdgcn_sched_barrier(0);  // (see the loop)
+        block_reload(rblk, blk_off, lp_rsrc);
+        __builtin_amdgcn_sched_barrier(0);
+        blk_off += 1024u;
+    } else {
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            const uint32_t tt = (uint32_t)i < T ? (uint32_t)i : T - 1;
+            rows[i] = row_load(lane_off, lp + (size_t)tt * ld);
+        }
+#pragma unroll
+        for (int i = 0; i < D; ++i) row_wait<0>(rows[i]);
+        lrow[lane] = rows[0];
+        e0[0] = first_lane(rows[0]);
+        absum = __builtin_fabsf(rows[0]);
     }
 #pragma unroll
-    for (int i = 0; i < D; ++i) row_wait<0>(rows[i]);
-    f32x2 E[4];                             // emissions of the label cells (see frame_scores)
-    float e0[2];                            // blank emission, double-buffered by frame parity
-    __shared__ float lrow[64];              // row t+1 while frame t is computed (the workgroup is this one wavefront)
-    lrow[lane] = rows[0];
-#pragma unroll
     for (int i = 0; i < 8; ++i) E[i >> 1][i & 1] = lds_col(lrow, la[i]);
-    e0[0] = first_lane(rows[0]);
-    absum = __builtin_fabsf(rows[0]);
 
     const char *ckp = reinterpret_cast<const char *>(d.bp);
     // row min(t+D, T-1) of the current frame t, as a byte offset into the lattice's log-probs (forward_ck_kernel has made sure
     // that it fits 32 bits)
     const uint32_t ld32 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ld), last_row = (T - 1u) * ld32;
     uint32_t row_ahead = (D < T ? (uint32_t)D : T - 1u) * ld32;
-    const u32x4 lp_rsrc = lp_descriptor(d.lp, (uint64_t)T * ld);
     const uint32_t thr_real = dq != 0 ? 0u : T;   // floor(L*t/T) moves in this frame <=> rem + dr >= thr_real
     // static mask: frame 8k+7 when the ring has at least 8*(M-1) dead slots (7 unmasked frames leak 7*(M-1) cells and
-    // lo reads M-1 below itself), else frame 4k+3.  Checkpoints (frame 32k+31) are masked frames either way.
-    const uint32_t mask_every4 = 1024u - (B < L ? B : L) >= 8u * (M - 1) ? 0u : 4u;
+    // lo reads M-1 below itself), else frame 4k+3: a period of P = 8 or 4 frames.
+    const uint32_t P_static = 1024u - (B < L ? B : L) >= 8u * (M - 1) ? 8u : 4u;
+    // Every frame in which floor(L*t/T) moves masks too (the rare block below).  With dq >= 1 that is every frame.  With dq == 0
+    // the remainder grows by dr = L per frame and a move takes it back below T, so two moves - and frame 0 and the first move -
+    // are at most ceil(T/dr) frames apart: at most P-1 frames iff (P-1)*dr >= T.  Then at most P-1 frames run between two
+    // masks, which leaks no further than the static schedule's P frames do, and the static pass is kept only where something
+    // reads the masked ring: on checkpoint frames (32k+31) and after the last frame.
+    const bool steps_mask = dq != 0 || (uint64_t)(P_static - 1u) * dr >= T;
+    // frame 4k+3 runs the static pass <=> every bit of mask_bits is set in 4k: 4k+3 = 3 mod 4 (0), 7 mod 8 (4), 31 mod 32 (28)
+    const uint32_t mask_bits = steps_mask ? ((uint32_t)kCkFrames - 1u) & ~3u : (P_static - 1u) & ~3u;
     uint32_t thr = thr_real;                // 0 for one frame after a band step: that frame must come through the rare block
     asm("" : "+s"(thr));                    // (opaque: one s_cmp + s_cbranch per frame instead of a boolean expression)
     // halos of frame 0: lane 63's cells 13..15 of the initial state
     float h1 = wave_ror1(KA_P(P, 15)), h2 = wave_ror1(KA_P(P, 14)), h3 = wave_ror1(KA_P(P, 13));
-    for (uint32_t tb = 0; tb < T; tb += D) {
+    for (uint32_t t0 = 0; t0 < T; t0 += U) {
 #pragma unroll
-        for (int dd = 0; dd < D; ++dd) {
-            const uint32_t t = tb + dd;
+        for (int u = 0; u < U; ++u) {
+            const int dd = u % D;                    // frame of its group of four
+            const uint32_t tb = t0 + (u - dd);      // first frame of that group
+            const uint32_t t = t0 + u;
             if (t < T) {
-                // row t+1 (its emissions are gathered while frame t is computed): issued D-1 frames ago, D-2
-                // younger row loads behind it (checkpoint stores and label reloads only add younger operations)
-                row_wait<D - 2>(rows[(dd + 1) % D]);
-                const float rn = rows[(dd + 1) % D];
-                lrow[lane] = rn;                 // (LDS operations of a wave execute in order: the reads of row t are done)
-                e0[(dd + 1) & 1] = first_lane(rn);
-                absum += __builtin_fabsf(rn);
-                const float e0t = e0[dd & 1];
-                frame_scores<M, ZL, 3>(P, h1, h2, h3, E, vz, f32x2{e0t, e0t}, la, lrow);
-                // prefetch the row of frame t+D (the last row again once there is none: never consumed)
-                row_reload_buf(rows[dd], lane_off, lp_rsrc, row_ahead);
-                row_ahead = min(row_ahead + ld32, last_row);
-                if (dd == D - 1 && ((tb | mask_every4) & 4u) != 0) {
+                const float *next_row = lrow;        // where row t+1 lies while frame t is computed
+                float e0t;
+                if constexpr (BLK) {
+                    const int nu = (u + 1) % U;      // frame t+1: row nu % 4 of buffer nu / 4
+                    if (dd == D - 1) {
+                        // block (t+1)/4: requested four frames ago; no other request has been made since
+                        block_wait(rblk);
+                        *reinterpret_cast<f32x4 *>(lrow + (nu / 4) * 256 + lane * 4) = rblk;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) e0[(nu / 4) * 4 + r] = lane_of(rblk[0], 16 * r);
+                        absum += __builtin_fabsf(rblk[0]);
+                        absum += __builtin_fabsf(rblk[1]);
+                        absum += __builtin_fabsf(rblk[2]);
+                        absum += __builtin_fabsf(rblk[3]);
+                        asm volatile("" : "+v"(absum));   // (here, not sunk into a later block: that would be a reader behind the request)
+                        // the block after it, into the registers just freed (past the lattice's end: zeros, never consumed).
+                        // Nothing may move across the request: a reader of the block scheduled behind it makes the compiler
+                        // copy the four registers - before the wait, while their load is in flight (tools/lint_inflight.py)
+                        __builtin_amdgcn_sched_barrier(0);
+                        block_reload(rblk, blk_off, lp_rsrc);
+                        __builtin_amdgcn_sched_barrier(0);
+                        blk_off += 1024u;
+                    }
+                    next_row = lrow + (nu / 4) * 256 + (nu % 4) * 64;
+                    e0t = e0[u];
+                } else {
+                    // row t+1 (its emissions are gathered while frame t is computed): issued D-1 frames ago, D-2
+                    // younger row loads behind it (checkpoint stores and label reloads only add younger operations)
+                    row_wait<D - 2>(rows[(dd + 1) % D]);
+                    const float rn = rows[(dd + 1) % D];
+                    lrow[lane] = rn;                 // (LDS operations of a wave execute in order: the reads of row t are done)
+                    e0[(dd + 1) & 1] = first_lane(rn);
+                    absum += __builtin_fabsf(rn);
+                    e0t = e0[dd & 1];
+                }
+                frame_scores<M, ZL, 3>(P, h1, h2, h3, E, vz, f32x2{e0t, e0t}, la, next_row);
+                if constexpr (!BLK) {
+                    // prefetch the row of frame t+D (the last row again once there is none: never consumed)
+                    row_reload_buf(rows[dd], lane_off, lp_rsrc, row_ahead);
+                    row_ahead = min(row_ahead + ld32, last_row);
+                }
+                if (dd == D - 1 && (~tb & mask_bits) == 0) {
                     mask_scores<15>(P, mk, NINF);
                     if (((tb + D) & (kCkFrames - 1)) == 0 && tb + D < T) {
                         // checkpoint (tb+D)/kCkFrames: the scores after frame tb+D-1, [lane][16 cells], 4 KB.  Taken
@@ -361,7 +428,7 @@ __device__ __forceinline__ void forward_ck(const Lattice &d, int32_t *meta)
                 if (__builtin_expect(rem >= thr, 0)) {
                     asm volatile("" ::: "memory");  // a real branch: the common frame pays an add, a compare and a jump
                     thr = thr_real;
-                    if (dd != D - 1 || ((tb | mask_every4) & 4u) == 0) {
+                    if (dd != D - 1 || (~tb & mask_bits) != 0) {
                         mask_scores<15>(P, mk, NINF);
                         h1 = wave_ror1(KA_P(P, 15));
                         h2 = wave_ror1(KA_P(P, 14));
@@ -397,7 +464,7 @@ __device__ __forceinline__ void forward_ck(const Lattice &d, int32_t *meta)
                                 for (int k = 0; k < 16; ++k) KA_P(P, k) = reset_lane ? NINF : KA_P(P, k);
                                 // emissions of frame t+1 with the new labels (the cells gathered them with the old ones)
 #pragma unroll
-                                for (int i = 0; i < 8; ++i) E[i >> 1][i & 1] = lds_col(lrow, la[i]);
+                                for (int i = 0; i < 8; ++i) E[i >> 1][i & 1] = lds_col(next_row, la[i]);
                                 if constexpr (ZL) {
 #pragma unroll
                                     for (int i = 0; i < 8; ++i) vz[i] = la[i] == 0 ? NINF : __builtin_inff();
@@ -420,8 +487,13 @@ __device__ __forceinline__ void forward_ck(const Lattice &d, int32_t *meta)
             }
         }
     }
+    // drain the prefetches (see forward_w16)
+    if constexpr (BLK) {
+        block_wait(rblk);
+    } else {
 #pragma unroll
-    for (int i = 0; i < D; ++i) row_wait<0>(rows[i]);   // drain the prefetches (see forward_w16)
+        for (int i = 0; i < D; ++i) row_wait<0>(rows[i]);
+    }
 
     int32_t *m = meta_of(meta, d.idx);
     mask_scores<15>(P, mk, NINF);   // the last frame may have run unmasked
@@ -469,6 +541,20 @@ __device__ __forceinline__ void forward_ck(const Lattice &d, int32_t *meta)
         m[1] = best;
         m[3] = __builtin_bit_cast(int32_t, v);
     }
+}
+
+// The block path wants four consecutive rows to be one contiguous, 16-byte aligned kilobyte with no padding columns (the
+// finiteness sum reads every element of it), and its byte offsets - up to three rows and two blocks past the last row - to fit
+// 32 bits.  Everything else, the books' V = 39 lattices among it, goes row by row.  Wave-uniform, decided once per lattice.
+template <int M, bool ZL>
+__device__ __forceinline__ void forward_ck(const Lattice &d, int32_t *meta)
+{
+    __shared__ __attribute__((aligned(16))) float lrow[2 * 4 * 64];   // (the workgroup is this one wavefront)
+    const uint32_t base_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)reinterpret_cast<uint64_t>(d.lp));
+    const bool blocks = __builtin_amdgcn_readfirstlane(d.ld) == 64 && __builtin_amdgcn_readfirstlane(d.V) == 64 && (base_lo & 15u) == 0 &&
+                        (uint32_t)__builtin_amdgcn_readfirstlane(d.T) <= (0xffffffffu - 4096u) / 256u;
+    if (blocks) forward_ck_body<M, ZL, true>(d, meta, lrow);
+    else forward_ck_body<M, ZL, false>(d, meta, lrow);
 }
 
 constexpr int kFwdMinWaves = 4;   // __launch_bounds__ of the wave forward kernels: wavefronts per SIMD

@@ -107,7 +107,7 @@ def check(path):
             mv = VMEM.match(ln)
             if mv:
                 issued += 1
-                if mv.group(1) == "global_load":
+                if mv.group(1) in ("global_load", "buffer_load"):
                     dst = mv.group(2).split(",")[0]
                     for r in regs(dst):
                         if in_asm:
