@@ -144,6 +144,8 @@ __global__ __launch_bounds__(64) void backtrace_w16_kernel(const Lattice *__rest
 // [p-96, p+31]: whatever is wrong at the window's low edge (unknown neighbours) climbs 3 positions
 // per frame, exactly as fast as the path can fall.  64 lanes x (one blank + one label cell); same
 // float operations in the same order as the forward kernel, so the scores are bit-identical.
+// With max_move = 4 only the chunk's first kRcSplit frames run in that form; the others run one cell per lane on a second,
+// narrower window (rc_frame1 below: the walk reads a triangle of the chunk, not a rectangle).
 // The kernel also writes best_labels / best_scores: the chunk's log-prob rows are in registers
 // (lane v = lp[t, v]), so a score is one v_readlane - no second pass over the log-probs.
 // ---------------------------------------------------------------------------------------
@@ -245,6 +247,67 @@ __device__ __forceinline__ void rc_frame4(float &sb, float &sl, uint32_t &word, 
     else
         asm volatile(KA_RC_HEAD KA_RC_MAX KA_RC_CODES KA_RC_BAND : KA_RC_OUTS : KA_RC_INS : "memory", "scc");
 }
+// ---- the chunk's upper frames: ONE cell per lane ----
+// The walk reads a triangle of the chunk, not a rectangle: at chunk frame f the path lies in [p - 3(31-f), p].  From frame
+// kRcSplit on, the recurrence therefore runs on a second, narrower window: lane i owns position w2 + i (w2 even: even lanes are
+// blanks), kRc1Lanes = 61 live lanes, p - w2 = 59 or 60 (w2 = 0 while p < 60).
+// Why that is exact.  Cells below a window are unknown, and an unknown cell spoils only cells above it, 3 positions further per
+// frame (a cell depends on the 3 positions below it).  After frame f of phase 1 the positions >= wlo + 3(f+1) are exact (the
+// argument at the head of this section).  Phase 2 adds the unknowns below w2, so after frame f >= kRcSplit the positions
+//     >= max(wlo + 3 kRcSplit, w2) + 3(f - kRcSplit + 1)
+// are exact.  The walk reads frame f on [p - 3(31-f), p]; with wlo <= p - 96 (or wlo = 0: nothing unknown below it) that is
+// covered for every f iff  w2 <= p - 96 + 3 kRcSplit  (or w2 = 0), and the window reaches p iff p - w2 <= kRc1Lanes - 1.  With
+// p - w2 >= 59 the first asks for 3 kRcSplit >= 96 - 59, i.e. kRcSplit >= 13.  (tests/test_rc_split_cpu.py runs this arithmetic
+// in NumPy against a full DP, with anything from -inf to 1e30 below both windows.)
+constexpr int kRcSplit = 16;     // first frame of a chunk in the one-cell form
+constexpr int kRc1Lanes = 61;    // live lanes of the one-cell window; lanes 61 .. 63 are the "nothing below position 0" of lanes 0 .. 2
+constexpr int kRc1Back = 59;     // p - w2 is kRc1Back or kRc1Back + 1 (w2 even)
+static_assert(kRc1Back >= 96 - 3 * kRcSplit, "one-cell window starts above what phase 1 and phase 2 leave exact: split too early");
+static_assert(kRc1Back + 1 <= kRc1Lanes - 1 && kRc1Lanes + 3 <= 64, "one-cell window does not reach p, or leaves no idle lanes below lane 0");
+static_assert(kRcSplit >= 1 && kRcSplit < kCkFrames, "both phases have frames");
+// second window of a chunk entered at p
+__device__ __forceinline__ int rc_window1(int p) { return p > kRc1Back ? (p - kRc1Back) & ~1 : 0; }
+// One frame of it, 14 vector instructions (15 with the band select): the score is ONE register s, its three neighbours come from a
+// chain of wave_ror:1 (two v_mov_dpp, and every add takes its neighbour through DPP), the emission is gathered per lane - a blank
+// lane's lab1 is 0, so it gathers column 0 - and a blank is a label cell whose move 2 is vetoed: the per-lane addend vadd is -inf on
+// blank lanes (and on label-0 lanes of the ZL instance), -0.0 elsewhere; e + (-0.0) is e bit for bit, so c2 is the forward kernel's
+// sum or -inf.  The code is cell_label<4>'s (for a blank: e2 only when everything is -inf, and then e0 too - the same move 0 as
+// rc_blank_to_uniform makes of (e0, e1)).  2 bits per frame go into `word`.
+// DPP hazard (2 wait states after the VALU write of a DPP source): s is written by the previous block's v_max / v_cndmask, at least
+// s_waitcnt, ds_bpermute and v_add before the first DPP read; r1 and r2 are each read two instructions after they are written.
+#define KA_RC1_BLOCK                                                                      \
+    "ds_bpermute_b32 %[en], %[lab1], %[rown]\n\t"                                         \
+    "v_add_f32 %[c0], %[s], %[e]\n\t"                                                     \
+    "v_mov_b32_dpp %[r1], %[s] wave_ror:1 row_mask:0xf bank_mask:0xf\n\t"                 \
+    "v_add_f32_dpp %[c1], %[s], %[e] wave_ror:1 row_mask:0xf bank_mask:0xf\n\t"           \
+    "v_add_f32 %[ev], %[e], %[vadd]\n\t"                                                  \
+    "v_mov_b32_dpp %[r2], %[r1] wave_ror:1 row_mask:0xf bank_mask:0xf\n\t"                \
+    "v_add_f32_dpp %[c2], %[r1], %[ev] wave_ror:1 row_mask:0xf bank_mask:0xf\n\t"         \
+    "v_max3_f32 %[m], %[c0], %[c1], %[c2]\n\t"                                            \
+    "v_add_f32_dpp %[c3], %[r2], %[e] wave_ror:1 row_mask:0xf bank_mask:0xf\n\t"          \
+    "v_max_f32 %[s], %[m], %[c3]\n\t"                                                     \
+    "v_cmp_eq_f32 %[sa], %[c0], %[s]\n\t"                                                 \
+    "v_cmp_eq_f32 %[sb2], %[c1], %[s]\n\t"                                                \
+    "v_cmp_eq_f32 %[sc], %[c2], %[s]\n\t"                                                 \
+    KA_RC_COMBINE                                                                         \
+    "s_bitcmp1_b32 %[open], 0\n\t"                                                        \
+    "s_cbranch_scc1 .Lka_rc1_open_%=\n\t"                                                 \
+    "v_cndmask_b32 %[s], %[ninf], %[s], %[mk]\n"                                          \
+    ".Lka_rc1_open_%=:\n\t"                                                               \
+    "s_waitcnt lgkmcnt(0)"
+__device__ __forceinline__ void rc_frame1(float &s, uint32_t &word, float e, float &e_next, float row_next, int lab1, float vadd,
+                                          uint32_t open, uint64_t mask, float NINF)
+{
+    float c0, c1, c2, c3, r1, r2, ev, m;
+    uint64_t sa, sb2, sc, sx, sy;
+    asm volatile(KA_RC1_BLOCK
+                 : [s] "+v"(s), [w] "+v"(word), [en] "=&v"(e_next), [c0] "=&v"(c0), [c1] "=&v"(c1), [c2] "=&v"(c2), [c3] "=&v"(c3),
+                   [r1] "=&v"(r1), [r2] "=&v"(r2), [ev] "=&v"(ev), [m] "=&v"(m), [sa] "=&s"(sa), [sb2] "=&s"(sb2), [sc] "=&s"(sc),
+                   [sx] "=&s"(sx), [sy] "=&s"(sy)
+                 : [e] "v"(e), [rown] "v"(row_next), [lab1] "v"(lab1), [vadd] "v"(vadd), [open] "s"(open), [mk] "s"(mask), [ninf] "v"(NINF)
+                 : "memory", "scc");
+}
+#undef KA_RC1_BLOCK
 #undef KA_RC_HEAD
 #undef KA_RC_GATHER
 #undef KA_RC_E0_OUT
@@ -276,13 +339,50 @@ constexpr int kRcLanes = 62;   // lanes 62 and 63 are kept at -inf: they are the
 //     register (lane v = lp[t0+f, v]) at the label kept in a scalar register, and a v_writelane.
 // FULL: all 32 frames, straight line.  Otherwise frames f >= n (past T-1, last chunk only) are left out: no moves, and
 // their lanes' results are not stored.
-template <bool FULL>
-__device__ __forceinline__ void rc_walk_out(const uint32_t (&codes)[kCkFrames / 8], const float (&rows)[kCkFrames], int lab4, int n,
-                                            int lane, int &qq, int &pathv, int &labv, float &scv)
+// SPLIT < 32: frames SPLIT .. 31 were recomputed one cell per lane (rc_frame1) on the window that starts d2 positions above
+// the first: there the path's lane is qq - d2, EVERY move is a lane change, a frame has 2 code bits (frame f in bit pair
+// 15 - (f-SPLIT)%16 of codes2[(f-SPLIT)/16], coded 3 - move already) and the label comes from lab1 (4 * label on odd lanes,
+// 0 on blanks).  Below SPLIT the walk is on the two-cell window as before; it reads that window's words and label at its lane
+// once when it gets there.  A last chunk of n <= SPLIT frames is walked in the first window only.
+template <bool FULL, int SPLIT>
+__device__ __forceinline__ void rc_walk_out(const uint32_t (&codes)[kCkFrames / 8], const uint32_t (&codes2)[2], const float (&rows)[kCkFrames],
+                                            int lab4, int lab1, int d2, int n, int lane, int &qq, int &pathv, int &labv, float &scv)
 {
-    constexpr int G = kCkFrames / 8;
+    constexpr int G = (SPLIT + 7) / 8;
+    constexpr int G2 = (kCkFrames - SPLIT + 15) / 16;
     static_assert(kCkFrames == 32, "one bit per frame in a 32-bit move mask");
+    static_assert(G2 <= 2, "two words of second-phase codes at the most");
     const int q_in = qq;
+    uint32_t mlo = 0, mhi = 0;
+    if constexpr (SPLIT < kCkFrames) {
+        if (FULL || n > SPLIT) {
+            int l2 = qq - d2;
+            uint32_t cw2[G2 > 0 ? G2 : 1];
+#pragma unroll
+            for (int g = 0; g < G2; ++g) cw2[g] = (uint32_t)__builtin_amdgcn_readlane((int)codes2[g], l2);
+            int col2 = __builtin_amdgcn_readlane(lab1, l2) >> 2;
+#pragma unroll
+            for (int f = kCkFrames - 1; f >= SPLIT; --f) {
+                if (FULL || f < n) {
+                    const int k = f - SPLIT;
+                    const int sc = __builtin_amdgcn_readlane(__builtin_bit_cast(int, rows[f]), col2);
+                    asm("v_writelane_b32 %0, %1, %2" : "+v"(scv) : "s"(sc), "i"(f));
+                    const uint32_t mv = (uint32_t)bp_decode(cw2[k >> 4] >> (2 * (15 - (k & 15))));
+                    if (mv != 0) {
+                        qq -= (int)mv;
+                        mlo |= (mv & 1u) << f;
+                        mhi |= (mv >> 1) << f;
+                        if (k > 0) {                     // (what follows serves the frames below, down to SPLIT)
+                            l2 = qq - d2;
+#pragma unroll
+                            for (int g = 0; g <= (k - 1) >> 4; ++g) cw2[g] = (uint32_t)__builtin_amdgcn_readlane((int)codes2[g], l2);
+                            col2 = __builtin_amdgcn_readlane(lab1, l2) >> 2;
+                        }
+                    }
+                }
+            }
+        }
+    }
     int j = qq >> 1;
     uint32_t cw[G];                                  // codes[g] at lane j
 #pragma unroll
@@ -290,9 +390,8 @@ __device__ __forceinline__ void rc_walk_out(const uint32_t (&codes)[kCkFrames / 
     int cl = __builtin_amdgcn_readlane(lab4, j);     // lab4 at lane j
     int col = (qq & 1) ? cl >> 2 : 0;                // label of the path's cell
     uint32_t par = (qq & 1) ? 0u : 2u;               // where the cell's code sits in its nibble
-    uint32_t mlo = 0, mhi = 0;
 #pragma unroll
-    for (int f = kCkFrames - 1; f >= 0; --f) {
+    for (int f = SPLIT - 1; f >= 0; --f) {
         if (FULL || f < n) {
             const int sc = __builtin_amdgcn_readlane(__builtin_bit_cast(int, rows[f]), col);
             asm("v_writelane_b32 %0, %1, %2" : "+v"(scv) : "s"(sc), "i"(f));
@@ -419,6 +518,11 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
         }
         // ---- forward over the chunk: scores + back-pointer codes of the window ----
         uint32_t codes[kCkFrames / 8] = {};
+        // max_move = 4: frames kRcSplit .. 31 run one cell per lane on the window [w2, w2 + 60] (rc_frame1), 2 code bits each
+        constexpr int SPLIT = M == 4 ? kRcSplit : kCkFrames;
+        uint32_t codes2[2] = {};
+        const int w2 = __builtin_amdgcn_readfirstlane(rc_window1(p));
+        int lab1 = 0;                                        // 4 * label of position w2 + lane (0 on the even lanes: blanks)
         // floor(L*(t0+f)/T) of all frames of the chunk at once, lane f <-> frame f (r0 + 33*dr < 34*T: the host
         // keeps T below 2^26 in this form), and the frames after which it moves as a bit mask: the common frame
         // then pays one s_bitcmp1 + s_cbranch for the band instead of a scalar Bresenham step
@@ -449,6 +553,21 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
             const uint32_t xb = (uint32_t)(x + 1) >> 1, yb = (uint32_t)(y + 1) >> 1, xl = (uint32_t)x >> 1, yl = (uint32_t)y >> 1;
             mask_b = lane_field(yb - xb, xb);
             mask_l = lane_field(yl - xl, xl);
+        };
+        // the same for the one-cell window: position w2 + l in band and l < kRc1Lanes <=> l in [x, y) - ONE mask
+        uint64_t mask_1 = 0;
+        const auto band_mask1 = [&](int f) {
+            const uint32_t q = (uint32_t)__builtin_amdgcn_readlane((int)qa, f);
+            const int32_t dl = (int32_t)q - (int32_t)halfB;
+            const int32_t lo = dl > 0 ? dl : 0;
+            const int32_t hi = (L - (uint32_t)lo < B) ? (int32_t)L : lo + (int32_t)B;
+            int32_t x = lo - w2, y = hi - w2;
+            x = x < 0 ? 0 : x;
+            y = y < 0 ? 0 : y;
+            asm("" : "+s"(x), "+s"(y));
+            x = x > kRc1Lanes ? kRc1Lanes : x;
+            y = y > kRc1Lanes ? kRc1Lanes : y;
+            mask_1 = lane_field((uint32_t)(y - x), (uint32_t)x);
         };
         if constexpr (M == 4) {
             // Does the band cut into the cells the walk can reach, [wlo, p], at any frame t0-1 .. t0+31?  The band only
@@ -484,20 +603,46 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
                 sl = ckv.y;
             } else {
                 const uint32_t qb = q0 + (uint32_t)(lane + 1) * dq + div_T(qnum + dr);
-                moves = (uint32_t)__builtin_amdgcn_ballot_w64(qa != qb) << 1 | 1u;   // bit f: frame f's band differs from frame f-1's (bit 0: set it up)
+                // bit f: frame f's band differs from frame f-1's (bit 0: set it up; bit kRcSplit: set the one-cell window's up)
+                moves = (uint32_t)__builtin_amdgcn_ballot_w64(qa != qb) << 1 | 1u | (1u << kRcSplit);
             }
             asm volatile("s_nop 1" : "+v"(sb), "+v"(sl));   // (a DPP read follows within the next block)
-            // ONE loop for both kinds of chunk: the row registers are waited for in one place per frame whichever way the
-            // chunk goes (two loops made hipcc copy rows whose loads were in flight)
+            float s1 = NINF, vadd = NINF, e1c = NINF, e1n;
+            // ONE loop for both kinds of chunk and both phases: the row registers are waited for in one place per frame
+            // whichever way the chunk goes (two loops made hipcc copy rows whose loads were in flight)
 #pragma unroll
             for (int f = 0; f < kCkFrames; ++f) {
-                if ((moves >> f) & 1u) band_masks(f);
+                if (f < kRcSplit) {
+                    if ((moves >> f) & 1u) band_masks(f);
+                    if (f + 1 < kCkFrames) row_wait_n(rows[f + 1], kCkFrames - 2 - f);
+                    rc_frame4<ZL>(sb, sl, codes[f >> 3], e0c, elc, e0n, eln, rows[f + 1 < kCkFrames ? f + 1 : f], lab4, zero, veto,
+                                  open_bit, mask_b, mask_l, NINF);
+                    e0c = e0n;
+                    elc = eln;
+                    continue;
+                }
+                if (f == kRcSplit) {
+                    // relayout, once per chunk: lane i takes position w2 + i, the cell of its own parity (w2 - wlo is even) of
+                    // lane (w2 - wlo + i) / 2 < 64; lanes 61 .. 63 start at -inf (a masked chunk keeps them there)
+                    const int src4 = ((lane + (w2 - wlo)) >> 1) << 2;
+                    const bool odd = (lane & 1) != 0;
+                    const float xb = bperm(src4, sb), xl = bperm(src4, sl);
+                    const int l4 = __builtin_amdgcn_ds_bpermute(src4, lab4);
+                    s1 = lane < kRc1Lanes ? (odd ? xl : xb) : NINF;
+                    lab1 = odd ? l4 : 0;
+                    vadd = (!odd || (ZL && l4 == 0)) ? NINF : -0.0f;
+                    asm volatile("ds_bpermute_b32 %0, %1, %2\n\t"
+                                 "s_waitcnt lgkmcnt(0)"
+                                 : "=&v"(e1c) : "v"(lab1), "v"(rows[kRcSplit]), "v"(s1) : "memory");
+                }
+                if ((moves >> f) & 1u) band_mask1(f);
                 if (f + 1 < kCkFrames) row_wait_n(rows[f + 1], kCkFrames - 2 - f);
-                rc_frame4<ZL>(sb, sl, codes[f >> 3], e0c, elc, e0n, eln, rows[f + 1 < kCkFrames ? f + 1 : f], lab4, zero, veto,
-                              open_bit, mask_b, mask_l, NINF);
-                e0c = e0n;
-                elc = eln;
+                rc_frame1(s1, codes2[(f - kRcSplit) >> 4], e1c, e1n, rows[f + 1 < kCkFrames ? f + 1 : f], lab1, vadd, open_bit, mask_1, NINF);
+                e1c = e1n;
             }
+            // partly filled words: their first frame to the top, as in a full word
+            if constexpr (kRcSplit % 8 != 0) codes[kRcSplit / 8] <<= 4 * (8 - kRcSplit % 8);
+            if constexpr ((kCkFrames - kRcSplit) % 16 != 0) codes2[(kCkFrames - kRcSplit) / 16] <<= 2 * (16 - (kCkFrames - kRcSplit) % 16);
         } else {
             const uint32_t qb = q0 + (uint32_t)(lane + 1) * dq + div_T(qnum + dr);
             const uint32_t moves = (uint32_t)__builtin_amdgcn_ballot_w64(qa != qb);
@@ -521,7 +666,7 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
         }
         // ---- walk back over the chunk: pathv[lane f] = position of frame t0+f, relative to wlo ----
 #pragma unroll
-        for (int g = 0; g < kCkFrames / 8; ++g) codes[g] = rc_blank_to_uniform(codes[g]);
+        for (int g = 0; g < (SPLIT + 7) / 8; ++g) codes[g] = rc_blank_to_uniform(codes[g]);
         int pathv = 0;
         int qq = p - wlo;
         // best_path, best_labels = lab'[best_path], best_scores[t] = lp[t, best_labels[t]] (align.py:105-107), lane f
@@ -529,9 +674,9 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
         int labv = 0;
         float scv = 0.0f;
         if (n == kCkFrames)
-            rc_walk_out<true>(codes, rows, lab4, n, lane, qq, pathv, labv, scv);
+            rc_walk_out<true, SPLIT>(codes, codes2, rows, lab4, lab1, w2 - wlo, n, lane, qq, pathv, labv, scv);
         else
-            rc_walk_out<false>(codes, rows, lab4, n, lane, qq, pathv, labv, scv);
+            rc_walk_out<false, SPLIT>(codes, codes2, rows, lab4, lab1, w2 - wlo, n, lane, qq, pathv, labv, scv);
         if (lane < n) {
             path[t0 + lane] = pathv + wlo;
             lab_out[t0 + lane] = labv;
