@@ -12,7 +12,8 @@ Where the work runs:
   * the MFCCs of ALL segments of a recording are computed together: HIP kernels for framing + window
     (``ka_stft_frames_f32``), |X|^2 (``ka_power_f32``) and the per-segment dB conversion with its top_db floor
     (``ka_power_to_db_f32``), library GEMMs (PyTorch-ROCm) for the three contractions: frames x DFT basis
-    [512, 514], power x mel filters [257, 40], dB x DCT [40, 40].  Float32 like the reference's transform.
+    [512, 514], power x mel filters [257, 40], dB x DCT [40, 40].  Float32 like the reference's transform, except the DCT:
+    float64 over the 40 float32 levels, rounded to float32 once.
 There is no CPU path: without the HIP library / a GPU these functions raise.
 
 Audio decoding is not part of this package: ``split_audio`` takes 16-bit PCM ``.wav`` (standard library) or ``.npy``
@@ -186,6 +187,10 @@ def _merge_short_pieces(points, num_frames, minimum_split_distance):
 # MFCC of all segments at once
 # ----------------------------------------------------------------------------------------
 _CONST = {}
+# a slab of mfcc_segments: whole segments, at most this many frame rows (unless one segment alone has more) and this many
+# segments (gridDim.y of the per-segment kernels); read at call time
+_SLAB_ROWS = 1 << 21
+_SLAB_SEGMENTS = 65535
 
 
 def _constants(device, sample_rate, n_mfcc, n_mels, n_fft):
@@ -194,7 +199,7 @@ def _constants(device, sample_rate, n_mfcc, n_mels, n_fft):
     if key not in _CONST:
         f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)   # noqa: E731
         _CONST[key] = (f32(_hann_periodic(n_fft)), f32(_dft_basis(n_fft)), f32(_mel_filterbank(n_fft // 2 + 1, n_mels, sample_rate)),
-                       f32(_dct_ortho(n_mfcc, n_mels)))
+                       torch.from_numpy(np.ascontiguousarray(_dct_ortho(n_mfcc, n_mels))).to(device))     # float64, see mfcc_segments
     return _CONST[key]
 
 
@@ -228,11 +233,11 @@ def mfcc_segments(y, ends, sample_rate=22050, n_mfcc=40, n_mels=40, n_fft=512, t
     nf = n_fft // 2 + 1
     out = torch.empty((total, n_mfcc), dtype=torch.float32, device=dev)
     # in slabs of whole segments, so that the [frames, 514] transform of a long recording stays a few GB
-    max_rows = 1 << 21
+    max_rows, max_segments = _SLAB_ROWS, _SLAB_SEGMENTS
     s0 = 0
     while s0 < len(ends):
         s1 = s0 + 1
-        while s1 < len(ends) and foff[s1 + 1] - foff[s0] <= max_rows and s1 - s0 < 65535:
+        while s1 < len(ends) and foff[s1 + 1] - foff[s0] <= max_rows and s1 - s0 < max_segments:
             s1 += 1
         r0, r1 = int(foff[s0]), int(foff[s1])
         n = r1 - r0
@@ -251,7 +256,9 @@ def mfcc_segments(y, ends, sample_rate=22050, n_mfcc=40, n_mels=40, n_fft=512, t
         segmax = torch.full((s1 - s0,), float("-inf"), dtype=torch.float32, device=dev)
         _lib.check(lib.ka_power_to_db_f32(mel.data_ptr(), mel.stride(0), n_mels, rel.data_ptr(), s1 - s0, int(nfr[s0:s1].max()),
                                           float(top_db), segmax.data_ptr(), stream), "ka_power_to_db_f32")
-        torch.mm(mel, dct, out=out[r0:r1])
+        # the DCT in float64, rounded to float32 once: coefficient 0 of a segment at -60 dB is about 0.158 * 40 * -70 = -440,
+        # where a float32 ulp is 3e-5, and a 40-term float32 sum there misses the 1e-4 the MFCCs are held to
+        out[r0:r1] = torch.mm(mel.double(), dct)
         s0 = s1
     return out, foff[1:].copy()
 
