@@ -453,6 +453,55 @@ size_t ka_tracking_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S
                                    int32_t mem);
 
 /*
+ * Best-path margins from max-marginals: how much score the best alignment would lose if, at frame t, it had to be somewhere
+ * else.  The best path's own recurrence in max-plus arithmetic, run forwards (D) and backwards (E): adds and compares only, no
+ * transcendental, float64 throughout, so every output is defined bit for bit by IEEE add and max.
+ *
+ * The lattice is that of ka_ctc_best_path_banded: lab' the blank-expanded labels, L = 2S+1; lo_t = band_lo[t], or the
+ * reference's diagonal max(0, L t / T - beam_size / 2) when the table argument is NULL; hi_t = min(lo_t + beam_size, L); moves
+ * j in [0, max_move); the veto: j even, j >= 2, target label == 0 is not a move; before frame 0 the virtual state is {0: 0.0};
+ * the terminal is s* = path[T-1], as ka_ctc_path_posteriors takes it.  All values are float64, each log-prob is widened
+ * exactly, each + is one IEEE double add, absent and vetoed candidates are -inf.
+ *
+ *   D_t(p) = max over j of ( D_{t-1}(p-j) + lp[t, lab'[p]] )         p in [lo_t, hi_t), p-j in band t-1, veto on lab'[p]
+ *   E_{T-1} = {s*: 0.0};
+ *   E_t(p) = max over j of ( E_{t+1}(p+j) + lp[t+1, lab'[p+j]] )     p+j in band t+1, veto on lab'[p+j]
+ *   m_t(p) = D_t(p) + E_t(p)
+ *   score      = D_{T-1}(s*)                                          (host double, per lattice)
+ *   through[t] = m_t(path[t]) if path[t] in [lo_t, hi_t) else -inf
+ *   alt[t]     = max of m_t(p) over p in [lo_t, hi_t) with (p >> unit) != (path[t] >> unit);  -inf if there is none
+ *   runner_up[t] = the LOWEST p attaining alt[t];  -1 where alt[t] is -inf
+ *
+ * unit is 0 (another state) or 1 (another text index p / 2, which is what align() reads off the path at a segment's ends).
+ * The path is input only: any values in [0, L) are legal, it need not be connected and need not be a best path; then
+ * through[t] - alt[t] is signed and says how much better the best path through the caller's state is than the best path that
+ * avoids it.  (Rounding is monotone: max_j(D_{t-1}(p-j)) + lp has the bits of the maximum of the sums.)
+ *
+ * log_probs, labels, band_lo, path, through, alt and runner_up lie where `mem` says; band_lo [T] int32 may be NULL (the batch
+ * call: the array may be NULL, every lattice on the diagonal, or hold NULL entries), runner_up may be NULL (likewise), score
+ * (a host double per lattice) and status (host) may be NULL.  Statuses are the family's, per lattice: KA_ERR_BAD_LABEL;
+ * KA_ERR_NAN / KA_ERR_NONFINITE for a NaN / +inf among the log-probs (-inf is legal); KA_ERR_BAD_ARGS for a path value outside
+ * [0, L) or an invalid table (checked on the device before use), for that lattice alone; KA_ERR_ZERO_MASS where score is -inf.
+ * A failed lattice gets NaN over [0, T) of through and alt, -1 over runner_up and a NaN score (-inf for KA_ERR_ZERO_MASS).
+ * unit outside {0, 1} is KA_ERR_BAD_ARGS before anything is launched or written.  The batch call returns the first failed
+ * lattice's status.  The call synchronises `stream`; the engine's mode and backtrace settings do not apply.
+ * Forms: one wavefront per lattice (band <= 1009, V <= 64, max_move <= 4), else a 256-thread workgroup (max_move <= 255).
+ * Cost (MI355X, cfg2: T = 50 000, S = 5000, beam 1000, V = 64): one lattice 564 ms, 0.32 x the
+ * label-posterior call and 17.0 x ka_ctc_best_path_banded_batch_f32; 1024 lattices in one call 623 ms, 0.29 x and 17.1 x.
+ * ka_path_margin_workspace_bytes: the engine workspace a call of these shapes needs (0 for unsupported shapes); after
+ * ka_engine_reserve of that figure the call allocates nothing.
+ */
+int ka_ctc_path_margins_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                            int32_t beam_size, int32_t max_move, const int32_t *band_lo, const int32_t *path, int32_t unit, double *through,
+                            double *alt, int32_t *runner_up, double *score, int32_t mem, void *stream);
+int ka_ctc_path_margins_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                  const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                  const int32_t *const *band_lo, const int32_t *const *path, int32_t unit, double *const *through,
+                                  double *const *alt, int32_t *const *runner_up, double *score, int32_t *status, int32_t mem, void *stream);
+size_t ka_path_margin_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                      int32_t mem);
+
+/*
  * Forward-backward posteriors over a caller-given band: ka_ctc_path_posteriors, ka_ctc_label_posteriors,
  * ka_ctc_state_posteriors and ka_ctc_state_durations on the band of ka_ctc_best_path_banded instead of the reference's
  * diagonal, so that a path found under a table can be judged under the same table.  Each call is its sibling with one

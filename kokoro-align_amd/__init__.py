@@ -19,7 +19,9 @@ alignment with the most frames at the right state in expectation (ctc_mea_path[_
 segment_path_disagreement), and the probability that the path passes through every phoneme at all, the soft form of the
 reference's keep-or-drop test of a segment (ctc_state_visits[_batch|_device], phoneme_visits, phoneme_spans,
 segment_expected_match), and the exact quantiles of every boundary's frame, the interval a cut lies in with a given probability
-(ctc_boundary_quantiles[_batch|_device], boundary_cuts, segment_boundary_interval).
+(ctc_boundary_quantiles[_batch|_device], boundary_cuts, segment_boundary_interval), and on the best-path side the per-frame
+margin of a path over the best alignment that disagrees with it, from max-marginals in exact float64 max-plus arithmetic
+(ctc_path_margins[_batch|_device], segment_boundary_margin, segment_min_margin).
 
 The DP and backtrace run in the HIP C-ABI library (include/kokoro_align_amd.h); there is no
 CPU fallback — importing works without a GPU, computing does not.
@@ -56,6 +58,9 @@ from .posteriors import (  # noqa: F401
     ctc_mea_path,
     ctc_mea_path_batch,
     ctc_mea_path_device,
+    ctc_path_margins,
+    ctc_path_margins_batch,
+    ctc_path_margins_device,
     ctc_path_posteriors,
     ctc_path_posteriors_batch,
     ctc_path_posteriors_device,
@@ -81,10 +86,12 @@ from .posteriors import (  # noqa: F401
     segment_agreement,
     segment_boundary_confidence,
     segment_boundary_interval,
+    segment_boundary_margin,
     segment_boundary_shift,
     segment_boundary_spread,
     segment_confidence,
     segment_expected_match,
+    segment_min_margin,
     segment_path_disagreement,
 )
 from ._lib import KAError, build_library, library_path, load_library  # noqa: F401

@@ -2,7 +2,8 @@
 // (ka_occupancy.hpp), state posteriors at chosen frames (ka_state_posterior.hpp), expected state durations (ka_duration.hpp),
 // state visit probabilities (ka_visit.hpp), exact boundary-time quantiles (ka_quantile.hpp), alignments sampled from the band
 // posterior (ka_sample.hpp) and the maximum-expected-accuracy alignment (ka_mea.hpp); and, with a driver of its own
-// (banded_impl), the best path over a caller-given band (ka_banded.hpp).  The first four also run over a caller-given band
+// (banded_impl), the best path over a caller-given band (ka_banded.hpp); and, through fb_impl again, the best-path margins
+// from max-marginals (ka_margin.hpp), which are max-plus and no forward-backward.  The first four also run over a caller-given band
 // (ka_ctc_*_banded_*: fb_impl<Call, ka::BandTable>, the same driver on Banded<Desc> descriptors).  Host code only.
 // They use the engine's workspace and pinned buffer, with their own kernels and workspace layout, whatever
 // the engine's mode, and run to the end inside the call: no batch stays in flight.
@@ -439,6 +440,65 @@ struct MeaCall {
     int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
     {
         KA_HIP(hipMemcpyAsync(path[i], ws + c.path, (size_t)a.T[i] * 4, hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
+// The best-path margins (ka_margin.hpp): fb_impl on the diagonal's descriptors, with the table a field the call fills itself,
+// since one batch mixes lattices that bring a table with lattices that do not.  The score rides in PostResult::log_likelihood.
+struct MarginCall {
+    using Desc = ka::MarginLattice;
+    static constexpr size_t kBandedGranule = ka::kBandedDescBytes;   // (never carved: no Banded<> sibling)
+    using Carve = ka::plan::MarginCarve;
+    static constexpr const char *kName = "path margins";
+    static constexpr const char *kBadArgs = ": a path value outside [0, 2S+1), or band_lo does not hold non-decreasing values in [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score reaches the path's last state";
+    const int32_t *const *band_lo;   // NULL, or an array in which any entry may be NULL: that lattice runs on the diagonal
+    const int32_t *const *path;
+    int32_t unit;
+    double *const *through;
+    double *const *alt;
+    int32_t *const *runner_up;       // NULL, or an array in which any entry may be NULL
+
+    bool arrays() const { return path && through && alt; }
+    const char *bad_lattice(const FbArgs &, int32_t) const { return nullptr; }
+    bool buffers(int32_t i) const { return path[i] && through[i] && alt[i]; }
+    const int32_t *table(int32_t i) const { return band_lo ? band_lo[i] : nullptr; }
+    int32_t *runner(int32_t i) const { return runner_up ? runner_up[i] : nullptr; }
+    static constexpr auto plan = ka::plan::path_margin_workspace;
+    template <class Band>
+    static constexpr auto launch = ka::launch_path_margins;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (a.mem == KA_MEM_HOST) {
+            d.band_lo = table(i) ? reinterpret_cast<const int32_t *>(ws + c.tab) : nullptr;
+            d.path = reinterpret_cast<const int32_t *>(ws + c.path);
+            d.through = reinterpret_cast<double *>(ws + c.through);
+            d.alt = reinterpret_cast<double *>(ws + c.alt);
+            d.runner = runner(i) ? reinterpret_cast<int32_t *>(ws + c.runner) : nullptr;
+        } else {
+            d.band_lo = table(i);
+            d.path = path[i];
+            d.through = through[i];
+            d.alt = alt[i];
+            d.runner = runner(i);
+        }
+        d.unit = unit;
+        fill_slot(d, c, -1, ws);
+    }
+    int upload(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        KA_HIP(hipMemcpyAsync(ws + c.path, path[i], (size_t)a.T[i] * 4, hipMemcpyHostToDevice, a.stream));
+        if (table(i)) KA_HIP(hipMemcpyAsync(ws + c.tab, table(i), (size_t)a.T[i] * 4, hipMemcpyHostToDevice, a.stream));
+        return KA_OK;
+    }
+    int stage(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        const size_t T = (size_t)a.T[i];
+        KA_HIP(hipMemcpyAsync(through[i], ws + c.through, T * sizeof(double), hipMemcpyDeviceToHost, a.stream));
+        KA_HIP(hipMemcpyAsync(alt[i], ws + c.alt, T * sizeof(double), hipMemcpyDeviceToHost, a.stream));
+        if (runner(i)) KA_HIP(hipMemcpyAsync(runner(i), ws + c.runner, T * 4, hipMemcpyDeviceToHost, a.stream));
         return KA_OK;
     }
 };
@@ -1112,6 +1172,32 @@ int ka_ctc_mea_path_banded_f32(ka_engine *e, const float *log_probs, int64_t T, 
                                double *expected_accuracy, double *log_likelihood, int32_t mem, void *stream)
 {
     return fb_impl<MeaCall, ka::BandTable>(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo}, MeaCall{&terminal, &path, expected_accuracy});
+}
+
+// ---- best-path margins from max-marginals (ka_margin.hpp) ----
+int ka_ctc_path_margins_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                  const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                  const int32_t *const *band_lo, const int32_t *const *path, int32_t unit, double *const *through,
+                                  double *const *alt, int32_t *const *runner_up, double *score, int32_t *status, int32_t mem, void *stream)
+{
+    if (unit != 0 && unit != 1) return fail(KA_ERR_BAD_ARGS, "path margins: unit must be 0 (state) or 1 (text index)");
+    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, score, status, mem, (hipStream_t)stream},
+                   MarginCall{band_lo, path, unit, through, alt, runner_up});
+}
+
+int ka_ctc_path_margins_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                            int32_t beam_size, int32_t max_move, const int32_t *band_lo, const int32_t *path, int32_t unit, double *through,
+                            double *alt, int32_t *runner_up, double *score, int32_t mem, void *stream)
+{
+    if (unit != 0 && unit != 1) return fail(KA_ERR_BAD_ARGS, "path margins: unit must be 0 (state) or 1 (text index)");
+    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, score, nullptr, mem, (hipStream_t)stream},
+                   MarginCall{&band_lo, &path, unit, &through, &alt, &runner_up});
+}
+
+size_t ka_path_margin_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::path_margin_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -1009,3 +1009,38 @@ inline size_t band_table_workspace(int32_t n, const int64_t *T, bool host_buffer
 
 }  // namespace plan
 }  // namespace ka
+
+namespace ka {
+namespace plan {
+
+// ---- ka_ctc_path_margins_batch_f32 (ka_margin.hpp): workspace layout ----
+// label_posterior_workspace's layout and slots (a slot's block offsets and V-wide global bins go unused) with MarginLattice
+// descriptors; for host buffers, beside the staged log-probs and labels, the staged path and table (T int32 each; the table's
+// room is carved whether or not the lattice brings one, so that the byte count depends on the shapes alone) and the staged
+// outputs (through and alt: T doubles each; runner_up: T int32).
+struct MarginCarve : SlotCarve {
+    size_t path, tab, through, alt, runner;   // host buffers only
+};
+inline size_t path_margin_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
+                                    MarginCarve *cv, size_t *off_res)
+{
+    return slot_workspace(n, sizeof(MarginLattice), T, S, V, beam, max_move, cv, off_res, [&](int32_t, const Shape &sh, MarginCarve &c, size_t &off) {
+        if (host_buffers) {
+            carve_staged(off, sh, V, c);
+            c.path = off;
+            off += align_up((size_t)sh.T * 4);
+            c.tab = off;
+            off += align_up((size_t)sh.T * 4);
+            c.through = off;
+            off += align_up((size_t)sh.T * sizeof(double));
+            c.alt = off;
+            off += align_up((size_t)sh.T * sizeof(double));
+            c.runner = off;
+            off += align_up((size_t)sh.T * 4);
+        }
+        return true;
+    });
+}
+
+}  // namespace plan
+}  // namespace ka

@@ -237,6 +237,18 @@ struct MeaLattice : FbCkLattice {
     double *wcol;                 // generic form only: 2 x L doubles, W of frame t+1 and of frame t (slot)
 };
 static_assert(sizeof(MeaLattice) == 136, "descriptor sizes");
+// ---- best-path margins from max-marginals (ka_margin.hpp): the occupancy's slots and form split; no Banded<> sibling, the
+// table is a field of its own because one call mixes lattices with a table and lattices on the diagonal ----
+struct MarginLattice : FbCkLattice {
+    const int32_t *band_lo;       // [T] the caller's table (device): lo_t; NULL: the reference's diagonal
+    const int32_t *path;          // [T] the path the margins are asked for (device)
+    double *through;              // [T] output: m_t(path[t])
+    double *alt;                  // [T] output: the best m_t(p) outside the path's group
+    int32_t *runner;              // [T] output, or NULL: the lowest p attaining alt[t]
+    int32_t unit;                 // a group is p >> unit: 0 a state, 1 a text index
+    int32_t pad_;
+};
+static_assert(sizeof(MarginLattice) == 152, "descriptor sizes");
 // the workspace planners (ka_plan.hpp) carve n descriptors: their sizes are part of the published workspace byte counts
 static_assert(sizeof(PostLattice) == 88 && sizeof(FbCkLattice) == 104 && sizeof(OccLattice) == 120 && sizeof(StateLattice) == 136 &&
                   sizeof(DurLattice) == 120 && sizeof(SampleLattice) == 128 && sizeof(VisitLattice) == 120 &&

@@ -1,8 +1,9 @@
 """Forward-backward over the band of ``ctc_best_path``: path posteriors, label occupancy, state posteriors at chosen frames,
 expected state durations, state visit probabilities, exact boundary-time quantiles, alignments sampled from the posterior, the
-maximum-expected-accuracy alignment.
+maximum-expected-accuracy alignment; and, from the best path's own recurrence instead of the sum over paths, the per-frame margin
+of a path over the best alignment that disagrees with it (``ctc_path_margins``).
 
-The six calls take the same lattices (log-probs, labels, beam_size, max_move) in host or device memory and answer with one
+The calls take the same lattices (log-probs, labels, beam_size, max_move) in host or device memory and answer with one
 log-likelihood and one status per lattice.  ``_Lattices`` (_lattices.py, shared with the best-path batch calls of align.py) is
 that common input, normalised once and aware of its memory mode; ``_run_lattices`` is the one C call and the one status
 handling.  What is a call's own (its extra inputs, its outputs, its argument tables) is in its private function; ``X_batch``
@@ -988,3 +989,121 @@ def segment_path_disagreement(best_path, mea_path, seg_ends, n_phonemes):
         if b > a:
             share[i] = differs[a:b].mean()
     return (both[1] - both[0]).astype(np.int64), share
+
+
+# ------------------------------------------------------------------------------------------
+# best-path margins from max-marginals: what the best alignment would lose if it had to be elsewhere
+# ------------------------------------------------------------------------------------------
+_MARGIN_UNITS = {"state": 0, "text": 1, 0: 0, 1: 1}
+
+
+def ctc_path_margins(log_probs, labels, path, beam_size=1000, max_move=4, unit="state", band_lo=None, raw=False):
+    """How far a path is ahead of the best alignment that disagrees with it, frame by frame: (margin float64 [T], runner_up
+    int32 [T], score float).
+
+    With m_t(s) the score of the best complete path of the band of ``ctc_best_path`` that is at state s in frame t and ends where
+    ``path`` ends (the best path's own recurrence run forwards and backwards: adds and maxima only, float64, exact),
+    margin[t] = m_t(path[t]) - max of m_t over the states of another group, runner_up[t] the lowest state attaining that maximum
+    (-1 if there is none) and score the best path's score to path[T-1].  ``unit``: "state" - any other state - or "text" -
+    another text index s // 2, which is what ``align()`` reads off the path at a segment's ends.  For a best path the margin
+    is >= 0: the score it would lose if it had to be elsewhere at frame t.  Any path with values in [0, 2S+1) is legal; the
+    margin is then signed.  It is +inf where no alternative exists and NaN where neither side has a path.  ``raw``: return
+    (through, alt, runner_up, score), the two sides of the difference.  NumPy in -> NumPy out; ROCm torch tensors go to
+    ``ctc_path_margins_device``.  Raises as ``ctc_path_posteriors``.  ``band_lo``: the band as a table [T], as
+    ``ctc_best_path_banded`` takes it; None is the diagonal band of ``ctc_best_path``.
+    """
+    call = ctc_path_margins_device if _is_tensor(log_probs) else ctc_path_margins_batch
+    (result,) = call([log_probs], [labels], [path], beam_size, max_move, unit, band_lo=_one_table(band_lo), raw=raw)
+    return result
+
+
+def _path_margins(lat, paths, beam_size, max_move, unit, return_status, band_lo, raw):
+    if unit not in _MARGIN_UNITS:
+        raise ValueError('unit must be "state" or "text"')
+    if lat is None:
+        return ([], []) if return_status else []
+    paths = [lat.int32(x) for x in paths]
+    if any(p.shape[0] != T for p, T in zip(paths, lat.T)):
+        raise ValueError("a path must have one position per frame")
+    p_band, _k0 = None, None
+    if band_lo is not None:      # (an entry may be None: that lattice runs on the diagonal)
+        if len(band_lo) != lat.n:
+            raise ValueError("band_lo must hold one table (or None) per lattice")
+        given = [i for i, b in enumerate(band_lo) if b is not None]
+        sub = _Sub(lat, given)
+        tables = dict(zip(given, _band_tables(sub, [band_lo[i] for i in given]))) if given else {}
+        p_band, _k0 = _ptr_array([lat.ptr(tables[i]) if i in tables else None for i in range(lat.n)])
+    through = [lat.empty(T, np.float64) for T in lat.T]
+    alt = [lat.empty(T, np.float64) for T in lat.T]
+    runner = [lat.empty(T, np.int32) for T in lat.T]
+    p_path, _k1 = _ptr_array([lat.ptr(x) for x in paths])
+    p_thr, _k2 = _ptr_array([lat.ptr(x) for x in through])
+    p_alt, _k3 = _ptr_array([lat.ptr(x) for x in alt])
+    p_run, _k4 = _ptr_array([lat.ptr(x) for x in runner])
+    got = _run_lattices(lat, "path_margins", beam_size, max_move, (p_band, p_path, _MARGIN_UNITS[unit], p_thr, p_alt, p_run),
+                        list(zip(through, alt, runner)), return_status)
+    if not raw:     # through - alt: +inf where alt is -inf, NaN where both are (and for a failed lattice)
+        def margin(th, al):
+            if _is_tensor(th):
+                return th - al
+            with np.errstate(invalid="ignore"):
+                return th - al
+        results = [(margin(th, al), r, z) for th, al, r, z in (got[0] if return_status else got)]
+        return (results, got[1]) if return_status else results
+    return got
+
+
+class _Sub:
+    """The lattices ``given`` of a ``_Lattices``, as ``_band_tables`` reads them."""
+
+    def __init__(self, lat, given):
+        self.n, self.T, self.form, self.int32 = len(given), [lat.T[i] for i in given], lat.form, lat.int32
+
+
+def ctc_path_margins_batch(log_probs_list, labels_list, path_list, beam_size=1000, max_move=4, unit="state", device=None,
+                           return_status=False, band_lo=None, raw=False):
+    """Margins of many lattices in ONE launch; host NumPy buffers in and out.
+
+    Returns a list of (margin, runner_up, score), or of (through, alt, runner_up, score) with ``raw``; with ``return_status``
+    also the per-lattice status list, in which case failures do not raise (their margins are NaN, their runner_up -1, their
+    score NaN, or -inf for KA_ERR_ZERO_MASS).  ``band_lo``: a list with one table or None per lattice.
+    """
+    lat = _host_lattices(log_probs_list, labels_list, path_list, "paths", device)
+    return _path_margins(lat, path_list, beam_size, max_move, unit, return_status, band_lo, raw)
+
+
+def ctc_path_margins_device(log_probs, labels, paths, beam_size=1000, max_move=4, unit="state", return_status=False, band_lo=None,
+                            raw=False):
+    """Lists of ROCm torch tensors in (float32 log-probs [T_i, V], labels [S_i], paths [T_i] - e.g. the outputs of
+    ``ctc_best_path_device``), list of (margin float64 tensor [T_i], runner_up int32 tensor [T_i], score float) out, on the
+    device.  One launch on torch's current stream.  ``band_lo``: a list with one table (a tensor on the device or a host
+    array) or None per lattice."""
+    lat = _device_lattices(log_probs, labels, paths, "paths")
+    return _path_margins(lat, paths, beam_size, max_move, unit, return_status, band_lo, raw)
+
+
+def segment_boundary_margin(margin_text, seg_ends):
+    """Per segment that ``align()`` writes a line for, how safe its two text boundaries are (host only): the smaller of the
+    ``unit="text"`` margins at its first frame a (seg_ends[i-1], 0 for the first) and at the frame after its last, b =
+    seg_ends[i]; a frame b >= T counts +inf, the convention of ``segment_boundary_confidence``.  float64 array."""
+    m = np.asarray(margin_text.detach().cpu() if _is_tensor(margin_text) else margin_text, dtype=np.float64).reshape(-1)
+    T = len(m)
+    ends = np.asarray(seg_ends, dtype=np.int64).reshape(-1)
+    out = np.empty(len(ends))
+    for i in range(len(ends)):
+        a, b = (int(ends[i - 1]) if i > 0 else 0), int(ends[i])
+        at = [m[t] if t < T else np.inf for t in (a, b)]
+        out[i] = np.nan if np.isnan(at).any() else min(at)
+    return out
+
+
+def segment_min_margin(margin, seg_ends):
+    """Per segment that ``align()`` writes a line for, the smallest margin over its frames [a, b) (``_segments``); +inf for
+    a segment without frames, NaN if one of its frames has none (host only).  float64 array."""
+    m = np.asarray(margin.detach().cpu() if _is_tensor(margin) else margin, dtype=np.float64).reshape(-1)
+    segs = _segments(np.asarray(seg_ends, dtype=np.int64), len(m))
+    out = np.full(len(segs), np.inf)
+    for i, a, b in segs:
+        if b > a:
+            out[i] = np.nan if np.isnan(m[a:b]).any() else m[a:b].min()
+    return out
