@@ -458,6 +458,9 @@ __device__ __forceinline__ f32x2 label_pair_max(float l1, float b1, float l0, fl
 // column with ds_read_b32.  ds_bpermute_b32 on the row register does the same without the write, but costs 7.0
 // cycles of the CU's LDS pipe per wave-instruction against 3.8 for the read (tools/ubench/lds_rates.hip) - with
 // 8 gathers per frame and 32 waves per CU that pipe was 75 % busy with them.
+// `row` is where the frame's row begins and `byte_addr` the column's offset in it: 4 * label in a row of its own (row by row),
+// 8 * label in forward_ck's four-row blocks, whose rows lie in LDS as frame pairs interleaved by column (lds_col2 below) - there
+// `row` is the pair's base plus one float for the odd frame.
 __device__ __forceinline__ float lds_col(const float *row, int byte_addr)
 {
     return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(row) + byte_addr);
@@ -479,6 +482,51 @@ __device__ __forceinline__ void frame_scores(f32x2 (&P)[8], float h1, float h2, 
     E[G][0] = lds_col(next_row, la[2 * G]);
     E[G][1] = lds_col(next_row, la[2 * G + 1]);
     if constexpr (G > 0) frame_scores<M, ZL, G - 1>(P, h1, h2, h3, E, vz, e00, la, next_row);
+}
+
+// Two frames per gather (forward_ck's four-row blocks): rows 2p and 2p+1 of a block lie interleaved by column, element
+// (row r, column c) at byte (r >> 1) * 512 + c * 8 + (r & 1) * 4, so ONE ds_read_b64 at 8 * label fetches a label cell's
+// emissions of both frames - it costs the LDS pipe what a ds_read_b32 costs (3.84 against 3.78 cycles per wave-instruction,
+// profiles/r01_ubench_issue_rates.txt), and that pipe is the kernel's second bottleneck beside the vector ALU.
+__device__ __forceinline__ f32x2 lds_col2(const float *pair, int byte_addr)
+{
+    return *reinterpret_cast<const f32x2 *>(reinterpret_cast<const char *>(pair) + byte_addr);
+}
+// a + b as ONE v_add_f32 the compiler cannot re-pair: left to itself the SLP vectoriser packs the two label cells of a group
+// again and builds the emission operand of its v_pk_add_f32 with two v_mov (two single adds cost the vector ALU what the packed
+// one does: 2.4 cycles each against 4.8)
+__device__ __forceinline__ float add_single(float a, float b)
+{
+    float r;
+    asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// frame_scores with one emission PAIR per label cell, EP[i] = {e(t), e(t+1)} for even t: the even frame (odd = false) consumes
+// the first halves, the odd frame the second halves and then requests the pair of frames t+1 and t+2 (next_pair: where rows t+1
+// and t+2 lie) - every value still has a whole frame between request and use.  No label-0 veto (see forward_ck_body).
+template <int M, int G>
+__device__ __forceinline__ void frame_scores_pair(f32x2 (&P)[8], float h1, float h2, float h3, f32x2 (&EP)[8], f32x2 e00,
+                                                  const int (&la)[8], const float *next_pair, bool odd)
+{
+    const float b0 = P[2 * G][0], l0 = P[2 * G + 1][0], b1 = P[2 * G][1], l1 = P[2 * G + 1][1];
+    const float p1 = G > 0 ? P[2 * (G > 0 ? G - 1 : 0) + 1][1] : h1;   // cell 4G-1 (label)
+    const float p2 = G > 0 ? P[2 * (G > 0 ? G - 1 : 0)][1] : h2;       // cell 4G-2 (blank)
+    const float p3 = G > 0 ? P[2 * (G > 0 ? G - 1 : 0) + 1][0] : h3;   // cell 4G-3 (label)
+    f32x2 ml, mb;
+    ml = label_pair_max<M, false>(l1, b1, l0, b0, p1, p2, 0.0f, 0.0f);   // {lower, upper}
+    mb[1] = cell_blank_max<M>(b1, l0, p1);
+    mb[0] = cell_blank_max<M>(b0, p1, p3);
+    P[2 * G + 1][0] = add_single(ml[0], EP[2 * G][odd]);
+    P[2 * G + 1][1] = add_single(ml[1], EP[2 * G + 1][odd]);
+    P[2 * G] = mb + e00;
+    if (odd) {
+        EP[2 * G] = lds_col2(next_pair, la[2 * G]);
+        EP[2 * G + 1] = lds_col2(next_pair, la[2 * G + 1]);
+        // keep each group's two reads right behind its adds: left alone, the scheduler collects all eight at the end of the frame,
+        // a dozen instructions before the next frame's first add waits for them (55.8-56.0 ms per step against 55.4-55.5)
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (G > 0) frame_scores_pair<M, G - 1>(P, h1, h2, h3, EP, e00, la, next_pair, odd);
 }
 
 // -inf into the cells outside the band

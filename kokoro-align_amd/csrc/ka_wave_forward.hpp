@@ -256,19 +256,31 @@ __device__ __forceinline__ void forward_w16(const Lattice &d, int32_t *meta)
 //
 // Log-prob rows reach the loop in one of two ways (BLK; forward_ck chooses per lattice, see there):
 //   * row by row: one 256-byte load per frame, four rows in flight, each dropped into LDS (ds_write_b32) one frame ahead;
-//   * in blocks of four rows (ld == 64: rows 4b..4b+3 are one contiguous 1-KB run): one 16-byte load and one ds_write_b128
-//     per lane per FOUR frames, LDS as [2 buffers][4 rows][64], block b in buffer b & 1.  Block b+1 is written before frame
-//     4b+3 gathers the emissions of frame 4b+4 and block b+2 is requested right behind, into the same four registers.  The
-//     loop is unrolled by eight frames, so buffer and row of every gather are the immediate offset of its ds_read_b32.
-//     Lane 16 r of a block register's first component holds lp[4b+r, 0]: the four blank emissions are read (v_readlane)
-//     when the block is written.  The finiteness sum takes each lane's four components: every element of the lattice is
-//     in exactly one lane's sum, as before; rows past T-1 come back as zeros (block_reload).
+//   * in blocks of four rows (ld == 64: rows 4b..4b+3 are one contiguous 1-KB run): one 16-byte load per lane per FOUR
+//     frames, block b in LDS buffer b & 1.  A buffer holds its four rows as two FRAME PAIRS interleaved by column: element
+//     (row r, column c) at byte buffer * 1024 + (r >> 1) * 512 + c * 8 + (r & 1) * 4.  A lane holds row lane / 16, columns
+//     4 (lane % 16) .. + 3, and drops them with two ds_write2_b32 at a per-lane base computed once.  A label cell then
+//     fetches the emissions of frames 2p and 2p+1 with ONE ds_read_b64 at 8 * label (labels are pre-scaled when loaded) into
+//     a register pair of its own: the even frame adds the first half, the odd frame the second and requests the next pair
+//     right behind the add - four gathers per frame instead of eight on an LDS pipe that costs a read of 8 bytes what it
+//     costs a read of 4, and every value still a whole frame ahead of its use.  The two label cells of a group no longer
+//     find their emissions in one aligned register pair, so their packed add is two single adds (the same vector time).
+//     The half of the last pair past T-1 is a row that came back as zeros and is never consumed.  The label-0 instance (ZL)
+//     has no registers for the pairs and reads the same image with one ds_read_b32 per label cell and frame.
+//     Block b+1 is written before frame 4b+3 gathers frames 4b+4 and 4b+5, and block b+2 is requested right behind, into
+//     the same four registers.  The loop is unrolled by eight frames, so buffer and pair of every gather are the immediate
+//     offset of its read.  Lane 16 r of a block register's first component holds lp[4b+r, 0]: the four blank emissions are
+//     read (v_readlane) when the block is written.  The finiteness sum takes each lane's four components: every element
+//     of the lattice is in exactly one lane's sum, as before; rows past T-1 come back as zeros (block_reload).
 // ---------------------------------------------------------------------------------------
 template <int M, bool ZL, bool BLK>
 __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta, float *lrow)
 {
     constexpr int D = kRowDepth;
     constexpr int U = BLK ? 2 * D : D;      // frames per trip of the loop
+    // Two frames per emission gather.  Not with the label-0 veto: its 8 veto registers and 8 more emission registers do not fit
+    // 64 VGPRs, so that instance reads the same LDS image one frame at a time.
+    constexpr bool PAIR = BLK && !ZL;
     const int lane = threadIdx.x;
     const uint32_t T = (uint32_t)__builtin_amdgcn_readfirstlane(d.T);
     const uint32_t L = (uint32_t)__builtin_amdgcn_readfirstlane(d.L);
@@ -291,6 +303,10 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
     load_block_labels(labx, blk, la);
 #pragma unroll
     for (int i = 0; i < 8; ++i) vz[i] = (ZL && la[i] == 0) ? NINF : __builtin_inff();
+    if constexpr (BLK) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) la[i] *= 2;   // blocks: a column is 8 bytes wide (two frames)
+    }
 
     uint32_t q = 0, rem = 0;                // floor(L*t/T) and its remainder, advanced per frame
     uint32_t lo = 0, hi = B < L ? B : L;    // band of frame 0
@@ -304,13 +320,17 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
     [[maybe_unused]] float rows[D];         // row by row: rows t+1 .. t+D-1 and the request for row t+D
     [[maybe_unused]] f32x4 rblk;            // blocks: block (t+1)/4 + 1, requested when block (t+1)/4 went to LDS
     [[maybe_unused]] uint32_t blk_off = (uint32_t)lane * 16u;   // byte offset of this lane's part of the block that is requested next
-    f32x2 E[4];                             // emissions of the label cells (see frame_scores)
+    [[maybe_unused]] f32x2 E[4];            // emissions of the label cells (see frame_scores)
+    [[maybe_unused]] f32x2 EP[8];           // the same for two frames, one pair per label cell (see frame_scores_pair)
+    // blocks: where this lane's part of a block (row lane / 16, columns 4 (lane % 16) .. + 3) goes in an LDS buffer
+    [[maybe_unused]] float *const lblk = lrow + (lane >> 5) * 128 + ((lane >> 4) & 1) + (lane & 15) * 8;
     float e0[BLK ? 8 : 2];                  // blank emissions: of frame t and t+1 by frame parity; blocks: [buffer][row]
     if constexpr (BLK) {
         asm("" : "=v"(rblk));
         block_reload(rblk, blk_off, lp_rsrc);
         block_wait(rblk);
-        *reinterpret_cast<f32x4 *>(lrow + lane * 4) = rblk;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) lblk[2 * c] = rblk[c];
 #pragma unroll
         for (int r = 0; r < 4; ++r) e0[r] = lane_of(rblk[0], 16 * r);
         absum = __builtin_fabsf(rblk[0]) + __builtin_fabsf(rblk[1]) + __builtin_fabsf(rblk[2]) + __builtin_fabsf(rblk[3]);
@@ -331,8 +351,13 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
         e0[0] = first_lane(rows[0]);
         absum = __builtin_fabsf(rows[0]);
     }
+    if constexpr (PAIR) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) E[i >> 1][i & 1] = lds_col(lrow, la[i]);
+        for (int i = 0; i < 8; ++i) EP[i] = lds_col2(lrow, la[i]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) E[i >> 1][i & 1] = lds_col(lrow, la[i]);
+    }
 
     const char *ckp = reinterpret_cast<const char *>(d.bp);
     // row min(t+D, T-1) of the current frame t, as a byte offset into the lattice's log-probs (forward_ck_kernel has made sure
@@ -369,7 +394,8 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
                     if (dd == D - 1) {
                         // block (t+1)/4: requested four frames ago; no other request has been made since
                         block_wait(rblk);
-                        *reinterpret_cast<f32x4 *>(lrow + (nu / 4) * 256 + lane * 4) = rblk;
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) lblk[(nu / 4) * 256 + 2 * c] = rblk[c];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) e0[(nu / 4) * 4 + r] = lane_of(rblk[0], 16 * r);
                         absum += __builtin_fabsf(rblk[0]);
@@ -385,7 +411,7 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
                         __builtin_amdgcn_sched_barrier(0);
                         blk_off += 1024u;
                     }
-                    next_row = lrow + (nu / 4) * 256 + (nu % 4) * 64;
+                    next_row = lrow + (nu / 4) * 256 + ((nu % 4) >> 1) * 128 + (nu & 1);
                     e0t = e0[u];
                 } else {
                     // row t+1 (its emissions are gathered while frame t is computed): issued D-1 frames ago, D-2
@@ -397,7 +423,8 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
                     absum += __builtin_fabsf(rn);
                     e0t = e0[dd & 1];
                 }
-                frame_scores<M, ZL, 3>(P, h1, h2, h3, E, vz, f32x2{e0t, e0t}, la, next_row);
+                if constexpr (PAIR) frame_scores_pair<M, 3>(P, h1, h2, h3, EP, f32x2{e0t, e0t}, la, next_row, (u & 1) != 0);
+                else frame_scores<M, ZL, 3>(P, h1, h2, h3, E, vz, f32x2{e0t, e0t}, la, next_row);
                 if constexpr (!BLK) {
                     // prefetch the row of frame t+D (the last row again once there is none: never consumed)
                     row_reload_buf(rows[dd], lane_off, lp_rsrc, row_ahead);
@@ -454,6 +481,10 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
                                     load_block_labels(labx, blk, la);
 #pragma unroll
                                     for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(la[i]));
+                                    if constexpr (BLK) {
+#pragma unroll
+                                        for (int i = 0; i < 8; ++i) la[i] *= 2;
+                                    }
                                 }
                                 const bool left_reset = __builtin_amdgcn_update_dpp(0, (int)reset_lane, 0x13C, 0xF, 0xF, false) != 0;
                                 const bool kill = reset_lane && left_reset;
@@ -463,8 +494,15 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
 #pragma unroll
                                 for (int k = 0; k < 16; ++k) KA_P(P, k) = reset_lane ? NINF : KA_P(P, k);
                                 // emissions of frame t+1 with the new labels (the cells gathered them with the old ones)
+                                if constexpr (PAIR) {
+                                    // the pair that holds frame t+1: after an even frame its second half is still owed,
+                                    // after an odd frame both are (the cells have just requested it with the old labels)
 #pragma unroll
-                                for (int i = 0; i < 8; ++i) E[i >> 1][i & 1] = lds_col(next_row, la[i]);
+                                    for (int i = 0; i < 8; ++i) EP[i] = lds_col2(next_row - ((u + 1) & 1), la[i]);
+                                } else {
+#pragma unroll
+                                    for (int i = 0; i < 8; ++i) E[i >> 1][i & 1] = lds_col(next_row, la[i]);
+                                }
                                 if constexpr (ZL) {
 #pragma unroll
                                     for (int i = 0; i < 8; ++i) vz[i] = la[i] == 0 ? NINF : __builtin_inff();
