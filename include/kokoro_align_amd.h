@@ -453,6 +453,62 @@ size_t ka_tracking_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S
                                    int32_t mem);
 
 /*
+ * Resumable best path: ka_ctc_best_path_banded started from a caller-given score row, ended at a
+ * caller-given cell or rule, and returning the score row after its last frame and the cell of the start row its path left
+ * from.  The recurrence, the table and its check, forms, limits, memory modes, statuses, return convention and stream
+ * synchronisation are ka_ctc_best_path_banded[_batch]_f32's; only the boundary conditions are the caller's.  L = 2S+1.
+ *   init_scores   [L] float32, where `mem` says, or NULL (batch: a HOST array of n such pointers, itself or any entry NULL).
+ *                 NULL: the virtual state {0: 0.0}.  Else the state before frame 0 is A_{-1} = {p : init_scores[p] is not a
+ *                 NaN} with sc_{-1}[p] = init_scores[p]; -inf is a LIVE cell of score -inf (liveness is separate from the
+ *                 score, and a resumed chunk keeps it).  No band applies to this row: frame 0 reads sc_{-1}[p-j] for p in
+ *                 [lo_0, hi_0), so only the cells [lo_0 - (max_move-1), hi_0) can matter; no live cell among them ends in
+ *                 KA_ERR_EMPTY_BEAM.  A +inf anywhere in the row is KA_ERR_BAD_ARGS for that lattice alone, found on the
+ *                 device by the preparation kernel.  In KA_MEM_DEVICE the row must not overlap final_scores.
+ *   end           int32 (batch: a HOST array of n, NULL = all -1).  -1: the path ends at the highest live position of frame
+ *                 T-1 (the reference's rule); -2: at the first maximum of the scores after frame T-1 over the live cells in
+ *                 ascending position (ka_ctc_best_path_tracking's end_rule 1); p >= 0: at p, and if p is not live after frame
+ *                 T-1 the lattice ends in KA_ERR_EMPTY_BEAM.  A value < -2 or >= L is KA_ERR_BAD_ARGS before anything is
+ *                 launched or written.
+ *   final_scores  [L] float32 output, where `mem` says; NULL as init_scores.  A position live after frame T-1 gets
+ *                 sc_{T-1}[p], every other position of [0, L) the quiet NaN of bits 0x7fc00000.  Written whenever the forward
+ *                 pass ran, so also for a dead end cell and for an empty beam (all NaN); a lattice that ends in
+ *                 KA_ERR_BAD_LABEL, KA_ERR_NAN or KA_ERR_BAD_ARGS (as a lattice's status) gets all NaN, so that a chunk
+ *                 resumed from it ends in KA_ERR_EMPTY_BEAM, never in numbers.
+ *   entry         int32 output, HOST memory in both modes (batch: [n]); may be NULL.  The cell of A_{-1} the path left from,
+ *                 path[0] - j*_0(path[0]); 0 for a NULL init_scores; -1 for a lattice without a path.
+ *   total_score   sc_{T-1}[end cell], as in the banded call.
+ * What follows, exactly:
+ *   1. with init_scores NULL (or NaN everywhere but 0.0 at position 0), end -1 and final_scores NULL every output is
+ *      ka_ctc_best_path_banded's, bit for bit;
+ *   2. cut and resume: for any table and k in [1, T), chunk A = frames [0, k) with band_lo[:k], chunk B = frames [k, T) with
+ *      band_lo[k:], init_scores = A's final_scores and end -1, then A again with end = B's entry: the two paths, label and score
+ *      arrays concatenated are the uncut banded call's and B's total_score has its bits; if the uncut call ends in
+ *      KA_ERR_EMPTY_BEAM, so does A or B;
+ *   3. a lattice gives the same bits alone or inside a batch, whatever its neighbours' rows and ends are.
+ * Cost: the start and last rows are O(L) once per call against the frame loop's O(T x band), and the frame loop is the banded
+ * call's instruction for instruction (the start row goes through the re-labelling block a band step takes, in frame 0 only).
+ * Measured against ka_ctc_best_path_banded_batch_f32 of the same build on the same table (tools/bench_resume.py,
+ * profiles/resume_bench.jsonl; MI355X, cfg2): 1.0035 times that call for one lattice with NULL rows and 1.0033 with a start row,
+ * a last row and a given end (33.50 and 33.49 against 33.38 ms); 1.0050 and 1.0055 for 1024 lattices (36.36 and 36.38 against
+ * 36.18 ms).  Cutting one lattice into 8 chunks that resume from each other (ctc_best_path_chunked) costs 1.888 times the
+ * uncut call, (2 - 1/8) forward passes, and needs the move codes of one chunk.
+ */
+int ka_ctc_best_path_resume_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                int32_t beam_size, int32_t max_move, const int32_t *band_lo, const float *init_scores, int32_t end,
+                                int32_t *best_path, int32_t *best_labels, float *best_scores, float *final_scores, int32_t *entry,
+                                float *total_score, int32_t mem, void *stream);
+int ka_ctc_best_path_resume_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                      const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                      const int32_t *const *band_lo, const float *const *init_scores, const int32_t *end,
+                                      int32_t *const *best_path, int32_t *const *best_labels, float *const *best_scores,
+                                      float *const *final_scores, int32_t *entry, float *total_score, int32_t *status, int32_t mem,
+                                      void *stream);
+/* device-workspace bytes such a call carves (0 for unsupported arguments): ka_banded_workspace_bytes plus 36 bytes per lattice
+ * (its rows' descriptor and entry cell, rounded up for the batch) and, for KA_MEM_HOST, the two staged rows of every lattice */
+size_t ka_resume_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                 int32_t mem);
+
+/*
  * Best-path margins from max-marginals: how much score the best alignment would lose if, at frame t, it had to be somewhere
  * else.  The best path's own recurrence in max-plus arithmetic, run forwards (D) and backwards (E): adds and compares only, no
  * transcendental, float64 throughout, so every output is defined bit for bit by IEEE add and max.

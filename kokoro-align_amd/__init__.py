@@ -7,7 +7,9 @@ Public surface mirrors the reference (kokoro_align/align.py):
     pandas_read_align(files)                                       align.py:172
 plus batched / device-resident entry points (ctc_best_path_batch, ctc_best_path_device), the best path over a band the caller
 gives (ctc_best_path_banded[_batch|_device], diagonal_band, anchored_band, band_around_path, band_edge_contact) or that steers
-itself by the scores and returns the table it walked (ctc_best_path_tracking[_batch|_device]) and the
+itself by the scores and returns the table it walked (ctc_best_path_tracking[_batch|_device]), or started from a score row,
+ended at a chosen cell and resumable from the row it returns (ctc_best_path_resume[_batch|_device], free_start_scores,
+ctc_best_path_chunked) and the
 forward-backward quality signal of a best path (ctc_path_posteriors[_batch|_device], segment_confidence), the label
 occupancy of every frame (ctc_label_posteriors[_batch|_device], segment_agreement), the differentiable lattice
 log-likelihood (lattice_log_likelihood) and the state posteriors at chosen frames behind the confidence of align()'s text
@@ -38,11 +40,16 @@ from .align import (  # noqa: F401
     ctc_best_path_banded_batch,
     ctc_best_path_banded_device,
     ctc_best_path_batch,
+    ctc_best_path_chunked,
     ctc_best_path_device,
+    ctc_best_path_resume,
+    ctc_best_path_resume_batch,
+    ctc_best_path_resume_device,
     ctc_best_path_tracking,
     ctc_best_path_tracking_batch,
     ctc_best_path_tracking_device,
     diagonal_band,
+    free_start_scores,
     log_softmax_device,
     pandas_read_align,
 )

@@ -8,7 +8,8 @@
 plus what the reference has no name for: many lattices in one launch (ctc_best_path_batch, DeviceBatch,
 ctc_best_path_device), the log-softmax of align.py:116-117 on the device (log_softmax_device) and the best path over a band
 the caller gives (ctc_best_path_banded[_batch|_device] with the tables diagonal_band, anchored_band, band_around_path and the
-diagnostic band_edge_contact).
+diagnostic band_edge_contact), over a band that steers itself (ctc_best_path_tracking[_batch|_device]) and the banded best path
+with the caller's boundary conditions (ctc_best_path_resume[_batch|_device], free_start_scores, ctc_best_path_chunked).
 
 The DP + backtrace (the reference's per-frame NumPy loop) run in the HIP library through the C
 ABI of include/kokoro_align_amd.h.  NumPy arrays are handed over as host buffers; torch tensors
@@ -74,14 +75,16 @@ _BEST_PATH_CALLS = {
     "": ((np.int32, np.int32, np.float32), (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_NONFINITE)),
     "_banded": ((np.int32, np.int32, np.float32), (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_BAD_ARGS)),
     "_tracking": ((np.int32, np.int32, np.float32, np.int32), (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN)),
+    "_resume": ((np.int32, np.int32, np.float32), (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_BAD_ARGS)),
 }
 
 
-def _run_best_path(lat, call, beam_size, max_move, own_args, outputs, return_status):
-    """The call ``ka_ctc_best_path<call>_batch_f32`` ("", "_banded", "_tracking"): the arguments all three take, ``own_args``
-    behind ``max_move`` (the band tables; period and end rule), then the outputs (paths, labels, scores and, for tracking, the
-    tables walked: allocated here, or the caller's ``outputs`` after a check), totals and statuses, and the status handling
-    of ``return_status``.  KA_ERR_BAD_ARGS is let through only as a lattice's own status (a bad table), not as the call's."""
+def _run_best_path(lat, call, beam_size, max_move, own_args, outputs, return_status, more_outputs=()):
+    """The call ``ka_ctc_best_path<call>_batch_f32`` ("", "_banded", "_tracking", "_resume"): the arguments all take, ``own_args``
+    behind ``max_move`` (the band tables; period and end rule; start rows and ends), then the outputs (paths, labels, scores and,
+    for tracking, the tables walked: allocated here, or the caller's ``outputs`` after a check), ``more_outputs`` as they are
+    (the resumed call's last rows and entries), totals and statuses, and the status handling of ``return_status``.
+    KA_ERR_BAD_ARGS is let through only as a lattice's own status (a bad table), not as the call's."""
     dtypes, let_through = _BEST_PATH_CALLS[call]
     if outputs is None:
         outputs = [[lat.empty(T, dt) for T in lat.T] for dt in dtypes]
@@ -102,7 +105,7 @@ def _run_best_path(lat, call, beam_size, max_move, own_args, outputs, return_sta
     with lat.guard():
         rc = getattr(eng.lib, f"ka_ctc_best_path{call}_batch_f32")(
             eng.handle, lat.n, p_lp, p_T, lat.V, p_ld, p_lab, p_S, int(beam_size), int(max_move), *own_args,
-            *[p for p, _ in p_outs], total.ctypes.data, status.ctypes.data, lat.mem, lat.stream())
+            *[p for p, _ in p_outs], *more_outputs, total.ctypes.data, status.ctypes.data, lat.mem, lat.stream())
     results = list(zip(*outputs))
     if return_status:
         if rc not in let_through or (rc == _lib.KA_ERR_BAD_ARGS and not np.any(status == _lib.KA_ERR_BAD_ARGS)):
@@ -356,6 +359,146 @@ def ctc_best_path_tracking(log_probs, labels, beam_size=1000, max_move=4, period
     if lp.ndim != 2:
         raise ValueError("log_probs must be [T, V]")
     return ctc_best_path_tracking_batch([lp], [labels], beam_size, max_move, period, end_rule)[0]
+
+
+# ------------------------------------------------------------------------------------------
+# resumable best path: the banded best path under the caller's boundary conditions
+# ------------------------------------------------------------------------------------------
+END_CELLS = {"highest": -1, "best": -2}
+
+
+def free_start_scores(L, lo=0, hi=None):
+    """A start row for ``ctc_best_path_resume`` that lets the path begin anywhere in [lo, hi) at no cost: float32 [L], 0.0 there
+    and NaN (a dead cell) elsewhere.  ``hi`` None is L."""
+    row = np.full(int(L), np.nan, np.float32)
+    row[int(lo):int(L) if hi is None else int(hi)] = 0.0
+    return row
+
+
+def _score_rows(lat, rows):
+    """The start rows of a resumed call as the call wants them: per lattice None or float32 [2S+1] where the lattices are."""
+    if rows is None:
+        return [None] * lat.n
+    if len(rows) != lat.n:
+        raise ValueError("init_scores must hold one row (or None) per lattice")
+    out = []
+    for r, S in zip(rows, lat.S):
+        if r is not None:
+            if lat.form == "batch":
+                r = np.ascontiguousarray(np.asarray(r.detach().cpu() if _is_tensor(r) else r, dtype=np.float32).reshape(-1))
+            else:
+                import torch
+                r = (r if _is_tensor(r) else torch.as_tensor(np.asarray(r, dtype=np.float32))).reshape(-1)
+                r = r.to(device=lat.dev, dtype=torch.float32).contiguous()
+            if r.shape[0] != 2 * S + 1:
+                raise ValueError("a start row must have 2S+1 entries")
+        out.append(r)
+    return out
+
+
+def _best_path_resume(lat, band_lo, init_scores, end, beam_size, max_move, final_scores, return_status):
+    tables = _band_tables(lat, band_lo)         # (held until the call has returned, like the rows: the addresses below are theirs)
+    rows = _score_rows(lat, init_scores)
+    ends = [end] * lat.n if isinstance(end, (str, int, np.integer)) else list(end)
+    if len(ends) != lat.n:
+        raise ValueError("end must be one value or one per lattice")
+    ends = np.array([END_CELLS[x] if isinstance(x, str) else int(x) for x in ends], np.int32)
+    last = [lat.empty((2 * S + 1,), np.float32) for S in lat.S] if final_scores else None
+    entry = np.full(lat.n, -1, np.int32)
+    p_band, _k1 = _ptr_array([lat.ptr(x) for x in tables])
+    p_init, _k2 = _ptr_array([None if x is None else lat.ptr(x) for x in rows])
+    p_last, _k3 = _ptr_array([lat.ptr(x) for x in last]) if final_scores else (None, None)
+    out = _run_best_path(lat, "_resume", beam_size, max_move, (p_band, p_init, ends.ctypes.data), None, return_status,
+                         (p_last, entry.ctypes.data))
+    results = out[0] if return_status else out
+    results = [r + (int(entry[i]), last[i] if final_scores else None) for i, r in enumerate(results)]
+    return (results,) + tuple(out[1:]) if return_status else results
+
+
+def ctc_best_path_resume_batch(log_probs_list, labels_list, band_lo_list, init_scores_list=None, end="highest", beam_size=1000,
+                               max_move=4, device=None, return_status=False, final_scores=True):
+    """``ctc_best_path_resume`` for a list of lattices in one call.  Host NumPy buffers in and out: a list of (best_path,
+    best_labels, best_scores, entry, final_scores).  ``init_scores_list``: None, or per lattice None or a row; ``end``: one value
+    for all or one per lattice.  With ``return_status`` failures of single lattices do not raise and (results, statuses, totals)
+    are returned; a failed lattice's path arrays are not written, its entry is -1 and its last row is written (all NaN unless
+    its forward pass ran).  ``final_scores=False`` asks for no last rows (None in the results)."""
+    lat = _host_lattices(log_probs_list, labels_list, band_lo_list, "band_lo", device)
+    if lat is None:
+        return ([], [], []) if return_status else []
+    return _best_path_resume(lat, band_lo_list, init_scores_list, end, beam_size, max_move, final_scores, return_status)
+
+
+def ctc_best_path_resume_device(log_probs, labels, band_lo, init_scores=None, end="highest", beam_size=1000, max_move=4,
+                                return_status=False, final_scores=True):
+    """``ctc_best_path_resume_batch`` on lists of ROCm torch tensors (labels, tables and rows may also be NumPy arrays): paths,
+    labels, scores and last rows stay on the device, so a chunk resumes from the row the chunk before it left there; the entries
+    are Python integers."""
+    lat = _device_lattices(log_probs, labels, band_lo, "band_lo")
+    return _best_path_resume(lat, band_lo, init_scores, end, beam_size, max_move, final_scores, return_status)
+
+
+def ctc_best_path_resume(log_probs, labels, band_lo, init_scores=None, end="highest", beam_size=1000, max_move=4):
+    """``ctc_best_path_banded`` under the caller's boundary conditions: started from a score row, ended at a cell or by a rule,
+    returning the row after its last frame and the cell of the start row its path left from.
+
+    ``init_scores`` [2S+1] float32: the scores before frame 0; NaN is a dead cell, -inf a live cell of score -inf, +inf a
+    ValueError.  No band applies to the row (only the cells frame 0 can reach matter).  None is the reference's start, position
+    0 at score 0.0; ``free_start_scores`` lets the path begin anywhere (a recording that holds a part of its text).
+    ``end``: "highest" ends the path at the highest live position of the last frame (the reference's rule), "best" at the
+    best-scoring one (the first maximum in ascending position), an integer at that position (ValueError if it is not live).
+    Returns (best_path, best_labels, best_scores, entry, final_scores): ``entry`` is the cell of the start row the path left
+    from (0 for None), ``final_scores`` [2S+1] the live cells' scores after the last frame and NaN elsewhere, which is the
+    ``init_scores`` of a call on the frames that follow.  With None, "highest" every array is ``ctc_best_path_banded``'s bit for
+    bit, and a lattice cut into chunks that resume from each other (``ctc_best_path_chunked``) gives the uncut call's bits.
+    NumPy in -> NumPy out; ROCm torch tensors in -> torch tensors out."""
+    if _is_tensor(log_probs):
+        return ctc_best_path_resume_device([log_probs], [labels], [band_lo], [init_scores], end, beam_size, max_move)[0]
+    lp = np.asarray(log_probs)
+    if lp.ndim != 2:
+        raise ValueError("log_probs must be [T, V]")
+    return ctc_best_path_resume_batch([lp], [labels], [band_lo], [init_scores], end, beam_size, max_move)[0]
+
+
+def ctc_best_path_chunked(log_probs, labels, band_lo, chunk_frames, beam_size=1000, max_move=4):
+    """``ctc_best_path_banded`` in chunks of ``chunk_frames`` frames: the same (best_path, best_labels, best_scores), bit for bit.
+    A forward sweep runs the chunks in order, each from the row the one before it ended with, and keeps every chunk's start
+    row; the last chunk's path is taken at once; the earlier chunks are then run again, last to first, from their kept rows
+    with ``end`` = the next chunk's ``entry``.  Cost: (2 - 1/chunks) forward passes instead of one.  What it buys: the kernels
+    hold move codes for ``chunk_frames`` frames instead of T (256 bytes per frame in the one-wavefront form), so a long
+    recording's workspace is bounded by the chunk, and the first sweep can run while the log-probs still arrive."""
+    chunk_frames = int(chunk_frames)
+    if chunk_frames < 1:
+        raise ValueError("chunk_frames must be at least 1")
+    tensor = _is_tensor(log_probs)
+    if not tensor:
+        log_probs = np.asarray(log_probs)
+    if log_probs.ndim != 2:
+        raise ValueError("log_probs must be [T, V]")
+    T = int(log_probs.shape[0])
+    if not tensor or not _is_tensor(band_lo):
+        band_lo = np.asarray(band_lo.detach().cpu() if _is_tensor(band_lo) else band_lo).reshape(-1)
+    if band_lo.shape[0] != T:
+        raise ValueError("a band table must have one entry per frame")
+    cuts = list(range(0, T, chunk_frames))
+    if not cuts:
+        raise IndexError("list index out of range")
+
+    def run(a, init, end):
+        b = min(a + chunk_frames, T)
+        return ctc_best_path_resume(log_probs[a:b], labels, band_lo[a:b], init, end, beam_size, max_move)
+
+    starts, init = [], None
+    for a in cuts[:-1]:
+        starts.append(init)
+        init = run(a, init, "highest")[4]
+    parts = [run(cuts[-1], init, "highest")]
+    for a, init in zip(reversed(cuts[:-1]), reversed(starts)):
+        parts.append(run(a, init, parts[-1][3]))
+    parts.reverse()
+    if tensor:
+        import torch
+        return tuple(torch.cat([p[i] for p in parts]) for i in range(3))
+    return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
 
 
 def log_softmax_device(logits, out=None):

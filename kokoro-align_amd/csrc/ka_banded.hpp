@@ -1,6 +1,7 @@
 // ka_banded.hpp — best path over a caller-given band (ka_ctc_best_path_banded[_batch]_f32).
-// Included by ka_banded.hip, which holds the table's own kernels (preparation, the two walks back), and by ka_tracking.hip for
-// the self-steering band of ka_ctc_best_path_tracking (section 4.32): what the two share lives here.
+// Included by ka_banded.hip, which holds the table's own kernels (preparation, the two walks back), by ka_tracking.hip for
+// the self-steering band of ka_ctc_best_path_tracking (section 4.32) and by ka_resume.hip for the caller's boundary conditions
+// of ka_ctc_best_path_resume (section 4.34): what the three share lives here, the table's check and the walks back included.
 //
 // The recurrence is ka_device.hpp's with ONE change: the band's low end comes from a table,
 //   frame t:  lo = band_lo[t], hi = min(lo + B, L)         (align.py:64-65 replaced; everything else align.py:62-107)
@@ -53,6 +54,29 @@ __device__ __forceinline__ void prep_labels(const BandLattice &d, int32_t *m)
     if (zero) atomicOr(&m[2], kFlagZeroLabel);
 }
 
+// the band table of one lattice: validate (in range and non-decreasing), shift, pad (every thread of a 256-thread workgroup);
+// false, with the lattice flagged, for an invalid table
+__device__ __forceinline__ bool prep_band_table(const BandLattice &d, int32_t *m)
+{
+    int bad_tab = 0;
+    for (int i = threadIdx.x; i < d.T; i += blockDim.x) {
+        const int v = d.band_lo[i];
+        if (v < 0 || v >= d.L) bad_tab = 1;
+        if (i > 0 && d.band_lo[i - 1] > v) bad_tab = 1;
+    }
+    if (__syncthreads_or(bad_tab)) {
+        if (threadIdx.x == 0) {
+            atomicMin(&m[0], kStatusBadArgs);
+            atomicOr(&m[2], kBandFlagBadTable);
+            m[1] = -1;
+        }
+        return false;
+    }
+    if (d.tab)
+        for (int i = threadIdx.x; i < d.tab_len; i += blockDim.x) d.tab[i] = d.band_lo[i + 1 < d.T ? i + 1 : d.T - 1];
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------
 // where the band's low end comes from: the frame loops below ask a policy for the low end of frame t+1 while sc[] / pres2
 // hold the cells of frame t-1
@@ -88,9 +112,23 @@ __device__ __forceinline__ int wave_best_live(const float (&sc)[16], uint32_t pr
     return (h | l) == 0u ? -1 : (int)~l;
 }
 
+// the highest live position of a wavefront's ring, -1 without a live cell
+__device__ __forceinline__ int wave_highest_live(uint32_t pres2, int blk)
+{
+    int best = -1;
+    if (pres2) best = blk * 16 + ((31 - __clz((int)pres2)) >> 1);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const int o = __shfl_xor(best, off);
+        best = o > best ? o : best;
+    }
+    return best;
+}
+
 // the caller's table: prep shifted and padded it, one aligned scalar load per group of four frames, a group ahead of its use
 struct BandFromTable {
     static constexpr bool kTracking = false;
+    static constexpr bool kStart = false;   // the lattice's boundary conditions are the reference's (BandResume: the caller's)
     typedef v4i_t Group;   // low ends of the four frames behind a group's first
     cc4_t tab;
     v4i_t step_next;
@@ -122,6 +160,7 @@ struct BandFromTable {
 // a group share one low end, which lanes 0..3 write to the table the call returns (band_lo, here an output).
 struct BandTracking {
     static constexpr bool kTracking = true;
+    static constexpr bool kStart = false;
     struct Group {};
     uint32_t period, next_rt;
     int end_rule;
@@ -159,6 +198,73 @@ struct BandTracking {
     __device__ __forceinline__ bool end_at_best() const { return end_rule == 1; }
 };
 
+// a score row's cell as the kernels hold it: a NaN (found by its bits: the library is built with -fno-honor-nans) is a dead
+// cell, which enters sc[] as -inf with its liveness bit clear; -inf is a LIVE cell of score -inf
+__device__ __forceinline__ bool row_cell_live(uint32_t bits) { return (bits & 0x7fffffffu) <= 0x7f800000u; }
+__device__ __forceinline__ float row_cell_score(uint32_t bits) { return __builtin_bit_cast(float, row_cell_live(bits) ? bits : 0xff800000u); }
+
+// the caller's table under the caller's boundary conditions (ka_ctc_best_path_resume): the state before
+// frame 0 is a score row (no band applies to it), the path ends at the reference's cell, the best cell or a given cell, and the
+// live cells after frame T-1 go out as a row.  The frame loop is BandFromTable's: the start row touches the prologue and the
+// re-labelling block of frame 0 (forward_banded_wave), the rest the epilogue.
+struct BandResume : BandFromTable {
+    static constexpr bool kStart = true;
+    gcu32_t init;   // [L] the start row's bits, or NULL: the virtual state {0: 0.0}
+    gf32_t fin;     // [L] the last row (prep filled it with kDeadScoreBits), or NULL
+    int end;        // ResumeRows::end, wave-uniform
+    // cells of block `blk` before frame 0.  The ring holds the 64 blocks from lo_0 >> 4: every cell frame 0 reads but the three
+    // below the lowest block (start_halos), and none at or above L.
+    __device__ __forceinline__ uint32_t start_row(float (&sc)[16], int blk, uint32_t L) const
+    {
+        uint32_t pres2 = 0u;
+        if (!init) {
+            if (blk == 0) {
+                sc[0] = 0.0f;
+                pres2 = 1u;
+            }
+            return pres2;
+        }
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const uint32_t p = (uint32_t)blk * 16u + (uint32_t)k;
+            if (p < L) {
+                const uint32_t b = init[p];
+                sc[k] = row_cell_score(b);
+                pres2 |= row_cell_live(b) ? 1u << (2 * k) : 0u;
+            }
+        }
+        return pres2;
+    }
+    // frame 0's halo of the lane that owns the ring's lowest block: its left neighbour holds the block 64 above, not the one
+    // below, so the three cells come from the row itself (every other lane's halo is its neighbour's, as in any frame)
+    __device__ __forceinline__ void start_halos(float &h1, float &h2, float &h3, int blk, uint32_t blo) const
+    {
+        if (init && blo > 0u && blk == (int)blo) {
+            const uint32_t p = blo * 16u;
+            const uint32_t b1 = init[p - 1], b2 = init[p - 2], b3 = init[p - 3];
+            h1 = row_cell_score(b1);
+            h2 = row_cell_score(b2);
+            h3 = row_cell_score(b3);
+        }
+    }
+    __device__ __forceinline__ bool end_at_best() const { return end == -2; }
+    __device__ __forceinline__ bool end_given() const { return end >= 0; }
+    // the caller's end cell if it is live after the last frame (pres2 of the lane that holds its block), else -1
+    __device__ __forceinline__ int end_cell(uint32_t pres2, int blk) const
+    {
+        const bool live = (end >> 4) == blk && ((pres2 >> (2 * (end & 15))) & 1u) != 0u;
+        return __builtin_amdgcn_ballot_w64(live) ? end : -1;
+    }
+    // the live cells after frame T-1 (a live cell lies in the last band, so below L)
+    __device__ __forceinline__ void last_row(const float (&sc)[16], uint32_t pres2, int blk) const
+    {
+        if (!fin) return;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if ((pres2 >> (2 * k)) & 1u) fin[(size_t)blk * 16 + (size_t)k] = sc[k];
+    }
+};
+
 // ---------------------------------------------------------------------------------------
 // forward DP, one wavefront per lattice, every cell's code stored
 // ---------------------------------------------------------------------------------------
@@ -181,11 +287,18 @@ __device__ __forceinline__ void forward_banded_wave(const BandLattice &d, int32_
     float sc[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) sc[k] = NINF;
-    // virtual state before frame 0 (align.py:57-58): position 0, which a lane holds only while block 0 is on the ring
-    const bool holds0 = blk == 0;
-    if (holds0) sc[0] = 0.0f;
-    uint32_t pres2 = holds0 ? 1u : 0u;      // bit 2k: cell k holds a live state
-    bool pend_reset = false;                // wave-uniform: lanes were re-labelled for this frame
+    uint32_t pres2;                         // bit 2k: cell k holds a live state
+    if constexpr (Src::kStart) {
+        pres2 = src.start_row(sc, blk, L);  // the caller's state before frame 0
+    } else {
+        // virtual state before frame 0 (align.py:57-58): position 0, which a lane holds only while block 0 is on the ring
+        const bool holds0 = blk == 0;
+        if (holds0) sc[0] = 0.0f;
+        pres2 = holds0 ? 1u : 0u;
+    }
+    // wave-uniform: lanes were re-labelled for this frame.  A start row takes frame 0 through that block, with no lane reset:
+    // it kills the wrapped halo of the lane that owns the lowest block and puts the row's own three cells there.
+    bool pend_reset = Src::kStart;
     bool reset_lane = false;                // per lane: this lane was re-labelled
 
     int la[8];
@@ -246,6 +359,9 @@ __device__ __forceinline__ void forward_banded_wave(const BandLattice &d, int32_
                     h1 = kill ? NINF : h1;
                     h2 = kill ? NINF : h2;
                     h3 = kill ? NINF : h3;
+                    if constexpr (Src::kStart) {
+                        if (dd == 0 && tb == 0) src.start_halos(h1, h2, h3, blk, blo);
+                    }
 #pragma unroll
                     for (int k = 0; k < 16; ++k) sc[k] = reset_lane ? NINF : sc[k];
                     pres2 = reset_lane ? 0u : pres2;
@@ -321,17 +437,18 @@ __device__ __forceinline__ void forward_banded_wave(const BandLattice &d, int32_
         }
         return;
     }
-    // terminal state: the HIGHEST live position of frame T-1 (align.py:99-101), or on request the tracking call's best one
-    int best = -1;
-    if (Src::kTracking && src.end_at_best()) {
+    if constexpr (Src::kStart) {
+        if (m[0] == kStatusOk) src.last_row(sc, pres2, blk);   // (a lattice with a bad label keeps the row prep wrote: all dead)
+    }
+    // terminal state: the HIGHEST live position of frame T-1 (align.py:99-101), or on request the tracking call's best one,
+    // or the resumed call's given one
+    int best;
+    if ((Src::kTracking || Src::kStart) && src.end_at_best()) {
         best = wave_best_live(sc, pres2, blk);
+    } else if constexpr (Src::kStart) {
+        best = src.end_given() ? src.end_cell(pres2, blk) : wave_highest_live(pres2, blk);
     } else {
-        if (pres2) best = blk * 16 + ((31 - __clz((int)pres2)) >> 1);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const int o = __shfl_xor(best, off);
-            best = o > best ? o : best;
-        }
+        best = wave_highest_live(pres2, blk);
     }
     if (best < 0) {
         if (lane == 0) {
@@ -400,8 +517,11 @@ __device__ __forceinline__ unsigned long long block_best_live(const float *sc, c
 
 // kTrack: the self-steering band of BandTracking instead of the table.  The arg-max of frame t-2 is taken at the end of frame
 // t-2, when its column is the current one, and held in shared memory for two frames; thread 0 writes the table.
-template <bool kTrack>
-__device__ __forceinline__ void forward_banded_generic(const BandLattice &d, int32_t *meta, int period, int end_rule)
+// kStart: the resumed call's boundary conditions (BandResume's, `rr` the lattice's rows): the start row goes into the first
+// column with every position open, the last row comes out of the last column's band.
+template <bool kTrack, bool kStart = false>
+__device__ __forceinline__ void forward_banded_generic(const BandLattice &d, int32_t *meta, int period, int end_rule,
+                                                       const ResumeRows *rr = nullptr)
 {
     const int tid = threadIdx.x;
     int32_t *m = meta_of(meta, d.idx);
@@ -427,9 +547,20 @@ __device__ __forceinline__ void forward_banded_generic(const BandLattice &d, int
     uint8_t *bp = reinterpret_cast<uint8_t *>(d.bp);
     for (int64_t p = tid; p < L; p += 256) { prA[p] = 0; prB[p] = 0; }
     __syncthreads();
-    if (tid == 0) { scA[0] = 0.0f; prA[0] = 1; }
-    __syncthreads();
     int64_t plo = 0, phi = 1;
+    if (kStart && rr->init) {
+        const uint32_t *init = reinterpret_cast<const uint32_t *>(rr->init);
+        for (int64_t p = tid; p < L; p += 256) {
+            const uint32_t b = init[p];
+            scA[p] = row_cell_score(b);
+            prA[p] = row_cell_live(b) ? 1 : 0;
+        }
+        phi = L;
+    } else if (tid == 0) {
+        scA[0] = 0.0f;
+        prA[0] = 1;
+    }
+    __syncthreads();
     __shared__ unsigned long long s_key;
     int64_t lo_track = 0;
     for (int64_t t = 0; t < T; ++t) {
@@ -470,9 +601,18 @@ __device__ __forceinline__ void forward_banded_generic(const BandLattice &d, int
         phi = hi;
         if (kTrack && t + 2 < T && (t + 2) % period == 0) block_best_live(scA, prA, plo, phi, &s_key);
     }
-    // highest live position of the last frame (the tracking call's end rule 1: the best one)
+    if constexpr (kStart) {
+        if (rr->fin && m[0] == kStatusOk)   // (a lattice with a bad label keeps the row prep wrote: all dead)
+            for (int64_t p = plo + tid; p < phi; p += 256)
+                if (prA[p]) rr->fin[p] = scA[p];
+    }
+    // highest live position of the last frame (the tracking call's end rule 1 and the resumed call's end -2: the best one; the
+    // resumed call's end >= 0: that cell if it is live)
     __shared__ int64_t s_best;
-    if (kTrack && end_rule == 1) {
+    if (kStart && rr->end >= 0) {
+        const int64_t q = rr->end;
+        if (tid == 0) s_best = (q >= plo && q < phi && prA[q]) ? q : -1;
+    } else if ((kTrack && end_rule == 1) || (kStart && rr->end == -2)) {
         const unsigned long long k = block_best_live(scA, prA, plo, phi, &s_key);
         if (tid == 0) s_best = k ? (int64_t)(uint32_t)~(uint32_t)k : -1;
     } else {
@@ -493,6 +633,98 @@ __device__ __forceinline__ void forward_banded_generic(const BandLattice &d, int
             m[3] = __builtin_bit_cast(int32_t, scA[s_best]);
         }
     }
+}
+
+
+// ---------------------------------------------------------------------------------------
+// the walk back, one wavefront per lattice: path, labels and scores of 16 frames at a time.  Returns the position
+// before frame 0 (the cell of the start state the path left from), -1 without a path.
+//
+// A path drops at most 3 positions per frame.  The chunk entered at position p (its last frame) stays within [p - 45, p];
+// the chunk below it within [p - 93, p]: its window of 8 blocks from block (p - 96) >> 4 is loaded while the current
+// chunk is walked.  Window register r[v]: lane = (f & 7) * 8 + j holds the code dword of frame 8 v + (f & 7), block j.
+// ---------------------------------------------------------------------------------------
+constexpr int kBandBtChunk = 16;
+__device__ __forceinline__ int band_bt_window(int p_entry)
+{
+    const int lo = p_entry - 6 * kBandBtChunk;
+    return (lo > 0 ? lo : 0) >> 4;
+}
+__device__ __forceinline__ void band_bt_load(uint32_t (&r)[2], gcu32_t bp, int t0, int n, int w0, int lane)
+{
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+        const int f = 8 * v + (lane >> 3);
+        const int t = t0 + f;
+        const size_t at = (size_t)(t >> 2) * 256 + (size_t)((w0 + (lane & 7)) & 63) * 4 + (size_t)(t & 3);
+        r[v] = f < n ? bp[at] : 0u;
+    }
+}
+__device__ __forceinline__ int backtrace_banded_wave(const BandLattice &d, const int32_t *meta)
+{
+    const int lane = threadIdx.x;
+    int p = __builtin_amdgcn_readfirstlane(meta[4 * (size_t)d.idx + 1]);
+    if (p < 0) return -1;   // no path: the status says why
+    const int T = __builtin_amdgcn_readfirstlane(d.T);
+    gcu32_t bp = (gcu32_t)d.bp;
+    gci32_t labx = (gci32_t)d.labx;
+    gcf32_t lp = (gcf32_t)d.lp;
+    const size_t ld = (size_t)d.ld;
+    int t0 = ((T - 1) / kBandBtChunk) * kBandBtChunk;
+    int n = T - t0;
+    int w = band_bt_window(p + 3 * kBandBtChunk);   // the tail chunk is entered at the end position itself
+    uint32_t cur[2], nxt[2] = {0u, 0u};
+    band_bt_load(cur, bp, t0, n, w, lane);
+    for (;;) {
+        const int t1 = t0 - kBandBtChunk;
+        const int wn = band_bt_window(p);
+        if (t1 >= 0) band_bt_load(nxt, bp, t1, kBandBtChunk, wn, lane);
+        const uint32_t c0 = blank_to_uniform(cur[0]), c1 = blank_to_uniform(cur[1]);
+        int q = p - 16 * w;   // position relative to the window: 0 .. 127
+        int pathv = 0;
+#pragma unroll
+        for (int f = kBandBtChunk - 1; f >= 0; --f) {
+            if (f < n) {
+                const uint32_t word = (uint32_t)__builtin_amdgcn_readlane((int)(f >= 8 ? c1 : c0), (f & 7) * 8 + (q >> 4));
+                pathv = lane == f ? q : pathv;
+                q -= bp_decode(word >> ((q * 2) & 31));
+            }
+        }
+        if (lane < n) {
+            const int pos = pathv + 16 * w;
+            const int t = t0 + lane;
+            const int lab = (pos & 1) ? (labx[pos >> 1] >> 2) : 0;
+            ((gi32_t)d.path)[t] = pos;
+            ((gi32_t)d.lab_out)[t] = lab;
+            ((gf32_t)d.sc_out)[t] = lp[(size_t)t * ld + (size_t)lab];
+        }
+        p = q + 16 * w;
+        if (t1 < 0) break;
+        cur[0] = nxt[0];
+        cur[1] = nxt[1];
+        w = wn;
+        t0 = t1;
+        n = kBandBtChunk;
+    }
+    return p;
+}
+
+// the generic form's walk back, by thread 0, which returns the position before frame 0 (every other thread, and a lattice
+// without a path: -1)
+__device__ __forceinline__ int64_t backtrace_banded_generic(const BandLattice &d, const int32_t *meta)
+{
+    int64_t p = meta[4 * (size_t)d.idx + 1];
+    if (p < 0 || threadIdx.x != 0) return -1;
+    const int64_t T = d.T, W = d.W;
+    const uint8_t *bp = reinterpret_cast<const uint8_t *>(d.bp);
+    for (int64_t t = T - 1; t >= 0; --t) {
+        const int lab = (p & 1) ? (d.labx[p >> 1] >> 2) : 0;
+        d.path[t] = (int32_t)p;
+        d.lab_out[t] = lab;
+        d.sc_out[t] = d.lp[(size_t)t * (size_t)d.ld + (size_t)lab];
+        p -= bp[(size_t)t * (size_t)W + (size_t)(p - d.band_lo[t])];
+    }
+    return p;
 }
 
 }  // namespace ka

@@ -133,5 +133,9 @@ void launch_backtrace_banded(const BandLattice *lats, int n_fast, int n_generic,
 // the table the forward kernels WRITE; period a multiple of 4, end_rule 0 (highest live position) or 1 (best live position) ----
 void launch_best_path_tracking(const BandLattice *lats, int n_fast, int n_generic, int max_move, int period, int end_rule, int32_t *meta,
                                hipStream_t s);
+// ---- ka_resume.hip: the resumable best path (ka_banded.hpp's BandResume): the same descriptors and, in their order, a
+// ResumeRows per lattice: start row, last row, end cell or rule, and where the walk back puts the cell it ends on ----
+void launch_best_path_resume(const BandLattice *lats, const ResumeRows *rows, int n_fast, int n_generic, int max_move, int32_t *meta,
+                             hipStream_t s);
 
 }  // namespace ka

@@ -295,4 +295,16 @@ struct BandLattice {
 };
 static_assert(sizeof(BandLattice) == 128, "descriptor sizes");
 
+// ---- ... resumed (ka_ctc_best_path_resume): what the call adds to a lattice, one entry per descriptor
+// and in the descriptors' order ----
+constexpr uint32_t kDeadScoreBits = 0x7fc00000u;   // the quiet NaN a dead cell of a score row holds
+struct ResumeRows {
+    const float *init;   // [L] the score row before frame 0 (device), NaN = dead; NULL: the virtual state {0: 0.0}
+    float *fin;          // [L] the score row after frame T-1 (device), NaN = dead; NULL: not wanted
+    int32_t *entry;      // one int32 (device, preset to -1): the cell of the start row the path left from
+    int32_t end;         // -1: the highest live cell, -2: the best live cell, p >= 0: that cell
+    int32_t pad;
+};
+static_assert(sizeof(ResumeRows) == 32, "descriptor sizes");
+
 }  // namespace ka
