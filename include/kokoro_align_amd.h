@@ -509,6 +509,67 @@ size_t ka_resume_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, 
                                  int32_t mem);
 
 /*
+ * Resumable tracking best path: ka_ctc_best_path_tracking under ka_ctc_best_path_resume's boundary
+ * conditions, plus one value in and one value out, so that a self-steering band crosses a cut: a long recording is aligned
+ * chunk by chunk, in the memory of one chunk, without a table known in advance.  L = 2S+1, B = beam_size, P = period.
+ *   init_scores, end, final_scores, entry, total_score
+ *                 exactly as in ka_ctc_best_path_resume: a NaN is a dead cell, -inf a live cell, a +inf that lattice's
+ *                 KA_ERR_BAD_ARGS, found by the preparation kernel; no band applies to the start row; end is -1, -2 or a
+ *                 position (it replaces ka_ctc_best_path_tracking's end_rule: -2 is end_rule 1); the last row holds 0x7fc00000
+ *                 in dead cells and is all dead for a lattice that failed; entry is -1 without a path, 0 for a NULL row.
+ *   first_lo      int32 (batch: a HOST array of n, NULL = all 0): lo_0, the band of the chunk's frame 0.  A value outside
+ *                 [0, L) is KA_ERR_BAD_ARGS before anything is launched or written.
+ *   retargets     fall on the chunk's OWN frames t > 0 with t % P == 0, by ka_ctc_best_path_tracking's rule, unchanged: c = the
+ *                 first maximum of the float32 scores after local frame t-2 over the live cells in ascending position,
+ *                 lo_t = min(max(lo_{t-1}, c - B / 2), L - 1); no live cell keeps lo_{t-1}.  Frame 0 never retargets: its band
+ *                 is first_lo.  (A chunk of the caller's therefore continues an uncut call only if it starts at a multiple of P.)
+ *   band_lo_out   [T] the table walked, as in the tracking call.  Required.
+ *   next_lo       int32 output, HOST memory in both modes (batch: [n]); may be NULL.  The low end local frame T would get:
+ *                 if T % P == 0 the retarget rule applied to lo_{T-1} and the scores after frame T-2, else lo_{T-1}.  It is the
+ *                 first_lo of a call on the frames that follow.  -1 for a lattice that ends in KA_ERR_BAD_LABEL, KA_ERR_NAN or
+ *                 KA_ERR_BAD_ARGS.  A lattice that ends in KA_ERR_EMPTY_BEAM (its forward pass ran to the last frame: a dead
+ *                 end cell, or no live cell at all) still gets its table and next_lo, like final_scores.
+ *   period        a multiple of 4 in [4, 65536], else KA_ERR_BAD_ARGS before anything is launched.
+ * Statuses, forms, limits, memory modes, return convention and stream synchronisation are those of the two parent calls.
+ * ka_ctc_best_path_tracking's property 4 (never KA_ERR_EMPTY_BEAM) does NOT carry over: a start row without a live cell in
+ * reach of [first_lo, first_lo + B) (a NULL row with first_lo >= max_move, for one) and a given end that is dead both end there.
+ * What follows, exactly, bit for bit:
+ *   1. with init_scores NULL, first_lo 0, final_scores NULL and end -1 or -2, every output (path, labels, scores, table, total
+ *      score, status) is ka_ctc_best_path_tracking's for end_rule 0 or 1;
+ *   2. cut and resume: for any k in [P, T) with k % P == 0, chunk A = frames [0, k), chunk B = frames [k, T) with init_scores =
+ *      A's final_scores, first_lo = A's next_lo and the uncut call's end, then A again with end = B's entry: the tables, paths,
+ *      label and score arrays concatenated are the uncut tracking call's; B's total_score, final_scores and next_lo are those of
+ *      the uncut call run through this entry point; where the uncut call fails, A or B fails too.  (A's next_lo is the uncut
+ *      lo_k because the retarget at global frame k reads the scores after frame k-2, which A holds when it computes next_lo,
+ *      and B's own retargets fall on global multiples of P because k is one.)
+ *   3. ka_ctc_best_path_resume over a chunk's returned table, with the same start row and end, returns that chunk's path,
+ *      labels, scores, total score, entry and last row (ctc_best_path_tracking_chunked's second sweep relies on it);
+ *   4. a lattice gives the same bits alone or inside a batch, whatever its neighbours' rows, ends and first_lo are.
+ * Cost: the frame loop is the tracking call's; next_lo is computed in the once-per-period retarget branch, for the last frame
+ * only; the start and last rows are O(L) once per call.  Measured against ka_ctc_best_path_tracking_batch_f32 of the same build
+ * (tools/bench_tracking_resume.py, profiles/tracking_resume_bench.jsonl; MI355X, cfg2): one lattice 0.975 times that call with NULL
+ * rows and 0.976 with a start row, a last row, a given end and next_lo at period 16 (30.44 and 30.49 against 31.24 ms), 0.972 and
+ * 0.974 at period 64; 1024 lattices 0.976 and 0.974 at period 16 (33.06 and 33.01 against 33.88 ms), 0.975 and 0.974 at period 64.
+ * One lattice in 8 chunks that resume from each other (ctc_best_path_tracking_chunked) costs 1.866 times the uncut tracking call at
+ * period 16 and 1.912 times at period 64, against (2 - 1/8) forward passes, and needs the move codes of one chunk.
+ */
+int ka_ctc_best_path_tracking_resume_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                         int32_t beam_size, int32_t max_move, int32_t period, int32_t first_lo, const float *init_scores,
+                                         int32_t end, int32_t *best_path, int32_t *best_labels, float *best_scores, int32_t *band_lo_out,
+                                         float *final_scores, int32_t *entry, int32_t *next_lo, float *total_score, int32_t mem, void *stream);
+int ka_ctc_best_path_tracking_resume_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                               const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                               int32_t max_move, int32_t period, const int32_t *first_lo, const float *const *init_scores,
+                                               const int32_t *end, int32_t *const *best_path, int32_t *const *best_labels,
+                                               float *const *best_scores, int32_t *const *band_lo_out, float *const *final_scores,
+                                               int32_t *entry, int32_t *next_lo, float *total_score, int32_t *status, int32_t mem, void *stream);
+/* device-workspace bytes such a call carves (0 for unsupported arguments): ka_tracking_workspace_bytes plus 40 bytes per lattice
+ * (its rows' descriptor, entry cell and next_lo cell, rounded up for the batch) and, for KA_MEM_HOST, the two staged rows of
+ * every lattice */
+size_t ka_tracking_resume_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                          int32_t mem);
+
+/*
  * Best-path margins from max-marginals: how much score the best alignment would lose if, at frame t, it had to be somewhere
  * else.  The best path's own recurrence in max-plus arithmetic, run forwards (D) and backwards (E): adds and compares only, no
  * transcendental, float64 throughout, so every output is defined bit for bit by IEEE add and max.

@@ -9,7 +9,8 @@ plus batched / device-resident entry points (ctc_best_path_batch, ctc_best_path_
 gives (ctc_best_path_banded[_batch|_device], diagonal_band, anchored_band, band_around_path, band_edge_contact) or that steers
 itself by the scores and returns the table it walked (ctc_best_path_tracking[_batch|_device]), or started from a score row,
 ended at a chosen cell and resumable from the row it returns (ctc_best_path_resume[_batch|_device], free_start_scores,
-ctc_best_path_chunked) and the
+ctc_best_path_chunked), or both, so that the self-steering band crosses a cut (ctc_best_path_tracking_resume[_batch|_device],
+ctc_best_path_tracking_chunked), and the
 forward-backward quality signal of a best path (ctc_path_posteriors[_batch|_device], segment_confidence), the label
 occupancy of every frame (ctc_label_posteriors[_batch|_device], segment_agreement), the differentiable lattice
 log-likelihood (lattice_log_likelihood) and the state posteriors at chosen frames behind the confidence of align()'s text
@@ -47,7 +48,11 @@ from .align import (  # noqa: F401
     ctc_best_path_resume_device,
     ctc_best_path_tracking,
     ctc_best_path_tracking_batch,
+    ctc_best_path_tracking_chunked,
     ctc_best_path_tracking_device,
+    ctc_best_path_tracking_resume,
+    ctc_best_path_tracking_resume_batch,
+    ctc_best_path_tracking_resume_device,
     diagonal_band,
     free_start_scores,
     log_softmax_device,

@@ -56,6 +56,7 @@ EXPORTS = [
     "ka_ctc_mea_path_banded_f32", "ka_ctc_mea_path_banded_batch_f32", "ka_boundary_quantile_band_table_workspace_bytes",
     "ka_ctc_best_path_tracking_f32", "ka_ctc_best_path_tracking_batch_f32", "ka_tracking_workspace_bytes",
     "ka_ctc_best_path_resume_f32", "ka_ctc_best_path_resume_batch_f32", "ka_resume_workspace_bytes",
+    "ka_ctc_best_path_tracking_resume_f32", "ka_ctc_best_path_tracking_resume_batch_f32", "ka_tracking_resume_workspace_bytes",
     "ka_ctc_path_margins_f32", "ka_ctc_path_margins_batch_f32", "ka_path_margin_workspace_bytes",
 ]
 
@@ -185,6 +186,14 @@ def load_library():
     L.ka_ctc_best_path_resume_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pp, pp, vp, pp, pp, pp, pp, vp, vp, vp, i32, vp]
     L.ka_resume_workspace_bytes.restype = sz
     L.ka_resume_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
+    L.ka_ctc_best_path_tracking_resume_f32.restype = ctypes.c_int
+    L.ka_ctc_best_path_tracking_resume_f32.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                       i32, vp]
+    L.ka_ctc_best_path_tracking_resume_batch_f32.restype = ctypes.c_int
+    L.ka_ctc_best_path_tracking_resume_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, i32, vp, pp, vp, pp, pp, pp, pp, pp,
+                                                             vp, vp, vp, vp, i32, vp]
+    L.ka_tracking_resume_workspace_bytes.restype = sz
+    L.ka_tracking_resume_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
     # the table (a pointer, or an array of pointers) may be NULL, and so may runner_up
     L.ka_ctc_path_margins_f32.restype = ctypes.c_int
     L.ka_ctc_path_margins_f32.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp]

@@ -8,8 +8,9 @@
 plus what the reference has no name for: many lattices in one launch (ctc_best_path_batch, DeviceBatch,
 ctc_best_path_device), the log-softmax of align.py:116-117 on the device (log_softmax_device) and the best path over a band
 the caller gives (ctc_best_path_banded[_batch|_device] with the tables diagonal_band, anchored_band, band_around_path and the
-diagnostic band_edge_contact), over a band that steers itself (ctc_best_path_tracking[_batch|_device]) and the banded best path
-with the caller's boundary conditions (ctc_best_path_resume[_batch|_device], free_start_scores, ctc_best_path_chunked).
+diagnostic band_edge_contact), over a band that steers itself (ctc_best_path_tracking[_batch|_device]), the banded best path
+with the caller's boundary conditions (ctc_best_path_resume[_batch|_device], free_start_scores, ctc_best_path_chunked) and the
+two together (ctc_best_path_tracking_resume[_batch|_device], ctc_best_path_tracking_chunked).
 
 The DP + backtrace (the reference's per-frame NumPy loop) run in the HIP library through the C
 ABI of include/kokoro_align_amd.h.  NumPy arrays are handed over as host buffers; torch tensors
@@ -76,11 +77,13 @@ _BEST_PATH_CALLS = {
     "_banded": ((np.int32, np.int32, np.float32), (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_BAD_ARGS)),
     "_tracking": ((np.int32, np.int32, np.float32, np.int32), (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN)),
     "_resume": ((np.int32, np.int32, np.float32), (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_BAD_ARGS)),
+    "_tracking_resume": ((np.int32, np.int32, np.float32, np.int32),
+                         (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_BAD_ARGS)),
 }
 
 
 def _run_best_path(lat, call, beam_size, max_move, own_args, outputs, return_status, more_outputs=()):
-    """The call ``ka_ctc_best_path<call>_batch_f32`` ("", "_banded", "_tracking", "_resume"): the arguments all take, ``own_args``
+    """The call ``ka_ctc_best_path<call>_batch_f32`` ("", "_banded", "_tracking", "_resume", "_tracking_resume"): the arguments all take, ``own_args``
     behind ``max_move`` (the band tables; period and end rule; start rows and ends), then the outputs (paths, labels, scores and,
     for tracking, the tables walked: allocated here, or the caller's ``outputs`` after a check), ``more_outputs`` as they are
     (the resumed call's last rows and entries), totals and statuses, and the status handling of ``return_status``.
@@ -396,13 +399,18 @@ def _score_rows(lat, rows):
     return out
 
 
-def _best_path_resume(lat, band_lo, init_scores, end, beam_size, max_move, final_scores, return_status):
-    tables = _band_tables(lat, band_lo)         # (held until the call has returned, like the rows: the addresses below are theirs)
-    rows = _score_rows(lat, init_scores)
+def _end_cells(lat, end):
+    """The ends of a resumed call: one value for all lattices or one per lattice, rule names or positions -> int32 [n]."""
     ends = [end] * lat.n if isinstance(end, (str, int, np.integer)) else list(end)
     if len(ends) != lat.n:
         raise ValueError("end must be one value or one per lattice")
-    ends = np.array([END_CELLS[x] if isinstance(x, str) else int(x) for x in ends], np.int32)
+    return np.array([END_CELLS[x] if isinstance(x, str) else int(x) for x in ends], np.int32)
+
+
+def _best_path_resume(lat, band_lo, init_scores, end, beam_size, max_move, final_scores, return_status):
+    tables = _band_tables(lat, band_lo)         # (held until the call has returned, like the rows: the addresses below are theirs)
+    rows = _score_rows(lat, init_scores)
+    ends = _end_cells(lat, end)
     last = [lat.empty((2 * S + 1,), np.float32) for S in lat.S] if final_scores else None
     entry = np.full(lat.n, -1, np.int32)
     p_band, _k1 = _ptr_array([lat.ptr(x) for x in tables])
@@ -501,6 +509,112 @@ def ctc_best_path_chunked(log_probs, labels, band_lo, chunk_frames, beam_size=10
     return tuple(np.concatenate([p[i] for p in parts]) for i in range(3))
 
 
+# ------------------------------------------------------------------------------------------
+# resumable tracking best path: the self-steering band under the caller's boundary conditions
+# ------------------------------------------------------------------------------------------
+def _best_path_tracking_resume(lat, first_lo, init_scores, end, beam_size, max_move, period, final_scores, return_status):
+    rows = _score_rows(lat, init_scores)        # (held until the call has returned: the addresses below are theirs)
+    ends = _end_cells(lat, end)
+    first = [first_lo] * lat.n if isinstance(first_lo, (int, np.integer)) else list(first_lo)
+    if len(first) != lat.n:
+        raise ValueError("first_lo must be one value or one per lattice")
+    first = np.array([int(x) for x in first], np.int32)
+    last = [lat.empty((2 * S + 1,), np.float32) for S in lat.S] if final_scores else None
+    entry = np.full(lat.n, -1, np.int32)
+    next_lo = np.full(lat.n, -1, np.int32)
+    p_init, _k1 = _ptr_array([None if x is None else lat.ptr(x) for x in rows])
+    p_last, _k2 = _ptr_array([lat.ptr(x) for x in last]) if final_scores else (None, None)
+    out = _run_best_path(lat, "_tracking_resume", beam_size, max_move, (int(period), first.ctypes.data, p_init, ends.ctypes.data), None,
+                         return_status, (p_last, entry.ctypes.data, next_lo.ctypes.data))
+    results = out[0] if return_status else out
+    results = [r + (int(entry[i]), last[i] if final_scores else None, int(next_lo[i])) for i, r in enumerate(results)]
+    return (results,) + tuple(out[1:]) if return_status else results
+
+
+def ctc_best_path_tracking_resume_batch(log_probs_list, labels_list, first_lo=0, init_scores_list=None, end="highest", beam_size=1000,
+                                        max_move=4, period=16, device=None, return_status=False, final_scores=True):
+    """``ctc_best_path_tracking_resume`` for a list of lattices in one call.  Host NumPy buffers in and out: a list of (best_path,
+    best_labels, best_scores, band_lo, entry, final_scores, next_lo).  ``first_lo`` and ``end``: one value for all or one per
+    lattice; ``init_scores_list``: None, or per lattice None or a row.  With ``return_status`` failures of single lattices do not
+    raise and (results, statuses, totals) are returned; a failed lattice's path arrays are not written, its entry is -1, its last
+    row is written (all NaN unless its forward pass ran) and its next_lo is -1 unless its forward pass ran (status -1: then its
+    table is written too).  ``final_scores=False`` asks for no last rows (None in the results)."""
+    lat = _host_lattices(log_probs_list, labels_list, None, None, device)
+    if lat is None:
+        return ([], [], []) if return_status else []
+    return _best_path_tracking_resume(lat, first_lo, init_scores_list, end, beam_size, max_move, period, final_scores, return_status)
+
+
+def ctc_best_path_tracking_resume_device(log_probs, labels, first_lo=0, init_scores=None, end="highest", beam_size=1000, max_move=4,
+                                         period=16, return_status=False, final_scores=True):
+    """``ctc_best_path_tracking_resume_batch`` on lists of ROCm torch tensors (labels and rows may also be NumPy arrays): paths,
+    labels, scores, tables and last rows stay on the device; the entries and next_lo are Python integers."""
+    lat = _device_lattices(log_probs, labels, None, None)
+    return _best_path_tracking_resume(lat, first_lo, init_scores, end, beam_size, max_move, period, final_scores, return_status)
+
+
+def ctc_best_path_tracking_resume(log_probs, labels, first_lo=0, init_scores=None, end="highest", beam_size=1000, max_move=4, period=16):
+    """``ctc_best_path_tracking`` under ``ctc_best_path_resume``'s boundary conditions, so that the self-steering band crosses a
+    cut: started from the score row ``init_scores`` with the band of frame 0 at ``first_lo``, ended by ``end`` ("highest", "best"
+    or a position), returning (best_path, best_labels, best_scores, band_lo, entry, final_scores, next_lo).  ``next_lo`` is the
+    low end the frame behind the last would get: with ``final_scores`` it is what a call on the frames that follow starts from
+    (``first_lo=``, ``init_scores=``), and if this chunk's length is a multiple of ``period`` that call continues the uncut one bit
+    for bit (``ctc_best_path_tracking_chunked``).  The retargets fall on the chunk's own frames t > 0 with t % period == 0; frame 0
+    never retargets.  With 0, None every array is ``ctc_best_path_tracking``'s.  Unlike that call this one can raise ValueError
+    for an empty beam: a start row out of the first band's reach, or an end cell that is not live.
+    NumPy in -> NumPy out; ROCm torch tensors in -> torch tensors out."""
+    if _is_tensor(log_probs):
+        return ctc_best_path_tracking_resume_device([log_probs], [labels], first_lo, [init_scores], end, beam_size, max_move, period)[0]
+    lp = np.asarray(log_probs)
+    if lp.ndim != 2:
+        raise ValueError("log_probs must be [T, V]")
+    return ctc_best_path_tracking_resume_batch([lp], [labels], first_lo, [init_scores], end, beam_size, max_move, period)[0]
+
+
+def ctc_best_path_tracking_chunked(log_probs, labels, chunk_frames, beam_size=1000, max_move=4, period=16, end_rule="highest"):
+    """``ctc_best_path_tracking`` in chunks of ``chunk_frames`` frames, a positive multiple of ``period`` (ValueError otherwise: a
+    chunk's retargets fall on its own multiples of the period, so any other cut steers another band): the same (best_path,
+    best_labels, best_scores, band_lo), bit for bit.  A forward sweep of ``ctc_best_path_tracking_resume`` runs the chunks in
+    order, each from the row and the low end the one before it ended with, and keeps every chunk's start row and table; the last
+    chunk's path is taken at once; the earlier chunks are then run again, last to first, with ``ctc_best_path_resume`` over
+    their kept tables and ``end`` = the next chunk's ``entry``.  Cost: (2 - 1/chunks) forward passes instead of one.  What it
+    buys: move codes for ``chunk_frames`` frames instead of T, with no table known in advance."""
+    chunk_frames, period = int(chunk_frames), int(period)
+    if period < 4 or period % 4 != 0:
+        raise ValueError("period must be a multiple of 4 in [4, 65536]")
+    if chunk_frames < 1 or chunk_frames % period != 0:
+        raise ValueError("chunk_frames must be a positive multiple of period")
+    tensor = _is_tensor(log_probs)
+    if not tensor:
+        log_probs = np.asarray(log_probs)
+    if log_probs.ndim != 2:
+        raise ValueError("log_probs must be [T, V]")
+    T = int(log_probs.shape[0])
+    cuts = list(range(0, T, chunk_frames))
+    if not cuts:
+        raise IndexError("list index out of range")
+    end = END_RULES[end_rule] if isinstance(end_rule, str) else int(end_rule)
+    end = {0: "highest", 1: "best"}[end]
+
+    starts, tables, init, lo = [], [], None, 0
+    for a in cuts[:-1]:
+        starts.append(init)
+        r = ctc_best_path_tracking_resume(log_probs[a:a + chunk_frames], labels, lo, init, "highest", beam_size, max_move, period)
+        tables.append(r[3])
+        init, lo = r[5], r[6]
+    last = ctc_best_path_tracking_resume(log_probs[cuts[-1]:], labels, lo, init, end, beam_size, max_move, period)
+    parts, entry = [last[:4]], last[4]
+    for a, init, table in zip(reversed(cuts[:-1]), reversed(starts), reversed(tables)):
+        r = ctc_best_path_resume(log_probs[a:a + chunk_frames], labels, table, init, entry, beam_size, max_move)
+        parts.append(r[:3] + (table,))
+        entry = r[3]
+    parts.reverse()
+    if tensor:
+        import torch
+        return tuple(torch.cat([p[i] for p in parts]) for i in range(4))
+    return tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
+
+
 def log_softmax_device(logits, out=None):
     """Mean-subtracted log-softmax of align.py:116-117 on the device (HIP kernel), float32."""
     import torch
@@ -527,7 +641,7 @@ def _host_log_softmax(logits):
     return centred - np.log(np.sum(np.exp(centred), axis=-1, keepdims=True))
 
 
-def best_path(input_file, voca_file, output_file, device_softmax=False, track_period=None):
+def best_path(input_file, voca_file, output_file, device_softmax=False, track_period=None, track_chunk=None):
     """``*.logits.npz`` + ``*.voca.txt`` -> ``*.best_path.npz`` (reference: align.py:112-124).
 
     Keys/dtypes of the output: best_path int32, best_labels int32, best_scores float32.
@@ -536,6 +650,8 @@ def best_path(input_file, voca_file, output_file, device_softmax=False, track_pe
     host NumPy arithmetic bit for bit and hands the DP a host buffer.
     ``track_period``: a period for ``ctc_best_path_tracking`` instead of the reference's diagonal band; the table it walked is
     stored as a fourth key, band_lo int32 (``align`` reads its three keys as before).  None changes nothing.
+    ``track_chunk``: with ``track_period``, a chunk length (a multiple of the period) for ``ctc_best_path_tracking_chunked``: the
+    same file, bit for bit, from kernels that hold one chunk's move codes.
     """
     from .transcript import read_transcript
     with np.load(input_file) as f:
@@ -546,9 +662,13 @@ def best_path(input_file, voca_file, output_file, device_softmax=False, track_pe
             import torch
             dev = torch.device("cuda", _current_device())
             lp = log_softmax_device(torch.from_numpy(np.ascontiguousarray(logits, np.float32)).to(dev))
-            p, l, s, b = (x.cpu().numpy() for x in ctc_best_path_tracking(lp, labels, period=track_period))
         else:
-            p, l, s, b = ctc_best_path_tracking(_host_log_softmax(logits), labels, period=track_period)
+            lp = _host_log_softmax(logits)
+        if track_chunk is not None:
+            out = ctc_best_path_tracking_chunked(lp, labels, track_chunk, period=track_period)
+        else:
+            out = ctc_best_path_tracking(lp, labels, period=track_period)
+        p, l, s, b = (x.cpu().numpy() if _is_tensor(x) else x for x in out)
         np.savez(output_file, best_path=p, best_labels=l, best_scores=s, band_lo=b)
         return
     if device_softmax:

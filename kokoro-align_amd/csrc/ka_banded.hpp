@@ -1,7 +1,8 @@
 // ka_banded.hpp — best path over a caller-given band (ka_ctc_best_path_banded[_batch]_f32).
 // Included by ka_banded.hip, which holds the table's own kernels (preparation, the two walks back), by ka_tracking.hip for
-// the self-steering band of ka_ctc_best_path_tracking (section 4.32) and by ka_resume.hip for the caller's boundary conditions
-// of ka_ctc_best_path_resume (section 4.34): what the three share lives here, the table's check and the walks back included.
+// the self-steering band of ka_ctc_best_path_tracking (section 4.32), by ka_resume.hip for the caller's boundary conditions
+// of ka_ctc_best_path_resume (section 4.34) and by ka_tracking_resume.hip for the two together (section 4.35): what they share
+// lives here, the table's check and the walks back included.
 //
 // The recurrence is ka_device.hpp's with ONE change: the band's low end comes from a table,
 //   frame t:  lo = band_lo[t], hi = min(lo + B, L)         (align.py:64-65 replaced; everything else align.py:62-107)
@@ -165,6 +166,19 @@ struct BandTracking {
     uint32_t period, next_rt;
     int end_rule;
     int32_t *out;
+    // the retarget rule: the low end behind lo under the scores sc[] / pres2 (wave-uniform)
+    static __device__ __forceinline__ uint32_t retarget(uint32_t lo, uint32_t L, uint32_t B, const float (&sc)[16], uint32_t pres2, int blk)
+    {
+        uint32_t nlo = lo;
+        const int c = wave_best_live(sc, pres2, blk);
+        if (c >= 0) {
+            int v = c - (int)(B >> 1);
+            v = v > (int)lo ? v : (int)lo;
+            v = v < (int)L - 1 ? v : (int)L - 1;   // unconditional: whatever the floats were, lo stays in [0, L)
+            nlo = (uint32_t)v;
+        }
+        return nlo;
+    }
     static __device__ __forceinline__ uint32_t first_lo(const BandLattice &) { return 0u; }
     __device__ __forceinline__ void begin(const BandLattice &d)
     {
@@ -183,15 +197,7 @@ struct BandTracking {
         if (dd == kRowDepth - 1 && __builtin_expect(tb + kRowDepth == next_rt, 0)) {
             asm volatile("" ::: "memory");  // a real branch: the common group pays a compare and a jump
             next_rt += period;
-            if (tb + kRowDepth < T) {   // (no step into frame T)
-                const int c = wave_best_live(sc, pres2, blk);
-                if (c >= 0) {
-                    int v = c - (int)(B >> 1);
-                    v = v > (int)lo ? v : (int)lo;
-                    v = v < (int)L - 1 ? v : (int)L - 1;   // unconditional: whatever the floats were, lo stays in [0, L)
-                    nlo = (uint32_t)v;
-                }
-            }
+            if (tb + kRowDepth < T) nlo = retarget(lo, L, B, sc, pres2, blk);   // (no step into frame T)
         }
         return nlo;
     }
@@ -203,12 +209,11 @@ struct BandTracking {
 __device__ __forceinline__ bool row_cell_live(uint32_t bits) { return (bits & 0x7fffffffu) <= 0x7f800000u; }
 __device__ __forceinline__ float row_cell_score(uint32_t bits) { return __builtin_bit_cast(float, row_cell_live(bits) ? bits : 0xff800000u); }
 
-// the caller's table under the caller's boundary conditions (ka_ctc_best_path_resume): the state before
-// frame 0 is a score row (no band applies to it), the path ends at the reference's cell, the best cell or a given cell, and the
-// live cells after frame T-1 go out as a row.  The frame loop is BandFromTable's: the start row touches the prologue and the
-// re-labelling block of frame 0 (forward_banded_wave), the rest the epilogue.
-struct BandResume : BandFromTable {
-    static constexpr bool kStart = true;
+// the caller's boundary conditions (ka_ctc_best_path_resume): the state before frame 0 is a score row
+// (no band applies to it), the path ends at the reference's cell, the best cell or a given cell, and the live cells after frame
+// T-1 go out as a row.  The start row touches the prologue and the re-labelling block of frame 0 (forward_banded_wave), the
+// rest the epilogue; the frame loop is that of the band source the rows are combined with (BandResume, BandTrackingResume).
+struct BandRows {
     gcu32_t init;   // [L] the start row's bits, or NULL: the virtual state {0: 0.0}
     gf32_t fin;     // [L] the last row (prep filled it with kDeadScoreBits), or NULL
     int end;        // ResumeRows::end, wave-uniform
@@ -265,6 +270,44 @@ struct BandResume : BandFromTable {
     }
 };
 
+// the caller's table under the caller's boundary conditions: the frame loop is BandFromTable's
+struct BandResume : BandFromTable, BandRows {
+    static constexpr bool kStart = true;
+    using BandRows::end_at_best;
+};
+
+// the self-steering band under the caller's boundary conditions (ka_ctc_best_path_tracking_resume):
+// BandTracking's frame loop from the caller's lo_0, BandRows' prologue and epilogue, and the low end frame T would get, which
+// BandTracking declines to compute: here it goes to a cell of the lattice's own, and lo stays.  The chunk that follows takes it
+// as its lo_0, so a band steered across a cut at a multiple of the period is the uncut call's.
+struct BandTrackingResume : BandTracking, BandRows {
+    static constexpr bool kStart = true;
+    using BandRows::end_at_best;
+    uint32_t lo0;    // lo_0, in [0, L) (the host checked it)
+    uint32_t lo_T;   // the retarget that falls on frame T, where T % period == 0 (wave-uniform; last_lo writes it)
+    gi32_t next;     // one int32: lo_T
+    __device__ __forceinline__ uint32_t first_lo(const BandLattice &) const { return lo0; }
+    __device__ __forceinline__ uint32_t next_lo(const Group &, int dd, uint32_t tb, uint32_t lo, uint32_t T, uint32_t L, uint32_t B, const float (&sc)[16],
+                                                uint32_t pres2, int blk)
+    {
+        uint32_t nlo = lo;
+        if (dd == kRowDepth - 1 && __builtin_expect(tb + kRowDepth == next_rt, 0)) {
+            asm volatile("" ::: "memory");  // a real branch: the common group pays a compare and a jump
+            next_rt += period;
+            const uint32_t v = retarget(lo, L, B, sc, pres2, blk);
+            if (tb + kRowDepth < T) nlo = v;
+            else lo_T = v;   // T % period == 0: frame T's low end, not walked here
+        }
+        return nlo;
+    }
+    // behind the frame loop, one lane: frame T's low end; T % period != 0 keeps the last frame's.  (Not stored from next_lo's
+    // branch: a per-lane store there makes the frame loop's scalar values cross divergent control flow.)
+    __device__ __forceinline__ void last_lo(uint32_t lo, uint32_t T) const
+    {
+        if (threadIdx.x == 0) *next = (int32_t)(T % period != 0u ? lo : lo_T);
+    }
+};
+
 // ---------------------------------------------------------------------------------------
 // forward DP, one wavefront per lattice, every cell's code stored
 // ---------------------------------------------------------------------------------------
@@ -278,7 +321,7 @@ __device__ __forceinline__ void forward_banded_wave(const BandLattice &d, int32_
     const uint32_t B = (uint32_t)__builtin_amdgcn_readfirstlane(d.beam);
     const float NINF = ninf();
 
-    uint32_t lo = Src::first_lo(d);   // band of frame 0 (a table is valid: prep)
+    uint32_t lo = src.first_lo(d);   // band of frame 0 (a table is valid: prep; a caller's lo_0: the host)
     uint32_t hi = (L - lo < B) ? L : lo + B;
     uint32_t blo = lo >> 4;
     int blk = (int)blo + ((lane - (int)blo) & 63);   // block of 16 positions this lane currently owns
@@ -440,6 +483,7 @@ __device__ __forceinline__ void forward_banded_wave(const BandLattice &d, int32_
     if constexpr (Src::kStart) {
         if (m[0] == kStatusOk) src.last_row(sc, pres2, blk);   // (a lattice with a bad label keeps the row prep wrote: all dead)
     }
+    if constexpr (Src::kTracking && Src::kStart) src.last_lo(lo, T);   // (lo is lo_{T-1}: no step into frame T)
     // terminal state: the HIGHEST live position of frame T-1 (align.py:99-101), or on request the tracking call's best one,
     // or the resumed call's given one
     int best;
@@ -517,15 +561,15 @@ __device__ __forceinline__ unsigned long long block_best_live(const float *sc, c
 
 // kTrack: the self-steering band of BandTracking instead of the table.  The arg-max of frame t-2 is taken at the end of frame
 // t-2, when its column is the current one, and held in shared memory for two frames; thread 0 writes the table.
-// kStart: the resumed call's boundary conditions (BandResume's, `rr` the lattice's rows): the start row goes into the first
-// column with every position open, the last row comes out of the last column's band.
+// kStart: the resumed call's boundary conditions (BandRows', `rr` the lattice's rows): the start row goes into the first
+// column with every position open, the last row comes out of the last column's band.  Both: BandTrackingResume.
 template <bool kTrack, bool kStart = false>
 __device__ __forceinline__ void forward_banded_generic(const BandLattice &d, int32_t *meta, int period, int end_rule,
                                                        const ResumeRows *rr = nullptr)
 {
     const int tid = threadIdx.x;
     int32_t *m = meta_of(meta, d.idx);
-    if (!kTrack && (m[2] & kBandFlagBadTable)) return;
+    if ((!kTrack || kStart) && (m[2] & kBandFlagBadTable)) return;   // a bad table, or a +inf cell in the start row
     const int64_t T = d.T, L = d.L, B = d.beam;
     const int M = d.max_move;
     const int64_t W = d.W;
@@ -563,6 +607,7 @@ __device__ __forceinline__ void forward_banded_generic(const BandLattice &d, int
     __syncthreads();
     __shared__ unsigned long long s_key;
     int64_t lo_track = 0;
+    if constexpr (kTrack && kStart) lo_track = rr->first_lo;   // the caller's lo_0, in [0, L) (the host checked it)
     for (int64_t t = 0; t < T; ++t) {
         if (kTrack) {
             if (t > 0 && t % period == 0 && s_key != 0ull) {
@@ -599,7 +644,18 @@ __device__ __forceinline__ void forward_banded_generic(const BandLattice &d, int
         { uint8_t *x = prA; prA = prB; prB = x; }
         plo = lo;
         phi = hi;
-        if (kTrack && t + 2 < T && (t + 2) % period == 0) block_best_live(scA, prA, plo, phi, &s_key);
+        // (with a start row also for frame T, whose low end goes to the chunk that follows)
+        if (kTrack && (t + 2 < T || (kStart && t + 2 == T)) && (t + 2) % period == 0) block_best_live(scA, prA, plo, phi, &s_key);
+    }
+    if constexpr (kTrack && kStart) {   // the low end frame T would get: BandTrackingResume's cell
+        if (T % period == 0 && s_key != 0ull) {
+            const int64_t c = (int64_t)(uint32_t)~(uint32_t)s_key;
+            int64_t v = c - B / 2;
+            v = v > lo_track ? v : lo_track;
+            lo_track = v < L - 1 ? v : L - 1;
+        }
+        if (tid == 0) rr->entry[1] = (int32_t)lo_track;
+        __syncthreads();   // (s_key is used again below)
     }
     if constexpr (kStart) {
         if (rr->fin && m[0] == kStatusOk)   // (a lattice with a bad label keeps the row prep wrote: all dead)

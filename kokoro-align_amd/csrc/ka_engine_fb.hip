@@ -633,12 +633,16 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
 
 // ---- best path over a caller-given band (ka_banded.hpp): its own kernels and workspace layout, whatever the engine's mode.
 // period > 0: the self-steering band (ka_ctc_best_path_tracking): band_lo is then the table the call WRITES, a fourth output.
-// rs: the resumed call (ka_ctc_best_path_resume): the caller's boundary conditions, a last row and an entry cell per lattice ----
+// rs: the resumed call (ka_ctc_best_path_resume): the caller's boundary conditions, a last row and an entry cell per lattice.
+// Both: the resumed tracking call (ka_ctc_best_path_tracking_resume), whose end is rs's and which adds lo_0 and the low end of
+// frame T, a second cell beside the entry ----
 struct ResumeArgs {
     const float *const *init_scores;   // [n] or NULL; an entry may be NULL
     const int32_t *end;                // [n] host, or NULL: all -1
     float *const *final_scores;        // [n] or NULL; an entry may be NULL
     int32_t *entry;                    // [n] host, or NULL
+    const int32_t *first_lo;           // tracking only: [n] host, or NULL: all 0
+    int32_t *next_lo;                  // tracking only: [n] host, or NULL
 };
 int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
                 const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move, const int32_t *const *band_lo,
@@ -658,13 +662,17 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
     size_t off_meta = 0, off_rows = 0, off_entry = 0;
     std::vector<size_t> row_init(rs ? n : 0), row_fin(rs ? n : 0);
     const size_t total = rs ? ka::plan::resume_workspace(n, T, S, V, beam_size, max_move, host, cv.data(), &off_meta, &off_rows, &off_entry,
-                                                         row_init.data(), row_fin.data())
+                                                         row_init.data(), row_fin.data(), tracking)
                             : ka::plan::banded_workspace(n, T, S, V, beam_size, max_move, host, cv.data(), &off_meta, tracking);
     if (total == 0) return fail(KA_ERR_BAD_ARGS, "banded best path: unsupported T/S/V/beam_size/max_move");
     if (rs && rs->end)
         for (int32_t i = 0; i < n; ++i)
             if (rs->end[i] < -2 || rs->end[i] > 2 * S[i])
                 return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": end must be -1 (highest live), -2 (best live) or a position in [0, 2S+1)");
+    if (rs && rs->first_lo)
+        for (int32_t i = 0; i < n; ++i)
+            if (rs->first_lo[i] < 0 || rs->first_lo[i] > 2 * S[i])
+                return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": first_lo must be a position in [0, 2S+1)");
     for (int32_t i = 0; i < n; ++i) {
         if (ld[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld < V");
         if (!log_probs[i] || !band_lo[i] || !best_path[i] || !best_labels[i] || !best_scores[i] || (S[i] > 0 && !labels[i]))
@@ -677,7 +685,8 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
     const size_t desc_bytes = align_up((size_t)n * sizeof(Desc));
     const size_t meta_bytes = align_up((size_t)n * sizeof(ka::LatticeMeta));
     const size_t rows_bytes = rs ? align_up((size_t)n * sizeof(ka::ResumeRows)) : 0;
-    rc = ensure_pin(e, desc_bytes + meta_bytes + rows_bytes + (rs ? (size_t)n * sizeof(int32_t) : 0));
+    const int32_t cells = rs && tracking ? 2 : 1;   // per lattice behind the rows: the entry, and under tracking the low end of frame T
+    rc = ensure_pin(e, desc_bytes + meta_bytes + rows_bytes + (rs ? (size_t)n * cells * sizeof(int32_t) : 0));
     if (rc != KA_OK) return rc;
     // the workspace is shared with the best-path calls (see fb_impl)
     if (e->res.refill_done) KA_HIP(hipStreamWaitEvent(stream, e->res.refill_done, 0));
@@ -702,9 +711,9 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
             ka::ResumeRows &r = h_rows[slot];
             r.init = !init ? nullptr : host ? reinterpret_cast<const float *>(ws + row_init[i]) : init;
             r.fin = !fin ? nullptr : host ? reinterpret_cast<float *>(ws + row_fin[i]) : fin;
-            r.entry = reinterpret_cast<int32_t *>(ws + off_entry) + i;
+            r.entry = reinterpret_cast<int32_t *>(ws + off_entry) + (size_t)i * cells;
             r.end = rs->end ? rs->end[i] : -1;
-            r.pad = 0;
+            r.first_lo = rs->first_lo ? rs->first_lo[i] : 0;
         }
         if (host) {
             d.lp = reinterpret_cast<const float *>(ws + c.lp);
@@ -754,20 +763,24 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
     if (rs) {
         ka::ResumeRows *d_rows = reinterpret_cast<ka::ResumeRows *>(ws + off_rows);
         KA_HIP(hipMemcpyAsync(d_rows, h_rows, (size_t)n * sizeof(ka::ResumeRows), hipMemcpyHostToDevice, stream));
-        ka::launch_best_path_resume(d_lats, d_rows, n_fast, n - n_fast, max_move, d_meta, stream);
+        if (tracking) ka::launch_best_path_tracking_resume(d_lats, d_rows, n_fast, n - n_fast, max_move, period, d_meta, stream);
+        else ka::launch_best_path_resume(d_lats, d_rows, n_fast, n - n_fast, max_move, d_meta, stream);
     } else if (tracking) ka::launch_best_path_tracking(d_lats, n_fast, n - n_fast, max_move, period, end_rule, d_meta, stream);
     else ka::launch_best_path_banded(d_lats, n_fast, n - n_fast, max_move, d_meta, stream);
     KA_HIP(hipGetLastError());
     KA_HIP(hipMemcpyAsync(h_meta, d_meta, (size_t)n * sizeof(ka::LatticeMeta), hipMemcpyDeviceToHost, stream));
-    if (rs) KA_HIP(hipMemcpyAsync(h_entry, ws + off_entry, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (rs) KA_HIP(hipMemcpyAsync(h_entry, ws + off_entry, (size_t)n * cells * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     KA_HIP(hipStreamSynchronize(stream));
     if (host) {   // only what succeeded is copied out: a failed lattice's outputs stay as the caller left them
         for (int32_t i = 0; i < n; ++i) {
             // (but the last row of every lattice: all dead where the forward pass did not run, or found a NaN or a bad label)
             if (rs && rs->final_scores && rs->final_scores[i])
                 KA_HIP(hipMemcpyAsync(rs->final_scores[i], ws + row_fin[i], (size_t)(2 * S[i] + 1) * 4, hipMemcpyDeviceToHost, stream));
-            if (h_meta[i].status != KA_OK) continue;
             const size_t bytes = (size_t)T[i] * 4;
+            // (and the table of a resumed tracking call whose forward pass ran to its end: a dead end cell leaves it valid)
+            if (rs && tracking && h_meta[i].status == KA_ERR_EMPTY_BEAM)
+                KA_HIP(hipMemcpyAsync(const_cast<int32_t *>(band_lo[i]), ws + cv[i].band, bytes, hipMemcpyDeviceToHost, stream));
+            if (h_meta[i].status != KA_OK) continue;
             KA_HIP(hipMemcpyAsync(best_path[i], ws + cv[i].path, bytes, hipMemcpyDeviceToHost, stream));
             KA_HIP(hipMemcpyAsync(best_labels[i], ws + cv[i].lab_out, bytes, hipMemcpyDeviceToHost, stream));
             KA_HIP(hipMemcpyAsync(best_scores[i], ws + cv[i].sc_out, bytes, hipMemcpyDeviceToHost, stream));
@@ -780,14 +793,16 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
         const int32_t st = h_meta[i].status;
         if (status) status[i] = st;
         if (total_score) total_score[i] = h_meta[i].score;
-        if (rs && rs->entry) rs->entry[i] = st == KA_OK ? h_entry[i] : -1;
+        if (rs && rs->entry) rs->entry[i] = st == KA_OK ? h_entry[(size_t)i * cells] : -1;
+        if (rs && tracking && rs->next_lo) rs->next_lo[i] = st == KA_OK || st == KA_ERR_EMPTY_BEAM ? h_entry[(size_t)i * cells + 1] : -1;
         if (st != KA_OK && first_bad == KA_OK) {
             first_bad = st;
             g_err = "lattice " + std::to_string(i) +
                     status_message(st, {rs ? ": no live state in the last frame, or the end cell is not live" : ": no live state in the last frame",
                                         nullptr, nullptr,
-                                        rs ? ": band_lo must hold non-decreasing values in [0, 2S+1) and init_scores no +inf"
-                                           : ": band_lo must hold non-decreasing values in [0, 2S+1)",
+                                        rs && tracking ? ": init_scores must hold no +inf"
+                                        : rs           ? ": band_lo must hold non-decreasing values in [0, 2S+1) and init_scores no +inf"
+                                                       : ": band_lo must hold non-decreasing values in [0, 2S+1)",
                                         nullptr});
         }
     }
@@ -850,7 +865,7 @@ int ka_ctc_best_path_resume_batch_f32(ka_engine *e, int32_t n, const float *cons
                                       int32_t *const *best_path, int32_t *const *best_labels, float *const *best_scores,
                                       float *const *final_scores, int32_t *entry, float *total_score, int32_t *status, int32_t mem, void *stream)
 {
-    const ResumeArgs rs{init_scores, end, final_scores, entry};
+    const ResumeArgs rs{init_scores, end, final_scores, entry, nullptr, nullptr};
     return banded_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, band_lo, best_path, best_labels, best_scores, total_score,
                        status, mem, (hipStream_t)stream, 0, 0, &rs);
 }
@@ -860,7 +875,7 @@ int ka_ctc_best_path_resume_f32(ka_engine *e, const float *log_probs, int64_t T,
                                 int32_t *best_path, int32_t *best_labels, float *best_scores, float *final_scores, int32_t *entry,
                                 float *total_score, int32_t mem, void *stream)
 {
-    const ResumeArgs rs{&init_scores, &end, &final_scores, entry};
+    const ResumeArgs rs{&init_scores, &end, &final_scores, entry, nullptr, nullptr};
     return banded_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo, &best_path, &best_labels, &best_scores,
                        total_score, nullptr, mem, (hipStream_t)stream, 0, 0, &rs);
 }
@@ -869,6 +884,40 @@ size_t ka_resume_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, 
 {
     if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
     return ka::plan::resume_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int ka_ctc_best_path_tracking_resume_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                               const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                               int32_t max_move, int32_t period, const int32_t *first_lo, const float *const *init_scores,
+                                               const int32_t *end, int32_t *const *best_path, int32_t *const *best_labels,
+                                               float *const *best_scores, int32_t *const *band_lo_out, float *const *final_scores,
+                                               int32_t *entry, int32_t *next_lo, float *total_score, int32_t *status, int32_t mem, void *stream)
+{
+    const int rc = tracking_args(period, 0);
+    if (rc != KA_OK) return rc;
+    const ResumeArgs rs{init_scores, end, final_scores, entry, first_lo, next_lo};
+    return banded_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, band_lo_out, best_path, best_labels, best_scores, total_score,
+                       status, mem, (hipStream_t)stream, period, 0, &rs);
+}
+
+int ka_ctc_best_path_tracking_resume_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                         int32_t beam_size, int32_t max_move, int32_t period, int32_t first_lo, const float *init_scores,
+                                         int32_t end, int32_t *best_path, int32_t *best_labels, float *best_scores, int32_t *band_lo_out,
+                                         float *final_scores, int32_t *entry, int32_t *next_lo, float *total_score, int32_t mem, void *stream)
+{
+    const int rc = tracking_args(period, 0);
+    if (rc != KA_OK) return rc;
+    const ResumeArgs rs{&init_scores, &end, &final_scores, entry, &first_lo, next_lo};
+    return banded_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo_out, &best_path, &best_labels, &best_scores,
+                       total_score, nullptr, mem, (hipStream_t)stream, period, 0, &rs);
+}
+
+size_t ka_tracking_resume_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                          int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::resume_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                      true);
 }
 
 size_t ka_tracking_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)

@@ -137,5 +137,11 @@ void launch_best_path_tracking(const BandLattice *lats, int n_fast, int n_generi
 // ResumeRows per lattice: start row, last row, end cell or rule, and where the walk back puts the cell it ends on ----
 void launch_best_path_resume(const BandLattice *lats, const ResumeRows *rows, int n_fast, int n_generic, int max_move, int32_t *meta,
                              hipStream_t s);
+// ... its walk back alone, over a table some forward pass has used
+void launch_backtrace_resume(const BandLattice *lats, const ResumeRows *rows, int n_fast, int n_generic, const int32_t *meta, hipStream_t s);
+// ---- ka_tracking_resume.hip: the resumable tracking best path (ka_banded.hpp's BandTrackingResume): the two above together.
+// A lattice's ResumeRows brings first_lo, and entry points at two cells: the entry and the low end frame T would get ----
+void launch_best_path_tracking_resume(const BandLattice *lats, const ResumeRows *rows, int n_fast, int n_generic, int max_move, int period,
+                                      int32_t *meta, hipStream_t s);
 
 }  // namespace ka

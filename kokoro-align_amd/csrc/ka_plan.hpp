@@ -987,16 +987,18 @@ inline size_t banded_workspace(int32_t n, const int64_t *T, const int64_t *S, in
 
 // ---- ka_ctc_best_path_resume_batch_f32: banded_workspace and, behind it, a ResumeRows and an entry cell (int32) per lattice;
 // for host buffers the two staged rows of every lattice ([2S+1] float32 each: init[i], then fin[i], offsets from the start of
-// the workspace).  0 where banded_workspace is 0.
+// the workspace).  0 where banded_workspace is 0.  `tracking` (ka_ctc_best_path_tracking_resume_batch_f32): banded_workspace's
+// tracking layout (no shifted table, the staged table an output) and two cells per lattice, the entry and the low end of frame T.
 inline size_t resume_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
-                               BandCarve *cv, size_t *off_meta, size_t *off_rows, size_t *off_entry, size_t *init, size_t *fin)
+                               BandCarve *cv, size_t *off_meta, size_t *off_rows, size_t *off_entry, size_t *init, size_t *fin,
+                               bool tracking = false)
 {
-    size_t off = banded_workspace(n, T, S, V, beam, max_move, host_buffers, cv, off_meta);
+    size_t off = banded_workspace(n, T, S, V, beam, max_move, host_buffers, cv, off_meta, tracking);
     if (off == 0) return 0;
     if (off_rows) *off_rows = off;
     off += align_up((size_t)n * sizeof(ResumeRows));
     if (off_entry) *off_entry = off;
-    off += align_up((size_t)n * sizeof(int32_t));
+    off += align_up((size_t)n * (tracking ? 2 : 1) * sizeof(int32_t));
     if (host_buffers)
         for (int32_t i = 0; i < n; ++i) {
             const size_t row = align_up((size_t)(2 * S[i] + 1) * sizeof(float));

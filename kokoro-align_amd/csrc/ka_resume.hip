@@ -76,6 +76,12 @@ static void launch_forward_resume_wave(const BandLattice *lats, const ResumeRows
     forward_resume_wave_kernel<M, true><<<dim3(n), dim3(64), 0, s>>>(lats, rows, meta);
 }
 
+void launch_backtrace_resume(const BandLattice *lats, const ResumeRows *rows, int n_fast, int n_generic, const int32_t *meta, hipStream_t s)
+{
+    if (n_fast > 0) backtrace_resume_wave_kernel<<<dim3(n_fast), dim3(64), 0, s>>>(lats, rows, meta);
+    if (n_generic > 0) backtrace_resume_generic_kernel<<<dim3(n_generic), dim3(64), 0, s>>>(lats + n_fast, rows + n_fast, meta);
+}
+
 void launch_best_path_resume(const BandLattice *lats, const ResumeRows *rows, int n_fast, int n_generic, int max_move, int32_t *meta,
                              hipStream_t s)
 {
@@ -87,12 +93,9 @@ void launch_best_path_resume(const BandLattice *lats, const ResumeRows *rows, in
         case 3: launch_forward_resume_wave<3>(lats, rows, n_fast, meta, s); break;
         default: launch_forward_resume_wave<4>(lats, rows, n_fast, meta, s); break;
         }
-        backtrace_resume_wave_kernel<<<dim3(n_fast), dim3(64), 0, s>>>(lats, rows, meta);
     }
-    if (n_generic > 0) {
-        forward_resume_generic_kernel<<<dim3(n_generic), dim3(256), 0, s>>>(lats + n_fast, rows + n_fast, meta);
-        backtrace_resume_generic_kernel<<<dim3(n_generic), dim3(64), 0, s>>>(lats + n_fast, rows + n_fast, meta);
-    }
+    if (n_generic > 0) forward_resume_generic_kernel<<<dim3(n_generic), dim3(256), 0, s>>>(lats + n_fast, rows + n_fast, meta);
+    launch_backtrace_resume(lats, rows, n_fast, n_generic, meta, s);
 }
 
 }  // namespace ka

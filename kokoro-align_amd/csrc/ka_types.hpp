@@ -301,9 +301,10 @@ constexpr uint32_t kDeadScoreBits = 0x7fc00000u;   // the quiet NaN a dead cell 
 struct ResumeRows {
     const float *init;   // [L] the score row before frame 0 (device), NaN = dead; NULL: the virtual state {0: 0.0}
     float *fin;          // [L] the score row after frame T-1 (device), NaN = dead; NULL: not wanted
-    int32_t *entry;      // one int32 (device, preset to -1): the cell of the start row the path left from
+    int32_t *entry;      // one int32 (device, preset to -1): the cell of the start row the path left from; under a self-steering
+                         // band (ka_ctc_best_path_tracking_resume, section 4.35) two: entry[1] (preset to -1) the low end of frame T
     int32_t end;         // -1: the highest live cell, -2: the best live cell, p >= 0: that cell
-    int32_t pad;
+    int32_t first_lo;    // self-steering band only: the low end of frame 0, in [0, L); else 0
 };
 static_assert(sizeof(ResumeRows) == 32, "descriptor sizes");
 
