@@ -570,6 +570,73 @@ size_t ka_tracking_resume_workspace_bytes(int32_t n, const int64_t *T, const int
                                           int32_t mem);
 
 /*
+ * Determined prefix of a resumed best path: ka_ctc_best_path_resume and
+ * ka_ctc_best_path_tracking_resume with one more output, how many frames of the returned path are final whatever audio
+ * follows.  It is the reference's flush_determined_path (kokoro_align/align.py:21-40) as a call: a walk back from ALL live
+ * cells of the last frame until their back-pointers meet in one cell.  The arguments are the parent call's, in its order, with
+ *   determined    int32 output behind entry (tracking: behind next_lo), HOST memory in both modes (batch: [n]).  Required: NULL
+ *                 is KA_ERR_BAD_ARGS before anything is launched or written.
+ * Definition, no tolerance anywhere.  A_{-1} the start row's live cells, A_t the live cells after frame t, j*_t(p) the move
+ * chosen for cell p in frame t (the first maximum, as in every best-path call):
+ *   anc_{T-1} = A_{T-1}                          (every live cell after the last frame, NOT only the end cell)
+ *   anc_{t-1} = { p - j*_t(p) : p in anc_t }     for t = T-1 ... 0     (anc_{-1} is a set of cells of the start row)
+ *   determined = 1 + max{ t in [-1, T-1] : |anc_t| == 1 },   -1 if there is no such t
+ * |anc_t| does not increase going back, so determined is the first frame, walking back, at which one cell is left.
+ *   d >= 1        frames [0, d) of the returned path are the same whichever live cell the path ends at, and stay the same if the
+ *                 alignment continues from final_scores; with a live end cell path[d-1] is the merge cell.  d = T: one live cell
+ *                 after the last frame.
+ *   d = 0         no frame of this chunk is final, but all live cells leave the start row from one cell: the returned entry,
+ *                 which closes the chunk before this one.  A NULL init_scores has the start row {0}: d >= 0 whenever a cell is live.
+ *   d = -1        the live cells trace back to more than one start cell, or no cell is live after frame T-1 (a lattice that
+ *                 ends in KA_ERR_BAD_LABEL, KA_ERR_NAN or KA_ERR_BAD_ARGS included).
+ * determined depends on the live set, not on end: a given end cell that is dead still ends in KA_ERR_EMPTY_BEAM with entry -1,
+ * and determined is reported as defined.  An ancestor of a live cell is live, and a live cell of score -inf counts like any other.
+ * Every other output, status, return value and stream synchronisation is the parent call's, bit for bit; a lattice gives the
+ * same bits alone or inside a batch.  The forward kernels and walks back are the parent's; one kernel more runs behind them
+ * (ka_determined.hpp): one wavefront per lattice over the 2-bit move codes with the set as a bit mask over the ring, or a
+ * 256-thread workgroup over the byte codes in the generic form.  It stops at the merge frame: its cost is the merge lag
+ * T - determined, not T.
+ * Measured against the parent entry point of the same build on the same inputs (tools/bench_determined.py,
+ * profiles/determined_bench.jsonl; MI355X, cfg2: T = 50000, S = 5000, beam 1000, V = 64): the walk costs about 96 ns per frame
+ * walked.  One lattice whose lines merge 2579 frames before the end (a peaked input): 1.0075 times ka_ctc_best_path_resume
+ * (33.64 against 33.39 ms) and 1.0070 / 1.0082 times ka_ctc_best_path_tracking_resume at periods 16 / 64; 1024 such lattices
+ * 1.0097, 1.0119 and 1.0099.  The hash input (noise: merge lags of 39 000 to 43 000 frames): 1.11, 1.13 and 1.14 for one lattice,
+ * 1.15, 1.16 and 1.17 for 1024.  The worst case, where the walk runs all T frames (flat log-probs, a band as wide as the label
+ * axis, a free start row: determined = -1): 1.16, 1.16 and 1.17 for one lattice, 1.19, 1.19 and 1.20 for 1024.  StreamingAligner
+ * (Python) in 8 chunks costs 1.04 (peaked) to 1.09 (hash) times ctc_best_path_tracking_chunked and commits its first frames
+ * after the first chunk.
+ */
+int ka_ctc_best_path_determined_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                    int32_t beam_size, int32_t max_move, const int32_t *band_lo, const float *init_scores, int32_t end,
+                                    int32_t *best_path, int32_t *best_labels, float *best_scores, float *final_scores, int32_t *entry,
+                                    int32_t *determined, float *total_score, int32_t mem, void *stream);
+int ka_ctc_best_path_determined_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                          const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                          const int32_t *const *band_lo, const float *const *init_scores, const int32_t *end,
+                                          int32_t *const *best_path, int32_t *const *best_labels, float *const *best_scores,
+                                          float *const *final_scores, int32_t *entry, int32_t *determined, float *total_score, int32_t *status,
+                                          int32_t mem, void *stream);
+int ka_ctc_best_path_tracking_determined_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels,
+                                             int64_t S, int32_t beam_size, int32_t max_move, int32_t period, int32_t first_lo,
+                                             const float *init_scores, int32_t end, int32_t *best_path, int32_t *best_labels,
+                                             float *best_scores, int32_t *band_lo_out, float *final_scores, int32_t *entry, int32_t *next_lo,
+                                             int32_t *determined, float *total_score, int32_t mem, void *stream);
+int ka_ctc_best_path_tracking_determined_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                                   const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                                   int32_t max_move, int32_t period, const int32_t *first_lo, const float *const *init_scores,
+                                                   const int32_t *end, int32_t *const *best_path, int32_t *const *best_labels,
+                                                   float *const *best_scores, int32_t *const *band_lo_out, float *const *final_scores,
+                                                   int32_t *entry, int32_t *next_lo, int32_t *determined, float *total_score, int32_t *status,
+                                                   int32_t mem, void *stream);
+/* device-workspace bytes such a call carves (0 for unsupported arguments): the parent's figure (tracking 0:
+ * ka_resume_workspace_bytes, else ka_tracking_resume_workspace_bytes) plus the determined cell of every lattice (4 bytes,
+ * rounded up for the batch) and, for KA_MEM_DEVICE, a last row of the engine's own per lattice (the walk starts from the last
+ * row, whether or not the caller asks for it; with KA_MEM_HOST the staged row serves).  After ka_engine_reserve of it the call
+ * allocates nothing. */
+size_t ka_determined_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                     int32_t mem, int32_t tracking);
+
+/*
  * Best-path margins from max-marginals: how much score the best alignment would lose if, at frame t, it had to be somewhere
  * else.  The best path's own recurrence in max-plus arithmetic, run forwards (D) and backwards (E): adds and compares only, no
  * transcendental, float64 throughout, so every output is defined bit for bit by IEEE add and max.

@@ -10,7 +10,9 @@ gives (ctc_best_path_banded[_batch|_device], diagonal_band, anchored_band, band_
 itself by the scores and returns the table it walked (ctc_best_path_tracking[_batch|_device]), or started from a score row,
 ended at a chosen cell and resumable from the row it returns (ctc_best_path_resume[_batch|_device], free_start_scores,
 ctc_best_path_chunked), or both, so that the self-steering band crosses a cut (ctc_best_path_tracking_resume[_batch|_device],
-ctc_best_path_tracking_chunked), and the
+ctc_best_path_tracking_chunked), with the number of frames of such a chunk that are final whatever follows
+(ctc_best_path_determined[_batch|_device], ctc_best_path_tracking_determined[_batch|_device]) and the aligner built on it that
+commits frames while it is fed (StreamingAligner), and the
 forward-backward quality signal of a best path (ctc_path_posteriors[_batch|_device], segment_confidence), the label
 occupancy of every frame (ctc_label_posteriors[_batch|_device], segment_agreement), the differentiable lattice
 log-likelihood (lattice_log_likelihood) and the state posteriors at chosen frames behind the confidence of align()'s text
@@ -31,6 +33,7 @@ CPU fallback — importing works without a GPU, computing does not.
 """
 from . import encoder, transcript  # noqa: F401
 from .align import (  # noqa: F401
+    StreamingAligner,
     align,
     anchored_band,
     band_around_path,
@@ -42,6 +45,9 @@ from .align import (  # noqa: F401
     ctc_best_path_banded_device,
     ctc_best_path_batch,
     ctc_best_path_chunked,
+    ctc_best_path_determined,
+    ctc_best_path_determined_batch,
+    ctc_best_path_determined_device,
     ctc_best_path_device,
     ctc_best_path_resume,
     ctc_best_path_resume_batch,
@@ -49,6 +55,9 @@ from .align import (  # noqa: F401
     ctc_best_path_tracking,
     ctc_best_path_tracking_batch,
     ctc_best_path_tracking_chunked,
+    ctc_best_path_tracking_determined,
+    ctc_best_path_tracking_determined_batch,
+    ctc_best_path_tracking_determined_device,
     ctc_best_path_tracking_device,
     ctc_best_path_tracking_resume,
     ctc_best_path_tracking_resume_batch,

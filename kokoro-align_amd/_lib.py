@@ -58,6 +58,8 @@ EXPORTS = [
     "ka_ctc_best_path_resume_f32", "ka_ctc_best_path_resume_batch_f32", "ka_resume_workspace_bytes",
     "ka_ctc_best_path_tracking_resume_f32", "ka_ctc_best_path_tracking_resume_batch_f32", "ka_tracking_resume_workspace_bytes",
     "ka_ctc_path_margins_f32", "ka_ctc_path_margins_batch_f32", "ka_path_margin_workspace_bytes",
+    "ka_ctc_best_path_determined_f32", "ka_ctc_best_path_determined_batch_f32",
+    "ka_ctc_best_path_tracking_determined_f32", "ka_ctc_best_path_tracking_determined_batch_f32", "ka_determined_workspace_bytes",
 ]
 
 
@@ -194,6 +196,15 @@ def load_library():
                                                              vp, vp, vp, vp, i32, vp]
     L.ka_tracking_resume_workspace_bytes.restype = sz
     L.ka_tracking_resume_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
+    # the determined calls: their parents' arguments with the determined cell(s) in front of total_score
+    for call in ("", "_tracking"):
+        for form, back in (("", 3), ("_batch", 4)):
+            parent = getattr(L, f"ka_ctc_best_path{call}_resume{form}_f32")
+            det = getattr(L, f"ka_ctc_best_path{call}_determined{form}_f32")
+            det.restype = ctypes.c_int
+            det.argtypes = parent.argtypes[:-back] + [vp] + parent.argtypes[-back:]
+    L.ka_determined_workspace_bytes.restype = sz
+    L.ka_determined_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32, i32]
     # the table (a pointer, or an array of pointers) may be NULL, and so may runner_up
     L.ka_ctc_path_margins_f32.restype = ctypes.c_int
     L.ka_ctc_path_margins_f32.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp]

@@ -10,7 +10,9 @@ ctc_best_path_device), the log-softmax of align.py:116-117 on the device (log_so
 the caller gives (ctc_best_path_banded[_batch|_device] with the tables diagonal_band, anchored_band, band_around_path and the
 diagnostic band_edge_contact), over a band that steers itself (ctc_best_path_tracking[_batch|_device]), the banded best path
 with the caller's boundary conditions (ctc_best_path_resume[_batch|_device], free_start_scores, ctc_best_path_chunked) and the
-two together (ctc_best_path_tracking_resume[_batch|_device], ctc_best_path_tracking_chunked).
+two together (ctc_best_path_tracking_resume[_batch|_device], ctc_best_path_tracking_chunked), and how much of a resumed
+chunk's path is final (ctc_best_path_determined[_batch|_device], ctc_best_path_tracking_determined[_batch|_device]) with the
+aligner that commits frames while it is fed (StreamingAligner).
 
 The DP + backtrace (the reference's per-frame NumPy loop) run in the HIP library through the C
 ABI of include/kokoro_align_amd.h.  NumPy arrays are handed over as host buffers; torch tensors
@@ -80,10 +82,13 @@ _BEST_PATH_CALLS = {
     "_tracking_resume": ((np.int32, np.int32, np.float32, np.int32),
                          (_lib.KA_OK, _lib.KA_ERR_EMPTY_BEAM, _lib.KA_ERR_BAD_LABEL, _lib.KA_ERR_NAN, _lib.KA_ERR_BAD_ARGS)),
 }
+_BEST_PATH_CALLS["_determined"] = _BEST_PATH_CALLS["_resume"]
+_BEST_PATH_CALLS["_tracking_determined"] = _BEST_PATH_CALLS["_tracking_resume"]
 
 
 def _run_best_path(lat, call, beam_size, max_move, own_args, outputs, return_status, more_outputs=()):
-    """The call ``ka_ctc_best_path<call>_batch_f32`` ("", "_banded", "_tracking", "_resume", "_tracking_resume"): the arguments all take, ``own_args``
+    """The call ``ka_ctc_best_path<call>_batch_f32`` ("", "_banded", "_tracking", "_resume", "_tracking_resume", "_determined",
+    "_tracking_determined"): the arguments all take, ``own_args``
     behind ``max_move`` (the band tables; period and end rule; start rows and ends), then the outputs (paths, labels, scores and,
     for tracking, the tables walked: allocated here, or the caller's ``outputs`` after a check), ``more_outputs`` as they are
     (the resumed call's last rows and entries), totals and statuses, and the status handling of ``return_status``.
@@ -407,7 +412,7 @@ def _end_cells(lat, end):
     return np.array([END_CELLS[x] if isinstance(x, str) else int(x) for x in ends], np.int32)
 
 
-def _best_path_resume(lat, band_lo, init_scores, end, beam_size, max_move, final_scores, return_status):
+def _best_path_resume(lat, band_lo, init_scores, end, beam_size, max_move, final_scores, return_status, determined=False):
     tables = _band_tables(lat, band_lo)         # (held until the call has returned, like the rows: the addresses below are theirs)
     rows = _score_rows(lat, init_scores)
     ends = _end_cells(lat, end)
@@ -416,10 +421,11 @@ def _best_path_resume(lat, band_lo, init_scores, end, beam_size, max_move, final
     p_band, _k1 = _ptr_array([lat.ptr(x) for x in tables])
     p_init, _k2 = _ptr_array([None if x is None else lat.ptr(x) for x in rows])
     p_last, _k3 = _ptr_array([lat.ptr(x) for x in last]) if final_scores else (None, None)
-    out = _run_best_path(lat, "_resume", beam_size, max_move, (p_band, p_init, ends.ctypes.data), None, return_status,
-                         (p_last, entry.ctypes.data))
+    det = np.full(lat.n, -1, np.int32)           # (the determined call: one more cell per lattice, one more entry per result)
+    out = _run_best_path(lat, "_determined" if determined else "_resume", beam_size, max_move, (p_band, p_init, ends.ctypes.data), None,
+                         return_status, (p_last, entry.ctypes.data) + ((det.ctypes.data,) if determined else ()))
     results = out[0] if return_status else out
-    results = [r + (int(entry[i]), last[i] if final_scores else None) for i, r in enumerate(results)]
+    results = [r + (int(entry[i]), last[i] if final_scores else None) + ((int(det[i]),) if determined else ()) for i, r in enumerate(results)]
     return (results,) + tuple(out[1:]) if return_status else results
 
 
@@ -512,7 +518,7 @@ def ctc_best_path_chunked(log_probs, labels, band_lo, chunk_frames, beam_size=10
 # ------------------------------------------------------------------------------------------
 # resumable tracking best path: the self-steering band under the caller's boundary conditions
 # ------------------------------------------------------------------------------------------
-def _best_path_tracking_resume(lat, first_lo, init_scores, end, beam_size, max_move, period, final_scores, return_status):
+def _best_path_tracking_resume(lat, first_lo, init_scores, end, beam_size, max_move, period, final_scores, return_status, determined=False):
     rows = _score_rows(lat, init_scores)        # (held until the call has returned: the addresses below are theirs)
     ends = _end_cells(lat, end)
     first = [first_lo] * lat.n if isinstance(first_lo, (int, np.integer)) else list(first_lo)
@@ -524,10 +530,13 @@ def _best_path_tracking_resume(lat, first_lo, init_scores, end, beam_size, max_m
     next_lo = np.full(lat.n, -1, np.int32)
     p_init, _k1 = _ptr_array([None if x is None else lat.ptr(x) for x in rows])
     p_last, _k2 = _ptr_array([lat.ptr(x) for x in last]) if final_scores else (None, None)
-    out = _run_best_path(lat, "_tracking_resume", beam_size, max_move, (int(period), first.ctypes.data, p_init, ends.ctypes.data), None,
-                         return_status, (p_last, entry.ctypes.data, next_lo.ctypes.data))
+    det = np.full(lat.n, -1, np.int32)           # (the determined call: one more cell per lattice, one more entry per result)
+    out = _run_best_path(lat, "_tracking_determined" if determined else "_tracking_resume", beam_size, max_move,
+                         (int(period), first.ctypes.data, p_init, ends.ctypes.data), None, return_status,
+                         (p_last, entry.ctypes.data, next_lo.ctypes.data) + ((det.ctypes.data,) if determined else ()))
     results = out[0] if return_status else out
-    results = [r + (int(entry[i]), last[i] if final_scores else None, int(next_lo[i])) for i, r in enumerate(results)]
+    results = [r + (int(entry[i]), last[i] if final_scores else None, int(next_lo[i])) + ((int(det[i]),) if determined else ())
+               for i, r in enumerate(results)]
     return (results,) + tuple(out[1:]) if return_status else results
 
 
@@ -613,6 +622,164 @@ def ctc_best_path_tracking_chunked(log_probs, labels, chunk_frames, beam_size=10
         import torch
         return tuple(torch.cat([p[i] for p in parts]) for i in range(4))
     return tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
+
+
+# ------------------------------------------------------------------------------------------
+# determined prefixes: how much of a resumed chunk's path is final, and the aligner that commits frames while it is fed
+# ------------------------------------------------------------------------------------------
+def ctc_best_path_determined_batch(log_probs_list, labels_list, band_lo_list, init_scores_list=None, end="highest", beam_size=1000,
+                                   max_move=4, device=None, return_status=False, final_scores=True):
+    """``ctc_best_path_determined`` for a list of lattices in one call: ``ctc_best_path_resume_batch``'s arguments and results,
+    each result with ``determined`` appended.  A failed lattice's ``determined`` is -1 unless its forward pass ran to its end
+    with live cells (a given end that is dead)."""
+    lat = _host_lattices(log_probs_list, labels_list, band_lo_list, "band_lo", device)
+    if lat is None:
+        return ([], [], []) if return_status else []
+    return _best_path_resume(lat, band_lo_list, init_scores_list, end, beam_size, max_move, final_scores, return_status, True)
+
+
+def ctc_best_path_determined_device(log_probs, labels, band_lo, init_scores=None, end="highest", beam_size=1000, max_move=4,
+                                    return_status=False, final_scores=True):
+    """``ctc_best_path_determined_batch`` on lists of ROCm torch tensors, as ``ctc_best_path_resume_device``; ``determined`` is a
+    Python integer."""
+    lat = _device_lattices(log_probs, labels, band_lo, "band_lo")
+    return _best_path_resume(lat, band_lo, init_scores, end, beam_size, max_move, final_scores, return_status, True)
+
+
+def ctc_best_path_determined(log_probs, labels, band_lo, init_scores=None, end="highest", beam_size=1000, max_move=4):
+    """``ctc_best_path_resume`` that also says how much of its path is final: (best_path, best_labels, best_scores, entry,
+    final_scores, determined).  The live cells after the last frame are all followed back along their chosen moves until they
+    meet in one cell (the reference's flush_determined_path, kokoro_align/align.py:21-40); ``determined`` is the number of
+    frames before that: frames [0, determined) are the same whichever live cell the path later ends at and whatever audio
+    follows.  0: no frame of this chunk is final, but every line leaves the start row at ``entry``, which closes the chunk
+    before this one.  -1: the lines reach more than one start cell, or no cell is live.  It depends on the live cells, not on
+    ``end``.  Every other value is ``ctc_best_path_resume``'s, bit for bit."""
+    if _is_tensor(log_probs):
+        return ctc_best_path_determined_device([log_probs], [labels], [band_lo], [init_scores], end, beam_size, max_move)[0]
+    lp = np.asarray(log_probs)
+    if lp.ndim != 2:
+        raise ValueError("log_probs must be [T, V]")
+    return ctc_best_path_determined_batch([lp], [labels], [band_lo], [init_scores], end, beam_size, max_move)[0]
+
+
+def ctc_best_path_tracking_determined_batch(log_probs_list, labels_list, first_lo=0, init_scores_list=None, end="highest", beam_size=1000,
+                                            max_move=4, period=16, device=None, return_status=False, final_scores=True):
+    """``ctc_best_path_tracking_determined`` for a list of lattices in one call: ``ctc_best_path_tracking_resume_batch``'s
+    arguments and results, each result with ``determined`` appended."""
+    lat = _host_lattices(log_probs_list, labels_list, None, None, device)
+    if lat is None:
+        return ([], [], []) if return_status else []
+    return _best_path_tracking_resume(lat, first_lo, init_scores_list, end, beam_size, max_move, period, final_scores, return_status, True)
+
+
+def ctc_best_path_tracking_determined_device(log_probs, labels, first_lo=0, init_scores=None, end="highest", beam_size=1000, max_move=4,
+                                             period=16, return_status=False, final_scores=True):
+    """``ctc_best_path_tracking_determined_batch`` on lists of ROCm torch tensors, as ``ctc_best_path_tracking_resume_device``;
+    ``determined`` is a Python integer."""
+    lat = _device_lattices(log_probs, labels, None, None)
+    return _best_path_tracking_resume(lat, first_lo, init_scores, end, beam_size, max_move, period, final_scores, return_status, True)
+
+
+def ctc_best_path_tracking_determined(log_probs, labels, first_lo=0, init_scores=None, end="highest", beam_size=1000, max_move=4, period=16):
+    """``ctc_best_path_tracking_resume`` that also says how much of its path is final: (best_path, best_labels, best_scores,
+    band_lo, entry, final_scores, next_lo, determined), ``determined`` as in ``ctc_best_path_determined``.  Every other value is
+    ``ctc_best_path_tracking_resume``'s, bit for bit."""
+    if _is_tensor(log_probs):
+        return ctc_best_path_tracking_determined_device([log_probs], [labels], first_lo, [init_scores], end, beam_size, max_move, period)[0]
+    lp = np.asarray(log_probs)
+    if lp.ndim != 2:
+        raise ValueError("log_probs must be [T, V]")
+    return ctc_best_path_tracking_determined_batch([lp], [labels], first_lo, [init_scores], end, beam_size, max_move, period)[0]
+
+
+class StreamingAligner:
+    """The self-steering band fed chunk by chunk, committing frames as soon as they are final.
+
+    ``push(log_probs_chunk)`` takes the next ``[frames, V]`` log-prob rows (NumPy, or ROCm torch tensors throughout) and returns
+    the frames that have become final since the last call as (best_path, best_labels, best_scores, band_lo) arrays, possibly
+    empty; ``finish()`` returns the rest under the aligner's ``end`` rule ("highest" or "best").  The commits concatenated are
+    ``ctc_best_path_tracking`` of the whole input, bit for bit, and a committed frame never changes.  A chunk's length must be
+    a multiple of ``period``; only the last may be ragged, and a push after a ragged one raises ValueError.
+
+    Per push the chunk runs once through ``ctc_best_path_tracking_determined`` from the row and low end the chunk before it
+    left.  If its lines merge (``determined >= 0``), every pending earlier chunk is closed, newest first, by
+    ``ctc_best_path_resume`` over its own table with ``end`` = the entry of the chunk after it, and those frames are emitted
+    followed by this chunk's determined frames; the chunk stays pending from there on.  At most two forward passes per chunk,
+    as ``ctc_best_path_tracking_chunked``; the pending chunks are the only state held.  (A separate class from ``streams.py``'s
+    ``StreamedAligner``, which runs whole lattices on several streams.)"""
+
+    def __init__(self, labels, beam_size=1000, max_move=4, period=16, end="highest"):
+        self.labels = labels
+        self.beam_size, self.max_move, self.period = int(beam_size), int(max_move), int(period)
+        if self.period < 4 or self.period % 4 != 0:
+            raise ValueError("period must be a multiple of 4 in [4, 65536]")
+        if end not in END_CELLS:
+            raise ValueError('end must be "highest" or "best"')
+        self.end = end
+        self._row, self._lo = None, 0      # what the next chunk starts from
+        self._pending = []                 # oldest first: dicts of a chunk's rows, start row, table, path parts, emitted frames
+        self._ragged = False
+        self._finished = False
+        self.frames_pushed = 0
+        self.frames_committed = 0
+
+    @staticmethod
+    def _cat(parts):
+        if _is_tensor(parts[0][0]):
+            import torch
+            return tuple(torch.cat([p[i] for p in parts]) for i in range(4))
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
+
+    def _close_pending(self, entry):
+        """Close every pending chunk but the newest, newest first, from the entry of the chunk after it."""
+        for c in reversed(self._pending[:-1]):
+            r = ctc_best_path_resume(c["lp"], self.labels, c["table"], c["init"], entry, self.beam_size, self.max_move)
+            c["out"] = r[:3] + (c["table"],)
+            entry = r[3]
+
+    def _emit(self, upto_last):
+        """The not-yet-emitted frames of the closed chunks in order, then frames [emitted, upto_last) of the newest chunk."""
+        parts = [tuple(x[c["emitted"]:] for x in c["out"]) for c in self._pending[:-1]]
+        last = self._pending[-1]
+        parts.append(tuple(x[last["emitted"]:upto_last] for x in last["out"]))
+        last["emitted"] = max(last["emitted"], upto_last)
+        self._pending = [last]
+        out = self._cat(parts)
+        self.frames_committed += int(out[0].shape[0])
+        return out
+
+    def push(self, log_probs_chunk):
+        if self._finished:
+            raise ValueError("the aligner is finished")
+        if self._ragged:
+            raise ValueError("a chunk whose length is no multiple of period must be the last")
+        lp = log_probs_chunk if _is_tensor(log_probs_chunk) else np.asarray(log_probs_chunk)
+        if lp.ndim != 2 or lp.shape[0] == 0:
+            raise ValueError("a chunk must be non-empty [frames, V] log-probs")
+        self._ragged = int(lp.shape[0]) % self.period != 0
+        r = ctc_best_path_tracking_determined(lp, self.labels, self._lo, self._row, self.end, self.beam_size, self.max_move, self.period)
+        path, lab, sc, table, entry, row, next_lo, det = r
+        self._pending.append({"lp": lp, "init": self._row, "table": table, "out": (path, lab, sc, table), "emitted": 0, "entry": entry})
+        self._row, self._lo = row, next_lo
+        self.frames_pushed += int(lp.shape[0])
+        if det >= 0:
+            self._close_pending(entry)
+            return self._emit(det)
+        empty = self._pending[-1]["out"]
+        return tuple(x[:0] for x in empty)
+
+    def finish(self):
+        """Close what is pending with the last chunk's own entry and return the remaining frames."""
+        if self._finished:
+            raise ValueError("the aligner is finished")
+        self._finished = True
+        if not self._pending:
+            raise IndexError("list index out of range")   # (no frame was pushed: ctc_best_path's error for T = 0)
+        last = self._pending[-1]
+        self._close_pending(last["entry"])
+        out = self._emit(int(last["out"][0].shape[0]))
+        self._pending = []
+        return out
 
 
 def log_softmax_device(logits, out=None):

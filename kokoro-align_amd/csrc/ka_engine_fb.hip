@@ -643,6 +643,8 @@ struct ResumeArgs {
     int32_t *entry;                    // [n] host, or NULL
     const int32_t *first_lo;           // tracking only: [n] host, or NULL: all 0
     int32_t *next_lo;                  // tracking only: [n] host, or NULL
+    bool walk = false;                 // the determined calls (ka_determined.hpp): the walk from every live cell behind the call
+    int32_t *determined = nullptr;     // ... and its result: [n] host, required
 };
 int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
                 const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move, const int32_t *const *band_lo,
@@ -657,11 +659,15 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
     if (n < 0 || (n > 0 && (!log_probs || !T || !ld || !labels || !S || !band_lo || !best_path || !best_labels || !best_scores)))
         return fail(KA_ERR_BAD_ARGS, "banded best path: NULL array argument");
     if (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE) return fail(KA_ERR_BAD_ARGS, "mem must be KA_MEM_HOST or KA_MEM_DEVICE");
+    const bool walk = rs && rs->walk;
+    if (walk && !rs->determined) return fail(KA_ERR_BAD_ARGS, "determined best path: determined is NULL");
     if (n == 0) return KA_OK;
     std::vector<ka::plan::BandCarve> cv(n);
-    size_t off_meta = 0, off_rows = 0, off_entry = 0;
-    std::vector<size_t> row_init(rs ? n : 0), row_fin(rs ? n : 0);
-    const size_t total = rs ? ka::plan::resume_workspace(n, T, S, V, beam_size, max_move, host, cv.data(), &off_meta, &off_rows, &off_entry,
+    size_t off_meta = 0, off_rows = 0, off_entry = 0, off_det = 0;
+    std::vector<size_t> row_init(rs ? n : 0), row_fin(rs ? n : 0), own_fin(walk ? n : 0);
+    const size_t total = walk ? ka::plan::determined_workspace(n, T, S, V, beam_size, max_move, host, cv.data(), &off_meta, &off_rows, &off_entry,
+                                                               row_init.data(), row_fin.data(), &off_det, own_fin.data(), tracking)
+                         : rs ? ka::plan::resume_workspace(n, T, S, V, beam_size, max_move, host, cv.data(), &off_meta, &off_rows, &off_entry,
                                                          row_init.data(), row_fin.data(), tracking)
                             : ka::plan::banded_workspace(n, T, S, V, beam_size, max_move, host, cv.data(), &off_meta, tracking);
     if (total == 0) return fail(KA_ERR_BAD_ARGS, "banded best path: unsupported T/S/V/beam_size/max_move");
@@ -686,7 +692,8 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
     const size_t meta_bytes = align_up((size_t)n * sizeof(ka::LatticeMeta));
     const size_t rows_bytes = rs ? align_up((size_t)n * sizeof(ka::ResumeRows)) : 0;
     const int32_t cells = rs && tracking ? 2 : 1;   // per lattice behind the rows: the entry, and under tracking the low end of frame T
-    rc = ensure_pin(e, desc_bytes + meta_bytes + rows_bytes + (rs ? (size_t)n * cells * sizeof(int32_t) : 0));
+    const size_t entry_bytes = rs ? align_up((size_t)n * cells * sizeof(int32_t)) : 0;
+    rc = ensure_pin(e, desc_bytes + meta_bytes + rows_bytes + entry_bytes + (walk ? (size_t)n * sizeof(int32_t) : 0));
     if (rc != KA_OK) return rc;
     // the workspace is shared with the best-path calls (see fb_impl)
     if (e->res.refill_done) KA_HIP(hipStreamWaitEvent(stream, e->res.refill_done, 0));
@@ -697,6 +704,7 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
     ka::LatticeMeta *h_meta = reinterpret_cast<ka::LatticeMeta *>(e->res.pin + desc_bytes);
     ka::ResumeRows *h_rows = reinterpret_cast<ka::ResumeRows *>(e->res.pin + desc_bytes + meta_bytes);
     int32_t *h_entry = reinterpret_cast<int32_t *>(e->res.pin + desc_bytes + meta_bytes + rows_bytes);
+    int32_t *h_det = reinterpret_cast<int32_t *>(e->res.pin + desc_bytes + meta_bytes + rows_bytes + entry_bytes);
     int32_t n_fast = 0;
     for (int32_t i = 0; i < n; ++i) n_fast += cv[i].fast ? 1 : 0;
     int32_t k_fast = 0, k_gen = 0;
@@ -711,6 +719,8 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
             ka::ResumeRows &r = h_rows[slot];
             r.init = !init ? nullptr : host ? reinterpret_cast<const float *>(ws + row_init[i]) : init;
             r.fin = !fin ? nullptr : host ? reinterpret_cast<float *>(ws + row_fin[i]) : fin;
+            // (the walk starts from the last row: where the caller wants none, the staged row or one of the engine's own)
+            if (walk && !fin) r.fin = reinterpret_cast<float *>(ws + (host ? row_fin[i] : own_fin[i]));
             r.entry = reinterpret_cast<int32_t *>(ws + off_entry) + (size_t)i * cells;
             r.end = rs->end ? rs->end[i] : -1;
             r.first_lo = rs->first_lo ? rs->first_lo[i] : 0;
@@ -765,11 +775,13 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
         KA_HIP(hipMemcpyAsync(d_rows, h_rows, (size_t)n * sizeof(ka::ResumeRows), hipMemcpyHostToDevice, stream));
         if (tracking) ka::launch_best_path_tracking_resume(d_lats, d_rows, n_fast, n - n_fast, max_move, period, d_meta, stream);
         else ka::launch_best_path_resume(d_lats, d_rows, n_fast, n - n_fast, max_move, d_meta, stream);
+        if (walk) ka::launch_determined(d_lats, d_rows, n_fast, n - n_fast, d_meta, reinterpret_cast<int32_t *>(ws + off_det), stream);
     } else if (tracking) ka::launch_best_path_tracking(d_lats, n_fast, n - n_fast, max_move, period, end_rule, d_meta, stream);
     else ka::launch_best_path_banded(d_lats, n_fast, n - n_fast, max_move, d_meta, stream);
     KA_HIP(hipGetLastError());
     KA_HIP(hipMemcpyAsync(h_meta, d_meta, (size_t)n * sizeof(ka::LatticeMeta), hipMemcpyDeviceToHost, stream));
     if (rs) KA_HIP(hipMemcpyAsync(h_entry, ws + off_entry, (size_t)n * cells * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    if (walk) KA_HIP(hipMemcpyAsync(h_det, ws + off_det, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     KA_HIP(hipStreamSynchronize(stream));
     if (host) {   // only what succeeded is copied out: a failed lattice's outputs stay as the caller left them
         for (int32_t i = 0; i < n; ++i) {
@@ -795,6 +807,7 @@ int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const in
         if (total_score) total_score[i] = h_meta[i].score;
         if (rs && rs->entry) rs->entry[i] = st == KA_OK ? h_entry[(size_t)i * cells] : -1;
         if (rs && tracking && rs->next_lo) rs->next_lo[i] = st == KA_OK || st == KA_ERR_EMPTY_BEAM ? h_entry[(size_t)i * cells + 1] : -1;
+        if (walk) rs->determined[i] = h_det[i];
         if (st != KA_OK && first_bad == KA_OK) {
             first_bad = st;
             g_err = "lattice " + std::to_string(i) +
@@ -918,6 +931,64 @@ size_t ka_tracking_resume_workspace_bytes(int32_t n, const int64_t *T, const int
     if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
     return ka::plan::resume_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                       true);
+}
+
+int ka_ctc_best_path_determined_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                          const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                          const int32_t *const *band_lo, const float *const *init_scores, const int32_t *end,
+                                          int32_t *const *best_path, int32_t *const *best_labels, float *const *best_scores,
+                                          float *const *final_scores, int32_t *entry, int32_t *determined, float *total_score, int32_t *status,
+                                          int32_t mem, void *stream)
+{
+    const ResumeArgs rs{init_scores, end, final_scores, entry, nullptr, nullptr, true, determined};
+    return banded_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, band_lo, best_path, best_labels, best_scores, total_score,
+                       status, mem, (hipStream_t)stream, 0, 0, &rs);
+}
+
+int ka_ctc_best_path_determined_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                    int32_t beam_size, int32_t max_move, const int32_t *band_lo, const float *init_scores, int32_t end,
+                                    int32_t *best_path, int32_t *best_labels, float *best_scores, float *final_scores, int32_t *entry,
+                                    int32_t *determined, float *total_score, int32_t mem, void *stream)
+{
+    const ResumeArgs rs{&init_scores, &end, &final_scores, entry, nullptr, nullptr, true, determined};
+    return banded_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo, &best_path, &best_labels, &best_scores,
+                       total_score, nullptr, mem, (hipStream_t)stream, 0, 0, &rs);
+}
+
+int ka_ctc_best_path_tracking_determined_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                                   const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                                   int32_t max_move, int32_t period, const int32_t *first_lo, const float *const *init_scores,
+                                                   const int32_t *end, int32_t *const *best_path, int32_t *const *best_labels,
+                                                   float *const *best_scores, int32_t *const *band_lo_out, float *const *final_scores,
+                                                   int32_t *entry, int32_t *next_lo, int32_t *determined, float *total_score, int32_t *status,
+                                                   int32_t mem, void *stream)
+{
+    const int rc = tracking_args(period, 0);
+    if (rc != KA_OK) return rc;
+    const ResumeArgs rs{init_scores, end, final_scores, entry, first_lo, next_lo, true, determined};
+    return banded_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, band_lo_out, best_path, best_labels, best_scores, total_score,
+                       status, mem, (hipStream_t)stream, period, 0, &rs);
+}
+
+int ka_ctc_best_path_tracking_determined_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels,
+                                             int64_t S, int32_t beam_size, int32_t max_move, int32_t period, int32_t first_lo,
+                                             const float *init_scores, int32_t end, int32_t *best_path, int32_t *best_labels,
+                                             float *best_scores, int32_t *band_lo_out, float *final_scores, int32_t *entry, int32_t *next_lo,
+                                             int32_t *determined, float *total_score, int32_t mem, void *stream)
+{
+    const int rc = tracking_args(period, 0);
+    if (rc != KA_OK) return rc;
+    const ResumeArgs rs{&init_scores, &end, &final_scores, entry, &first_lo, next_lo, true, determined};
+    return banded_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo_out, &best_path, &best_labels, &best_scores,
+                       total_score, nullptr, mem, (hipStream_t)stream, period, 0, &rs);
+}
+
+size_t ka_determined_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem,
+                                     int32_t tracking)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::determined_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                          nullptr, nullptr, tracking != 0);
 }
 
 size_t ka_tracking_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)

@@ -143,5 +143,10 @@ void launch_backtrace_resume(const BandLattice *lats, const ResumeRows *rows, in
 // A lattice's ResumeRows brings first_lo, and entry points at two cells: the entry and the low end frame T would get ----
 void launch_best_path_tracking_resume(const BandLattice *lats, const ResumeRows *rows, int n_fast, int n_generic, int max_move, int period,
                                       int32_t *meta, hipStream_t s);
+// ---- ka_determined.hip: the determined prefix of a resumed call (ka_determined.hpp), behind either launch above: the walk
+// from every live cell of the last row (ResumeRows::fin, which must be there) back to where the lines merge.  `det`: one int32
+// per lattice of the batch, in the caller's order ----
+void launch_determined(const BandLattice *lats, const ResumeRows *rows, int n_fast, int n_generic, const int32_t *meta, int32_t *det,
+                       hipStream_t s);
 
 }  // namespace ka

@@ -1009,6 +1009,26 @@ inline size_t resume_workspace(int32_t n, const int64_t *T, const int64_t *S, in
     return off;
 }
 
+// ---- ka_ctc_best_path_determined_batch_f32, ka_ctc_best_path_tracking_determined_batch_f32 (ka_determined.hpp):
+// resume_workspace and, behind it, the `determined` cell (int32) of every lattice and, for device buffers, a last row of the
+// engine's own per lattice ([2S+1] float32: the walk starts from the last row, whether or not the caller asks for it; with host
+// buffers the staged row serves).  The byte count depends on the shapes alone, not on which rows the caller gives.
+inline size_t determined_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
+                                   BandCarve *cv, size_t *off_meta, size_t *off_rows, size_t *off_entry, size_t *init, size_t *fin,
+                                   size_t *off_det, size_t *own_fin, bool tracking)
+{
+    size_t off = resume_workspace(n, T, S, V, beam, max_move, host_buffers, cv, off_meta, off_rows, off_entry, init, fin, tracking);
+    if (off == 0) return 0;
+    if (off_det) *off_det = off;
+    off += align_up((size_t)n * sizeof(int32_t));
+    if (!host_buffers)
+        for (int32_t i = 0; i < n; ++i) {
+            if (own_fin) own_fin[i] = off;
+            off += align_up((size_t)(2 * S[i] + 1) * sizeof(float));
+        }
+    return off;
+}
+
 }  // namespace plan
 }  // namespace ka
 

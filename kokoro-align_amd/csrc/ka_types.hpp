@@ -307,5 +307,9 @@ struct ResumeRows {
     int32_t first_lo;    // self-steering band only: the low end of frame 0, in [0, L); else 0
 };
 static_assert(sizeof(ResumeRows) == 32, "descriptor sizes");
+// ---- ... and its determined prefix (ka_ctc_best_path_determined): the walk of ka_determined.hpp reads
+// ResumeRows::fin, which the engine then always sets (a row of its own where the caller wants none), and writes one int32 per
+// lattice of the batch ----
+constexpr int32_t kUndetermined = -1;   // the live cells trace back to more than one start cell, or no cell is live
 
 }  // namespace ka
