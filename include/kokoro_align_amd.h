@@ -743,6 +743,63 @@ int ka_ctc_state_durations_banded_batch_f32(ka_engine *e, int32_t n, const float
 size_t ka_band_table_workspace_bytes(int32_t n, const int64_t *T, int32_t mem);
 
 /*
+ * Forward-backward posteriors under the caller's boundary conditions: the posterior side of
+ * ka_ctc_best_path_resume.  The checkpointed forward-backward of ka_ctc_label_posteriors_banded over a table band_lo (required;
+ * there is no diagonal form) with the row before frame 0 and the row at frame T-1 given by the caller, and the two rows a
+ * neighbouring chunk needs handed back.  Recurrence, veto, forms, memory modes, statuses, return convention and stream
+ * synchronisation are that call's.  L = 2S+1.  Every row is [L] float64 in nats, absolute; -inf is no mass.
+ *   alpha_in   NULL: the virtual state {0: 0.0}.  Else ln alpha of the row before frame 0.  No band applies to it: frame 0
+ *              reads alpha_in[p-j] for p in [lo_0, hi_0), so only [lo_0 - (max_move-1), hi_0) matters; the veto applies to frame
+ *              0's moves as to any frame's.
+ *   beta_in    NULL: beta_{T-1} = {terminal: 0}.  Else beta_{T-1}(p) = beta_in[p] over band T-1 (cells outside it are checked
+ *              for NaN and +inf and otherwise unused) and `terminal` is ignored.  A row of zeros lets the path end anywhere: Z is the mass of the audio so far.
+ *   path       [T] int32 or NULL; required by path_post.
+ *   occupancy  [T, ld_out] or NULL: the sibling's output.
+ *   path_post  [T] float32 or NULL: gamma at (t, path[t]) as the state posteriors form it; 0 where path[t] is outside band t.
+ *   alpha_out  [L] or NULL: ln alpha_{T-1}(p) over band T-1, -inf elsewhere.
+ *   beta_out   [L] or NULL: the beta of the row before frame 0: logsumexp_j(beta_0(p+j) + lp[0, lab'[p+j]]) over the moves into
+ *              band 0 (a skip into a cell whose label value is 0 is vetoed), for p in [max(lo_0 - (max_move-1), 0), hi_0); -inf
+ *              elsewhere.
+ *   log_likelihood   Z = logsumexp over band T-1 of alpha_{T-1}(p) + beta_{T-1}(p); with a NULL beta_in the sibling's Z.
+ * In the batch call alpha_in, beta_in, path, occupancy, path_post, alpha_out and beta_out are HOST arrays of n pointers; an array
+ * or any entry may be NULL (ld_out is required with occupancy; terminal may be NULL if every lattice brings a beta_in).
+ * alpha_out and beta_out may not overlap alpha_in or beta_in (the kernel reads the input rows again after it has written
+ * alpha_out): such a call fails with KA_ERR_BAD_ARGS before anything is launched.  To move a row on, write it beside the old one.
+ * A NaN or +inf anywhere in either row (all 2S+1 cells, read or not) is KA_ERR_BAD_ARGS for that lattice alone.  Any status but KA_OK fills every requested output of
+ * the lattice with NaN, rows included, so a chunk resumed from a failed chunk fails too; KA_ERR_ZERO_MASS is Z = -inf.
+ * The forward pass always runs; checkpoints and the block recompute only for occupancy or path_post; the backward pass only
+ * for occupancy, path_post or beta_out: alpha_out and Z alone cost one forward pass.
+ * What follows:
+ *   1. alpha_in NULL, beta_in NULL, no rows out: occupancy, log_likelihood, status and return code are
+ *      ka_ctc_label_posteriors_banded[_batch]_f32's bit for bit.
+ *   2. alpha_out has the same bits whether or not the backward pass ran, beta_out whether or not gamma was asked for.
+ *   3. A lattice gives the same bits alone or inside a batch, whatever its neighbours' rows.
+ *   4. Cut at any k in [1, T): chunk A = frames [0, k), chunk B = frames [k, T), B's alpha_in = A's alpha_out, A's beta_in = B's
+ *      beta_out.  The occupancies and path posteriors, concatenated, are the uncut lattice's; A's Z, B's Z and the uncut Z
+ *      agree; logsumexp(alpha_in + beta_out) over a chunk's start row is its Z.
+ * Cost as measured (cfg2: T = 50000, V = 64, S = 5000, beam 1000, one MI355X, against ka_ctc_label_posteriors_banded_batch_f32
+ * of the same build, minimum of nine; tools/bench_fb_resume.py): NULL rows 1.018 x (one lattice) and 1.017 x (1024 lattices) the
+ * sibling, whose run-to-run spread is 1.003; both rows in and out 1.028 x and 1.017 x; alpha_out and Z alone 0.300 x and 0.273 x.
+ * A recording in 8 chunks (a forward-only sweep, then the chunks newest first) 1.29 x the uncut call.
+ * ka_posteriors_resume_workspace_bytes: the device-workspace bytes of a call (the sibling's figure plus the descriptors, the
+ * staged tables and, for KA_MEM_HOST, the staged path, path posteriors and four rows); 0 for unsupported arguments.
+ */
+int ka_ctc_posteriors_resume_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                 int32_t beam_size, int32_t max_move, const int32_t *band_lo, const double *alpha_in,
+                                 const double *beta_in, int64_t terminal, const int32_t *path, float *occupancy, int64_t ld_out,
+                                 float *path_post, double *alpha_out, double *beta_out, double *log_likelihood, int32_t mem,
+                                 void *stream);
+int ka_ctc_posteriors_resume_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
+                                       const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
+                                       int32_t max_move, const int32_t *const *band_lo, const double *const *alpha_in,
+                                       const double *const *beta_in, const int64_t *terminal, const int32_t *const *path,
+                                       float *const *occupancy, const int64_t *ld_out, float *const *path_post,
+                                       double *const *alpha_out, double *const *beta_out, double *log_likelihood, int32_t *status,
+                                       int32_t mem, void *stream);
+size_t ka_posteriors_resume_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size,
+                                            int32_t max_move, int32_t mem);
+
+/*
  * State visits, boundary quantiles, sampled paths and the MEA path over a caller-given band: the
  * other half of the forward-backward family on the table of the block above, by the same rule.  Each call is its sibling with
  * the table behind max_move (single call: const int32_t *band_lo, [T] int32 where `mem` says; batch call: a HOST array of n

@@ -26,7 +26,9 @@ reference's keep-or-drop test of a segment (ctc_state_visits[_batch|_device], ph
 segment_expected_match), and the exact quantiles of every boundary's frame, the interval a cut lies in with a given probability
 (ctc_boundary_quantiles[_batch|_device], boundary_cuts, segment_boundary_interval), and on the best-path side the per-frame
 margin of a path over the best alignment that disagrees with it, from max-marginals in exact float64 max-plus arithmetic
-(ctc_path_margins[_batch|_device], segment_boundary_margin, segment_min_margin).
+(ctc_path_margins[_batch|_device], segment_boundary_margin, segment_min_margin); and the forward-backward itself resumable, a
+chunk at a time from a caller-given start row to a caller-given end row (ctc_posteriors_resume[_batch|_device], free_end_scores,
+ctc_label_posteriors_chunked, StreamingAligner(confidence=True)).
 
 The DP and backtrace run in the HIP C-ABI library (include/kokoro_align_amd.h); there is no
 CPU fallback — importing works without a GPU, computing does not.
@@ -82,9 +84,14 @@ from .posteriors import (  # noqa: F401
     ctc_path_margins,
     ctc_path_margins_batch,
     ctc_path_margins_device,
+    ctc_label_posteriors_chunked,
     ctc_path_posteriors,
     ctc_path_posteriors_batch,
     ctc_path_posteriors_device,
+    ctc_posteriors_resume,
+    ctc_posteriors_resume_batch,
+    ctc_posteriors_resume_device,
+    free_end_scores,
     ctc_sample_paths,
     ctc_sample_paths_batch,
     ctc_sample_paths_device,

@@ -60,6 +60,7 @@ EXPORTS = [
     "ka_ctc_path_margins_f32", "ka_ctc_path_margins_batch_f32", "ka_path_margin_workspace_bytes",
     "ka_ctc_best_path_determined_f32", "ka_ctc_best_path_determined_batch_f32",
     "ka_ctc_best_path_tracking_determined_f32", "ka_ctc_best_path_tracking_determined_batch_f32", "ka_determined_workspace_bytes",
+    "ka_ctc_posteriors_resume_f32", "ka_ctc_posteriors_resume_batch_f32", "ka_posteriors_resume_workspace_bytes",
 ]
 
 
@@ -221,6 +222,14 @@ def load_library():
             banded = getattr(L, f"ka_ctc_{call}_banded{form}_f32")
             banded.restype = ctypes.c_int
             banded.argtypes = sibling.argtypes[:at] + [kind] + sibling.argtypes[at:]
+    # the resumed forward-backward: the table, the two rows in, terminal, path, then occupancy, ld_out, path_post and the two rows out
+    L.ka_ctc_posteriors_resume_f32.restype = ctypes.c_int
+    L.ka_ctc_posteriors_resume_f32.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i32, vp]
+    L.ka_ctc_posteriors_resume_batch_f32.restype = ctypes.c_int
+    L.ka_ctc_posteriors_resume_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pp, pp, pp, pi64, pp, pp, pi64, pp, pp, pp,
+                                                     vp, vp, i32, vp]
+    L.ka_posteriors_resume_workspace_bytes.restype = sz
+    L.ka_posteriors_resume_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
     L.ka_band_table_workspace_bytes.restype = sz
     L.ka_band_table_workspace_bytes.argtypes = [i32, pi64, i32]
     L.ka_boundary_quantile_band_table_workspace_bytes.restype = sz

@@ -706,9 +706,17 @@ class StreamingAligner:
     ``ctc_best_path_resume`` over its own table with ``end`` = the entry of the chunk after it, and those frames are emitted
     followed by this chunk's determined frames; the chunk stays pending from there on.  At most two forward passes per chunk,
     as ``ctc_best_path_tracking_chunked``; the pending chunks are the only state held.  (A separate class from ``streams.py``'s
-    ``StreamedAligner``, which runs whole lattices on several streams.)"""
+    ``StreamedAligner``, which runs whole lattices on several streams.)
 
-    def __init__(self, labels, beam_size=1000, max_move=4, period=16, end="highest"):
+    ``confidence=True``: ``push()`` and ``finish()`` return a fifth array, float32, one value per committed frame: the posterior
+    of the committed state given all audio pushed so far, under the tracked band (``ctc_posteriors_resume``).  Every push runs its
+    chunk forward-only from the alpha row the chunk before it left.  On a commit the pending chunks are visited newest first: the
+    newest ends anywhere (``free_end_scores``; at ``finish()`` it ends at the final path's last state), every older one at the
+    ``beta_out`` of the chunk after it; only the newly committed frames' values are returned.  Cost: at most two full
+    forward-backward passes and one forward-only pass per chunk, and one more row of 2S+1 doubles per pending chunk.  With
+    ``False`` nothing changes."""
+
+    def __init__(self, labels, beam_size=1000, max_move=4, period=16, end="highest", confidence=False):
         self.labels = labels
         self.beam_size, self.max_move, self.period = int(beam_size), int(max_move), int(period)
         if self.period < 4 or self.period % 4 != 0:
@@ -716,7 +724,9 @@ class StreamingAligner:
         if end not in END_CELLS:
             raise ValueError('end must be "highest" or "best"')
         self.end = end
+        self.confidence = bool(confidence)
         self._row, self._lo = None, 0      # what the next chunk starts from
+        self._alpha = None                 # confidence: ln alpha of the last pushed frame, the next chunk's start row
         self._pending = []                 # oldest first: dicts of a chunk's rows, start row, table, path parts, emitted frames
         self._ragged = False
         self._finished = False
@@ -748,6 +758,33 @@ class StreamingAligner:
         self.frames_committed += int(out[0].shape[0])
         return out
 
+    def _confidence(self, upto_last, terminal=None):
+        """The posterior of the committed state at every frame ``_emit(upto_last)`` is about to return: the pending chunks newest
+        first, the newest to a free end (or ``terminal``), each older one to the row the chunk after it handed back."""
+        from .posteriors import ctc_posteriors_resume, free_end_scores
+        L = 2 * int(self._pending[-1]["S"]) + 1
+        end = free_end_scores(L) if terminal is None else int(terminal)
+        posts = []
+        for k in range(len(self._pending) - 1, -1, -1):
+            c = self._pending[k]
+            _o, post, _a, end, _z = ctc_posteriors_resume(c["lp"], self.labels, c["table"], c["alpha_in"], end, c["out"][0], False,
+                                                          "beta" if k > 0 else False, self.beam_size, self.max_move)
+            posts.append(post[c["emitted"]:upto_last] if k == len(self._pending) - 1 else post[c["emitted"]:])
+        posts.reverse()
+        if _is_tensor(posts[0]):
+            import torch
+            return torch.cat(posts)
+        return np.concatenate(posts)
+
+    def _forward(self, lp, table):
+        """confidence: the chunk forward-only from the kept alpha row; what it adds to the chunk's pending entry"""
+        from .posteriors import ctc_posteriors_resume, free_end_scores
+        S = int(self.labels.shape[0]) if _is_tensor(self.labels) else int(np.asarray(self.labels).reshape(-1).shape[0])
+        alpha_in = self._alpha
+        self._alpha = ctc_posteriors_resume(lp, self.labels, table, alpha_in, free_end_scores(2 * S + 1), None, False, "alpha",
+                                            self.beam_size, self.max_move)[2]
+        return {"alpha_in": alpha_in, "S": S}
+
     def push(self, log_probs_chunk):
         if self._finished:
             raise ValueError("the aligner is finished")
@@ -759,14 +796,17 @@ class StreamingAligner:
         self._ragged = int(lp.shape[0]) % self.period != 0
         r = ctc_best_path_tracking_determined(lp, self.labels, self._lo, self._row, self.end, self.beam_size, self.max_move, self.period)
         path, lab, sc, table, entry, row, next_lo, det = r
-        self._pending.append({"lp": lp, "init": self._row, "table": table, "out": (path, lab, sc, table), "emitted": 0, "entry": entry})
+        forward = self._forward(lp, table) if self.confidence else {}      # (before the chunk is registered: it may raise)
+        self._pending.append({"lp": lp, "init": self._row, "table": table, "out": (path, lab, sc, table), "emitted": 0, "entry": entry, **forward})
         self._row, self._lo = row, next_lo
         self.frames_pushed += int(lp.shape[0])
         if det >= 0:
             self._close_pending(entry)
-            return self._emit(det)
+            conf = (self._confidence(det),) if self.confidence else ()
+            return self._emit(det) + conf
         empty = self._pending[-1]["out"]
-        return tuple(x[:0] for x in empty)
+        conf = ((sc[:0] if _is_tensor(sc) else np.zeros(0, np.float32)),) if self.confidence else ()
+        return tuple(x[:0] for x in empty) + conf
 
     def finish(self):
         """Close what is pending with the last chunk's own entry and return the remaining frames."""
@@ -777,7 +817,9 @@ class StreamingAligner:
             raise IndexError("list index out of range")   # (no frame was pushed: ctc_best_path's error for T = 0)
         last = self._pending[-1]
         self._close_pending(last["entry"])
-        out = self._emit(int(last["out"][0].shape[0]))
+        n = int(last["out"][0].shape[0])
+        conf = (self._confidence(n, int(last["out"][0][-1])),) if self.confidence else ()
+        out = self._emit(n) + conf
         self._pending = []
         return out
 

@@ -503,6 +503,83 @@ struct MarginCall {
     }
 };
 
+// Forward-backward posteriors under the caller's boundary conditions (ka_fb_resume.hpp): OccCall's slots with up to four rows, a
+// path and two more outputs per lattice, every one of them optional (a NULL array, or a NULL entry).  Banded only.
+struct ResumeFbCall {
+    using Desc = ka::ResumeFbLattice;
+    static constexpr size_t kBandedGranule = ka::kBandedResumeFbDescBytes;
+    using Carve = ka::plan::ResumeFbCarve;
+    static constexpr const char *kName = "posteriors resume";
+    static constexpr const char *kBadArgs = ": terminal outside [0, 2S+1), or a NaN or +inf in alpha_in or beta_in";
+    static constexpr const char *kZeroMass = ": no path of finite score joins the start row to the end";
+    const double *const *alpha_in;
+    const double *const *beta_in;
+    const int64_t *terminal;         // may be NULL: every lattice then needs a beta_in
+    const int32_t *const *path;
+    float *const *occupancy;
+    const int64_t *ld_out;           // required with occupancy
+    float *const *path_post;
+    double *const *alpha_out;
+    double *const *beta_out;
+
+    template <class P>
+    static P at(P const *arr, int32_t i) { return arr ? arr[i] : nullptr; }
+    bool arrays() const { return !occupancy || ld_out; }
+    const char *bad_lattice(const FbArgs &a, int32_t i) const
+    {
+        if (at(occupancy, i) && ld_out[i] < a.V) return ": ld_out < V";
+        if (at(path_post, i) && !at(path, i)) return ": path_post without path";
+        // (the kernel reads alpha_in again behind the store of alpha_out, and beta_in behind it)
+        const size_t row = (size_t)(2 * a.S[i] + 1) * sizeof(double);
+        auto overlap = [row](const double *x, const double *y) {
+            return x && y && reinterpret_cast<uintptr_t>(x) < reinterpret_cast<uintptr_t>(y) + row &&
+                   reinterpret_cast<uintptr_t>(y) < reinterpret_cast<uintptr_t>(x) + row;
+        };
+        for (const double *out : {(const double *)at(alpha_out, i), (const double *)at(beta_out, i)})
+            if (overlap(out, at(alpha_in, i)) || overlap(out, at(beta_in, i))) return ": an output row overlaps an input row";
+        return nullptr;
+    }
+    bool buffers(int32_t) const { return true; }
+    static constexpr auto plan = ka::plan::posteriors_resume_workspace;
+    template <class Band>
+    static constexpr auto launch = ka::launch_posteriors_resume<Band>;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        const bool host = a.mem == KA_MEM_HOST;
+        auto dbl = [&](const double *p, int k) { return !p ? nullptr : host ? reinterpret_cast<double *>(ws + c.rows[k]) : const_cast<double *>(p); };
+        d.occ = !at(occupancy, i) ? nullptr : host ? reinterpret_cast<float *>(ws + c.occ) : occupancy[i];
+        d.ld_out = !at(occupancy, i) ? 0 : host ? a.V : ld_out[i];
+        d.alpha_in = dbl(at(alpha_in, i), 0);
+        d.beta_in = dbl(at(beta_in, i), 1);
+        d.alpha_out = dbl(at(alpha_out, i), 2);
+        d.beta_out = dbl(at(beta_out, i), 3);
+        d.path = !at(path, i) ? nullptr : host ? reinterpret_cast<const int32_t *>(ws + c.path) : path[i];
+        d.path_post = !at(path_post, i) ? nullptr : host ? reinterpret_cast<float *>(ws + c.ppost) : path_post[i];
+        fill_slot(d, c, terminal ? terminal[i] : -1, ws);
+        d.gbin = reinterpret_cast<unsigned long long *>(ws + c.slot + c.parts.gbin);
+    }
+    int upload(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        const size_t row = (size_t)(2 * a.S[i] + 1) * sizeof(double);
+        if (at(alpha_in, i)) KA_HIP(hipMemcpyAsync(ws + c.rows[0], alpha_in[i], row, hipMemcpyHostToDevice, a.stream));
+        if (at(beta_in, i)) KA_HIP(hipMemcpyAsync(ws + c.rows[1], beta_in[i], row, hipMemcpyHostToDevice, a.stream));
+        if (at(path, i)) KA_HIP(hipMemcpyAsync(ws + c.path, path[i], (size_t)a.T[i] * 4, hipMemcpyHostToDevice, a.stream));
+        return KA_OK;
+    }
+    int stage(const Carve &, const FbArgs &, int32_t, char *) const { return KA_OK; }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        const size_t row = (size_t)(2 * a.S[i] + 1) * sizeof(double);
+        if (at(occupancy, i))
+            KA_HIP(hipMemcpy2DAsync(occupancy[i], (size_t)ld_out[i] * 4, ws + c.occ, (size_t)a.V * 4, (size_t)a.V * 4, (size_t)a.T[i],
+                                    hipMemcpyDeviceToHost, a.stream));
+        if (at(path_post, i)) KA_HIP(hipMemcpyAsync(path_post[i], ws + c.ppost, (size_t)a.T[i] * 4, hipMemcpyDeviceToHost, a.stream));
+        if (at(alpha_out, i)) KA_HIP(hipMemcpyAsync(alpha_out[i], ws + c.rows[2], row, hipMemcpyDeviceToHost, a.stream));
+        if (at(beta_out, i)) KA_HIP(hipMemcpyAsync(beta_out[i], ws + c.rows[3], row, hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
 // what a call reads back per lattice besides PostResult, in both memory modes, enqueued behind the launch: nothing, but for
 // the expected accuracies of MeaCall (one double per lattice, consecutive from lattice 0's)
 template <class Call>
@@ -1178,6 +1255,37 @@ int ka_ctc_state_durations_banded_f32(ka_engine *e, const float *log_probs, int6
     return fb_impl<DurCall, ka::BandTable>(
         e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo},
         DurCall{&terminal, &duration, &time_sum});
+}
+
+int ka_ctc_posteriors_resume_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                       const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                       const int32_t *const *band_lo, const double *const *alpha_in, const double *const *beta_in,
+                                       const int64_t *terminal, const int32_t *const *path, float *const *occupancy, const int64_t *ld_out,
+                                       float *const *path_post, double *const *alpha_out, double *const *beta_out, double *log_likelihood,
+                                       int32_t *status, int32_t mem, void *stream)
+{
+    if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "posteriors resume: NULL band_lo");
+    return fb_impl<ResumeFbCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
+                                                ResumeFbCall{alpha_in, beta_in, terminal, path, occupancy, ld_out, path_post, alpha_out, beta_out});
+}
+
+int ka_ctc_posteriors_resume_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                                 int32_t beam_size, int32_t max_move, const int32_t *band_lo, const double *alpha_in, const double *beta_in,
+                                 int64_t terminal, const int32_t *path, float *occupancy, int64_t ld_out, float *path_post, double *alpha_out,
+                                 double *beta_out, double *log_likelihood, int32_t mem, void *stream)
+{
+    return fb_impl<ResumeFbCall, ka::BandTable>(
+        e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo},
+        ResumeFbCall{&alpha_in, &beta_in, &terminal, &path, &occupancy, &ld_out, &path_post, &alpha_out, &beta_out});
+}
+
+size_t ka_posteriors_resume_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
+                                            int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    const size_t own = ka::plan::posteriors_resume_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+    const size_t tab = ka::plan::band_table_workspace(n, T, mem == KA_MEM_HOST, nullptr, ka::kBandedResumeFbDescBytes);
+    return own && tab ? align_up(own) + tab : 0;
 }
 
 size_t ka_band_table_workspace_bytes(int32_t n, const int64_t *T, int32_t mem)

@@ -64,6 +64,34 @@ struct fb_begin : std::false_type {};
 template <class Out>
 struct fb_begin<Out, std::void_t<decltype(&Out::begin)>> : std::true_type {};
 
+// The boundary policy of the passes below: what stands before frame 0 and at frame T-1.  FbVirtualBound, the default, is the
+// virtual state {0: 0} and one terminal s*: every `if constexpr (Bound::kVirtual)` below keeps the lines the calls have always
+// run.  A caller's boundary conditions (FbCallerBound of ka_fb_resume.hpp, the only other one) are named by an Out as its
+// member type Bound and handed over by its bound(); such a policy brings
+//   place(f, bw, prev, plo, phi, C, flags)   the row before frame 0 into prev over [plo, phi), its maximum into the offset C (bw
+//                                stands at frame 0); the forward pass and the recompute of block 0 both call it, so block 0 has no
+//                                checkpoint of its own
+//   stores()                     does the forward pass store checkpoints (is any gamma asked for)?
+//   finish(f, prev, plo, phi, Cb, Ca, flags, Z, Zr)   the end of the forward pass: the status, Z, and what the call keeps of the last row
+//   backward()                   does the backward pass run?
+//   d0(), end(sstar)             the offset D the backward pass starts from and the End its frame T-1 is seeded with (fb_end_w)
+//   before(f, gn, vn, nlo, nhi, nprev, D)   behind frame 0 of the backward pass: what the call keeps of the row before frame 0
+struct FbVirtualBound {
+    static constexpr bool kVirtual = true;
+    __device__ __forceinline__ static double d0() { return 0.0; }   // D_T = 0: beta_{T-1} = {s*: 0}
+    __device__ __forceinline__ static int64_t end(int64_t sstar) { return sstar; }
+};
+template <class Out, class = void>
+struct fb_bound_of {
+    using type = FbVirtualBound;
+    __device__ __forceinline__ static FbVirtualBound get(Out &) { return {}; }
+};
+template <class Out>
+struct fb_bound_of<Out, std::void_t<typename Out::Bound>> {
+    using type = typename Out::Bound;
+    __device__ __forceinline__ static type &get(Out &out) { return out.bound(); }
+};
+
 // one cell's gamma as a float from its log2 argument (occ_fix of ka_occupancy.hpp before the fixed-point step): what the state
 // posteriors write and the state durations add
 __device__ __forceinline__ float fb_gamma(double arg)
@@ -76,8 +104,8 @@ __device__ __forceinline__ float fb_gamma(double arg)
 // zero-mass checks, Z (log2 alpha_{T-1}(s*), the expression gamma's alpha is formed with) and Zr (fb_reported_z).  Returns
 // kStatusOk or the status the lattice fails with; col(0) / col(1) are its working columns, bw ends at frame T.  It ends behind
 // f.sync(): in the generic form a barrier, which also orders the sampler's first slab.
-template <class Form, class Band>
-__device__ __forceinline__ int fb_ck_forward(Form &f, Band &bw, double &Z, double &Zr)
+template <class Form, class Band, class Bound>
+__device__ __forceinline__ int fb_ck_forward(Form &f, Band &bw, double &Z, double &Zr, Bound &bd)
 {
     const FbCkLattice &d = f.d;
     const int tid = threadIdx.x;
@@ -87,10 +115,12 @@ __device__ __forceinline__ int fb_ck_forward(Form &f, Band &bw, double &Z, doubl
     if (!bw.start()) return kStatusBadArgs;   // (a caller's table that is no band: before any of its values places a cell)
     auto no_cell = [](int64_t, double) {};
     double *prev = f.col(0), *cur = f.col(1);
-    if (tid == 0) prev[0] = 0.0;   // virtual state before frame 0
+    if constexpr (Bound::kVirtual)
+        if (tid == 0) prev[0] = 0.0;   // virtual state before frame 0
     int64_t plo = 0, phi = 1;
     double C = 0.0, Cb = 0.0, Ca = 0.0, mprev = 0.0;
     int flags = 0;
+    if constexpr (!Bound::kVirtual) bd.place(f, bw, prev, plo, phi, C, flags);
     f.row_prefetch(0);
     f.sync();
     for (int64_t t = 0; t < T; ++t) {
@@ -100,11 +130,15 @@ __device__ __forceinline__ int fb_ck_forward(Form &f, Band &bw, double &Z, doubl
         if (t % kPostCk == 0) {
             const int64_t k = t / kPostCk;
             Cb = C;
-            if (tid == 0) {
-                d.ck[2 * k] = C;
-                d.ck[2 * k + 1] = mprev;
+            bool store = true;
+            if constexpr (!Bound::kVirtual) store = k > 0 && bd.stores();
+            if (store) {
+                if (tid == 0) {
+                    d.ck[2 * k] = C;
+                    d.ck[2 * k + 1] = mprev;
+                }
+                f.ck_store(k, prev, plo, phi);
             }
-            f.ck_store(k, prev, plo, phi);
         }
         f.fence();
         double m = f.max(f.fwd(lo, hi, plo, phi, prev, cur, mprev, no_cell));
@@ -118,6 +152,7 @@ __device__ __forceinline__ int fb_ck_forward(Form &f, Band &bw, double &Z, doubl
         bw.next();
         f.fence();
     }
+    if constexpr (!Bound::kVirtual) return bd.finish(f, prev, plo, phi, Cb, Ca, flags, Z, Zr);
     const int64_t sstar = d.terminal;
     flags |= (sstar < 0 || sstar >= L) ? 4 : 0;
     flags = post_block_flags(flags);
@@ -129,13 +164,19 @@ __device__ __forceinline__ int fb_ck_forward(Form &f, Band &bw, double &Z, doubl
     f.sync();
     return kStatusOk;
 }
+template <class Form, class Band>
+__device__ __forceinline__ int fb_ck_forward(Form &f, Band &bw, double &Z, double &Zr)
+{
+    FbVirtualBound bd;
+    return fb_ck_forward(f, bw, Z, Zr, bd);
+}
 
 // The recompute of block k = [t0, t1): alpha from the block's checkpoint into the slab (row t - t0, slot Form::slot) with the
 // forward pass's frame function on the forward pass's operands, pv / cu the working columns; note(t - t0, C) is handed every
 // frame's offset before the frame runs.  bw ends at frame t1.  A cell's slab entry is written by the thread that owns the
 // cell in that frame.  The generic form ends behind a barrier; the fast form's last frame ends in its fence.
-template <class Form, class Band, class Note>
-__device__ __forceinline__ void fb_ck_recompute(Form &f, int64_t k, int64_t t0, int64_t t1, Band &bw, double *pv, double *cu, Note note)
+template <class Form, class Band, class Note, class Bound>
+__device__ __forceinline__ void fb_ck_recompute(Form &f, int64_t k, int64_t t0, int64_t t1, Band &bw, double *pv, double *cu, Note note, Bound &bd)
 {
     const FbCkLattice &d = f.d;
     const double NINF = post_dninf();
@@ -146,14 +187,21 @@ __device__ __forceinline__ void fb_ck_recompute(Form &f, int64_t k, int64_t t0, 
         C2 = d.ck[2 * k];
         mp = d.ck[2 * k + 1];
     };
-    if (Form::kWave) load();   // (all of the column's slots, whatever the band: issued before the seek's division)
+    const bool placed = !Bound::kVirtual && k == 0;   // block 0 under a caller's start row: placed again, not loaded
+    if (Form::kWave && !placed) load();   // (all of the column's slots, whatever the band: issued before the seek's division)
     bw.seek(t0);
     if (t0 > 0) {
         bw.prev();
         bw.band(rlo, rhi);
         bw.next();
     }
-    if (!Form::kWave) load();
+    if (!Form::kWave && !placed) load();
+    if constexpr (!Bound::kVirtual)
+        if (placed) {
+            int none = 0;
+            mp = 0.0;
+            bd.place(f, bw, pv, rlo, rhi, C2, none);
+        }
     f.row_prefetch(t0);
     f.sync();
     for (int64_t t = t0; t < t1; ++t) {
@@ -175,6 +223,12 @@ __device__ __forceinline__ void fb_ck_recompute(Form &f, int64_t k, int64_t t0, 
     }
     if (!Form::kWave) f.sync();
 }
+template <class Form, class Band, class Note>
+__device__ __forceinline__ void fb_ck_recompute(Form &f, int64_t k, int64_t t0, int64_t t1, Band &bw, double *pv, double *cu, Note note)
+{
+    FbVirtualBound bd;
+    fb_ck_recompute(f, k, t0, t1, bw, pv, cu, note, bd);
+}
 
 // The driver of the calls that need gamma; cav: kPostCk doubles of LDS, the offsets of the block's frames; Band: the band
 // (BandWalk, or BandTable of ka_posterior_common.hpp on `tab`, the caller's table).
@@ -187,26 +241,36 @@ __device__ __forceinline__ void fb_ck(Form &f, PostResult *res, double *cav, Out
     const double NINF = post_dninf();
 
     // ---- forward: Z, and a checkpoint before every block ----
+    using Bound = typename fb_bound_of<Out>::type;
+    decltype(auto) bd = fb_bound_of<Out>::get(out);
     Band bw(d.L, d.beam, T, tab);
     double Z, Zr;
-    const int status = fb_ck_forward(f, bw, Z, Zr);
+    const int status = fb_ck_forward(f, bw, Z, Zr, bd);
     if (status != kStatusOk) {
         out.fail(res, status);
         return;
     }
     const int64_t sstar = d.terminal;
     if constexpr (fb_begin<Out>::value) out.begin();
+    if constexpr (!Bound::kVirtual)
+        if (!bd.backward()) {   // a forward pass alone
+            if (tid == 0) {
+                res[d.idx].status = kStatusOk;
+                res[d.idx].log_likelihood = Zr;
+            }
+            return;
+        }
 
     // ---- backward, a block at a time ----
     double *gn = f.col(0), *vn = f.col(1), *gc = f.col(2), *vc = f.col(3);   // G_{t+1} and its vetoable copy; scratch
     int64_t nlo = 0, nhi = 0;
-    double D = 0.0, nprev = 0.0;   // D_T = 0: beta_{T-1} = {s*: 0}
+    double D = bd.d0(), nprev = 0.0;   // D_T = 0: beta_{T-1} = {s*: 0}; a caller's row: its maximum
     for (int64_t k = (T - 1) / kPostCk; k >= 0; --k) {
         const int64_t t0 = k * kPostCk, t1 = (t0 + kPostCk < T) ? t0 + kPostCk : T;
         if (out.recompute(t0)) {   // alpha over [t0, t1) into the slab, gc / vc as the working columns
             fb_ck_recompute(f, k, t0, t1, bw, gc, vc, [&](int64_t fr, double c) {
                 if (tid == 0) cav[fr] = c;
-            });
+            }, bd);
         } else {
             bw.seek(t1);
         }
@@ -222,7 +286,7 @@ __device__ __forceinline__ void fb_ck(Form &f, PostResult *res, double *cav, Out
             if constexpr (fb_next_column<Out>::value) out.next_column(gn, vn, nprev, t == T - 1);
             auto cell = out.cells(t, lo);
             f.fence();
-            const double mymax = f.bwd(lo, hi, nlo, nhi, gn, vn, gc, vc, nprev, t == T - 1, sstar, [&](int64_t p, int32_t lab, double w) {
+            const double mymax = f.bwd(lo, hi, nlo, nhi, gn, vn, gc, vc, nprev, t == T - 1, bd.end(sstar), [&](int64_t p, int32_t lab, double w) {
                 auto arg = [&] { return ((ca + al[Form::slot(p, lo)]) + (D + w)) - Z; };
                 if constexpr (fb_next_column<Out>::value)
                     cell(p, lab, w, arg);
@@ -242,6 +306,7 @@ __device__ __forceinline__ void fb_ck(Form &f, PostResult *res, double *cav, Out
             f.fence();
         }
     }
+    if constexpr (!Bound::kVirtual) bd.before(f, gn, vn, nlo, nhi, nprev, D);
     if (tid == 0) {
         res[d.idx].status = kStatusOk;
         res[d.idx].log_likelihood = Zr;

@@ -7,6 +7,7 @@
 //   fence()            post_wave_sync: the frame hand-off, before a frame's cells     nothing: the barrier inside max() orders
 //                      and after its bookkeeping                                      the frames
 //   max(x)             post_wave_max                                                  post_block_max on red[ph], ph its state
+//   sum(x)             post_wave_sum: a butterfly, every lane the same bits           post_block_sum on red[ph]: the four wavefronts' sums in order
 //   col(k)             LDS column k, position p at cslot(p) = p & 1023                d.col + k L, position p at cslot(p) = p
 //   slot(p, lo), cw()  checkpoint and slab: p & 1023 of 1024                          p - lo of d.cw, lo the frame's low end
 //   ck_store, ck_load  all 1024 slots                                                 [plo, phi) of the column's band
@@ -118,6 +119,7 @@ struct FbFast {
     __device__ __forceinline__ void sync() const { post_wave_sync(); }
     __device__ __forceinline__ void fence() const { post_wave_sync(); }
     __device__ __forceinline__ double max(double x) { return post_wave_max(x); }
+    __device__ __forceinline__ double sum(double x) { return post_wave_sum(x); }
 
     __device__ __forceinline__ double *col(int k) const { return cols[k]; }
     __device__ __forceinline__ static int64_t cslot(int64_t p) { return p & 1023; }
@@ -156,11 +158,11 @@ struct FbFast {
     {
         return fb_fast_fwd<M>(lo, hi, plo, phi, prev, cur, lds_row, mprev, lab, cell);
     }
-    template <class Cell>
+    template <class End, class Cell>
     __device__ __forceinline__ double bwd(int64_t lo, int64_t hi, int64_t nlo, int64_t nhi, const double *gn, const double *vn, double *gc,
-                                          double *vc, double nprev, bool last, int64_t sstar, Cell cell) const
+                                          double *vc, double nprev, bool last, End end, Cell cell) const
     {
-        return fb_fast_bwd<M>(lo, hi, nlo, nhi, gn, vn, gc, vc, lds_row, nprev, last, sstar, lab, cell);
+        return fb_fast_bwd<M>(lo, hi, nlo, nhi, gn, vn, gc, vc, lds_row, nprev, last, end, lab, cell);
     }
 };
 
@@ -186,6 +188,12 @@ struct FbGen {
     __device__ __forceinline__ double max(double x)
     {
         const double m = post_block_max(x, red[ph]);
+        ph ^= 1;
+        return m;
+    }
+    __device__ __forceinline__ double sum(double x)
+    {
+        const double m = post_block_sum(x, red[ph]);
         ph ^= 1;
         return m;
     }
@@ -219,11 +227,11 @@ struct FbGen {
     {
         return fb_gen_fwd(d, lrow, lo, hi, plo, phi, prev, cur, mprev, cell);
     }
-    template <class Cell>
+    template <class End, class Cell>
     __device__ __forceinline__ double bwd(int64_t lo, int64_t hi, int64_t nlo, int64_t nhi, const double *gn, const double *vn, double *gc,
-                                          double *vc, double nprev, bool last, int64_t sstar, Cell cell) const
+                                          double *vc, double nprev, bool last, End end, Cell cell) const
     {
-        return fb_gen_bwd(d, lrow, lo, hi, nlo, nhi, gn, vn, gc, vc, nprev, last, sstar, cell);
+        return fb_gen_bwd(d, lrow, lo, hi, nlo, nhi, gn, vn, gc, vc, nprev, last, end, cell);
     }
 };
 

@@ -114,6 +114,10 @@ void launch_boundary_quantiles(const BandDesc<QuantLattice, Band> *lats, int n_f
 template <class Band>
 void launch_mea_path(const BandDesc<MeaLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 
+// ka_fb_resume.hip: label occupancy and path posteriors under the caller's boundary conditions (ka_fb_resume.hpp); BandTable only
+template <class Band>
+void launch_posteriors_resume(const BandDesc<ResumeFbLattice, Band> *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+
 // ka_sample.hip, ka_sample_banded.hip: alignments sampled from the band posterior (ka_sample.hpp): ka_fb_ck.hpp's forward pass
 // and block recompute with kernels of its own, launch_fb_ck's form split, grid and slots
 template <class Band>

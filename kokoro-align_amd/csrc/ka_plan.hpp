@@ -1057,6 +1057,36 @@ inline size_t band_table_workspace(int32_t n, const int64_t *T, bool host_buffer
 namespace ka {
 namespace plan {
 
+// ---- ka_ctc_posteriors_resume_batch_f32 (ka_fb_resume.hpp): workspace layout ----
+// label_posterior_workspace's layout and slots; for host buffers, beside the staged log-probs, labels and occupancy, the staged
+// path and path posteriors (T int32, T float) and the four rows (2S+1 doubles each: alpha_in, beta_in, alpha_out, beta_out).
+// Their room is carved whether or not the lattice brings them, so that the byte count depends on the shapes alone.  The call
+// runs over a table only: its Banded<ResumeFbLattice> descriptors (kBandedResumeFbDescBytes each) and staged tables lie behind
+// this layout, as band_table_workspace places them.
+struct ResumeFbCarve : OccCarve {
+    size_t path, ppost, rows[4];   // host buffers only
+};
+inline size_t posteriors_resume_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move,
+                                          bool host_buffers, ResumeFbCarve *cv, size_t *off_res)
+{
+    return slot_workspace(n, sizeof(OccLattice), T, S, V, beam, max_move, cv, off_res, [&](int32_t, const Shape &sh, ResumeFbCarve &c, size_t &off) {
+        if (host_buffers) {
+            carve_staged(off, sh, V, c);
+            c.occ = off;
+            off += align_up((size_t)sh.T * (size_t)V * 4);
+            c.path = off;
+            off += align_up((size_t)sh.T * 4);
+            c.ppost = off;
+            off += align_up((size_t)sh.T * 4);
+            for (size_t &r : c.rows) {
+                r = off;
+                off += align_up((size_t)sh.L * sizeof(double));
+            }
+        }
+        return true;
+    });
+}
+
 // ---- ka_ctc_path_margins_batch_f32 (ka_margin.hpp): workspace layout ----
 // label_posterior_workspace's layout and slots (a slot's block offsets and V-wide global bins go unused) with MarginLattice
 // descriptors; for host buffers, beside the staged log-probs and labels, the staged path and table (T int32 each; the table's

@@ -207,6 +207,22 @@ __device__ __forceinline__ double post_block_max(double x, double *red)   // red
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
+// sums in a fixed order (a butterfly; then the four wavefronts' sums from the first to the last), so that every thread holds the
+// same bits and a lattice's do not depend on what ran before it
+__device__ __forceinline__ double post_wave_sum(double x)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+__device__ __forceinline__ double post_block_sum(double x, double *red)   // red: 4 values of this frame's parity
+{
+    x = post_wave_sum(x);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 // ---------------------------------------------------------------------------------------
 // the frame recurrences, with lab'[s] the label of position s:
 //   forward:  u_t(s) = lse2_j u_{t-1}(s-j) - m_{t-1} + e_t(s)          j in [0, max_move), s-j in band t-1, not vetoed
@@ -244,11 +260,21 @@ __device__ __forceinline__ double fb_fast_fwd(int64_t lo, int64_t hi, int64_t pl
     }
     return mymax;
 }
+// w_{T-1}(p) of a backward pass, by the End the pass is given: a terminal s* (an int64_t), beta_{T-1} = {s*: 0}; or an FbEndRow,
+// the caller's row (nats, absolute) in log2 units relative to its maximum d0, or its terminal where the row is NULL
+struct FbEndRow {
+    const double *row;
+    double d0;
+    int64_t sstar;
+};
+__device__ __forceinline__ double fb_end_w(int64_t sstar, int64_t p) { return (p == sstar) ? 0.0 : post_dninf(); }
+__device__ __forceinline__ double fb_end_w(const FbEndRow &e, int64_t p) { return e.row ? e.row[p] * kLog2e64 - e.d0 : fb_end_w(e.sstar, p); }
+
 // G_t over [lo, hi) from G_{t+1} (gn, its vetoable copy vn) over [nlo, nhi) into gc / vc.  last: t = T-1 of a pass that
-// starts there, beta_{T-1} = {sstar: 0}.  cell(p, lab, w): the caller's use of w_t(p).  Returns the lane's maximum of G_t.
-template <int M, class LabAt, class Cell>
+// starts there, beta_{T-1} = fb_end_w(end, .).  cell(p, lab, w): the caller's use of w_t(p).  Returns the lane's maximum of G_t.
+template <int M, class End, class LabAt, class Cell>
 __device__ __forceinline__ double fb_fast_bwd(int64_t lo, int64_t hi, int64_t nlo, int64_t nhi, const double *gn, const double *vn,
-                                              double *gc, double *vc, const double *row, double nprev, bool last, int64_t sstar,
+                                              double *gc, double *vc, const double *row, double nprev, bool last, End end,
                                               LabAt lab_at, Cell cell)
 {
     const double NINF = post_dninf();
@@ -257,7 +283,7 @@ __device__ __forceinline__ double fb_fast_bwd(int64_t lo, int64_t hi, int64_t nl
         const int32_t lab = lab_at(p);
         double w;
         if (last) {
-            w = (p == sstar) ? 0.0 : NINF;
+            w = fb_end_w(end, p);
         } else {
             double x[M];
             double mx = NINF;
@@ -310,10 +336,10 @@ __device__ __forceinline__ double fb_gen_fwd(const FbLattice &d, const float *lr
     }
     return mymax;
 }
-template <class Cell>
+template <class End, class Cell>
 __device__ __forceinline__ double fb_gen_bwd(const FbLattice &d, const float *lrow, int64_t lo, int64_t hi, int64_t nlo, int64_t nhi,
                                              const double *gn, const double *vn, double *gc, double *vc, double nprev, bool last,
-                                             int64_t sstar, Cell cell)
+                                             End end, Cell cell)
 {
     const int M = d.max_move;
     const double NINF = post_dninf();
@@ -323,7 +349,7 @@ __device__ __forceinline__ double fb_gen_bwd(const FbLattice &d, const float *lr
         const double e = (double)lrow[lab] * kLog2e64;
         double w;
         if (last) {
-            w = (p == sstar) ? 0.0 : NINF;
+            w = fb_end_w(end, p);
         } else {
             auto g = [&](int j) { return fb_skip(j) ? vn[p + j] : gn[p + j]; };
             double mx = NINF;

@@ -274,6 +274,20 @@ static_assert(sizeof(Banded<PostLattice>) == 96 && sizeof(Banded<OccLattice>) ==
                   sizeof(Banded<MeaLattice>) == kBandedDescBytes && sizeof(Banded<QuantLattice>) == kBandedQuantDescBytes,
               "descriptor sizes");
 
+// ---- forward-backward posteriors under the caller's boundary conditions (ka_fb_resume.hpp): the
+// occupancy's descriptor, slots and form split; run over a caller's table only (Banded<ResumeFbLattice>).  The rows are [L]
+// doubles in nats, absolute, -inf = no mass ----
+struct ResumeFbLattice : OccLattice {   // occ may be NULL
+    const double *alpha_in;       // ln alpha of the row before frame 0; NULL: the virtual state {0: 0}
+    const double *beta_in;        // ln beta of frame T-1; NULL: {terminal: 0}
+    double *alpha_out;            // output, or NULL: ln alpha of frame T-1
+    double *beta_out;             // output, or NULL: ln beta of the row before frame 0
+    const int32_t *path;          // [T] the path path_post is asked for, or NULL
+    float *path_post;             // [T] output, or NULL: gamma at (t, path[t])
+};
+constexpr size_t kBandedResumeFbDescBytes = 176;   // what ka_posteriors_resume_workspace_bytes reserves per lattice
+static_assert(sizeof(ResumeFbLattice) == 168 && sizeof(Banded<ResumeFbLattice>) == kBandedResumeFbDescBytes, "descriptor sizes");
+
 // ---- best path over a caller-given band (ka_banded.hpp) ----
 struct BandLattice {
     const float *lp;          // [T, ld] log-probs (device)

@@ -1107,3 +1107,153 @@ def segment_min_margin(margin, seg_ends):
         if b > a:
             out[i] = np.nan if np.isnan(m[a:b]).any() else m[a:b].min()
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# forward-backward under the caller's boundary conditions: posteriors of a recording cut into chunks
+# ------------------------------------------------------------------------------------------
+_RESUME_ROWS = {True: (True, True), False: (False, False), "alpha": (True, False), "beta": (False, True)}
+
+
+def free_end_scores(L):
+    """The end row under which a path may end anywhere: ``L`` = 2S+1 zeros (float64).  Z is then the mass of the audio so far."""
+    return np.zeros(int(L), np.float64)
+
+
+def ctc_posteriors_resume(log_probs, labels, band_lo, alpha_in=None, end=None, path=None, occupancy=True, rows=True, beam_size=1000,
+                          max_move=4):
+    """Forward-backward over one chunk of a recording: (occ, path_post, alpha_out, beta_out, log_likelihood).
+
+    The chunk's frames ``log_probs`` [T, V] run over the table ``band_lo`` [T] (required) from the row ``alpha_in`` (float64
+    [2S+1], ln alpha of the row before the chunk's first frame, -inf = no mass; None: the virtual start state) to ``end``: an int,
+    the terminal state, or a float64 row [2S+1], ln beta of the chunk's last frame (``free_end_scores``: the path may end
+    anywhere).  ``alpha_out`` (ln alpha of the last frame over its band, -inf elsewhere) is the next chunk's ``alpha_in``;
+    ``beta_out`` (ln beta of the row before the first frame) is the previous chunk's ``end``.  With both exchanged, occ and
+    path_post of the chunks, concatenated, are the uncut recording's and every chunk's log_likelihood is the recording's.
+    occ float32 [T, V] as ``ctc_label_posteriors`` (``occupancy=False``: None, and not computed); path_post float32 [T], the
+    posterior of ``path[t]`` at frame t (None without ``path``); ``rows``: True, False, "alpha" or "beta" - which rows are
+    returned (alpha_out and log_likelihood alone cost one forward pass).  NumPy in -> NumPy out; ROCm torch tensors go to
+    ``ctc_posteriors_resume_device``.  Raises as ``ctc_label_posteriors``; a NaN or +inf in a row raises ValueError.
+    """
+    call = ctc_posteriors_resume_device if _is_tensor(log_probs) else ctc_posteriors_resume_batch
+    (result,) = call([log_probs], [labels], [band_lo], None if alpha_in is None else [alpha_in], [end], None if path is None else [path],
+                     occupancy, rows, beam_size, max_move)
+    return result
+
+
+def _row_f64(lat, x, L, what):
+    """A row of a resumed call as the call wants it: float64 [L] where the lattices are."""
+    if lat.form == "batch":
+        if _is_tensor(x):
+            x = x.detach().cpu().numpy()
+        x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(-1))
+    else:
+        import torch
+        x = x if _is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float64).reshape(-1))
+        x = x.reshape(-1).to(device=lat.dev, dtype=torch.float64).contiguous()
+    if x.shape[0] != L:
+        raise ValueError(f"{what} must have 2S+1 = {L} entries")
+    return x
+
+
+def _is_end_row(end):
+    return _is_tensor(end) and end.dim() > 0 or not _is_tensor(end) and np.ndim(end) > 0
+
+
+def _posteriors_resume(lat, band_lo, alpha_in, end, path, occupancy, rows, beam_size, max_move, return_status):
+    if rows not in _RESUME_ROWS:
+        raise ValueError('rows must be True, False, "alpha" or "beta"')
+    want_a, want_b = _RESUME_ROWS[rows]
+    n, Ls = lat.n, [2 * S + 1 for S in lat.S]
+    for name, x in (("alpha_in", alpha_in), ("path", path)):
+        if x is not None and len(x) != n:
+            raise ValueError(f"{name} must hold one entry (or None) per lattice")
+    if end is None or len(end) != n or any(e is None for e in end):
+        raise ValueError("end must hold a terminal or an end row per lattice")
+    tables = _band_tables(lat, band_lo)
+    a_in = [None if alpha_in is None or alpha_in[i] is None else _row_f64(lat, alpha_in[i], Ls[i], "alpha_in") for i in range(n)]
+    b_in = [_row_f64(lat, end[i], Ls[i], "an end row") if _is_end_row(end[i]) else None for i in range(n)]
+    terms = [-1 if b_in[i] is not None else _terminal_of(end[i]) for i in range(n)]
+    paths = [None if path is None or path[i] is None else lat.int32(path[i]) for i in range(n)]
+    if any(p is not None and p.shape[0] != T for p, T in zip(paths, lat.T)):
+        raise ValueError("a path must have one position per frame")
+    occs = [lat.empty((T, lat.V), np.float32) if occupancy else None for T in lat.T]
+    posts = [None if p is None else lat.empty(T, np.float32) for p, T in zip(paths, lat.T)]
+    a_out = [lat.empty(L, np.float64) if want_a else None for L in Ls]
+    b_out = [lat.empty(L, np.float64) if want_b else None for L in Ls]
+
+    def ptrs(xs):
+        return _ptr_array([None if x is None else lat.ptr(x) for x in xs])
+    p_band, _k0 = ptrs(tables)
+    p_ain, _k1 = ptrs(a_in)
+    p_bin, _k2 = ptrs(b_in)
+    p_term, _k3 = _i64_array(terms)
+    p_path, _k4 = ptrs(paths)
+    p_occ, _k5 = ptrs(occs)
+    p_ldo, _k6 = _i64_array([lat.V if o is None else lat.ld(o) for o in occs])
+    p_post, _k7 = ptrs(posts)
+    p_aout, _k8 = ptrs(a_out)
+    p_bout, _k9 = ptrs(b_out)
+    return _run_lattices(lat, "posteriors_resume", beam_size, max_move,
+                         (p_band, p_ain, p_bin, p_term, p_path, p_occ, p_ldo, p_post, p_aout, p_bout),
+                         list(zip(occs, posts, a_out, b_out)), return_status)
+
+
+def ctc_posteriors_resume_batch(log_probs_list, labels_list, band_lo, alpha_in=None, end=None, path=None, occupancy=True, rows=True,
+                                beam_size=1000, max_move=4, device=None, return_status=False):
+    """``ctc_posteriors_resume`` of many chunks in ONE launch; host NumPy buffers in and out.  ``band_lo`` and ``end`` hold one
+    entry per lattice; ``alpha_in`` and ``path`` are None or lists in which any entry may be None.  Returns a list of (occ,
+    path_post, alpha_out, beta_out, log_likelihood); with ``return_status`` also the per-lattice status list, in which case
+    failures do not raise (every output of a failed lattice is NaN, rows included)."""
+    lat = _host_lattices(log_probs_list, labels_list, band_lo, "tables", device)
+    if lat is None:
+        return ([], []) if return_status else []
+    return _posteriors_resume(lat, band_lo, alpha_in, end, path, occupancy, rows, beam_size, max_move, return_status)
+
+
+def ctc_posteriors_resume_device(log_probs, labels, band_lo, alpha_in=None, end=None, path=None, occupancy=True, rows=True,
+                                 beam_size=1000, max_move=4, return_status=False):
+    """``ctc_posteriors_resume_batch`` on lists of ROCm torch tensors: results and rows stay on the device (float64 rows), so
+    that a chunk's rows reach its neighbour without a copy.  One launch on torch's current stream."""
+    lat = _device_lattices(log_probs, labels, band_lo, "tables")
+    return _posteriors_resume(lat, band_lo, alpha_in, end, path, occupancy, rows, beam_size, max_move, return_status)
+
+
+def ctc_label_posteriors_chunked(log_probs, labels, band_lo, chunk_frames, terminal, path=None, beam_size=1000, max_move=4):
+    """``ctc_label_posteriors(..., band_lo=)`` of a recording in the checkpoint workspace of one chunk: (occ float32 [T, V],
+    path_post float32 [T] or None, log_likelihood).
+
+    A forward-only sweep over chunks of ``chunk_frames`` frames keeps every chunk's start row (2S+1 doubles per chunk); the
+    chunks are then visited newest first, each from its start row to the end row its successor handed back (the last one to
+    ``terminal``).  By pass count that is one forward pass more than the uncut call.  NumPy in, NumPy out.
+    """
+    lp = np.asarray(log_probs)
+    T = lp.shape[0]
+    chunk = int(chunk_frames)
+    if chunk < 1:
+        raise ValueError("chunk_frames must be at least 1")
+    band = np.asarray(band_lo).reshape(-1)
+    if band.shape[0] != T:
+        raise ValueError("a band table must have one entry per frame")
+    pth = None if path is None else np.asarray(path).reshape(-1)
+    if pth is not None and pth.shape[0] != T:
+        raise ValueError("a path must have one position per frame")
+    cuts = list(range(0, T, chunk)) + [T]
+    starts, row = [], None
+    for a, b in zip(cuts[:-2], cuts[1:-1]):      # forward only: the start row of every chunk but the first
+        starts.append(row)
+        _o, _p, row, _b, _z = ctc_posteriors_resume(lp[a:b], labels, band[a:b], row, free_end_scores(2 * len(np.asarray(labels).reshape(-1)) + 1),
+                                                    None, False, "alpha", beam_size, max_move)
+    starts.append(row)
+    occ = np.empty((T, lp.shape[1]), np.float32)
+    post = None if pth is None else np.empty(T, np.float32)
+    end, z = _terminal_of(terminal), None
+    for k in range(len(starts) - 1, -1, -1):     # newest first, with both rows
+        a, b = cuts[k], cuts[k + 1]
+        o, p, _a, end, zk = ctc_posteriors_resume(lp[a:b], labels, band[a:b], starts[k], end, None if pth is None else pth[a:b], True,
+                                                  "beta" if k > 0 else False, beam_size, max_move)
+        occ[a:b] = o
+        if post is not None:
+            post[a:b] = p
+        z = zk if z is None else z
+    return occ, post, z
