@@ -217,6 +217,13 @@ __device__ __forceinline__ void band_advance(TileCore<CELLS> &c)
     if (c.r0 >= c.T) { c.r0 -= c.T; ++c.q0; }
 }
 
+// bytes of the contiguous block of rows that starts at row `first` (< T): 32 rows, fewer at the end of the array
+template <int PITCH>
+__device__ __forceinline__ uint32_t block_bytes(uint32_t T, uint32_t first)
+{
+    return (T - first < (uint32_t)kTpBlock ? T - first : (uint32_t)kTpBlock) * (uint32_t)PITCH;
+}
+
 // The log-prob rows of block k (k >= 0) into LDS at `dst`.  PITCH = bytes between two rows of a staged block in LDS.
 // CONTIG = false (PITCH 256): rows are staged one by one (lane = column; any row stride of the caller's array; rows behind
 // T - 1 repeat it).  CONTIG = true (PITCH = 4 V; the array's rows are contiguous, V columns): the block is copied as it lies in
@@ -243,9 +250,13 @@ __device__ __forceinline__ void stage_rows(const TileCore<CELLS> &c, int32_t k, 
             }
         }
     } else {
-        const uint32_t first = tb < last_row ? tb : last_row;
-        const uint32_t rows_there = c.T - first < (uint32_t)kTpBlock ? c.T - first : (uint32_t)kTpBlock;
-        const uint32_t last_chunk = (rows_there * PITCH - 16u) & ~15u;
+        // The pieces of a block are clamped to the one that holds the block's LAST BYTE.  A block starts on a 16-byte border
+        // (the array's base is aligned, 32 rows are a multiple of 16 bytes), so that piece starts on a byte of the lattice and
+        // stays inside its page; with V = 39 and T % 4 != 0 it ends up to 12 bytes behind row T - 1, which sum_rows keeps out of
+        // the finiteness sum and no frame reads.  (A block behind the last one - the 256-position tile requests one, and
+        // nobody reads it - repeats block 0: row T - 1 alone need not start on a 16-byte border.)
+        const uint32_t first = tb < c.T ? tb : 0u;
+        const uint32_t last_chunk = (block_bytes<PITCH>(c.T, first) - 1u) & ~15u;
         const char *bp = c.lp + (size_t)first * PITCH;
 #pragma unroll
         for (int j = 0; j < TileRows<PITCH, CONTIG>::kRowDmas; ++j) {
@@ -268,9 +279,12 @@ __device__ __forceinline__ void stage_packets(const TileCore<CELLS> &c, int32_t 
     }
 }
 
-// |log-prob| of a landed block of rows (at `rows`) into c.absum: all reads first, then the adds
+// |log-prob| of the landed block k of rows (at `rows`) into c.absum: all reads first, then the adds.  Every 16 bytes of the
+// slot hold a piece of the block (stage_rows: the ones behind the block's end repeat its last piece) - only a last block of
+// V = 39 rows that does not end on a 16-byte border has a last piece with 1 to 3 floats of row T - 1 and then whatever lies
+// behind the array: those do not count, in that piece and in its repeats.
 template <int PITCH, bool CONTIG, int CELLS>
-__device__ __forceinline__ void sum_rows(TileCore<CELLS> &c, uint32_t rows, int lane)
+__device__ __forceinline__ void sum_rows(TileCore<CELLS> &c, int32_t k, uint32_t rows, int lane)
 {
     const uint32_t r = rows + (uint32_t)lane * 16u;
     constexpr int kReads = TileRows<PITCH, CONTIG>::kSlot / 1024;
@@ -278,6 +292,18 @@ __device__ __forceinline__ void sum_rows(TileCore<CELLS> &c, uint32_t rows, int 
 #pragma unroll
     for (int j = 0; j < kReads; ++j) v[j] = lds_f32x4(r + j * 1024);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if constexpr (CONTIG && PITCH % 16 != 0) {
+        const uint32_t bytes = block_bytes<PITCH>(c.T, (uint32_t)k * kTpBlock);
+        if (bytes & 15u) {      // (wave-uniform; at most once in a tile's life)
+            const uint32_t last_chunk = bytes & ~15u, floats = (bytes & 15u) >> 2;
+#pragma unroll
+            for (int j = 0; j < kReads; ++j) {
+                const bool last = (uint32_t)j * 1024u + (uint32_t)lane * 16u >= last_chunk;
+#pragma unroll
+                for (int i = 1; i < 4; ++i) v[j][i] = (last && (uint32_t)i >= floats) ? 0.0f : v[j][i];
+            }
+        }
+    }
 #pragma unroll
     for (int j = 0; j < kReads; ++j) c.absum += (__builtin_fabsf(v[j][0]) + __builtin_fabsf(v[j][1])) + (__builtin_fabsf(v[j][2]) + __builtin_fabsf(v[j][3]));
 }

@@ -288,7 +288,7 @@ __device__ __forceinline__ void ts_run_tile(const Lattice &d, const TileTask &tk
             if (k + 1 >= kb0 && k + 1 <= kb1) {
                 const uint32_t tbn = (uint32_t)(k + 1) * kTpBlock;
                 const uint32_t rows = lds_rows + (uint32_t)((k + 1) & 1) * kRowSlot;
-                sum_rows<PITCH, CONTIG>(c, rows, lane);   // block k+1 landed before the last barrier: its finiteness sum
+                sum_rows<PITCH, CONTIG>(c, k + 1, rows, lane);   // block k+1 landed before the last barrier: its finiteness sum
                 band_block(c, tbn, lane);
                 // the emissions of block k+1, per frame and lane {blank, label} ...
                 const uint32_t pb = lds_pairs + (uint32_t)((k + 1) & 1) * kTgPairBytes;

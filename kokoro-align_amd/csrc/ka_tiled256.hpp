@@ -305,7 +305,7 @@ __device__ __forceinline__ void tp2_run_tile(const Lattice &d, const TileTask &t
     bool stale = false;
     auto landed_block = [&](int32_t k) {
         const uint32_t slot = ring(k);
-        sum_rows<PITCH, CONTIG>(c, c.lds_rows + slot * kSlot, lane);
+        sum_rows<PITCH, CONTIG>(c, k, c.lds_rows + slot * kSlot, lane);
         if (verify & 1) {
             const int32_t sidx = k * kTpBlock + (lane & (kTpBlock - 1));
             const f32x4 h = lds_f32x4(c.lds_halo + slot * (kTpBlock * 16) + (uint32_t)(lane & (kTpBlock - 1)) * 16u);
