@@ -686,6 +686,73 @@ size_t ka_path_margin_workspace_bytes(int32_t n, const int64_t *T, const int64_t
                                       int32_t mem);
 
 /*
+ * Best-path margins under the caller's boundary conditions, and rows of max-marginals at chosen frames:
+ * ka_ctc_path_margins over ONE CHUNK of a recording.  Lattice, band, moves and veto are ka_ctc_path_margins' (lab' the
+ * blank-expanded labels, L = 2S+1, M = max_move, band [lo_t, hi_t) from band_lo or, for a NULL table, the diagonal); what
+ * stands before frame 0 and at frame T-1 is the caller's, and the two rows a neighbouring chunk needs are handed back.  Every
+ * value is a float64, every + one IEEE add, every max exact: all outputs are defined bit for bit.
+ *   d_in      [L] float64 or NULL: D of the row before frame 0, -inf = no path.  NULL: the virtual state {0: 0.0}.  No band
+ *             applies to it: D_0(p) = max_j d_in[p-j] + lp[0, lab'[p]] for p in band 0, p-j >= 0, veto on lab'[p]; only
+ *             [lo_0 - (M-1), hi_0) can matter
+ *   e_in      [L] float64 or NULL: E_{T-1}(p) = e_in[p] over band T-1 (zeros: the path may end anywhere); `terminal` is then
+ *             ignored.  NULL: E_{T-1} = {terminal: 0.0}, terminal = -1 meaning path[T-1] (path is then required)
+ *   score     max over band T-1 of D_{T-1}(p) + E_{T-1}(p); with a NULL e_in that is D_{T-1}(terminal), the sibling's value.
+ *             -inf: KA_ERR_ZERO_MASS
+ *   d_out     [L] float64 or NULL: D_{T-1}(p) over band T-1, -inf elsewhere: the next chunk's d_in
+ *   e_out     [L] float64 or NULL: the E of the row before frame 0, e_out[p] = max_j (E_0(p+j) + lp[0, lab'[p+j]]), p+j in band 0,
+ *             veto on lab'[p+j], for p in [max(lo_0 - (M-1), 0), hi_0), -inf elsewhere: the previous chunk's e_in
+ *   through, alt, runner_up   the sibling's definitions with m_t(p) = D_t(p) + E_t(p); each may be NULL (NULL arrays, or NULL
+ *             entries); path is required if any is asked for
+ *   frames    [K] HOST int64 in both memory modes, strictly increasing in [0, T); K = 0 is legal (K NULL in the batch form: all 0)
+ *   rows      [K, ld_rows] float64: rows[k][j] = m_{f_k}(lo_k + j) for j < hi_k - lo_k, -inf for j in [hi_k - lo_k, W),
+ *             W = min(beam_size, L); absolute values: subtract score for "how far behind the best path".  ld_rows >= W
+ *   rows_lo   [K] int64: lo_k
+ * The batch form takes HOST arrays of n pointers; any of band_lo, d_in, e_in, path, through, alt, runner_up, frames, rows,
+ * rows_lo, d_out, e_out may be NULL or hold NULL entries, and terminal, K, ld_rows may be NULL where nothing needs them.
+ * What runs: the forward pass always; checkpoints and the recompute of D for every 32-frame block if through, alt or
+ * runner_up is asked for, else only for blocks that hold a query frame; the backward pass only if one of through, alt,
+ * runner_up, rows or e_out is asked for.  d_out and score alone are one forward pass.
+ * Properties (each holds bit for bit, and is tested so):
+ *   1. With d_in, e_in, frames, d_out and e_out absent and terminal = -1 every output, status and return code is
+ *      ka_ctc_path_margins[_batch]_f32's, over a table and over the diagonal.
+ *   2. Cut a lattice at any k in [1, T): A = frames [0, k) with band_lo[:k], B = frames [k, T) with band_lo[k:], d_in = A's
+ *      d_out and the uncut terminal; then A with e_in = B's e_out.  The concatenated through, alt and runner_up are the uncut
+ *      call's, B's score has the uncut score's bits, and state rows at any frame equal the uncut call's rows.
+ *   3. rows[k] reproduces frame f_k's through (at path[f_k] - lo_k), alt (its maximum outside the path's group) and runner_up
+ *      (the lowest position attaining it).
+ *   4. A lattice gives the same bits alone or in a batch, whatever its neighbours bring.
+ *   5. d_out is the same whether or not anything else is asked for.
+ * Failures: a NaN or +inf anywhere in d_in or e_in, a terminal or path value outside [0, L), or a table that is no band is
+ * KA_ERR_BAD_ARGS for that lattice alone (status), as are the sibling's statuses for labels and log-probs.  A failed lattice has
+ * NaN over every requested float output, rows and d_out / e_out included, -1 over runner_up and rows_lo, and a NaN score (-inf
+ * for KA_ERR_ZERO_MASS): a chunk resumed from a failed chunk fails too.  Refused on the host before any launch, with every
+ * output untouched (KA_ERR_BAD_ARGS): a unit other than 0 or 1, frames out of order or range, K outside [0, T], ld_rows < W,
+ * an output asked for without what it needs (path; rows with rows_lo), no end at all, and an output row (d_out, e_out) that
+ * overlaps an input row (d_in, e_in).
+ * Cost (MI355X, cfg2: T = 50 000, S = 5000, beam 1000, V = 64, minimum of nine; ms for one lattice / for
+ * 1024 in one call): ka_ctc_path_margins_batch_f32 562.9 / 616.1, its machine code and its time unchanged from the commit before
+ * this call (562.9 / 616.2 there, run alternately); this call with NULL rows 581.9 / 635.3 (1.034 x / 1.031 x), with both rows
+ * in and out 582.0 / 635.0; d_out and score alone 147.5 / 150.7 (0.26 x / 0.24 x: one forward pass); state rows at 100 frames
+ * without through / alt 317.3 / 335.2 (0.56 x / 0.54 x); the Python ctc_path_margins_chunked in 8 chunks 1.26 x the uncut call.
+ * ka_margins_resume_workspace_bytes: the engine workspace a call of these shapes and K needs (K may be NULL; 0 for unsupported
+ * shapes): the sibling's slots, these descriptors, the frame lists and, for KA_MEM_HOST, the staged rows.
+ */
+int ka_ctc_margins_resume_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                              int32_t beam_size, int32_t max_move, const int32_t *band_lo, const double *d_in, const double *e_in,
+                              int64_t terminal, const int32_t *path, int32_t unit, double *through, double *alt, int32_t *runner_up,
+                              const int64_t *frames, int64_t K, double *rows, int64_t ld_rows, int64_t *rows_lo, double *d_out, double *e_out,
+                              double *score, int32_t mem, void *stream);
+int ka_ctc_margins_resume_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                    const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                    const int32_t *const *band_lo, const double *const *d_in, const double *const *e_in, const int64_t *terminal,
+                                    const int32_t *const *path, int32_t unit, double *const *through, double *const *alt,
+                                    int32_t *const *runner_up, const int64_t *const *frames, const int64_t *K, double *const *rows,
+                                    const int64_t *ld_rows, int64_t *const *rows_lo, double *const *d_out, double *const *e_out, double *score,
+                                    int32_t *status, int32_t mem, void *stream);
+size_t ka_margins_resume_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t V, int32_t beam_size,
+                                         int32_t max_move, int32_t mem);
+
+/*
  * Forward-backward posteriors over a caller-given band: ka_ctc_path_posteriors, ka_ctc_label_posteriors,
  * ka_ctc_state_posteriors and ka_ctc_state_durations on the band of ka_ctc_best_path_banded instead of the reference's
  * diagonal, so that a path found under a table can be judged under the same table.  Each call is its sibling with one

@@ -28,7 +28,9 @@ segment_expected_match), and the exact quantiles of every boundary's frame, the 
 margin of a path over the best alignment that disagrees with it, from max-marginals in exact float64 max-plus arithmetic
 (ctc_path_margins[_batch|_device], segment_boundary_margin, segment_min_margin); and the forward-backward itself resumable, a
 chunk at a time from a caller-given start row to a caller-given end row (ctc_posteriors_resume[_batch|_device], free_end_scores,
-ctc_label_posteriors_chunked, StreamingAligner(confidence=True)).
+ctc_label_posteriors_chunked, StreamingAligner(confidence=True)), and so are the margins, whose chunks return the uncut call's
+bits (ctc_margins_resume[_batch|_device], ctc_path_margins_chunked, StreamingAligner(confidence="margin")), with rows of
+max-marginals at chosen frames (ctc_state_margins).
 
 The DP and backtrace run in the HIP C-ABI library (include/kokoro_align_amd.h); there is no
 CPU fallback — importing works without a GPU, computing does not.
@@ -84,6 +86,11 @@ from .posteriors import (  # noqa: F401
     ctc_path_margins,
     ctc_path_margins_batch,
     ctc_path_margins_device,
+    ctc_path_margins_chunked,
+    ctc_margins_resume,
+    ctc_margins_resume_batch,
+    ctc_margins_resume_device,
+    ctc_state_margins,
     ctc_label_posteriors_chunked,
     ctc_path_posteriors,
     ctc_path_posteriors_batch,

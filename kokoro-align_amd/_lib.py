@@ -61,6 +61,7 @@ EXPORTS = [
     "ka_ctc_best_path_determined_f32", "ka_ctc_best_path_determined_batch_f32",
     "ka_ctc_best_path_tracking_determined_f32", "ka_ctc_best_path_tracking_determined_batch_f32", "ka_determined_workspace_bytes",
     "ka_ctc_posteriors_resume_f32", "ka_ctc_posteriors_resume_batch_f32", "ka_posteriors_resume_workspace_bytes",
+    "ka_ctc_margins_resume_f32", "ka_ctc_margins_resume_batch_f32", "ka_margins_resume_workspace_bytes",
 ]
 
 
@@ -213,6 +214,14 @@ def load_library():
     L.ka_ctc_path_margins_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pp, pp, i32, pp, pp, pp, vp, vp, i32, vp]
     L.ka_path_margin_workspace_bytes.restype = sz
     L.ka_path_margin_workspace_bytes.argtypes = [i32, pi64, pi64, i32, i32, i32, i32]
+    L.ka_ctc_margins_resume_f32.restype = ctypes.c_int
+    L.ka_ctc_margins_resume_f32.argtypes = [vp, vp, i64, i32, i64, vp, i64, i32, i32, vp, vp, vp, i64, vp, i32, vp, vp, vp,
+                                            vp, i64, vp, i64, vp, vp, vp, vp, i32, vp]
+    L.ka_ctc_margins_resume_batch_f32.restype = ctypes.c_int
+    L.ka_ctc_margins_resume_batch_f32.argtypes = [vp, i32, pp, pi64, i32, pi64, pp, pi64, i32, i32, pp, pp, pp, pi64, pp, i32, pp, pp, pp,
+                                                  pp, pi64, pp, pi64, pp, pp, pp, vp, vp, i32, vp]
+    L.ka_margins_resume_workspace_bytes.restype = sz
+    L.ka_margins_resume_workspace_bytes.argtypes = [i32, pi64, pi64, pi64, i32, i32, i32, i32]
     # the forward-backward calls over a caller-given band: their siblings' arguments with the table behind max_move (the
     # tenth argument of a single call, a pointer; the eleventh of a batch call, an array of pointers)
     for call in ("path_posteriors", "label_posteriors", "state_posteriors", "state_durations",

@@ -714,7 +714,14 @@ class StreamingAligner:
     newest ends anywhere (``free_end_scores``; at ``finish()`` it ends at the final path's last state), every older one at the
     ``beta_out`` of the chunk after it; only the newly committed frames' values are returned.  Cost: at most two full
     forward-backward passes and one forward-only pass per chunk, and one more row of 2S+1 doubles per pending chunk.  With
-    ``False`` nothing changes."""
+    ``False`` nothing changes.
+
+    ``confidence="margin"``: the fifth array is float64, the best-path margin of every committed state (``ctc_margins_resume``,
+    ``unit="state"``): how much the best alignment of all audio pushed so far would lose if it had to be at another state in
+    that frame, >= 0 for a committed frame, +inf where no other state has a path.  The same visits as ``confidence=True`` with
+    max-plus passes in its place (no exp or log; a third of the cost), and exact: at every commit the values are those of the
+    whole prefix under the concatenated table with a free end, bit for bit, and at ``finish()`` those of
+    ``ctc_path_margins(..., band_lo=table)`` of the whole input.  Any other value of ``confidence`` raises ValueError."""
 
     def __init__(self, labels, beam_size=1000, max_move=4, period=16, end="highest", confidence=False):
         self.labels = labels
@@ -724,7 +731,9 @@ class StreamingAligner:
         if end not in END_CELLS:
             raise ValueError('end must be "highest" or "best"')
         self.end = end
-        self.confidence = bool(confidence)
+        if confidence != "margin" if isinstance(confidence, str) else confidence not in (True, False):
+            raise ValueError('confidence must be False, True or "margin"')
+        self.confidence = "margin" if isinstance(confidence, str) else bool(confidence)
         self._row, self._lo = None, 0      # what the next chunk starts from
         self._alpha = None                 # confidence: ln alpha of the last pushed frame, the next chunk's start row
         self._pending = []                 # oldest first: dicts of a chunk's rows, start row, table, path parts, emitted frames
@@ -761,14 +770,18 @@ class StreamingAligner:
     def _confidence(self, upto_last, terminal=None):
         """The posterior of the committed state at every frame ``_emit(upto_last)`` is about to return: the pending chunks newest
         first, the newest to a free end (or ``terminal``), each older one to the row the chunk after it handed back."""
-        from .posteriors import ctc_posteriors_resume, free_end_scores
+        from .posteriors import ctc_margins_resume, ctc_posteriors_resume, free_end_scores
         L = 2 * int(self._pending[-1]["S"]) + 1
         end = free_end_scores(L) if terminal is None else int(terminal)
         posts = []
         for k in range(len(self._pending) - 1, -1, -1):
             c = self._pending[k]
-            _o, post, _a, end, _z = ctc_posteriors_resume(c["lp"], self.labels, c["table"], c["alpha_in"], end, c["out"][0], False,
-                                                          "beta" if k > 0 else False, self.beam_size, self.max_move)
+            if self.confidence == "margin":     # (the same visit in max-plus: the start row is D, the row handed back E)
+                post, _r, _s, _l, _d, end, _z = ctc_margins_resume(c["lp"], self.labels, c["table"], c["out"][0], c["alpha_in"], end, "state",
+                                                                   None, "e" if k > 0 else False, self.beam_size, self.max_move)
+            else:
+                _o, post, _a, end, _z = ctc_posteriors_resume(c["lp"], self.labels, c["table"], c["alpha_in"], end, c["out"][0], False,
+                                                              "beta" if k > 0 else False, self.beam_size, self.max_move)
             posts.append(post[c["emitted"]:upto_last] if k == len(self._pending) - 1 else post[c["emitted"]:])
         posts.reverse()
         if _is_tensor(posts[0]):
@@ -778,11 +791,15 @@ class StreamingAligner:
 
     def _forward(self, lp, table):
         """confidence: the chunk forward-only from the kept alpha row; what it adds to the chunk's pending entry"""
-        from .posteriors import ctc_posteriors_resume, free_end_scores
+        from .posteriors import ctc_margins_resume, ctc_posteriors_resume, free_end_scores
         S = int(self.labels.shape[0]) if _is_tensor(self.labels) else int(np.asarray(self.labels).reshape(-1).shape[0])
         alpha_in = self._alpha
-        self._alpha = ctc_posteriors_resume(lp, self.labels, table, alpha_in, free_end_scores(2 * S + 1), None, False, "alpha",
-                                            self.beam_size, self.max_move)[2]
+        if self.confidence == "margin":
+            self._alpha = ctc_margins_resume(lp, self.labels, table, None, alpha_in, free_end_scores(2 * S + 1), "state", None, "d",
+                                             self.beam_size, self.max_move)[4]
+        else:
+            self._alpha = ctc_posteriors_resume(lp, self.labels, table, alpha_in, free_end_scores(2 * S + 1), None, False, "alpha",
+                                                self.beam_size, self.max_move)[2]
         return {"alpha_in": alpha_in, "S": S}
 
     def push(self, log_probs_chunk):
@@ -805,7 +822,10 @@ class StreamingAligner:
             conf = (self._confidence(det),) if self.confidence else ()
             return self._emit(det) + conf
         empty = self._pending[-1]["out"]
-        conf = ((sc[:0] if _is_tensor(sc) else np.zeros(0, np.float32)),) if self.confidence else ()
+        conf = ()
+        if self.confidence:
+            dtype = np.float64 if self.confidence == "margin" else np.float32
+            conf = ((sc[:0].double() if dtype is np.float64 else sc[:0]) if _is_tensor(sc) else np.zeros(0, dtype),)
         return tuple(x[:0] for x in empty) + conf
 
     def finish(self):

@@ -3,7 +3,7 @@
 // state visit probabilities (ka_visit.hpp), exact boundary-time quantiles (ka_quantile.hpp), alignments sampled from the band
 // posterior (ka_sample.hpp) and the maximum-expected-accuracy alignment (ka_mea.hpp); and, with a driver of its own
 // (banded_impl), the best path over a caller-given band (ka_banded.hpp); and, through fb_impl again, the best-path margins
-// from max-marginals (ka_margin.hpp), which are max-plus and no forward-backward.  The first four also run over a caller-given band
+// from max-marginals (ka_margin.hpp) and their resumed form (ka_margin_resume.hpp), which are max-plus and no forward-backward.  The first four also run over a caller-given band
 // (ka_ctc_*_banded_*: fb_impl<Call, ka::BandTable>, the same driver on Banded<Desc> descriptors).  Host code only.
 // They use the engine's workspace and pinned buffer, with their own kernels and workspace layout, whatever
 // the engine's mode, and run to the end inside the call: no batch stays in flight.
@@ -499,6 +499,127 @@ struct MarginCall {
         KA_HIP(hipMemcpyAsync(through[i], ws + c.through, T * sizeof(double), hipMemcpyDeviceToHost, a.stream));
         KA_HIP(hipMemcpyAsync(alt[i], ws + c.alt, T * sizeof(double), hipMemcpyDeviceToHost, a.stream));
         if (runner(i)) KA_HIP(hipMemcpyAsync(runner(i), ws + c.runner, T * 4, hipMemcpyDeviceToHost, a.stream));
+        return KA_OK;
+    }
+};
+
+// The best-path margins under the caller's boundary conditions, with rows of m at chosen frames (ka_margin_resume.hpp):
+// MarginCall's arrays, every one of them optional here, and beside them two rows in, two rows out and the query frames with
+// their rows.  Like MarginCall it runs as fb_impl on the diagonal's descriptors and fills the table itself.
+struct MarginResumeCall {
+    using Desc = ka::MarginResumeLattice;
+    static constexpr size_t kBandedGranule = ka::kBandedDescBytes;   // (never carved: no Banded<> sibling)
+    using Carve = ka::plan::MarginResumeCarve;
+    static constexpr const char *kName = "margins resume";
+    static constexpr const char *kBadArgs =
+        ": a path value or the terminal outside [0, 2S+1), a NaN or +inf in d_in or e_in, or band_lo does not hold non-decreasing values in [0, 2S+1)";
+    static constexpr const char *kZeroMass = ": no path of finite score joins the start row to the end";
+    const int32_t *const *band_lo;
+    const double *const *d_in;
+    const double *const *e_in;
+    const int64_t *terminal;         // NULL: all -1 (path[T-1])
+    const int32_t *const *path;
+    int32_t unit;
+    double *const *through;
+    double *const *alt;
+    int32_t *const *runner_up;
+    const int64_t *const *frames;    // host arrays in both memory modes
+    const int64_t *K;                // NULL: no query frames
+    double *const *rows;
+    const int64_t *ld_rows;
+    int64_t *const *rows_lo;
+    double *const *d_out;
+    double *const *e_out;
+
+    template <class P>
+    static P at(P const *arr, int32_t i) { return arr ? arr[i] : nullptr; }
+    int64_t k(int32_t i) const { return K ? K[i] : 0; }
+    int64_t term(int32_t i) const { return terminal ? terminal[i] : -1; }
+    bool arrays() const { return true; }
+    const char *bad_lattice(const FbArgs &a, int32_t i) const
+    {
+        const int64_t n = k(i);
+        if (n > 0 && !at(frames, i)) return ": NULL frames";
+        for (int64_t j = 0; j < n; ++j) {
+            if (frames[i][j] < 0 || frames[i][j] >= a.T[i]) return ": a frame outside [0, T)";
+            if (j > 0 && frames[i][j] <= frames[i][j - 1]) return ": frames not strictly increasing";
+        }
+        if (n > 0 && (!at(rows, i) || !at(rows_lo, i) || !ld_rows)) return ": state rows asked for without rows, ld_rows or rows_lo";
+        const int64_t W = std::max<int64_t>(1, std::min<int64_t>(a.beam_size, 2 * a.S[i] + 1));
+        if (n > 0 && ld_rows[i] < W) return ": ld_rows < min(beam_size, 2S+1)";
+        if ((at(through, i) || at(alt, i) || at(runner_up, i)) && !at(path, i)) return ": through, alt or runner_up without path";
+        if (term(i) < -1) return ": terminal must be -1 (the path's last state) or a position";
+        if (!at(e_in, i) && term(i) == -1 && !at(path, i)) return ": neither e_in, a terminal nor a path says where the lattice ends";
+        // (the kernel reads d_in again behind the store of d_out, and e_in behind it)
+        const size_t row = (size_t)(2 * a.S[i] + 1) * sizeof(double);
+        auto overlap = [row](const double *x, const double *y) {
+            return x && y && reinterpret_cast<uintptr_t>(x) < reinterpret_cast<uintptr_t>(y) + row &&
+                   reinterpret_cast<uintptr_t>(y) < reinterpret_cast<uintptr_t>(x) + row;
+        };
+        for (const double *out : {(const double *)at(d_out, i), (const double *)at(e_out, i)})
+            if (overlap(out, at(d_in, i)) || overlap(out, at(e_in, i))) return ": an output row overlaps an input row";
+        return nullptr;
+    }
+    bool buffers(int32_t) const { return true; }
+    size_t plan(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host, Carve *cv,
+                size_t *off_res) const
+    {
+        return ka::plan::margins_resume_workspace(n, T, S, K, V, beam, max_move, host, cv, off_res);   // (0 for K < 0 or K > T)
+    }
+    template <class Band>
+    static constexpr auto launch = ka::launch_margins_resume;
+    void fill(Desc &d, const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        const bool host = a.mem == KA_MEM_HOST;
+        auto dbl = [&](const double *p, size_t off) { return !p ? nullptr : host ? reinterpret_cast<double *>(ws + off) : const_cast<double *>(p); };
+        d.band_lo = !at(band_lo, i) ? nullptr : host ? reinterpret_cast<const int32_t *>(ws + c.tab) : band_lo[i];
+        d.path = !at(path, i) ? nullptr : host ? reinterpret_cast<const int32_t *>(ws + c.path) : path[i];
+        d.through = dbl(at(through, i), c.through);
+        d.alt = dbl(at(alt, i), c.alt);
+        d.runner = !at(runner_up, i) ? nullptr : host ? reinterpret_cast<int32_t *>(ws + c.runner) : runner_up[i];
+        d.unit = unit;
+        d.d_in = dbl(at(d_in, i), c.rows[0]);
+        d.e_in = dbl(at(e_in, i), c.rows[1]);
+        d.d_out = dbl(at(d_out, i), c.rows[2]);
+        d.e_out = dbl(at(e_out, i), c.rows[3]);
+        fill_slot(d, c, -1, ws);
+        d.terminal = term(i) < 0 ? -1 : (int32_t)std::min<int64_t>(term(i), INT32_MAX);   // (a position past the lattice is the kernel's to refuse)
+        d.K = (int32_t)k(i);
+        d.W = c.W;
+        d.frames = reinterpret_cast<const int64_t *>(ws + c.frames);
+        if (d.K > 0) {
+            d.rows = host ? reinterpret_cast<double *>(ws + c.qrows) : rows[i];
+            d.rows_lo = host ? reinterpret_cast<int64_t *>(ws + c.qlo) : rows_lo[i];
+            d.ld_rows = host ? c.W : ld_rows[i];
+        }
+    }
+    int upload(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        const size_t row = (size_t)(2 * a.S[i] + 1) * sizeof(double);
+        if (at(path, i)) KA_HIP(hipMemcpyAsync(ws + c.path, path[i], (size_t)a.T[i] * 4, hipMemcpyHostToDevice, a.stream));
+        if (at(band_lo, i)) KA_HIP(hipMemcpyAsync(ws + c.tab, band_lo[i], (size_t)a.T[i] * 4, hipMemcpyHostToDevice, a.stream));
+        if (at(d_in, i)) KA_HIP(hipMemcpyAsync(ws + c.rows[0], d_in[i], row, hipMemcpyHostToDevice, a.stream));
+        if (at(e_in, i)) KA_HIP(hipMemcpyAsync(ws + c.rows[1], e_in[i], row, hipMemcpyHostToDevice, a.stream));
+        return KA_OK;
+    }
+    int stage(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        if (k(i) > 0) KA_HIP(hipMemcpyAsync(ws + c.frames, frames[i], (size_t)k(i) * 8, hipMemcpyHostToDevice, a.stream));
+        return KA_OK;
+    }
+    int download(const Carve &c, const FbArgs &a, int32_t i, char *ws) const
+    {
+        const size_t T = (size_t)a.T[i], row = (size_t)(2 * a.S[i] + 1) * sizeof(double);
+        if (at(through, i)) KA_HIP(hipMemcpyAsync(through[i], ws + c.through, T * sizeof(double), hipMemcpyDeviceToHost, a.stream));
+        if (at(alt, i)) KA_HIP(hipMemcpyAsync(alt[i], ws + c.alt, T * sizeof(double), hipMemcpyDeviceToHost, a.stream));
+        if (at(runner_up, i)) KA_HIP(hipMemcpyAsync(runner_up[i], ws + c.runner, T * 4, hipMemcpyDeviceToHost, a.stream));
+        if (at(d_out, i)) KA_HIP(hipMemcpyAsync(d_out[i], ws + c.rows[2], row, hipMemcpyDeviceToHost, a.stream));
+        if (at(e_out, i)) KA_HIP(hipMemcpyAsync(e_out[i], ws + c.rows[3], row, hipMemcpyDeviceToHost, a.stream));
+        if (k(i) > 0) {
+            KA_HIP(hipMemcpy2DAsync(rows[i], (size_t)ld_rows[i] * 8, ws + c.qrows, (size_t)c.W * 8, (size_t)c.W * 8, (size_t)k(i),
+                                    hipMemcpyDeviceToHost, a.stream));
+            KA_HIP(hipMemcpyAsync(rows_lo[i], ws + c.qlo, (size_t)k(i) * 8, hipMemcpyDeviceToHost, a.stream));
+        }
         return KA_OK;
     }
 };
@@ -1496,6 +1617,39 @@ size_t ka_path_margin_workspace_bytes(int32_t n, const int64_t *T, const int64_t
 {
     if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
     return ka::plan::path_margin_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
+}
+
+// ---- best-path margins under the caller's boundary conditions, rows of max-marginals at chosen frames (ka_margin_resume.hpp) ----
+int ka_ctc_margins_resume_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
+                                    const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
+                                    const int32_t *const *band_lo, const double *const *d_in, const double *const *e_in, const int64_t *terminal,
+                                    const int32_t *const *path, int32_t unit, double *const *through, double *const *alt,
+                                    int32_t *const *runner_up, const int64_t *const *frames, const int64_t *K, double *const *rows,
+                                    const int64_t *ld_rows, int64_t *const *rows_lo, double *const *d_out, double *const *e_out, double *score,
+                                    int32_t *status, int32_t mem, void *stream)
+{
+    if (unit != 0 && unit != 1) return fail(KA_ERR_BAD_ARGS, "margins resume: unit must be 0 (state) or 1 (text index)");
+    return fb_impl(e, FbArgs{n, log_probs, T, V, ld, labels, S, beam_size, max_move, score, status, mem, (hipStream_t)stream, nullptr},
+                   MarginResumeCall{band_lo, d_in, e_in, terminal, path, unit, through, alt, runner_up, frames, K, rows, ld_rows, rows_lo, d_out,
+                                    e_out});
+}
+
+int ka_ctc_margins_resume_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
+                              int32_t beam_size, int32_t max_move, const int32_t *band_lo, const double *d_in, const double *e_in,
+                              int64_t terminal, const int32_t *path, int32_t unit, double *through, double *alt, int32_t *runner_up,
+                              const int64_t *frames, int64_t K, double *rows, int64_t ld_rows, int64_t *rows_lo, double *d_out, double *e_out,
+                              double *score, int32_t mem, void *stream)
+{
+    return ka_ctc_margins_resume_batch_f32(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo, &d_in, &e_in, &terminal, &path,
+                                           unit, &through, &alt, &runner_up, &frames, &K, &rows, &ld_rows, &rows_lo, &d_out, &e_out, score,
+                                           nullptr, mem, stream);
+}
+
+size_t ka_margins_resume_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t V, int32_t beam_size,
+                                         int32_t max_move, int32_t mem)
+{
+    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    return ka::plan::margins_resume_workspace(n, T, S, K, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
 }  // extern "C"

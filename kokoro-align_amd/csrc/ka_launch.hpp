@@ -126,6 +126,9 @@ void launch_sample_paths(const BandDesc<SampleLattice, Band> *lats, int n_fast, 
 // ---- ka_margin.hip: best-path margins from max-marginals (ka_margin.hpp): launch_fb_slots' form split, grid and slots; a
 // descriptor with a table (MarginLattice::band_lo) runs over it, one without over the reference's diagonal ----
 void launch_path_margins(const MarginLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
+// ---- ka_margin_resume.hip: the same pass under the caller's boundary conditions, with rows of m at chosen frames
+// (ka_margin_resume.hpp) ----
+void launch_margins_resume(const MarginResumeLattice *lats, int n_fast, int n_generic, int max_move, PostResult *res, hipStream_t s);
 
 // ---- ka_banded.hip: best path over a caller-given band (ka_banded.hpp).  Descriptors [0, n_fast): one wavefront per lattice
 // (band <= kFastMaxBand, V <= 64, max_move <= 4), then [n_fast, n_fast + n_generic): one 256-thread workgroup per lattice.

@@ -1,5 +1,5 @@
 // ka_margin.hpp — best-path margins from max-marginals (ka_ctc_path_margins_*).  Included by
-// ka_margin.hip only.
+// ka_margin.hip and, through ka_margin_resume.hpp, by ka_margin_resume.hip.
 //
 // The best path's own recurrence, run forwards (D) and backwards (E) in max-plus arithmetic, over the lattice of
 // ka_ctc_best_path_banded (lab' the blank-expanded labels, L = 2S+1, band [lo_t, hi_t) from the caller's table or, without one,
@@ -64,11 +64,13 @@ struct MarginRed {
     int32_t p[4];
 };
 
-template <int M>
-struct MgFast : FbFast<M, MarginLattice, LabRing> {
-    using Base = FbFast<M, MarginLattice, LabRing>;
+// The forms are written over the descriptor type (MgFastOn, MgGenOn): MarginLattice for ka_ctc_path_margins (MgFast<M>, MgGen
+// below), MarginResumeLattice for the resumed call (ka_margin_resume.hpp).
+template <int M, class Desc>
+struct MgFastOn : FbFast<M, Desc, LabRing> {
+    using Base = FbFast<M, Desc, LabRing>;
     template <class Sh>
-    __device__ __forceinline__ MgFast(const MarginLattice &d_, Sh &sh) : Base(d_, sh) {}
+    __device__ __forceinline__ MgFastOn(const Desc &d_, Sh &sh) : Base(d_, sh) {}
 
     // the row in natural units: a float widens exactly
     __device__ __forceinline__ int row(int64_t, int64_t tn, bool more, bool check = false)
@@ -89,6 +91,12 @@ struct MgFast : FbFast<M, MarginLattice, LabRing> {
         const int64_t end = (lo + 1024 < this->d.L) ? lo + 1024 : (int64_t)this->d.L;
         for (int64_t p = lo + threadIdx.x; p < end; p += 64) this->lab.ring[p & 1023] = fb_lab(this->d, p);
         this->lab.lfill = end;
+    }
+    // ... for a backward walk that starts at a frame whose band begins at lo, with no forward walk before it
+    __device__ __forceinline__ void reseat_bwd(int64_t lo)
+    {
+        reseat(lo);
+        this->lab.lbot = lo;
     }
     __device__ __forceinline__ void best(double &m, int32_t &p, MarginRed &) const { margin_wave_best(m, p); }
 
@@ -138,10 +146,10 @@ struct MgFast : FbFast<M, MarginLattice, LabRing> {
         }
     }
     // G_t over [lo, hi) from G_{t+1} (gn, its vetoable copy vn) over [nlo, nhi) into gc / vc; cell(p, E_t(p), pre(p)), pre(p)
-    // fetched with the group's loads.  kLast: t = T-1
+    // fetched with the group's loads.  kLast: t = T-1, E_{T-1} = {sstar: 0}, or the caller's row ein where there is one
     template <bool kLast, class Pre, class Cell>
     __device__ __forceinline__ void bwd(int64_t lo_, int64_t hi_, int64_t nlo_, int64_t nhi_, const double *gn, const double *vn, double *gc,
-                                        double *vc, int64_t sstar, Pre pre, Cell cell) const
+                                        double *vc, int64_t sstar, Pre pre, Cell cell, const double *ein = nullptr) const
     {
         const double NINF = post_dninf();
         const int32_t hi = (int32_t)hi_, nlo = (int32_t)nlo_, nhi = (int32_t)nhi_;
@@ -159,7 +167,7 @@ struct MgFast : FbFast<M, MarginLattice, LabRing> {
                 const int32_t p = b + 64 * k;
                 e[k] = this->lds_row[lab[k]];
                 if (kLast) {
-                    w[k] = (p == sstar) ? 0.0 : NINF;
+                    w[k] = ein ? (p < hi ? ein[p] : NINF) : (p == sstar) ? 0.0 : NINF;
                 } else {
                     w[k] = NINF;
 #pragma unroll
@@ -185,13 +193,23 @@ struct MgFast : FbFast<M, MarginLattice, LabRing> {
     }
 };
 
-struct MgGen : FbGen<MarginLattice> {
-    using Base = FbGen<MarginLattice>;
+template <int M>
+struct MgFast : MgFastOn<M, MarginLattice> {
     template <class Sh>
-    __device__ __forceinline__ MgGen(const MarginLattice &d_, Sh &sh) : Base(d_, sh) {}
+    __device__ __forceinline__ MgFast(const MarginLattice &d_, Sh &sh) : MgFastOn<M, MarginLattice>(d_, sh) {}
+};
+
+template <class Desc>
+struct MgGenOn : FbGen<Desc> {
+    using Base = FbGen<Desc>;
+    using Base::d;
+    using Base::lrow;
+    template <class Sh>
+    __device__ __forceinline__ MgGenOn(const Desc &d_, Sh &sh) : Base(d_, sh) {}
 
     __device__ __forceinline__ void fence() const { __syncthreads(); }   // (no frame maximum here whose barrier would order the frames)
     __device__ __forceinline__ void reseat(int64_t) {}
+    __device__ __forceinline__ void reseat_bwd(int64_t) {}
     __device__ __forceinline__ void best(double &m, int32_t &p, MarginRed &red) const
     {
         margin_wave_best(m, p);
@@ -225,7 +243,7 @@ struct MgGen : FbGen<MarginLattice> {
     }
     template <bool kLast, class Pre, class Cell>
     __device__ __forceinline__ void bwd(int64_t lo, int64_t hi, int64_t nlo, int64_t nhi, const double *gn, const double *vn, double *gc,
-                                        double *vc, int64_t sstar, Pre pre, Cell cell) const
+                                        double *vc, int64_t sstar, Pre pre, Cell cell, const double *ein = nullptr) const
     {
         const int M = d.max_move;
         const double NINF = post_dninf();
@@ -233,7 +251,7 @@ struct MgGen : FbGen<MarginLattice> {
             const int32_t lab = fb_lab(d, p);
             double w;
             if (kLast) {
-                w = (p == sstar) ? 0.0 : NINF;
+                w = ein ? ein[p] : (p == sstar) ? 0.0 : NINF;
             } else {
                 w = NINF;
                 for (int j = 0; j < M && p + j < nhi; ++j)
@@ -246,30 +264,51 @@ struct MgGen : FbGen<MarginLattice> {
         }
     }
 };
+struct MgGen : MgGenOn<MarginLattice> {
+    template <class Sh>
+    __device__ __forceinline__ MgGen(const MarginLattice &d_, Sh &sh) : MgGenOn<MarginLattice>(d_, sh) {}
+};
+
+// What stands before frame 0 and at frame T-1, and what is read out of m: a policy of margin_lattice.  MgPlain, the default,
+// is ka_ctc_path_margins: the virtual start {0: 0.0}, E_{T-1} = {path[T-1]: 0}, through / alt / runner_up of every frame; every
+// `if constexpr (Pol::kPlain)` below keeps the lines that call has always run.  The one other policy, MgResume
+// (ka_margin_resume.hpp), takes the two rows from the caller, hands two back and reads rows of m out at chosen frames.
+struct MgPlain {
+    static constexpr bool kPlain = true;
+    const MarginLattice &d;
+    __device__ __forceinline__ explicit MgPlain(const MarginLattice &d_) : d(d_) {}
+    __device__ __forceinline__ void fail(PostResult *res, int status) const { margin_fail(d, res, status); }
+};
 
 // One lattice: the forward pass with its checkpoints and checks, then the blocks backwards.
-template <class Form, class Band>
+template <class Form, class Band, class Pol = MgPlain>
 __device__ __forceinline__ void margin_lattice(Form &f, PostResult *res, MarginRed &red)
 {
-    const MarginLattice &d = f.d;
+    const auto &d = f.d;
+    Pol pol(d);
     const int tid = threadIdx.x;
     const int64_t T = d.T, L = d.L;
     const double NINF = post_dninf();
-    if (fb_labels_bad(d)) return margin_fail(d, res, kStatusBadLabel);
+    if (fb_labels_bad(d)) return pol.fail(res, kStatusBadLabel);
     Band bw(L, d.beam, T, d.band_lo);
-    if (!bw.start()) return margin_fail(d, res, kStatusBadArgs);   // (a caller's table that is no band: before any of its values places a cell)
+    if (!bw.start()) return pol.fail(res, kStatusBadArgs);   // (a caller's table that is no band: before any of its values places a cell)
     int flags = 0;
-    for (int64_t t = tid; t < T; t += Form::NT) {
-        const int32_t pv = d.path[t];
-        flags |= (pv < 0 || pv >= L) ? 4 : 0;
-    }
+    if (Pol::kPlain || d.path)
+        for (int64_t t = tid; t < T; t += Form::NT) {
+            const int32_t pv = d.path[t];
+            flags |= (pv < 0 || pv >= L) ? 4 : 0;
+        }
 
     // ---- forward: D through every frame, a checkpoint before every block ----
     auto no_cell = [](int64_t, double) {};
     f.lab.fill();
     double *prev = f.col(0), *cur = f.col(1);
-    if (tid == 0) prev[0] = 0.0;   // virtual state before frame 0
     int64_t plo = 0, phi = 1;
+    if constexpr (Pol::kPlain) {
+        if (tid == 0) prev[0] = 0.0;   // virtual state before frame 0
+    } else {
+        pol.place(bw, prev, plo, phi);
+    }
     f.row_prefetch(0);
     f.sync();
     for (int64_t t = 0; t < T; ++t) {
@@ -280,7 +319,11 @@ __device__ __forceinline__ void margin_lattice(Form &f, PostResult *res, MarginR
         const bool more = t + 1 < T;
         if (more) f.lab.fwd_request(lon);
         flags |= f.row(t, t + 1, more, true);
-        if (t % kPostCk == 0) f.ck_store(t / kPostCk, prev, plo, phi);
+        if (t % kPostCk == 0) {
+            bool store = true;
+            if constexpr (!Pol::kPlain) store = pol.stores(t / kPostCk);
+            if (store) f.ck_store(t / kPostCk, prev, plo, phi);
+        }
         f.fence();
         f.fwd(lo, hi, plo, phi, prev, cur, no_cell);
         { double *x = prev; prev = cur; cur = x; }
@@ -289,12 +332,26 @@ __device__ __forceinline__ void margin_lattice(Form &f, PostResult *res, MarginR
         if (more) f.lab.fwd_commit();
         f.fence();
     }
-    flags = post_block_flags(flags);
-    if (flags) return margin_fail(d, res, post_status_of(flags));
-    const int64_t sstar = d.path[T - 1];
-    const double score = (sstar >= plo && sstar < phi) ? prev[Form::cslot(sstar)] : NINF;
-    f.sync();   // (every thread has read the score before a column is written again)
-    if (score == NINF) return margin_fail(d, res, kStatusZeroMass);
+    int64_t sstar;
+    double score;
+    if constexpr (Pol::kPlain) {
+        flags = post_block_flags(flags);
+        if (flags) return pol.fail(res, post_status_of(flags));
+        sstar = d.path[T - 1];
+        score = (sstar >= plo && sstar < phi) ? prev[Form::cslot(sstar)] : NINF;
+        f.sync();   // (every thread has read the score before a column is written again)
+        if (score == NINF) return pol.fail(res, kStatusZeroMass);
+    } else {
+        const int status = pol.finish(f, red, prev, plo, phi, flags, sstar, score);
+        if (status != kStatusOk) return pol.fail(res, status);
+        if (!pol.backward()) {   // a forward pass alone
+            if (tid == 0) {
+                res[d.idx].status = kStatusOk;
+                res[d.idx].log_likelihood = score;
+            }
+            return;
+        }
+    }
 
     // ---- backward, a block at a time ----
     double *gn = f.col(0), *vn = f.col(1), *gc = f.col(2), *vc = f.col(3);   // G_{t+1} and its vetoable copy; frame t's, and scratch
@@ -302,44 +359,60 @@ __device__ __forceinline__ void margin_lattice(Form &f, PostResult *res, MarginR
     const int unit = d.unit;
     for (int64_t k = (T - 1) / kPostCk; k >= 0; --k) {
         const int64_t t0 = k * kPostCk, t1 = (t0 + kPostCk < T) ? t0 + kPostCk : T;
-        // D over [t0, t1) from the block's checkpoint into the slab, gc / vc as the working columns
+        bool with_d = true;   // is the block's D asked for?  (a resumed call may want E alone)
+        if constexpr (!Pol::kPlain) {
+            if (pol.done()) break;
+            with_d = pol.block(t0, t1);
+        }
         int64_t rlo = 0, rhi = 1;
-        bw.seek(t0);
-        if (t0 > 0) {
-            bw.prev();
+        if (with_d) {
+            // D over [t0, t1) from the block's checkpoint into the slab, gc / vc as the working columns
+            bw.seek(t0);
+            if (t0 > 0) {
+                bw.prev();
+                bw.band(rlo, rhi);
+                bw.next();
+            }
+            double *pv = gc, *cu = vc;
+            if (Pol::kPlain || k > 0) {
+                f.ck_load(k, pv, rlo, rhi);
+            } else {
+                if constexpr (!Pol::kPlain) pol.place(bw, pv, rlo, rhi);   // (block 0 has no checkpoint: its start row is placed again)
+            }
+            {
+                int64_t lo, hi;
+                bw.band(lo, hi);
+                f.reseat(lo);
+            }
+            f.row_prefetch(t0);
+            f.sync();
+            for (int64_t t = t0; t < t1; ++t) {
+                int64_t lo, hi, lon, hin;
+                bw.band(lo, hi);
+                bw.next();
+                bw.band(lon, hin);
+                const bool more = t + 1 < t1;
+                if (more) f.lab.fwd_request(lon);
+                f.row(t, t + 1, more);
+                f.fence();
+                double *al = d.slab + (t - t0) * f.cw();
+                f.fwd(lo, hi, rlo, rhi, pv, cu, [&](int64_t p, double val) { al[Form::slot(p, lo)] = val; });
+                { double *x = pv; pv = cu; cu = x; }
+                rlo = lo;
+                rhi = hi;
+                if (more) f.lab.fwd_commit();
+                f.fence();
+            }
+            // E back through the block; bw stands at t1, and is kept a frame ahead (below) of the frame at work
+            f.lab.turn(rlo);
+        } else {
+            bw.seek(t1 - 1);
             bw.band(rlo, rhi);
             bw.next();
+            f.reseat_bwd(rlo);
         }
-        double *pv = gc, *cu = vc;
-        f.ck_load(k, pv, rlo, rhi);
-        {
-            int64_t lo, hi;
-            bw.band(lo, hi);
-            f.reseat(lo);
-        }
-        f.row_prefetch(t0);
-        f.sync();
-        for (int64_t t = t0; t < t1; ++t) {
-            int64_t lo, hi, lon, hin;
-            bw.band(lo, hi);
-            bw.next();
-            bw.band(lon, hin);
-            const bool more = t + 1 < t1;
-            if (more) f.lab.fwd_request(lon);
-            f.row(t, t + 1, more);
-            f.fence();
-            double *al = d.slab + (t - t0) * f.cw();
-            f.fwd(lo, hi, rlo, rhi, pv, cu, [&](int64_t p, double val) { al[Form::slot(p, lo)] = val; });
-            { double *x = pv; pv = cu; cu = x; }
-            rlo = lo;
-            rhi = hi;
-            if (more) f.lab.fwd_commit();
-            f.fence();
-        }
-        // E back through the block; bw stands at t1, and is kept a frame ahead (below) of the frame at work
-        f.lab.turn(rlo);
         f.row_prefetch(t1 - 1);
-        int32_t ptn = d.path[t1 - 1];
+        int32_t ptn = (Pol::kPlain || d.path) ? d.path[t1 - 1] : -1;
         bw.prev();
         f.sync();
         for (int64_t t = t1 - 1; t >= t0; --t) {
@@ -351,30 +424,75 @@ __device__ __forceinline__ void margin_lattice(Form &f, PostResult *res, MarginR
             f.lab.bwd_request(lon, more);
             f.row(t, t - 1, more);
             const int32_t pt = ptn;
-            if (more) ptn = d.path[t - 1];
+            if (more && (Pol::kPlain || d.path)) ptn = d.path[t - 1];
             f.fence();
             const double *al = d.slab + (t - t0) * f.cw();
             double bm = NINF;
             int32_t bp = -1;
-            auto pre = [&](int64_t p) { return al[Form::slot(p, lo)]; };   // D_t(p), from the slab
-            auto cell = [&](int64_t p, double w, double dt) {
-                const double m = dt + w;
-                if ((p >> unit) == ((int64_t)pt >> unit)) {
-                    if (p == pt) d.through[t] = m;
-                } else if (m > bm) {   // (a lane's cells ascend: the first of equal m stays)
-                    bm = m;
-                    bp = (int32_t)p;
+            if constexpr (Pol::kPlain) {
+                auto pre = [&](int64_t p) { return al[Form::slot(p, lo)]; };   // D_t(p), from the slab
+                auto cell = [&](int64_t p, double w, double dt) {
+                    const double m = dt + w;
+                    if ((p >> unit) == ((int64_t)pt >> unit)) {
+                        if (p == pt) d.through[t] = m;
+                    } else if (m > bm) {   // (a lane's cells ascend: the first of equal m stays)
+                        bm = m;
+                        bp = (int32_t)p;
+                    }
+                };
+                if (t == T - 1)
+                    f.template bwd<true>(lo, hi, nlo, nhi, gn, vn, gc, vc, sstar, pre, cell);
+                else
+                    f.template bwd<false>(lo, hi, nlo, nhi, gn, vn, gc, vc, sstar, pre, cell);
+                f.best(bm, bp, red);
+                if (tid == 0) {
+                    if (!(pt >= lo && pt < hi)) d.through[t] = NINF;
+                    d.alt[t] = bm;
+                    if (d.runner) d.runner[t] = bp;
                 }
-            };
-            if (t == T - 1)
-                f.template bwd<true>(lo, hi, nlo, nhi, gn, vn, gc, vc, sstar, pre, cell);
-            else
-                f.template bwd<false>(lo, hi, nlo, nhi, gn, vn, gc, vc, sstar, pre, cell);
-            f.best(bm, bp, red);
-            if (tid == 0) {
-                if (!(pt >= lo && pt < hi)) d.through[t] = NINF;
-                d.alt[t] = bm;
-                if (d.runner) d.runner[t] = bp;
+            } else {
+                // the frame in two instantiations, chosen per block: with D (from the slab, with every read-out of m) and without (E
+                // alone: no slab load, no cell work), so that neither carries the other's branches in its cells
+                auto frame = [&](auto with) {
+                    constexpr bool kD = decltype(with)::value;
+                    double *row = nullptr;   // where m_t goes, if the frame is asked for
+                    if constexpr (kD) row = pol.query(t);
+                    const bool paths = kD && pol.path_out();
+                    auto pre = [&](int64_t p) {
+                        if constexpr (kD) return al[Form::slot(p, lo)];
+                        else return 0.0;
+                    };
+                    auto cell = [&](int64_t p, double w, double dt) {
+                        if constexpr (kD) {
+                            const double m = dt + w;
+                            if (row) row[p - lo] = m;
+                            if (!paths) return;
+                            if ((p >> unit) == ((int64_t)pt >> unit)) {
+                                if (p == pt && d.through) d.through[t] = m;
+                            } else if (m > bm) {
+                                bm = m;
+                                bp = (int32_t)p;
+                            }
+                        }
+                    };
+                    if (t == T - 1)
+                        f.template bwd<true>(lo, hi, nlo, nhi, gn, vn, gc, vc, sstar, pre, cell, d.e_in);
+                    else
+                        f.template bwd<false>(lo, hi, nlo, nhi, gn, vn, gc, vc, sstar, pre, cell);
+                    if constexpr (kD) {
+                        if (d.alt || d.runner) f.best(bm, bp, red);
+                        if (tid == 0 && paths) {
+                            if (d.through && !(pt >= lo && pt < hi)) d.through[t] = NINF;
+                            if (d.alt) d.alt[t] = bm;
+                            if (d.runner) d.runner[t] = bp;
+                        }
+                        if (row) pol.row_done(row, lo, hi);
+                    }
+                };
+                if (with_d)
+                    frame(std::true_type{});
+                else
+                    frame(std::false_type{});
             }
             { double *x = gn; gn = gc; gc = x; }
             { double *x = vn; vn = vc; vc = x; }
@@ -384,6 +502,7 @@ __device__ __forceinline__ void margin_lattice(Form &f, PostResult *res, MarginR
             f.fence();
         }
     }
+    if constexpr (!Pol::kPlain) pol.before(gn, vn, nlo, nhi);
     if (tid == 0) {
         res[d.idx].status = kStatusOk;
         res[d.idx].log_likelihood = score;

@@ -1116,5 +1116,51 @@ inline size_t path_margin_workspace(int32_t n, const int64_t *T, const int64_t *
     });
 }
 
+// ---- ka_ctc_margins_resume_batch_f32 (ka_margin_resume.hpp): workspace layout ----
+// path_margin_workspace's layout and slots with MarginResumeLattice descriptors and, per lattice, its K query frames (int64; both
+// memory modes: the kernel reads them from the workspace); for host buffers, beside the sibling's staged arrays, the four rows
+// (d_in, e_in, d_out, e_out: 2S+1 doubles each), the staged state rows (K x W doubles) and their low ends (K int64).  Room is
+// carved whether or not the lattice brings an array, so that the byte count depends on the shapes and K alone.  K may be NULL:
+// no query frames.  0 for a K outside [0, T].
+struct MarginResumeCarve : MarginCarve {
+    size_t frames;
+    size_t rows[4], qrows, qlo;   // host buffers only
+    int32_t W;
+};
+inline size_t margins_resume_workspace(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t V, int32_t beam, int32_t max_move,
+                                       bool host_buffers, MarginResumeCarve *cv, size_t *off_res)
+{
+    return slot_workspace(n, sizeof(MarginResumeLattice), T, S, V, beam, max_move, cv, off_res,
+                          [&](int32_t i, const Shape &sh, MarginResumeCarve &c, size_t &off) {
+        const int64_t k = K ? K[i] : 0;
+        if (k < 0 || k > T[i]) return false;
+        c.W = (int32_t)sh.W;
+        c.frames = off;
+        off += align_up((size_t)k * 8);
+        if (host_buffers) {
+            carve_staged(off, sh, V, c);
+            c.path = off;
+            off += align_up((size_t)sh.T * 4);
+            c.tab = off;
+            off += align_up((size_t)sh.T * 4);
+            c.through = off;
+            off += align_up((size_t)sh.T * sizeof(double));
+            c.alt = off;
+            off += align_up((size_t)sh.T * sizeof(double));
+            c.runner = off;
+            off += align_up((size_t)sh.T * 4);
+            for (size_t &r : c.rows) {
+                r = off;
+                off += align_up((size_t)sh.L * sizeof(double));
+            }
+            c.qrows = off;
+            off += align_up((size_t)k * (size_t)sh.W * sizeof(double));
+            c.qlo = off;
+            off += align_up((size_t)k * 8);
+        }
+        return true;
+    });
+}
+
 }  // namespace plan
 }  // namespace ka

@@ -249,6 +249,23 @@ struct MarginLattice : FbCkLattice {
     int32_t pad_;
 };
 static_assert(sizeof(MarginLattice) == 152, "descriptor sizes");
+// ---- best-path margins under the caller's boundary conditions and rows of max-marginals at chosen frames
+// (ka_margin_resume.hpp): a descriptor of its own, so that MarginLattice and the workspace figures of
+// ka_ctc_path_margins stay as they are.  path, through, alt and runner may each be NULL here; FbCkLattice::terminal is the
+// end state where e_in is NULL, -1 for path[T-1].  The rows are [L] doubles, absolute, -inf = no path ----
+struct MarginResumeLattice : MarginLattice {
+    const double *d_in;           // D of the row before frame 0; NULL: the virtual state {0: 0.0}
+    const double *e_in;           // E of frame T-1; NULL: {terminal: 0.0}
+    double *d_out;                // output, or NULL: D of frame T-1 over its band, -inf elsewhere
+    double *e_out;                // output, or NULL: E of the row before frame 0
+    const int64_t *frames;        // [K] query frames, strictly increasing in [0, T) (workspace)
+    double *rows;                 // [K, ld_rows] output, W columns written: m at every query frame, from the band's low end
+    int64_t *rows_lo;             // [K] output: the band's low end at every query frame
+    int64_t ld_rows;
+    int32_t K;
+    int32_t W;                    // widest band: max(1, min(beam, L))
+};
+static_assert(sizeof(MarginResumeLattice) == 224, "descriptor sizes");
 // the workspace planners (ka_plan.hpp) carve n descriptors: their sizes are part of the published workspace byte counts
 static_assert(sizeof(PostLattice) == 88 && sizeof(FbCkLattice) == 104 && sizeof(OccLattice) == 120 && sizeof(StateLattice) == 136 &&
                   sizeof(DurLattice) == 120 && sizeof(SampleLattice) == 128 && sizeof(VisitLattice) == 120 &&

@@ -1257,3 +1257,180 @@ def ctc_label_posteriors_chunked(log_probs, labels, band_lo, chunk_frames, termi
             post[a:b] = p
         z = zk if z is None else z
     return occ, post, z
+
+
+# ------------------------------------------------------------------------------------------
+# best-path margins under the caller's boundary conditions: margins of a recording cut into chunks, and rows of
+# max-marginals at chosen frames
+# ------------------------------------------------------------------------------------------
+_MARGIN_ROWS = {True: (True, True), False: (False, False), "d": (True, False), "e": (False, True)}
+
+
+def ctc_margins_resume(log_probs, labels, band_lo, path=None, d_in=None, end=None, unit="state", frames=None, rows=True, beam_size=1000,
+                       max_move=4):
+    """``ctc_path_margins`` over one chunk of a recording: (margin, runner_up, state_rows, rows_lo, d_out, e_out, score).
+
+    The chunk's frames ``log_probs`` [T, V] run over the table ``band_lo`` [T] (None: the diagonal band) from the row ``d_in``
+    (float64 [2S+1], the best score of every state of the row before the chunk's first frame, -inf = no path; None: the
+    virtual start state) to ``end``: None (the last state of ``path``), an int, the terminal state, or a float64 row [2S+1],
+    what a path that is at a state in the last frame still gains (``free_end_scores``: it may end anywhere).  ``d_out`` (the
+    last frame's scores over its band, -inf elsewhere) is the next chunk's ``d_in``; ``e_out`` (the gain from the row before the
+    first frame) is the previous chunk's ``end``.  With both exchanged the margins of the chunks, concatenated, are the uncut
+    recording's bit for bit, and the last chunk's score is the recording's.  margin float64 [T] and runner_up int32 [T] as
+    ``ctc_path_margins`` returns them (None without ``path``); ``frames`` (strictly increasing in [0, T)): state_rows float64
+    [K, W] holds m at state rows_lo[k] + j of frame frames[k] (absolute: subtract ``score``), -inf past the band's width, W =
+    min(beam_size, 2S+1); both None without ``frames``.  ``rows``: True, False, "d" or "e" - which rows are returned (d_out and
+    score alone cost one forward pass).  All arithmetic is float64 adds and maxima: no tolerance applies anywhere.  NumPy in ->
+    NumPy out; ROCm torch tensors go to ``ctc_margins_resume_device``.  Raises as ``ctc_path_margins``; a NaN or +inf in a row
+    raises ValueError.
+    """
+    call = ctc_margins_resume_device if _is_tensor(log_probs) else ctc_margins_resume_batch
+    (result,) = call([log_probs], [labels], [band_lo], None if path is None else [path], None if d_in is None else [d_in], [end], unit,
+                     None if frames is None else [frames], rows, beam_size, max_move)
+    return result
+
+
+def _margins_resume(lat, band_lo, path, d_in, end, unit, frames, rows, beam_size, max_move, return_status, raw):
+    if unit not in _MARGIN_UNITS:
+        raise ValueError('unit must be "state" or "text"')
+    if rows not in _MARGIN_ROWS:
+        raise ValueError('rows must be True, False, "d" or "e"')
+    want_d, want_e = _MARGIN_ROWS[rows]
+    n, Ls = lat.n, [2 * S + 1 for S in lat.S]
+    for name, x in (("band_lo", band_lo), ("path", path), ("d_in", d_in), ("end", end), ("frames", frames)):
+        if x is not None and len(x) != n:
+            raise ValueError(f"{name} must hold one entry (or None) per lattice")
+    entry = lambda xs, i: None if xs is None else xs[i]
+    given = [i for i in range(n) if entry(band_lo, i) is not None]
+    tabs = dict(zip(given, _band_tables(_Sub(lat, given), [band_lo[i] for i in given]))) if given else {}
+    tables = [tabs.get(i) for i in range(n)]
+    paths = [None if entry(path, i) is None else lat.int32(path[i]) for i in range(n)]
+    if any(p is not None and p.shape[0] != T for p, T in zip(paths, lat.T)):
+        raise ValueError("a path must have one position per frame")
+    a_in = [None if entry(d_in, i) is None else _row_f64(lat, d_in[i], Ls[i], "d_in") for i in range(n)]
+    ends = [entry(end, i) for i in range(n)]
+    b_in = [_row_f64(lat, e, L, "an end row") if e is not None and _is_end_row(e) else None for e, L in zip(ends, Ls)]
+    terms = [-1 if e is None or b is not None else _terminal_of(e) for e, b in zip(ends, b_in)]
+    if any(e is None and p is None for e, p in zip(ends, paths)):
+        raise ValueError("end=None is the last state of path: a lattice needs one of the two")
+    fr = [None if entry(frames, i) is None else _frames_of(frames[i], lat.T[i]) for i in range(n)]     # (host memory in both forms)
+    Ws = [_band_width(S, beam_size) for S in lat.S]
+    thr = [None if p is None else lat.empty(T, np.float64) for p, T in zip(paths, lat.T)]
+    alt = [None if p is None else lat.empty(T, np.float64) for p, T in zip(paths, lat.T)]
+    run = [None if p is None else lat.empty(T, np.int32) for p, T in zip(paths, lat.T)]
+    srows = [None if f is None else lat.empty((len(f), W), np.float64) for f, W in zip(fr, Ws)]
+    slo = [None if f is None else lat.empty(len(f), np.int64) for f in fr]
+    a_out = [lat.empty(L, np.float64) if want_d else None for L in Ls]
+    b_out = [lat.empty(L, np.float64) if want_e else None for L in Ls]
+
+    def ptrs(xs):
+        return _ptr_array([None if x is None else lat.ptr(x) for x in xs])
+    p_band, _k0 = ptrs(tables)
+    p_din, _k1 = ptrs(a_in)
+    p_ein, _k2 = ptrs(b_in)
+    p_term, _k3 = _i64_array(terms)
+    p_path, _k4 = ptrs(paths)
+    p_thr, _k5 = ptrs(thr)
+    p_alt, _k6 = ptrs(alt)
+    p_run, _k7 = ptrs(run)
+    p_fr, _k8 = _ptr_array([None if f is None or not len(f) else f.ctypes.data for f in fr])
+    p_K, _k9 = _i64_array([0 if f is None else len(f) for f in fr])
+    p_rows, _k10 = ptrs([None if f is None or not len(f) else r for f, r in zip(fr, srows)])
+    p_ld, _k11 = _i64_array(Ws)
+    p_lo, _k12 = ptrs([None if f is None or not len(f) else x for f, x in zip(fr, slo)])
+    p_dout, _k13 = ptrs(a_out)
+    p_eout, _k14 = ptrs(b_out)
+    got = _run_lattices(lat, "margins_resume", beam_size, max_move,
+                        (p_band, p_din, p_ein, p_term, p_path, _MARGIN_UNITS[unit], p_thr, p_alt, p_run, p_fr, p_K, p_rows, p_ld, p_lo,
+                         p_dout, p_eout), list(zip(thr, alt, run, srows, slo, a_out, b_out)), return_status)
+    if raw:
+        return got
+
+    def margin(th, al):
+        if th is None or _is_tensor(th):
+            return None if th is None else th - al
+        with np.errstate(invalid="ignore"):
+            return th - al
+    results = [(margin(th, al), *rest) for th, al, *rest in (got[0] if return_status else got)]
+    return (results, got[1]) if return_status else results
+
+
+def ctc_margins_resume_batch(log_probs_list, labels_list, band_lo, path=None, d_in=None, end=None, unit="state", frames=None, rows=True,
+                             beam_size=1000, max_move=4, device=None, return_status=False, raw=False):
+    """``ctc_margins_resume`` of many chunks in ONE launch; host NumPy buffers in and out.  ``band_lo``, ``path``, ``d_in``,
+    ``end`` and ``frames`` are None or lists in which any entry may be None.  Returns a list of (margin, runner_up, state_rows,
+    rows_lo, d_out, e_out, score), with ``raw`` of (through, alt, runner_up, ...); with ``return_status`` also the per-lattice
+    status list, in which case failures do not raise (every float output of a failed lattice is NaN, rows included)."""
+    lat = _host_lattices(log_probs_list, labels_list, log_probs_list, "log-probs", device)
+    if lat is None:
+        return ([], []) if return_status else []
+    return _margins_resume(lat, band_lo, path, d_in, end, unit, frames, rows, beam_size, max_move, return_status, raw)
+
+
+def ctc_margins_resume_device(log_probs, labels, band_lo, path=None, d_in=None, end=None, unit="state", frames=None, rows=True,
+                              beam_size=1000, max_move=4, return_status=False, raw=False):
+    """``ctc_margins_resume_batch`` on lists of ROCm torch tensors: results and rows stay on the device (float64 tensors), so
+    that a chunk's rows reach its neighbour without a copy; ``frames`` are host lists.  One launch on torch's current stream."""
+    lat = _device_lattices(log_probs, labels, log_probs, "log-probs")
+    if lat is None:
+        return ([], []) if return_status else []
+    return _margins_resume(lat, band_lo, path, d_in, end, unit, frames, rows, beam_size, max_move, return_status, raw)
+
+
+def ctc_state_margins(log_probs, labels, terminal, frames, beam_size=1000, max_move=4, band_lo=None):
+    """How far every band position of chosen frames lies behind the best alignment: (rows float64 [K, W], band_lo int64 [K],
+    score float).
+
+    rows[k, j] = m - score, with m the score of the best complete path of the band of ``ctc_best_path`` that is at state
+    band_lo[k] + j in frame ``frames[k]`` and ends at ``terminal`` (an int, or a best path whose last value is used), and score
+    the best path's: every entry is <= 0, 0 on a best path's state, -inf where no path passes or past the band's width.  W =
+    min(beam_size, 2S+1).  The best-path counterpart of ``ctc_state_posteriors``: adds and maxima only, float64, exact.
+    ``band_lo``: the band as a table [T]; None is the diagonal band.  NumPy in -> NumPy out, tensors in -> tensors out.
+    """
+    _m, _r, srows, lo, _d, _e, score = ctc_margins_resume(log_probs, labels, band_lo, None, None, _terminal_of(terminal), "state", frames, False,
+                                                          beam_size, max_move)
+    if _is_tensor(srows):
+        return srows - score, lo, score
+    with np.errstate(invalid="ignore"):
+        return srows - score, lo, score
+
+
+def ctc_path_margins_chunked(log_probs, labels, path, band_lo, chunk_frames, unit="state", beam_size=1000, max_move=4, raw=False):
+    """``ctc_path_margins(..., band_lo=)`` of a recording in the checkpoint workspace of one chunk, bit for bit: (margin float64
+    [T], runner_up int32 [T], score float), or (through, alt, runner_up, score) with ``raw``.
+
+    A forward-only sweep over chunks of ``chunk_frames`` frames keeps every chunk's start row (2S+1 doubles per chunk); the
+    chunks are then visited newest first, each from its start row to the row its successor handed back (the last one to the
+    path's last state).  By pass count that is one forward pass more than the uncut call.  NumPy in, NumPy out.
+    """
+    lp = np.asarray(log_probs)
+    T = lp.shape[0]
+    chunk = int(chunk_frames)
+    if chunk < 1:
+        raise ValueError("chunk_frames must be at least 1")
+    band = np.asarray(band_lo).reshape(-1)
+    if band.shape[0] != T:
+        raise ValueError("a band table must have one entry per frame")
+    pth = np.asarray(path).reshape(-1)
+    if pth.shape[0] != T:
+        raise ValueError("a path must have one position per frame")
+    L = 2 * len(np.asarray(labels).reshape(-1)) + 1
+    cuts = list(range(0, T, chunk)) + [T]
+    starts, row = [], None
+    for a, b in zip(cuts[:-2], cuts[1:-1]):      # forward only: the start row of every chunk but the first
+        starts.append(row)
+        row = ctc_margins_resume(lp[a:b], labels, band[a:b], None, row, free_end_scores(L), unit, None, "d", beam_size, max_move)[4]
+    starts.append(row)
+    through, alt, runner = np.empty(T, np.float64), np.empty(T, np.float64), np.empty(T, np.int32)
+    end, score = None, None
+    for k in range(len(starts) - 1, -1, -1):     # newest first, with both rows
+        a, b = cuts[k], cuts[k + 1]
+        ((th, al, ru, _s, _l, _d, end, z),) = ctc_margins_resume_batch([lp[a:b]], [labels], [band[a:b]], [pth[a:b]],
+                                                                       None if starts[k] is None else [starts[k]], [end], unit, None,
+                                                                       "e" if k > 0 else False, beam_size, max_move, raw=True)
+        through[a:b], alt[a:b], runner[a:b] = th, al, ru
+        score = z if score is None else score
+    if raw:
+        return through, alt, runner, score
+    with np.errstate(invalid="ignore"):
+        return through - alt, runner, score
