@@ -1006,6 +1006,12 @@ int ka_debug_chunk_entries(ka_engine *e, int32_t *out, int32_t max_entries, uint
  * number of rows: 0 (and *pitch = 0) where no checkpoints were stored - the exact and generic forms, and a lattice that
  * the checkpointed forms declined (non-finite log-probs). */
 int ka_debug_checkpoints(ka_engine *e, float *out, int64_t max_floats, int64_t *pitch);
+/* Diagnostics of the kernels' routing: the flag word the kernels left for every lattice of the last finished best-path batch,
+ * in the caller's order (at most max_lattices are copied; returns the number of lattices of that batch).  Bit 0: a transcript
+ * label is 0; bit 1: the checkpointed form declined the lattice to the exact kernels (non-finite log-probs); bit 2: declined
+ * and too wide for them; bit 3: the checkpointed one-wavefront forward pass found the sign bit set in every log-prob (a +0.0
+ * clears it), so its serial backtrace took the keyed frames. */
+int ka_debug_meta_flags(ka_engine *e, int32_t *out, int32_t max_lattices);
 /* Host-side probe of the tiled form's plan (no GPU needed): for a lattice of T frames, S phonemes, V classes the
  * 256-position tiles the band of align.py:64-65 ever touches and the frames [t_in, t_end) each of them is alive in.
  * Returns the number of tiles (t_in / t_end are filled up to max_tiles), 0 if the shape is not run in the tiled form,

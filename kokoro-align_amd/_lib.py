@@ -33,7 +33,7 @@ EXPORTS = [
     "ka_engine_last_kernel_ms", "ka_log_softmax_f32", "ka_hash_logprobs_f32", "ka_hash_labels_i32",
     "ka_hash_logprobs_batch_f32", "ka_hash_labels_batch_i32", "ka_engine_set_mode", "ka_lstm_step_f32",
     "ka_lstm_layer_f32", "ka_window_energy_f32", "ka_stft_frames_f32", "ka_power_f32", "ka_power_to_db_f32",
-    "ka_debug_tile_stats", "ka_engine_set_backtrace", "ka_debug_chunk_entries", "ka_debug_checkpoints", "ka_debug_plan_tiles",
+    "ka_debug_tile_stats", "ka_engine_set_backtrace", "ka_debug_chunk_entries", "ka_debug_checkpoints", "ka_debug_meta_flags", "ka_debug_plan_tiles",
     "ka_engine_set_verify", "ka_stream_create", "ka_stream_destroy",
     "ka_debug_set_split", "ka_engine_workspace_bytes", "ka_debug_set_tile_lds",
     "ka_debug_auto_split", "ka_lstm_layer0_f32", "ka_debug_set_tile_width", "ka_debug_tile_width_choice", "ka_debug_plan_tiles_width",
@@ -271,6 +271,8 @@ def load_library():
     L.ka_debug_chunk_entries.argtypes = [vp, vp, i32, vp, i64]
     L.ka_debug_checkpoints.restype = ctypes.c_int
     L.ka_debug_checkpoints.argtypes = [vp, vp, i64, pi64]
+    L.ka_debug_meta_flags.restype = ctypes.c_int
+    L.ka_debug_meta_flags.argtypes = [vp, vp, i32]
     L.ka_debug_plan_tiles.restype = ctypes.c_int
     L.ka_debug_plan_tiles.argtypes = [i64, i64, i32, i32, i32, vp, vp, i32, vp]
     L.ka_debug_plan_tiles_width.restype = ctypes.c_int

@@ -659,6 +659,8 @@ int ka_batch_finish(ka_engine *e, float *total_score, int32_t *status)
     // (a copy: the redo lays its own descriptors and status records over the pinned ones)
     std::vector<ka::LatticeMeta> meta(b.meta, b.meta + (size_t)b.n);
     if (e->dbg.ck_idx < b.n && (meta[e->dbg.ck_idx].flags & (ka::kFlagExact | ka::kFlagDeclined))) e->dbg.ck_bytes = 0;
+    e->dbg.flags.resize((size_t)b.n);
+    for (int32_t i = 0; i < b.n; ++i) e->dbg.flags[(size_t)i] = meta[i].flags;
     // wide tiled lattices the scores-only form declined: KA_MODE_AUTO redoes them through the generic kernels, an explicit
     // KA_MODE_TILED reports KA_ERR_NONFINITE
     std::vector<ka_engine::Redo> again;
@@ -724,6 +726,15 @@ int ka_debug_chunk_entries(ka_engine *e, int32_t *out, int32_t max_entries, uint
     if (map0_out && map0_max > 0 && e->dbg.map0_bytes)
         KA_HIP(hipMemcpy(map0_out, e->res.ws + e->dbg.map0, std::min<size_t>(e->dbg.map0_bytes, (size_t)map0_max), hipMemcpyDeviceToHost));
     return (int)n;
+}
+
+int ka_debug_meta_flags(ka_engine *e, int32_t *out, int32_t max_lattices)
+{
+    if (!e || max_lattices < 0 || (max_lattices > 0 && !out)) return fail(KA_ERR_BAD_ARGS, "ka_debug_meta_flags: bad arguments");
+    if (e->batch.pending) return fail(KA_ERR_BAD_ARGS, "ka_debug_meta_flags: a batch is enqueued and not finished");
+    const size_t n = std::min<size_t>(e->dbg.flags.size(), (size_t)max_lattices);
+    for (size_t i = 0; i < n; ++i) out[i] = e->dbg.flags[i];
+    return (int)e->dbg.flags.size();
 }
 
 int ka_debug_checkpoints(ka_engine *e, float *out, int64_t max_floats, int64_t *pitch)

@@ -106,6 +106,7 @@ struct ka_engine {
         size_t ck = 0, ck_bytes = 0, ck_pitch = 0;
         int32_t ck_idx = 0;      // the caller's index of descriptor 0
         size_t tasks = 0, stats = 0, n_tasks = 0;
+        std::vector<int32_t> flags;   // ka_debug_meta_flags: the kFlag* word of every lattice of the last finished batch
     } dbg;
 };
 

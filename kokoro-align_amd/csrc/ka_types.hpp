@@ -37,6 +37,7 @@ constexpr int kStatusNaN = -6;      // a log-prob is NaN (the reference's np.arg
 constexpr int kFlagZeroLabel = 1;   // meta flags: a transcript label is 0
 constexpr int kFlagExact = 2;       // meta flags: the checkpointed path declined this lattice (non-finite log-probs)
 constexpr int kFlagDeclined = 4;    // meta flags: declined, and too wide for the exact kernels' ring: no result (KA_ERR_NONFINITE)
+constexpr int kFlagAllNeg = 8;      // meta flags: every log-prob has its sign bit set (forward_ck; a +0.0 clears it): the keyed backtrace is exact
 
 constexpr int kSlots = 1024;        // 64 lanes x 16 cells
 constexpr int kFastMaxBand = 1009;  // kSlots - 15: widest band the w16 layout can hold

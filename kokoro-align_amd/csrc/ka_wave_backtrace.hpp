@@ -307,6 +307,100 @@ __device__ __forceinline__ void rc_frame1(float &s, uint32_t &word, float e, flo
                  : [e] "v"(e), [rown] "v"(row_next), [lab1] "v"(lab1), [vadd] "v"(vadd), [open] "s"(open), [mk] "s"(mask), [ninf] "v"(NINF)
                  : "memory", "scc");
 }
+// ---- the keyed frames: the maximum AND its first index from one v_min_f64 per candidate ----
+// For lattices whose log-probs all have the sign bit set (kFlagAllNeg, ka_wave_forward.hpp) every candidate sum is -0.0 or
+// below, or -inf.  Then |sum|, read as the HIGH word of a double, is an order-reversing key that is always a finite double (the
+// f32 exponent 0xFF is the f64 exponent 0x7F8), and with the candidate's move j in the LOW word
+//     v_min_f64 d, |a|, |b|
+// returns the pair of the largest sum and, among equal sums, of the smallest j - np.argmax's choice (align.py:83).  An all -inf
+// cell comes out as move 0, as from the compares.  One v_min_f64 per candidate replaces v_max3 / v_max, a v_cmp_eq per candidate
+// and two v_addc per cell; the cell's code is the low word of the result, one v_lshl_or_b32 (coded as the move itself: the
+// kernel complements the code words once per chunk, the walk decodes 3 - move as before).
+// Scores are kept as |score| in the high word of a result pair; the next frame forms e - |score|, which is the forward kernel's
+// e + score bit for bit (a subtraction is the addition of the negated operand; where the forward kernel holds +0.0 this form
+// holds -0.0, which has the same key).  A key whose f32 bits lie under 0x00100000 (|sum| < 2^-129, -0.0 among them) is an f64
+// denormal or zero: the kernel must run with f64 denormals preserved (FLOAT_DENORM_MODE_16_64 of the kernel descriptor, which
+// is the default).
+// The pairs are fixed registers, because an operand of an asm block cannot name half of a 64-bit register: candidates
+// v[2:3], v[4:5], v[6:7], v[8:9] with low words 0, 1, 2, 3 written once, results v[10:11] (label cell; the one-cell form's
+// cell) and v[12:13] (blank cell).  The blank cell takes the pairs 0, 1 and 3 again: its candidates are moves 0, 1 and 3.
+// DPP hazards as in the compare form: v11 / v13 are last written by the previous block's v_min_f64 or select, at least
+// s_waitcnt, the gather and two more instructions before their first DPP read; v5 is read through DPP three instructions after
+// the v_mov_dpp that writes it, %[x] five after its v_sub.
+#define KA_RCK_DPP " wave_ror:1 row_mask:0xf bank_mask:0xf\n\t"
+#define KA_RCK_PAIRS(a, b, c, d, rl) "+{v[2:3]}"(a), "+{v[4:5]}"(b), "+{v[6:7]}"(c), "+{v[8:9]}"(d), "+{v[10:11]}"(rl)
+#define KA_RCK_FRAME4                                                                     \
+    KA_RC_GATHER                                                                          \
+    "v_sub_f32 %[x], %[e0], v11\n\t"                                                      \
+    "v_subrev_f32_dpp v7, v11, %[el]" KA_RCK_DPP                                          \
+    "v_subrev_f32_dpp v9, v13, %[el]" KA_RCK_DPP                                          \
+    "v_sub_f32 v3, %[el], v11\n\t"                                                        \
+    "v_sub_f32 v5, %[el], v13\n\t"                                                        \
+    "v_min_f64 v[10:11], |v[2:3]|, |v[4:5]|\n\t"                                          \
+    "v_mov_b32_dpp v5, %[x]" KA_RCK_DPP                                                   \
+    "v_min_f64 v[10:11], v[10:11], |v[6:7]|\n\t"                                          \
+    "v_sub_f32 v3, %[e0], v13\n\t"                                                        \
+    "v_min_f64 v[10:11], v[10:11], |v[8:9]|\n\t"                                          \
+    "v_mov_b32_dpp v9, v5" KA_RCK_DPP                                                     \
+    "v_min_f64 v[12:13], |v[2:3]|, |v[4:5]|\n\t"                                          \
+    "v_min_f64 v[12:13], v[12:13], |v[8:9]|\n\t"                                          \
+    "v_lshl_or_b32 %[w], %[w], 2, v12\n\t"                                                \
+    "v_lshl_or_b32 %[w], %[w], 2, v10\n\t"                                                \
+    "s_bitcmp1_b32 %[open], 0\n\t"                                                        \
+    "s_cbranch_scc1 .Lka_rck_open_%=\n\t"                                                 \
+    "v_cndmask_b32 v13, %[pinf], v13, %[mb]\n\t"                                          \
+    "v_cndmask_b32 v11, %[pinf], v11, %[ml]\n"                                            \
+    ".Lka_rck_open_%=:\n\t"                                                               \
+    "s_waitcnt lgkmcnt(0)"
+// the six pairs of a keyed wavefront
+struct RcKeyed {
+    uint64_t a, b, c, d, rl, rb;
+};
+__device__ __forceinline__ float rck_hi(uint64_t pair) { return __builtin_bit_cast(float, (uint32_t)(pair >> 32)); }
+// |score| into the high word of a result pair
+__device__ __forceinline__ uint64_t rck_key(float score) { return (uint64_t)(__builtin_bit_cast(uint32_t, score) & 0x7fffffffu) << 32; }
+__device__ __forceinline__ void rc_frame4_keyed(RcKeyed &k, uint32_t &word, float e0, float el, float &e0_next, float &el_next, float row_next,
+                                                int lab4, uint32_t open, uint64_t mask_b, uint64_t mask_l, float PINF)
+{
+    float x;
+    asm volatile(KA_RCK_FRAME4
+                 : KA_RCK_PAIRS(k.a, k.b, k.c, k.d, k.rl), "+{v[12:13]}"(k.rb), [w] "+v"(word), [eln] "=&v"(el_next), [e0n] KA_RC_E0_OUT(e0_next), [x] "=&v"(x)
+                 : [e0] KA_RC_E0_IN(e0), [el] "v"(el), [rown] "v"(row_next), [lab4] "v"(lab4), [open] "s"(open), [mb] "s"(mask_b),
+                   [ml] "s"(mask_l), [pinf] "v"(PINF)
+                 : "memory", "scc");
+}
+// the one-cell frame (rc_frame1): the cell is v[10:11]; 11 vector instructions instead of 14
+#define KA_RCK_FRAME1                                                                     \
+    "ds_bpermute_b32 %[en], %[lab1], %[rown]\n\t"                                         \
+    "v_sub_f32 v3, %[e], v11\n\t"                                                         \
+    "v_mov_b32_dpp %[r1], v11" KA_RCK_DPP                                                 \
+    "v_subrev_f32_dpp v5, v11, %[e]" KA_RCK_DPP                                           \
+    "v_add_f32 %[ev], %[e], %[vadd]\n\t"                                                  \
+    "v_mov_b32_dpp %[r2], %[r1]" KA_RCK_DPP                                               \
+    "v_subrev_f32_dpp v7, %[r1], %[ev]" KA_RCK_DPP                                        \
+    "v_min_f64 v[10:11], |v[2:3]|, |v[4:5]|\n\t"                                          \
+    "v_subrev_f32_dpp v9, %[r2], %[e]" KA_RCK_DPP                                         \
+    "v_min_f64 v[10:11], v[10:11], |v[6:7]|\n\t"                                          \
+    "v_min_f64 v[10:11], v[10:11], |v[8:9]|\n\t"                                          \
+    "v_lshl_or_b32 %[w], %[w], 2, v10\n\t"                                                \
+    "s_bitcmp1_b32 %[open], 0\n\t"                                                        \
+    "s_cbranch_scc1 .Lka_rck1_open_%=\n\t"                                                \
+    "v_cndmask_b32 v11, %[pinf], v11, %[mk]\n"                                            \
+    ".Lka_rck1_open_%=:\n\t"                                                              \
+    "s_waitcnt lgkmcnt(0)"
+__device__ __forceinline__ void rc_frame1_keyed(RcKeyed &k, uint32_t &word, float e, float &e_next, float row_next, int lab1, float vadd,
+                                                uint32_t open, uint64_t mask, float PINF)
+{
+    float r1, r2, ev;
+    asm volatile(KA_RCK_FRAME1
+                 : KA_RCK_PAIRS(k.a, k.b, k.c, k.d, k.rl), [w] "+v"(word), [en] "=&v"(e_next), [r1] "=&v"(r1), [r2] "=&v"(r2), [ev] "=&v"(ev)
+                 : [e] "v"(e), [rown] "v"(row_next), [lab1] "v"(lab1), [vadd] "v"(vadd), [open] "s"(open), [mk] "s"(mask), [pinf] "v"(PINF)
+                 : "memory", "scc");
+}
+#undef KA_RCK_FRAME1
+#undef KA_RCK_FRAME4
+#undef KA_RCK_PAIRS
+#undef KA_RCK_DPP
 #undef KA_RC1_BLOCK
 #undef KA_RC_HEAD
 #undef KA_RC_GATHER
@@ -426,9 +520,13 @@ __device__ __forceinline__ void rc_walk_out(const uint32_t (&codes)[kCkFrames / 
 // best_labels / best_scores stay in registers all the way: the labels come out of the window's label register after the walk,
 // the scores out of the row registers during it (rc_walk_out).  (Fetching both from memory after the walk instead, with a
 // gather per chunk, was measured and removed: the numbers are in DESIGN.md 8, the code under tools/experiments/.)
-template <int M, bool ZL, bool PAR>
+// KEYED (max_move = 4, no label 0, serial walk only): the frames above in their keyed form, for the lattices the forward kernel
+// has flagged kFlagAllNeg.  The plain instance of the same (M, ZL, PAR) leaves those lattices to it and takes the others.
+template <int M, bool ZL, bool PAR, bool KEYED = false>
 __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ lats, const int32_t *meta, int n_lats)
 {
+    constexpr bool HAS_KEYED = M == 4 && !ZL && !PAR;   // this (M, ZL, PAR) has a keyed twin
+    static_assert(!KEYED || HAS_KEYED, "the keyed frames exist for max_move 4 without label 0 in the serial walk");
     const int which = PAR ? __builtin_amdgcn_readfirstlane(lattice_of_chunk(lats, n_lats, (int64_t)blockIdx.x)) : (int)blockIdx.x;
     const Lattice &d = lats[which];
     const int lane = threadIdx.x;
@@ -437,6 +535,7 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
     const int flags = __builtin_amdgcn_readfirstlane(mt[2]);
     if (flags & (kFlagExact | kFlagDeclined)) return;        // handled by the exact kernels / not at all
     if (((flags & kFlagZeroLabel) != 0) != ZL) return;       // the other instance's lattice (as in the forward kernels)
+    if (HAS_KEYED && ((flags & kFlagAllNeg) != 0) != KEYED) return;   // likewise
     if (__builtin_amdgcn_readfirstlane(mt[0]) != kStatusOk) return;   // rejected (bad label, NaN, empty beam): no path
     int p = __builtin_amdgcn_readfirstlane(mt[1]);
     if (p < 0) return;  // empty beam: status already set by the forward kernel
@@ -469,6 +568,8 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
     uint32_t q0 = uni(((uint64_t)L * t0) / T), r0 = uni(((uint64_t)L * t0) % T);
     const uint32_t D32 = uni(((uint64_t)L * kCkFrames) / T), R32 = uni(((uint64_t)L * kCkFrames) % T);
     const float inv_T = 1.0f / (float)T;
+    [[maybe_unused]] RcKeyed key = {0, 1, 2, 3, 0, 0};       // (KEYED) low words of the candidate pairs: their moves, written once
+    [[maybe_unused]] const float PINF = __builtin_inff();    // (KEYED) the key of -inf
 
     for (;;) {
         const int n = (int)(T - t0 < (uint32_t)kCkFrames ? T - t0 : (uint32_t)kCkFrames);
@@ -606,7 +707,13 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
                 // bit f: frame f's band differs from frame f-1's (bit 0: set it up; bit kRcSplit: set the one-cell window's up)
                 moves = (uint32_t)__builtin_amdgcn_ballot_w64(qa != qb) << 1 | 1u | (1u << kRcSplit);
             }
-            asm volatile("s_nop 1" : "+v"(sb), "+v"(sl));   // (a DPP read follows within the next block)
+            if constexpr (KEYED) {
+                key.rb = rck_key(sb);
+                key.rl = rck_key(sl);
+                asm volatile("s_nop 1" : "+{v[10:11]}"(key.rl), "+{v[12:13]}"(key.rb));
+            } else {
+                asm volatile("s_nop 1" : "+v"(sb), "+v"(sl));   // (a DPP read follows within the next block)
+            }
             float s1 = NINF, vadd = NINF, e1c = NINF, e1n;
             // ONE loop for both kinds of chunk and both phases: the row registers are waited for in one place per frame
             // whichever way the chunk goes (two loops made hipcc copy rows whose loads were in flight)
@@ -615,8 +722,11 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
                 if (f < kRcSplit) {
                     if ((moves >> f) & 1u) band_masks(f);
                     if (f + 1 < kCkFrames) row_wait_n(rows[f + 1], kCkFrames - 2 - f);
-                    rc_frame4<ZL>(sb, sl, codes[f >> 3], e0c, elc, e0n, eln, rows[f + 1 < kCkFrames ? f + 1 : f], lab4, zero, veto,
-                                  open_bit, mask_b, mask_l, NINF);
+                    if constexpr (KEYED)
+                        rc_frame4_keyed(key, codes[f >> 3], e0c, elc, e0n, eln, rows[f + 1 < kCkFrames ? f + 1 : f], lab4, open_bit, mask_b, mask_l, PINF);
+                    else
+                        rc_frame4<ZL>(sb, sl, codes[f >> 3], e0c, elc, e0n, eln, rows[f + 1 < kCkFrames ? f + 1 : f], lab4, zero, veto,
+                                      open_bit, mask_b, mask_l, NINF);
                     e0c = e0n;
                     elc = eln;
                     continue;
@@ -626,9 +736,11 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
                     // lane (w2 - wlo + i) / 2 < 64; lanes 61 .. 63 start at -inf (a masked chunk keeps them there)
                     const int src4 = ((lane + (w2 - wlo)) >> 1) << 2;
                     const bool odd = (lane & 1) != 0;
-                    const float xb = bperm(src4, sb), xl = bperm(src4, sl);
+                    // (KEYED: the scores are the keys, and -inf is +inf)
+                    const float xb = bperm(src4, KEYED ? rck_hi(key.rb) : sb), xl = bperm(src4, KEYED ? rck_hi(key.rl) : sl);
                     const int l4 = __builtin_amdgcn_ds_bpermute(src4, lab4);
-                    s1 = lane < kRc1Lanes ? (odd ? xl : xb) : NINF;
+                    s1 = lane < kRc1Lanes ? (odd ? xl : xb) : (KEYED ? PINF : NINF);
+                    if constexpr (KEYED) key.rl = rck_key(s1);
                     lab1 = odd ? l4 : 0;
                     vadd = (!odd || (ZL && l4 == 0)) ? NINF : -0.0f;
                     asm volatile("ds_bpermute_b32 %0, %1, %2\n\t"
@@ -637,7 +749,10 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
                 }
                 if ((moves >> f) & 1u) band_mask1(f);
                 if (f + 1 < kCkFrames) row_wait_n(rows[f + 1], kCkFrames - 2 - f);
-                rc_frame1(s1, codes2[(f - kRcSplit) >> 4], e1c, e1n, rows[f + 1 < kCkFrames ? f + 1 : f], lab1, vadd, open_bit, mask_1, NINF);
+                if constexpr (KEYED)
+                    rc_frame1_keyed(key, codes2[(f - kRcSplit) >> 4], e1c, e1n, rows[f + 1 < kCkFrames ? f + 1 : f], lab1, vadd, open_bit, mask_1, PINF);
+                else
+                    rc_frame1(s1, codes2[(f - kRcSplit) >> 4], e1c, e1n, rows[f + 1 < kCkFrames ? f + 1 : f], lab1, vadd, open_bit, mask_1, NINF);
                 e1c = e1n;
             }
             // partly filled words: their first frame to the top, as in a full word
@@ -665,8 +780,16 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
             }
         }
         // ---- walk back over the chunk: pathv[lane f] = position of frame t0+f, relative to wlo ----
+        if constexpr (KEYED) {
+            // the keyed cells shifted their moves in, blanks included: every code to 3 - move
 #pragma unroll
-        for (int g = 0; g < (SPLIT + 7) / 8; ++g) codes[g] = rc_blank_to_uniform(codes[g]);
+            for (int g = 0; g < (SPLIT + 7) / 8; ++g) codes[g] = ~codes[g];
+#pragma unroll
+            for (int g = 0; g < 2; ++g) codes2[g] = ~codes2[g];
+        } else {
+#pragma unroll
+            for (int g = 0; g < (SPLIT + 7) / 8; ++g) codes[g] = rc_blank_to_uniform(codes[g]);
+        }
         int pathv = 0;
         int qq = p - wlo;
         // best_path, best_labels = lab'[best_path], best_scores[t] = lp[t, best_labels[t]] (align.py:105-107), lane f
@@ -692,10 +815,11 @@ __device__ __forceinline__ void backtrace_rc_body(const Lattice *__restrict__ la
 }
 
 // PAR = false: two kernels per launch (ZL: the transcript contains label 0), each skips the other's lattices - as in the forward kernels
-template <int M, bool ZL, bool PAR>
+// KEYED: a third kernel beside <4, false, false> for the lattices flagged kFlagAllNeg, routed the same way
+template <int M, bool ZL, bool PAR, bool KEYED = false>
 __global__ __launch_bounds__(64, kRcMinWaves) void backtrace_rc_kernel(const Lattice *__restrict__ lats, const int32_t *meta, int n_lats)
 {
-    backtrace_rc_body<M, ZL, PAR>(lats, meta, n_lats);
+    backtrace_rc_body<M, ZL, PAR, KEYED>(lats, meta, n_lats);
 }
 // PAR = true (one wavefront per chunk of every chunk-parallel lattice): ONE kernel, the two instances behind a wave-uniform branch -
 // a grid of 430 000 workgroups that only look their lattice up and leave cost the corpus launch 0.1 ms; 53 / 54 registers

@@ -9,6 +9,8 @@ static void rc_serial(const Lattice *lats, int n, int32_t *meta, hipStream_t s)
 {
     hipLaunchKernelGGL((backtrace_rc_kernel<M, false, false>), dim3(n), dim3(64), 0, s, lats, meta, n);
     hipLaunchKernelGGL((backtrace_rc_kernel<M, true, false>), dim3(n), dim3(64), 0, s, lats, meta, n);
+    // max_move 4: the lattices whose log-probs all have the sign bit set take the keyed frames (ka_wave_backtrace.hpp)
+    if constexpr (M == 4) hipLaunchKernelGGL((backtrace_rc_kernel<4, false, false, true>), dim3(n), dim3(64), 0, s, lats, meta, n);
 }
 
 void launch_backtrace_rc_serial(int max_move, const Lattice *lats, int n, int32_t *meta, hipStream_t s)

@@ -294,6 +294,14 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
     for (int k = 0; k < 16; ++k) KA_P(P, k) = NINF;
     if (lane == 0) KA_P(P, 0) = 0.0f;       // virtual state before frame 0 (align.py:57-58)
     float absum = 0.0f;                     // this lane's share of the sum of all |lp| (finiteness check)
+    uint32_t andb = 0x80000000u;            // this lane's share of the AND of all lp bits: the sign bit survives iff none is >= +0.0 (kFlagAllNeg)
+    const auto bits = [](float x) { return __builtin_bit_cast(uint32_t, x); };
+    // blocks: rows past T-1 come back as zeros, and only the LAST block the loop takes in can hold such rows.  So the loop
+    // ANDs one block late (andb takes the block before, `pend` holds this one's: no compare in the loop - a scalar one cost
+    // more in SGPR spills than the ANDs), and the last block's lanes of rows past T-1 (row lane / 16 of the block) are
+    // excused behind the loop.
+    [[maybe_unused]] uint32_t pend = 0xffffffffu;
+    [[maybe_unused]] const auto excused = [&](uint32_t row0) { return row0 + ((uint32_t)lane >> 4) < T ? 0u : 0x80000000u; };
 
     int blk = lane;                         // block of 16 positions this lane currently owns
     uint32_t blo = 0;                       // lo >> 4
@@ -334,6 +342,7 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
 #pragma unroll
         for (int r = 0; r < 4; ++r) e0[r] = lane_of(rblk[0], 16 * r);
         absum = __builtin_fabsf(rblk[0]) + __builtin_fabsf(rblk[1]) + __builtin_fabsf(rblk[2]) + __builtin_fabsf(rblk[3]);
+        andb &= (bits(rblk[0]) & bits(rblk[1]) & bits(rblk[2]) & bits(rblk[3])) | excused(0u);
         blk_off += 1024u;
         __builtin_amdgcn_sched_barrier(0);  // (see the loop)
         block_reload(rblk, blk_off, lp_rsrc);
@@ -350,6 +359,7 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
         lrow[lane] = rows[0];
         e0[0] = first_lane(rows[0]);
         absum = __builtin_fabsf(rows[0]);
+        andb &= bits(rows[0]);
     }
     if constexpr (PAIR) {
 #pragma unroll
@@ -402,7 +412,9 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
                         absum += __builtin_fabsf(rblk[1]);
                         absum += __builtin_fabsf(rblk[2]);
                         absum += __builtin_fabsf(rblk[3]);
-                        asm volatile("" : "+v"(absum));   // (here, not sunk into a later block: that would be a reader behind the request)
+                        andb &= pend;
+                        pend = bits(rblk[0]) & bits(rblk[1]) & bits(rblk[2]) & bits(rblk[3]);
+                        asm volatile("" : "+v"(absum), "+v"(pend));   // (here, not sunk into a later block: that would be a reader behind the request)
                         // the block after it, into the registers just freed (past the lattice's end: zeros, never consumed).
                         // Nothing may move across the request: a reader of the block scheduled behind it makes the compiler
                         // copy the four registers - before the wait, while their load is in flight (tools/lint_inflight.py)
@@ -421,6 +433,7 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
                     lrow[lane] = rn;                 // (LDS operations of a wave execute in order: the reads of row t are done)
                     e0[(dd + 1) & 1] = first_lane(rn);
                     absum += __builtin_fabsf(rn);
+                    andb &= bits(rn);   // (row t+1, or row T-1 again)
                     e0t = e0[dd & 1];
                 }
                 if constexpr (PAIR) frame_scores_pair<M, 3>(P, h1, h2, h3, EP, f32x2{e0t, e0t}, la, next_row, (u & 1) != 0);
@@ -551,6 +564,11 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
     if (__builtin_amdgcn_ballot_w64(abits >= __builtin_bit_cast(uint32_t, 1e30f))) {
         if (lane == 0) atomicOr(&m[2], kFlagExact);
         return;
+    }
+    // every log-prob is -0.0 or below: backtrace_rc may take its arg-max codes from the keyed minimum (ka_wave_backtrace.hpp)
+    if constexpr (BLK) andb &= pend | excused(T & ~3u);   // the last block taken in: rows T & ~3 .. (none of them real when 4 divides T)
+    if (!__builtin_amdgcn_ballot_w64((andb & 0x80000000u) == 0u)) {
+        if (lane == 0) atomicOr(&m[2], kFlagAllNeg);
     }
     float sc[16];
     uint32_t pres2 = 0;

@@ -144,6 +144,83 @@ template <> __global__ __launch_bounds__(64) void kk<133>(float *out, int iters,
     out[blockIdx.x * 64 + threadIdx.x] = a0 + a1 + a2 + a3 + e + (float)w;
 }
 
+// ---- keyed arg-max (one v_min_f64 per candidate gives the maximum AND its index) against the compare form ----
+// independent v_min_f64 with both abs modifiers
+template <> __global__ __launch_bounds__(64) void kk<140>(float *out, int iters, float seed) {
+    double d0 = seed + threadIdx.x, d1 = d0 * 1.1, d2 = d0 * 1.2, d3 = d0 * 1.3, d4 = d0 * 1.4, d5 = d0 * 1.5, d6 = d0 * 1.6, d7 = d0 * 1.7, e = -seed * 3.0;
+    for (int i = 0; i < iters; ++i) {
+        asm volatile(REP8("v_min_f64 %0, |%0|, |%8|\n v_min_f64 %1, |%1|, |%8|\n v_min_f64 %2, |%2|, |%8|\n v_min_f64 %3, |%3|, |%8|\n v_min_f64 %4, |%4|, |%8|\n v_min_f64 %5, |%5|, |%8|\n v_min_f64 %6, |%6|, |%8|\n v_min_f64 %7, |%7|, |%8|\n")
+                     : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3), "+v"(d4), "+v"(d5), "+v"(d6), "+v"(d7) : "v"(e));
+    }
+    out[blockIdx.x * 64 + threadIdx.x] = (float)(d0 + d1 + d2 + d3 + d4 + d5 + d6 + d7);
+}
+// keyed cell: 4 add, 3 v_min_f64, 1 v_lshl_or_b32 (8 instr per cell).  The candidate pairs are v[20:27] (high word: the sum,
+// low word: the candidate's index, written once), the running pair is v[28:29]; the four scores of the next cell are its high
+// word and three earlier ones, kept positive (|s|), so every add is e - |s|.
+template <> __global__ __launch_bounds__(64) void kk<141>(float *out, int iters, float seed) {
+    float a1 = seed * 1.1f + threadIdx.x, a2 = a1 * 1.2f, a3 = a1 * 1.3f, e = -0.5f; uint32_t w = 1;
+    asm volatile("v_mov_b32 v20, 0\n v_mov_b32 v22, 1\n v_mov_b32 v24, 2\n v_mov_b32 v26, 3\n v_mov_b32 v29, %0\n" : : "v"(a1)
+                 : "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29");
+    for (int i = 0; i < iters; ++i) {
+        asm volatile(REP8(
+            "v_sub_f32 v21, %4, v29\n v_sub_f32 v23, %4, %0\n v_sub_f32 v25, %4, %1\n v_sub_f32 v27, %4, %2\n"
+            "v_min_f64 v[28:29], |v[20:21]|, |v[22:23]|\n v_min_f64 v[28:29], v[28:29], |v[24:25]|\n v_min_f64 v[28:29], v[28:29], |v[26:27]|\n"
+            "v_lshl_or_b32 %3, %3, 2, v28\n")
+            : "+v"(a1), "+v"(a2), "+v"(a3), "+v"(w) : "v"(e) : "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29");
+    }
+    float r; asm volatile("v_mov_b32 %0, v29" : "=v"(r) : : "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29");
+    out[blockIdx.x * 64 + threadIdx.x] = a1 + a2 + a3 + r + (float)w;
+}
+// compare cell, the same work as it stands in rc_frame1: 4 add, v_max3, v_max, 3 v_cmp_eq, 2 v_addc (11 vector instr per cell)
+// and the three scalar instructions that combine the masks
+template <> __global__ __launch_bounds__(64) void kk<142>(float *out, int iters, float seed) {
+    float a0 = seed + threadIdx.x, a1 = a0 * 1.1f, a2 = a0 * 1.2f, a3 = a0 * 1.3f, c0, c1, c2, c3, m, e = -0.5f; uint32_t w = 1; uint64_t s0, s1, s2, s3, s4;
+    for (int i = 0; i < iters; ++i) {
+        asm volatile(REP8(
+            "v_add_f32 %4, %0, %9\n v_add_f32 %5, %1, %9\n v_add_f32 %6, %2, %9\n v_add_f32 %7, %3, %9\n"
+            "v_max3_f32 %8, %4, %5, %6\n v_max_f32 %0, %8, %7\n"
+            "v_cmp_eq_f32 %11, %4, %0\n v_cmp_eq_f32 %12, %5, %0\n v_cmp_eq_f32 %13, %6, %0\n"
+            "s_or_b64 %14, %11, %12\n v_addc_co_u32 %10, %15, %10, %10, %14\n s_andn2_b64 %13, %13, %12\n s_or_b64 %13, %13, %11\n"
+            "v_addc_co_u32 %10, %15, %10, %10, %13\n")
+            : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "=&v"(c0), "=&v"(c1), "=&v"(c2), "=&v"(c3), "=&v"(m), "+v"(e), "+v"(w), "=&s"(s0), "=&s"(s1), "=&s"(s2), "=&s"(s3), "=&s"(s4) : : "scc");
+    }
+    out[blockIdx.x * 64 + threadIdx.x] = a0 + a1 + a2 + a3 + e + (float)w;
+}
+// one walk's worth of both, as they would stand inside a frame: the keyed cell with its DPP operands (wave_ror:1 on three adds)
+template <> __global__ __launch_bounds__(64) void kk<143>(float *out, int iters, float seed) {
+    float r1, r2, e = -0.5f; uint32_t w = 1;
+    asm volatile("v_mov_b32 v20, 0\n v_mov_b32 v22, 1\n v_mov_b32 v24, 2\n v_mov_b32 v26, 3\n v_mov_b32 v29, %0\n" : : "v"(seed + threadIdx.x)
+                 : "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29");
+    for (int i = 0; i < iters; ++i) {
+        asm volatile(REP8(
+            "v_sub_f32 v21, %3, v29\n v_mov_b32_dpp %0, v29 wave_ror:1 row_mask:0xf bank_mask:0xf\n"
+            "v_subrev_f32_dpp v23, v29, %3 wave_ror:1 row_mask:0xf bank_mask:0xf\n s_nop 0\n v_mov_b32_dpp %1, %0 wave_ror:1 row_mask:0xf bank_mask:0xf\n"
+            "v_subrev_f32_dpp v25, %0, %3 wave_ror:1 row_mask:0xf bank_mask:0xf\n v_min_f64 v[28:29], |v[20:21]|, |v[22:23]|\n"
+            "v_subrev_f32_dpp v27, %1, %3 wave_ror:1 row_mask:0xf bank_mask:0xf\n"
+            "v_min_f64 v[28:29], v[28:29], |v[24:25]|\n v_min_f64 v[28:29], v[28:29], |v[26:27]|\n"
+            "v_lshl_or_b32 %2, %2, 2, v28\n")
+            : "=&v"(r1), "=&v"(r2), "+v"(w) : "v"(e) : "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29");
+    }
+    float r; asm volatile("v_mov_b32 %0, v29" : "=v"(r) : : "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29");
+    out[blockIdx.x * 64 + threadIdx.x] = r + (float)w;
+}
+// the compare cell with the same DPP operands: rc_frame1 without its gather and band select
+template <> __global__ __launch_bounds__(64) void kk<144>(float *out, int iters, float seed) {
+    float s = seed + threadIdx.x, c0, c1, c2, c3, r1, r2, m, e = -0.5f; uint32_t w = 1; uint64_t s0, s1, s2, s3, s4;
+    for (int i = 0; i < iters; ++i) {
+        asm volatile(REP8(
+            "v_add_f32 %3, %0, %9\n v_mov_b32_dpp %7, %0 wave_ror:1 row_mask:0xf bank_mask:0xf\n"
+            "v_add_f32_dpp %4, %0, %9 wave_ror:1 row_mask:0xf bank_mask:0xf\n s_nop 0\n v_mov_b32_dpp %8, %7 wave_ror:1 row_mask:0xf bank_mask:0xf\n"
+            "v_add_f32_dpp %5, %7, %9 wave_ror:1 row_mask:0xf bank_mask:0xf\n v_max3_f32 %2, %3, %4, %5\n"
+            "v_add_f32_dpp %6, %8, %9 wave_ror:1 row_mask:0xf bank_mask:0xf\n v_max_f32 %0, %2, %6\n"
+            "v_cmp_eq_f32 %10, %3, %0\n v_cmp_eq_f32 %11, %4, %0\n v_cmp_eq_f32 %12, %5, %0\n"
+            "s_or_b64 %13, %10, %11\n v_addc_co_u32 %1, %14, %1, %1, %13\n s_andn2_b64 %12, %12, %11\n s_or_b64 %12, %12, %10\n"
+            "v_addc_co_u32 %1, %14, %1, %1, %12\n")
+            : "+v"(s), "+v"(w), "=&v"(m), "=&v"(c0), "=&v"(c1), "=&v"(c2), "=&v"(c3), "=&v"(r1), "=&v"(r2), "+v"(e), "=&s"(s0), "=&s"(s1), "=&s"(s2), "=&s"(s3), "=&s"(s4) : : "scc");
+    }
+    out[blockIdx.x * 64 + threadIdx.x] = s + e + (float)w;
+}
+
 template <int NAME>
 void run2(const char *name, float *d_out)
 {
@@ -159,6 +236,23 @@ void run2(const char *name, float *d_out)
         if (er != hipSuccess) printf("%s: launch error %s\n", name, hipGetErrorString(er));
         float ms = 0; hipEventElapsedTime(&ms, a, b);
         printf("%-44s waves/SIMD=%d  %.3f ms  %.2f cyc per wave-instr per SIMD (@2.4GHz)\n", name, wps, ms, ms * 1e-3 * 2.4e9 / ((double)iters * 64 * wps));
+    }
+}
+
+// a whole cell per repetition (REP8: eight cells per iteration): cycles per cell and SIMD
+template <int NAME>
+void run_cell(const char *name, float *d_out)
+{
+    const int iters = 4000;
+    hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
+    for (int wps : {2, 8}) {
+        const int blocks = 1024 * wps;
+        hipLaunchKernelGGL(kk<NAME>, dim3(blocks), dim3(64), 0, 0, d_out, 10, 1.0f);
+        hipEventRecord(a);
+        hipLaunchKernelGGL(kk<NAME>, dim3(blocks), dim3(64), 0, 0, d_out, iters, 1.0f);
+        hipEventRecord(b); hipEventSynchronize(b);
+        float ms = 0; hipEventElapsedTime(&ms, a, b);
+        printf("%-72s waves/SIMD=%d  %.3f ms  %.1f cyc per cell per SIMD (@2.4GHz)\n", name, wps, ms, ms * 1e-3 * 2.4e9 / ((double)iters * 8 * wps));
     }
 }
 
@@ -182,9 +276,20 @@ void run(const char *name, int n_per_iter, float *d_out)
     }
 }
 
-int main()
+static void run_keyed(float *d_out)
+{
+    run2<103>("v_min_f32", d_out); run2<123>("v_max3_f32 (3 vgpr)", d_out); run2<100>("v_sub_f32", d_out);
+    run2<140>("v_min_f64 |a|, |b| (indep)", d_out);
+    run_cell<141>("keyed cell: 4 add, 3 min_f64, lshl_or (8 vector)", d_out);
+    run_cell<142>("compare cell: 4 add, max3, max, 3 cmp_eq, 2 addc (11 vector), 3 salu", d_out);
+    run_cell<143>("keyed cell as in rc_frame1: 3 of the adds and 2 moves through DPP (10 vector)", d_out);
+    run_cell<144>("compare cell as in rc_frame1: the same (13 vector), 3 salu", d_out);
+}
+
+int main(int argc, char **argv)
 {
     float *d_out; hipMalloc(&d_out, 8192 * 64 * 4);
+    if (argc > 1 && argv[1][0] == 'k') { run_keyed(d_out); return 0; }   // "keyed": only the rows of the keyed arg-max
     run<0>("v_add_f32 (indep)", 64, d_out);
     run<1>("v_max_f32", 64, d_out);
     run<10>("v_max3_f32", 64, d_out);
@@ -205,6 +310,7 @@ int main()
     run2<115>("v_add3_u32", d_out); run2<116>("v_lshl_add_u32", d_out); run2<118>("v_mad_u32_u24", d_out); run2<120>("v_bitop3_b32", d_out);
     run2<124>("v_mov_b32", d_out);
     run2<130>("v_or_b32", d_out); run2<131>("exec-masked v_or pairs (7 instr/unit, x64 => per unit)", d_out);
+    run_keyed(d_out);
     run2<132>("cell A: addc packing (15 instr per cell, reported per 1/64 iter)", d_out); run2<133>("cell B: exec-masked v_or packing (18 instr per cell)", d_out);
     return 0;
 }
