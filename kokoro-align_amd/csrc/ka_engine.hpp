@@ -1,10 +1,14 @@
-// ka_engine.hpp — what the host translation units (ka_engine.hip, ka_engine_fb.hip, ka_entry_misc.hip) share: the engine
-// object, the error string and its helpers, the device guard, the two growing buffers and the status-to-message table.
+// ka_engine.hpp — what the host translation units (ka_engine.hip, ka_engine_fb.hip, ka_engine_band.hip, ka_entry_misc.hip)
+// share: the engine object, the error string and its helpers, the device guard, the two growing buffers and the
+// status-to-message table; and, for the two drivers that lay their own layout over the engine's buffers (fb_impl in
+// ka_engine_fb.hip, banded_impl in ka_engine_band.hip), the head of their call record and the steps they take alike.
 #pragma once
 #include "../../include/kokoro_align_amd.h"
 #include "ka_launch.hpp"
 #include "ka_plan.hpp"
 
+#include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -162,6 +166,104 @@ inline std::string status_message(int32_t status, const StatusTexts &t)
                                                    : nullptr;
     if (own) return own;
     return status == KA_ERR_BAD_LABEL ? ": label outside [0, V)" : status == KA_ERR_NAN ? ": a log-prob is NaN" : t.other;
+}
+
+// ---- what fb_impl and banded_impl do alike.  What differs stays in each driver: its own checks and their order, its planner,
+// its result records, its rows, launches and copy-out ----
+
+// the head of a call's record: the lattices, as every batch entry point takes them
+struct LatticeArgs {
+    int32_t n;
+    const float *const *log_probs;
+    const int64_t *T;
+    int32_t V;
+    const int64_t *ld;
+    const int32_t *const *labels;
+    const int64_t *S;
+    int32_t beam_size, max_move;
+    int32_t mem;
+    hipStream_t stream;
+    bool host() const { return mem == KA_MEM_HOST; }
+};
+
+// The refusals that precede planning.  `name`: what the call is called in the message; `arrays`: the caller's answer to
+// "are the arrays of my own there" (asked for n > 0 only).
+inline int refuse_call(const ka_engine *e, const LatticeArgs &a, const char *name, bool arrays)
+{
+    if (!e) return fail(KA_ERR_BAD_ARGS, "engine is NULL");
+    if (e->batch.pending) return fail(KA_ERR_BAD_ARGS, "a batch is already enqueued: call ka_batch_finish first");
+    if (a.n < 0 || (a.n > 0 && (!a.log_probs || !a.T || !a.ld || !a.labels || !a.S || !arrays)))
+        return fail(KA_ERR_BAD_ARGS, std::string(name) + ": NULL array argument");
+    if (a.mem != KA_MEM_HOST && a.mem != KA_MEM_DEVICE) return fail(KA_ERR_BAD_ARGS, "mem must be KA_MEM_HOST or KA_MEM_DEVICE");
+    return KA_OK;
+}
+
+// what every *_workspace_bytes export answers 0 to before it plans: a negative count, a NULL table among those it needs
+// (for n > 0), a bad mem
+inline bool countable(int32_t n, int32_t mem, std::initializer_list<const void *> tables)
+{
+    for (const void *t : tables)
+        if (n > 0 && !t) return false;
+    return n >= 0 && (mem == KA_MEM_HOST || mem == KA_MEM_DEVICE);
+}
+
+// The start of a call, with the engine's device current (the DeviceGuard is the driver's own): both buffers large enough, and
+// the workspace is shared with the best-path calls: wait for the refill behind their last tile launch, and what it left clean
+// is clean no more.
+inline int begin_call(ka_engine *e, size_t ws_bytes, size_t pin_bytes, hipStream_t stream)
+{
+    int rc = ensure_ws(e, ws_bytes);
+    if (rc != KA_OK) return rc;
+    rc = ensure_pin(e, pin_bytes);
+    if (rc != KA_OK) return rc;
+    if (e->res.refill_done) KA_HIP(hipStreamWaitEvent(stream, e->res.refill_done, 0));
+    e->clean.invalidate();
+    e->dbg = ka_engine::DebugView();
+    return KA_OK;
+}
+
+// descriptor order: fast-form lattices first, then the generic ones, each in batch order (the order occupancy slots assume).
+// next(fast), asked for lattice 0, 1, ... in turn, is that lattice's descriptor slot.
+struct SlotOrder {
+    int32_t n_fast = 0, k_fast = 0, k_gen = 0;
+    template <class Carve>
+    SlotOrder(const Carve *cv, int32_t n)
+    {
+        for (int32_t i = 0; i < n; ++i) n_fast += cv[i].fast ? 1 : 0;
+    }
+    int32_t next(bool fast) { return fast ? k_fast++ : n_fast + k_gen++; }
+};
+
+// the head of lattice i's descriptor (a BandLattice, or one of the FbLattice family: the same field names), zeroed first; the
+// log-probs and labels are the staged copies (plan::FbCarve) for host buffers
+template <class Desc>
+inline void fill_head(Desc &d, const plan::FbCarve &c, const LatticeArgs &a, int32_t i, char *ws)
+{
+    std::memset(&d, 0, sizeof(d));
+    if (a.host()) {
+        d.lp = reinterpret_cast<const float *>(ws + c.lp);
+        d.labels = reinterpret_cast<const int32_t *>(ws + c.lab);
+        d.ld = a.V;
+    } else {
+        d.lp = a.log_probs[i];
+        d.labels = a.labels[i];
+        d.ld = a.ld[i];
+    }
+    d.T = (int32_t)a.T[i];
+    d.S = (int32_t)a.S[i];
+    d.L = (int32_t)(2 * a.S[i] + 1);
+    d.V = a.V;
+    d.beam = a.beam_size;
+    d.max_move = a.max_move;
+    d.idx = i;
+}
+// ... and, for host buffers, that staging: lattice i's log-probs, packed to V columns, and its labels
+inline int stage_lattice(const plan::FbCarve &c, const LatticeArgs &a, int32_t i, char *ws)
+{
+    KA_HIP(hipMemcpy2DAsync(ws + c.lp, (size_t)a.V * 4, a.log_probs[i], (size_t)a.ld[i] * 4, (size_t)a.V * 4, (size_t)a.T[i], hipMemcpyHostToDevice,
+                            a.stream));
+    if (a.S[i] > 0) KA_HIP(hipMemcpyAsync(ws + c.lab, a.labels[i], (size_t)a.S[i] * 4, hipMemcpyHostToDevice, a.stream));
+    return KA_OK;
 }
 
 }  // namespace host

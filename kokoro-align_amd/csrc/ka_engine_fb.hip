@@ -1,12 +1,12 @@
 // ka_engine_fb.hip — the forward-backward calls of the C ABI: best-path posteriors (ka_posterior.hpp), label occupancy
 // (ka_occupancy.hpp), state posteriors at chosen frames (ka_state_posterior.hpp), expected state durations (ka_duration.hpp),
 // state visit probabilities (ka_visit.hpp), exact boundary-time quantiles (ka_quantile.hpp), alignments sampled from the band
-// posterior (ka_sample.hpp) and the maximum-expected-accuracy alignment (ka_mea.hpp); and, with a driver of its own
-// (banded_impl), the best path over a caller-given band (ka_banded.hpp); and, through fb_impl again, the best-path margins
-// from max-marginals (ka_margin.hpp) and their resumed form (ka_margin_resume.hpp), which are max-plus and no forward-backward.  The first four also run over a caller-given band
-// (ka_ctc_*_banded_*: fb_impl<Call, ka::BandTable>, the same driver on Banded<Desc> descriptors).  Host code only.
-// They use the engine's workspace and pinned buffer, with their own kernels and workspace layout, whatever
-// the engine's mode, and run to the end inside the call: no batch stays in flight.
+// posterior (ka_sample.hpp), the maximum-expected-accuracy alignment (ka_mea.hpp) and the posteriors under the caller's boundary
+// conditions (ka_fb_resume.hpp); and, through the same driver, fb_impl, the best-path margins from max-marginals (ka_margin.hpp)
+// and their resumed form (ka_margin_resume.hpp), which are max-plus and no forward-backward.  The first eight also run over a
+// caller-given band (ka_ctc_*_banded_*: fb_impl<Call, ka::BandTable>, the same driver on Banded<Desc> descriptors).  Host code
+// only.  They use the engine's workspace and pinned buffer, with their own kernels and workspace layout, whatever the engine's
+// mode, and run to the end inside the call: no batch stays in flight.  (The best path over a band: ka_engine_band.hip.)
 #include "ka_engine.hpp"
 
 #include <algorithm>
@@ -25,21 +25,38 @@ using ka::plan::align_up;
 // DurCall and VisitCall) brings what differs: its own arrays and their checks, its planner and its launch (launch<Band>, one
 // for either band), the descriptor fields beyond FbLattice, its own staging (upload: host buffers only; stage: every memory
 // mode), what two statuses mean, and kBandedGranule, the bytes a lattice's Banded<Desc> descriptor is carved as.
-struct FbArgs {
-    int32_t n;
-    const float *const *log_probs;
-    const int64_t *T;
-    int32_t V;
-    const int64_t *ld;
-    const int32_t *const *labels;
-    const int64_t *S;
-    int32_t beam_size, max_move;
+struct FbArgs : LatticeArgs {
     double *log_likelihood;
     int32_t *status;
-    int32_t mem;
-    hipStream_t stream;
     const int32_t *const *band_lo;   // NULL: the reference's diagonal band; else a table per lattice ([T] int32, where `mem` says)
 };
+
+// an optional array's entry: NULL where the array is
+template <class P>
+P at(P const *arr, int32_t i) { return arr ? arr[i] : nullptr; }
+
+// why a lattice's k query frames are refused (StateCall, MarginResumeCall), or nullptr
+const char *bad_frames(const int64_t *frames, int64_t k, int64_t T)
+{
+    if (k > 0 && !frames) return ": NULL frames";
+    for (int64_t j = 0; j < k; ++j) {
+        if (frames[j] < 0 || frames[j] >= T) return ": a frame outside [0, T)";
+        if (j > 0 && frames[j] <= frames[j - 1]) return ": frames not strictly increasing";
+    }
+    return nullptr;
+}
+
+// whether one of a lattice's two output rows lies over one of its two input rows (2S+1 doubles each; any may be NULL): the
+// resumed kernels read an input row again behind the store of an output row
+bool rows_overlap(int64_t S, const double *out0, const double *out1, const double *in0, const double *in1)
+{
+    const size_t row = (size_t)(2 * S + 1) * sizeof(double);
+    auto overlap = [row](const double *x, const double *y) {
+        return x && y && reinterpret_cast<uintptr_t>(x) < reinterpret_cast<uintptr_t>(y) + row &&
+               reinterpret_cast<uintptr_t>(y) < reinterpret_cast<uintptr_t>(x) + row;
+    };
+    return overlap(out0, in0) || overlap(out0, in1) || overlap(out1, in0) || overlap(out1, in1);
+}
 
 struct PostCall {
     using Desc = ka::PostLattice;
@@ -150,12 +167,7 @@ struct StateCall {
     bool arrays() const { return terminal && frames && K && gamma && ld_out && band_lo; }
     const char *bad_lattice(const FbArgs &a, int32_t i) const
     {
-        const int64_t k = K[i];
-        if (k > 0 && !frames[i]) return ": NULL frames";
-        for (int64_t j = 0; j < k; ++j) {
-            if (frames[i][j] < 0 || frames[i][j] >= a.T[i]) return ": a frame outside [0, T)";
-            if (j > 0 && frames[i][j] <= frames[i][j - 1]) return ": frames not strictly increasing";
-        }
+        if (const char *why = bad_frames(frames[i], K[i], a.T[i])) return why;
         const int64_t W = std::max<int64_t>(1, std::min<int64_t>(a.beam_size, 2 * a.S[i] + 1));
         return ld_out[i] < W ? ": ld_out < min(beam_size, 2S+1)" : nullptr;
     }
@@ -531,19 +543,13 @@ struct MarginResumeCall {
     double *const *d_out;
     double *const *e_out;
 
-    template <class P>
-    static P at(P const *arr, int32_t i) { return arr ? arr[i] : nullptr; }
     int64_t k(int32_t i) const { return K ? K[i] : 0; }
     int64_t term(int32_t i) const { return terminal ? terminal[i] : -1; }
     bool arrays() const { return true; }
     const char *bad_lattice(const FbArgs &a, int32_t i) const
     {
         const int64_t n = k(i);
-        if (n > 0 && !at(frames, i)) return ": NULL frames";
-        for (int64_t j = 0; j < n; ++j) {
-            if (frames[i][j] < 0 || frames[i][j] >= a.T[i]) return ": a frame outside [0, T)";
-            if (j > 0 && frames[i][j] <= frames[i][j - 1]) return ": frames not strictly increasing";
-        }
+        if (const char *why = bad_frames(at(frames, i), n, a.T[i])) return why;
         if (n > 0 && (!at(rows, i) || !at(rows_lo, i) || !ld_rows)) return ": state rows asked for without rows, ld_rows or rows_lo";
         const int64_t W = std::max<int64_t>(1, std::min<int64_t>(a.beam_size, 2 * a.S[i] + 1));
         if (n > 0 && ld_rows[i] < W) return ": ld_rows < min(beam_size, 2S+1)";
@@ -551,14 +557,7 @@ struct MarginResumeCall {
         if (term(i) < -1) return ": terminal must be -1 (the path's last state) or a position";
         if (!at(e_in, i) && term(i) == -1 && !at(path, i)) return ": neither e_in, a terminal nor a path says where the lattice ends";
         // (the kernel reads d_in again behind the store of d_out, and e_in behind it)
-        const size_t row = (size_t)(2 * a.S[i] + 1) * sizeof(double);
-        auto overlap = [row](const double *x, const double *y) {
-            return x && y && reinterpret_cast<uintptr_t>(x) < reinterpret_cast<uintptr_t>(y) + row &&
-                   reinterpret_cast<uintptr_t>(y) < reinterpret_cast<uintptr_t>(x) + row;
-        };
-        for (const double *out : {(const double *)at(d_out, i), (const double *)at(e_out, i)})
-            if (overlap(out, at(d_in, i)) || overlap(out, at(e_in, i))) return ": an output row overlaps an input row";
-        return nullptr;
+        return rows_overlap(a.S[i], at(d_out, i), at(e_out, i), at(d_in, i), at(e_in, i)) ? ": an output row overlaps an input row" : nullptr;
     }
     bool buffers(int32_t) const { return true; }
     size_t plan(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host, Carve *cv,
@@ -643,22 +642,14 @@ struct ResumeFbCall {
     double *const *alpha_out;
     double *const *beta_out;
 
-    template <class P>
-    static P at(P const *arr, int32_t i) { return arr ? arr[i] : nullptr; }
     bool arrays() const { return !occupancy || ld_out; }
     const char *bad_lattice(const FbArgs &a, int32_t i) const
     {
         if (at(occupancy, i) && ld_out[i] < a.V) return ": ld_out < V";
         if (at(path_post, i) && !at(path, i)) return ": path_post without path";
         // (the kernel reads alpha_in again behind the store of alpha_out, and beta_in behind it)
-        const size_t row = (size_t)(2 * a.S[i] + 1) * sizeof(double);
-        auto overlap = [row](const double *x, const double *y) {
-            return x && y && reinterpret_cast<uintptr_t>(x) < reinterpret_cast<uintptr_t>(y) + row &&
-                   reinterpret_cast<uintptr_t>(y) < reinterpret_cast<uintptr_t>(x) + row;
-        };
-        for (const double *out : {(const double *)at(alpha_out, i), (const double *)at(beta_out, i)})
-            if (overlap(out, at(alpha_in, i)) || overlap(out, at(beta_in, i))) return ": an output row overlaps an input row";
-        return nullptr;
+        return rows_overlap(a.S[i], at(alpha_out, i), at(beta_out, i), at(alpha_in, i), at(beta_in, i)) ? ": an output row overlaps an input row"
+                                                                                                       : nullptr;
     }
     bool buffers(int32_t) const { return true; }
     static constexpr auto plan = ka::plan::posteriors_resume_workspace;
@@ -726,13 +717,9 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
     static_assert(sizeof(Desc) <= Call::kBandedGranule || !kBanded, "descriptor sizes");
     const int32_t n = a.n, V = a.V;
     const hipStream_t stream = a.stream;
-    const bool host = a.mem == KA_MEM_HOST;
-    if (!e) return fail(KA_ERR_BAD_ARGS, "engine is NULL");
-    if (e->batch.pending) return fail(KA_ERR_BAD_ARGS, "a batch is already enqueued: call ka_batch_finish first");
-    if (n < 0 || (n > 0 && (!a.log_probs || !a.T || !a.ld || !a.labels || !a.S || !call.arrays() || (kBanded && !a.band_lo))))
-        return fail(KA_ERR_BAD_ARGS, std::string(Call::kName) + ": NULL array argument");
-    if (a.mem != KA_MEM_HOST && a.mem != KA_MEM_DEVICE) return fail(KA_ERR_BAD_ARGS, "mem must be KA_MEM_HOST or KA_MEM_DEVICE");
-    if (n == 0) return KA_OK;
+    const bool host = a.host();
+    int rc = refuse_call(e, a, Call::kName, call.arrays() && (!kBanded || a.band_lo));
+    if (rc != KA_OK || n == 0) return rc;
     std::vector<typename Call::Carve> cv(n);
     size_t off_res = 0;
     size_t total = call.plan(n, a.T, a.S, V, a.beam_size, a.max_move, host, cv.data(), &off_res);
@@ -752,51 +739,23 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
     }
     DeviceGuard guard;
     KA_HIP(guard.enter(e->device));
-    int rc = ensure_ws(e, total);
-    if (rc != KA_OK) return rc;
     const size_t desc_bytes = align_up((size_t)n * sizeof(Desc));
-    rc = ensure_pin(e, desc_bytes + (size_t)n * sizeof(ka::PostResult));
-    if (rc != KA_OK) return rc;
-    // the workspace is shared with the best-path calls: wait for the refill behind their last tile launch, and what it left
-    // clean is clean no more
-    if (e->res.refill_done) KA_HIP(hipStreamWaitEvent(stream, e->res.refill_done, 0));
-    e->clean.invalidate();
-    e->dbg = ka_engine::DebugView();
-    // descriptors: fast-form lattices first, then the generic ones, each in batch order (the order occupancy slots assume)
+    if ((rc = begin_call(e, total, desc_bytes + (size_t)n * sizeof(ka::PostResult), stream)) != KA_OK) return rc;
     Desc *h = reinterpret_cast<Desc *>(e->res.pin);
     ka::PostResult *h_res = reinterpret_cast<ka::PostResult *>(e->res.pin + desc_bytes);
-    int32_t n_fast = 0;
-    for (int32_t i = 0; i < n; ++i) n_fast += cv[i].fast ? 1 : 0;
-    int32_t k_fast = 0, k_gen = 0;
+    SlotOrder order(cv.data(), n);
+    const int32_t n_fast = order.n_fast;
     for (int32_t i = 0; i < n; ++i) {
         const auto &c = cv[i];
-        Desc &d = h[c.fast ? k_fast++ : n_fast + k_gen++];
-        std::memset(&d, 0, sizeof(d));
-        if (host) {
-            d.lp = reinterpret_cast<const float *>(e->res.ws + c.lp);
-            d.labels = reinterpret_cast<const int32_t *>(e->res.ws + c.lab);
-            d.ld = V;
-        } else {
-            d.lp = a.log_probs[i];
-            d.labels = a.labels[i];
-            d.ld = a.ld[i];
-        }
-        d.T = (int32_t)a.T[i];
-        d.S = (int32_t)a.S[i];
-        d.L = (int32_t)(2 * a.S[i] + 1);
-        d.V = V;
-        d.beam = a.beam_size;
-        d.max_move = a.max_move;
-        d.idx = i;
+        Desc &d = h[order.next(c.fast)];
+        fill_head(d, c, a, i, e->res.ws);
         call.fill(d, c, a, i, e->res.ws);
         if constexpr (kBanded)
             d.band_lo = host ? reinterpret_cast<const int32_t *>(e->res.ws + off_desc + off_tab[(size_t)i]) : a.band_lo[i];
     }
     if (host)
         for (int32_t i = 0; i < n; ++i) {
-            KA_HIP(hipMemcpy2DAsync(e->res.ws + cv[i].lp, (size_t)V * 4, a.log_probs[i], (size_t)a.ld[i] * 4, (size_t)V * 4, (size_t)a.T[i],
-                                    hipMemcpyHostToDevice, stream));
-            if (a.S[i] > 0) KA_HIP(hipMemcpyAsync(e->res.ws + cv[i].lab, a.labels[i], (size_t)a.S[i] * 4, hipMemcpyHostToDevice, stream));
+            if ((rc = stage_lattice(cv[i], a, i, e->res.ws)) != KA_OK) return rc;
             if ((rc = call.upload(cv[i], a, i, e->res.ws)) != KA_OK) return rc;
             if (kBanded)
                 KA_HIP(hipMemcpyAsync(e->res.ws + off_desc + off_tab[(size_t)i], a.band_lo[i], (size_t)a.T[i] * 4, hipMemcpyHostToDevice, stream));
@@ -829,384 +788,16 @@ int fb_impl(ka_engine *e, const FbArgs &a, const Call &call)
 }
 
 
-// ---- best path over a caller-given band (ka_banded.hpp): its own kernels and workspace layout, whatever the engine's mode.
-// period > 0: the self-steering band (ka_ctc_best_path_tracking): band_lo is then the table the call WRITES, a fourth output.
-// rs: the resumed call (ka_ctc_best_path_resume): the caller's boundary conditions, a last row and an entry cell per lattice.
-// Both: the resumed tracking call (ka_ctc_best_path_tracking_resume), whose end is rs's and which adds lo_0 and the low end of
-// frame T, a second cell beside the entry ----
-struct ResumeArgs {
-    const float *const *init_scores;   // [n] or NULL; an entry may be NULL
-    const int32_t *end;                // [n] host, or NULL: all -1
-    float *const *final_scores;        // [n] or NULL; an entry may be NULL
-    int32_t *entry;                    // [n] host, or NULL
-    const int32_t *first_lo;           // tracking only: [n] host, or NULL: all 0
-    int32_t *next_lo;                  // tracking only: [n] host, or NULL
-    bool walk = false;                 // the determined calls (ka_determined.hpp): the walk from every live cell behind the call
-    int32_t *determined = nullptr;     // ... and its result: [n] host, required
-};
-int banded_impl(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
-                const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move, const int32_t *const *band_lo,
-                int32_t *const *best_path, int32_t *const *best_labels, float *const *best_scores, float *total_score, int32_t *status,
-                int32_t mem, hipStream_t stream, int32_t period = 0, int32_t end_rule = 0, const ResumeArgs *rs = nullptr)
-{
-    using Desc = ka::BandLattice;
-    const bool host = mem == KA_MEM_HOST;
-    const bool tracking = period > 0;
-    if (!e) return fail(KA_ERR_BAD_ARGS, "engine is NULL");
-    if (e->batch.pending) return fail(KA_ERR_BAD_ARGS, "a batch is already enqueued: call ka_batch_finish first");
-    if (n < 0 || (n > 0 && (!log_probs || !T || !ld || !labels || !S || !band_lo || !best_path || !best_labels || !best_scores)))
-        return fail(KA_ERR_BAD_ARGS, "banded best path: NULL array argument");
-    if (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE) return fail(KA_ERR_BAD_ARGS, "mem must be KA_MEM_HOST or KA_MEM_DEVICE");
-    const bool walk = rs && rs->walk;
-    if (walk && !rs->determined) return fail(KA_ERR_BAD_ARGS, "determined best path: determined is NULL");
-    if (n == 0) return KA_OK;
-    std::vector<ka::plan::BandCarve> cv(n);
-    size_t off_meta = 0, off_rows = 0, off_entry = 0, off_det = 0;
-    std::vector<size_t> row_init(rs ? n : 0), row_fin(rs ? n : 0), own_fin(walk ? n : 0);
-    const size_t total = walk ? ka::plan::determined_workspace(n, T, S, V, beam_size, max_move, host, cv.data(), &off_meta, &off_rows, &off_entry,
-                                                               row_init.data(), row_fin.data(), &off_det, own_fin.data(), tracking)
-                         : rs ? ka::plan::resume_workspace(n, T, S, V, beam_size, max_move, host, cv.data(), &off_meta, &off_rows, &off_entry,
-                                                         row_init.data(), row_fin.data(), tracking)
-                            : ka::plan::banded_workspace(n, T, S, V, beam_size, max_move, host, cv.data(), &off_meta, tracking);
-    if (total == 0) return fail(KA_ERR_BAD_ARGS, "banded best path: unsupported T/S/V/beam_size/max_move");
-    if (rs && rs->end)
-        for (int32_t i = 0; i < n; ++i)
-            if (rs->end[i] < -2 || rs->end[i] > 2 * S[i])
-                return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": end must be -1 (highest live), -2 (best live) or a position in [0, 2S+1)");
-    if (rs && rs->first_lo)
-        for (int32_t i = 0; i < n; ++i)
-            if (rs->first_lo[i] < 0 || rs->first_lo[i] > 2 * S[i])
-                return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": first_lo must be a position in [0, 2S+1)");
-    for (int32_t i = 0; i < n; ++i) {
-        if (ld[i] < V) return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": ld < V");
-        if (!log_probs[i] || !band_lo[i] || !best_path[i] || !best_labels[i] || !best_scores[i] || (S[i] > 0 && !labels[i]))
-            return fail(KA_ERR_BAD_ARGS, "lattice " + std::to_string(i) + ": NULL buffer");
-    }
-    DeviceGuard guard;
-    KA_HIP(guard.enter(e->device));
-    int rc = ensure_ws(e, total);
-    if (rc != KA_OK) return rc;
-    const size_t desc_bytes = align_up((size_t)n * sizeof(Desc));
-    const size_t meta_bytes = align_up((size_t)n * sizeof(ka::LatticeMeta));
-    const size_t rows_bytes = rs ? align_up((size_t)n * sizeof(ka::ResumeRows)) : 0;
-    const int32_t cells = rs && tracking ? 2 : 1;   // per lattice behind the rows: the entry, and under tracking the low end of frame T
-    const size_t entry_bytes = rs ? align_up((size_t)n * cells * sizeof(int32_t)) : 0;
-    rc = ensure_pin(e, desc_bytes + meta_bytes + rows_bytes + entry_bytes + (walk ? (size_t)n * sizeof(int32_t) : 0));
-    if (rc != KA_OK) return rc;
-    // the workspace is shared with the best-path calls (see fb_impl)
-    if (e->res.refill_done) KA_HIP(hipStreamWaitEvent(stream, e->res.refill_done, 0));
-    e->clean.invalidate();
-    e->dbg = ka_engine::DebugView();
-    char *ws = e->res.ws;
-    Desc *h = reinterpret_cast<Desc *>(e->res.pin);
-    ka::LatticeMeta *h_meta = reinterpret_cast<ka::LatticeMeta *>(e->res.pin + desc_bytes);
-    ka::ResumeRows *h_rows = reinterpret_cast<ka::ResumeRows *>(e->res.pin + desc_bytes + meta_bytes);
-    int32_t *h_entry = reinterpret_cast<int32_t *>(e->res.pin + desc_bytes + meta_bytes + rows_bytes);
-    int32_t *h_det = reinterpret_cast<int32_t *>(e->res.pin + desc_bytes + meta_bytes + rows_bytes + entry_bytes);
-    int32_t n_fast = 0;
-    for (int32_t i = 0; i < n; ++i) n_fast += cv[i].fast ? 1 : 0;
-    int32_t k_fast = 0, k_gen = 0;
-    for (int32_t i = 0; i < n; ++i) {
-        const ka::plan::BandCarve &c = cv[i];
-        const int32_t slot = c.fast ? k_fast++ : n_fast + k_gen++;
-        Desc &d = h[slot];
-        std::memset(&d, 0, sizeof(d));
-        if (rs) {   // (a staged row is in the workspace; a caller's device row is used where it lies)
-            const float *init = rs->init_scores ? rs->init_scores[i] : nullptr;
-            float *fin = rs->final_scores ? rs->final_scores[i] : nullptr;
-            ka::ResumeRows &r = h_rows[slot];
-            r.init = !init ? nullptr : host ? reinterpret_cast<const float *>(ws + row_init[i]) : init;
-            r.fin = !fin ? nullptr : host ? reinterpret_cast<float *>(ws + row_fin[i]) : fin;
-            // (the walk starts from the last row: where the caller wants none, the staged row or one of the engine's own)
-            if (walk && !fin) r.fin = reinterpret_cast<float *>(ws + (host ? row_fin[i] : own_fin[i]));
-            r.entry = reinterpret_cast<int32_t *>(ws + off_entry) + (size_t)i * cells;
-            r.end = rs->end ? rs->end[i] : -1;
-            r.first_lo = rs->first_lo ? rs->first_lo[i] : 0;
-        }
-        if (host) {
-            d.lp = reinterpret_cast<const float *>(ws + c.lp);
-            d.labels = reinterpret_cast<const int32_t *>(ws + c.lab);
-            d.band_lo = reinterpret_cast<const int32_t *>(ws + c.band);
-            d.path = reinterpret_cast<int32_t *>(ws + c.path);
-            d.lab_out = reinterpret_cast<int32_t *>(ws + c.lab_out);
-            d.sc_out = reinterpret_cast<float *>(ws + c.sc_out);
-            d.ld = V;
-        } else {
-            d.lp = log_probs[i];
-            d.labels = labels[i];
-            d.band_lo = band_lo[i];
-            d.path = best_path[i];
-            d.lab_out = best_labels[i];
-            d.sc_out = best_scores[i];
-            d.ld = ld[i];
-        }
-        d.labx = reinterpret_cast<int32_t *>(ws + c.labx);
-        d.tab = c.fast && !tracking ? reinterpret_cast<int32_t *>(ws + c.tab) : nullptr;
-        d.bp = ws + c.bp;
-        d.col = c.fast ? nullptr : reinterpret_cast<float *>(ws + c.col);
-        d.T = (int32_t)T[i];
-        d.S = (int32_t)S[i];
-        d.L = (int32_t)(2 * S[i] + 1);
-        d.V = V;
-        d.beam = beam_size;
-        d.max_move = max_move;
-        d.labx_len = c.labx_len;
-        d.W = c.W;
-        d.tab_len = c.tab_len;
-        d.idx = i;
-    }
-    if (host)
-        for (int32_t i = 0; i < n; ++i) {
-            KA_HIP(hipMemcpy2DAsync(ws + cv[i].lp, (size_t)V * 4, log_probs[i], (size_t)ld[i] * 4, (size_t)V * 4, (size_t)T[i], hipMemcpyHostToDevice,
-                                    stream));
-            if (S[i] > 0) KA_HIP(hipMemcpyAsync(ws + cv[i].lab, labels[i], (size_t)S[i] * 4, hipMemcpyHostToDevice, stream));
-            if (!tracking) KA_HIP(hipMemcpyAsync(ws + cv[i].band, band_lo[i], (size_t)T[i] * 4, hipMemcpyHostToDevice, stream));
-            if (rs && rs->init_scores && rs->init_scores[i])
-                KA_HIP(hipMemcpyAsync(ws + row_init[i], rs->init_scores[i], (size_t)(2 * S[i] + 1) * 4, hipMemcpyHostToDevice, stream));
-        }
-    Desc *d_lats = reinterpret_cast<Desc *>(ws);
-    int32_t *d_meta = reinterpret_cast<int32_t *>(ws + off_meta);
-    KA_HIP(hipMemcpyAsync(d_lats, h, (size_t)n * sizeof(Desc), hipMemcpyHostToDevice, stream));
-    KA_HIP(hipMemsetAsync(d_meta, 0, (size_t)n * sizeof(ka::LatticeMeta), stream));
-    if (rs) {
-        ka::ResumeRows *d_rows = reinterpret_cast<ka::ResumeRows *>(ws + off_rows);
-        KA_HIP(hipMemcpyAsync(d_rows, h_rows, (size_t)n * sizeof(ka::ResumeRows), hipMemcpyHostToDevice, stream));
-        if (tracking) ka::launch_best_path_tracking_resume(d_lats, d_rows, n_fast, n - n_fast, max_move, period, d_meta, stream);
-        else ka::launch_best_path_resume(d_lats, d_rows, n_fast, n - n_fast, max_move, d_meta, stream);
-        if (walk) ka::launch_determined(d_lats, d_rows, n_fast, n - n_fast, d_meta, reinterpret_cast<int32_t *>(ws + off_det), stream);
-    } else if (tracking) ka::launch_best_path_tracking(d_lats, n_fast, n - n_fast, max_move, period, end_rule, d_meta, stream);
-    else ka::launch_best_path_banded(d_lats, n_fast, n - n_fast, max_move, d_meta, stream);
-    KA_HIP(hipGetLastError());
-    KA_HIP(hipMemcpyAsync(h_meta, d_meta, (size_t)n * sizeof(ka::LatticeMeta), hipMemcpyDeviceToHost, stream));
-    if (rs) KA_HIP(hipMemcpyAsync(h_entry, ws + off_entry, (size_t)n * cells * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    if (walk) KA_HIP(hipMemcpyAsync(h_det, ws + off_det, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    KA_HIP(hipStreamSynchronize(stream));
-    if (host) {   // only what succeeded is copied out: a failed lattice's outputs stay as the caller left them
-        for (int32_t i = 0; i < n; ++i) {
-            // (but the last row of every lattice: all dead where the forward pass did not run, or found a NaN or a bad label)
-            if (rs && rs->final_scores && rs->final_scores[i])
-                KA_HIP(hipMemcpyAsync(rs->final_scores[i], ws + row_fin[i], (size_t)(2 * S[i] + 1) * 4, hipMemcpyDeviceToHost, stream));
-            const size_t bytes = (size_t)T[i] * 4;
-            // (and the table of a resumed tracking call whose forward pass ran to its end: a dead end cell leaves it valid)
-            if (rs && tracking && h_meta[i].status == KA_ERR_EMPTY_BEAM)
-                KA_HIP(hipMemcpyAsync(const_cast<int32_t *>(band_lo[i]), ws + cv[i].band, bytes, hipMemcpyDeviceToHost, stream));
-            if (h_meta[i].status != KA_OK) continue;
-            KA_HIP(hipMemcpyAsync(best_path[i], ws + cv[i].path, bytes, hipMemcpyDeviceToHost, stream));
-            KA_HIP(hipMemcpyAsync(best_labels[i], ws + cv[i].lab_out, bytes, hipMemcpyDeviceToHost, stream));
-            KA_HIP(hipMemcpyAsync(best_scores[i], ws + cv[i].sc_out, bytes, hipMemcpyDeviceToHost, stream));
-            if (tracking) KA_HIP(hipMemcpyAsync(const_cast<int32_t *>(band_lo[i]), ws + cv[i].band, bytes, hipMemcpyDeviceToHost, stream));
-        }
-        KA_HIP(hipStreamSynchronize(stream));
-    }
-    int first_bad = KA_OK;
-    for (int32_t i = 0; i < n; ++i) {
-        const int32_t st = h_meta[i].status;
-        if (status) status[i] = st;
-        if (total_score) total_score[i] = h_meta[i].score;
-        if (rs && rs->entry) rs->entry[i] = st == KA_OK ? h_entry[(size_t)i * cells] : -1;
-        if (rs && tracking && rs->next_lo) rs->next_lo[i] = st == KA_OK || st == KA_ERR_EMPTY_BEAM ? h_entry[(size_t)i * cells + 1] : -1;
-        if (walk) rs->determined[i] = h_det[i];
-        if (st != KA_OK && first_bad == KA_OK) {
-            first_bad = st;
-            g_err = "lattice " + std::to_string(i) +
-                    status_message(st, {rs ? ": no live state in the last frame, or the end cell is not live" : ": no live state in the last frame",
-                                        nullptr, nullptr,
-                                        rs && tracking ? ": init_scores must hold no +inf"
-                                        : rs           ? ": band_lo must hold non-decreasing values in [0, 2S+1) and init_scores no +inf"
-                                                       : ": band_lo must hold non-decreasing values in [0, 2S+1)",
-                                        nullptr});
-        }
-    }
-    return first_bad;
-}
-
-// the two arguments ka_ctc_best_path_tracking adds: checked before anything is launched
-int tracking_args(int32_t period, int32_t end_rule)
-{
-    if (period < 4 || period > 65536 || period % 4 != 0) return fail(KA_ERR_BAD_ARGS, "tracking best path: period must be a multiple of 4 in [4, 65536]");
-    if (end_rule != 0 && end_rule != 1) return fail(KA_ERR_BAD_ARGS, "tracking best path: end_rule must be 0 (highest live) or 1 (best live)");
-    return KA_OK;
-}
-
 }  // namespace
 
 extern "C" {
-
-int ka_ctc_best_path_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
-                                      const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
-                                      const int32_t *const *band_lo, int32_t *const *best_path, int32_t *const *best_labels,
-                                      float *const *best_scores, float *total_score, int32_t *status, int32_t mem, void *stream)
-{
-    return banded_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, band_lo, best_path, best_labels, best_scores, total_score,
-                       status, mem, (hipStream_t)stream);
-}
-
-int ka_ctc_best_path_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
-                                int32_t beam_size, int32_t max_move, const int32_t *band_lo, int32_t *best_path, int32_t *best_labels,
-                                float *best_scores, float *total_score, int32_t mem, void *stream)
-{
-    return banded_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo, &best_path, &best_labels, &best_scores,
-                       total_score, nullptr, mem, (hipStream_t)stream);
-}
-
-int ka_ctc_best_path_tracking_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
-                                        const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move, int32_t period,
-                                        int32_t end_rule, int32_t *const *best_path, int32_t *const *best_labels, float *const *best_scores,
-                                        int32_t *const *band_lo_out, float *total_score, int32_t *status, int32_t mem, void *stream)
-{
-    const int rc = tracking_args(period, end_rule);
-    if (rc != KA_OK) return rc;
-    return banded_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, band_lo_out, best_path, best_labels, best_scores, total_score,
-                       status, mem, (hipStream_t)stream, period, end_rule);
-}
-
-int ka_ctc_best_path_tracking_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
-                                  int32_t beam_size, int32_t max_move, int32_t period, int32_t end_rule, int32_t *best_path,
-                                  int32_t *best_labels, float *best_scores, int32_t *band_lo_out, float *total_score, int32_t mem, void *stream)
-{
-    const int rc = tracking_args(period, end_rule);
-    if (rc != KA_OK) return rc;
-    return banded_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo_out, &best_path, &best_labels, &best_scores,
-                       total_score, nullptr, mem, (hipStream_t)stream, period, end_rule);
-}
-
-int ka_ctc_best_path_resume_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
-                                      const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
-                                      const int32_t *const *band_lo, const float *const *init_scores, const int32_t *end,
-                                      int32_t *const *best_path, int32_t *const *best_labels, float *const *best_scores,
-                                      float *const *final_scores, int32_t *entry, float *total_score, int32_t *status, int32_t mem, void *stream)
-{
-    const ResumeArgs rs{init_scores, end, final_scores, entry, nullptr, nullptr};
-    return banded_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, band_lo, best_path, best_labels, best_scores, total_score,
-                       status, mem, (hipStream_t)stream, 0, 0, &rs);
-}
-
-int ka_ctc_best_path_resume_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
-                                int32_t beam_size, int32_t max_move, const int32_t *band_lo, const float *init_scores, int32_t end,
-                                int32_t *best_path, int32_t *best_labels, float *best_scores, float *final_scores, int32_t *entry,
-                                float *total_score, int32_t mem, void *stream)
-{
-    const ResumeArgs rs{&init_scores, &end, &final_scores, entry, nullptr, nullptr};
-    return banded_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo, &best_path, &best_labels, &best_scores,
-                       total_score, nullptr, mem, (hipStream_t)stream, 0, 0, &rs);
-}
-
-size_t ka_resume_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
-{
-    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
-    return ka::plan::resume_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-}
-
-int ka_ctc_best_path_tracking_resume_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
-                                               const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
-                                               int32_t max_move, int32_t period, const int32_t *first_lo, const float *const *init_scores,
-                                               const int32_t *end, int32_t *const *best_path, int32_t *const *best_labels,
-                                               float *const *best_scores, int32_t *const *band_lo_out, float *const *final_scores,
-                                               int32_t *entry, int32_t *next_lo, float *total_score, int32_t *status, int32_t mem, void *stream)
-{
-    const int rc = tracking_args(period, 0);
-    if (rc != KA_OK) return rc;
-    const ResumeArgs rs{init_scores, end, final_scores, entry, first_lo, next_lo};
-    return banded_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, band_lo_out, best_path, best_labels, best_scores, total_score,
-                       status, mem, (hipStream_t)stream, period, 0, &rs);
-}
-
-int ka_ctc_best_path_tracking_resume_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
-                                         int32_t beam_size, int32_t max_move, int32_t period, int32_t first_lo, const float *init_scores,
-                                         int32_t end, int32_t *best_path, int32_t *best_labels, float *best_scores, int32_t *band_lo_out,
-                                         float *final_scores, int32_t *entry, int32_t *next_lo, float *total_score, int32_t mem, void *stream)
-{
-    const int rc = tracking_args(period, 0);
-    if (rc != KA_OK) return rc;
-    const ResumeArgs rs{&init_scores, &end, &final_scores, entry, &first_lo, next_lo};
-    return banded_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo_out, &best_path, &best_labels, &best_scores,
-                       total_score, nullptr, mem, (hipStream_t)stream, period, 0, &rs);
-}
-
-size_t ka_tracking_resume_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
-                                          int32_t mem)
-{
-    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
-    return ka::plan::resume_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                      true);
-}
-
-int ka_ctc_best_path_determined_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
-                                          const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
-                                          const int32_t *const *band_lo, const float *const *init_scores, const int32_t *end,
-                                          int32_t *const *best_path, int32_t *const *best_labels, float *const *best_scores,
-                                          float *const *final_scores, int32_t *entry, int32_t *determined, float *total_score, int32_t *status,
-                                          int32_t mem, void *stream)
-{
-    const ResumeArgs rs{init_scores, end, final_scores, entry, nullptr, nullptr, true, determined};
-    return banded_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, band_lo, best_path, best_labels, best_scores, total_score,
-                       status, mem, (hipStream_t)stream, 0, 0, &rs);
-}
-
-int ka_ctc_best_path_determined_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
-                                    int32_t beam_size, int32_t max_move, const int32_t *band_lo, const float *init_scores, int32_t end,
-                                    int32_t *best_path, int32_t *best_labels, float *best_scores, float *final_scores, int32_t *entry,
-                                    int32_t *determined, float *total_score, int32_t mem, void *stream)
-{
-    const ResumeArgs rs{&init_scores, &end, &final_scores, entry, nullptr, nullptr, true, determined};
-    return banded_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo, &best_path, &best_labels, &best_scores,
-                       total_score, nullptr, mem, (hipStream_t)stream, 0, 0, &rs);
-}
-
-int ka_ctc_best_path_tracking_determined_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
-                                                   const int64_t *ld, const int32_t *const *labels, const int64_t *S, int32_t beam_size,
-                                                   int32_t max_move, int32_t period, const int32_t *first_lo, const float *const *init_scores,
-                                                   const int32_t *end, int32_t *const *best_path, int32_t *const *best_labels,
-                                                   float *const *best_scores, int32_t *const *band_lo_out, float *const *final_scores,
-                                                   int32_t *entry, int32_t *next_lo, int32_t *determined, float *total_score, int32_t *status,
-                                                   int32_t mem, void *stream)
-{
-    const int rc = tracking_args(period, 0);
-    if (rc != KA_OK) return rc;
-    const ResumeArgs rs{init_scores, end, final_scores, entry, first_lo, next_lo, true, determined};
-    return banded_impl(e, n, log_probs, T, V, ld, labels, S, beam_size, max_move, band_lo_out, best_path, best_labels, best_scores, total_score,
-                       status, mem, (hipStream_t)stream, period, 0, &rs);
-}
-
-int ka_ctc_best_path_tracking_determined_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels,
-                                             int64_t S, int32_t beam_size, int32_t max_move, int32_t period, int32_t first_lo,
-                                             const float *init_scores, int32_t end, int32_t *best_path, int32_t *best_labels,
-                                             float *best_scores, int32_t *band_lo_out, float *final_scores, int32_t *entry, int32_t *next_lo,
-                                             int32_t *determined, float *total_score, int32_t mem, void *stream)
-{
-    const int rc = tracking_args(period, 0);
-    if (rc != KA_OK) return rc;
-    const ResumeArgs rs{&init_scores, &end, &final_scores, entry, &first_lo, next_lo, true, determined};
-    return banded_impl(e, 1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, &band_lo_out, &best_path, &best_labels, &best_scores,
-                       total_score, nullptr, mem, (hipStream_t)stream, period, 0, &rs);
-}
-
-size_t ka_determined_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem,
-                                     int32_t tracking)
-{
-    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
-    return ka::plan::determined_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                          nullptr, nullptr, tracking != 0);
-}
-
-size_t ka_tracking_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
-{
-    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
-    return ka::plan::banded_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr, true);
-}
-
-size_t ka_banded_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
-{
-    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
-    return ka::plan::banded_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
-}
 
 int ka_ctc_path_posteriors_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
                                      const int32_t *const *labels, const int64_t *S, int32_t beam_size, int32_t max_move,
                                      const int32_t *const *best_path, float *const *posteriors, double *log_likelihood, int32_t *status,
                                      int32_t mem, void *stream)
 {
-    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+    return fb_impl(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status},
                    PostCall{best_path, posteriors});
 }
 
@@ -1214,13 +805,13 @@ int ka_ctc_path_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T, 
                                int32_t beam_size, int32_t max_move, const int32_t *best_path, float *posteriors, double *log_likelihood,
                                int32_t mem, void *stream)
 {
-    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+    return fb_impl(e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr},
                    PostCall{&best_path, &posteriors});
 }
 
 size_t ka_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
 {
-    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    if (!countable(n, mem, {T, S})) return 0;
     return ka::plan::posterior_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
@@ -1229,7 +820,7 @@ int ka_ctc_label_posteriors_batch_f32(ka_engine *e, int32_t n, const float *cons
                                       const int64_t *terminal, float *const *occupancy, const int64_t *ld_out, double *log_likelihood,
                                       int32_t *status, int32_t mem, void *stream)
 {
-    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+    return fb_impl(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status},
                    OccCall{terminal, occupancy, ld_out});
 }
 
@@ -1237,14 +828,14 @@ int ka_ctc_label_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T,
                                 int32_t beam_size, int32_t max_move, int64_t terminal, float *occupancy, int64_t ld_out,
                                 double *log_likelihood, int32_t mem, void *stream)
 {
-    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+    return fb_impl(e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr},
                    OccCall{&terminal, &occupancy, &ld_out});
 }
 
 size_t ka_label_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
                                           int32_t mem)
 {
-    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    if (!countable(n, mem, {T, S})) return 0;
     return ka::plan::label_posterior_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
@@ -1254,7 +845,7 @@ int ka_ctc_state_posteriors_batch_f32(ka_engine *e, int32_t n, const float *cons
                                       const int64_t *ld_out, int64_t *const *band_lo, double *log_likelihood, int32_t *status, int32_t mem,
                                       void *stream)
 {
-    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+    return fb_impl(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status},
                    StateCall{terminal, frames, K, gamma, ld_out, band_lo});
 }
 
@@ -1262,14 +853,14 @@ int ka_ctc_state_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T,
                                 int32_t beam_size, int32_t max_move, int64_t terminal, const int64_t *frames, int64_t K, float *gamma,
                                 int64_t ld_out, int64_t *band_lo, double *log_likelihood, int32_t mem, void *stream)
 {
-    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+    return fb_impl(e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr},
                    StateCall{&terminal, &frames, &K, &gamma, &ld_out, &band_lo});
 }
 
 size_t ka_state_posterior_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t V, int32_t beam_size,
                                           int32_t max_move, int32_t mem)
 {
-    if (n < 0 || (n > 0 && (!T || !S || !K)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    if (!countable(n, mem, {T, S, K})) return 0;
     return ka::plan::state_posterior_workspace(n, T, S, K, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
@@ -1278,7 +869,7 @@ int ka_ctc_state_durations_batch_f32(ka_engine *e, int32_t n, const float *const
                                      const int64_t *terminal, double *const *duration, double *const *time_sum, double *log_likelihood,
                                      int32_t *status, int32_t mem, void *stream)
 {
-    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+    return fb_impl(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status},
                    DurCall{terminal, duration, time_sum});
 }
 
@@ -1286,14 +877,14 @@ int ka_ctc_state_durations_f32(ka_engine *e, const float *log_probs, int64_t T, 
                                int32_t beam_size, int32_t max_move, int64_t terminal, double *duration, double *time_sum,
                                double *log_likelihood, int32_t mem, void *stream)
 {
-    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+    return fb_impl(e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr},
                    DurCall{&terminal, &duration, &time_sum});
 }
 
 size_t ka_state_duration_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
                                          int32_t mem)
 {
-    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    if (!countable(n, mem, {T, S})) return 0;
     return ka::plan::pair_sum_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
@@ -1304,7 +895,7 @@ int ka_ctc_path_posteriors_banded_batch_f32(ka_engine *e, int32_t n, const float
                                             float *const *posteriors, double *log_likelihood, int32_t *status, int32_t mem, void *stream)
 {
     if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "posteriors: NULL band_lo");
-    return fb_impl<PostCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
+    return fb_impl<PostCall, ka::BandTable>(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status, band_lo},
                                    PostCall{best_path, posteriors});
 }
 
@@ -1313,7 +904,7 @@ int ka_ctc_path_posteriors_banded_f32(ka_engine *e, const float *log_probs, int6
                                       float *posteriors, double *log_likelihood, int32_t mem, void *stream)
 {
     return fb_impl<PostCall, ka::BandTable>(
-        e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo},
+        e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr, &band_lo},
         PostCall{&best_path, &posteriors});
 }
 
@@ -1324,7 +915,7 @@ int ka_ctc_label_posteriors_banded_batch_f32(ka_engine *e, int32_t n, const floa
                                              int32_t mem, void *stream)
 {
     if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "label posteriors: NULL band_lo");
-    return fb_impl<OccCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
+    return fb_impl<OccCall, ka::BandTable>(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status, band_lo},
                                   OccCall{terminal, occupancy, ld_out});
 }
 
@@ -1333,7 +924,7 @@ int ka_ctc_label_posteriors_banded_f32(ka_engine *e, const float *log_probs, int
                                        int64_t ld_out, double *log_likelihood, int32_t mem, void *stream)
 {
     return fb_impl<OccCall, ka::BandTable>(
-        e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo},
+        e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr, &band_lo},
         OccCall{&terminal, &occupancy, &ld_out});
 }
 
@@ -1344,7 +935,7 @@ int ka_ctc_state_posteriors_banded_batch_f32(ka_engine *e, int32_t n, const floa
                                              int64_t *const *band_lo, double *log_likelihood, int32_t *status, int32_t mem, void *stream)
 {
     if (n > 0 && !band_table) return fail(KA_ERR_BAD_ARGS, "state posteriors: NULL band table");
-    return fb_impl<StateCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_table},
+    return fb_impl<StateCall, ka::BandTable>(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status, band_table},
                                     StateCall{terminal, frames, K, gamma, ld_out, band_lo});
 }
 
@@ -1354,7 +945,7 @@ int ka_ctc_state_posteriors_banded_f32(ka_engine *e, const float *log_probs, int
                                        void *stream)
 {
     return fb_impl<StateCall, ka::BandTable>(
-        e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_table},
+        e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr, &band_table},
         StateCall{&terminal, &frames, &K, &gamma, &ld_out, &band_lo});
 }
 
@@ -1365,7 +956,7 @@ int ka_ctc_state_durations_banded_batch_f32(ka_engine *e, int32_t n, const float
                                             int32_t mem, void *stream)
 {
     if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "state durations: NULL band_lo");
-    return fb_impl<DurCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
+    return fb_impl<DurCall, ka::BandTable>(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status, band_lo},
                                   DurCall{terminal, duration, time_sum});
 }
 
@@ -1374,7 +965,7 @@ int ka_ctc_state_durations_banded_f32(ka_engine *e, const float *log_probs, int6
                                       double *time_sum, double *log_likelihood, int32_t mem, void *stream)
 {
     return fb_impl<DurCall, ka::BandTable>(
-        e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo},
+        e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr, &band_lo},
         DurCall{&terminal, &duration, &time_sum});
 }
 
@@ -1386,7 +977,7 @@ int ka_ctc_posteriors_resume_batch_f32(ka_engine *e, int32_t n, const float *con
                                        int32_t *status, int32_t mem, void *stream)
 {
     if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "posteriors resume: NULL band_lo");
-    return fb_impl<ResumeFbCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo},
+    return fb_impl<ResumeFbCall, ka::BandTable>(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status, band_lo},
                                                 ResumeFbCall{alpha_in, beta_in, terminal, path, occupancy, ld_out, path_post, alpha_out, beta_out});
 }
 
@@ -1396,14 +987,14 @@ int ka_ctc_posteriors_resume_f32(ka_engine *e, const float *log_probs, int64_t T
                                  double *beta_out, double *log_likelihood, int32_t mem, void *stream)
 {
     return fb_impl<ResumeFbCall, ka::BandTable>(
-        e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo},
+        e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr, &band_lo},
         ResumeFbCall{&alpha_in, &beta_in, &terminal, &path, &occupancy, &ld_out, &path_post, &alpha_out, &beta_out});
 }
 
 size_t ka_posteriors_resume_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move,
                                             int32_t mem)
 {
-    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    if (!countable(n, mem, {T, S})) return 0;
     const size_t own = ka::plan::posteriors_resume_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
     const size_t tab = ka::plan::band_table_workspace(n, T, mem == KA_MEM_HOST, nullptr, ka::kBandedResumeFbDescBytes);
     return own && tab ? align_up(own) + tab : 0;
@@ -1411,13 +1002,13 @@ size_t ka_posteriors_resume_workspace_bytes(int32_t n, const int64_t *T, const i
 
 size_t ka_band_table_workspace_bytes(int32_t n, const int64_t *T, int32_t mem)
 {
-    if (n < 0 || (n > 0 && !T) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    if (!countable(n, mem, {T})) return 0;
     return ka::plan::band_table_workspace(n, T, mem == KA_MEM_HOST, nullptr);
 }
 
 size_t ka_boundary_quantile_band_table_workspace_bytes(int32_t n, const int64_t *T, int32_t mem)
 {
-    if (n < 0 || (n > 0 && !T) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    if (!countable(n, mem, {T})) return 0;
     return ka::plan::band_table_workspace(n, T, mem == KA_MEM_HOST, nullptr, ka::kBandedQuantDescBytes);
 }
 
@@ -1426,7 +1017,7 @@ int ka_ctc_state_visits_batch_f32(ka_engine *e, int32_t n, const float *const *l
                                   const int64_t *terminal, double *const *visit, double *const *exit_time, double *log_likelihood,
                                   int32_t *status, int32_t mem, void *stream)
 {
-    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+    return fb_impl(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status},
                    VisitCall{terminal, visit, exit_time});
 }
 
@@ -1434,13 +1025,13 @@ int ka_ctc_state_visits_f32(ka_engine *e, const float *log_probs, int64_t T, int
                             int32_t beam_size, int32_t max_move, int64_t terminal, double *visit, double *exit_time, double *log_likelihood,
                             int32_t mem, void *stream)
 {
-    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+    return fb_impl(e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr},
                    VisitCall{&terminal, &visit, &exit_time});
 }
 
 size_t ka_state_visit_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
 {
-    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    if (!countable(n, mem, {T, S})) return 0;
     return ka::plan::pair_sum_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
@@ -1452,7 +1043,7 @@ int ka_ctc_boundary_quantiles_batch_f32(ka_engine *e, int32_t n, const float *co
 {
     QuantCall call{terminal, cuts, K, quantile, ld_q, M, {}, {}};
     if (const char *why = quant_thresholds(levels, M, call.thr)) return fail(KA_ERR_BAD_ARGS, why);
-    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream}, call);
+    return fb_impl(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status}, call);
 }
 
 int ka_ctc_boundary_quantiles_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
@@ -1461,13 +1052,13 @@ int ka_ctc_boundary_quantiles_f32(ka_engine *e, const float *log_probs, int64_t 
 {
     QuantCall call{&terminal, &cuts, &K, &quantile, &ld_q, M, {}, {}};
     if (const char *why = quant_thresholds(levels, M, call.thr)) return fail(KA_ERR_BAD_ARGS, why);
-    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream}, call);
+    return fb_impl(e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr}, call);
 }
 
 size_t ka_boundary_quantile_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t M, int32_t V,
                                             int32_t beam_size, int32_t max_move, int32_t mem)
 {
-    if (n < 0 || (n > 0 && (!T || !S || !K)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    if (!countable(n, mem, {T, S, K})) return 0;
     return ka::plan::boundary_quantile_workspace(n, T, S, K, M, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
@@ -1476,7 +1067,7 @@ int ka_ctc_sample_paths_batch_f32(ka_engine *e, int32_t n, const float *const *l
                                   const int64_t *terminal, const int32_t *n_samples, const uint64_t *seed, int32_t *const *paths,
                                   const int64_t *ld_paths, double *log_likelihood, int32_t *status, int32_t mem, void *stream)
 {
-    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+    return fb_impl(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status},
                    SampleCall{terminal, n_samples, seed, paths, ld_paths});
 }
 
@@ -1484,14 +1075,14 @@ int ka_ctc_sample_paths_f32(ka_engine *e, const float *log_probs, int64_t T, int
                             int32_t beam_size, int32_t max_move, int64_t terminal, int32_t n_samples, uint64_t seed, int32_t *paths,
                             int64_t ld_paths, double *log_likelihood, int32_t mem, void *stream)
 {
-    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+    return fb_impl(e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr},
                    SampleCall{&terminal, &n_samples, &seed, &paths, &ld_paths});
 }
 
 size_t ka_sample_paths_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int32_t *n_samples, int32_t V, int32_t beam_size,
                                        int32_t max_move, int32_t mem)
 {
-    if (n < 0 || (n > 0 && (!T || !S || !n_samples)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    if (!countable(n, mem, {T, S, n_samples})) return 0;
     for (int32_t i = 0; i < n; ++i)
         if (n_samples[i] < 1 || n_samples[i] > ka::kMaxSamples) return 0;
     return ka::plan::sample_paths_workspace(n, T, S, n_samples, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
@@ -1502,7 +1093,7 @@ int ka_ctc_mea_path_batch_f32(ka_engine *e, int32_t n, const float *const *log_p
                               int32_t *const *path, double *expected_accuracy, double *log_likelihood, int32_t *status, int32_t mem,
                               void *stream)
 {
-    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream},
+    return fb_impl(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status},
                    MeaCall{terminal, path, expected_accuracy});
 }
 
@@ -1510,13 +1101,13 @@ int ka_ctc_mea_path_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t
                         int32_t beam_size, int32_t max_move, int64_t terminal, int32_t *path, double *expected_accuracy,
                         double *log_likelihood, int32_t mem, void *stream)
 {
-    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream},
+    return fb_impl(e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr},
                    MeaCall{&terminal, &path, expected_accuracy});
 }
 
 size_t ka_mea_path_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
 {
-    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    if (!countable(n, mem, {T, S})) return 0;
     return ka::plan::mea_path_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
@@ -1527,14 +1118,14 @@ int ka_ctc_state_visits_banded_batch_f32(ka_engine *e, int32_t n, const float *c
                                          double *const *exit_time, double *log_likelihood, int32_t *status, int32_t mem, void *stream)
 {
     if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "state visits: NULL band_lo");
-    return fb_impl<VisitCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo}, VisitCall{terminal, visit, exit_time});
+    return fb_impl<VisitCall, ka::BandTable>(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status, band_lo}, VisitCall{terminal, visit, exit_time});
 }
 
 int ka_ctc_state_visits_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
                                    int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal, double *visit,
                                    double *exit_time, double *log_likelihood, int32_t mem, void *stream)
 {
-    return fb_impl<VisitCall, ka::BandTable>(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo}, VisitCall{&terminal, &visit, &exit_time});
+    return fb_impl<VisitCall, ka::BandTable>(e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr, &band_lo}, VisitCall{&terminal, &visit, &exit_time});
 }
 
 int ka_ctc_boundary_quantiles_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V,
@@ -1547,7 +1138,7 @@ int ka_ctc_boundary_quantiles_banded_batch_f32(ka_engine *e, int32_t n, const fl
     QuantCall call{terminal, cuts, K, quantile, ld_q, M, {}, {}};
     if (const char *why = quant_thresholds(levels, M, call.thr)) return fail(KA_ERR_BAD_ARGS, why);
     if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "boundary quantiles: NULL band_lo");
-    return fb_impl<QuantCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo}, call);
+    return fb_impl<QuantCall, ka::BandTable>(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status, band_lo}, call);
 }
 
 int ka_ctc_boundary_quantiles_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels,
@@ -1557,7 +1148,7 @@ int ka_ctc_boundary_quantiles_banded_f32(ka_engine *e, const float *log_probs, i
 {
     QuantCall call{&terminal, &cuts, &K, &quantile, &ld_q, M, {}, {}};
     if (const char *why = quant_thresholds(levels, M, call.thr)) return fail(KA_ERR_BAD_ARGS, why);
-    return fb_impl<QuantCall, ka::BandTable>(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo}, call);
+    return fb_impl<QuantCall, ka::BandTable>(e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr, &band_lo}, call);
 }
 
 int ka_ctc_sample_paths_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
@@ -1567,14 +1158,14 @@ int ka_ctc_sample_paths_banded_batch_f32(ka_engine *e, int32_t n, const float *c
                                          int32_t *status, int32_t mem, void *stream)
 {
     if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "sample paths: NULL band_lo");
-    return fb_impl<SampleCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo}, SampleCall{terminal, n_samples, seed, paths, ld_paths});
+    return fb_impl<SampleCall, ka::BandTable>(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status, band_lo}, SampleCall{terminal, n_samples, seed, paths, ld_paths});
 }
 
 int ka_ctc_sample_paths_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
                                    int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal, int32_t n_samples,
                                    uint64_t seed, int32_t *paths, int64_t ld_paths, double *log_likelihood, int32_t mem, void *stream)
 {
-    return fb_impl<SampleCall, ka::BandTable>(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo}, SampleCall{&terminal, &n_samples, &seed, &paths, &ld_paths});
+    return fb_impl<SampleCall, ka::BandTable>(e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr, &band_lo}, SampleCall{&terminal, &n_samples, &seed, &paths, &ld_paths});
 }
 
 int ka_ctc_mea_path_banded_batch_f32(ka_engine *e, int32_t n, const float *const *log_probs, const int64_t *T, int32_t V, const int64_t *ld,
@@ -1583,14 +1174,14 @@ int ka_ctc_mea_path_banded_batch_f32(ka_engine *e, int32_t n, const float *const
                                      double *expected_accuracy, double *log_likelihood, int32_t *status, int32_t mem, void *stream)
 {
     if (n > 0 && !band_lo) return fail(KA_ERR_BAD_ARGS, "mea path: NULL band_lo");
-    return fb_impl<MeaCall, ka::BandTable>(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, log_likelihood, status, mem, (hipStream_t)stream, band_lo}, MeaCall{terminal, path, expected_accuracy});
+    return fb_impl<MeaCall, ka::BandTable>(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, status, band_lo}, MeaCall{terminal, path, expected_accuracy});
 }
 
 int ka_ctc_mea_path_banded_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld, const int32_t *labels, int64_t S,
                                int32_t beam_size, int32_t max_move, const int32_t *band_lo, int64_t terminal, int32_t *path,
                                double *expected_accuracy, double *log_likelihood, int32_t mem, void *stream)
 {
-    return fb_impl<MeaCall, ka::BandTable>(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, log_likelihood, nullptr, mem, (hipStream_t)stream, &band_lo}, MeaCall{&terminal, &path, expected_accuracy});
+    return fb_impl<MeaCall, ka::BandTable>(e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, log_likelihood, nullptr, &band_lo}, MeaCall{&terminal, &path, expected_accuracy});
 }
 
 // ---- best-path margins from max-marginals (ka_margin.hpp) ----
@@ -1600,7 +1191,7 @@ int ka_ctc_path_margins_batch_f32(ka_engine *e, int32_t n, const float *const *l
                                   double *const *alt, int32_t *const *runner_up, double *score, int32_t *status, int32_t mem, void *stream)
 {
     if (unit != 0 && unit != 1) return fail(KA_ERR_BAD_ARGS, "path margins: unit must be 0 (state) or 1 (text index)");
-    return fb_impl(e, {n, log_probs, T, V, ld, labels, S, beam_size, max_move, score, status, mem, (hipStream_t)stream},
+    return fb_impl(e, {{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, score, status},
                    MarginCall{band_lo, path, unit, through, alt, runner_up});
 }
 
@@ -1609,13 +1200,13 @@ int ka_ctc_path_margins_f32(ka_engine *e, const float *log_probs, int64_t T, int
                             double *alt, int32_t *runner_up, double *score, int32_t mem, void *stream)
 {
     if (unit != 0 && unit != 1) return fail(KA_ERR_BAD_ARGS, "path margins: unit must be 0 (state) or 1 (text index)");
-    return fb_impl(e, {1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, score, nullptr, mem, (hipStream_t)stream},
+    return fb_impl(e, {{1, &log_probs, &T, V, &ld, &labels, &S, beam_size, max_move, mem, (hipStream_t)stream}, score, nullptr},
                    MarginCall{&band_lo, &path, unit, &through, &alt, &runner_up});
 }
 
 size_t ka_path_margin_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam_size, int32_t max_move, int32_t mem)
 {
-    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    if (!countable(n, mem, {T, S})) return 0;
     return ka::plan::path_margin_workspace(n, T, S, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 
@@ -1629,7 +1220,7 @@ int ka_ctc_margins_resume_batch_f32(ka_engine *e, int32_t n, const float *const 
                                     int32_t *status, int32_t mem, void *stream)
 {
     if (unit != 0 && unit != 1) return fail(KA_ERR_BAD_ARGS, "margins resume: unit must be 0 (state) or 1 (text index)");
-    return fb_impl(e, FbArgs{n, log_probs, T, V, ld, labels, S, beam_size, max_move, score, status, mem, (hipStream_t)stream, nullptr},
+    return fb_impl(e, FbArgs{{n, log_probs, T, V, ld, labels, S, beam_size, max_move, mem, (hipStream_t)stream}, score, status, nullptr},
                    MarginResumeCall{band_lo, d_in, e_in, terminal, path, unit, through, alt, runner_up, frames, K, rows, ld_rows, rows_lo, d_out,
                                     e_out});
 }
@@ -1648,7 +1239,7 @@ int ka_ctc_margins_resume_f32(ka_engine *e, const float *log_probs, int64_t T, i
 size_t ka_margins_resume_workspace_bytes(int32_t n, const int64_t *T, const int64_t *S, const int64_t *K, int32_t V, int32_t beam_size,
                                          int32_t max_move, int32_t mem)
 {
-    if (n < 0 || (n > 0 && (!T || !S)) || (mem != KA_MEM_HOST && mem != KA_MEM_DEVICE)) return 0;
+    if (!countable(n, mem, {T, S})) return 0;
     return ka::plan::margins_resume_workspace(n, T, S, K, V, beam_size, max_move, mem == KA_MEM_HOST, nullptr, nullptr);
 }
 

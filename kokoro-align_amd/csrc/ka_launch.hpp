@@ -1,8 +1,8 @@
 // ka_launch.hpp — the host-callable launch functions of every device translation unit.
 //
-// The library is built from twenty-two translation units so that the device code compiles in parallel (a single unit took three
-// minutes): ka_engine.hip, ka_engine_fb.hip and ka_entry_misc.hip are host code only and reach the kernels through these
-// functions; each kernel family lives in the .hip file named below and nowhere else.  A forward-backward call's launch is a
+// The library is built from thirty-four translation units so that the device code compiles in parallel (a single unit took three
+// minutes): ka_engine.hip, ka_engine_fb.hip, ka_engine_band.hip and ka_entry_misc.hip are host code only and reach the kernels
+// through these functions; each kernel family lives in the .hip file named below and nowhere else.  A forward-backward call's launch is a
 // template over the band, defined in the call's header; its units hold nothing but that template's explicit instantiation, one
 // band each.  All functions only enqueue; errors surface through hipGetLastError().
 #pragma once

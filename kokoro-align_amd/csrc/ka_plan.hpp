@@ -588,7 +588,7 @@ inline bool posterior_fast(int64_t S, int32_t V, int32_t beam, int32_t max_move)
 {
     return V <= 64 && max_move <= 4 && std::min<int64_t>(beam, 2 * S + 1) <= kFastMaxBand;
 }
-// what both planners carve per lattice: its form, and for host buffers its staged log-probs [T, V] and labels [S]
+// what every planner below carves per lattice: its form, and for host buffers its staged log-probs [T, V] and labels [S]
 struct FbCarve {
     size_t lp, lab;   // host buffers only
     bool fast;
@@ -936,24 +936,46 @@ inline size_t mea_path_workspace(int32_t n, const int64_t *T, const int64_t *S, 
 namespace ka {
 namespace plan {
 
-// ---- ka_ctc_best_path_banded_batch_f32 (ka_banded.hpp): workspace layout ----
-// descriptors, a LatticeMeta per lattice, then per lattice: the prepared labels, in the one-wavefront form the shifted and
-// padded table (4 ceil(T/4) + 4 int32) and the codes (256 bytes per frame, whole groups of four frames), in the generic form a
-// byte per band cell and the two score / two liveness columns; for host buffers the staged log-probs, labels, table and the three
-// outputs of every lattice.  `tracking` (ka_ctc_best_path_tracking_batch_f32): the same without the shifted table; the staged
-// table is then the call's fourth output.
-struct BandCarve {
-    size_t lp, lab, band, path, lab_out, sc_out;   // host buffers only
-    size_t labx, tab, bp, col;
-    int32_t labx_len, tab_len, W;
-    bool fast;
+// ---- the band best-path calls (ka_engine_band.hip): one workspace layout, by the call's mode ----
+// ka_ctc_best_path_banded_batch_f32 (ka_banded.hpp): descriptors, a LatticeMeta per lattice, then per lattice: the prepared
+// labels, in the one-wavefront form the shifted and padded table (4 ceil(T/4) + 4 int32) and the codes (256 bytes per frame, whole
+// groups of four frames), in the generic form a byte per band cell and the two score / two liveness columns; for host buffers the
+// staged log-probs, labels, table and the three outputs of every lattice.
+// `tracking` (ka_ctc_best_path_tracking_batch_f32): the same without the shifted table; the staged table is then the call's
+// fourth output.
+// `resumed` (ka_ctc_best_path_resume_batch_f32, ka_ctc_best_path_tracking_resume_batch_f32): behind all that a ResumeRows per
+// lattice and its cells (int32: the entry, and under tracking the low end of frame T beside it); for host buffers the two
+// staged rows of every lattice ([2S+1] float32 each: init, then fin).
+// `walk` (the determined calls, ka_determined.hpp; implies resumed): behind that the `determined` cell (int32) of every lattice
+// and, for device buffers, a last row of the engine's own per lattice ([2S+1] float32: the walk starts from the last row, whether
+// or not the caller asks for it; with host buffers the staged row serves).
+// The byte count depends on the shapes and the mode alone, not on which rows the caller gives.
+struct BandMode {
+    bool tracking = false, resumed = false, walk = false;
 };
-inline size_t banded_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
-                               BandCarve *cv, size_t *off_meta, bool tracking = false)
+struct BandCarve : FbCarve {
+    size_t band, path, lab_out, sc_out;            // host buffers only
+    size_t labx, tab, bp, col;
+    size_t init, fin;                              // resumed, host buffers: the staged rows
+    size_t own_fin;                                // walk, device buffers: the engine's own last row
+    int32_t labx_len, tab_len, W;
+};
+struct BandLayout {
+    size_t total = 0, off_meta = 0, off_rows = 0, off_entry = 0, off_det = 0;
+    size_t desc_bytes = 0, meta_bytes = 0, rows_bytes = 0, entry_bytes = 0;   // the regions the host fills or reads, as the pinned buffer repeats them
+    int32_t cells = 1;            // per lattice behind the rows
+    std::vector<BandCarve> cv;    // by the caller's index
+};
+// Fills *lay; with lay == nullptr it only counts.  Returns the bytes, 0 for an unsupported shape.
+inline size_t band_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
+                             BandMode mode, BandLayout *lay)
 {
-    size_t off = align_up((size_t)n * sizeof(BandLattice));
-    if (off_meta) *off_meta = off;
-    off += align_up((size_t)n * sizeof(LatticeMeta));
+    BandLayout counted;
+    BandLayout &l = lay ? *lay : counted;
+    l = BandLayout();
+    if (lay) l.cv.resize((size_t)n);
+    size_t off = l.off_meta = l.desc_bytes = align_up((size_t)n * sizeof(BandLattice));
+    off += l.meta_bytes = align_up((size_t)n * sizeof(LatticeMeta));
     for (int32_t i = 0; i < n; ++i) {
         Shape sh;
         if (!shape_of(T[i], S[i], V, beam, max_move, sh)) return 0;
@@ -965,68 +987,44 @@ inline size_t banded_workspace(int32_t n, const int64_t *T, const int64_t *S, in
         c.labx = off;
         off += align_up((size_t)sh.labx_len * 4);
         c.tab = off;
-        if (c.fast && !tracking) off += align_up((size_t)c.tab_len * 4);
+        if (c.fast && !mode.tracking) off += align_up((size_t)c.tab_len * 4);
         c.bp = off;
         off += align_up(c.fast ? (((size_t)sh.T + 3) / 4) * 1024 : (size_t)sh.T * (size_t)sh.W);
         c.col = off;
         if (!c.fast) off += align_up((size_t)sh.L * 2 * sizeof(float) + (size_t)sh.L * 2);
         if (host_buffers) {
-            c.lp = off;
-            off += align_up((size_t)sh.T * (size_t)V * 4);
-            c.lab = off;
-            off += align_up((size_t)sh.S * 4);
+            carve_staged(off, sh, V, c);
             for (size_t *x : {&c.band, &c.path, &c.lab_out, &c.sc_out}) {
                 *x = off;
                 off += align_up((size_t)sh.T * 4);
             }
         }
-        if (cv) cv[i] = c;
+        if (lay) l.cv[i] = c;
     }
-    return off;
-}
-
-// ---- ka_ctc_best_path_resume_batch_f32: banded_workspace and, behind it, a ResumeRows and an entry cell (int32) per lattice;
-// for host buffers the two staged rows of every lattice ([2S+1] float32 each: init[i], then fin[i], offsets from the start of
-// the workspace).  0 where banded_workspace is 0.  `tracking` (ka_ctc_best_path_tracking_resume_batch_f32): banded_workspace's
-// tracking layout (no shifted table, the staged table an output) and two cells per lattice, the entry and the low end of frame T.
-inline size_t resume_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
-                               BandCarve *cv, size_t *off_meta, size_t *off_rows, size_t *off_entry, size_t *init, size_t *fin,
-                               bool tracking = false)
-{
-    size_t off = banded_workspace(n, T, S, V, beam, max_move, host_buffers, cv, off_meta, tracking);
-    if (off == 0) return 0;
-    if (off_rows) *off_rows = off;
-    off += align_up((size_t)n * sizeof(ResumeRows));
-    if (off_entry) *off_entry = off;
-    off += align_up((size_t)n * (tracking ? 2 : 1) * sizeof(int32_t));
-    if (host_buffers)
-        for (int32_t i = 0; i < n; ++i) {
-            const size_t row = align_up((size_t)(2 * S[i] + 1) * sizeof(float));
-            if (init) init[i] = off;
-            if (fin) fin[i] = off + row;
-            off += 2 * row;
-        }
-    return off;
-}
-
-// ---- ka_ctc_best_path_determined_batch_f32, ka_ctc_best_path_tracking_determined_batch_f32 (ka_determined.hpp):
-// resume_workspace and, behind it, the `determined` cell (int32) of every lattice and, for device buffers, a last row of the
-// engine's own per lattice ([2S+1] float32: the walk starts from the last row, whether or not the caller asks for it; with host
-// buffers the staged row serves).  The byte count depends on the shapes alone, not on which rows the caller gives.
-inline size_t determined_workspace(int32_t n, const int64_t *T, const int64_t *S, int32_t V, int32_t beam, int32_t max_move, bool host_buffers,
-                                   BandCarve *cv, size_t *off_meta, size_t *off_rows, size_t *off_entry, size_t *init, size_t *fin,
-                                   size_t *off_det, size_t *own_fin, bool tracking)
-{
-    size_t off = resume_workspace(n, T, S, V, beam, max_move, host_buffers, cv, off_meta, off_rows, off_entry, init, fin, tracking);
-    if (off == 0) return 0;
-    if (off_det) *off_det = off;
-    off += align_up((size_t)n * sizeof(int32_t));
-    if (!host_buffers)
-        for (int32_t i = 0; i < n; ++i) {
-            if (own_fin) own_fin[i] = off;
-            off += align_up((size_t)(2 * S[i] + 1) * sizeof(float));
-        }
-    return off;
+    if (mode.resumed || mode.walk) {
+        l.cells = mode.tracking ? 2 : 1;
+        l.off_rows = off;
+        off += l.rows_bytes = align_up((size_t)n * sizeof(ResumeRows));
+        l.off_entry = off;
+        off += l.entry_bytes = align_up((size_t)n * l.cells * sizeof(int32_t));
+        if (host_buffers)
+            for (int32_t i = 0; i < n; ++i) {
+                const size_t row = align_up((size_t)(2 * S[i] + 1) * sizeof(float));
+                if (lay) l.cv[i].init = off;
+                if (lay) l.cv[i].fin = off + row;
+                off += 2 * row;
+            }
+    }
+    if (mode.walk) {
+        l.off_det = off;
+        off += align_up((size_t)n * sizeof(int32_t));
+        if (!host_buffers)
+            for (int32_t i = 0; i < n; ++i) {
+                if (lay) l.cv[i].own_fin = off;
+                off += align_up((size_t)(2 * S[i] + 1) * sizeof(float));
+            }
+    }
+    return l.total = off;
 }
 
 }  // namespace plan
