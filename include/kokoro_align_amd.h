@@ -40,7 +40,10 @@ extern "C" {
                                  is not reproduced - the lattice is rejected (fast path, V <= 64, band <= 1009 or tiled form) */
 
 #define KA_ERR_ZERO_MASS (-9) /* posteriors: no path of finite score reaches the best path's terminal (the lattice
-                                 log-likelihood is -inf; the reference can end its path on a state reached only through -inf) */
+                                 log-likelihood is -inf; the reference can end its path on a state reached only through -inf).
+                                 The test is made on the float the log-likelihood is reported from (below): a lattice whose
+                                 terminal lies beyond float32's range below the offset of its last 32-frame block, more than
+                                 2.3e38 nats within those frames, reports it too */
 
 /* where the caller's buffers live */
 #define KA_MEM_HOST 0
@@ -131,6 +134,17 @@ int ka_batch_finish(ka_engine *e, float *total_score, int32_t *status);
  * (a best_path value outside [0, 2S+1)) - posteriors NaN, log-likelihood NaN; KA_ERR_ZERO_MASS - posteriors NaN,
  * log-likelihood -inf.  The call returns KA_OK or the status of the first lattice that failed.  It uses its own kernels
  * (ka_engine_set_mode / set_backtrace do not apply) and synchronises `stream` before it returns.
+ *
+ * Magnitude (this call and every forward-backward call below).  Log-probs are float32 and the
+ * recurrences float64, all of it, their maxima included: any finite log-prob is legal, and a frame c nats below its neighbours
+ * (padding, a row of masked logits after log_softmax) changes no posterior.  What float64 itself costs is an ulp of c per
+ * step: posteriors, occupancies, durations and visits keep their usual accuracy to a relative 2^-10 up to c = 2^37 for one such
+ * frame, 2^33 for eight, 2^30 for seventy; beyond that every call still returns KA_OK, finite values, probabilities in [0, 1]
+ * and legal paths (a visit probability, a sum, may exceed 1 by its error: 3e-2 at 2^44).  Two float32 steps of the design see
+ * the magnitude sooner.  THIS call stores alpha at the path relative to the offset of its 32-frame block as a float, so a frame
+ * c below its neighbours costs the posteriors of the later frames of its block half a float32 ulp of 1.44 c in the exponent:
+ * 2^-7 from c = 2^17.  And every call reports log_likelihood from such a float at the terminal: a deep frame in the last block
+ * costs it 2^-25 of that block's share; deep frames in earlier blocks cost it nothing beyond float64's own rounding.
  */
 int ka_ctc_path_posteriors_f32(ka_engine *e, const float *log_probs, int64_t T, int32_t V, int64_t ld,
                                const int32_t *labels, int64_t S, int32_t beam_size, int32_t max_move,

@@ -158,6 +158,8 @@ __device__ __forceinline__ int fb_ck_forward(Form &f, Band &bw, double &Z, doubl
     flags = post_block_flags(flags);
     if (flags) return post_status_of(flags);
     const double us = (sstar >= plo && sstar < phi) ? prev[Form::cslot(sstar)] : NINF;
+    // (tested on the float Z is reported from, as the path call tests its stored float: a terminal beyond float32's range below
+    //  its block's offset is zero mass in every call alike - include/kokoro_align_amd.h, KA_ERR_ZERO_MASS)
     if ((float)((Ca - Cb) + us) == post_ninf()) return kStatusZeroMass;
     Z = Ca + us;
     Zr = fb_reported_z(Cb, Ca, us);

@@ -103,7 +103,7 @@ struct FbCallerBound {
         flags |= bad ? 4 : 0;
         flags = post_block_flags(flags);
         if (flags) return post_status_of(flags);
-        if (!bin) {   // the sibling's expressions, and so its bits
+        if (!bin) {   // the sibling's expressions, and so its bits (its zero-mass test on the float Z is reported from included)
             const double us = (sstar >= plo && sstar < phi) ? prev[Form::cslot(sstar)] : NINF;
             if ((float)((Ca - Cb) + us) == post_ninf()) return kStatusZeroMass;
             Z = Ca + us;

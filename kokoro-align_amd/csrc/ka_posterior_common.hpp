@@ -23,10 +23,12 @@ __device__ __forceinline__ int post_bad_bits(float x)
     asm volatile("" : "+v"(b));
     return ((b & 0x7fffffffu) > 0x7f800000u ? 1 : 0) | (b == 0x7f800000u ? 2 : 0);   // 1: NaN, 2: +inf
 }
+// (fmax, not fmaxf: HIP declares fmaxf for floats only, and a double maximum taken through it is rounded to float32 - harmless
+//  while the cells stay within exp2's range of it, fatal for a frame 2^37 nats below its neighbours)
 __device__ __forceinline__ double post_wave_max(double x)
 {
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = fmaxf(x, __shfl_xor(x, off));
+    for (int off = 32; off >= 1; off >>= 1) x = fmax(x, __shfl_xor(x, off));
     return x;
 }
 // One wavefront: its LDS operations execute in program order, so a frame hand-off needs no s_barrier (whose fence would also
@@ -204,7 +206,7 @@ __device__ __forceinline__ double post_block_max(double x, double *red)   // red
     x = post_wave_max(x);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
     __syncthreads();
-    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
 }
 
 // sums in a fixed order (a butterfly; then the four wavefronts' sums from the first to the last), so that every thread holds the
@@ -251,12 +253,12 @@ __device__ __forceinline__ double fb_fast_fwd(int64_t lo, int64_t hi, int64_t pl
             const int64_t u = p - j;
             const bool ok = u >= plo && u < phi && !fb_vetoed(j, lab);
             x[j] = ok ? prev[u & 1023] : NINF;
-            mx = fmaxf(mx, x[j]);
+            mx = fmax(mx, x[j]);
         }
         const double val = post_lse2(x, M, mx) + (e - mprev);
         cur[p & 1023] = val;
         cell(p, val);
-        mymax = fmaxf(mymax, val);
+        mymax = fmax(mymax, val);
     }
     return mymax;
 }
@@ -293,14 +295,14 @@ __device__ __forceinline__ double fb_fast_bwd(int64_t lo, int64_t hi, int64_t nl
                 const bool ok = u >= nlo && u < nhi;
                 const double g = fb_skip(j) ? vn[u & 1023] : gn[u & 1023];
                 x[j] = ok ? g : NINF;
-                mx = fmaxf(mx, x[j]);
+                mx = fmax(mx, x[j]);
             }
             w = post_lse2(x, M, mx) - nprev;
         }
         const double g = w + row[lab];   // (read here, not before the branch: a global label load stays behind the lse)
         gc[p & 1023] = g;
         vc[p & 1023] = lab == 0 ? NINF : g;
-        mymax = fmaxf(mymax, g);
+        mymax = fmax(mymax, g);
         cell(p, lab, w);
     }
     return mymax;
@@ -324,7 +326,7 @@ __device__ __forceinline__ double fb_gen_fwd(const FbLattice &d, const float *lr
         };
         double mx = NINF;
         for (int j = 0; j < M && j <= p; ++j)
-            if (in(j)) mx = fmaxf(mx, prev[p - j]);
+            if (in(j)) mx = fmax(mx, prev[p - j]);
         double s = 0.0;
         for (int j = 0; j < M && j <= p; ++j)
             if (in(j)) s += exp2(prev[p - j] - mx);
@@ -332,7 +334,7 @@ __device__ __forceinline__ double fb_gen_fwd(const FbLattice &d, const float *lr
         const double val = l + (e - mprev);
         cur[p] = val;
         cell(p, val);
-        mymax = fmaxf(mymax, val);
+        mymax = fmax(mymax, val);
     }
     return mymax;
 }
@@ -354,7 +356,7 @@ __device__ __forceinline__ double fb_gen_bwd(const FbLattice &d, const float *lr
             auto g = [&](int j) { return fb_skip(j) ? vn[p + j] : gn[p + j]; };
             double mx = NINF;
             for (int j = 0; j < M; ++j)
-                if (p + j >= nlo && p + j < nhi) mx = fmaxf(mx, g(j));
+                if (p + j >= nlo && p + j < nhi) mx = fmax(mx, g(j));
             double s = 0.0;
             for (int j = 0; j < M; ++j)
                 if (p + j >= nlo && p + j < nhi) s += exp2(g(j) - mx);
@@ -363,7 +365,7 @@ __device__ __forceinline__ double fb_gen_bwd(const FbLattice &d, const float *lr
         const double g = w + e;
         gc[p] = g;
         vc[p] = lab == 0 ? NINF : g;
-        mymax = fmaxf(mymax, g);
+        mymax = fmax(mymax, g);
         cell(p, lab, w);
     }
     return mymax;

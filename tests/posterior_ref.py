@@ -17,6 +17,7 @@ OK, BAD_ARGS, BAD_LABEL, NAN, NONFINITE, ZERO_MASS = 0, -2, -5, -6, -7, -9
 CK = 32                                  # frames per block of the kernels' offsets and checkpoints (kPostCk)
 LOG2E, LN2 = 1.4426950408889634, 0.6931471805599453
 FAULTS = ("lo_high", "hi_low", "no_veto_fwd", "bwd_drop_move", "stale_row", "late_label", "short_offset", "beta_seed")
+DEEP_FAULTS = ("max32",)                 # seen only by the deep inputs at the end of this file (tests/test_posterior_deep_cpu.py)
 
 
 def windows(T, L, beam):
@@ -33,9 +34,20 @@ def expand(labels):
     return lab
 
 
-def _lse(stack):
+def _lse(stack, max32=False):
     m = np.max(stack, axis=0)
     safe = np.where(np.isfinite(m), m, 0.0)
+    if max32:
+        # The fault "max32": the maximum taken off the sum is rounded to float32 in log2 units, as a float maximum on the
+        # kernels' doubles does.  In exact arithmetic that changes nothing: max32 + log sum exp(x - max32) is the same number.  It
+        # bites where exp(x - max32) leaves float64's range and the sum comes out 0 or inf; only there does the faulty value
+        # replace the clean one, so that the fault is not drowned in the rounding noise of an absolute alpha of 1e4 nats (one ulp
+        # of which is 2e-12, and would move a gamma near 1 by that much whatever the perturbation).
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            clean = safe + np.log(np.sum(np.exp(stack - safe), axis=0))
+            m32 = (safe * LOG2E).astype(np.float32).astype(np.float64) * LN2
+            faulty = m32 + np.log(np.sum(np.exp(stack - m32), axis=0))
+            return np.where(np.isfinite(m), np.where(np.isfinite(faulty), clean, faulty), -np.inf)
     with np.errstate(divide="ignore"):
         return np.where(np.isfinite(m), safe + np.log(np.sum(np.exp(stack - safe), axis=0)), -np.inf)
 
@@ -46,7 +58,8 @@ def forward_backward(log_probs, labels, path, beam_size=1000, max_move=4, full=F
     error models below rebuild the kernels' block offsets.  ``fault`` = (name, frame or block): one of FAULTS, a deliberate
     mistake of the kind a kernel could make, for tests/test_posterior_ref_cpu.py."""
     kind, at = fault if fault else (None, None)
-    assert kind is None or kind in FAULTS, kind
+    assert kind is None or kind in FAULTS + DEEP_FAULTS, kind
+    m32 = kind == "max32"
     lp = np.asarray(log_probs, dtype=np.float64)
     T, V = lp.shape
     lab = expand(labels)
@@ -92,7 +105,7 @@ def forward_backward(log_probs, labels, path, beam_size=1000, max_move=4, full=F
             c = np.full(len(s), -np.inf)
             c[ok] = prev[u[ok] - plo]
             cands.append(c)
-        a = (_lse(np.array(cands)) if len(s) else np.zeros(0)) + row[labs]
+        a = (_lse(np.array(cands), m32) if len(s) else np.zeros(0)) + row[labs]
         if lo[t] <= path[t] < hi[t]:
             alpha_at[t] = a[path[t] - lo[t]]
         fmax[t] = np.max(a) if len(a) else -np.inf
@@ -133,7 +146,7 @@ def forward_backward(log_probs, labels, path, beam_size=1000, max_move=4, full=F
             c = np.full(len(s), -np.inf)
             c[ok] = g[u[ok] - nlo]
             cands.append(c)
-        b = _lse(np.array(cands)) if len(s) else np.zeros(0)
+        b = _lse(np.array(cands), m32) if len(s) else np.zeros(0)
         if lo[t] <= path[t] < hi[t]:
             post[t] = np.exp(alpha_at[t] + b[path[t] - lo[t]] - ll)
         if full:
@@ -502,3 +515,253 @@ def mixed_path(ref, lo_hi, terminal):
     p[t % 11 == 10] = 0
     p[-1] = terminal
     return p
+
+
+# ---------------------------------------------------------------------------------------
+# Deep inputs ("magnitude"): rows c = 2^k nats below their neighbours, and single cells masked with a
+# large finite constant.  The reference of a deep lattice is forward_backward of the exactly UNSHIFTED float64 rows (row + c), Z
+# moved by -sum c_t: adding c_t to every entry of row t changes no posterior, so the reference never sees the magnitude and is
+# valid at every rung.  tests/test_posterior_deep_cpu.py asserts the conditions, tests/test_posterior_deep_gpu.py runs the calls.
+# ---------------------------------------------------------------------------------------
+DEEP_RUNGS = (10, 17, 20, 24, 30, 33, 35, 37, 40, 44)
+DEEP_SLACK = 2.0 ** 11      # log2 units: what an ordinary lattice of the deep shapes (T <= 70) adds to an offset beside the shifts
+CAP, CAP_FLOOR = 2.0 ** -10, 2.0 ** -20
+Z_DEEP_REL = 2.0 ** -40
+
+
+def deep_rows(base, frames, c):
+    """(lp float32 [T, V], shift float64 [T]): ``base`` with the rows at ``frames`` replaced by float32(-c) + d, d a per-label
+    offset in {-4, -2, 0, 2, 4} where float32's spacing at c is at most 2 (k <= 24: one d for all those rungs), all zero where
+    it exceeds 8; the rows are exactly representable, so lp + shift is the unshifted lattice exactly."""
+    lp = np.array(base, np.float32)
+    T, V = lp.shape
+    assert float(np.float32(c)) == float(c)
+    sp = float(np.spacing(np.float32(c)))
+    assert sp <= 2.0 or sp > 8.0, c
+    d = 2.0 * np.random.default_rng(V).integers(-2, 3, size=V) if sp <= 2.0 else np.zeros(V)
+    shift = np.zeros(T)
+    for t in frames:
+        row = (-float(c) + d).astype(np.float32)
+        assert np.array_equal(row.astype(np.float64), -float(c) + d)
+        lp[t] = row
+        shift[t] = float(c)
+    return lp, shift
+
+
+def deep_unshifted(lp, shift):
+    """The float64 rows the reference runs on: row t + shift_t, exact."""
+    return np.asarray(lp, np.float64) + np.asarray(shift, np.float64)[:, None]
+
+
+def deep_ref(lp, shift, labels, terminal, beam, mm, fault=None):
+    """ref_at of the unshifted rows; ``ll`` stays the unshifted lattice's, ``z`` is the deep lattice's (ll - sum shift)."""
+    ref = ref_at(deep_unshifted(lp, shift), labels, terminal, beam, mm, fault=fault)
+    ref["shift"] = np.asarray(shift, np.float64)
+    ref["z"] = ref["ll"] - float(np.sum(shift))
+    return ref
+
+
+def shifted_view(ref, shift):
+    """What path_error_model, z_error_model and block_offsets read, with the shifts put back: the kernels' offsets and the
+    float-stored relative alpha are formed from the shifted maxima."""
+    cum = np.cumsum(np.asarray(shift, np.float64))
+    return dict(alpha_at=ref["alpha_at"] - cum, fmax=ref["fmax"] - cum, post=ref["post"], ll=ref["ll"] - cum[-1])
+
+
+def _hulp64(x):
+    """Half a float64 ulp at x + DEEP_SLACK for x > 0, else 0."""
+    x = np.asarray(x, np.float64)
+    return np.where(x > 0.0, 0.5 * np.spacing(np.where(x > 0.0, x + DEEP_SLACK, 1.0)), 0.0)
+
+
+def deep_roundings(shift):
+    """(R [T], h): h = half a float64 ulp of log2 e max c_t, R_t the float64 roundings at that magnitude between the input and a
+    cell of frame t, counted from the code:
+      5 per deep frame at or before t (forward: the product lp log2 e, e - m_{t-1}, the add to the log-sum-exp; in the frame
+        behind it mx + log2 s and e - m_{t-1} again), 3 per deep frame behind t (backward: the product, w + e, mx + log2 s of the
+        frame before), 5 per deep frame for Z (the forward pass up to T-1);
+      the adds C += m and D += n of every frame behind t (they cancel between alpha, beta and Z up to t), each half an ulp of the
+        offset it forms, in units of h;
+      6 at the magnitude of Z: (ca + alpha), (D + w), their sum, Z = Ca + u, and the path call's C - Cb and + u."""
+    c = np.asarray(shift, np.float64) * LOG2E
+    T = len(c)
+    if not np.any(c > 0.0):
+        return np.zeros(T), 0.0
+    h = float(0.5 * np.spacing(np.max(c)))
+    deep = c > 0.0
+    n_le = np.cumsum(deep)
+    n_all = n_le[-1]
+    cells = 5.0 * n_le + 3.0 * (n_all - n_le) + 5.0 * n_all
+    cmag, dmag = np.cumsum(c), np.cumsum(c[::-1])[::-1]
+    adds = _hulp64(cmag) + _hulp64(dmag)                       # frame u's two adds
+    behind = np.concatenate([np.cumsum(adds[::-1])[::-1][1:], np.zeros(1)])
+    return cells + (behind + 6.0 * _hulp64(cmag[-1])) / h, h
+
+
+def deep_cost(shift):
+    """[T] what a cell of frame t may move by, as a share of its value: ln 2 R_t h."""
+    Rn, h = deep_roundings(shift)
+    return LN2 * Rn * h
+
+
+def deep_error_model(call, ref, shift, labels=None, V=None):
+    """The call's existing model plus value x deep_cost: "state" -> list over frames of arrays over the window, "label" ->
+    [T, V], "path" -> [T] (path_error_model on block_offsets of the shifted maxima: the design's own float store), "z" -> float
+    (z_error_model of the shifted values, plus the forward pass's roundings and the add that forms Z)."""
+    cost = deep_cost(shift)
+    if call == "state":
+        return [state_error_model(g) + g * cost[t] for t, (_, g) in enumerate(ref["gamma"])]
+    if call == "label":
+        lab = expand(labels)
+        occ = np.zeros((len(ref["gamma"]), V))
+        for t, (lo, g) in enumerate(ref["gamma"]):
+            np.add.at(occ[t], lab[lo:lo + len(g)], g)
+        return label_error_model(ref["gamma"], labels, V) + occ * cost[:, None]
+    if call == "path":
+        return path_error_model(shifted_view(ref, shift)) + ref["post"] * cost
+    assert call == "z", call
+    Rn, h = deep_roundings(shift)
+    n_all = float(np.sum(np.asarray(shift) > 0.0))
+    return z_error_model(shifted_view(ref, shift)) + LN2 * (5.0 * n_all * h + float(_hulp64(np.sum(shift) * LOG2E)))
+
+
+def inside_cap(E, value):
+    """Is a (case, call) pair compared cell by cell?  Only if E <= 2^-10 value at every cell whose value is >= 2^-20."""
+    E, value = (np.concatenate([np.asarray(x, np.float64).reshape(-1) for x in xs]) if isinstance(xs, list) else
+                np.asarray(xs, np.float64).reshape(-1) for xs in (E, value))
+    big = value >= CAP_FLOOR
+    return bool(np.all(E[big] <= CAP * value[big]))
+
+
+def z_rel_holds(ref, shift):
+    """Can the reported Z lie within 2^-40 of the reference, relatively?  Its model from the reference alone says: not where a
+    deep frame lies in the last block, whose share of Z goes through the float store of the terminal's relative alpha."""
+    return bool(deep_error_model("z", ref, shift) <= Z_DEEP_REL * abs(ref["ll"] - float(np.sum(shift))))
+
+
+def masked_cells(base, mask, value):
+    """(lp with ``value`` at the cells of ``mask`` [T, V] bool, the same lattice with -inf there: the reference's input)."""
+    lp, ninf = np.array(base, np.float32), np.array(base, np.float32)
+    lp[mask] = np.float32(value)
+    ninf[mask] = -np.inf
+    return lp, ninf
+
+
+def masked_mass(ref_value, ref_ninf):
+    """The share of the lattice's mass that runs through the masked cells: 1 - Z(-inf there) / Z(the value there), both float64."""
+    return float(-np.expm1(ref_ninf["ll"] - ref_value["ll"]))
+
+
+def deep_row_model(want, shift, which, carried=0.0):
+    """A row of ka_ctc_posteriors_resume on a deep chunk ([L] nats, the reference's row less the shifts it carries): the float64
+    chain's 2^-53 (frames + 1) max(1, |value|) of fb_resume_ref.row_error_model, plus the roundings of deep_roundings that do
+    not cancel in a single row: 5 (alpha_out) or 3 (beta_out) per deep frame, and every frame's add to the offset.  ``carried``:
+    the shifts (nats) the chunk's start row (alpha_out) or end row (beta_out) brings from the chunks beside it."""
+    want = np.asarray(want, np.float64)
+    c = np.asarray(shift, np.float64) * LOG2E
+    base = 2.0 ** -53 * (len(c) + 1) * np.maximum(1.0, np.abs(np.where(np.isfinite(want), want, 0.0)))
+    if not np.any(c > 0.0) and carried == 0.0:
+        return base
+    h = float(0.5 * np.spacing(max(np.max(c), carried * LOG2E)))
+    mags = carried * LOG2E + (np.cumsum(c) if which == "alpha_out" else np.cumsum(c[::-1]))
+    per = 5.0 if which == "alpha_out" else 3.0
+    return base + LN2 * (per * float(np.sum(c > 0.0)) * h + float(np.sum(_hulp64(mags))) + 2.0 * float(_hulp64(mags[-1])))
+
+
+# (T, S, beam, max_move, terminal back from L-1): the window slides under beam 16; 1000 holds every position
+DEEP_SHAPES = {"T40_S12_B16_M4": (40, 12, 16, 4, 0), "T70_S20_B16_M4": (70, 20, 16, 4, 1), "T70_S12_B1000_M2": (70, 12, 1000, 2, 0),
+               "T40_S20_B1000_M4": (40, 20, 1000, 4, 1)}
+DEEP_V = 39
+
+
+def deep_patterns(T):
+    return {"first": [0], "last": [T - 1], "f31": [31], "f32": [32], "f33": [33], "f30_34": list(range(30, 35)),
+            "pad8": list(range(T - 8, T)), "lead5": list(range(5)), "all": list(range(T))}
+
+
+def deep_base(shape):
+    """(base log-probs float32 [T, 39]: log-softmax of N(0, 1) logits, labels, terminal, beam, max_move)."""
+    T, S, beam, mm, back = DEEP_SHAPES[shape]
+    rng = np.random.default_rng(sum(map(ord, shape)))
+    labels = random_labels(rng, S, DEEP_V, zero_every=7)
+    return _normalise(rng.standard_normal((T, DEEP_V))), labels, 2 * S - back, beam, mm
+
+
+def deep_case(shape, pattern, k):
+    """dict(lp, shift, labels, terminal, beam, mm) of one rung."""
+    base, labels, term, beam, mm = deep_base(shape)
+    lp, shift = deep_rows(base, deep_patterns(base.shape[0])[pattern], 2.0 ** k)
+    return dict(lp=lp, shift=shift, labels=labels, terminal=term, beam=beam, mm=mm)
+
+
+def deep_ref_key(k):
+    """Rungs that share a reference: the rows' offsets d do not depend on k up to 2^24 and are zero above."""
+    return "d" if k <= 24 else "zero"
+
+
+_DEEP_REFS = {}
+
+
+def deep_built(shape, pattern, k):
+    """deep_case with its references: ``ref`` (ref_at of the unshifted rows, shared by the rungs of a deep_ref_key and left
+    unchanged), ``path`` (mixed_path through it), ``pref`` (forward_backward along that path) and ``z`` (ll - sum shift)."""
+    c = deep_case(shape, pattern, k)
+    key = (shape, pattern, deep_ref_key(k))
+    if key not in _DEEP_REFS:
+        plain = deep_unshifted(c["lp"], c["shift"])
+        ref = ref_at(plain, c["labels"], c["terminal"], c["beam"], c["mm"])
+        assert ref["status"] == OK, key
+        T, L = plain.shape[0], 2 * len(c["labels"]) + 1
+        path = mixed_path(ref, windows(T, L, c["beam"]), c["terminal"])
+        pref = forward_backward(plain, c["labels"], path, c["beam"], c["mm"])
+        assert pref["status"] == OK, key
+        _DEEP_REFS[key] = (plain, ref, path, pref)
+    plain, ref, path, pref = _DEEP_REFS[key]
+    assert np.array_equal(plain, deep_unshifted(c["lp"], c["shift"])), (shape, pattern, k)
+    return dict(c, name="%s-%s-k%d" % (shape, pattern, k), shape=shape, pattern=pattern, k=k, plain=plain, ref=ref, path=path, pref=pref,
+                z=ref["ll"] - float(np.sum(c["shift"])))
+
+
+def deep_all(shape):
+    return [deep_built(shape, p, k) for p in deep_patterns(DEEP_SHAPES[shape][0]) for k in DEEP_RUNGS]
+
+
+def deep_caps(c):
+    """{call: is the pair compared cell by cell?} for the state, label and path calls of a built case, from the reference alone."""
+    ref, shift = c["ref"], c["shift"]
+    occ = np.zeros((len(ref["gamma"]), DEEP_V))
+    lab = expand(c["labels"])
+    for t, (lo, g) in enumerate(ref["gamma"]):
+        np.add.at(occ[t], lab[lo:lo + len(g)], g)
+    return dict(state=inside_cap(deep_error_model("state", ref, shift), [g for _, g in ref["gamma"]]),
+                label=inside_cap(deep_error_model("label", ref, shift, c["labels"], DEEP_V), occ),
+                path=inside_cap(deep_error_model("path", c["pref"], shift), c["pref"]["post"]))
+
+
+MASK_VALUES = (-1e9, -1e30, float(np.finfo(np.float32).min))
+
+
+def masked_case(shape, value):
+    """Single cells of four frames (round a block boundary and at both ends) set to ``value``: the label of the likeliest
+    non-blank cell of the frame, so the cell lies beside live alternatives (the blank column among them)."""
+    base, labels, term, beam, mm = deep_base(shape)
+    ref = ref_at(base, labels, term, beam, mm)
+    lab = expand(labels)
+    mask = np.zeros(base.shape, bool)
+    for t in (3, 31, 32, base.shape[0] - 2):
+        lo, g = ref["gamma"][t]
+        idx = lab[lo:lo + len(g)]
+        mask[t, idx[int(np.argmax(np.where(idx != 0, g, -1.0)))]] = True
+    lp, ninf = masked_cells(base, mask, value)
+    return lp, ninf, mask, labels, term, beam, mm
+
+
+# ---------------------------------------------------------------------------------------
+# The multipliers of the deep models: twice the worst ratio |kernel - float64| / deep_error_model measured on the MI355X over
+# tests/test_posterior_deep_gpu.py, rounded up to two digits (profiles/posterior_accuracy.json, key "deep"; the rule of DESIGN.md
+# section 4.21).  Measured: 0.972 state (durations are held to its multiplier: 0.414 and 0.417), 0.999 label, 0.983 path,
+# 0.981 Z, 0.494 visit and 0.499 exit_time, 0.254 alpha_out and 0.614 beta_out (a pair of outputs shares the larger of its two
+# multipliers).  No ratio exceeds 1: the count of deep_roundings misses no rounding, and is generous where the worst ratio is
+# far below 1.
+# ---------------------------------------------------------------------------------------
+M_DEEP_STATE, M_DEEP_LABEL, M_DEEP_PATH, M_DEEP_Z, M_DEEP_VISIT, M_DEEP_ROW = 2.0, 2.0, 2.0, 2.0, 1.0, 1.3

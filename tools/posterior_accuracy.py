@@ -33,6 +33,14 @@ and z, which joins the file's records:
 
     KA_ACCURACY_OUT=ratios.jsonl python -m pytest tests/test_boundary_quantiles_gpu.py -q -m gpu
     python tools/posterior_accuracy.py ratios.jsonl profiles/posterior_accuracy.json quantile_left_out quantile_mismatch z
+
+The deep inputs (tests/test_posterior_deep_gpu.py, DESIGN.md section 4.21, "magnitude") record each call against its deep model
+under keys of their own, deep_*, whose multipliers follow the rule above (the two duration figures are held to deep_state's);
+the file's masked-cell tests record state, label, path and z, which join the file's records:
+
+    KA_ACCURACY_OUT=ratios.jsonl python -m pytest tests/test_posterior_deep_gpu.py -q -m gpu
+    python tools/posterior_accuracy.py ratios.jsonl profiles/posterior_accuracy.json deep_state deep_label deep_path deep_z \
+        deep_duration deep_time_sum deep_visit deep_exit_time deep_alpha_out deep_beta_out state label path z
 """
 import json
 import math
@@ -43,6 +51,8 @@ DURATION_CALLS = ("duration", "time_sum", "duration_sum", "time_sum_sum")
 MEA_CALLS = ("mea", "mea_total", "mea_value")
 VISIT_CALLS = ("visit", "exit_time")
 QUANTILE_CALLS = ("quantile_left_out", "quantile_mismatch")
+DEEP_CALLS = ("deep_state", "deep_label", "deep_path", "deep_z", "deep_duration", "deep_time_sum", "deep_visit", "deep_exit_time",
+              "deep_alpha_out", "deep_beta_out")
 
 
 def round_up(x):
@@ -55,7 +65,7 @@ def round_up(x):
 
 def main(src, dst, only=()):
     calls = tuple(only) or CALLS
-    assert all(c in CALLS + DURATION_CALLS + MEA_CALLS + VISIT_CALLS + QUANTILE_CALLS for c in calls), calls
+    assert all(c in CALLS + DURATION_CALLS + MEA_CALLS + VISIT_CALLS + QUANTILE_CALLS + DEEP_CALLS for c in calls), calls
     worst = {c: {} for c in calls}
     held = {}                                    # the multiplier the tests held a call against (every record carries it)
     with open(src) as f:
@@ -79,6 +89,8 @@ def main(src, dst, only=()):
         top = max(worst[c].values(), default=0.0)
         # (the duration figures are held against the state call's multiplier: their model is a sum of its per-cell model)
         m = out["calls"]["state"]["m"] if c in DURATION_CALLS and "state" in out["calls"] else held[c] if c in MEA_CALLS + QUANTILE_CALLS else round_up(2 * top)
+        if c in ("deep_duration", "deep_time_sum") and "deep_state" in out["calls"]:
+            m = out["calls"]["deep_state"]["m"]
         out["calls"][c] = {"m": m, "worst_ratio": top, "tests": len(worst[c]),
                            "records": [{"test": t, "ratio": r} for t, r in sorted(worst[c].items())]}
     with open(dst, "w") as f:
