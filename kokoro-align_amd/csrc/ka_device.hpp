@@ -536,6 +536,32 @@ __device__ __forceinline__ void mask_scores(f32x2 (&P)[8], BandMasks &mk, float 
     KA_P(P, K) = select_by_mask(NINF, KA_P(P, K), mk.at<K>());
     if constexpr (K > 0) mask_scores<K - 1>(P, mk, NINF);
 }
+// The same over one quarter of a lane's cells, 4Q .. 4Q+3, where bit Q of `sel` is set (forward_ck: the frame behind a band step
+// that took lo one further owes the quarter that holds the position which left, every other masked frame all four).  The bit
+// test and the jump are inside the statement, so the compiler sees straight-line code that rewrites four cells in place.  As
+// four `if`s the quarters are four more merge points in a frame loop that is unrolled eight times: the register allocator then
+// leaves P a register pair further up behind every other frame and copies it back on the COMMON path (8 v_mov_b64 in three
+// frames of eight; two `if`s over halves: 78 VGPRs).  Not volatile: a volatile statement with four tied operands pins the order
+// of everything round it and costs 75 VGPRs.
+template <int Q>
+__device__ __forceinline__ void mask_quarter(f32x2 (&P)[8], BandMasks &mk, float NINF, uint32_t sel)
+{
+    float a = KA_P(P, 4 * Q), b = KA_P(P, 4 * Q + 1), c = KA_P(P, 4 * Q + 2), e = KA_P(P, 4 * Q + 3);
+    asm("s_bitcmp0_b32 %4, %10\n\t"
+        "s_cbranch_scc1 .Lka_mq_%=\n\t"
+        "v_cndmask_b32 %0, %5, %0, %6\n\t"
+        "v_cndmask_b32 %1, %5, %1, %7\n\t"
+        "v_cndmask_b32 %2, %5, %2, %8\n\t"
+        "v_cndmask_b32 %3, %5, %3, %9\n"
+        ".Lka_mq_%=:"
+        : "+v"(a), "+v"(b), "+v"(c), "+v"(e)
+        : "s"(sel), "v"(NINF), "s"(mk.at<4 * Q>()), "s"(mk.at<4 * Q + 1>()), "s"(mk.at<4 * Q + 2>()), "s"(mk.at<4 * Q + 3>()), "n"(Q)
+        : "scc");
+    KA_P(P, 4 * Q) = a;
+    KA_P(P, 4 * Q + 1) = b;
+    KA_P(P, 4 * Q + 2) = c;
+    KA_P(P, 4 * Q + 3) = e;
+}
 
 // cells 15..0 of one frame, in place (descending k: cell k reads the old k-1..k-3)
 // The emission register of a label cell is refilled for the NEXT frame (ds_bpermute of the next

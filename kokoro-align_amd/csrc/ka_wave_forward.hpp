@@ -247,7 +247,8 @@ __device__ __forceinline__ void forward_w16(const Lattice &d, int32_t *meta)
 //     of lanes, their reset and the band masks all live in one rare block after the cells;
 //   * the band mask (a v_cndmask per cell) is applied only where it is needed: in the frame before a band
 //     step (the cells that become live must hold -inf), in the first frame of a new band (cells that left
-//     it must die) - both inside the rare block, the second by forcing the next frame through it - and in
+//     it must die: where lo went one further, only the quarter of the cells that holds it) - both inside the rare block,
+//     the second by forcing the next frame through it - and in
 //     every eighth (narrow gap: fourth) frame; checkpoints are taken there.  In between, cells above hi pick
 //     up "leaked" scores from the live cells below them, M-1 cells further per frame; moves only go up, so a
 //     leak cannot reach a live cell except around the ring, through the >= 15 dead slots between hi and lo:
@@ -317,9 +318,9 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
     }
 
     uint32_t q = 0, rem = 0;                // floor(L*t/T) and its remainder, advanced per frame
-    uint32_t lo = 0, hi = B < L ? B : L;    // band of frame 0
+    uint32_t lo = 0;                        // band of frame 0: [0, min(beam, L)); hi is a function of lo and not kept
     BandMasks mk;
-    band_rebuild(mk, lo, hi);
+    band_rebuild(mk, lo, B < L ? B : L);
 
     const uint32_t lane_off = (lane < d.V ? (uint32_t)lane : 0u) * 4u;
     const char *lp = reinterpret_cast<const char *>(d.lp);
@@ -388,6 +389,7 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
     const uint32_t mask_bits = steps_mask ? ((uint32_t)kCkFrames - 1u) & ~3u : (P_static - 1u) & ~3u;
     uint32_t thr = thr_real;                // 0 for one frame after a band step: that frame must come through the rare block
     asm("" : "+s"(thr));                    // (opaque: one s_cmp + s_cbranch per frame instead of a boolean expression)
+    uint32_t quarter = 15u;                 // what that frame has to mask: bit g for cells 4g .. 4g+3; set by the step
     // halos of frame 0: lane 63's cells 13..15 of the initial state
     float h1 = wave_ror1(KA_P(P, 15)), h2 = wave_ror1(KA_P(P, 14)), h3 = wave_ror1(KA_P(P, 13));
     for (uint32_t t0 = 0; t0 < T; t0 += U) {
@@ -468,12 +470,28 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
                 if (__builtin_expect(rem >= thr, 0)) {
                     asm volatile("" ::: "memory");  // a real branch: the common frame pays an add, a compare and a jump
                     thr = thr_real;
-                    if (dd != D - 1 || (~tb & mask_bits) != 0) {
-                        mask_scores<15>(P, mk, NINF);
-                        h1 = wave_ror1(KA_P(P, 15));
-                        h2 = wave_ror1(KA_P(P, 14));
-                        h3 = wave_ror1(KA_P(P, 13));
-                    }
+                    // A frame that is here only as the first of a new band (not to step it again) owes ONE kill: the
+                    // position that has just left on the lo side, which this frame has computed once more from live
+                    // cells and the next frame would read.  Where lo went one further that is cell lo_old & 15 of its
+                    // lane, and masking the quarter of the cells it lies in is enough (`quarter`, set by the step):
+                    //   * cells below lo_old were -inf before and have read nothing but each other;
+                    //   * cells at or above hi hold leaked scores as they do between any two masks.  Nothing reads them
+                    //     before they enter the band, and the mask in front of the next step - or the periodic one -
+                    //     clears them first.  How far a leak climbs in the meantime is bounded by the frames between
+                    //     those full masks alone: steps_mask counts the frames from one step's mask to the next
+                    //     step's, this one is not in its sum, and without steps_mask the periodic pass runs as before.
+                    // A frame in front of a step masks all four quarters; one bit test and jump per quarter, inside
+                    // mask_quarter's statement.  The halos are cells 13..15 and only the last quarter changes them, but they
+                    // are taken again on every visit: a second place that defines them under a condition costs copies.
+                    uint32_t sel = rem >= thr_real ? 15u : quarter;
+                    if (dd == D - 1 && (~tb & mask_bits) == 0) sel = 0;   // the static pass has just masked this frame
+                    mask_quarter<3>(P, mk, NINF, sel);
+                    mask_quarter<2>(P, mk, NINF, sel);
+                    mask_quarter<1>(P, mk, NINF, sel);
+                    mask_quarter<0>(P, mk, NINF, sel);
+                    h1 = wave_ror1(KA_P(P, 15));
+                    h2 = wave_ror1(KA_P(P, 14));
+                    h3 = wave_ror1(KA_P(P, 13));
                     if (rem >= thr_real) {
                         q += dq;
                         if (rem >= T) { rem -= T; ++q; }
@@ -521,16 +539,28 @@ __device__ __forceinline__ void forward_ck_body(const Lattice &d, int32_t *meta,
                                     for (int i = 0; i < 8; ++i) vz[i] = la[i] == 0 ? NINF : __builtin_inff();
                                 }
                             }
-                            if (nlo != lo || nhi != hi) {
-                                if (nhi - hi <= 1u && nlo - lo <= 1u) {
-                                    if (nhi != hi) band_toggle(mk, hi);
-                                    if (nlo != lo) band_toggle(mk, lo);
-                                } else {
+                            // (hi is a function of lo: while lo stays - clamped at 0 - the band stays, nothing leaves it and
+                            //  frame t+1 owes no mask)
+                            if (nlo != lo) {
+                                // one position left, lo itself: frame t+1 has to mask the quarter of its lane's cells that
+                                // holds it; more than one: all four.  (Worked out in front of the mask update and pinned there.)
+                                quarter = nlo - lo == 1u ? 1u << ((lo >> 2) & 3u) : 15u;
+                                asm volatile("" : "+s"(quarter));
+                                const uint32_t hi = (L - lo < B) ? L : lo + B;   // (the old one, worked out again: not kept across frames)
+                                if (__builtin_expect(nhi - hi > 1u || nlo - lo > 1u, 0)) {
+                                    // A band that moved further is built anew - in a triangle IN FRONT of the toggles, with two
+                                    // toggles of its own that the ones below take back.  As the other arm of an if / else the
+                                    // rebuild, which needs every scalar register there is, made the toggles' arm - the common
+                                    // one - spill and reload all sixteen masks to meet it at the merge (16 v_writelane, 16
+                                    // v_readlane, 16 s_mov_b64 per step); like this the kernel has no scalar spill at all.
                                     band_rebuild(mk, nlo, nhi);
+                                    if (nhi != hi) band_toggle(mk, hi);
+                                    band_toggle(mk, lo);
                                 }
+                                if (nhi != hi) band_toggle(mk, hi);
+                                band_toggle(mk, lo);
                                 lo = nlo;
-                                hi = nhi;
-                                thr = 0;   // frame t+1 is the first of a new band: it must be masked
+                                thr = 0;   // frame t+1 is the first of a new band: it must come through here
                             }
                         }
                     }
